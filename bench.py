@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Train-step benchmark of the DualQ-SELD-TCN hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--workload c3|c2|c1|c4|c5] [--mode graph|eager]
+    python bench.py --gpus N --steps K --warmup W [--workload c3|c2|c1|c4|c5] [--mode graph|eager] [--dump-outputs DIR]
 
 One step = zero_grad -> forward -> BCE + 5*MSE -> backward -> (gradient exchange) -> Adam on one synthetic
 minibatch resident in HBM.  Prints ONE JSON line (rank 0) with the whole-job samples/s, the
@@ -19,6 +19,16 @@ Either launch it under `python -m torch.distributed.run --nproc-per-node N ... b
 RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* in the environment), or plainly as `python bench.py --gpus N`: the process
 then is a PARENT that never touches the GPU -- it starts that same torch.distributed.run command as a child on a free
 port of 127.0.0.1, relays rank 0's JSON line and exits with the child's code.
+
+`--dump-outputs DIR`: after the timed region, rank 0 writes what the last timed step handed its caller as float32 .npy
+files (dump_outputs), so that two builds run with the same arguments -- hence the same seeded inputs -- can be compared.
+The run then takes the library's reproducible mode (SELD_DETERMINISTIC=1, `config.deterministic` in the result line):
+the default step folds split reductions with float atomics in whatever order the workgroups finish, and Adam's update
+lr * m / sqrt(v) turns the sign of a near-zero gradient into a whole lr, so two default runs of one build part by more
+than rounding from the first step on (gradients by ~2.5e-4 of their scale, parameters by 2 lr) and further with every
+step (after the ~40 steps of `--steps 20 --warmup 5`: gradients 11 %, BatchNorm statistics 1.3 %).  That mode orders
+every reduction and takes other weight-gradient and statistics kernels for it (hip_ops.deterministic), so the timing
+of a dumping run is the reproducible mode's (c3: 9.48 ms per step against 8.77): take speed from a run without it.
 """
 import argparse
 import importlib
@@ -163,6 +173,32 @@ def cpu_baseline(w, freq=128, seconds_budget=14.0):
                        f"(oracle, torch-CPU fp32, dropout on); `runs` lists every thread setting, `value` is the faster")
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_bytes(model, opt):
+    """Bytes dump_outputs writes: known from the shapes, so every rank can check the limit before the timed region."""
+    n_params = sum(p.numel() for p in opt.params)
+    return 4 * (1 + 2 * n_params + sum(b.numel() for b in model.buffers() if b.is_floating_point()))
+
+
+def dump_outputs(out_dir, loss, model, opt, grad_scale):
+    """What one training step hands its caller: the loss, the parameters Adam just updated, the gradient it applied
+    (the exchanged gradient times `grad_scale`, the 1 / N of the data-parallel mean, as Adam scales it) and the BatchNorm
+    running statistics the forward pass updated.  Each is flattened in model.parameters() / model.buffers() order (not
+    FlatAdam's storage order, which depends on the data-parallel bucketing) and written as DIR/<name>.npy in float32."""
+    import numpy as np
+    arrays = {
+        "loss": loss.detach().reshape(1),
+        "params": torch.cat([p.detach().reshape(-1) for p in opt.params]),
+        "grads": torch.cat([p.grad.detach().reshape(-1) for p in opt.params]) * grad_scale,
+        "bn_running_stats": torch.cat([b.detach().reshape(-1) for b in model.buffers() if b.is_floating_point()]),
+    }
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a.float().cpu().numpy())
+
+
 def launch_ranks(argv, n):
     """`python bench.py --gpus N` without a torch.distributed environment: start the N ranks as children of THIS process
     (which has not touched the GPU and never will: no exec, no HIP call), relay rank 0's JSON line, return the exit code."""
@@ -207,7 +243,15 @@ def main():
     ap.add_argument("--roofline-steps", type=int, default=5, help="instrumented eager steps after the timed region")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-kernel-timer", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's loss, updated parameters, gradient and BatchNorm statistics to "
+                         "DIR/*.npy (float32); the run takes the reproducible mode (SELD_DETERMINISTIC=1)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs:
+        # before the library reads its switches (first use), and inherited by the ranks `launch_ranks` starts
+        os.environ["SELD_DETERMINISTIC"] = "1"
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         if os.environ.get("SELD_BENCH_CHILD"):
@@ -238,6 +282,8 @@ def main():
     DP.broadcast_parameters(opt.flat_param)
     sync = DP.BucketedGradSync(opt, model)
     x, target = T.synthetic_batch(batch, w["input_channels"], args.freq, 512, 42, 1234 + rank, dev)
+    if args.dump_outputs and dump_bytes(model, opt) > DUMP_LIMIT_BYTES:       # on every rank: none is left in a collective
+        raise SystemExit(f"bench.py: --dump-outputs would write {dump_bytes(model, opt)} bytes, more than {DUMP_LIMIT_BYTES}")
 
     def eager_step():
         return DP.dp_train_step(model, opt, sync, x, target, 42, T.seld_loss_fn)
@@ -332,6 +378,8 @@ def main():
         elapsed = float(t.item())
     final_loss = float(loss.item())
     per_step = [marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps)]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, loss, model, opt, sync.average_scale())    # before the roofline pass's eager steps move the weights on
 
     # ---- roofline pass: the same step, eager, only the dominant kernel and the first-layer DualQ-Conv bracketed
     summ = {}

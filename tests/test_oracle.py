@@ -173,15 +173,34 @@ def test_stft_matches_reference(golden):
     assert np.abs(c[:nb] - g["magphase_128"][:nb]).max() < 1e-12
 
 
+def _reference_with_this_hosts_roots(ref, x, arg, root):
+    """The reference's output for `x` had its torch.sqrt call returned this host's roots instead of those of the host
+    that wrote the fixtures (norm_roots.npz).  torch's CPU sqrt is MKL VML, whose code path -- and so the last bit of a
+    float32 root -- follows the CPU.  A root only reaches the q channels (q / sqrt(|q|^2), train.py:257-275): pin that
+    `arg` is the |q|^2 formed here and that the fixture's q channels are exactly q / `root`, then divide by this host's."""
+    t = torch.tensor(x)
+    q = [t[:, i:i + 1] for i in range(4)]
+    den0 = q[0] ** 2 + q[1] ** 2 + q[2] ** 2 + q[3] ** 2
+    assert np.array_equal(den0.numpy(), arg)
+    assert np.array_equal((t[:, :4] / torch.from_numpy(root)).float().numpy(), ref[:, :4])
+    out = ref.copy()
+    out[:, :4] = (t[:, :4] / torch.sqrt(den0)).float().numpy()
+    return out
+
+
 def test_dataset_normalisation_matches_reference(golden):
     """norm.npz = the arrays the reference's train.main hands to its TensorDatasets (make_golden.gen_norm);
-    the oracle restatement must reproduce them bit for bit (same torch / numpy primitives, same dtype)."""
+    the oracle restatement must reproduce them bit for bit (same torch / numpy primitives, same dtype), with this
+    host's square roots where the reference took one."""
     from tests.golden.cases import NORM_CASES, norm_input
-    g = golden("norm")
+    g, roots = golden("norm"), golden("norm_roots")
     for name, shape, dtype, mode, n_mics, domain, phase in NORM_CASES:
         for k in range(3):
-            got = O.normalize_dataset(norm_input(shape, dtype, k), mode, n_mics, domain, phase)
+            x = norm_input(shape, dtype, k)
+            got = O.normalize_dataset(x, mode, n_mics, domain, phase)
             ref = g[f"{name}.{k}"]
+            if f"{name}.{k}.root" in roots:
+                ref = _reference_with_this_hosts_roots(ref, x, roots[f"{name}.{k}.arg"], roots[f"{name}.{k}.root"])
             assert got.dtype == np.float32 and got.shape == ref.shape
             assert np.array_equal(got, ref), (name, k, np.abs(got - ref).max())
     with pytest.raises(ValueError):
