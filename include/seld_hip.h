@@ -149,6 +149,33 @@ int seld_hc_conv_pair_bwd_weight_acc(const seld_conv_desc* d, const float* x, co
 int seld_hc_conv_kernel_label(const seld_conv_desc* d, int32_t which, char* buf, int32_t buflen);
 
 /* ------------------------------------------------------------------------------------------
+ * Hypercomplex TRANSPOSED convolution.  Replaces quaternion_transpose_conv (quaternion_ops.py:149-171) and the real
+ * F.conv_transpose1d/2d:  y = conv_transpose(x, M, bias, stride, pad, out_pad, dil), M (Cin, Cout, kh, kw) the Hamilton
+ * block matrix of the component tensors (Cin/A, Cout/A, kh, kw), as for the forward convolution.  algebra 1 or 4.
+ * `d` keeps its layout with TRANSPOSED meaning: Cin / in[] are the transposed convolution's input channels / extent,
+ * Cout its output channels.  Output extent per axis: (in - 1)*stride - 2*pad + dil*(k - 1) + out_pad + 1, with
+ * out_pad < stride or out_pad < dil (PyTorch's rule).  groups != 1: SELD_EUNSUPPORTED.
+ *   seld_hc_conv_transpose_out_shape        the output extent (H, W)
+ *   seld_hc_conv_transpose_fwd              y = ... + bias (nullable).  Stride-phase kernel (csrc/hc_conv_transpose.hip):
+ *                                           no float atomics, run-to-run bit-identical
+ *   seld_hc_conv_transpose_bwd_data         dx = conv(dy, M) with the same stride / pad / dil (the forward convolution)
+ *   seld_hc_conv_transpose_bwd_weight_acc   dw[c] += weight gradient, dbias += sum of dy (nullable).  Under
+ *                                           SELD_DETERMINISTIC the reproducible path of seld_hc_conv_bwd_weight_det, with a
+ *                                           workspace of seld_hc_conv_transpose_bwd_weight_workspace bytes (0 otherwise)
+ *   seld_hc_conv_transpose_kernel_label     kernel symbol of a call; which: 0 forward, 1 input gradient, 2 weight gradient */
+int seld_hc_conv_transpose_out_shape(const seld_conv_desc* d, const int32_t out_pad[2], int32_t out[2]);
+int seld_hc_conv_transpose_fwd(const seld_conv_desc* d, const int32_t out_pad[2], const float* x, const float* const w[8],
+                               const float* bias, float* y, void* stream);
+int seld_hc_conv_transpose_bwd_data(const seld_conv_desc* d, const int32_t out_pad[2], const float* dy,
+                                    const float* const w[8], float* dx, void* stream);
+size_t seld_hc_conv_transpose_bwd_weight_workspace(const seld_conv_desc* d, const int32_t out_pad[2]);
+int seld_hc_conv_transpose_bwd_weight_acc(const seld_conv_desc* d, const int32_t out_pad[2], const float* x,
+                                          const float* dy, float* const dw[8], float* dbias, void* workspace,
+                                          size_t workspace_bytes, void* stream);
+int seld_hc_conv_transpose_kernel_label(const seld_conv_desc* d, const int32_t out_pad[2], int32_t which, char* buf,
+                                        int32_t buflen);
+
+/* ------------------------------------------------------------------------------------------
  * Hypercomplex / real linear  y[rows, out] = x[rows, in] @ M + b.
  *   SELD_LIN_REAL   : torch.nn.Linear, weight (out, in)                 (model.py:23,439,454,458)
  *   SELD_LIN_QUAT   : quaternion_linear, weights (in/4, out/4)          (quaternion_ops.py:299-327)

@@ -49,6 +49,7 @@ def lib():
         _lib.seld_build_arch.restype = ctypes.c_char_p
         _lib.seld_hc_conv_bwd_weight_workspace.restype = ctypes.c_size_t
         _lib.seld_hcq_wgrad_group_workspace.restype = ctypes.c_size_t
+        _lib.seld_hc_conv_transpose_bwd_weight_workspace.restype = ctypes.c_size_t
     return _lib
 
 

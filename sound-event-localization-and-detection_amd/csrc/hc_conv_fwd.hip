@@ -672,6 +672,23 @@ extern "C" int seld_hc_conv_bwd_data_wt(const seld_conv_desc* d, const float* dy
 }
 
 namespace seld {
+// Forward convolution evaluated on the output extent o (at most the natural one): the transposed convolution's input
+// gradient (hc_conv_transpose.hip), where output_padding >= stride leaves the natural extent larger than the input.
+int hc_conv_fwd_out(const seld_conv_desc* d, const int o[2], const float* x, const float* const w[8], float* y,
+                    hipStream_t st) {
+    int rc = hc_validate(d);
+    if (rc) return rc;
+    int nat[2];
+    hc_out_shape(d, nat);
+    if (o[0] <= 0 || o[1] <= 0 || o[0] > nat[0] || o[1] > nat[1] || !x || !w || !y) return SELD_EINVAL;
+    if (o[0] == nat[0] && o[1] == nat[1]) return seld_hc_conv_fwd_ex(d, x, w, nullptr, y, SELD_EPI_NONE, nullptr, nullptr, st);
+    ConvP p{};
+    fill_fwd(p, d, w, o);
+    p.epilogue = SELD_EPI_NONE;
+    p.src = x; p.bias = nullptr; p.dst = y;
+    return run_conv<MODE_FWD>(p, st);
+}
+
 int hc_wgrad_label(const seld_conv_desc* d, char* buf, int buflen);
 int hc_wgrad_pair_ok(const seld_conv_desc* d);
 }

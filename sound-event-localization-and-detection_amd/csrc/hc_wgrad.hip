@@ -514,13 +514,19 @@ static void launch_wgrad(const WgradP& p, hipStream_t st) {
 #undef SELD_WG
 }
 
-// One weight gradient, or (dy2 != nullptr) the two of a pair that shares x and the geometry.
+// One weight gradient, or (dy2 != nullptr) the two of a pair that shares x and the geometry.  o_over: reduce over the
+// first o_over[0] x o_over[1] output positions only (dy has that extent; the transposed convolution's weight gradient).
 static int wgrad_run2(const seld_conv_desc* d, const float* x, const float* dy, float* const dw[8], float* dbias,
-                      const float* dy2, float* const dw2[8], float* dbias2, int accumulate, hipStream_t st) {
+                      const float* dy2, float* const dw2[8], float* dbias2, int accumulate, hipStream_t st,
+                      const int* o_over = nullptr) {
     int rc = hc_validate(d);
     if (rc) return rc;
     int o[2];
     hc_out_shape(d, o);
+    if (o_over) {
+        if (o_over[0] > o[0] || o_over[1] > o[1]) return SELD_EINVAL;
+        o[0] = o_over[0]; o[1] = o_over[1];
+    }
     if (o[0] <= 0 || o[1] <= 0 || !x || !dy || !dw) return SELD_EINVAL;
     if (dy2 && !dw2) return SELD_EINVAL;
     WgradP p{};
@@ -718,18 +724,25 @@ extern "C" size_t seld_hc_conv_bwd_weight_det_workspace(const seld_conv_desc* d)
     if (hc_validate(d) != SELD_OK) return 0;
     return (size_t)d->Cout * d->Cin * d->k[0] * d->k[1] * sizeof(float);
 }
+static int wgrad_det(const seld_conv_desc* d, const float* x, const float* dy, float* const dw[8], float* dbias,
+                     void* workspace, size_t workspace_bytes, hipStream_t st, const int* o_over);
+
 extern "C" int seld_hc_conv_bwd_weight_det(const seld_conv_desc* d, const float* x, const float* dy, float* const dw[8],
                                            float* dbias, void* workspace, size_t workspace_bytes, void* stream) {
+    return wgrad_det(d, x, dy, dw, dbias, workspace, workspace_bytes, (hipStream_t)stream, nullptr);
+}
+
+static int wgrad_det(const seld_conv_desc* d, const float* x, const float* dy, float* const dw[8], float* dbias,
+                     void* workspace, size_t workspace_bytes, hipStream_t st, const int* o_over) {
     int rc = hc_validate(d);
     if (rc) return rc;
     if (!x || !dy || !dw || !workspace) return SELD_EINVAL;
     if (workspace_bytes < seld_hc_conv_bwd_weight_det_workspace(d)) return SELD_EWORKSPACE;
     if (!env().deterministic) return SELD_EUNSUPPORTED;           // the single-range launch plan is tied to the switch
-    hipStream_t st = (hipStream_t)stream;
     seld_conv_desc real = *d;
     real.algebra = 1;
     float* full[8] = {(float*)workspace, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    rc = wgrad_run(&real, x, dy, full, nullptr, 0, st);           // zero-fills `full`, then one contribution per element
+    rc = wgrad_run2(&real, x, dy, full, nullptr, nullptr, nullptr, nullptr, 0, st, o_over);           // zero-fills `full`, then one contribution per element
     if (rc) return rc;
     DetFoldP f{};
     f.full = (const float*)workspace; f.A = d->algebra; f.OA = d->Cout / d->algebra; f.IA = d->Cin / d->algebra;
@@ -745,6 +758,7 @@ extern "C" int seld_hc_conv_bwd_weight_det(const seld_conv_desc* d, const float*
     if (dbias) {
         int o[2];
         hc_out_shape(d, o);
+        if (o_over) { o[0] = o_over[0]; o[1] = o_over[1]; }
         hipLaunchKernelGGL(channel_sum_kernel, dim3(d->Cout), dim3(256), 0, st, dy, d->N, d->Cout, o[0] * o[1], dbias);
         rc = check_launch();
     }
@@ -756,3 +770,14 @@ extern "C" int seld_hc_conv_bwd_weight_acc(const seld_conv_desc* d, const float*
                                            float* const dw[8], float* dbias, void* stream) {
     return wgrad_run(d, x, dy, dw, dbias, 1, (hipStream_t)stream);
 }
+
+namespace seld {
+// dw[c] += weight gradient reduced over the output extent o (at most the natural one; dy has that extent): the transposed
+// convolution's weight gradient (hc_conv_transpose.hip).  SELD_DETERMINISTIC: the reproducible path above, workspace of
+// seld_hc_conv_bwd_weight_det_workspace(d) bytes.
+int hc_wgrad_out(const seld_conv_desc* d, const int o[2], const float* x, const float* dy, float* const dw[8],
+                 void* det_ws, size_t det_bytes, hipStream_t st) {
+    if (env().deterministic) return wgrad_det(d, x, dy, dw, nullptr, det_ws, det_bytes, st, o);
+    return wgrad_run2(d, x, dy, dw, nullptr, nullptr, nullptr, nullptr, 1, st, o);
+}
+}  // namespace seld

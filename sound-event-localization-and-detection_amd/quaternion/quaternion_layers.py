@@ -66,8 +66,8 @@ class QuaternionConv(_QuaternionConvBase):
 
 
 class QuaternionTransposeConv(_QuaternionConvBase):
-    """API surface only (quaternion_layers.py:19-98): parameters and state dict are provided, the SELD
-    models never call it and there is no HIP kernel for it."""
+    """Quaternion transposed convolution (quaternion_layers.py:19-98), weights (in/4, out/4, *k); forward on the
+    stride-phase kernel (csrc/hc_conv_transpose.hip).  rotation=True has no HIP kernel."""
     _transposed = True
 
     def __init__(self, in_channels, out_channels, kernel_size, stride, dilatation=1, padding=0, output_padding=0,
@@ -78,7 +78,11 @@ class QuaternionTransposeConv(_QuaternionConvBase):
                          init_criterion, weight_init, seed, operation, rotation, quaternion_format)
 
     def forward(self, input):
-        return _ops.quaternion_transpose_conv(input)
+        if self.rotation:
+            return _ops.quaternion_transpose_conv_rotation(input)
+        return _ops.quaternion_transpose_conv(input, self.r_weight, self.i_weight, self.j_weight, self.k_weight, self.bias,
+                                              self.stride, self.padding, self.output_padding, self.groups,
+                                              self.dilatation)
 
 
 class _QuaternionLinearBase(Module):

@@ -62,6 +62,14 @@ def quaternion_conv(input, r_weight, i_weight, j_weight, k_weight, bias, stride,
     return H.hyper_conv(input, (r_weight, i_weight, j_weight, k_weight), bias, stride, padding, dilatation)
 
 
+def quaternion_transpose_conv(input, r_weight, i_weight, j_weight, k_weight, bias, stride, padding, output_padding,
+                              groups, dilatation):
+    """y = conv_transpose(x, W_hamilton, bias) on the stride-phase kernel (replaces quaternion_ops.py:149-171)."""
+    _conv_guard(input, groups)
+    return H.hyper_conv_transpose(input, (r_weight, i_weight, j_weight, k_weight), bias, stride, padding, output_padding,
+                                  dilatation)
+
+
 def quaternion_linear(input, r_weight, i_weight, j_weight, k_weight, bias=None):
     """y = x @ W_hamilton + b (replaces quaternion_ops.py:299-327); any leading dims."""
     return H.hyper_linear(input, (r_weight, i_weight, j_weight, k_weight), bias, L.SELD_LIN_QUAT)
@@ -84,7 +92,6 @@ def _no_kernel(name):
     return fn
 
 
-quaternion_transpose_conv = _no_kernel("quaternion_transpose_conv")
 quaternion_conv_rotation = _no_kernel("quaternion_conv_rotation")
 quaternion_transpose_conv_rotation = _no_kernel("quaternion_transpose_conv_rotation")
 quaternion_linear_rotation = _no_kernel("quaternion_linear_rotation")
