@@ -176,6 +176,27 @@ int seld_hc_conv_transpose_kernel_label(const seld_conv_desc* d, const int32_t o
                                         int32_t buflen);
 
 /* ------------------------------------------------------------------------------------------
+ * Quaternion ROTATION weight: quaternion_conv_rotation / quaternion_transpose_conv_rotation / quaternion_linear_rotation
+ * (quaternion_ops.py:174-388) build one real weight K from the component tensors (A, B, *taps) element by element and run
+ * one real convolution / transposed convolution / matmul with it (the algebra-1 entry points above and below).
+ * Per element, with u = (r, i, j, k), n = |u|, f = 2n:  E = I + f*Q(u),  Q the 3x3 rotation quadratic of
+ * csrc/quat_rotation.hip;  K[m*A + a][c*B + b][t] = E[m][c](a, b, t), K (3A, 3B, *taps).  qformat (quaternion_format):
+ * K (4A, 4B, *taps), block row 0 and block column 0 zero, E at block (m+1, c+1).
+ *   layout SELD_ROT_LAYOUT_CONV    K as above (F.convNd / F.conv_transposeNd weight)
+ *   layout SELD_ROT_LAYOUT_LINEAR  K^T, (MB*B, MB*A) with MB = 3 or 4, taps == 1 (the SELD_LIN_REAL weight)
+ *   seld_quat_rotation_form        writes all of K, zero blocks included
+ *   seld_quat_rotation_form_bwd    dw[c] (+)= dL/du_c from dK (accumulate 0: store, 1: add); no atomics, run-to-run
+ *                                  bit-identical.  n = 0 gives inf / NaN, as the reference's autograd.
+ * SELD_EINVAL: bad layout / sizes (A, B, taps >= 1), taps != 1 with the linear layout, NULL pointers. */
+#define SELD_ROT_LAYOUT_CONV    0
+#define SELD_ROT_LAYOUT_LINEAR  1
+int seld_quat_rotation_form(int32_t layout, int32_t qformat, int32_t A, int32_t B, int32_t taps,
+                            const float* const w[4], float* K, void* stream);
+int seld_quat_rotation_form_bwd(int32_t layout, int32_t qformat, int32_t A, int32_t B, int32_t taps,
+                                const float* const w[4], const float* dK, float* const dw[4], int32_t accumulate,
+                                void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Hypercomplex / real linear  y[rows, out] = x[rows, in] @ M + b.
  *   SELD_LIN_REAL   : torch.nn.Linear, weight (out, in)                 (model.py:23,439,454,458)
  *   SELD_LIN_QUAT   : quaternion_linear, weights (in/4, out/4)          (quaternion_ops.py:299-327)

@@ -799,6 +799,123 @@ def hyper_conv_transpose(x, ws, bias, stride, padding, output_padding, dilation)
     return ConvTransposeFn.apply(x, bias, stride, padding, output_padding, dilation, *ws)
 
 
+# ---- quaternion rotation weight (csrc/quat_rotation.hip) -----------------------------------------------------------------
+# quaternion_{conv,transpose_conv,linear}_rotation (quaternion_ops.py:174-388) build ONE real weight K from the four
+# component tensors and run one real op with it: here K comes from seld_quat_rotation_form and the op is the algebra-1
+# convolution / transposed convolution / SELD_LIN_REAL linear above, with their own backward, deterministic mode and
+# capture.  RotationWeightFn folds dK back onto the components.
+def _rot_dims(ws, layout):
+    """(A, B, taps, shape) of the component tensors (A, B, *taps); 2-D for the linear layout."""
+    if len(ws) != 4 or any(w is None for w in ws):
+        raise L.SeldHipError("rotation: needs the four component tensors r, i, j, k")
+    shape = tuple(ws[0].shape)
+    if any(tuple(w.shape) != shape for w in ws):
+        raise L.SeldHipError(f"rotation: component shapes differ: {[tuple(w.shape) for w in ws]}")
+    if len(shape) < 2 or (layout == L.SELD_ROT_LAYOUT_LINEAR and len(shape) != 2):
+        raise L.SeldHipError(f"rotation: bad component shape {shape}")
+    taps = 1
+    for s in shape[2:]:
+        taps *= int(s)
+    return int(shape[0]), int(shape[1]), taps, shape
+
+
+def rotation_weight_shape(layout, qformat, w_shape):
+    """K (MB*A, MB*B, *taps) for SELD_ROT_LAYOUT_CONV, K^T (MB*B, MB*A) for SELD_ROT_LAYOUT_LINEAR; MB = 4 with
+    quaternion_format, else 3."""
+    m = 4 if qformat else 3
+    if layout == L.SELD_ROT_LAYOUT_CONV:
+        return (m * w_shape[0], m * w_shape[1]) + tuple(w_shape[2:])
+    return (m * w_shape[1], m * w_shape[0])
+
+
+def rotation_form(layout, qformat, ws):
+    A, B, taps, shape = _rot_dims(ws, layout)
+    ws = [_req(w, "w") for w in ws]
+    K = torch.empty(rotation_weight_shape(layout, qformat, shape), device=ws[0].device, dtype=torch.float32)
+    L.check(L.lib().seld_quat_rotation_form(layout, int(bool(qformat)), A, B, taps, L.ptr_array8(ws), L.ptr(K),
+                                            L.current_stream()), "seld_quat_rotation_form")
+    return K
+
+
+def rotation_form_bwd(layout, qformat, ws, dK, dws, accumulate):
+    """dws[c] = (accumulate: +=) dL/dw_c from dK."""
+    A, B, taps, _ = _rot_dims(ws, layout)
+    ws = [_req(w, "w") for w in ws]
+    dK = _req(dK, "dK")
+    L.check(L.lib().seld_quat_rotation_form_bwd(layout, int(bool(qformat)), A, B, taps, L.ptr_array8(ws), L.ptr(dK),
+                                                L.ptr_array8(dws), int(bool(accumulate)), L.current_stream()),
+            "seld_quat_rotation_form_bwd")
+
+
+class RotationWeightFn(torch.autograd.Function):
+    """K = rotation weight of (r, i, j, k).  Backward: one kernel, each element's four gradients from its own entries of
+    dK (no atomics), straight into the optimiser's gradient slots when it owns all four (_claim_grad_slots), else into
+    fresh tensors for autograd."""
+
+    @staticmethod
+    def forward(ctx, layout, qformat, *ws):
+        wc = [_req(w, "w") for w in ws]
+        ctx.layout, ctx.qformat, ctx.params = layout, qformat, ws
+        ctx.save_for_backward(*wc)
+        return rotation_form(layout, qformat, wc)
+
+    @staticmethod
+    def backward(ctx, dK):
+        ws = ctx.saved_tensors
+        need = ctx.needs_input_grad[2:]
+        params = ctx.params
+        if all(need) and all(p.is_contiguous() for p in params):
+            slot, clean = _claim_grad_slots(params, adjacent=False)
+            if slot is not None and all(p.grad.is_contiguous() for p in params):
+                rotation_form_bwd(ctx.layout, ctx.qformat, ws, dK, [p.grad for p in params], accumulate=not clean)
+                return (None, None) + (None,) * len(ws)
+        dws = [torch.empty_like(w) for w in ws]
+        rotation_form_bwd(ctx.layout, ctx.qformat, ws, dK, dws, accumulate=False)
+        return (None, None) + tuple(g if n else None for g, n in zip(dws, need))
+
+
+def _rot_check(what, channels, want_channels, bias, out_channels, m):
+    if channels != want_channels:
+        raise L.SeldHipError(f"{what}: the input has {channels} channels, the rotation weight takes {want_channels} "
+                             f"({m} x the component tensors' {want_channels // m}; quaternion_format gives 4, else 3)")
+    if bias is not None and (bias.dim() != 1 or bias.numel() != out_channels):
+        raise L.SeldHipError(f"{what}: bias of shape {tuple(bias.shape)}, the op has {out_channels} output channels "
+                             f"(the reference's F.conv / addmm call needs as many)")
+
+
+def hyper_conv_rotation(x, ws, bias, stride, padding, dilation, qformat):
+    """quaternion_conv_rotation: F.convNd(x, K, bias), K (MB*O, MB*I, *k) the rotation weight of (O, I, *k) components."""
+    A, B, _, shape = _rot_dims(ws, L.SELD_ROT_LAYOUT_CONV)
+    m = 4 if qformat else 3
+    if len(shape) != x.dim():
+        raise L.SeldHipError(f"quaternion_conv_rotation: {x.dim()}-D input, {len(shape)}-D component weights")
+    _rot_check("quaternion_conv_rotation", int(x.shape[1]), m * B, bias, m * A, m)
+    K = RotationWeightFn.apply(L.SELD_ROT_LAYOUT_CONV, bool(qformat), *ws)
+    return hyper_conv(x, (K,), bias, stride, padding, dilation)
+
+
+def hyper_conv_transpose_rotation(x, ws, bias, stride, padding, output_padding, dilation, qformat):
+    """quaternion_transpose_conv_rotation: F.conv_transposeNd(x, K, bias), K (MB*Iin, MB*Oout, *k) the rotation weight of
+    (Iin, Oout, *k) components."""
+    A, B, _, shape = _rot_dims(ws, L.SELD_ROT_LAYOUT_CONV)
+    m = 4 if qformat else 3
+    if len(shape) != x.dim():
+        raise L.SeldHipError(f"quaternion_transpose_conv_rotation: {x.dim()}-D input, {len(shape)}-D component weights")
+    _rot_check("quaternion_transpose_conv_rotation", int(x.shape[1]), m * A, bias, m * B, m)
+    K = RotationWeightFn.apply(L.SELD_ROT_LAYOUT_CONV, bool(qformat), *ws)
+    return hyper_conv_transpose(x, (K,), bias, stride, padding, output_padding, dilation)
+
+
+def hyper_linear_rotation(x, ws, bias, qformat):
+    """quaternion_linear_rotation: x @ K + bias, K (MB*I, MB*O) the rotation weight of (I, O) components; the real linear
+    kernel takes K^T, which the form kernel writes directly."""
+    A, B, _, _ = _rot_dims(ws, L.SELD_ROT_LAYOUT_LINEAR)
+    m = 4 if qformat else 3
+    _rot_check("quaternion_linear_rotation", int(x.shape[-1]) if x.dim() else 0, m * A, bias, m * B, m)
+    W = RotationWeightFn.apply(L.SELD_ROT_LAYOUT_LINEAR, bool(qformat), *ws)
+    return hyper_linear(x, (W,), bias, L.SELD_LIN_REAL)
+
+
 # ======================================================================================
 # 8-multiplication Hamilton product kernels (csrc/hcq_conv.hip)
 # ======================================================================================

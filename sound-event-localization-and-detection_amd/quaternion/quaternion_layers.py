@@ -60,14 +60,17 @@ class QuaternionConv(_QuaternionConvBase):
 
     def forward(self, input):
         if self.rotation:
-            return _ops.quaternion_conv_rotation(input)
+            return _ops.quaternion_conv_rotation(input, self.r_weight, self.i_weight, self.j_weight, self.k_weight,
+                                                 self.bias, self.stride, self.padding, self.groups, self.dilatation,
+                                                 self.quaternion_format)
         return _ops.quaternion_conv(input, self.r_weight, self.i_weight, self.j_weight, self.k_weight, self.bias,
                                     self.stride, self.padding, self.groups, self.dilatation)
 
 
 class QuaternionTransposeConv(_QuaternionConvBase):
     """Quaternion transposed convolution (quaternion_layers.py:19-98), weights (in/4, out/4, *k); forward on the
-    stride-phase kernel (csrc/hc_conv_transpose.hip).  rotation=True has no HIP kernel."""
+    stride-phase kernel (csrc/hc_conv_transpose.hip).  rotation=True: the rotation weight (csrc/quat_rotation.hip) on
+    the same kernel at algebra 1."""
     _transposed = True
 
     def __init__(self, in_channels, out_channels, kernel_size, stride, dilatation=1, padding=0, output_padding=0,
@@ -79,7 +82,10 @@ class QuaternionTransposeConv(_QuaternionConvBase):
 
     def forward(self, input):
         if self.rotation:
-            return _ops.quaternion_transpose_conv_rotation(input)
+            return _ops.quaternion_transpose_conv_rotation(input, self.r_weight, self.i_weight, self.j_weight,
+                                                           self.k_weight, self.bias, self.stride, self.padding,
+                                                           self.output_padding, self.groups, self.dilatation,
+                                                           self.quaternion_format)
         return _ops.quaternion_transpose_conv(input, self.r_weight, self.i_weight, self.j_weight, self.k_weight, self.bias,
                                               self.stride, self.padding, self.output_padding, self.groups,
                                               self.dilatation)
@@ -142,5 +148,6 @@ class QuaternionLinearAutograd(_QuaternionLinearBase):
 
     def forward(self, input):
         if self.rotation:
-            return _ops.quaternion_linear_rotation(input)
+            return _ops.quaternion_linear_rotation(input, self.r_weight, self.i_weight, self.j_weight, self.k_weight,
+                                                   self.bias, self.quaternion_format)
         return _ops.quaternion_linear(input, self.r_weight, self.i_weight, self.j_weight, self.k_weight, self.bias)

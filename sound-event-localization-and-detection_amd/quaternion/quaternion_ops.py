@@ -2,7 +2,8 @@
 quaternion/quaternion_ops.py, computed by the gfx950 kernels (include/seld_hip.h).
 
 The Hamilton block matrix (quaternion_ops.py:131-135 / :310-314) is never assembled; the kernels
-read the four component tensors directly.  Weight initialisers are host-side numpy and reproduce
+read the four component tensors directly.  The rotation ops build their real weight on the device, as
+the reference does on the host, and run the real kernels with it.  Weight initialisers are host-side numpy and reproduce
 the reference's random-number draws call for call so that equal seeds give equal weights.
 """
 import numpy as np
@@ -85,16 +86,40 @@ class QuaternionLinearFunction:
         return quaternion_linear(input, r_weight, i_weight, j_weight, k_weight, bias)
 
 
-def _no_kernel(name):
-    def fn(*a, **k):
-        raise L.SeldHipError(f"{name}: not on the DualQ-SELD-TCN hot path, no HIP kernel in this build")
-    fn.__name__ = name
-    return fn
+def _rotation_guard(name, input, weights):
+    if not input.is_cuda:
+        raise L.SeldHipError(f"{name}: expected a HIP device tensor (this package has no CPU path)")
+    if any(w is None for w in weights):
+        raise L.SeldHipError(f"{name}: needs r_weight, i_weight, j_weight and k_weight")
 
 
-quaternion_conv_rotation = _no_kernel("quaternion_conv_rotation")
-quaternion_transpose_conv_rotation = _no_kernel("quaternion_transpose_conv_rotation")
-quaternion_linear_rotation = _no_kernel("quaternion_linear_rotation")
+def quaternion_conv_rotation(input, r_weight=None, i_weight=None, j_weight=None, k_weight=None, bias=None, stride=1,
+                             padding=0, groups=1, dilatation=1, quaternion_format=False):
+    """F.convNd(x, K, bias) with K the rotation weight of the components (replaces quaternion_ops.py:174-233): the
+    input has 3*I channels, or 4*I with quaternion_format, and bias, if given, as many elements as the output channels."""
+    _rotation_guard("quaternion_conv_rotation", input, (r_weight, i_weight, j_weight, k_weight))
+    _conv_guard(input, groups)
+    return H.hyper_conv_rotation(input, (r_weight, i_weight, j_weight, k_weight), bias, stride, padding, dilatation,
+                                 quaternion_format)
+
+
+def quaternion_transpose_conv_rotation(input, r_weight=None, i_weight=None, j_weight=None, k_weight=None, bias=None,
+                                       stride=1, padding=0, output_padding=0, groups=1, dilatation=1,
+                                       quaternion_format=False):
+    """F.conv_transposeNd(x, K, bias) with K the rotation weight of the components (replaces quaternion_ops.py:
+    235-296)."""
+    _rotation_guard("quaternion_transpose_conv_rotation", input, (r_weight, i_weight, j_weight, k_weight))
+    _conv_guard(input, groups)
+    return H.hyper_conv_transpose_rotation(input, (r_weight, i_weight, j_weight, k_weight), bias, stride, padding,
+                                           output_padding, dilatation, quaternion_format)
+
+
+def quaternion_linear_rotation(input, r_weight=None, i_weight=None, j_weight=None, k_weight=None, bias=None,
+                               quaternion_format=False):
+    """x @ K + bias with K the rotation weight of the components (replaces quaternion_ops.py:330-388); any leading
+    dims."""
+    _rotation_guard("quaternion_linear_rotation", input, (r_weight, i_weight, j_weight, k_weight))
+    return H.hyper_linear_rotation(input, (r_weight, i_weight, j_weight, k_weight), bias, quaternion_format)
 
 
 # ---- initialisers (host side, numpy float64; quaternion_ops.py:509-645) --------------------
