@@ -176,6 +176,51 @@ int seld_hc_conv_transpose_kernel_label(const seld_conv_desc* d, const int32_t o
                                         int32_t buflen);
 
 /* ------------------------------------------------------------------------------------------
+ * Hypercomplex 3-D convolution and transposed convolution.  Replaces the F.conv3d / F.conv_transpose3d calls of
+ * quaternion_conv / dual_quaternion_conv / quaternion_transpose_conv (quaternion_ops.py:125-171,
+ * dual_quaternion_ops.py:111-153) for 5-D input (N, C, D, H, W).  Component tensors (Cout/A, Cin/A, kd, kh, kw) for the
+ * convolution, (Cin/A, Cout/A, kd, kh, kw) for the transposed one; per-axis arrays are (D, H, W).  The transposed
+ * entry points take `d` with transposed meaning as seld_hc_conv_transpose_* does, algebra 1 or 4, and out_pad[3] under
+ * PyTorch's rule (out_pad < stride or out_pad < dil).  Refused: groups != 1, a stride above 16, and extents whose
+ * images or weights outgrow the kernels' 32-bit offsets (SELD_EUNSUPPORTED); malformed descriptors (SELD_EINVAL).
+ * Nothing is launched or written on refusal.
+ *   *_out_shape               the output extent (D, H, W)
+ *   *_fwd                     y = ... + bias (nullable).  Convolution: implicit-GEMM kernel; transposed: stride-phase
+ *                             kernel (csrc/hc_conv3d.hip)
+ *   *_bwd_data                dx: the other of the two kernels, cut to the input extent
+ *   *_bwd_weight_workspace    bytes of the workspace *_bwd_weight_acc needs (never 0 for a valid descriptor)
+ *   *_bwd_weight_acc          dw[c] += weight gradient, dbias (nullable) += channel sums of dy: per-split partials in
+ *                             the workspace, then one fixed-order fold onto the components
+ *   *_kernel_label            kernel symbol of a call; which: 0 forward, 1 input gradient, 2 weight gradient
+ * No float atomics: every call is run-to-run bit-identical, with or without SELD_DETERMINISTIC. */
+typedef struct seld_conv3d_desc {
+    int32_t algebra, N, Cin, Cout;
+    int32_t in[3], k[3], stride[3], pad[3], dil[3];
+    int32_t groups;
+} seld_conv3d_desc;
+
+int seld_hc_conv3d_out_shape(const seld_conv3d_desc* d, int32_t out[3]);
+int seld_hc_conv3d_fwd(const seld_conv3d_desc* d, const float* x, const float* const w[8], const float* bias, float* y,
+                       void* stream);
+int seld_hc_conv3d_bwd_data(const seld_conv3d_desc* d, const float* dy, const float* const w[8], float* dx, void* stream);
+size_t seld_hc_conv3d_bwd_weight_workspace(const seld_conv3d_desc* d);
+int seld_hc_conv3d_bwd_weight_acc(const seld_conv3d_desc* d, const float* x, const float* dy, float* const dw[8],
+                                  float* dbias, void* workspace, size_t workspace_bytes, void* stream);
+int seld_hc_conv3d_kernel_label(const seld_conv3d_desc* d, int32_t which, char* buf, int32_t buflen);
+
+int seld_hc_conv3d_transpose_out_shape(const seld_conv3d_desc* d, const int32_t out_pad[3], int32_t out[3]);
+int seld_hc_conv3d_transpose_fwd(const seld_conv3d_desc* d, const int32_t out_pad[3], const float* x,
+                                 const float* const w[8], const float* bias, float* y, void* stream);
+int seld_hc_conv3d_transpose_bwd_data(const seld_conv3d_desc* d, const int32_t out_pad[3], const float* dy,
+                                      const float* const w[8], float* dx, void* stream);
+size_t seld_hc_conv3d_transpose_bwd_weight_workspace(const seld_conv3d_desc* d, const int32_t out_pad[3]);
+int seld_hc_conv3d_transpose_bwd_weight_acc(const seld_conv3d_desc* d, const int32_t out_pad[3], const float* x,
+                                            const float* dy, float* const dw[8], float* dbias, void* workspace,
+                                            size_t workspace_bytes, void* stream);
+int seld_hc_conv3d_transpose_kernel_label(const seld_conv3d_desc* d, const int32_t out_pad[3], int32_t which, char* buf,
+                                          int32_t buflen);
+
+/* ------------------------------------------------------------------------------------------
  * Quaternion ROTATION weight: quaternion_conv_rotation / quaternion_transpose_conv_rotation / quaternion_linear_rotation
  * (quaternion_ops.py:174-388) build one real weight K from the component tensors (A, B, *taps) element by element and run
  * one real convolution / transposed convolution / matmul with it (the algebra-1 entry points above and below).

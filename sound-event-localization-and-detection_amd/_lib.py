@@ -30,6 +30,13 @@ class ConvDesc(ctypes.Structure):
                 ("dil", ctypes.c_int32 * 2), ("groups", ctypes.c_int32)]
 
 
+class Conv3dDesc(ctypes.Structure):
+    """seld_conv3d_desc (include/seld_hip.h): per-axis arrays are (D, H, W)."""
+    _fields_ = [("algebra", ctypes.c_int32), ("N", ctypes.c_int32), ("Cin", ctypes.c_int32), ("Cout", ctypes.c_int32),
+                ("in_", ctypes.c_int32 * 3), ("k", ctypes.c_int32 * 3), ("stride", ctypes.c_int32 * 3),
+                ("pad", ctypes.c_int32 * 3), ("dil", ctypes.c_int32 * 3), ("groups", ctypes.c_int32)]
+
+
 class WgradJob(ctypes.Structure):
     """seld_wgrad_job (include/seld_hip.h): one convolution of a grouped weight-gradient call."""
     _fields_ = [("desc", ConvDesc), ("x", ctypes.c_void_p), ("dy", ctypes.c_void_p), ("dw", ctypes.c_void_p * 8)]
@@ -51,6 +58,8 @@ def lib():
         _lib.seld_hc_conv_bwd_weight_workspace.restype = ctypes.c_size_t
         _lib.seld_hcq_wgrad_group_workspace.restype = ctypes.c_size_t
         _lib.seld_hc_conv_transpose_bwd_weight_workspace.restype = ctypes.c_size_t
+        _lib.seld_hc_conv3d_bwd_weight_workspace.restype = ctypes.c_size_t
+        _lib.seld_hc_conv3d_transpose_bwd_weight_workspace.restype = ctypes.c_size_t
     return _lib
 
 

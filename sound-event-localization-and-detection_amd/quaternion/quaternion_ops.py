@@ -49,10 +49,10 @@ def get_k(input):
 
 # ---- ops ---------------------------------------------------------------------------------
 def _conv_guard(input, groups):
-    if input.dim() not in (3, 4):
-        if input.dim() == 5:
-            raise L.SeldHipError("convolution3d has no HIP kernel (the SELD models use 1-D and 2-D only)")
+    if input.dim() not in (3, 4, 5):
         raise Exception("The convolutional input is either 3, 4 or 5 dimensions. input.dim = " + str(input.dim()))
+    if input.dim() == 5 and not input.is_cuda:
+        raise L.SeldHipError("convolution3d: expected a HIP device tensor (this package has no CPU path)")
     if groups != 1:
         raise L.SeldHipError("groups != 1 is not supported")
 
