@@ -1,16 +1,20 @@
 #!/usr/bin/env python3
 """Train-step benchmark of the DualQ-SELD-TCN hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--workload c3|c2|c1|c4|c5] [--mode graph|eager] [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--workload c3|c2|c1|c4|c5] [--mode graph|eager] [--dump-outputs DIR] [--full]
 
 One step = zero_grad -> forward -> BCE + 5*MSE -> backward -> (gradient exchange) -> Adam on one synthetic
-minibatch resident in HBM.  Prints ONE JSON line (rank 0) with the whole-job samples/s, the
-roofline of the dominant kernel (and of the HBM-bound first-layer DualQ-Conv the north-star names) measured
-with HIP events, and the CPU baseline (the oracle timed on the host cores, rank 0, N = 1 only).
+minibatch resident in HBM.  Prints ONE JSON line (rank 0) with the whole-job samples/s.  A plain run does
+only what that figure needs: set-up, warm-up, the timed steps, the dump if asked for, the line.
+
+`--full` adds everything else the benchmark measures: the roofline of the dominant kernel (and of the HBM-bound first-layer
+DualQ-Conv the north-star names) measured with HIP events, the per-kernel survey of the warm-up (`conv_kernels`), and
+the CPU baseline (the oracle timed on the host cores, rank 0, N = 1 only).  It runs the same step sequence as a plain run
+with the same arguments, so both time and dump the same steps.
 
 `--mode graph` (default) replays the step as recorded HIP graphs (train.GraphedTrainStep): the same kernels,
 no host time between them.  HIP events cannot bracket a kernel inside a replayed graph, so the per-kernel
-roofline figures come from an instrumented EAGER pass of the same step run right after the timed region, in
+roofline figures of `--full` come from an instrumented EAGER pass of the same step run right after the timed region, in
 this process, on the stream the kernels are launched on (`roofline.measured_over` says so).
 
 N > 1: one process per GPU, two RCCL all-reduces of the flat gradient buffer per step (dp.BucketedGradSync), weak
@@ -240,9 +244,13 @@ def main():
     ap.add_argument("--mode", default=os.environ.get("SELD_BENCH_MODE", "auto"), choices=["auto", "graph", "eager"],
                     help="how the step is issued: one recorded HIP graph per step, eager launches, or (auto) whichever of "
                          "the two was faster over a few untimed steps after the warm-up -- same kernels, same work")
-    ap.add_argument("--roofline-steps", type=int, default=5, help="instrumented eager steps after the timed region")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-kernel-timer", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the warm-up's per-kernel survey, the "
+                         "roofline pass after the timed region and (one GPU) the CPU baseline")
+    ap.add_argument("--roofline-steps", type=int, default=5, help="--full: instrumented eager steps after the timed region")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: leave out the CPU baseline")
+    ap.add_argument("--no-kernel-timer", action="store_true",
+                    help="--full: leave out the survey and the roofline pass; either way: no floor of 2 warm-up steps")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write the last timed step's loss, updated parameters, gradient and BatchNorm statistics to "
                          "DIR/*.npy (float32); the run takes the reproducible mode (SELD_DETERMINISTIC=1)")
@@ -288,14 +296,16 @@ def main():
     def eager_step():
         return DP.dp_train_step(model, opt, sync, x, target, 42, T.seld_loss_fn)
 
-    # ---- warm-up = per-kernel survey: every conv launch of steps 1..W-1 is bracketed by HIP events (step 0 is cold:
-    # module load, allocator growth) to find the dominant kernel.  The survey runs with the weight-gradient side
-    # stream off: kernels that overlap on two queues stretch each other's brackets, and the survey is about which
-    # kernel costs most by itself.
+    # ---- warm-up; with --full also a per-kernel survey: every conv launch of steps 1..W-1 is bracketed by HIP events
+    # (step 0 is cold: module load, allocator growth) to find the dominant kernel.  The survey runs with the
+    # weight-gradient side stream off: kernels that overlap on two queues stretch each other's brackets, and the survey
+    # is about which kernel costs most by itself.
+    # The floor of two warm-up steps belongs to the survey, but a plain run keeps it too: then a plain and a --full run
+    # with the same arguments take the same steps before the timed region, and time and dump the same ones.
     survey = {}
     side_env = os.environ.get("SELD_WGRAD_SIDE_STREAM")
-    timing = not args.no_kernel_timer
-    n_warm = max(args.warmup, 2 if timing else 0)
+    timing = args.full and not args.no_kernel_timer
+    n_warm = max(args.warmup, 0 if args.no_kernel_timer else 2)
     for i in range(n_warm):
         if timing and i == 1:
             torch.cuda.synchronize()
@@ -381,7 +391,7 @@ def main():
     if args.dump_outputs and rank == 0:
         dump_outputs(args.dump_outputs, loss, model, opt, sync.average_scale())    # before the roofline pass's eager steps move the weights on
 
-    # ---- roofline pass: the same step, eager, only the dominant kernel and the first-layer DualQ-Conv bracketed
+    # ---- roofline pass (--full): the same step, eager, only the dominant kernel and the first-layer DualQ-Conv bracketed
     summ = {}
     if timing and dominant and args.roofline_steps > 0:
         first = first_layer_label(survey)
@@ -459,7 +469,7 @@ def main():
             per = [rates(k, v, max(n_warm - 1, 1)) for k, v in survey.items()]
             per.sort(key=lambda r: -r["ms_per_step"])
             out["conv_kernels"] = per[:8]
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(w, args.freq)
         print(json.dumps(out))
     if world > 1:

@@ -48,3 +48,27 @@ def test_bench_two_ranks_end_to_end():
     import math
     assert math.isfinite(out["loss"]) and 0 < out["loss"] < 10
     assert "cpu_baseline" not in out          # N > 1: no CPU leg
+
+
+@pytest.mark.gpu
+def test_bench_plain_and_full_lines():
+    """A plain one-GPU run prints the headline figures only; --full adds the survey and the roofline of the dominant
+    kernel (the CPU baseline is left out here: it alone takes most of a minute)."""
+    common = ["--gpus", "1", "--steps", "2", "--warmup", "2", "--batch", "4", "--mode", "eager"]
+    lines = {}
+    for name, extra in (("plain", []), ("full", ["--full", "--no-cpu-baseline", "--roofline-steps", "1"])):
+        r = _run(common + extra)
+        assert r.returncode == 0, r.stderr[-3000:]
+        out = [l for l in r.stdout.splitlines() if l.strip()]
+        assert len(out) == 1, r.stdout
+        lines[name] = json.loads(out[0])
+    for out in lines.values():
+        assert out["n_gpus"] == 1 and out["steps"] == 2 and out["warmup"] == 2 and out["value"] > 0
+        assert out["unit"] == "samples/s" and out["higher_is_better"] is True and out["dtype"] == "f32"
+        assert out["ms_per_step"] > 0
+    plain, full = lines["plain"], lines["full"]
+    for key in ("roofline", "roofline_hbm", "conv_kernels", "cpu_baseline"):
+        assert key not in plain, key
+    assert "cpu_baseline" not in full
+    assert full["conv_kernels"] and full["roofline"]["kernel"] in [k["kernel"] for k in full["conv_kernels"]]
+    assert full["roofline"]["measured_over"].startswith("1 instrumented eager steps")

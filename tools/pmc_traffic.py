@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
 """HBM-side traffic per launch of every kernel, from two rocprofv3 counter passes of the SAME command:
 
-    rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d gpurun_out/pmc_fetch -- python bench.py ...
-    rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d gpurun_out/pmc_write -- python bench.py ...
-    python tools/pmc_traffic.py gpurun_out/pmc_fetch gpurun_out/pmc_write profiles/r01_pmc_traffic.json
+    rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d pmc_fetch -- python bench.py --full ...
+    rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d pmc_write -- python bench.py --full ...
+    python tools/pmc_traffic.py pmc_fetch pmc_write profiles/r01_pmc_traffic.json
 
 Both counters are printed in KiB (checked: the first conv's 1.6106e9-byte output reads WRITE_SIZE = 1.574e6).  On gfx950 FETCH_SIZE counts a 128-byte request as 64 bytes for wide coalesced reads
 (/opt/skills/guides/MI355X_MICROARCH.md, HBM section): it is doubled here.  bench.py puts the value of the dominant
