@@ -621,7 +621,10 @@ int seld_adam_flat_state(float* param, const float* grad, float* exp_avg, float*
  * STFT magnitude / phase (utility_functions.py:129-155 = scipy.signal.stft(window='hamming',
  * boundary='zeros', padded=True) -> abs/angle -> drop DC bin -> drop last frame).
  * x (C, L) fp32; out (C or 2C, nperseg/2, frames-1) fp32, phase channels after magnitude channels.
- * nperseg must be a power of two <= 4096 (the reference uses 512).
+ * nperseg: any length 2 <= nperseg <= 4096 (the reference uses 512); longer segments return SELD_EUNSUPPORTED.
+ * Lengths that are not 7-smooth (2^a 3^b 5^c 7^d) run as a Bluestein transform and need a workspace of
+ * seld_stft_workspace(nperseg) bytes: only seld_stft_magphase_ws serves them, the two calls without a workspace
+ * return SELD_EWORKSPACE there.
  * ------------------------------------------------------------------------------------------ */
 int seld_stft_frames(int32_t L, int32_t nperseg, int32_t noverlap);   /* frames AFTER the cut */
 int seld_stft_magphase(const float* x, int32_t C, int32_t L, int32_t nperseg, int32_t noverlap,
@@ -634,6 +637,15 @@ int seld_stft_frames_ex(int32_t L, int32_t nperseg, int32_t noverlap, int32_t cu
 int seld_stft_magphase_ex(const float* x, int32_t C, int32_t L, int32_t nperseg, int32_t noverlap,
                           int32_t output_phase, int32_t cut_dc, int32_t cut_last_timeframe,
                           const float* window, float* out, void* stream);
+/* Bytes of device workspace seld_stft_magphase_ws needs for a segment length (0: none; the power-of-two lengths
+ * <= 1024 and every 7-smooth length need none).  The workspace is rewritten by every call (the chirp and its
+ * spectrum), so one buffer may serve calls on one stream in turn. */
+size_t seld_stft_workspace(int32_t nperseg);
+/* seld_stft_magphase_ex with a caller-provided workspace of at least seld_stft_workspace(nperseg) bytes
+ * (SELD_EWORKSPACE, nothing launched, if it is smaller).  Serves every length 2 <= nperseg <= 4096. */
+int seld_stft_magphase_ws(const float* x, int32_t C, int32_t L, int32_t nperseg, int32_t noverlap,
+                          int32_t output_phase, int32_t cut_dc, int32_t cut_last_timeframe,
+                          const float* window, float* out, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Dataset normalisation, in place on a resident predictor array x (items, channels, hw) fp32

@@ -237,12 +237,20 @@ __global__ __launch_bounds__(256) void stft512_kernel(const float* __restrict__ 
 static int frames_total(int L, int N, int noverlap) {
     const int hop = N - noverlap;
     if (hop <= 0) return -1;
-    long long Lp = (long long)L + N;                  // boundary='zeros' extension by N/2 on both sides
+    long long Lp = (long long)L + 2 * (N / 2);        // boundary='zeros' extension by N/2 (rounded down) on both sides
     long long nadd = ((-(Lp - N)) % hop + hop) % hop; // padded=True
     nadd %= N;
     long long frames = (Lp + nadd - N) / hop + 1;
     return (int)frames;
 }
+
+// the general path for every other length 2 <= N <= 4096 (stft_any.hip)
+size_t stft_any_workspace(int N);
+int stft_any_launch(const float* x, int C, int L, int N, int hop, int frames, int output_phase, int bin0,
+                    const float* window, float* out, void* workspace, size_t workspace_bytes, hipStream_t stream);
+
+// the power-of-two lengths of the kernels above
+static bool pow2_path(int N) { return N >= 4 && N <= 1024 && (N & (N - 1)) == 0; }
 
 }  // namespace seld
 using namespace seld;
@@ -255,15 +263,24 @@ extern "C" int seld_stft_frames(int32_t L, int32_t nperseg, int32_t noverlap) {
     return seld_stft_frames_ex(L, nperseg, noverlap, 1);
 }
 
-extern "C" int seld_stft_magphase_ex(const float* x, int32_t C, int32_t L, int32_t nperseg, int32_t noverlap,
+extern "C" size_t seld_stft_workspace(int32_t nperseg) {
+    if (nperseg < 2 || nperseg > 4096 || pow2_path(nperseg)) return 0;
+    return stft_any_workspace(nperseg);
+}
+
+extern "C" int seld_stft_magphase_ws(const float* x, int32_t C, int32_t L, int32_t nperseg, int32_t noverlap,
                                      int32_t output_phase, int32_t cut_dc, int32_t cut_last_timeframe,
-                                     const float* window, float* out, void* stream) {
+                                     const float* window, float* out, void* workspace, size_t workspace_bytes,
+                                     void* stream) {
     if (!x || !out || C <= 0 || L <= 0 || nperseg <= 1 || noverlap < 0 || noverlap >= nperseg) return SELD_EINVAL;
-    int logN = 0;
-    while ((1 << logN) < nperseg) ++logN;
-    if ((1 << logN) != nperseg || nperseg > 4096 || nperseg < 4) return SELD_EUNSUPPORTED;   // power-of-two segments only
+    if (nperseg > 4096) return SELD_EUNSUPPORTED;
     const int frames = frames_total(L, nperseg, noverlap) - (cut_last_timeframe ? 1 : 0);
     if (frames <= 0) return SELD_EINVAL;
+    if (!pow2_path(nperseg))
+        return stft_any_launch(x, C, L, nperseg, nperseg - noverlap, frames, output_phase, cut_dc ? 1 : 0, window, out,
+                               workspace, workspace_bytes, (hipStream_t)stream);
+    int logN = 0;
+    while ((1 << logN) < nperseg) ++logN;
     const int half = nperseg / 2;
     if (nperseg == 512 && !env().stft_radix2) {
         const size_t smem512 = sizeof(float) * ((size_t)3 * 512 + (size_t)4 * 2 * SK512 + (size_t)2 * 257 * (FT512 + 1));
@@ -272,10 +289,19 @@ extern "C" int seld_stft_magphase_ex(const float* x, int32_t C, int32_t L, int32
         return check_launch();
     }
     const size_t smem = sizeof(float) * ((size_t)2 * nperseg * 2 + (size_t)half * 2 + nperseg + (size_t)2 * (half + 1) * (FT + 1));
+    if (smem > 64 * 1024 &&       // N = 1024: 94 KB
+        hipFuncSetAttribute((const void*)stft_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess)
+        return SELD_ELAUNCH;
     dim3 grid((frames + FT - 1) / FT, C);
     hipLaunchKernelGGL(stft_kernel, grid, dim3(256), smem, (hipStream_t)stream, x, C, L, nperseg, logN,
                        nperseg - noverlap, frames, output_phase, cut_dc ? 1 : 0, window, out);
     return check_launch();
+}
+extern "C" int seld_stft_magphase_ex(const float* x, int32_t C, int32_t L, int32_t nperseg, int32_t noverlap,
+                                     int32_t output_phase, int32_t cut_dc, int32_t cut_last_timeframe,
+                                     const float* window, float* out, void* stream) {
+    return seld_stft_magphase_ws(x, C, L, nperseg, noverlap, output_phase, cut_dc, cut_last_timeframe, window, out,
+                                 nullptr, 0, stream);
 }
 extern "C" int seld_stft_magphase(const float* x, int32_t C, int32_t L, int32_t nperseg, int32_t noverlap,
                                   int32_t output_phase, float* out, void* stream) {

@@ -2245,9 +2245,15 @@ def stft_magphase(x, nperseg=512, noverlap=128, output_phase=True):
     frames = L.lib().seld_stft_frames(Ln, nperseg, noverlap)
     if frames <= 0:
         raise L.SeldHipError("seld_stft_frames: invalid segment parameters")
+    from .utility_functions import MAX_NPERSEG, stft_workspace
+    if nperseg > MAX_NPERSEG:
+        raise L.SeldHipError(f"stft_magphase: nperseg={nperseg} is longer than the longest segment the HIP STFT "
+                             f"transforms ({MAX_NPERSEG})")
     out = torch.empty(((2 if output_phase else 1) * C, nperseg // 2, frames), device=x.device, dtype=torch.float32)
-    L.check(L.lib().seld_stft_magphase(L.ptr(x), C, Ln, nperseg, noverlap, int(bool(output_phase)), L.ptr(out),
-                                       L.current_stream()), "seld_stft_magphase")
+    ws = stft_workspace(nperseg, x.device)
+    L.check(L.lib().seld_stft_magphase_ws(L.ptr(x), C, Ln, nperseg, noverlap, int(bool(output_phase)), 1, 1, None,
+                                          L.ptr(out), L.ptr(ws), ctypes.c_size_t(0 if ws is None else ws.numel()),
+                                          L.current_stream()), "seld_stft_magphase_ws")
     return out
 
 

@@ -1,8 +1,9 @@
 """Drop-in for the part of the reference's utility_functions.py that is on the hot path: `spectrum_fast`
 (utility_functions.py:129-155, called at model.py:562), the STFT magnitude / phase feature extractor.
 
-Same name, same arguments, same result layout.  The transform runs on the GPU (csrc/stft.hip through
-seld_stft_magphase_ex); there is no CPU path -- a missing device or library raises.
+Same name, same arguments, same result layout.  The transform runs on the GPU (csrc/stft.hip, csrc/stft_any.hip through
+seld_stft_magphase_ws) for every segment length 2 <= nperseg <= 4096; there is no CPU path -- a missing device or
+library raises.
 """
 import ctypes
 
@@ -10,6 +11,15 @@ import numpy as np
 import torch
 
 from . import _lib as L
+
+
+MAX_NPERSEG = 4096        # longest segment the device transforms (one workgroup's LDS)
+
+
+def stft_workspace(nperseg, device):
+    """The device workspace seld_stft_magphase_ws needs for this segment length (None when it needs none)."""
+    nbytes = L.lib().seld_stft_workspace(int(nperseg))
+    return torch.empty(nbytes, device=device, dtype=torch.uint8) if nbytes else None
 
 
 def _window_values(window, nperseg, device):
@@ -73,6 +83,9 @@ def spectrum_fast(x, nperseg=512, noverlap=128, window='hamming', cut_dc=True, o
     nperseg, noverlap = int(nperseg), int(noverlap)
     if noverlap >= nperseg:
         raise ValueError('noverlap must be less than nperseg.')          # scipy's message
+    if nperseg > MAX_NPERSEG:
+        raise L.SeldHipError(f"spectrum_fast: nperseg={nperseg} is longer than the longest segment the HIP STFT "
+                             f"transforms ({MAX_NPERSEG})")
     lib = L.lib()
     frames = lib.seld_stft_frames_ex(n, nperseg, noverlap, int(bool(cut_last_timeframe)))
     if frames <= 0:
@@ -80,10 +93,12 @@ def spectrum_fast(x, nperseg=512, noverlap=128, window='hamming', cut_dc=True, o
     bins = nperseg // 2 + 1 - int(bool(cut_dc))
     win = _window_values(window, nperseg, dev)
     out = torch.empty(((2 if output_phase else 1) * C, bins, frames), device=dev, dtype=torch.float32)
+    ws = stft_workspace(nperseg, dev)
     with torch.cuda.device(dev):
-        L.check(lib.seld_stft_magphase_ex(L.ptr(t), C, n, nperseg, noverlap, int(bool(output_phase)), int(bool(cut_dc)),
-                                          int(bool(cut_last_timeframe)), L.ptr(win), L.ptr(out), L.current_stream()),
-                "seld_stft_magphase_ex")
+        L.check(lib.seld_stft_magphase_ws(L.ptr(t), C, n, nperseg, noverlap, int(bool(output_phase)), int(bool(cut_dc)),
+                                          int(bool(cut_last_timeframe)), L.ptr(win), L.ptr(out), L.ptr(ws),
+                                          ctypes.c_size_t(0 if ws is None else ws.numel()), L.current_stream()),
+                "seld_stft_magphase_ws")
     if is_numpy:
         return out.cpu().numpy().astype(out_dtype)
     return out
