@@ -53,7 +53,8 @@ typedef struct seld_conv_desc {
     int32_t stride[2];
     int32_t pad[2];
     int32_t dil[2];      /* the reference spells the argument `dilatation`                       */
-    int32_t groups;      /* only 1 is supported (the reference never passes anything else)      */
+    int32_t groups;      /* 1 for seld_hc_conv_* (the reference never passes anything else);
+                            Cin for seld_dwconv_* (depthwise)                                    */
 } seld_conv_desc;
 
 /* epilogue flags for seld_hc_conv_fwd_ex */
@@ -219,6 +220,30 @@ int seld_hc_conv3d_transpose_bwd_weight_acc(const seld_conv3d_desc* d, const int
                                             size_t workspace_bytes, void* stream);
 int seld_hc_conv3d_transpose_kernel_label(const seld_conv3d_desc* d, const int32_t out_pad[3], int32_t which, char* buf,
                                           int32_t buflen);
+
+/* ------------------------------------------------------------------------------------------
+ * Depthwise convolution: the `depthwise` nn.Conv1d / nn.Conv2d(in, in, k, stride, padding, groups=in) of
+ * DepthwiseSeparableConv1D / DepthwiseSeparableConv2D (dual_quaternion_layers.py:19-47), and torch's groups == Cin with
+ * any channel multiplier m: output channel o reads input channel o / m.  Descriptor: seld_conv_desc with algebra 1,
+ * groups = Cin, Cout = m * Cin; weight (Cout, 1, kh, kw) contiguous, any kh * kw <= 255, stride, zero padding and
+ * dilation.  Exact fp32 VALU kernels (csrc/dwconv.hip).  SELD_EINVAL: groups != Cin, Cout % Cin != 0, algebra != 1,
+ * non-positive sizes, an empty output, missing buffers; SELD_EUNSUPPORTED: kh * kw > 255 or an image of either operand of
+ * 2^28 elements or more; SELD_EWORKSPACE: workspace too small.  Nothing is launched or written on refusal.
+ *   seld_dwconv_out_shape              output extent (H, W) (H = 1 for ndim 1)
+ *   seld_dwconv_fwd                    y = dwconv(x, w) + bias (nullable)
+ *   seld_dwconv_bwd_data               dx = dwconv^T(dy, w): gather form, no atomics
+ *   seld_dwconv_bwd_weight_workspace   bytes *_bwd_weight_acc needs (0 for a refused descriptor)
+ *   seld_dwconv_bwd_weight_acc         dw += sum x * dy, dbias (nullable) += sum dy: per-tile partials of every tap in
+ *                                      the workspace, then one fixed-order fold
+ *   seld_dwconv_kernel_label           kernel symbol of a call; which: 0 forward, 1 input gradient, 2 weight gradient
+ * No float atomics: every call is run-to-run bit-identical, with or without SELD_DETERMINISTIC. */
+int seld_dwconv_out_shape(const seld_conv_desc* d, int32_t out[2]);
+int seld_dwconv_fwd(const seld_conv_desc* d, const float* x, const float* w, const float* bias, float* y, void* stream);
+int seld_dwconv_bwd_data(const seld_conv_desc* d, const float* dy, const float* w, float* dx, void* stream);
+size_t seld_dwconv_bwd_weight_workspace(const seld_conv_desc* d);
+int seld_dwconv_bwd_weight_acc(const seld_conv_desc* d, const float* x, const float* dy, float* dw, float* dbias,
+                               void* workspace, size_t workspace_bytes, void* stream);
+int seld_dwconv_kernel_label(const seld_conv_desc* d, int32_t which, char* buf, int32_t buflen);
 
 /* ------------------------------------------------------------------------------------------
  * Quaternion ROTATION weight: quaternion_conv_rotation / quaternion_transpose_conv_rotation / quaternion_linear_rotation

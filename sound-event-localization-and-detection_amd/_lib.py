@@ -60,6 +60,7 @@ def lib():
         _lib.seld_hc_conv_transpose_bwd_weight_workspace.restype = ctypes.c_size_t
         _lib.seld_hc_conv3d_bwd_weight_workspace.restype = ctypes.c_size_t
         _lib.seld_hc_conv3d_transpose_bwd_weight_workspace.restype = ctypes.c_size_t
+        _lib.seld_dwconv_bwd_weight_workspace.restype = ctypes.c_size_t
         _lib.seld_stft_workspace.restype = ctypes.c_size_t
     return _lib
 

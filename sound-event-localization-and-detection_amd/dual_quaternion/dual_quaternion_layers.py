@@ -8,8 +8,42 @@ from torch.nn.parameter import Parameter
 
 from .dual_quaternion_ops import *     # noqa: F401,F403
 from . import dual_quaternion_ops as _ops
+from .. import _lib as _L
+from .. import hip_nn as _hnn
+from .. import hip_ops as _H
 
 _NAMES = ('r_weight', 'i_weight', 'j_weight', 'k_weight', 'r_weight_2', 'i_weight_2', 'j_weight_2', 'k_weight_2')
+
+
+class DepthwiseSeparableConv2D(Module):
+    """dual_quaternion_layers.py:19-32: depthwise k x k convolution (groups = in_channels), pointwise 1 x 1 convolution,
+    BatchNorm2d, ReLU.  Submodule names, state-dict keys and default initialisation (torch RNG draws in order) are the
+    reference's; the depthwise layer runs on the depthwise kernels, the 1 x 1 on the convolution path, BatchNorm + ReLU
+    as one fused op."""
+
+    def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0):
+        super().__init__()
+        self.depthwise = _hnn.Conv2d(in_channels, in_channels, kernel_size, stride, padding, groups=in_channels)
+        self.pointwise = _hnn.Conv2d(in_channels, out_channels, kernel_size=1)
+        self.bn = _hnn.BatchNorm2d(out_channels)
+        self.relu = _hnn.ReLU()
+
+    def forward(self, x):
+        return _H.bn_act(self.pointwise(self.depthwise(x)), self.bn, _L.SELD_ACT_RELU)
+
+
+class DepthwiseSeparableConv1D(Module):
+    """dual_quaternion_layers.py:34-47: the same on (N, C, T) input with Conv1d / BatchNorm1d."""
+
+    def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0):
+        super().__init__()
+        self.depthwise = _hnn.Conv1d(in_channels, in_channels, kernel_size, stride, padding, groups=in_channels)
+        self.pointwise = _hnn.Conv1d(in_channels, out_channels, kernel_size=1)
+        self.bn = _hnn.BatchNorm1d(out_channels)
+        self.relu = _hnn.ReLU()
+
+    def forward(self, x):
+        return _H.bn_act(self.pointwise(self.depthwise(x)), self.bn, _L.SELD_ACT_RELU)
 
 
 class DualQuaternionConv(Module):

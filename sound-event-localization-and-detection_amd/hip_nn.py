@@ -14,15 +14,23 @@ from . import hip_ops as H
 
 class Conv1d(nn.Conv1d):
     def forward(self, x):
+        if self.groups != 1 and self.groups == self.in_channels and self.out_channels % self.in_channels == 0 \
+                and self.padding_mode == "zeros" and not isinstance(self.padding, str):
+            return H.depthwise_conv(x, self.weight, self.bias, self.stride, self.padding, self.dilation)
         if self.groups != 1 or self.padding_mode != "zeros" or isinstance(self.padding, str):
-            raise L.SeldHipError("Conv1d: only groups=1, zero padding given as integers is supported")
+            raise L.SeldHipError("Conv1d: only groups=1 or groups=in_channels (depthwise), zero padding given as "
+                                 "integers is supported")
         return H.hyper_conv(x, (self.weight,), self.bias, self.stride, self.padding, self.dilation)
 
 
 class Conv2d(nn.Conv2d):
     def forward(self, x):
+        if self.groups != 1 and self.groups == self.in_channels and self.out_channels % self.in_channels == 0 \
+                and self.padding_mode == "zeros" and not isinstance(self.padding, str):
+            return H.depthwise_conv(x, self.weight, self.bias, self.stride, self.padding, self.dilation)
         if self.groups != 1 or self.padding_mode != "zeros" or isinstance(self.padding, str):
-            raise L.SeldHipError("Conv2d: only groups=1, zero padding given as integers is supported")
+            raise L.SeldHipError("Conv2d: only groups=1 or groups=in_channels (depthwise), zero padding given as "
+                                 "integers is supported")
         return H.hyper_conv(x, (self.weight,), self.bias, self.stride, self.padding, self.dilation)
 
 

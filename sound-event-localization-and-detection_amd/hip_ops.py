@@ -1009,6 +1009,160 @@ class ConvTranspose3dFn(torch.autograd.Function):
         return (dx, dbias, None, None, None, None, *dws)
 
 
+# ---- depthwise convolution (csrc/dwconv.hip) ----------------------------------------------------------------------------
+# nn.Conv1d / nn.Conv2d with groups == Cin and Cout = m * Cin: the `depthwise` layer of DepthwiseSeparableConv1D / 2D
+# (dual_quaternion_layers.py:19-47).  Descriptor: seld_conv_desc with algebra 1 and groups = Cin.
+def make_dwconv_desc(x_shape, cout, kernel, stride, padding, dilation):
+    return make_conv_desc(x_shape, cout, 1, kernel, stride, padding, dilation, groups=x_shape[1])
+
+
+def dwconv_out_shape(desc):
+    out = (ctypes.c_int32 * 2)()
+    L.check(L.lib().seld_dwconv_out_shape(ctypes.byref(desc), out), "seld_dwconv_out_shape")
+    return out[0], out[1]
+
+
+def dwconv_label(desc, which):
+    buf = ctypes.create_string_buffer(64)
+    L.check(L.lib().seld_dwconv_kernel_label(ctypes.byref(desc), which, buf, 64), "seld_dwconv_kernel_label")
+    return buf.value.decode()
+
+
+def dwconv_work(desc, which):
+    """Algorithmic flops / bytes of one call: 2 flops per (output, tap); the streamed operands once -- forward and input
+    gradient x + y + weights, weight gradient x + dy + weights."""
+    o = dwconv_out_shape(desc)
+    s_in, s_out = desc.in_[0] * desc.in_[1], o[0] * o[1]
+    K = desc.k[0] * desc.k[1]
+    flops = 2.0 * desc.N * desc.Cout * s_out * K
+    by = 4.0 * (desc.N * desc.Cin * s_in + desc.N * desc.Cout * s_out + desc.Cout * K)
+    return flops, by
+
+
+class _DwTimed:
+    """KernelTimer record of one depthwise launch (label from seld_dwconv_kernel_label)."""
+
+    def __init__(self, desc, which):
+        self.on = kernel_timer.active
+        if self.on:
+            self.label = dwconv_label(desc, which)
+            if kernel_timer.only is not None and self.label not in kernel_timer.only:
+                self.on = False
+        if self.on:
+            self.desc, self.which = desc, which
+            self.e0 = torch.cuda.Event(enable_timing=True)
+            self.e1 = torch.cuda.Event(enable_timing=True)
+
+    def __enter__(self):
+        if self.on:
+            self.e0.record()
+        return self
+
+    def __exit__(self, *exc):
+        if self.on:
+            self.e1.record()
+            fl, by = dwconv_work(self.desc, self.which)
+            kernel_timer.records.append((self.label, self.e0, self.e1, fl, by))
+        return False
+
+
+def _dw_y_shape(desc, o, C):
+    return (desc.N, C, o[1]) if desc.ndim == 1 else (desc.N, C, o[0], o[1])
+
+
+def dwconv_fwd(desc, x, w, bias=None):
+    x, w, bias = _req(x, "x"), _req(w, "w"), _req(bias, "bias")
+    y = torch.empty(_dw_y_shape(desc, dwconv_out_shape(desc), desc.Cout), device=x.device, dtype=torch.float32)
+    with _DwTimed(desc, 0):
+        L.check(L.lib().seld_dwconv_fwd(ctypes.byref(desc), L.ptr(x), L.ptr(w), L.ptr(bias), L.ptr(y),
+                                        L.current_stream()), "seld_dwconv_fwd")
+    return y
+
+
+def dwconv_bwd_data(desc, dy, w, x_shape):
+    dy, w = _req(dy, "dy"), _req(w, "w")
+    dx = torch.empty(x_shape, device=dy.device, dtype=torch.float32)
+    with _DwTimed(desc, 1):
+        L.check(L.lib().seld_dwconv_bwd_data(ctypes.byref(desc), L.ptr(dy), L.ptr(w), L.ptr(dx), L.current_stream()),
+                "seld_dwconv_bwd_data")
+    return dx
+
+
+_dwconv_scratch = {}         # (device, stream) -> workspace of the weight-gradient partials (fully rewritten per call)
+
+
+def _dwconv_ws(nbytes, device):
+    if torch.cuda.is_current_stream_capturing():
+        # a recorded step: the workspace comes from (and stays in) the graph's own memory pool
+        return torch.empty(nbytes, device=device, dtype=torch.uint8)
+    key = (device, torch.cuda.current_stream(device).cuda_stream)
+    ws = _dwconv_scratch.get(key)
+    if ws is None or ws.numel() < nbytes:
+        ws = _dwconv_scratch[key] = torch.empty(nbytes, device=device, dtype=torch.uint8)
+    return ws
+
+
+def dwconv_bwd_weight_acc(desc, x, dy, dw, dbias=None):
+    """dw += sum x * dy per (channel, tap), dbias += channel sums of dy: per-tile partials in a workspace, one fixed-order
+    fold (no atomics, so the same bits with or without SELD_DETERMINISTIC)."""
+    x, dy = _req(x, "x"), _req(dy, "dy")
+    lib = L.lib()
+    nbytes = int(lib.seld_dwconv_bwd_weight_workspace(ctypes.byref(desc)))
+    ws = _dwconv_ws(nbytes, x.device)
+    with _DwTimed(desc, 2):
+        L.check(lib.seld_dwconv_bwd_weight_acc(ctypes.byref(desc), L.ptr(x), L.ptr(dy), L.ptr(dw), L.ptr(dbias),
+                                               L.ptr(ws), ctypes.c_size_t(ws.numel()), L.current_stream()),
+                "seld_dwconv_bwd_weight_acc")
+
+
+class DepthwiseConvFn(torch.autograd.Function):
+    """y = conv(x, w, bias, groups=C) for a weight (m*C, 1, k) / (m*C, 1, kh, kw); replaces the depthwise F.conv1d/2d.
+    dx: gather-form transposed kernel; dw, dbias: per-tile partials + fold, straight into the optimiser's gradient slots
+    when it owns them (_claim_grad_slots), else into a buffer zeroed by seld_step_begin that autograd adds to .grad."""
+
+    @staticmethod
+    def forward(ctx, x, w, bias, stride, padding, dilation):
+        x = _req(x, "x")
+        if w.dim() != x.dim() or w.shape[1] != 1 or w.shape[0] % x.shape[1]:
+            raise L.SeldHipError(f"depthwise convolution: weight {tuple(w.shape)} for an input of shape {tuple(x.shape)}")
+        if bias is not None and tuple(bias.shape) != (w.shape[0],):
+            raise L.SeldHipError(f"depthwise convolution: bias {tuple(bias.shape)} for {w.shape[0]} output channels")
+        desc = make_dwconv_desc(tuple(x.shape), w.shape[0], tuple(w.shape[2:]), stride, padding, dilation)
+        y = dwconv_fwd(desc, x, w, bias)
+        ctx.desc = desc
+        ctx.params = (w, bias)
+        ctx.save_for_backward(x)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, = ctx.saved_tensors
+        w, bias = ctx.params
+        dy = _req(dy, "dy")
+        desc = ctx.desc
+        dx = dwconv_bwd_data(desc, dy, w, tuple(x.shape)) if ctx.needs_input_grad[0] else None
+        want_w = ctx.needs_input_grad[1]
+        want_b = bias is not None and ctx.needs_input_grad[2]
+        if not (want_w or want_b):
+            return dx, None, None, None, None, None
+        if want_w:
+            slot, _ = _claim_grad_slots([w] + ([bias] if want_b else []), adjacent=False)
+            if slot is not None:
+                dwconv_bwd_weight_acc(desc, x, dy, w.grad, bias.grad if want_b else None)
+                return dx, None, None, None, None, None
+        sizes = [w.numel()] + ([bias.numel()] if want_b else [])
+        flat = torch.empty(sum(sizes), device=dy.device, dtype=torch.float32)
+        step_begin(flat)
+        parts = torch.split(flat, sizes)
+        dwconv_bwd_weight_acc(desc, x, dy, parts[0], parts[1] if want_b else None)
+        return (dx, parts[0].view(w.shape) if want_w else None, parts[1] if want_b else None, None, None, None)
+
+
+def depthwise_conv(x, w, bias, stride, padding, dilation):
+    """Depthwise convolution (groups = input channels, Cout = m * Cin) of (N, C, T) or (N, C, H, W) input."""
+    return DepthwiseConvFn.apply(x, w, bias, stride, padding, dilation)
+
+
 # ---- quaternion rotation weight (csrc/quat_rotation.hip) -----------------------------------------------------------------
 # quaternion_{conv,transpose_conv,linear}_rotation (quaternion_ops.py:174-388) build ONE real weight K from the four
 # component tensors and run one real op with it: here K comes from seld_quat_rotation_form and the op is the algebra-1
