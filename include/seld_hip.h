@@ -604,6 +604,26 @@ int seld_mha_packed_ok(int32_t T, int32_t hd);
 int seld_mha_fwd_packed(const float* qkv, int32_t N, int32_t T, int32_t H, int32_t hd, float* out, float* lse, void* stream);
 int seld_mha_bwd_packed(const float* qkv, const float* out, const float* dout, const float* lse, int32_t N, int32_t T,
                         int32_t H, int32_t hd, float* dqkv, void* workspace, size_t workspace_bytes, void* stream);
+/* Masked and cross-length attention (model.py:25-51 with a mask, or key_len != query_len):
+ *   out = softmax(masked(q k^T) / sqrt(hd)) v, per head.
+ * q, out, dq: (N, H*hd, Tq); k, v, dk, dv: (N, H*hd, Tk); lse (N, H, Tq): the saved row statistics.  hd <= 64.
+ * keep (may be NULL: no mask): uint8 keep-mask over the (N, H, Tq, Tk) energy, element (n, h, q, k) at
+ * keep[n*s[0] + h*s[1] + q*s[2] + k*s[3]] with s = mask_strides (elements, >= 0; 0 on a broadcast dim).  A score
+ * whose keep byte is 0 is replaced by -1e9 / sqrt(hd) (masked_fill(mask == 0, -1e9) before the scaling): masked keys
+ * of a partially masked row get weight exactly 0, and a fully masked row attends uniformly to all Tk keys (its output
+ * is the mean of v; its lse is saved as +inf).  Backward follows masked_fill: a masked score has zero gradient, so a
+ * fully masked row gives dq = 0, nothing to dk, and dout / Tk to every key's dv.
+ * Dispatch: fp32 matrix cores for hd in {16, 32, 48, 64} with Tq % 16 == 0 and Tk % 16 == 0 (unless SELD_MHA_NO_MFMA),
+ * the VALU kernels otherwise.  SELD_EINVAL (NULL tensor, a size <= 0, keep without strides or with a negative
+ * stride), SELD_EUNSUPPORTED (hd > 64) and SELD_EWORKSPACE are returned before anything is written.  workspace:
+ * seld_mha_bwd_ex_workspace(N, Tq, H) bytes. */
+int seld_mha_fwd_ex(const float* q, const float* k, const float* v, int32_t N, int32_t Tq, int32_t Tk, int32_t H,
+                    int32_t hd, const uint8_t* keep, const int64_t mask_strides[4], float* out, float* lse, void* stream);
+size_t seld_mha_bwd_ex_workspace(int32_t N, int32_t Tq, int32_t H);
+int seld_mha_bwd_ex(const float* q, const float* k, const float* v, const float* out, const float* dout,
+                    const float* lse, int32_t N, int32_t Tq, int32_t Tk, int32_t H, int32_t hd, const uint8_t* keep,
+                    const int64_t mask_strides[4], float* dq, float* dk, float* dv, void* workspace,
+                    size_t workspace_bytes, void* stream);
 
 /* (N, C, T) <-> (N, T, C) transposes (the permutes of model.py:30-37, 220-222, 318) */
 int seld_transpose_nct_ntc(const float* x, int32_t N, int32_t C, int32_t T, float* y, void* stream);

@@ -2278,6 +2278,83 @@ def mha_core(q, k, v, heads):
     return MhaCoreFn.apply(q, k, v, heads)
 
 
+def _mha_keep_mask(mask, shape, device):
+    """The mask of model.py:43-44 as (uint8 keep tensor, int64[4] element strides) over the energy shape (N, H, Tq, Tk).
+    It broadcasts with torch's rules (a 2-D mask is (Tq, Tk); a 3-D mask's first dim lines up with the heads) and must
+    not enlarge the energy shape.  bool / uint8 masks are read as they are; any other dtype is converted once with
+    `mask != 0`, the only ATen launch on this path.  Shapes only: no host synchronisation."""
+    if not torch.is_tensor(mask):
+        raise L.SeldHipError(f"attention mask: expected a tensor, got {type(mask).__name__}")
+    if mask.device != device:
+        raise L.SeldHipError(f"attention mask: on {mask.device}, the attention runs on {device}")
+    try:
+        ok = mask.dim() <= 4 and tuple(torch.broadcast_shapes(tuple(mask.shape), shape)) == tuple(shape)
+    except RuntimeError:
+        ok = False
+    if not ok:
+        raise L.SeldHipError(f"attention mask: shape {tuple(mask.shape)} does not broadcast to the energy {tuple(shape)}")
+    if mask.dtype == torch.bool:
+        keep = mask.view(torch.uint8)
+    elif mask.dtype == torch.uint8:
+        keep = mask
+    else:
+        keep = mask != 0
+        keep = keep.view(torch.uint8)
+    strides = (ctypes.c_int64 * 4)(*keep.expand(shape).stride())
+    return keep, strides
+
+
+class MhaMaskedFn(torch.autograd.Function):
+    """softmax(masked(q k^T) / sqrt(hd)) v (model.py:25-51 with a mask) on q (N, E, Tq) and k, v (N, E, Tk):
+    seld_mha_fwd_ex / seld_mha_bwd_ex.  Masked scores take -1e9 / sqrt(hd); the mask has no gradient."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, heads, mask):
+        q, k, v = _req(q, "q"), _req(k, "k"), _req(v, "v")
+        if q.dim() != 3 or k.dim() != 3 or v.dim() != 3:
+            raise L.SeldHipError("mha_core_ex: expected (N, E, T) tensors")
+        N, E, Tq = q.shape
+        Tk = k.shape[2]
+        if tuple(k.shape) != (N, E, Tk) or tuple(v.shape) != (N, E, v.shape[2]):
+            raise L.SeldHipError(f"mha_core_ex: q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)} do not match")
+        if v.shape[2] != Tk:
+            raise L.SeldHipError(f"mha_core_ex: value_len {v.shape[2]} != key_len {Tk}")
+        if heads <= 0 or E % heads:
+            raise L.SeldHipError(f"mha_core_ex: {E} channels do not split into {heads} heads")
+        hd = E // heads
+        if hd > 64:
+            raise L.SeldHipError(f"mha_core_ex: head dim {hd} > 64 is not supported")
+        keep, strides = (None, None) if mask is None else _mha_keep_mask(mask, (N, heads, Tq, Tk), q.device)
+        out = torch.empty_like(q)
+        lse = torch.empty((N, heads, Tq), device=q.device, dtype=torch.float32)
+        L.check(L.lib().seld_mha_fwd_ex(L.ptr(q), L.ptr(k), L.ptr(v), N, Tq, Tk, heads, hd, L.ptr(keep), strides,
+                                        L.ptr(out), L.ptr(lse), L.current_stream()), "seld_mha_fwd_ex")
+        ctx.geom = (N, Tq, Tk, heads, hd)
+        ctx.strides = strides
+        ctx.save_for_backward(q, k, v, out, lse, keep)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        q, k, v, out, lse, keep = ctx.saved_tensors
+        N, Tq, Tk, H, hd = ctx.geom
+        dout = _req(dout, "dout")
+        dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
+        lib = L.lib()
+        lib.seld_mha_bwd_ex_workspace.restype = ctypes.c_size_t
+        nbytes = lib.seld_mha_bwd_ex_workspace(N, Tq, H)
+        wsb = torch.empty((nbytes + 3) // 4, device=q.device, dtype=torch.float32)
+        L.check(lib.seld_mha_bwd_ex(L.ptr(q), L.ptr(k), L.ptr(v), L.ptr(out), L.ptr(dout), L.ptr(lse), N, Tq, Tk, H, hd,
+                                    L.ptr(keep), ctx.strides, L.ptr(dq), L.ptr(dk), L.ptr(dv), L.ptr(wsb),
+                                    ctypes.c_size_t(nbytes), L.current_stream()), "seld_mha_bwd_ex")
+        return dq, dk, dv, None, None
+
+
+def mha_core_ex(q, k, v, heads, mask=None):
+    """Attention with an optional mask (broadcast to (N, heads, Tq, Tk), entries == 0 masked) and key_len != query_len."""
+    return MhaMaskedFn.apply(q, k, v, heads, mask)
+
+
 class MhaPackedFn(torch.autograd.Function):
     """The same attention on ONE projected tensor qkv (N, 3E, T) = [values | keys | queries] (seld_mha_fwd_packed): the
     three projections of model.py:31-33 are one convolution, and so are their data and weight gradients."""

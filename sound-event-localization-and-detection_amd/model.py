@@ -75,9 +75,12 @@ class MultiHeadAttention(nn.Module):
         self.queries = hnn.Conv1d(embed_size, embed_size, kernel_size=1, bias=False)
         self.fc_out = hnn.Linear(embed_size, embed_size)
 
-    def _attend(self, v, k, q):
+    def _attend(self, v, k, q, mask=None, general=False):
         v, k, q = self.values(v), self.keys(k), self.queries(q)
-        out = H.mha_core(q, k, v, self.num_heads)
+        if general:         # a mask, or key_len != query_len
+            out = H.mha_core_ex(q, k, v, self.num_heads, mask)
+        else:
+            out = H.mha_core(q, k, v, self.num_heads)
         # fc_out on the (N, E, T) layout = 1x1 convolution with the Linear's (E, E) weight
         w = self.fc_out.weight
         return H.hyper_conv(out, (H.as_conv_weight(w, (*w.shape, 1)),), self.fc_out.bias, 1, 0, 1)
@@ -103,8 +106,12 @@ class MultiHeadAttention(nn.Module):
         return H.hyper_conv(out, (H.as_conv_weight(wo, (*wo.shape, 1)),), self.fc_out.bias, 1, 0, 1)
 
     def forward(self, v, k, q, mask=None):
-        if mask is not None:
-            raise L.SeldHipError("MultiHeadAttention: attention masks are not supported (the reference always passes None)")
+        """mask: entries == 0 are masked (model.py:43-44); it broadcasts against the (N, heads, query_len, key_len)
+        energy, so a 2-D mask is (query_len, key_len) and a 3-D mask's first dim lines up with the heads."""
+        if v.shape[1] != k.shape[1]:
+            raise L.SeldHipError(f"MultiHeadAttention: value_len {v.shape[1]} != key_len {k.shape[1]}")
+        if mask is not None or k.shape[1] != q.shape[1]:
+            return H.transpose12(self._attend(H.transpose12(v), H.transpose12(k), H.transpose12(q), mask, general=True))
         if v is k and k is q:
             return H.transpose12(self.forward_nct(H.transpose12(q)))
         return H.transpose12(self._attend(H.transpose12(v), H.transpose12(k), H.transpose12(q)))
