@@ -246,6 +246,66 @@ int seld_dwconv_bwd_weight_acc(const seld_conv_desc* d, const float* x, const fl
 int seld_dwconv_kernel_label(const seld_conv_desc* d, int32_t which, char* buf, int32_t buflen);
 
 /* ------------------------------------------------------------------------------------------
+ * Element-wise quaternion algebra (csrc/quat_algebra.hip): get_modulus / get_normalized / hamilton_product of
+ * quaternion_ops.py:102-122, :467-506 and dual_quaternion_ops.py:88-108, :374-412, q_normalize / quaternion_exp of
+ * dual_quaternion_ops.py:206-243.  Exact fp32 VALU kernels, one pass over memory each (the sums over dim 0: one pass
+ * and a fold), forward and first derivatives.
+ * seld_quat_shape: the contiguous input as (dim0, mid, comp, inner), `comp` the component axis [r | i | j | k]:
+ *   2-D (N, 4Q)      -> (N, 1, 4Q, 1)        3-D (B, T, 4Q)          -> (B, T, 4Q, 1)
+ *   4-D (N, 4Q, H, W) -> (N, 1, 4Q, H*W)     5-D (N, 4Q, D, H, W)    -> (N, 1, 4Q, D*H*W)
+ * With Q = comp / 4 and M = Q * inner, per-quaternion arrays are (dim0, mid, M) and arrays summed over dim 0 (mid, M).
+ * layout (q_normalize / quaternion_exp, which concatenate on dim 1 whatever the rank): SELD_QUAT_LAYOUT_INPUT: y and dy
+ * laid out like x; SELD_QUAT_LAYOUT_CAT1: y and dy are (dim0, 4, mid, M), i.e. (B, 4T, Q) for a 3-D input, written and
+ * read in place (no permuted copy).  The two coincide for mid == 1.
+ * SELD_EINVAL: comp % 4 != 0, a non-positive extent, an unknown layout, a NULL pointer; SELD_EUNSUPPORTED: 2^31
+ * quaternions or more; SELD_EWORKSPACE: workspace missing or smaller than seld_quat_reduce_workspace(shape).  Nothing
+ * is launched or written on refusal.  16-byte accesses when M % 4 == 0 and every pointer is 16-byte aligned.
+ *   seld_quat_modulus_fwd         y[dim0, mid, M] = sqrt(r^2 + i^2 + j^2 + k^2)            (vector_form=True)
+ *   seld_quat_modulus_bwd         dx_c = dy * x_c / |q|   (0 at |q| = 0, where the reference's autograd gives NaN)
+ *   seld_quat_reduce_workspace    bytes the three calls below with a workspace need (0 for a refused shape)
+ *   seld_quat_modulus_sum_fwd     y[mid, M] = sqrt(sum over dim0 of r^2 + i^2 + j^2 + k^2)  (vector_form=False)
+ *   seld_quat_modulus_sum_bwd     dx_c = dy[mid, M] * x_c / y[mid, M]   (0 where y = 0)
+ *   seld_quat_normalized_fwd      y_c = x_c / (modulus[mid, M] + eps), modulus from seld_quat_modulus_sum_fwd
+ *   seld_quat_normalized_bwd      dx_c = dy_c / (D + eps) - x_c * G / ((D + eps)^2 * D), D = modulus, G[mid, M] the sum
+ *                                 over dim0 and the components of dy * x (second term dropped where D = 0)
+ *   seld_quat_normalize_fwd/_bwd  q_normalize: y_c = x_c / sqrt(|q|^2 + 1e-4); finite everywhere (dx = 100 dy at q = 0)
+ *   seld_quat_exp_fwd/_bwd        quaternion_exp: n = |(i, j, k)| + 1e-4, y = exp(r) [cos n, (i, j, k) sin(n) / n]; at
+ *                                 i = j = k = 0 the gradient is d/dr = the result's, d/d(i, j, k) = exp(r) dy sin(n) / n
+ *                                 (the reference's autograd gives NaN there)
+ *   seld_quat_hamilton_fwd        y = q0 (x) q1, both of `shape`
+ *   seld_quat_hamilton_bwd        dq0 = dy (x) conj(q1) and dq1 = conj(q0) (x) dy from one read of q0, q1, dy
+ * Sums over dim 0 are per-slice partials in the workspace and one fixed-order fold; no float atomics: every call is
+ * run-to-run bit-identical, with or without SELD_DETERMINISTIC. */
+typedef struct {
+    int32_t dim0;        /* extent of dim 0: what the summed forms reduce over                                   */
+    int32_t mid;         /* T of a 3-D input (B, T, 4Q), else 1                                                   */
+    int32_t comp;        /* extent of the component axis, 4Q                                                      */
+    int32_t inner;       /* product of the extents after the component axis (1 for 2-D / 3-D input)               */
+} seld_quat_shape;
+#define SELD_QUAT_LAYOUT_INPUT  0
+#define SELD_QUAT_LAYOUT_CAT1   1
+int seld_quat_modulus_fwd(const seld_quat_shape* shape, const float* x, float* y, void* stream);
+int seld_quat_modulus_bwd(const seld_quat_shape* shape, const float* x, const float* dy, float* dx, void* stream);
+size_t seld_quat_reduce_workspace(const seld_quat_shape* shape);
+int seld_quat_modulus_sum_fwd(const seld_quat_shape* shape, const float* x, float* y, void* workspace,
+                              size_t workspace_bytes, void* stream);
+int seld_quat_modulus_sum_bwd(const seld_quat_shape* shape, const float* x, const float* y, const float* dy, float* dx,
+                              void* stream);
+int seld_quat_normalized_fwd(const seld_quat_shape* shape, const float* x, const float* modulus, float eps, float* y,
+                             void* stream);
+int seld_quat_normalized_bwd(const seld_quat_shape* shape, const float* x, const float* modulus, const float* dy, float eps,
+                             float* dx, void* workspace, size_t workspace_bytes, void* stream);
+int seld_quat_normalize_fwd(const seld_quat_shape* shape, int32_t layout, const float* x, float* y, void* stream);
+int seld_quat_normalize_bwd(const seld_quat_shape* shape, int32_t layout, const float* x, const float* dy, float* dx,
+                            void* stream);
+int seld_quat_exp_fwd(const seld_quat_shape* shape, int32_t layout, const float* x, float* y, void* stream);
+int seld_quat_exp_bwd(const seld_quat_shape* shape, int32_t layout, const float* x, const float* dy, float* dx,
+                      void* stream);
+int seld_quat_hamilton_fwd(const seld_quat_shape* shape, const float* q0, const float* q1, float* y, void* stream);
+int seld_quat_hamilton_bwd(const seld_quat_shape* shape, const float* q0, const float* q1, const float* dy, float* dq0,
+                           float* dq1, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Quaternion ROTATION weight: quaternion_conv_rotation / quaternion_transpose_conv_rotation / quaternion_linear_rotation
  * (quaternion_ops.py:174-388) build one real weight K from the component tensors (A, B, *taps) element by element and run
  * one real convolution / transposed convolution / matmul with it (the algebra-1 entry points above and below).

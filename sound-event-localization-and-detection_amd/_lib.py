@@ -17,6 +17,7 @@ SELD_EPI_NONE, SELD_EPI_ACCUMULATE, SELD_EPI_ADD, SELD_EPI_STATS = 0, 1, 2, 4
 SELD_ACT_NONE, SELD_ACT_RELU, SELD_ACT_TANH, SELD_ACT_SIGMOID = 0, 1, 2, 3
 SELD_LIN_REAL, SELD_LIN_QUAT, SELD_LIN_DUALQ = 1, 4, 8
 SELD_ROT_LAYOUT_CONV, SELD_ROT_LAYOUT_LINEAR = 0, 1
+SELD_QUAT_LAYOUT_INPUT, SELD_QUAT_LAYOUT_CAT1 = 0, 1
 
 
 class SeldHipError(RuntimeError):
@@ -35,6 +36,11 @@ class Conv3dDesc(ctypes.Structure):
     _fields_ = [("algebra", ctypes.c_int32), ("N", ctypes.c_int32), ("Cin", ctypes.c_int32), ("Cout", ctypes.c_int32),
                 ("in_", ctypes.c_int32 * 3), ("k", ctypes.c_int32 * 3), ("stride", ctypes.c_int32 * 3),
                 ("pad", ctypes.c_int32 * 3), ("dil", ctypes.c_int32 * 3), ("groups", ctypes.c_int32)]
+
+
+class QuatShape(ctypes.Structure):
+    """seld_quat_shape (include/seld_hip.h): the contiguous input as (dim0, mid, comp, inner), comp the component axis."""
+    _fields_ = [("dim0", ctypes.c_int32), ("mid", ctypes.c_int32), ("comp", ctypes.c_int32), ("inner", ctypes.c_int32)]
 
 
 class WgradJob(ctypes.Structure):
@@ -62,6 +68,7 @@ def lib():
         _lib.seld_hc_conv3d_transpose_bwd_weight_workspace.restype = ctypes.c_size_t
         _lib.seld_dwconv_bwd_weight_workspace.restype = ctypes.c_size_t
         _lib.seld_stft_workspace.restype = ctypes.c_size_t
+        _lib.seld_quat_reduce_workspace.restype = ctypes.c_size_t
     return _lib
 
 

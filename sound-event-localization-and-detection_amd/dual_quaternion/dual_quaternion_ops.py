@@ -27,6 +27,57 @@ def check_input(input):
         raise RuntimeError("Quaternion Tensors must be divisible by 4. input.size()[1] = " + str(nb_hidden))
 
 
+# ---- element-wise algebra (dual_quaternion_ops.py:88-108, :206-243, :374-412) ---------------
+def get_modulus(input, vector_form=False):
+    """sqrt(r^2 + i^2 + j^2 + k^2) per quaternion with vector_form, else the root of that sum taken over dim 0 too
+    (the input's shape without dim 0, component axis / 4); ranks 2 to 5, one HIP pass (csrc/quat_algebra.hip)."""
+    check_input(input)
+    return H.quat_modulus(input, vector_form)
+
+
+def get_normalized(input, eps=0.0001):
+    """input / (get_modulus(input) repeated over dim 0 and the four components + eps), rank 2 or 3 (the reference has
+    no branch for rank 4 / 5 and dies with UnboundLocalError)."""
+    check_input(input)
+    if input.dim() not in (2, 3):
+        raise L.SeldHipError(f"get_normalized: expected an input of rank 2 or 3, got rank {input.dim()}")
+    return H.quat_normalized(input, eps)
+
+
+def _split_cat(y, input, channel):
+    """The four components of y (laid out like input) concatenated on `channel`."""
+    axis = input.dim() - 1 if input.dim() < 4 else 1
+    return torch.cat(torch.chunk(y, 4, dim=axis), dim=channel)
+
+
+def q_normalize(input, channel=1):
+    """Each quaternion divided by sqrt(|q|^2 + 1e-4), components concatenated on `channel`.  channel = 1 is one pass:
+    for a 3-D input (B, T, 4Q) the kernel writes the (B, 4T, Q) result directly; another channel costs one copy."""
+    check_input(input)
+    ch = channel + input.dim() if channel < 0 else channel
+    if ch == 1 or (input.dim() == 3 and ch == 2):
+        return H.quat_unit(input, cat1=ch == 1)
+    return _split_cat(H.quat_unit(input, cat1=False), input, channel)
+
+
+def quaternion_exp(input):
+    """exp(r) * [cos n, (i, j, k) * sin(n) / n] with n = |(i, j, k)| + 1e-4, components concatenated on dim 1
+    ((B, 4T, Q) for a 3-D input)."""
+    check_input(input)
+    return H.quat_exp(input, cat1=True)
+
+
+def hamilton_product(q0, q1):
+    """q0 (x) q1 for rank 2, 4 or 5 tensors with the components on axis 1.  The reference concatenates on dim 1, so its
+    3-D call fails on the shapes; it is refused here."""
+    check_input(q0)
+    check_input(q1)
+    if q0.dim() == 3 or q1.dim() == 3 or q0.dim() != q1.dim():
+        raise L.SeldHipError("hamilton_product: expected two inputs of rank 2, 4 or 5, got "
+                             f"{tuple(q0.shape)} and {tuple(q1.shape)}")
+    return H.hamilton_product(q0, q1)
+
+
 def dual_quaternion_conv(input, r_weight, i_weight, j_weight, k_weight, r_weight_2, i_weight_2, j_weight_2,
                          k_weight_2, bias, stride, padding, groups, dilatation):
     _conv_guard(input, groups)

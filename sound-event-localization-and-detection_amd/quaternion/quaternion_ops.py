@@ -47,6 +47,40 @@ def get_k(input):
     return _component(input, 3)
 
 
+# ---- element-wise algebra (quaternion_ops.py:102-122, :467-506) ----------------------------
+def _algebra_input(input):
+    """The reference's own check_input (quaternion_ops.py:52-66): rank 2 or 3, last axis divisible by 4.  The
+    check_input above is wider because get_r .. get_k also serve the convolution paths."""
+    if input.dim() not in {2, 3}:
+        raise RuntimeError("quaternion linear accepts only input of dimension 2 or 3. input.dim = " + str(input.dim()))
+    if input.size()[-1] % 4 != 0:
+        raise RuntimeError("Quaternion Tensors must be divisible by 4. input.size()[1] = " + str(input.size()[-1]))
+
+
+def get_modulus(input, vector_form=False):
+    """sqrt(r^2 + i^2 + j^2 + k^2) per quaternion with vector_form, else the root of that sum taken over dim 0 too
+    (the input's shape without dim 0, last axis / 4); one HIP pass (csrc/quat_algebra.hip)."""
+    _algebra_input(input)
+    return H.quat_modulus(input, vector_form)
+
+
+def get_normalized(input, eps=0.0001):
+    """input / (get_modulus(input) repeated over dim 0 and the four components + eps)."""
+    _algebra_input(input)
+    return H.quat_normalized(input, eps)
+
+
+def hamilton_product(q0, q1):
+    """q0 (x) q1 for (batch, 4Q) tensors [r | i | j | k].  The reference concatenates on dim 1, so its 3-D call fails
+    on the shapes; it is refused here."""
+    _algebra_input(q0)
+    _algebra_input(q1)
+    if q0.dim() != 2 or q1.dim() != 2:
+        raise L.SeldHipError("hamilton_product: expected (batch, 4Q) inputs, got "
+                             f"{tuple(q0.shape)} and {tuple(q1.shape)}")
+    return H.hamilton_product(q0, q1)
+
+
 # ---- ops ---------------------------------------------------------------------------------
 def _conv_guard(input, groups):
     if input.dim() not in (3, 4, 5):
