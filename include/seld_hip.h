@@ -790,6 +790,44 @@ int seld_metrics_accumulate(const float* sed, const float* doa, const float* tar
                             double spatial_threshold, double doa_threshold, int32_t frames_per_block,
                             int64_t* counters, double* total_de, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Event decoding: the submission rows of resident network outputs (csrc/decode.hip).  Replaces
+ * gen_submission_list_task2_OLD (utility_functions.py:158-181) and gen_submission_list_task2
+ * (utility_functions.py:184-210), which train.py:110-116 calls on the prediction and on the target of
+ * every test recording, for a batch: sed (recordings, frames, n), doa (recordings, frames, 3n),
+ * n = classes * overlaps, both contiguous float32 (SELD_DECODE_F32) or both float64 (SELD_DECODE_F64).
+ * Slot j of a frame is class j / overlaps, event j % overlaps, coordinates doa[.., 3j : 3j + 3].  A slot
+ * is active when rint(sed) != 0 (half to even: 0.5 is off, 1.5 and -0.6 are on) and the frame's rounded
+ * activities do not sum to zero; that sum is exact in any order for |sed| < 2^18 and nothing is promised
+ * beyond.  Rows come out recording-major, frame-major, slot order:
+ *   rows[e]  = { frame, class, x, y, z } as doubles; float32 input: x = (double)(doa * (float)max_loc_value),
+ *              one float32 multiply then widened; float64 input: the multiply is in double
+ *   event[e] = j % overlaps (the fifth entry of the reference's per-frame dict)
+ *   rec_offsets[r] .. rec_offsets[r + 1] = the rows of recording r (recordings + 1 entries, CSR style)
+ * The row count depends on the data, so the work is two calls on one stream:
+ *   seld_decode_workspace  bytes of workspace both calls need (0 for a refused shape)
+ *   seld_decode_count      reads sed once; leaves the total row count E as an int64 in the first 8 bytes
+ *                          of the workspace (one device-to-host copy) and the frames' masks behind it
+ *   seld_decode_write      takes the SAME workspace, untouched since the count call on the same shape, and
+ *                          caller-allocated rows (capacity, 5), event (capacity), rec_offsets
+ *                          (recordings + 1); capacity >= E; rows beyond capacity are not written; rows and
+ *                          event may be NULL when capacity is 0.  Reads doa for active slots only.
+ * No atomics: two runs give the same bytes.  Non-positive sizes, an unknown dtype, a negative capacity
+ * and NULL pointers are SELD_EINVAL; classes * overlaps > 64 (one wave's ballot) or recordings * frames >=
+ * 2^31 are SELD_EUNSUPPORTED (overlaps itself is not limited: decoding has no association step); a missing
+ * or short workspace is SELD_EWORKSPACE.  A refused call launches nothing and writes nothing.
+ * The offsets are scanned by ONE workgroup in dependent tiles of 1024 chunks of 64 frames: 5 tiles for 500 x 600
+ * frames, 32768 serial tiles at the 2^31 - 1 frame limit, which is accepted but not what the scan is sized for.
+ * ------------------------------------------------------------------------------------------ */
+#define SELD_DECODE_F32 0
+#define SELD_DECODE_F64 1
+size_t seld_decode_workspace(int64_t recordings, int32_t frames, int32_t classes, int32_t overlaps);
+int seld_decode_count(const void* sed, int32_t dtype, int64_t recordings, int32_t frames, int32_t classes,
+                      int32_t overlaps, void* workspace, size_t workspace_bytes, void* stream);
+int seld_decode_write(const void* doa, int32_t dtype, int64_t recordings, int32_t frames, int32_t classes,
+                      int32_t overlaps, double max_loc_value, const void* workspace, size_t workspace_bytes,
+                      double* rows, int32_t* event, int64_t capacity, int64_t* rec_offsets, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

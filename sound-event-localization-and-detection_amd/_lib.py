@@ -18,6 +18,7 @@ SELD_ACT_NONE, SELD_ACT_RELU, SELD_ACT_TANH, SELD_ACT_SIGMOID = 0, 1, 2, 3
 SELD_LIN_REAL, SELD_LIN_QUAT, SELD_LIN_DUALQ = 1, 4, 8
 SELD_ROT_LAYOUT_CONV, SELD_ROT_LAYOUT_LINEAR = 0, 1
 SELD_QUAT_LAYOUT_INPUT, SELD_QUAT_LAYOUT_CAT1 = 0, 1
+SELD_DECODE_F32, SELD_DECODE_F64 = 0, 1
 
 
 class SeldHipError(RuntimeError):
@@ -69,6 +70,11 @@ def lib():
         _lib.seld_dwconv_bwd_weight_workspace.restype = ctypes.c_size_t
         _lib.seld_stft_workspace.restype = ctypes.c_size_t
         _lib.seld_quat_reduce_workspace.restype = ctypes.c_size_t
+        _lib.seld_decode_workspace.restype = ctypes.c_size_t
+        _lib.seld_decode_workspace.argtypes = [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]
+        i32, i64, vp = ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p
+        _lib.seld_decode_count.argtypes = [vp, i32, i64, i32, i32, i32, vp, ctypes.c_size_t, vp]
+        _lib.seld_decode_write.argtypes = [vp, i32, i64, i32, i32, i32, ctypes.c_double, vp, ctypes.c_size_t, vp, vp, i64, vp, vp]
     return _lib
 
 

@@ -2753,6 +2753,60 @@ def metrics_accumulate(acc, sed, doa, target, num_frames, num_classes=14, max_ov
     return acc
 
 
+def decode_events(sed, doa, max_loc_value=2., num_classes=14, max_overlaps=3):
+    """The submission rows of resident network outputs (utility_functions.py:158-210; csrc/decode.hip).
+
+    sed (T, n) or (R, T, n), doa (T, 3n) or (R, T, 3n), n = num_classes * max_overlaps <= 64: device tensors, both
+    float32 or both float64 (a non-contiguous one is copied).  Returns, on the device,
+      rows (E, 5) float64 [frame, class, x, y, z], recording-major, frame-major, slot order;
+      event (E,) int32, the slot's index inside its class;
+      rec_offsets (R + 1,) int64: rows[rec_offsets[r]:rec_offsets[r + 1]] belong to recording r.
+    Two launches with one device-to-host read (the row count E) between them."""
+    for t, name in ((sed, "sed"), (doa, "doa")):
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise L.SeldHipError(f"decode_events: {name}: expected a HIP device tensor (this package has no CPU path)")
+    if sed.dtype != doa.dtype or sed.dtype not in (torch.float32, torch.float64):
+        raise L.SeldHipError(f"decode_events: sed / doa must both be float32 or both float64, got {sed.dtype} / {doa.dtype}")
+    if sed.device != doa.device:
+        raise L.SeldHipError(f"decode_events: sed is on {sed.device}, doa on {doa.device}")
+    num_classes, max_overlaps = int(num_classes), int(max_overlaps)
+    n = num_classes * max_overlaps
+    if num_classes <= 0 or max_overlaps <= 0 or n > 64:
+        raise L.SeldHipError(f"decode_events: num_classes * max_overlaps = {num_classes} * {max_overlaps} is outside 1..64 "
+                             "(one wave's ballot)")
+    if sed.dim() not in (2, 3) or doa.dim() != sed.dim():
+        raise L.SeldHipError(f"decode_events: expected (T, n) or (R, T, n) tensors, got {tuple(sed.shape)} / {tuple(doa.shape)}")
+    if sed.dim() == 2:
+        sed, doa = sed[None], doa[None]
+    R, T = sed.shape[0], sed.shape[1]
+    if tuple(sed.shape) != (R, T, n) or tuple(doa.shape) != (R, T, 3 * n):
+        raise L.SeldHipError(f"decode_events: shapes {tuple(sed.shape)} / {tuple(doa.shape)} do not match "
+                             f"(recordings, frames, {n}) / (.., {3 * n})")
+    dev = sed.device
+    if R == 0 or T == 0:
+        return (torch.empty((0, 5), device=dev, dtype=torch.float64), torch.empty(0, device=dev, dtype=torch.int32),
+                torch.zeros(R + 1, device=dev, dtype=torch.int64))
+    sed, doa = sed.contiguous(), doa.contiguous()
+    lib = L.lib()
+    dtype = L.SELD_DECODE_F32 if sed.dtype == torch.float32 else L.SELD_DECODE_F64
+    nbytes = lib.seld_decode_workspace(R, T, num_classes, max_overlaps)
+    if nbytes == 0:
+        raise L.SeldHipError(f"decode_events: {R} x {T} frames is more than the decode kernels index (2^31 - 1)")
+    ws = torch.empty(nbytes // 8, device=dev, dtype=torch.int64)
+    with torch.cuda.device(dev):
+        L.check(lib.seld_decode_count(L.ptr(sed), dtype, ctypes.c_int64(R), T, num_classes, max_overlaps, L.ptr(ws),
+                                      ctypes.c_size_t(nbytes), L.current_stream()), "seld_decode_count")
+        total = int(ws[0].item())                       # the one read-back: the outputs' size depends on the data
+        rows = torch.empty((total, 5), device=dev, dtype=torch.float64)
+        event = torch.empty(total, device=dev, dtype=torch.int32)
+        rec_offsets = torch.empty(R + 1, device=dev, dtype=torch.int64)
+        L.check(lib.seld_decode_write(L.ptr(doa), dtype, ctypes.c_int64(R), T, num_classes, max_overlaps,
+                                      ctypes.c_double(max_loc_value), L.ptr(ws), ctypes.c_size_t(nbytes), L.ptr(rows),
+                                      L.ptr(event), ctypes.c_int64(total), L.ptr(rec_offsets), L.current_stream()),
+                "seld_decode_write")
+    return rows, event, rec_offsets
+
+
 _identity_cache = {}
 
 

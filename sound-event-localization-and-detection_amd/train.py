@@ -691,6 +691,24 @@ def evaluate_test(model, device, dataloader, epoch=0, max_loc_value=2., num_fram
     return results
 
 
+def predict_test(model, device, dataloader, max_loc_value=2., num_frames=600):
+    """The prediction half of evaluate_test (train.py:100-111): the model under no_grad exactly as there, every batch
+    decoded on the device (hip_ops.decode_events, with gen_submission_list_task2's default of 14 classes as the
+    reference's call has it), and one (E_i, 5) float64 array of [frame, class, x, y, z] rows per recording, in loader
+    order.  `num_frames` is accepted and ignored, as gen_submission_list_task2 does."""
+    model.eval()
+    out = []
+    with torch.no_grad():
+        for x, _ in dataloader:
+            sed, doa = model(x.to(device))
+            if sed.shape[-1] % 14:
+                raise H.L.SeldHipError(f"predict_test: {sed.shape[-1]} activity outputs are not 14 classes x overlaps")
+            rows, _, offsets = H.decode_events(sed, doa, max_loc_value, 14, sed.shape[-1] // 14)
+            rows, offsets = rows.cpu().numpy(), offsets.cpu().tolist()
+            out.extend(rows[a:b] for a, b in zip(offsets[:-1], offsets[1:]))
+    return out
+
+
 def evaluate(model, device, criterion_sed, criterion_doa, loader, args):
     """Mean loss over a loader, no grad (train.py:168-183)."""
     model.eval()

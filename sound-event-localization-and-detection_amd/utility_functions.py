@@ -1,9 +1,11 @@
-"""Drop-in for the part of the reference's utility_functions.py that is on the hot path: `spectrum_fast`
-(utility_functions.py:129-155, called at model.py:562), the STFT magnitude / phase feature extractor.
+"""Drop-in for the parts of the reference's utility_functions.py that are on the hot path: `spectrum_fast`
+(utility_functions.py:129-155, called at model.py:562), the STFT magnitude / phase feature extractor, and
+`gen_submission_list_task2` / `gen_submission_list_task2_OLD` (utility_functions.py:158-210, called at train.py:110-116),
+which turn the network's outputs into the challenge's submission rows.
 
-Same name, same arguments, same result layout.  The transform runs on the GPU (csrc/stft.hip, csrc/stft_any.hip through
-seld_stft_magphase_ws) for every segment length 2 <= nperseg <= 4096; there is no CPU path -- a missing device or
-library raises.
+Same names, same arguments, same result layout.  The transform runs on the GPU (csrc/stft.hip, csrc/stft_any.hip through
+seld_stft_magphase_ws) for every segment length 2 <= nperseg <= 4096, the decoding through csrc/decode.hip
+(hip_ops.decode_events); there is no CPU path -- a missing device or library raises.
 """
 import ctypes
 
@@ -11,6 +13,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from . import hip_ops as H
 
 
 MAX_NPERSEG = 4096        # longest segment the device transforms (one workgroup's LDS)
@@ -102,3 +105,72 @@ def spectrum_fast(x, nperseg=512, noverlap=128, window='hamming', cut_dc=True, o
     if is_numpy:
         return out.cpu().numpy().astype(out_dtype)
     return out
+
+
+def _decode_one(sed, doa, max_loc_value, num_classes, max_overlaps):
+    """(rows, event) of one recording as numpy arrays, one read-back each.
+
+    The reference rounds `sed` in sed's dtype and multiplies `doa` in doa's, so doa decides the arithmetic: float32 stays
+    float32 (one float32 multiply, widened), every other real dtype is computed in float64.  `sed` is brought to that
+    dtype where the conversion cannot move a rounding: float32 or integer sed with float64 doa, integer / bool sed with
+    float32 doa (exact below 2^24).  float64 sed with float32 doa is refused, since narrowing can carry a value across
+    a tie; float16 is refused as well."""
+    def as_array(a, name):
+        if torch.is_tensor(a):
+            return a
+        a = np.asarray(a)
+        if a.dtype.kind not in "fiub" or a.dtype == np.float16:
+            raise L.SeldHipError(f"gen_submission_list_task2: {name}: unsupported dtype {a.dtype}")
+        return a
+    sed, doa = as_array(sed, "sed"), as_array(doa, "doa")
+    if torch.is_tensor(sed) != torch.is_tensor(doa):
+        raise L.SeldHipError("gen_submission_list_task2: sed and doa must both be numpy arrays or both device tensors")
+    if not torch.is_tensor(sed):
+        if doa.dtype != np.float32:
+            doa = doa.astype(np.float64)
+        if sed.dtype != doa.dtype:
+            if sed.dtype == np.float64:
+                raise L.SeldHipError("gen_submission_list_task2: float64 sed with float32 doa is not supported "
+                                     "(narrowing sed can move a value across a rounding tie); pass doa as float64")
+            sed = sed.astype(doa.dtype)
+        if not torch.cuda.is_available():
+            raise L.SeldHipError("gen_submission_list_task2: no HIP device (this package has no CPU path)")
+        dev = torch.device("cuda", torch.cuda.current_device())
+        sed = torch.from_numpy(np.ascontiguousarray(sed)).to(dev)
+        doa = torch.from_numpy(np.ascontiguousarray(doa)).to(dev)
+    elif sed.dtype == torch.float32 and doa.dtype == torch.float64:
+        sed = sed.double()
+    if sed.dim() != 2:
+        raise L.SeldHipError(f"gen_submission_list_task2: expected one recording (T, n), got shape {tuple(sed.shape)}")
+    rows, event, _ = H.decode_events(sed, doa, max_loc_value, num_classes, max_overlaps)
+    return rows.cpu().numpy(), event.cpu().numpy()
+
+
+def gen_submission_list_task2_OLD(sed, doa, max_loc_value=2., num_frames=600, num_classes=14, max_overlaps=3):
+    '''
+    Process sed and doa output matrices (model's output) and generate the list of active sounds and their location for
+    every frame, in the format of the Challenge results submission -- utility_functions.py:158-181.
+
+    sed (T, num_classes * max_overlaps), doa (T, 3 * num_classes * max_overlaps): numpy arrays or device tensors.
+    doa's dtype decides the arithmetic as in the reference (float32, else float64); sed may differ from it except
+    float64 sed with float32 doa, which is refused.
+    Returns the float64 array of [time_frame, sound_class, x, y, z] rows, frame-major and in slot order; without any
+    active slot the reference's `np.array([])`, shape (0,).  `num_frames` is accepted and ignored, as in the reference.
+    '''
+    rows, _ = _decode_one(sed, doa, max_loc_value, num_classes, max_overlaps)
+    return rows if rows.shape[0] else np.array([])
+
+
+def gen_submission_list_task2(sed, doa, max_loc_value=2., num_frames=600, num_classes=14, max_overlaps=3):
+    '''
+    utility_functions.py:184-210: the rows of gen_submission_list_task2_OLD and the dictionary
+    {time_frame: [[sound_class, x, y, z, num_event], ...]} the DCASE21 metrics read, with Python int / float entries
+    and the frames in order of first appearance.  The dictionary is host work by nature; it is built from one
+    read-back of the rows and the event indices.
+    '''
+    rows, event = _decode_one(sed, doa, max_loc_value, num_classes, max_overlaps)
+    output_dict = {}
+    cols = [rows[:, k].tolist() for k in range(5)]
+    for f, c, x, y, z, e in zip(cols[0], cols[1], cols[2], cols[3], cols[4], event.tolist()):
+        output_dict.setdefault(int(f), []).append([int(c), x, y, z, e])
+    return (rows if rows.shape[0] else np.array([])), output_dict
