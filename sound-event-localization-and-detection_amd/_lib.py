@@ -62,15 +62,16 @@ def lib():
                 "This package has no CPU/eager fallback by design.")
         _lib = ctypes.CDLL(LIB_PATH)
         _lib.seld_build_arch.restype = ctypes.c_char_p
-        _lib.seld_hc_conv_bwd_weight_workspace.restype = ctypes.c_size_t
-        _lib.seld_hcq_wgrad_group_workspace.restype = ctypes.c_size_t
-        _lib.seld_hc_conv_transpose_bwd_weight_workspace.restype = ctypes.c_size_t
-        _lib.seld_hc_conv3d_bwd_weight_workspace.restype = ctypes.c_size_t
-        _lib.seld_hc_conv3d_transpose_bwd_weight_workspace.restype = ctypes.c_size_t
-        _lib.seld_dwconv_bwd_weight_workspace.restype = ctypes.c_size_t
-        _lib.seld_stft_workspace.restype = ctypes.c_size_t
-        _lib.seld_quat_reduce_workspace.restype = ctypes.c_size_t
-        _lib.seld_decode_workspace.restype = ctypes.c_size_t
+        # every query that returns a size_t: without its restype ctypes truncates the answer to a C int
+        for name in ("seld_hc_conv_bwd_data_workspace", "seld_hc_conv_bwd_weight_workspace",
+                     "seld_hc_conv_bwd_weight_det_workspace", "seld_hcq_pack_floats", "seld_hcq_pack_entry_bytes",
+                     "seld_hcq_wgrad_row_workspace", "seld_hcq_wgrad_group_workspace",
+                     "seld_hc_conv_transpose_bwd_weight_workspace", "seld_hc_conv3d_bwd_weight_workspace",
+                     "seld_hc_conv3d_transpose_bwd_weight_workspace", "seld_dwconv_bwd_weight_workspace",
+                     "seld_first_stage_gram_workspace", "seld_first_stage_bwd_workspace", "seld_hc_linear_bwd_workspace",
+                     "seld_mha_bwd_workspace", "seld_mha_bwd_ex_workspace", "seld_stft_workspace",
+                     "seld_quat_reduce_workspace", "seld_decode_workspace"):
+            getattr(_lib, name).restype = ctypes.c_size_t
         _lib.seld_decode_workspace.argtypes = [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]
         i32, i64, vp = ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p
         _lib.seld_decode_count.argtypes = [vp, i32, i64, i32, i32, i32, vp, ctypes.c_size_t, vp]
@@ -83,7 +84,7 @@ _reload_hooks = []
 
 def reload_env():
     """Make the library re-read its SELD_* environment switches (it reads them once, at first use); host-side caches
-    of kernel choices (hip_ops) are dropped with it."""
+    of kernel choices (hip_ops._core.memo) are dropped with it."""
     check(lib().seld_env_reload(), "seld_env_reload")
     for fn in _reload_hooks:
         fn()

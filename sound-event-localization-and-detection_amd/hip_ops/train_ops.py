@@ -1,0 +1,223 @@
+"""Around the network in a training step: loss, Adam, the step state, STFT, dataset normalisation, metrics, decoding."""
+import ctypes
+
+import torch
+
+from .. import _lib as L
+from ._core import _req
+
+
+# ======================================================================================
+# loss, Adam, STFT
+# ======================================================================================
+class SeldLossFn(torch.autograd.Function):
+    """BCELoss(sed, t_sed) * w_sed + MSELoss(doa, t_doa) * w_doa  (train.py:186-204)."""
+
+    @staticmethod
+    def forward(ctx, sed, doa, target, w_sed, w_doa):
+        sed2 = _req(sed.reshape(-1, sed.shape[-1]), "sed")
+        doa2 = _req(doa.reshape(-1, doa.shape[-1]), "doa")
+        tgt = _req(target.reshape(-1, target.shape[-1]), "target")
+        rows, n_sed = sed2.shape
+        n_doa = doa2.shape[1]
+        loss = torch.empty(1, device=sed.device, dtype=torch.float32)       # written, not accumulated (ticketed reduction)
+        dsed, ddoa = torch.empty_like(sed2), torch.empty_like(doa2)
+        L.check(L.lib().seld_loss_fwd_bwd(L.ptr(sed2), L.ptr(doa2), L.ptr(tgt), ctypes.c_int64(rows), n_sed, n_doa,
+                                          ctypes.c_float(w_sed), ctypes.c_float(w_doa), L.ptr(loss), L.ptr(dsed),
+                                          L.ptr(ddoa), L.current_stream()), "seld_loss_fwd_bwd")
+        ctx.shapes = (tuple(sed.shape), tuple(doa.shape))
+        ctx.save_for_backward(dsed, ddoa)
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        dsed, ddoa = ctx.saved_tensors
+        s1, s2 = ctx.shapes
+        if g.data_ptr() == unit_gradient(g.device).data_ptr():       # backward_from_loss(): d loss / d loss = 1
+            return dsed.reshape(s1), ddoa.reshape(s2), None, None, None
+        return (dsed * g).reshape(s1), (ddoa * g).reshape(s2), None, None, None
+
+
+_unit_gradients = {}
+
+
+def unit_gradient(device):
+    """The constant 1.0 the training step seeds the backward pass with: one cached tensor per device, so neither the
+    autograd engine (ones_like -> fill) nor SeldLossFn.backward (gradient * 1.0) launches a kernel for it."""
+    device = torch.device(device)
+    t = _unit_gradients.get(device)
+    if t is None:
+        t = _unit_gradients[device] = torch.ones((), device=device, dtype=torch.float32)
+    return t
+
+
+def backward_from_loss(loss):
+    """loss.backward() seeded with the cached unit gradient."""
+    loss.backward(unit_gradient(loss.device))
+
+
+def seld_loss(sed, doa, target, w_sed=1.0, w_doa=5.0):
+    return SeldLossFn.apply(sed, doa, target, float(w_sed), float(w_doa))
+
+
+def adam_flat_step(param, grad, exp_avg, exp_avg_sq, step, lr=1e-4, beta1=0.9, beta2=0.999, eps=1e-8,
+                   weight_decay=0.0, grad_scale=1.0):
+    L.check(L.lib().seld_adam_flat(L.ptr(param), L.ptr(grad), L.ptr(exp_avg), L.ptr(exp_avg_sq),
+                                   ctypes.c_int64(param.numel()), ctypes.c_float(lr), ctypes.c_float(beta1),
+                                   ctypes.c_float(beta2), ctypes.c_float(eps), ctypes.c_float(weight_decay), int(step),
+                                   ctypes.c_float(grad_scale), L.current_stream()), "seld_adam_flat")
+
+
+def step_begin(flat_grad, state=None):
+    """Zero the flat gradient buffer and (state given) advance the device-resident step state (seld_step_begin)."""
+    L.check(L.lib().seld_step_begin(L.ptr(flat_grad), ctypes.c_int64(flat_grad.numel()), L.ptr(state), L.current_stream()),
+            "seld_step_begin")
+
+
+def adam_flat_step_state(param, grad, exp_avg, exp_avg_sq, state, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0,
+                         grad_scale=1.0):
+    """seld_adam_flat with the step number and learning rate taken from the device-resident step state."""
+    L.check(L.lib().seld_adam_flat_state(L.ptr(param), L.ptr(grad), L.ptr(exp_avg), L.ptr(exp_avg_sq),
+                                         ctypes.c_int64(param.numel()), ctypes.c_float(beta1), ctypes.c_float(beta2),
+                                         ctypes.c_float(eps), ctypes.c_float(weight_decay), ctypes.c_float(grad_scale),
+                                         L.ptr(state), L.current_stream()), "seld_adam_flat_state")
+
+
+def stft_magphase(x, nperseg=512, noverlap=128, output_phase=True):
+    """x: (C, L) float32 device tensor -> (C or 2C, nperseg/2, frames) (utility_functions.py:129-155)."""
+    x = _req(x, "x")
+    C, Ln = x.shape
+    frames = L.lib().seld_stft_frames(Ln, nperseg, noverlap)
+    if frames <= 0:
+        raise L.SeldHipError("seld_stft_frames: invalid segment parameters")
+    from ..utility_functions import MAX_NPERSEG, stft_workspace
+    if nperseg > MAX_NPERSEG:
+        raise L.SeldHipError(f"stft_magphase: nperseg={nperseg} is longer than the longest segment the HIP STFT "
+                             f"transforms ({MAX_NPERSEG})")
+    out = torch.empty(((2 if output_phase else 1) * C, nperseg // 2, frames), device=x.device, dtype=torch.float32)
+    ws = stft_workspace(nperseg, x.device)
+    L.check(L.lib().seld_stft_magphase_ws(L.ptr(x), C, Ln, nperseg, noverlap, int(bool(output_phase)), 1, 1, None,
+                                          L.ptr(out), L.ptr(ws), ctypes.c_size_t(0 if ws is None else ws.numel()),
+                                          L.current_stream()), "seld_stft_magphase_ws")
+    return out
+
+
+
+def _req_inplace(x, name, min_channels=1):
+    if not x.is_cuda:
+        raise L.SeldHipError(f"{name}: expected a HIP device tensor (this package has no CPU path)")
+    if x.dtype != torch.float32 or not x.is_contiguous() or x.dim() < 2:
+        raise L.SeldHipError(f"{name}: expected a contiguous float32 (items, channels, ...) tensor, got {x.dtype} "
+                             f"{tuple(x.shape)} contiguous={x.is_contiguous()}")
+    if x.shape[1] < min_channels:
+        raise L.SeldHipError(f"{name}: needs at least {min_channels} channels, got {x.shape[1]}")
+    items, channels = x.shape[0], x.shape[1]
+    hw = x.numel() // max(1, items * channels)
+    return items, channels, hw
+
+
+def dq_unit_norm_(x):
+    """In place: channels 0..7 of every (item, f, t) position become a unit dual quaternion
+    (train.py:257-275).  x: (items, >=8, F, T) float32 on the device."""
+    items, channels, hw = _req_inplace(x, "dq_unit_norm_", 8)
+    L.check(L.lib().seld_dq_unit_norm(L.ptr(x), ctypes.c_int64(items), channels, ctypes.c_int64(hw), L.current_stream()),
+            "seld_dq_unit_norm")
+    return x
+
+
+def group_standardize_(x, c0, c1):
+    """In place: x[:, c0:c1] <- (x[:, c0:c1] - mean) / std with one scalar mean / population std over the
+    whole group (train.py:345-349).  Returns a 2-element device tensor (mean, std) as applied."""
+    items, channels, hw = _req_inplace(x, "group_standardize_")
+    c0, c1 = int(c0), min(int(c1), channels)        # a numpy slice clips at the channel count
+    work = torch.empty(3, device=x.device, dtype=torch.float64)
+    mean_std = torch.empty(2, device=x.device, dtype=torch.float32)
+    L.check(L.lib().seld_group_standardize(L.ptr(x), ctypes.c_int64(items), channels, c0, c1, ctypes.c_int64(hw), L.ptr(work),
+                                           L.ptr(mean_std), L.current_stream()), "seld_group_standardize")
+    return mean_std
+
+
+
+METRIC_COUNTERS = ("TP", "FP", "FN", "dc_TP", "dc_FP", "dc_FN", "dc_S", "dc_D", "dc_I", "dc_Nref", "dc_DE_TP", "dc_DE_FP",
+                   "dc_DE_FN")
+
+
+def metrics_new(device):
+    """Zeroed accumulators for `metrics_accumulate`: (13 int64 counters, 1 double)."""
+    return (torch.zeros(len(METRIC_COUNTERS), device=device, dtype=torch.int64),
+            torch.zeros(1, device=device, dtype=torch.float64))
+
+
+def metrics_accumulate(acc, sed, doa, target, num_frames, num_classes=14, max_overlaps=3, max_loc_value=2.0,
+                       spatial_threshold=2.0, doa_threshold=20, frames_per_block=10):
+    """Decode + L3DAS21 / DCASE21 counters of a batch of recordings (train.py:100-126), added to `acc`."""
+    sed, doa, target = _req(sed, "sed"), _req(doa, "doa"), _req(target, "target")
+    n = num_classes * max_overlaps
+    if sed.dim() == 2:
+        sed, doa, target = sed[None], doa[None], target[None]
+    clips, frames = sed.shape[0], sed.shape[1]
+    if tuple(sed.shape) != (clips, frames, n) or tuple(doa.shape) != (clips, frames, 3 * n) or \
+            tuple(target.shape) != (clips, frames, 4 * n):
+        raise L.SeldHipError(f"metrics_accumulate: shapes {tuple(sed.shape)} / {tuple(doa.shape)} / {tuple(target.shape)} do not "
+                             f"match (clips, frames, {n}) / (.., {3 * n}) / (.., {4 * n})")
+    counters, total_de = acc
+    L.check(L.lib().seld_metrics_accumulate(L.ptr(sed), L.ptr(doa), L.ptr(target), clips, frames, int(num_frames),
+                                            int(num_classes), int(max_overlaps), ctypes.c_float(max_loc_value),
+                                            ctypes.c_double(spatial_threshold), ctypes.c_double(doa_threshold),
+                                            int(frames_per_block), L.ptr(counters), L.ptr(total_de), L.current_stream()),
+            "seld_metrics_accumulate")
+    return acc
+
+
+def decode_events(sed, doa, max_loc_value=2., num_classes=14, max_overlaps=3):
+    """The submission rows of resident network outputs (utility_functions.py:158-210; csrc/decode.hip).
+
+    sed (T, n) or (R, T, n), doa (T, 3n) or (R, T, 3n), n = num_classes * max_overlaps <= 64: device tensors, both
+    float32 or both float64 (a non-contiguous one is copied).  Returns, on the device,
+      rows (E, 5) float64 [frame, class, x, y, z], recording-major, frame-major, slot order;
+      event (E,) int32, the slot's index inside its class;
+      rec_offsets (R + 1,) int64: rows[rec_offsets[r]:rec_offsets[r + 1]] belong to recording r.
+    Two launches with one device-to-host read (the row count E) between them."""
+    for t, name in ((sed, "sed"), (doa, "doa")):
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise L.SeldHipError(f"decode_events: {name}: expected a HIP device tensor (this package has no CPU path)")
+    if sed.dtype != doa.dtype or sed.dtype not in (torch.float32, torch.float64):
+        raise L.SeldHipError(f"decode_events: sed / doa must both be float32 or both float64, got {sed.dtype} / {doa.dtype}")
+    if sed.device != doa.device:
+        raise L.SeldHipError(f"decode_events: sed is on {sed.device}, doa on {doa.device}")
+    num_classes, max_overlaps = int(num_classes), int(max_overlaps)
+    n = num_classes * max_overlaps
+    if num_classes <= 0 or max_overlaps <= 0 or n > 64:
+        raise L.SeldHipError(f"decode_events: num_classes * max_overlaps = {num_classes} * {max_overlaps} is outside 1..64 "
+                             "(one wave's ballot)")
+    if sed.dim() not in (2, 3) or doa.dim() != sed.dim():
+        raise L.SeldHipError(f"decode_events: expected (T, n) or (R, T, n) tensors, got {tuple(sed.shape)} / {tuple(doa.shape)}")
+    if sed.dim() == 2:
+        sed, doa = sed[None], doa[None]
+    R, T = sed.shape[0], sed.shape[1]
+    if tuple(sed.shape) != (R, T, n) or tuple(doa.shape) != (R, T, 3 * n):
+        raise L.SeldHipError(f"decode_events: shapes {tuple(sed.shape)} / {tuple(doa.shape)} do not match "
+                             f"(recordings, frames, {n}) / (.., {3 * n})")
+    dev = sed.device
+    if R == 0 or T == 0:
+        return (torch.empty((0, 5), device=dev, dtype=torch.float64), torch.empty(0, device=dev, dtype=torch.int32),
+                torch.zeros(R + 1, device=dev, dtype=torch.int64))
+    sed, doa = sed.contiguous(), doa.contiguous()
+    lib = L.lib()
+    dtype = L.SELD_DECODE_F32 if sed.dtype == torch.float32 else L.SELD_DECODE_F64
+    nbytes = lib.seld_decode_workspace(R, T, num_classes, max_overlaps)
+    if nbytes == 0:
+        raise L.SeldHipError(f"decode_events: {R} x {T} frames is more than the decode kernels index (2^31 - 1)")
+    ws = torch.empty(nbytes // 8, device=dev, dtype=torch.int64)
+    with torch.cuda.device(dev):
+        L.check(lib.seld_decode_count(L.ptr(sed), dtype, ctypes.c_int64(R), T, num_classes, max_overlaps, L.ptr(ws),
+                                      ctypes.c_size_t(nbytes), L.current_stream()), "seld_decode_count")
+        total = int(ws[0].item())                       # the one read-back: the outputs' size depends on the data
+        rows = torch.empty((total, 5), device=dev, dtype=torch.float64)
+        event = torch.empty(total, device=dev, dtype=torch.int32)
+        rec_offsets = torch.empty(R + 1, device=dev, dtype=torch.int64)
+        L.check(lib.seld_decode_write(L.ptr(doa), dtype, ctypes.c_int64(R), T, num_classes, max_overlaps,
+                                      ctypes.c_double(max_loc_value), L.ptr(ws), ctypes.c_size_t(nbytes), L.ptr(rows),
+                                      L.ptr(event), ctypes.c_int64(total), L.ptr(rec_offsets), L.current_stream()),
+                "seld_decode_write")
+    return rows, event, rec_offsets

@@ -529,7 +529,7 @@ def test_hcq_wgrad_row_matches_block_matrix_kernels(shape, cout, k, pad, dil, se
     H.hcq_wgrad_acc(desc, x, dyA, new[0])
     H.hcq_wgrad_acc(desc, x, dyA, new[1], dyB, new[2])
     H.hcq_wgrad_acc(desc, x, dyA, new[0])                       # accumulates; the scratch came back zeroed
-    for ws in H._wgrad_row_scratch.values():
+    for ws in H._scratch_pools["wgrad_row"].values():
         assert float(ws.abs().max()) == 0.0
     seld_env.set("SELD_CONV_NO_HCQ", "1")
     assert H._hcq_wgrad_row_bytes(desc) == 0
