@@ -2,13 +2,19 @@
 
 There is deliberately NO fallback: if the shared library is missing or a launch fails the
 call raises.  The library is built in-tree by `__graft_entry__.build()` (hipcc, gfx950).
+
+The header is the one place a signature is written down: `lib()` reads it and sets `restype` and `argtypes` on every
+entry point, so callers pass plain Python numbers and ctypes gives each its declared width (`int64_t`, `size_t`,
+`float` against `double`).  A prototype the parser cannot type, or the library does not export, is an error at load.
 """
 import ctypes
 import os
+import re
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # SELD_HIP_LIB: another build of the same library (tools/hcq_ablate.sh timing variants); there is still no fallback
 LIB_PATH = os.environ.get("SELD_HIP_LIB") or os.path.join(_HERE, "csrc", "libseld_hip.so")
+HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "seld_hip.h")      # csrc/common.h includes it by the same path
 
 SELD_OK = 0
 _ERRORS = {-1: "SELD_EINVAL", -2: "SELD_EWORKSPACE", -3: "SELD_ELAUNCH", -4: "SELD_EUNSUPPORTED"}
@@ -49,33 +55,59 @@ class WgradJob(ctypes.Structure):
     _fields_ = [("desc", ConvDesc), ("x", ctypes.c_void_p), ("dy", ctypes.c_void_p), ("dw", ctypes.c_void_p * 8)]
 
 
+_C_TYPES = {"int32_t": ctypes.c_int32, "int": ctypes.c_int32, "int64_t": ctypes.c_int64, "long long": ctypes.c_int64,
+            "uint64_t": ctypes.c_uint64, "size_t": ctypes.c_size_t, "float": ctypes.c_float, "double": ctypes.c_double}
+_C_RETURNS = {"int": ctypes.c_int, "size_t": ctypes.c_size_t, "const char*": ctypes.c_char_p}
+_PROTOTYPE = re.compile(r"^([^\n;{}()]*?)\b(seld_\w+)\s*\(([^()]*)\)\s*;", re.M)
+
+
+def prototypes(header):
+    """{name: (restype, argtypes)} of every `<ret> seld_name(<params>);` in the text of include/seld_hip.h.  Anything
+    with `*` or `[` travels as a pointer; a by-value type outside the closed map above raises, naming the function."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", header, flags=re.S)
+    text = re.sub(r"^[ \t]*#.*$", "", text, flags=re.M)
+    out = {}
+    for ret, name, params in _PROTOTYPE.findall(text):
+        ret = re.sub(r"\s*\*", "*", " ".join(ret.split()))
+        if ret not in _C_RETURNS:
+            raise SeldHipError(f"seld_hip.h: {name} returns `{ret}`, which the binding does not know")
+        argtypes = []
+        for par in ([] if params.strip() in ("", "void") else params.split(",")):
+            ctype = " ".join(par.replace("const ", " ").split()[:-1])      # the last word is the parameter's name
+            if "*" in par or "[" in par:
+                argtypes.append(ctypes.c_void_p)
+            elif ctype in _C_TYPES:
+                argtypes.append(_C_TYPES[ctype])
+            else:
+                raise SeldHipError(f"seld_hip.h: {name} has the parameter `{par.strip()}`, which the binding does not know")
+        out[name] = (_C_RETURNS[ret], argtypes)
+    unread = sorted(set(re.findall(r"\b(seld_\w+)\s*\(", text)) - set(out))
+    if unread:      # e.g. a return type on a line of its own: never left untyped
+        raise SeldHipError(f"seld_hip.h: the binding cannot read the prototype of {', '.join(unread)}")
+    return out
+
+
 _lib = None
 
 
 def lib():
-    """Load (once) and return the ctypes handle.  Raises if the HIP library is not built."""
+    """Load (once) and return the ctypes handle, every entry point declared with the restype and argtypes that
+    include/seld_hip.h gives it.  Raises if the HIP library is not built or lacks a declared entry point."""
     global _lib
     if _lib is None:
         if not os.path.exists(LIB_PATH):
             raise SeldHipError(
                 f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'`. "
                 "This package has no CPU/eager fallback by design.")
-        _lib = ctypes.CDLL(LIB_PATH)
-        _lib.seld_build_arch.restype = ctypes.c_char_p
-        # every query that returns a size_t: without its restype ctypes truncates the answer to a C int
-        for name in ("seld_hc_conv_bwd_data_workspace", "seld_hc_conv_bwd_weight_workspace",
-                     "seld_hc_conv_bwd_weight_det_workspace", "seld_hcq_pack_floats", "seld_hcq_pack_entry_bytes",
-                     "seld_hcq_wgrad_row_workspace", "seld_hcq_wgrad_group_workspace",
-                     "seld_hc_conv_transpose_bwd_weight_workspace", "seld_hc_conv3d_bwd_weight_workspace",
-                     "seld_hc_conv3d_transpose_bwd_weight_workspace", "seld_dwconv_bwd_weight_workspace",
-                     "seld_first_stage_gram_workspace", "seld_first_stage_bwd_workspace", "seld_hc_linear_bwd_workspace",
-                     "seld_mha_bwd_workspace", "seld_mha_bwd_ex_workspace", "seld_stft_workspace",
-                     "seld_quat_reduce_workspace", "seld_decode_workspace"):
-            getattr(_lib, name).restype = ctypes.c_size_t
-        _lib.seld_decode_workspace.argtypes = [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]
-        i32, i64, vp = ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p
-        _lib.seld_decode_count.argtypes = [vp, i32, i64, i32, i32, i32, vp, ctypes.c_size_t, vp]
-        _lib.seld_decode_write.argtypes = [vp, i32, i64, i32, i32, i32, ctypes.c_double, vp, ctypes.c_size_t, vp, vp, i64, vp, vp]
+        handle = ctypes.CDLL(LIB_PATH)
+        with open(HEADER_PATH) as f:
+            declared = prototypes(f.read())
+        for name, (restype, argtypes) in declared.items():
+            fn = getattr(handle, name, None)
+            if fn is None:
+                raise SeldHipError(f"{LIB_PATH} does not export {name}, which {HEADER_PATH} declares")
+            fn.restype, fn.argtypes = restype, argtypes
+        _lib = handle
     return _lib
 
 

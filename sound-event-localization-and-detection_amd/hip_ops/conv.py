@@ -96,7 +96,7 @@ def conv_fwd(desc, x, ws, bias=None, out=None, epilogue=0, addend=None, stats=No
         return y
     with _timed(desc, 0):
         L.check(L.lib().seld_hc_conv_fwd_ex(ctypes.byref(desc), L.ptr(x), L.ptr_array8(ws), L.ptr(bias), L.ptr(y),
-                                            ctypes.c_int32(epilogue), L.ptr(_req(addend, "addend")), L.ptr(stats),
+                                            epilogue, L.ptr(_req(addend, "addend")), L.ptr(stats),
                                             L.current_stream()), "seld_hc_conv_fwd")
     return y
 
@@ -123,7 +123,7 @@ def conv_bwd_data(desc, dy, ws, x_shape, ahead=None):
     wsb = torch.empty((nbytes + 3) // 4, device=dy.device, dtype=torch.float32)
     with _timed(desc, 1):
         L.check(lib.seld_hc_conv_bwd_data_ex(ctypes.byref(desc), L.ptr(dy), L.ptr_array8(ws), L.ptr(dx), L.ptr(wsb),
-                                             ctypes.c_size_t(nbytes), L.current_stream()), "seld_hc_conv_bwd_data")
+                                             nbytes, L.current_stream()), "seld_hc_conv_bwd_data")
     return dx
 
 
@@ -165,7 +165,7 @@ def hcq_wgrad_acc(desc, x, dyA, dwA, dyB=None, dwB=None):
         with _timed(desc, 2, npair, label=lambda: _hcq_wgrad_row_label(desc, npair)):
             L.check(L.lib().seld_hcq_wgrad_row_acc(ctypes.byref(desc), npair, L.ptr(x), L.ptr(dyA), L.ptr(dyB),
                                                    L.ptr_array8(dwA), L.ptr_array8(dwB) if dwB is not None else None,
-                                                   L.ptr(ws), ctypes.c_size_t(ws.numel() * 4), L.current_stream()),
+                                                   L.ptr(ws), ws.numel() * 4, L.current_stream()),
                     "seld_hcq_wgrad_row_acc")
         return
     with _timed(desc, 2, npair, label=lambda: _hcq_wgrad_label(desc, npair)):
@@ -201,7 +201,7 @@ def wgrad_group(jobs):
         return False
     dev = jobs[0][1].device
     ws = scratch("wgrad_group", nbytes, dev)
-    L.check(L.lib().seld_hcq_wgrad_group(arr, len(arr), L.ptr(ws), ctypes.c_size_t(ws.numel()), L.current_stream()),
+    L.check(L.lib().seld_hcq_wgrad_group(arr, len(arr), L.ptr(ws), ws.numel(), L.current_stream()),
             "seld_hcq_wgrad_group")
     return True
 
@@ -293,8 +293,8 @@ def conv_bwd_weight(desc, x, dy, w_shape, want_bias, into=None, bias_into=None):
         dws = into if into is not None else [torch.zeros(w_shape, device=x.device, dtype=torch.float32) for _ in range(desc.algebra)]
         dbias = bias_into if bias_into is not None else (torch.zeros(desc.Cout, device=x.device, dtype=torch.float32) if want_bias else None)
         with _timed(desc, 2):
-            L.check(lib.seld_hc_conv_bwd_weight_det(ctypes.byref(desc), L.ptr(x), L.ptr(dy), L.ptr_array8(dws), L.ptr(dbias),
-                                                    L.ptr(wsb), ctypes.c_size_t(wsb.numel()), L.current_stream()),
+            L.check(lib.seld_hc_conv_bwd_weight_det(ctypes.byref(desc), L.ptr(x), L.ptr(dy), L.ptr_array8(dws),
+                                                    L.ptr(dbias), L.ptr(wsb), wsb.numel(), L.current_stream()),
                     "seld_hc_conv_bwd_weight_det")
         return (None, None) if into is not None else (dws, dbias)
     if not want_bias and bias_into is None and _hcq_wgrad_ok(desc):
@@ -313,8 +313,8 @@ def conv_bwd_weight(desc, x, dy, w_shape, want_bias, into=None, bias_into=None):
     dws = [torch.empty(w_shape, device=x.device, dtype=torch.float32) for _ in range(desc.algebra)]
     dbias = torch.empty(desc.Cout, device=x.device, dtype=torch.float32) if want_bias else None
     with _timed(desc, 2):
-        L.check(L.lib().seld_hc_conv_bwd_weight(ctypes.byref(desc), L.ptr(x), L.ptr(dy), L.ptr_array8(dws), L.ptr(dbias),
-                                                None, ctypes.c_size_t(0), L.current_stream()),
+        L.check(L.lib().seld_hc_conv_bwd_weight(ctypes.byref(desc), L.ptr(x), L.ptr(dy), L.ptr_array8(dws),
+                                                L.ptr(dbias), None, 0, L.current_stream()),
                 "seld_hc_conv_bwd_weight")
     return dws, dbias
 
@@ -437,8 +437,8 @@ def _transpose_ahead(desc, ws):
     ev0.record(torch.cuda.current_stream())
     st.wait_event(ev0)                                   # the weights may still be in flight (Adam of the last step)
     with torch.cuda.stream(st):
-        L.check(lib.seld_hc_conv_transpose_weights(ctypes.byref(desc), L.ptr_array8([_req(w, "w") for w in ws]), L.ptr(wt),
-                                                   ctypes.c_size_t(nbytes), L.current_stream()),
+        L.check(lib.seld_hc_conv_transpose_weights(ctypes.byref(desc), L.ptr_array8([_req(w, "w") for w in ws]),
+                                                   L.ptr(wt), nbytes, L.current_stream()),
                 "seld_hc_conv_transpose_weights")
         ev = torch.cuda.Event()
         ev.record(st)
@@ -700,7 +700,7 @@ class FanOut2Fn(torch.autograd.Function):
             return ga if gb is None else gb
         ga, gb = _req(ga, "ga"), _req(gb, "gb")
         out = torch.empty_like(ga)
-        L.check(L.lib().seld_add(L.ptr(ga), L.ptr(gb), ctypes.c_int64(ga.numel()), L.ptr(out), L.current_stream()), "seld_add")
+        L.check(L.lib().seld_add(L.ptr(ga), L.ptr(gb), ga.numel(), L.ptr(out), L.current_stream()), "seld_add")
         return out
 
 
@@ -821,8 +821,8 @@ class HyperConvPairFn(torch.autograd.Function):
                 rc = L.lib().seld_hc_conv_pair_fwd(
                     ctypes.byref(desc), L.ptr(x), L.ptr_array8([_req(w, "w") for w in wsA]),
                     L.ptr_array8([_req(w, "w") for w in wsB]), L.ptr(_req(biasA, "bias")), L.ptr(_req(biasB, "bias")),
-                    L.ptr(yA), L.ptr(yB), ctypes.c_int32(epiA), ctypes.c_int32(epiB), L.ptr(_req(addA, "addend")),
-                    L.ptr(_req(addB, "addend")), L.ptr(kstA), L.ptr(kstB), L.current_stream())
+                    L.ptr(yA), L.ptr(yB), epiA, epiB, L.ptr(_req(addA, "addend")), L.ptr(_req(addB, "addend")),
+                    L.ptr(kstA), L.ptr(kstB), L.current_stream())
             if rc == -4:       # SELD_EUNSUPPORTED: e.g. the two weight sets lie more than 4 GB apart
                 conv_fwd(desc, x, wsA, biasA, out=yA, epilogue=epiA, addend=addA, stats=kstA)
                 conv_fwd(desc, x, wsB, biasB, out=yB, epilogue=epiB, addend=addB, stats=kstB)
@@ -872,7 +872,7 @@ class HyperConvPairFn(torch.autograd.Function):
                 with _timed(desc, 1, 2):
                     L.check(lib.seld_hc_conv_pair_bwd_data(ctypes.byref(desc), L.ptr(dyA), L.ptr(dyB),
                                                            L.ptr_array8(list(wsA)), L.ptr_array8(list(wsB)), L.ptr(dx),
-                                                           L.ptr(wsb), ctypes.c_size_t(nbytes), L.current_stream()),
+                                                           L.ptr(wsb), nbytes, L.current_stream()),
                             "seld_hc_conv_pair_bwd_data")
             else:
                 dx = conv_bwd_data(desc, dyA, wsA, tuple(x.shape))

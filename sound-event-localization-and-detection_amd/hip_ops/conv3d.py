@@ -117,12 +117,12 @@ def conv3d_bwd_weight_acc(desc, out_pad, x, dy, dws, dbias=None):
     with _timed(desc, out_pad, 2):
         if out_pad is None:
             L.check(lib.seld_hc_conv3d_bwd_weight_acc(ctypes.byref(desc), L.ptr(x), L.ptr(dy), L.ptr_array8(dws),
-                                                      L.ptr(dbias), L.ptr(wsb), ctypes.c_size_t(nbytes),
+                                                      L.ptr(dbias), L.ptr(wsb), nbytes,
                                                       L.current_stream()), "seld_hc_conv3d_bwd_weight_acc")
         else:
             L.check(lib.seld_hc_conv3d_transpose_bwd_weight_acc(ctypes.byref(desc), out_pad, L.ptr(x), L.ptr(dy),
-                                                                L.ptr_array8(dws), L.ptr(dbias), L.ptr(wsb),
-                                                                ctypes.c_size_t(nbytes), L.current_stream()),
+                                                                L.ptr_array8(dws), L.ptr(dbias), L.ptr(wsb), nbytes,
+                                                                L.current_stream()),
                     "seld_hc_conv3d_transpose_bwd_weight_acc")
 
 

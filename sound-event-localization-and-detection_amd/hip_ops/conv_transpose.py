@@ -78,8 +78,8 @@ def conv_transpose_bwd_weight_acc(desc, out_pad, x, dy, dws, dbias=None):
     wsb = torch.empty(nbytes, device=x.device, dtype=torch.uint8) if nbytes else None
     with _timed(desc, out_pad, 2):
         L.check(lib.seld_hc_conv_transpose_bwd_weight_acc(ctypes.byref(desc), out_pad, L.ptr(x), L.ptr(dy),
-                                                          L.ptr_array8(dws), L.ptr(dbias), L.ptr(wsb),
-                                                          ctypes.c_size_t(nbytes), L.current_stream()),
+                                                          L.ptr_array8(dws), L.ptr(dbias), L.ptr(wsb), nbytes,
+                                                          L.current_stream()),
                 "seld_hc_conv_transpose_bwd_weight_acc")
 
 

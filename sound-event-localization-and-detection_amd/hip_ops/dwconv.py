@@ -73,7 +73,7 @@ def dwconv_bwd_weight_acc(desc, x, dy, dw, dbias=None):
     ws = scratch("dwconv", nbytes, x.device)         # the weight-gradient partials (fully rewritten per call)
     with _timed(desc, 2):
         L.check(lib.seld_dwconv_bwd_weight_acc(ctypes.byref(desc), L.ptr(x), L.ptr(dy), L.ptr(dw), L.ptr(dbias),
-                                               L.ptr(ws), ctypes.c_size_t(ws.numel()), L.current_stream()),
+                                               L.ptr(ws), ws.numel(), L.current_stream()),
                 "seld_dwconv_bwd_weight_acc")
 
 

@@ -65,9 +65,9 @@ class BnReluPoolFn(torch.autograd.Function):
             seed, off, state = philox.draw((pooled.numel() + 3) // 4, y.device)
             out = torch.empty_like(pooled)
             ctx.rng = (p_, seed, off, state)
-        L.check(L.lib().seld_bn_relu_pool_fwd_drop(L.ptr(y), N, C, Hh, Ww, ph, pw, L.ptr(mean), L.ptr(invstd), L.ptr(gamma),
-                                                   L.ptr(beta), L.ptr(pooled), L.ptr(idx), ctypes.c_float(p_),
-                                                   ctypes.c_uint64(seed), ctypes.c_uint64(off), L.ptr(state), L.ptr(out),
+        L.check(L.lib().seld_bn_relu_pool_fwd_drop(L.ptr(y), N, C, Hh, Ww, ph, pw, L.ptr(mean), L.ptr(invstd),
+                                                   L.ptr(gamma), L.ptr(beta), L.ptr(pooled), L.ptr(idx), p_, seed, off,
+                                                   L.ptr(state), L.ptr(out),
                                                    L.current_stream()), "seld_bn_relu_pool_fwd_drop")
         ctx.geom = (N, C, Hh, Ww, ph, pw, training)
         ctx.bn_params = (gamma, beta)
@@ -84,10 +84,10 @@ class BnReluPoolFn(torch.autograd.Function):
         red = slot if clean else torch.zeros(2 * C, device=y.device, dtype=torch.float32)
         dy = torch.empty_like(y)
         p_, seed, off, state = ctx.rng if ctx.rng is not None else (0.0, 0, 0, None)
-        L.check(L.lib().seld_bn_relu_pool_bwd_drop(L.ptr(dpooled), L.ptr(pooled), L.ptr(idx), L.ptr(y), N, C, Hh, Ww, ph, pw,
-                                                   L.ptr(mean), L.ptr(invstd), L.ptr(gamma), L.ptr(beta), int(training),
-                                                   L.ptr(red), L.ptr(dy), ctypes.c_float(p_), ctypes.c_uint64(seed),
-                                                   ctypes.c_uint64(off), L.ptr(state), L.current_stream()),
+        L.check(L.lib().seld_bn_relu_pool_bwd_drop(L.ptr(dpooled), L.ptr(pooled), L.ptr(idx), L.ptr(y), N, C, Hh, Ww,
+                                                   ph, pw, L.ptr(mean), L.ptr(invstd), L.ptr(gamma), L.ptr(beta),
+                                                   int(training), L.ptr(red), L.ptr(dy), p_, seed, off, L.ptr(state),
+                                                   L.current_stream()),
                 "seld_bn_relu_pool_bwd_drop")
         if slot is not None:
             if not clean:
@@ -138,7 +138,7 @@ class ConvBnReluPoolFn(torch.autograd.Function):
             fork.record(torch.cuda.current_stream())
             st.wait_event(fork)
             with torch.cuda.stream(st):
-                L.check(L.lib().seld_first_stage_gram(ctypes.byref(desc), L.ptr(x), L.ptr(gws), ctypes.c_size_t(gws.numel()),
+                L.check(L.lib().seld_first_stage_gram(ctypes.byref(desc), L.ptr(x), L.ptr(gws), gws.numel(),
                                                       L.current_stream()), "seld_first_stage_gram")
                 early = torch.cuda.Event()
                 early.record(st)
@@ -160,15 +160,15 @@ class ConvBnReluPoolFn(torch.autograd.Function):
             stage_timer.__enter__()
             if early is None:
                 gws = torch.empty(_fs_bytes(desc, "gram"), device=x.device, dtype=torch.uint8)
-                L.check(lib.seld_first_stage_gram(ctypes.byref(desc), L.ptr(x), L.ptr(gws), ctypes.c_size_t(gws.numel()),
+                L.check(lib.seld_first_stage_gram(ctypes.byref(desc), L.ptr(x), L.ptr(gws), gws.numel(),
                                                   L.current_stream()), "seld_first_stage_gram")
             mean = torch.empty(C, device=x.device, dtype=torch.float32)
             invstd = torch.empty(C, device=x.device, dtype=torch.float32)
             wg = torch.empty((C, 72), device=x.device, dtype=torch.float32)
-            L.check(lib.seld_first_stage_bn(ctypes.byref(desc), L.ptr_array8([_req(w, "w") for w in ws]), L.ptr(_req(bias, "bias")),
-                                            L.ptr(gws), ctypes.c_float(eps), ctypes.c_float(momentum), L.ptr(mean),
-                                            L.ptr(invstd), L.ptr(running_mean), L.ptr(running_var), L.ptr(nbt), L.ptr(wg),
-                                            L.current_stream()), "seld_first_stage_bn")
+            L.check(lib.seld_first_stage_bn(ctypes.byref(desc), L.ptr_array8([_req(w, "w") for w in ws]),
+                                            L.ptr(_req(bias, "bias")), L.ptr(gws), eps, momentum, L.ptr(mean),
+                                            L.ptr(invstd), L.ptr(running_mean), L.ptr(running_var), L.ptr(nbt),
+                                            L.ptr(wg), L.current_stream()), "seld_first_stage_bn")
             # raw: written (and read by the backward pass) only for channels with gamma == 0; untouched memory otherwise
             raw = torch.empty((N, C, Hh // ph, Ww), device=x.device, dtype=torch.float32)
             idx = torch.empty(raw.shape, device=x.device, dtype=torch.uint8)
@@ -178,9 +178,9 @@ class ConvBnReluPoolFn(torch.autograd.Function):
                 p_ = float(drop_p)
                 seed, off, state = philox.draw((raw.numel() + 3) // 4, x.device)
                 ctx.rng = (p_, seed, off, state)
-            L.check(lib.seld_hcq_first_pool_bn(ctypes.byref(desc), L.ptr(x), L.ptr(wp), L.ptr(_req(bias, "bias")), L.ptr(gamma),
-                                               L.ptr(beta), L.ptr(mean), L.ptr(invstd), ctypes.c_float(p_), ctypes.c_uint64(seed),
-                                               ctypes.c_uint64(off), L.ptr(state), L.ptr(raw), L.ptr(idx), L.ptr(result),
+            L.check(lib.seld_hcq_first_pool_bn(ctypes.byref(desc), L.ptr(x), L.ptr(wp), L.ptr(_req(bias, "bias")),
+                                               L.ptr(gamma), L.ptr(beta), L.ptr(mean), L.ptr(invstd), p_, seed, off,
+                                               L.ptr(state), L.ptr(raw), L.ptr(idx), L.ptr(result),
                                                L.current_stream()), "seld_hcq_first_pool_bn")
             stage_timer.__exit__(None, None, None)
             ctx.desc, ctx.geom = desc, (N, C, Hh, Ww, ph, training)
@@ -209,9 +209,9 @@ class ConvBnReluPoolFn(torch.autograd.Function):
                 seed, off, state = philox.draw((pooled.numel() + 3) // 4, x.device)
                 out = torch.empty_like(raw)
                 ctx.rng = (p_, seed, off, state)
-            L.check(L.lib().seld_bn_pool_finish(L.ptr(raw), N, C, (Hh // ph) * Ww, L.ptr(mean), L.ptr(invstd), L.ptr(gamma),
-                                                L.ptr(beta), L.ptr(pooled), ctypes.c_float(p_), ctypes.c_uint64(seed),
-                                                ctypes.c_uint64(off), L.ptr(state), L.ptr(out), L.current_stream()),
+            L.check(L.lib().seld_bn_pool_finish(L.ptr(raw), N, C, (Hh // ph) * Ww, L.ptr(mean), L.ptr(invstd),
+                                                L.ptr(gamma), L.ptr(beta), L.ptr(pooled), p_, seed, off, L.ptr(state),
+                                                L.ptr(out), L.current_stream()),
                     "seld_bn_pool_finish")
         else:
             y = conv_fwd(desc, x, ws, bias, epilogue=L.SELD_EPI_STATS if training else 0, stats=stats)
@@ -226,9 +226,8 @@ class ConvBnReluPoolFn(torch.autograd.Function):
             if drop_p > 0.0:
                 seed, off, state = philox.draw((pooled.numel() + 3) // 4, x.device)
                 out = torch.empty_like(pooled)
-                L.check(L.lib().seld_dropout_fwd(L.ptr(pooled), ctypes.c_int64(pooled.numel()), ctypes.c_float(drop_p),
-                                                 ctypes.c_uint64(seed), ctypes.c_uint64(off), L.ptr(state), L.ptr(out),
-                                                 L.current_stream()), "seld_dropout_fwd")
+                L.check(L.lib().seld_dropout_fwd(L.ptr(pooled), pooled.numel(), drop_p, seed, off, L.ptr(state),
+                                                 L.ptr(out), L.current_stream()), "seld_dropout_fwd")
                 ctx.rng = (float(drop_p), seed, off, state)
         ctx.desc, ctx.geom = desc, (N, C, Hh, Ww, ph, training)
         ctx.params = (ws, bias, gamma, beta)
@@ -245,7 +244,7 @@ class ConvBnReluPoolFn(torch.autograd.Function):
         dpooled = _req(dpooled, "dpooled")
         # ctx.rng: `dpooled` is the gradient BEHIND the stage's Dropout; both consumers replay its mask while they load it
         p_, seed, off, state = ctx.rng if ctx.rng is not None else (0.0, 0, 0, None)
-        drop = (ctypes.c_float(p_), ctypes.c_uint64(seed), ctypes.c_uint64(off), L.ptr(state))
+        drop = (p_, seed, off, L.ptr(state))
         direct = _direct_targets(ws, bias)
         if direct is None:
             raise L.SeldHipError("ConvBnReluPoolFn needs gradient slots (FlatAdam); use hyper_conv_stats + bn_relu_pool")
@@ -286,11 +285,11 @@ class ConvBnReluPoolFn(torch.autograd.Function):
         nbytes = _fs_bytes(ctx.desc, "bwd")
         wsb = torch.empty(nbytes, device=x.device, dtype=torch.uint8)
         with _timed(ctx.desc, 2, 1, label="fs_wgrad_kernel"):
-            L.check(L.lib().seld_first_stage_bwd(ctypes.byref(ctx.desc), L.ptr(x), L.ptr(dout), L.ptr(out), L.ptr(raw), L.ptr(idx),
-                                                 L.ptr(mean), L.ptr(invstd), L.ptr(gamma), L.ptr(beta), L.ptr(bias), L.ptr(gws),
-                                                 L.ptr(wg), L.ptr(red), ctypes.c_void_p(red.data_ptr() + 4 * C),
-                                                 L.ptr_array8(direct[0]), ctypes.c_float(p_), L.ptr(wsb),
-                                                 ctypes.c_size_t(nbytes), L.current_stream()),
+            L.check(L.lib().seld_first_stage_bwd(ctypes.byref(ctx.desc), L.ptr(x), L.ptr(dout), L.ptr(out), L.ptr(raw),
+                                                 L.ptr(idx), L.ptr(mean), L.ptr(invstd), L.ptr(gamma), L.ptr(beta),
+                                                 L.ptr(bias), L.ptr(gws), L.ptr(wg), L.ptr(red),
+                                                 ctypes.c_void_p(red.data_ptr() + 4 * C), L.ptr_array8(direct[0]), p_,
+                                                 L.ptr(wsb), nbytes, L.current_stream()),
                     "seld_first_stage_bwd")
         dg = db = None
         if slot is None:

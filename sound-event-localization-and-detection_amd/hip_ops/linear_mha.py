@@ -54,7 +54,7 @@ class HyperLinearFn(torch.autograd.Function):
         wsb = torch.empty((nbytes + 3) // 4, device=dev, dtype=torch.float32)
         L.check(L.lib().seld_hc_linear_bwd(kind, rows, in_f, out_f, L.ptr(x2), L.ptr(dy2), L.ptr_array8(ws), L.ptr(dx),
                                            L.ptr_array8(dws) if dws is not None else None, L.ptr(dbias), L.ptr(wsb),
-                                           ctypes.c_size_t(nbytes), L.current_stream()), "seld_hc_linear_bwd")
+                                           nbytes, L.current_stream()), "seld_hc_linear_bwd")
         dxr = dx.reshape(xshape) if dx is not None else None
         if direct:
             return (dxr, None, None, *([None] * len(ws)))
@@ -94,7 +94,7 @@ class MhaCoreFn(torch.autograd.Function):
         nbytes = lib.seld_mha_bwd_workspace(N, T, H)
         wsb = torch.empty((nbytes + 3) // 4, device=q.device, dtype=torch.float32)
         L.check(lib.seld_mha_bwd(L.ptr(q), L.ptr(k), L.ptr(v), L.ptr(out), L.ptr(dout), L.ptr(lse), N, T, H, hd,
-                                 L.ptr(dq), L.ptr(dk), L.ptr(dv), L.ptr(wsb), ctypes.c_size_t(nbytes),
+                                 L.ptr(dq), L.ptr(dk), L.ptr(dv), L.ptr(wsb), nbytes,
                                  L.current_stream()), "seld_mha_bwd")
         return dq, dk, dv, None
 
@@ -169,8 +169,8 @@ class MhaMaskedFn(torch.autograd.Function):
         nbytes = lib.seld_mha_bwd_ex_workspace(N, Tq, H)
         wsb = torch.empty((nbytes + 3) // 4, device=q.device, dtype=torch.float32)
         L.check(lib.seld_mha_bwd_ex(L.ptr(q), L.ptr(k), L.ptr(v), L.ptr(out), L.ptr(dout), L.ptr(lse), N, Tq, Tk, H, hd,
-                                    L.ptr(keep), ctx.strides, L.ptr(dq), L.ptr(dk), L.ptr(dv), L.ptr(wsb),
-                                    ctypes.c_size_t(nbytes), L.current_stream()), "seld_mha_bwd_ex")
+                                    L.ptr(keep), ctx.strides, L.ptr(dq), L.ptr(dk), L.ptr(dv), L.ptr(wsb), nbytes,
+                                    L.current_stream()), "seld_mha_bwd_ex")
         return dq, dk, dv, None, None
 
 
@@ -207,7 +207,7 @@ class MhaPackedFn(torch.autograd.Function):
         nbytes = lib.seld_mha_bwd_workspace(N, T, H)
         wsb = torch.empty((nbytes + 3) // 4, device=qkv.device, dtype=torch.float32)
         L.check(lib.seld_mha_bwd_packed(L.ptr(qkv), L.ptr(out), L.ptr(dout), L.ptr(lse), N, T, H, hd, L.ptr(dqkv),
-                                        L.ptr(wsb), ctypes.c_size_t(nbytes), L.current_stream()), "seld_mha_bwd_packed")
+                                        L.ptr(wsb), nbytes, L.current_stream()), "seld_mha_bwd_packed")
         return dqkv, None
 
 

@@ -1,6 +1,5 @@
 """BatchNorm + activation, the gate, activations, pooling, dropout and transposes (csrc/nn_ops.hip), and the optimiser's
 gradient slots as the backward kernels' targets."""
-import ctypes
 import os
 
 import torch
@@ -55,15 +54,14 @@ def bn_prepare(x, running_mean, running_var, training, momentum, eps, stats=None
         if stats is None:
             stats = channel_stats(x)
         pooled = getattr(stats, "_seld_pooled", False)
-        L.check(L.lib().seld_bn_finalize_ex(L.ptr(stats), C, ctypes.c_int64(N * S), ctypes.c_float(eps),
-                                            ctypes.c_float(momentum), L.ptr(mean), L.ptr(invstd), L.ptr(running_mean),
-                                            L.ptr(running_var), L.ptr(num_batches_tracked), int(pooled),
-                                            L.current_stream()), "seld_bn_finalize_ex")
+        L.check(L.lib().seld_bn_finalize_ex(L.ptr(stats), C, N * S, eps, momentum, L.ptr(mean), L.ptr(invstd),
+                                            L.ptr(running_mean), L.ptr(running_var), L.ptr(num_batches_tracked),
+                                            int(pooled), L.current_stream()), "seld_bn_finalize_ex")
         if pooled:      # per stream: the buffer is re-zeroed by a kernel on THIS stream and may only be reused in order behind it
             _stats_pool.setdefault((C, x.device, torch.cuda.current_stream(x.device).cuda_stream), []).append(stats)
     else:
-        L.check(L.lib().seld_bn_eval_stats(L.ptr(running_mean), L.ptr(running_var), C, ctypes.c_float(eps),
-                                           L.ptr(mean), L.ptr(invstd), L.current_stream()), "seld_bn_eval_stats")
+        L.check(L.lib().seld_bn_eval_stats(L.ptr(running_mean), L.ptr(running_var), C, eps, L.ptr(mean), L.ptr(invstd),
+                                           L.current_stream()), "seld_bn_eval_stats")
     return mean, invstd
 
 
@@ -115,7 +113,7 @@ def _direct_targets(params, bias):
 
 def axpy_(dst_first, src, n):
     """dst[0:n] += src[0:n] where dst_first is the first of several tensors that are adjacent in one flat buffer."""
-    L.check(L.lib().seld_accumulate(L.ptr(dst_first), L.ptr(src), ctypes.c_int64(n), L.current_stream()), "seld_accumulate")
+    L.check(L.lib().seld_accumulate(L.ptr(dst_first), L.ptr(src), n, L.current_stream()), "seld_accumulate")
 
 
 def _one_pass_ok(N, S, limit):
@@ -208,10 +206,10 @@ class GateFn(torch.autograd.Function):
                 and getattr(stats_g, "_seld_pooled", False)):
             # both layers' statistics are ready (the pair convolution gathered them): one finalize launch for the two
             mf, isf, mg, isg = (torch.empty(C, device=yf.device, dtype=torch.float32) for _ in range(4))
-            L.check(L.lib().seld_bn_finalize2_ex(L.ptr(stats_f), L.ptr(stats_g), C, ctypes.c_int64(N * S), ctypes.c_float(eps),
-                                                 ctypes.c_float(momentum), L.ptr(mf), L.ptr(isf), L.ptr(rmf), L.ptr(rvf),
-                                                 L.ptr(nbt_f), L.ptr(mg), L.ptr(isg), L.ptr(rmg), L.ptr(rvg), L.ptr(nbt_g),
-                                                 1, L.current_stream()), "seld_bn_finalize2_ex")
+            L.check(L.lib().seld_bn_finalize2_ex(L.ptr(stats_f), L.ptr(stats_g), C, N * S, eps, momentum, L.ptr(mf),
+                                                 L.ptr(isf), L.ptr(rmf), L.ptr(rvf), L.ptr(nbt_f), L.ptr(mg),
+                                                 L.ptr(isg), L.ptr(rmg), L.ptr(rvg), L.ptr(nbt_g), 1,
+                                                 L.current_stream()), "seld_bn_finalize2_ex")
             key = (C, yf.device, torch.cuda.current_stream(yf.device).cuda_stream)
             _stats_pool.setdefault(key, []).extend((stats_f, stats_g))
         else:
@@ -278,7 +276,7 @@ class ActFn(torch.autograd.Function):
     def forward(ctx, x, act):
         x = _req(x, "x")
         y = torch.empty_like(x)
-        L.check(L.lib().seld_act_fwd(L.ptr(x), ctypes.c_int64(x.numel()), act, L.ptr(y), L.current_stream()), "seld_act_fwd")
+        L.check(L.lib().seld_act_fwd(L.ptr(x), x.numel(), act, L.ptr(y), L.current_stream()), "seld_act_fwd")
         ctx.act = act
         ctx.save_for_backward(y)
         return y
@@ -288,7 +286,7 @@ class ActFn(torch.autograd.Function):
         (y,) = ctx.saved_tensors
         dy = _req(dy, "dy")
         dx = torch.empty_like(y)
-        L.check(L.lib().seld_act_bwd(L.ptr(dy), L.ptr(y), ctypes.c_int64(y.numel()), ctx.act, L.ptr(dx),
+        L.check(L.lib().seld_act_bwd(L.ptr(dy), L.ptr(y), y.numel(), ctx.act, L.ptr(dx),
                                      L.current_stream()), "seld_act_bwd")
         return dx, None
 
@@ -311,7 +309,7 @@ class MaxPoolFn(torch.autograd.Function):
             oshape = (N, C, H // ph, W // pw)
         y = torch.empty(oshape, device=x.device, dtype=torch.float32)
         idx = torch.empty(oshape, device=x.device, dtype=torch.uint8)
-        L.check(L.lib().seld_maxpool_fwd(L.ptr(x), ctypes.c_int64(N * C), H, W, ph, pw, L.ptr(y), L.ptr(idx),
+        L.check(L.lib().seld_maxpool_fwd(L.ptr(x), N * C, H, W, ph, pw, L.ptr(y), L.ptr(idx),
                                          L.current_stream()), "seld_maxpool_fwd")
         ctx.geom = (N * C, H, W, ph, pw, tuple(x.shape))
         ctx.save_for_backward(idx)
@@ -323,7 +321,7 @@ class MaxPoolFn(torch.autograd.Function):
         NC, H, W, ph, pw, xshape = ctx.geom
         dy = _req(dy, "dy")
         dx = torch.empty(xshape, device=dy.device, dtype=torch.float32)
-        L.check(L.lib().seld_maxpool_bwd(L.ptr(dy), L.ptr(idx), ctypes.c_int64(NC), H, W, ph, pw, L.ptr(dx),
+        L.check(L.lib().seld_maxpool_bwd(L.ptr(dy), L.ptr(idx), NC, H, W, ph, pw, L.ptr(dx),
                                          L.current_stream()), "seld_maxpool_bwd")
         return dx, None, None
 
@@ -388,8 +386,7 @@ class DropoutFn(torch.autograd.Function):
         n = x.numel()
         seed, off, state = philox.draw((n + 3) // 4, x.device)
         y = torch.empty_like(x)
-        L.check(L.lib().seld_dropout_fwd(L.ptr(x), ctypes.c_int64(n), ctypes.c_float(p), ctypes.c_uint64(seed),
-                                         ctypes.c_uint64(off), L.ptr(state), L.ptr(y), L.current_stream()),
+        L.check(L.lib().seld_dropout_fwd(L.ptr(x), n, p, seed, off, L.ptr(state), L.ptr(y), L.current_stream()),
                 "seld_dropout_fwd")
         ctx.rng = (p, seed, off, state)
         return y
@@ -399,8 +396,7 @@ class DropoutFn(torch.autograd.Function):
         p, seed, off, state = ctx.rng
         dy = _req(dy, "dy")
         dx = torch.empty_like(dy)
-        L.check(L.lib().seld_dropout_fwd(L.ptr(dy), ctypes.c_int64(dy.numel()), ctypes.c_float(p),
-                                         ctypes.c_uint64(seed), ctypes.c_uint64(off), L.ptr(state), L.ptr(dx),
+        L.check(L.lib().seld_dropout_fwd(L.ptr(dy), dy.numel(), p, seed, off, L.ptr(state), L.ptr(dx),
                                          L.current_stream()), "seld_dropout_fwd")
         return dx, None
 
@@ -416,8 +412,7 @@ def channel_dropout_mask(N, C, p, device):
     rows = N * C
     seed, off, state = philox.draw((rows + 3) // 4, device)
     mask = torch.empty(rows, device=device, dtype=torch.float32)
-    L.check(L.lib().seld_dropout_mask_rows(ctypes.c_int64(rows), ctypes.c_float(p), ctypes.c_uint64(seed),
-                                           ctypes.c_uint64(off), L.ptr(state), L.ptr(mask), L.current_stream()),
+    L.check(L.lib().seld_dropout_mask_rows(rows, p, seed, off, L.ptr(state), L.ptr(mask), L.current_stream()),
             "seld_dropout_mask_rows")
     return mask
 

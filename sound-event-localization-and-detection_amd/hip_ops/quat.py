@@ -59,8 +59,8 @@ def _quat_ws(qs, device):
 def _quat_modulus_sum(qs, x):
     y = torch.empty(_quat_summed_shape(x), device=x.device, dtype=torch.float32)
     ws = _quat_ws(qs, x.device)
-    L.check(L.lib().seld_quat_modulus_sum_fwd(ctypes.byref(qs), L.ptr(x), L.ptr(y), L.ptr(ws),
-                                              ctypes.c_size_t(ws.numel()), L.current_stream()),
+    L.check(L.lib().seld_quat_modulus_sum_fwd(ctypes.byref(qs), L.ptr(x), L.ptr(y), L.ptr(ws), ws.numel(),
+                                              L.current_stream()),
             "seld_quat_modulus_sum_fwd")
     return y
 
@@ -111,7 +111,7 @@ class QuatNormalizedFn(torch.autograd.Function):
         qs = quat_shape(x)
         mod = _quat_modulus_sum(qs, x)
         y = torch.empty_like(x)
-        L.check(L.lib().seld_quat_normalized_fwd(ctypes.byref(qs), L.ptr(x), L.ptr(mod), ctypes.c_float(eps), L.ptr(y),
+        L.check(L.lib().seld_quat_normalized_fwd(ctypes.byref(qs), L.ptr(x), L.ptr(mod), eps, L.ptr(y),
                                                  L.current_stream()), "seld_quat_normalized_fwd")
         ctx.save_for_backward(x, mod)
         ctx.qs, ctx.eps = qs, eps
@@ -123,9 +123,8 @@ class QuatNormalizedFn(torch.autograd.Function):
         x, mod = ctx.saved_tensors
         dx = torch.empty_like(x)
         ws = _quat_ws(ctx.qs, x.device)
-        L.check(L.lib().seld_quat_normalized_bwd(ctypes.byref(ctx.qs), L.ptr(x), L.ptr(mod), L.ptr(dy),
-                                                 ctypes.c_float(ctx.eps), L.ptr(dx), L.ptr(ws),
-                                                 ctypes.c_size_t(ws.numel()), L.current_stream()),
+        L.check(L.lib().seld_quat_normalized_bwd(ctypes.byref(ctx.qs), L.ptr(x), L.ptr(mod), L.ptr(dy), ctx.eps,
+                                                 L.ptr(dx), L.ptr(ws), ws.numel(), L.current_stream()),
                 "seld_quat_normalized_bwd")
         return dx, None
 

@@ -1,5 +1,4 @@
 """Around the network in a training step: loss, Adam, the step state, STFT, dataset normalisation, metrics, decoding."""
-import ctypes
 
 import torch
 
@@ -22,9 +21,9 @@ class SeldLossFn(torch.autograd.Function):
         n_doa = doa2.shape[1]
         loss = torch.empty(1, device=sed.device, dtype=torch.float32)       # written, not accumulated (ticketed reduction)
         dsed, ddoa = torch.empty_like(sed2), torch.empty_like(doa2)
-        L.check(L.lib().seld_loss_fwd_bwd(L.ptr(sed2), L.ptr(doa2), L.ptr(tgt), ctypes.c_int64(rows), n_sed, n_doa,
-                                          ctypes.c_float(w_sed), ctypes.c_float(w_doa), L.ptr(loss), L.ptr(dsed),
-                                          L.ptr(ddoa), L.current_stream()), "seld_loss_fwd_bwd")
+        L.check(L.lib().seld_loss_fwd_bwd(L.ptr(sed2), L.ptr(doa2), L.ptr(tgt), rows, n_sed, n_doa, w_sed, w_doa,
+                                          L.ptr(loss), L.ptr(dsed), L.ptr(ddoa),
+                                          L.current_stream()), "seld_loss_fwd_bwd")
         ctx.shapes = (tuple(sed.shape), tuple(doa.shape))
         ctx.save_for_backward(dsed, ddoa)
         return loss.reshape(())
@@ -62,25 +61,23 @@ def seld_loss(sed, doa, target, w_sed=1.0, w_doa=5.0):
 
 def adam_flat_step(param, grad, exp_avg, exp_avg_sq, step, lr=1e-4, beta1=0.9, beta2=0.999, eps=1e-8,
                    weight_decay=0.0, grad_scale=1.0):
-    L.check(L.lib().seld_adam_flat(L.ptr(param), L.ptr(grad), L.ptr(exp_avg), L.ptr(exp_avg_sq),
-                                   ctypes.c_int64(param.numel()), ctypes.c_float(lr), ctypes.c_float(beta1),
-                                   ctypes.c_float(beta2), ctypes.c_float(eps), ctypes.c_float(weight_decay), int(step),
-                                   ctypes.c_float(grad_scale), L.current_stream()), "seld_adam_flat")
+    L.check(L.lib().seld_adam_flat(L.ptr(param), L.ptr(grad), L.ptr(exp_avg), L.ptr(exp_avg_sq), param.numel(), lr,
+                                   beta1, beta2, eps, weight_decay, int(step), grad_scale,
+                                   L.current_stream()), "seld_adam_flat")
 
 
 def step_begin(flat_grad, state=None):
     """Zero the flat gradient buffer and (state given) advance the device-resident step state (seld_step_begin)."""
-    L.check(L.lib().seld_step_begin(L.ptr(flat_grad), ctypes.c_int64(flat_grad.numel()), L.ptr(state), L.current_stream()),
+    L.check(L.lib().seld_step_begin(L.ptr(flat_grad), flat_grad.numel(), L.ptr(state), L.current_stream()),
             "seld_step_begin")
 
 
 def adam_flat_step_state(param, grad, exp_avg, exp_avg_sq, state, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0,
                          grad_scale=1.0):
     """seld_adam_flat with the step number and learning rate taken from the device-resident step state."""
-    L.check(L.lib().seld_adam_flat_state(L.ptr(param), L.ptr(grad), L.ptr(exp_avg), L.ptr(exp_avg_sq),
-                                         ctypes.c_int64(param.numel()), ctypes.c_float(beta1), ctypes.c_float(beta2),
-                                         ctypes.c_float(eps), ctypes.c_float(weight_decay), ctypes.c_float(grad_scale),
-                                         L.ptr(state), L.current_stream()), "seld_adam_flat_state")
+    L.check(L.lib().seld_adam_flat_state(L.ptr(param), L.ptr(grad), L.ptr(exp_avg), L.ptr(exp_avg_sq), param.numel(),
+                                         beta1, beta2, eps, weight_decay, grad_scale, L.ptr(state),
+                                         L.current_stream()), "seld_adam_flat_state")
 
 
 def stft_magphase(x, nperseg=512, noverlap=128, output_phase=True):
@@ -97,7 +94,7 @@ def stft_magphase(x, nperseg=512, noverlap=128, output_phase=True):
     out = torch.empty(((2 if output_phase else 1) * C, nperseg // 2, frames), device=x.device, dtype=torch.float32)
     ws = stft_workspace(nperseg, x.device)
     L.check(L.lib().seld_stft_magphase_ws(L.ptr(x), C, Ln, nperseg, noverlap, int(bool(output_phase)), 1, 1, None,
-                                          L.ptr(out), L.ptr(ws), ctypes.c_size_t(0 if ws is None else ws.numel()),
+                                          L.ptr(out), L.ptr(ws), 0 if ws is None else ws.numel(),
                                           L.current_stream()), "seld_stft_magphase_ws")
     return out
 
@@ -120,7 +117,7 @@ def dq_unit_norm_(x):
     """In place: channels 0..7 of every (item, f, t) position become a unit dual quaternion
     (train.py:257-275).  x: (items, >=8, F, T) float32 on the device."""
     items, channels, hw = _req_inplace(x, "dq_unit_norm_", 8)
-    L.check(L.lib().seld_dq_unit_norm(L.ptr(x), ctypes.c_int64(items), channels, ctypes.c_int64(hw), L.current_stream()),
+    L.check(L.lib().seld_dq_unit_norm(L.ptr(x), items, channels, hw, L.current_stream()),
             "seld_dq_unit_norm")
     return x
 
@@ -132,8 +129,8 @@ def group_standardize_(x, c0, c1):
     c0, c1 = int(c0), min(int(c1), channels)        # a numpy slice clips at the channel count
     work = torch.empty(3, device=x.device, dtype=torch.float64)
     mean_std = torch.empty(2, device=x.device, dtype=torch.float32)
-    L.check(L.lib().seld_group_standardize(L.ptr(x), ctypes.c_int64(items), channels, c0, c1, ctypes.c_int64(hw), L.ptr(work),
-                                           L.ptr(mean_std), L.current_stream()), "seld_group_standardize")
+    L.check(L.lib().seld_group_standardize(L.ptr(x), items, channels, c0, c1, hw, L.ptr(work), L.ptr(mean_std),
+                                           L.current_stream()), "seld_group_standardize")
     return mean_std
 
 
@@ -162,9 +159,9 @@ def metrics_accumulate(acc, sed, doa, target, num_frames, num_classes=14, max_ov
                              f"match (clips, frames, {n}) / (.., {3 * n}) / (.., {4 * n})")
     counters, total_de = acc
     L.check(L.lib().seld_metrics_accumulate(L.ptr(sed), L.ptr(doa), L.ptr(target), clips, frames, int(num_frames),
-                                            int(num_classes), int(max_overlaps), ctypes.c_float(max_loc_value),
-                                            ctypes.c_double(spatial_threshold), ctypes.c_double(doa_threshold),
-                                            int(frames_per_block), L.ptr(counters), L.ptr(total_de), L.current_stream()),
+                                            int(num_classes), int(max_overlaps), max_loc_value, spatial_threshold,
+                                            doa_threshold, int(frames_per_block), L.ptr(counters), L.ptr(total_de),
+                                            L.current_stream()),
             "seld_metrics_accumulate")
     return acc
 
@@ -210,14 +207,13 @@ def decode_events(sed, doa, max_loc_value=2., num_classes=14, max_overlaps=3):
         raise L.SeldHipError(f"decode_events: {R} x {T} frames is more than the decode kernels index (2^31 - 1)")
     ws = torch.empty(nbytes // 8, device=dev, dtype=torch.int64)
     with torch.cuda.device(dev):
-        L.check(lib.seld_decode_count(L.ptr(sed), dtype, ctypes.c_int64(R), T, num_classes, max_overlaps, L.ptr(ws),
-                                      ctypes.c_size_t(nbytes), L.current_stream()), "seld_decode_count")
+        L.check(lib.seld_decode_count(L.ptr(sed), dtype, R, T, num_classes, max_overlaps, L.ptr(ws), nbytes,
+                                      L.current_stream()), "seld_decode_count")
         total = int(ws[0].item())                       # the one read-back: the outputs' size depends on the data
         rows = torch.empty((total, 5), device=dev, dtype=torch.float64)
         event = torch.empty(total, device=dev, dtype=torch.int32)
         rec_offsets = torch.empty(R + 1, device=dev, dtype=torch.int64)
-        L.check(lib.seld_decode_write(L.ptr(doa), dtype, ctypes.c_int64(R), T, num_classes, max_overlaps,
-                                      ctypes.c_double(max_loc_value), L.ptr(ws), ctypes.c_size_t(nbytes), L.ptr(rows),
-                                      L.ptr(event), ctypes.c_int64(total), L.ptr(rec_offsets), L.current_stream()),
+        L.check(lib.seld_decode_write(L.ptr(doa), dtype, R, T, num_classes, max_overlaps, max_loc_value, L.ptr(ws),
+                                      nbytes, L.ptr(rows), L.ptr(event), total, L.ptr(rec_offsets), L.current_stream()),
                 "seld_decode_write")
     return rows, event, rec_offsets

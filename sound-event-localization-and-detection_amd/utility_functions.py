@@ -7,7 +7,6 @@ Same names, same arguments, same result layout.  The transform runs on the GPU (
 seld_stft_magphase_ws) for every segment length 2 <= nperseg <= 4096, the decoding through csrc/decode.hip
 (hip_ops.decode_events); there is no CPU path -- a missing device or library raises.
 """
-import ctypes
 
 import numpy as np
 import torch
@@ -100,7 +99,7 @@ def spectrum_fast(x, nperseg=512, noverlap=128, window='hamming', cut_dc=True, o
     with torch.cuda.device(dev):
         L.check(lib.seld_stft_magphase_ws(L.ptr(t), C, n, nperseg, noverlap, int(bool(output_phase)), int(bool(cut_dc)),
                                           int(bool(cut_last_timeframe)), L.ptr(win), L.ptr(out), L.ptr(ws),
-                                          ctypes.c_size_t(0 if ws is None else ws.numel()), L.current_stream()),
+                                          0 if ws is None else ws.numel(), L.current_stream()),
                 "seld_stft_magphase_ws")
     if is_numpy:
         return out.cpu().numpy().astype(out_dtype)

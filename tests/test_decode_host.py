@@ -51,12 +51,11 @@ def test_header_declares_and_library_exports_entry_points():
 
 
 def _count(lib, sed, dtype, R, T, classes, overlaps, ws, ws_bytes):
-    return lib.seld_decode_count(sed, dtype, ctypes.c_int64(R), T, classes, overlaps, ws, ctypes.c_size_t(ws_bytes), None)
+    return lib.seld_decode_count(sed, dtype, R, T, classes, overlaps, ws, ws_bytes, None)
 
 
 def _write(lib, doa, dtype, R, T, classes, overlaps, ws, ws_bytes, rows, event, cap, offs):
-    return lib.seld_decode_write(doa, dtype, ctypes.c_int64(R), T, classes, overlaps, ctypes.c_double(2.0), ws,
-                                 ctypes.c_size_t(ws_bytes), rows, event, ctypes.c_int64(cap), offs, None)
+    return lib.seld_decode_write(doa, dtype, R, T, classes, overlaps, 2.0, ws, ws_bytes, rows, event, cap, offs, None)
 
 
 def test_refusals_without_gpu():

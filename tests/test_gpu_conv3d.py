@@ -342,20 +342,20 @@ def test_refused_descriptors_launch_nothing():
                 rcs = [lib.seld_hc_conv3d_fwd(ctypes.byref(desc), L.ptr(x), L.ptr_array8(ws), None, L.ptr(y), st),
                        lib.seld_hc_conv3d_bwd_data(ctypes.byref(desc), L.ptr(x), L.ptr_array8(ws), L.ptr(y), st),
                        lib.seld_hc_conv3d_bwd_weight_acc(ctypes.byref(desc), L.ptr(x), L.ptr(x), L.ptr_array8([y] * 8),
-                                                         L.ptr(y), L.ptr(x), ctypes.c_size_t(1 << 14), st)]
+                                                         L.ptr(y), L.ptr(x), 1 << 14, st)]
             else:
                 rcs = [lib.seld_hc_conv3d_transpose_fwd(ctypes.byref(desc), op, L.ptr(x), L.ptr_array8(ws), None,
                                                         L.ptr(y), st),
                        lib.seld_hc_conv3d_transpose_bwd_data(ctypes.byref(desc), op, L.ptr(x), L.ptr_array8(ws),
                                                              L.ptr(y), st),
                        lib.seld_hc_conv3d_transpose_bwd_weight_acc(ctypes.byref(desc), op, L.ptr(x), L.ptr(x),
-                                                                   L.ptr_array8([y] * 8), L.ptr(y), L.ptr(x),
-                                                                   ctypes.c_size_t(1 << 14), st)]
+                                                                   L.ptr_array8([y] * 8), L.ptr(y), L.ptr(x), 1 << 14,
+                                                                   st)]
             assert rcs == [want] * 3, (rcs, want)
         # a valid descriptor with too small a workspace
         desc = H.make_conv3d_desc((1, 8, 4, 4, 4), 8, 4, 3, 1, 1, 1)
         assert lib.seld_hc_conv3d_bwd_weight_acc(ctypes.byref(desc), L.ptr(x), L.ptr(x), L.ptr_array8([y] * 4),
-                                                 L.ptr(y), L.ptr(x), ctypes.c_size_t(4), L.current_stream()) == -2
+                                                 L.ptr(y), L.ptr(x), 4, L.current_stream()) == -2
         torch.cuda.synchronize()
     launched = [ev.name for ev in prof.events() if ev.device_type == torch.autograd.DeviceType.CUDA]
     assert not launched, launched

@@ -182,13 +182,11 @@ def test_refusals_raise_and_write_nothing():
     s = L.current_stream()
 
     def count(sed_p, classes, overlaps, ws_bytes, frames=10):
-        return lib.seld_decode_count(sed_p, 0, ctypes.c_int64(2), frames, classes, overlaps, L.ptr(ws),
-                                     ctypes.c_size_t(ws_bytes), s)
+        return lib.seld_decode_count(sed_p, 0, 2, frames, classes, overlaps, L.ptr(ws), ws_bytes, s)
 
     def write(doa_p, classes, overlaps, ws_bytes, cap=840, rows_p=None):
-        return lib.seld_decode_write(doa_p, 0, ctypes.c_int64(2), 10, classes, overlaps, ctypes.c_double(2.0), L.ptr(ws),
-                                     ctypes.c_size_t(ws_bytes), L.ptr(rows) if rows_p is None else rows_p, L.ptr(event),
-                                     ctypes.c_int64(cap), L.ptr(offs), s)
+        return lib.seld_decode_write(doa_p, 0, 2, 10, classes, overlaps, 2.0, L.ptr(ws), ws_bytes,
+                                     L.ptr(rows) if rows_p is None else rows_p, L.ptr(event), cap, L.ptr(offs), s)
     assert count(L.ptr(sed), 22, 3, need) == -4 and write(L.ptr(doa), 22, 3, need) == -4
     assert count(L.ptr(sed), 14, 3, need - 8) == -2 and write(L.ptr(doa), 14, 3, need - 8) == -2
     assert count(None, 14, 3, need) == -1 and write(None, 14, 3, need) == -1

@@ -281,11 +281,11 @@ def test_refused_descriptors_launch_nothing():
             rcs = [lib.seld_dwconv_fwd(ctypes.byref(desc), L.ptr(x), L.ptr(x), L.ptr(x), L.ptr(y), st),
                    lib.seld_dwconv_bwd_data(ctypes.byref(desc), L.ptr(x), L.ptr(x), L.ptr(y), st),
                    lib.seld_dwconv_bwd_weight_acc(ctypes.byref(desc), L.ptr(x), L.ptr(x), L.ptr(y), L.ptr(y), L.ptr(x),
-                                                  ctypes.c_size_t(1 << 16), st)]
+                                                  1 << 16, st)]
             assert rcs == [want] * 3, (rcs, want)
         ok = H.make_dwconv_desc((2, 8, 16, 16), 16, 3, 1, 1, 1)
-        assert lib.seld_dwconv_bwd_weight_acc(ctypes.byref(ok), L.ptr(x), L.ptr(x), L.ptr(y), L.ptr(y), L.ptr(x),
-                                              ctypes.c_size_t(4), L.current_stream()) == EWORKSPACE
+        assert lib.seld_dwconv_bwd_weight_acc(ctypes.byref(ok), L.ptr(x), L.ptr(x), L.ptr(y), L.ptr(y), L.ptr(x), 4,
+                                              L.current_stream()) == EWORKSPACE
         torch.cuda.synchronize()
     launched = [ev.name for ev in prof.events() if ev.device_type == torch.autograd.DeviceType.CUDA]
     assert not launched, launched

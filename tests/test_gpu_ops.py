@@ -721,7 +721,6 @@ def test_linear_backward_row_splits(kind, fin, fout, rows):
     workspace: the same bits (nothing depends on the workspace's previous contents, nothing is accumulated atomically)."""
     P = pkg()
     H, L = P.hip_ops, P._lib
-    import ctypes
     gen = torch.Generator().manual_seed(17)
     x = torch.randn(rows, fin, generator=gen)
     dy = torch.randn(rows, fout, generator=gen)
@@ -731,7 +730,6 @@ def test_linear_backward_row_splits(kind, fin, fout, rows):
         ws = [torch.randn(fin // kind, fout // kind, generator=gen) * 0.1 for _ in range(kind)]
     xd, dyd, wd = x.to(DEV), dy.to(DEV), [w.to(DEV) for w in ws]
     lib = L.lib()
-    lib.seld_hc_linear_bwd_workspace.restype = ctypes.c_size_t
     nbytes = lib.seld_hc_linear_bwd_workspace(kind, fin, fout)
 
     def run(fill, with_w=True):
@@ -739,7 +737,7 @@ def test_linear_backward_row_splits(kind, fin, fout, rows):
         dws = [torch.full_like(w, 7.0) for w in wd]
         db = torch.full((fout,), 7.0, device=DEV)
         L.check(lib.seld_hc_linear_bwd(kind, rows, fin, fout, L.ptr(xd), L.ptr(dyd), L.ptr_array8(wd), None,
-                                       L.ptr_array8(dws) if with_w else None, L.ptr(db), L.ptr(wsb), ctypes.c_size_t(nbytes),
+                                       L.ptr_array8(dws) if with_w else None, L.ptr(db), L.ptr(wsb), nbytes,
                                        L.current_stream()), "seld_hc_linear_bwd")
         torch.cuda.synchronize()
         return dws, db
@@ -768,7 +766,6 @@ def test_loss_needs_no_zeroed_scalar_and_repeats_bit_for_bit():
     evaluations back to back, sizes from one workgroup to the 256-workgroup cap."""
     P = pkg()
     L = P._lib
-    import ctypes
     lib = L.lib()
     for rows in (3, 700, 40000):
         gen = torch.Generator().manual_seed(rows)
@@ -779,8 +776,8 @@ def test_loss_needs_no_zeroed_scalar_and_repeats_bit_for_bit():
         outs = []
         for k in range(6):
             loss = torch.full((1,), float("nan") if k % 2 else 1e9, device=DEV)
-            L.check(lib.seld_loss_fwd_bwd(L.ptr(a), L.ptr(b), L.ptr(t), ctypes.c_int64(rows), 42, 126, ctypes.c_float(1.0),
-                                          ctypes.c_float(5.0), L.ptr(loss), None, None, L.current_stream()), "seld_loss_fwd_bwd")
+            L.check(lib.seld_loss_fwd_bwd(L.ptr(a), L.ptr(b), L.ptr(t), rows, 42, 126, 1.0, 5.0, L.ptr(loss), None,
+                                          None, L.current_stream()), "seld_loss_fwd_bwd")
             outs.append(loss)
         torch.cuda.synchronize()
         vals = [float(o.item()) for o in outs]

@@ -259,16 +259,14 @@ def test_refused_inputs_launch_nothing(golden):
             s = L.QuatShape(*dims)
             b = ctypes.byref(s)
             rcs = [lib.seld_quat_modulus_fwd(b, L.ptr(x), L.ptr(y), st),
-                   lib.seld_quat_modulus_sum_fwd(b, L.ptr(x), L.ptr(y), L.ptr(y), ctypes.c_size_t(1 << 14), st),
-                   lib.seld_quat_normalized_bwd(b, L.ptr(x), L.ptr(x), L.ptr(x), ctypes.c_float(1e-4), L.ptr(y), L.ptr(y),
-                                                ctypes.c_size_t(1 << 14), st),
+                   lib.seld_quat_modulus_sum_fwd(b, L.ptr(x), L.ptr(y), L.ptr(y), 1 << 14, st),
+                   lib.seld_quat_normalized_bwd(b, L.ptr(x), L.ptr(x), L.ptr(x), 1e-4, L.ptr(y), L.ptr(y), 1 << 14, st),
                    lib.seld_quat_normalize_fwd(b, 1, L.ptr(x), L.ptr(y), st),
                    lib.seld_quat_exp_bwd(b, 1, L.ptr(x), L.ptr(x), L.ptr(y), st),
                    lib.seld_quat_hamilton_bwd(b, L.ptr(x), L.ptr(x), L.ptr(x), L.ptr(y), L.ptr(y), st)]
             assert rcs == [want] * len(rcs), (dims, rcs)
         ok = L.QuatShape(8, 1, 16, 1)
-        assert lib.seld_quat_modulus_sum_fwd(ctypes.byref(ok), L.ptr(x), L.ptr(y), L.ptr(y), ctypes.c_size_t(16),
-                                             st) == EWORKSPACE
+        assert lib.seld_quat_modulus_sum_fwd(ctypes.byref(ok), L.ptr(x), L.ptr(y), L.ptr(y), 16, st) == EWORKSPACE
         assert lib.seld_quat_normalize_fwd(ctypes.byref(ok), 5, L.ptr(x), L.ptr(y), st) == EINVAL
         torch.cuda.synchronize()
     launched = [ev.name for ev in prof.events() if ev.device_type == torch.autograd.DeviceType.CUDA]

@@ -1,6 +1,5 @@
 """spectrum_fast at every segment length 2 <= nperseg <= 4096 (csrc/stft.hip, csrc/stft_any.hip) against the
 reference's outputs (tests/golden/stft_lengths.npz) and the float64 oracle."""
-import ctypes
 
 import numpy as np
 import pytest
@@ -142,9 +141,9 @@ def test_stft_refusals_write_nothing():
     assert lib.seld_stft_magphase_ex(L.ptr(x), 2, 9000, N, nov, 1, 1, 1, None, L.ptr(out), stream) == -2
     need = lib.seld_stft_workspace(N)
     ws = torch.empty(need, dtype=torch.uint8, device=DEV)
-    assert lib.seld_stft_magphase_ws(L.ptr(x), 2, 9000, N, nov, 1, 1, 1, None, L.ptr(out), L.ptr(ws),
-                                     ctypes.c_size_t(need - 1), stream) == -2
-    assert lib.seld_stft_magphase_ws(L.ptr(x), 2, 9000, 4097, 2048, 1, 1, 1, None, L.ptr(out), L.ptr(ws),
-                                     ctypes.c_size_t(need), stream) == -4
+    assert lib.seld_stft_magphase_ws(L.ptr(x), 2, 9000, N, nov, 1, 1, 1, None, L.ptr(out), L.ptr(ws), need - 1,
+                                     stream) == -2
+    assert lib.seld_stft_magphase_ws(L.ptr(x), 2, 9000, 4097, 2048, 1, 1, 1, None, L.ptr(out), L.ptr(ws), need,
+                                     stream) == -4
     torch.cuda.synchronize()
     assert torch.isnan(out).all()

@@ -185,8 +185,8 @@ def test_phase_kernel_equals_mirrored_data_gradient(shape, k, s, p, d):
     lib = L.lib()
     nbytes = int(lib.seld_hc_conv_bwd_data_workspace(ctypes.byref(mdesc)))
     wsb = torch.empty((nbytes + 3) // 4, device=DEV)
-    L.check(lib.seld_hc_conv_bwd_data_ex(ctypes.byref(mdesc), L.ptr(x), L.ptr_array8(ws), L.ptr(yd), L.ptr(wsb),
-                                         ctypes.c_size_t(nbytes), L.current_stream()), "seld_hc_conv_bwd_data_ex")
+    L.check(lib.seld_hc_conv_bwd_data_ex(ctypes.byref(mdesc), L.ptr(x), L.ptr_array8(ws), L.ptr(yd), L.ptr(wsb), nbytes,
+                                         L.current_stream()), "seld_hc_conv_bwd_data_ex")
     _close(y, yd.cpu(), 1e-6, "phase kernel vs mirrored data gradient")
 
 

@@ -1,6 +1,7 @@
 """CPU-only checks: the C ABI library exports what include/seld_hip.h declares, the host-side mirror has the
 reference's state-dict layout and initialisation, config handling, and the product path refuses to run
 without the HIP device (no fallback)."""
+import ctypes
 import importlib
 import os
 import re
@@ -16,7 +17,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_library_exports_every_declared_symbol():
-    import ctypes
     lib_path = os.path.join(ROOT, PKG, "csrc", "libseld_hip.so")
     if not os.path.exists(lib_path):
         import __graft_entry__ as g
@@ -32,9 +32,74 @@ def test_library_exports_every_declared_symbol():
     assert lib.seld_abi_version() >= 1
 
 
+def _declared():
+    """[(name, parameter count)] of every seld_* prototype in the header, counted independently of the binding's parser."""
+    text = open(os.path.join(ROOT, "include", "seld_hip.h")).read()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    text = "\n".join(ln for ln in text.split("\n") if not ln.lstrip().startswith("#"))
+    found = re.findall(r"\b(seld_\w+)\s*\(([^()]*)\)", text)
+    return [(name, 0 if params.strip() == "void" else params.count(",") + 1) for name, params in found]
+
+
+def test_every_declared_entry_point_is_typed():
+    lib = pkg()._lib.lib()
+    declared = _declared()
+    assert len(declared) == len(set(n for n, _ in declared)) >= 148
+    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "seld_hip.h")).read(), flags=re.S)
+    assert set(re.findall(r"\b(seld_\w+)\s*\(", text)) == set(n for n, _ in declared)
+    for name, nparams in declared:
+        fn = getattr(lib, name)
+        assert fn.argtypes is not None, name
+        assert len(fn.argtypes) == nparams, (name, nparams, fn.argtypes)
+
+
+def test_parser_agrees_with_prototypes_written_by_hand():
+    from ctypes import c_char_p, c_double, c_float, c_int, c_int32 as i32, c_int64 as i64, c_size_t, c_void_p as vp
+    lib = pkg()._lib.lib()
+    by_hand = {
+        "seld_decode_workspace": (c_size_t, [i64, i32, i32, i32]),
+        "seld_decode_count": (c_int, [vp, i32, i64, i32, i32, i32, vp, c_size_t, vp]),
+        "seld_decode_write": (c_int, [vp, i32, i64, i32, i32, i32, c_double, vp, c_size_t, vp, vp, i64, vp, vp]),
+        "seld_bn_finalize_ex": (c_int, [vp, i32, i64, c_float, c_float, vp, vp, vp, vp, vp, i32, vp]),
+        "seld_hc_conv_transpose_out_shape": (c_int, [vp, vp, vp]),
+        "seld_build_arch": (c_char_p, []),
+    }
+    for name, (restype, argtypes) in by_hand.items():
+        fn = getattr(lib, name)
+        assert fn.restype is restype, (name, fn.restype)
+        assert list(fn.argtypes) == argtypes, (name, fn.argtypes)
+    assert lib.seld_build_arch() == b"gfx950"
+
+
+def test_parser_refuses_what_it_cannot_type():
+    L = pkg()._lib
+    good = "int seld_a(const float* x /* nullable, (C) */, int64_t n, void* stream);\nsize_t seld_b(void);\n"
+    assert L.prototypes(good) == {"seld_a": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]),
+                                  "seld_b": (ctypes.c_size_t, [])}
+    with pytest.raises(L.SeldHipError, match="seld_half_scale"):
+        L.prototypes(good + "int seld_half_scale(float* x, _Float16 s, void* stream);\n")
+    with pytest.raises(L.SeldHipError, match="seld_norm"):
+        L.prototypes(good + "float seld_norm(const float* x, int64_t n);\n")
+    with pytest.raises(L.SeldHipError, match="seld_split"):
+        L.prototypes(good + "int\nseld_split(const float* x);\n")
+    with pytest.raises(L.SeldHipError, match="seld_each"):
+        L.prototypes(good + "int seld_each(void (*fn)(int32_t), void* stream);\n")
+
+
+def test_wide_arguments_keep_their_width_without_a_wrapper():
+    """Plain Python ints reach an int64_t / size_t parameter whole: 2 recordings give a positive size, (1 << 32) + 2 must
+    not be taken for 2 (tests/test_decode_host.py fixes both halves: 2 is accepted, 1 << 22 recordings are refused)."""
+    lib = pkg()._lib.lib()
+    p = ctypes.c_void_p(64)
+    assert lib.seld_decode_workspace(2, 600, 14, 3) > 0
+    assert lib.seld_decode_workspace((1 << 32) + 2, 600, 14, 3) == 0
+    need = lib.seld_decode_workspace(2, 600, 14, 3)
+    assert lib.seld_decode_count(p, 0, 2, 600, 14, 3, p, need - 1, None) == -2         # R = 2: the workspace is checked
+    assert lib.seld_decode_count(p, 0, (1 << 32) + 2, 600, 14, 3, p, (1 << 32) + need, None) == -4    # SELD_EUNSUPPORTED
+
+
 def test_descriptor_validation_without_gpu():
     """Pure host-side argument checking of the ABI (no kernel is launched)."""
-    import ctypes
     L = pkg()._lib
     H = pkg().hip_ops
     d = H.make_conv_desc((2, 16, 40), 32, 8, (3,), 1, 1, 1)
@@ -143,7 +208,6 @@ def test_shapes_beyond_32bit_offsets_are_not_given_to_the_fast_kernels():
     refuse them a tensor of 4 GB or more -- e.g. the first layer at batch 64, F = 256 (6.4 GB of output; /root/reference
     model.py:273-283 at twice the benchmark batch) -- so that such a call runs on the 64-bit-indexed generic kernels instead.
     Host-side queries only: nothing is launched."""
-    import ctypes
     pkg = importlib.import_module(PKG)
     H, L = pkg.hip_ops, pkg._lib
     big = H.make_conv_desc((64, 8, 256, 512), 192, 8, (3, 3), 1, 1, 1)           # y: 64*192*256*512*4 B = 6.4 GB

@@ -76,7 +76,6 @@ def test_header_declares_and_library_exports_entry_points():
 
 def test_workspace_query():
     lib = pkg()._lib.lib()
-    lib.seld_mha_bwd_ex_workspace.restype = ctypes.c_size_t
     assert lib.seld_mha_bwd_ex_workspace(3, 40, 8) == 3 * 8 * 40 * 4
     assert lib.seld_mha_bwd_ex_workspace(0, 40, 8) == 0
     assert lib.seld_mha_bwd_ex_workspace(3, -1, 8) == 0
@@ -94,8 +93,7 @@ def test_refused_descriptors_without_gpu():
         return lib.seld_mha_fwd_ex(q, P, P, N, Tq, Tk, H, hd, keep, strides, out, P, None)
 
     def bwd(hd=16, keep=None, strides=None, ws=None, nbytes=0, Tk=16):
-        return lib.seld_mha_bwd_ex(P, P, P, P, P, P, 2, 16, Tk, 2, hd, keep, strides, P, P, P, ws,
-                                   ctypes.c_size_t(nbytes), None)
+        return lib.seld_mha_bwd_ex(P, P, P, P, P, P, 2, 16, Tk, 2, hd, keep, strides, P, P, P, ws, nbytes, None)
     assert fwd(q=None) == EINVAL
     assert fwd(out=None) == EINVAL
     assert fwd(N=0) == EINVAL

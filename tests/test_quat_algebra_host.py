@@ -181,13 +181,13 @@ def test_header_declares_and_library_exports_entry_points():
 
 def _all_calls(lib, s, ws=None, ws_bytes=0, p=None):
     b = ctypes.byref(s)
-    e = ctypes.c_float(1e-4)
+    e = 1e-4
     return [lib.seld_quat_modulus_fwd(b, p, p, None),
             lib.seld_quat_modulus_bwd(b, p, p, p, None),
-            lib.seld_quat_modulus_sum_fwd(b, p, p, ws, ctypes.c_size_t(ws_bytes), None),
+            lib.seld_quat_modulus_sum_fwd(b, p, p, ws, ws_bytes, None),
             lib.seld_quat_modulus_sum_bwd(b, p, p, p, p, None),
             lib.seld_quat_normalized_fwd(b, p, p, e, p, None),
-            lib.seld_quat_normalized_bwd(b, p, p, p, e, p, ws, ctypes.c_size_t(ws_bytes), None),
+            lib.seld_quat_normalized_bwd(b, p, p, p, e, p, ws, ws_bytes, None),
             lib.seld_quat_normalize_fwd(b, 1, p, p, None),
             lib.seld_quat_normalize_bwd(b, 1, p, p, p, None),
             lib.seld_quat_exp_fwd(b, 0, p, p, None),
@@ -214,10 +214,9 @@ def test_refused_extents_without_gpu():
     assert set(_all_calls(lib, ok)) == {EINVAL}
     assert lib.seld_quat_normalize_fwd(ctypes.byref(ok), 2, p, p, None) == EINVAL
     assert lib.seld_quat_exp_bwd(ctypes.byref(ok), -1, p, p, p, None) == EINVAL
-    assert lib.seld_quat_modulus_sum_fwd(ctypes.byref(ok), p, p, None, ctypes.c_size_t(0), None) == EWORKSPACE
-    assert lib.seld_quat_modulus_sum_fwd(ctypes.byref(ok), p, p, p, ctypes.c_size_t(64), None) == EWORKSPACE
-    assert lib.seld_quat_normalized_bwd(ctypes.byref(ok), p, p, p, ctypes.c_float(1e-4), p, p, ctypes.c_size_t(64),
-                                        None) == EWORKSPACE
+    assert lib.seld_quat_modulus_sum_fwd(ctypes.byref(ok), p, p, None, 0, None) == EWORKSPACE
+    assert lib.seld_quat_modulus_sum_fwd(ctypes.byref(ok), p, p, p, 64, None) == EWORKSPACE
+    assert lib.seld_quat_normalized_bwd(ctypes.byref(ok), p, p, p, 1e-4, p, p, 64, None) == EWORKSPACE
 
 
 def test_workspace_holds_every_partial_and_the_folded_row():

@@ -8,7 +8,6 @@ reads sed once and writes one 8-byte mask per frame; the write phase reads the m
 writes 44 bytes per row (the row and its event index).  Rates are given as a fraction of the 6.3 TB/s float4-copy
 ceiling of DESIGN.md.  Prints one JSON line per density."""
 import argparse
-import ctypes
 import json
 import os
 import statistics
@@ -76,13 +75,12 @@ def main():
         s = L.current_stream()
 
         def count():
-            L.check(lib.seld_decode_count(L.ptr(sed), 0, ctypes.c_int64(R), T, classes, overlaps, L.ptr(ws),
-                                          ctypes.c_size_t(nbytes), s), "seld_decode_count")
+            L.check(lib.seld_decode_count(L.ptr(sed), 0, R, T, classes, overlaps, L.ptr(ws), nbytes,
+                                          s), "seld_decode_count")
 
         def write():
-            L.check(lib.seld_decode_write(L.ptr(doa), 0, ctypes.c_int64(R), T, classes, overlaps, ctypes.c_double(2.0),
-                                          L.ptr(ws), ctypes.c_size_t(nbytes), L.ptr(rows), L.ptr(event), ctypes.c_int64(E),
-                                          L.ptr(offsets), s), "seld_decode_write")
+            L.check(lib.seld_decode_write(L.ptr(doa), 0, R, T, classes, overlaps, 2.0, L.ptr(ws), nbytes, L.ptr(rows),
+                                          L.ptr(event), E, L.ptr(offsets), s), "seld_decode_write")
         count_us = timed(count, a.reps)
         write_us = timed(write, a.reps)
         whole_us = timed(lambda: H.decode_events(sed, doa), a.reps)

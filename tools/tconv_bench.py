@@ -69,8 +69,8 @@ def main():
         wp = L.ptr_array8(ws)
 
         def mirrored():
-            L.check(lib.seld_hc_conv_bwd_data_ex(ctypes.byref(mdesc), L.ptr(x), wp, L.ptr(y_m), L.ptr(wsb),
-                                                 ctypes.c_size_t(nbytes), stream), "seld_hc_conv_bwd_data_ex")
+            L.check(lib.seld_hc_conv_bwd_data_ex(ctypes.byref(mdesc), L.ptr(x), wp, L.ptr(y_m), L.ptr(wsb), nbytes,
+                                                 stream), "seld_hc_conv_bwd_data_ex")
             y_m.add_(bview)
         fns = {"fwd": lambda: H.conv_transpose_fwd(desc, out_pad, x, ws, bias),
                "fwd_mirrored_dgrad+bias": mirrored,
