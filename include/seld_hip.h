@@ -828,6 +828,58 @@ int seld_decode_write(const void* doa, int32_t dtype, int64_t recordings, int32_
                       int32_t overlaps, double max_loc_value, const void* workspace, size_t workspace_bytes,
                       double* rows, int32_t* event, int64_t capacity, int64_t* rec_offsets, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Target encoding and segmentation: the preparation half's label path (csrc/labels.hip).
+ *
+ * seld_encode_events replaces the fill loop of csv_to_matrix_task2 (utility_functions.py:219-267) for a batch of
+ * recordings, and is the exact inverse of the decode kernel above.  Events are CSR by recording, all on the device:
+ *   first_frame[E], last_frame[E]   int32, inclusive; last < first covers no frame (np.arange is empty)
+ *   cls[E]                          int32 class id
+ *   xyz[E, 3]                       double
+ *   rec_offsets[R + 1]              int64: events rec_offsets[r] .. rec_offsets[r + 1] belong to recording r
+ *   events = E; max_rec_events      the largest event count of one recording, as the caller knows it from the offsets
+ *                                   it built (it sizes the LDS staging); a recording that holds more is counted invalid
+ * target (R, frames, 4 * classes * overlaps), or (R, frames, 4 * classes) with no_overlaps != 0, contiguous, float32
+ * (SELD_DECODE_F32) or float64 (SELD_DECODE_F64); per frame [cl (classes * slots) | loc (classes * slots * 3)], slot
+ * class * slots + pos, as the reference stacks it.
+ *   * an event takes, in every frame it covers, the next free slot of its class IN EVENT ORDER within the recording
+ *     (the reference's pos = int(np.sum(cl[f][class_id])));
+ *   * loc = xyz / max_loc_value, divided in double; float32 output is that quotient rounded once; an empty loc slot is
+ *     0.0 / max_loc_value, as the reference divides the whole array;
+ *   * every element of target is written exactly once, zeros included: the caller does not clear it;
+ *   * overflow[0] receives the number of (recording, frame, class) cells that more than `overlaps` events want (the
+ *     reference raises IndexError there; with no_overlaps only slot 0 is emitted but the cells are still counted, as
+ *     the reference fills before it slices), overflow[1] the number of invalid events and recordings: a covered frame
+ *     outside [0, frames), a class outside [0, classes), offsets that are not ascending inside [0, E], more than
+ *     max_rec_events events.  Invalid events are skipped; nothing is ever written outside target.  The two ints are
+ *     cleared by the call (a memset node on the stream) and are the only words touched by atomics: target has one
+ *     writer per element, two runs give the same bytes.
+ * SELD_EINVAL: a NULL pointer (the four event arrays may be NULL when events == 0), non-positive recordings / frames /
+ * classes / overlaps, events < 0, max_rec_events outside [0, events], an unknown dtype.  SELD_EUNSUPPORTED:
+ * classes * overlaps > 64, max_rec_events > SELD_ENCODE_MAX_EVENTS, 2^31 workgroups or more.  A refused call launches
+ * nothing and writes nothing.
+ *
+ * seld_segment cuts overlapping, zero-padded segments (segment_task2, utility_functions.py:302-342, and
+ * segment_waveforms, :272-299):
+ *   layout SELD_SEGMENT_TIME_LAST    src (rows, length)  -> dst (segments, rows, seg_len)
+ *                                    dst[s, r, j] = src[r, s * hop + j], or 0 when s * hop + j >= length
+ *   layout SELD_SEGMENT_TIME_FIRST   src (length, rows)  -> dst (segments, seg_len, rows)
+ *                                    dst[s, j, r] = src[s * hop + j, r], or 0 when s * hop + j >= length
+ * float32 or float64 (dtype as above), hop >= 1, `segments` as the caller wants them.  16-byte loads and stores where
+ * the pointers and the extents allow, scalar loads at ragged edges and for odd hops, a scalar kernel otherwise.
+ * SELD_EINVAL: a NULL pointer, a non-positive extent, hop < 1, an unknown dtype or layout; SELD_EUNSUPPORTED: rows *
+ * length, rows * seg_len or segments * hop of 2^46 or more.  A refused call launches nothing.
+ * ------------------------------------------------------------------------------------------ */
+#define SELD_ENCODE_MAX_EVENTS 4096
+#define SELD_SEGMENT_TIME_LAST  0
+#define SELD_SEGMENT_TIME_FIRST 1
+int seld_encode_events(const int32_t* first_frame, const int32_t* last_frame, const int32_t* cls, const double* xyz,
+                       const int64_t* rec_offsets, int64_t events, int32_t max_rec_events, int64_t recordings,
+                       int32_t frames, int32_t classes, int32_t overlaps, double max_loc_value, int32_t no_overlaps,
+                       int32_t dtype, void* target, int32_t* overflow, void* stream);
+int seld_segment(const void* src, int32_t dtype, int32_t layout, int64_t rows, int64_t length, int64_t seg_len,
+                 int64_t hop, int64_t segments, void* dst, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

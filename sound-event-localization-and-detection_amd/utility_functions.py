@@ -1,11 +1,14 @@
 """Drop-in for the parts of the reference's utility_functions.py that are on the hot path: `spectrum_fast`
 (utility_functions.py:129-155, called at model.py:562), the STFT magnitude / phase feature extractor, and
 `gen_submission_list_task2` / `gen_submission_list_task2_OLD` (utility_functions.py:158-210, called at train.py:110-116),
-which turn the network's outputs into the challenge's submission rows.
+which turn the network's outputs into the challenge's submission rows, and `csv_to_matrix_task2` / `segment_waveforms` /
+`segment_task2` (utility_functions.py:212-342), which build the dense target from a label file and cut features, targets
+and waveforms into training segments.
 
 Same names, same arguments, same result layout.  The transform runs on the GPU (csrc/stft.hip, csrc/stft_any.hip through
 seld_stft_magphase_ws) for every segment length 2 <= nperseg <= 4096, the decoding through csrc/decode.hip
-(hip_ops.decode_events); there is no CPU path -- a missing device or library raises.
+(hip_ops.decode_events), the target encoding and the segmentation through csrc/labels.hip (hip_ops.encode_events,
+hip_ops.segment); there is no CPU path -- a missing device or library raises.
 """
 
 import numpy as np
@@ -173,3 +176,119 @@ def gen_submission_list_task2(sed, doa, max_loc_value=2., num_frames=600, num_cl
     for f, c, x, y, z, e in zip(cols[0], cols[1], cols[2], cols[3], cols[4], event.tolist()):
         output_dict.setdefault(int(f), []).append([int(c), x, y, z, e])
     return (rows if rows.shape[0] else np.array([])), output_dict
+
+
+def csv_to_matrix_task2(path, class_dict, dur=60, step=0.1, max_loc_value=2., no_overlaps=False):
+    '''
+    Read a task-2 label csv file and output the matrix of 100-msec frames, each filled with the activity of every
+    sound class present and its location coordinates -- utility_functions.py:212-269.
+
+    The file is read with pandas.read_csv as in the reference (its float parser is part of the result), the columns
+    Start / End are turned into frames on the host (hip_ops.event_frames) and the matrix is filled on the device
+    (hip_ops.encode_events, csrc/labels.hip).  Returns the (int(dur / step), 4 * len(class_dict) * 3) float64 numpy
+    array [cl | loc] -- (.., 4 * len(class_dict)) with no_overlaps -- and raises IndexError where more than three
+    sounds of one class overlap, as the reference does.
+    '''
+    try:
+        import pandas as pd
+    except ImportError as e:
+        raise ImportError("csv_to_matrix_task2 reads the label file with pandas.read_csv, as the reference does: "
+                          "install pandas") from e
+    max_overlap = 3
+    num_frames = int(dur / step)
+    df = pd.read_csv(path)
+    first, last = H.event_frames(df['Start'].to_numpy(dtype=np.float64), df['End'].to_numpy(dtype=np.float64), dur, step)
+    cls = np.asarray([class_dict[c] for c in df['Class']], dtype=np.int64)
+    xyz = df[['X', 'Y', 'Z']].to_numpy(dtype=np.float64)
+    out = H.encode_events(first, last, cls, xyz, [0, len(df)], num_frames, len(class_dict), max_overlap, max_loc_value,
+                          no_overlaps, torch.float64)
+    return out[0].cpu().numpy()
+
+
+def _segment_inputs(name, predictors, target):
+    """(predictors, target, is_numpy) as contiguous device tensors: numpy arrays go to the current device, device tensors
+    stay where they are.  float32 and float64 only."""
+    if torch.is_tensor(predictors) != torch.is_tensor(target):
+        raise L.SeldHipError(f"{name}: predictors and target must both be numpy arrays or both device tensors")
+    is_numpy = not torch.is_tensor(predictors)
+    if is_numpy:
+        predictors, target = np.asarray(predictors), np.asarray(target)
+        for a, what in ((predictors, "predictors"), (target, "target")):
+            if a.dtype not in (np.float32, np.float64):
+                raise L.SeldHipError(f"{name}: {what}: unsupported dtype {a.dtype} (float32 or float64)")
+        if not torch.cuda.is_available():
+            raise L.SeldHipError(f"{name}: no HIP device (this package has no CPU path)")
+        dev = torch.device("cuda", torch.cuda.current_device())
+        predictors = torch.from_numpy(np.ascontiguousarray(predictors)).to(dev)
+        target = torch.from_numpy(np.ascontiguousarray(target)).to(dev)
+    return predictors, target, is_numpy
+
+
+def _segment_lists(X, Y, is_numpy):
+    if is_numpy:
+        X, Y = X.cpu().numpy(), Y.cpu().numpy()
+        return [X[i] for i in range(X.shape[0])], [Y[i] for i in range(Y.shape[0])]
+    return list(X.unbind(0)), list(Y.unbind(0))
+
+
+def segment_waveforms(predictors, target, length):
+    '''
+    Segment input waveforms into shorter frames of predefined length (in samples), the last one zero-padded --
+    utility_functions.py:272-299.  predictors (channels, samples), target (channels', samples).
+
+    numpy arrays in give lists of numpy arrays, through the device; device tensors in give lists of views into the two
+    stacked device results (hip_ops.segment, csrc/labels.hip), without a host copy.  Every chunk has the input's dtype
+    (the reference returns its padded last chunk in float64; the values are equal).  A target shorter than the
+    predictors, for which the reference returns ragged chunks, raises ValueError.
+    '''
+    predictors, target, is_numpy = _segment_inputs("segment_waveforms", predictors, target)
+    if predictors.dim() != 2 or target.dim() != 2:
+        raise ValueError(f"segment_waveforms: expected (channels, samples) arrays, got {tuple(predictors.shape)} and "
+                         f"{tuple(target.shape)}")
+    length, n = int(length), predictors.shape[-1]
+    if length < 1:
+        raise ValueError(f"segment_waveforms: length must be positive, got {length}")
+    if target.shape[-1] < n:
+        raise ValueError(f"segment_waveforms: the target ({target.shape[-1]} samples) is shorter than the predictors ({n})")
+    count = len(range(0, n, length))
+    X = H.segment(predictors, length, length, segments=count)
+    Y = H.segment(target[:, :n], length, length, segments=count)
+    return _segment_lists(X, Y, is_numpy)
+
+
+def segment_task2(predictors, target, predictors_len_segment=50*8, target_len_segment=50, overlap=0.5):
+    '''
+    Segment input stft and target matrix of task 2 into shorter, overlapping chunks, the last ones zero-padded; the
+    default parameters cut 5-second frames -- utility_functions.py:302-342.  predictors (channels, bins, frames),
+    target (frames', width).
+
+    The reference's target path is kept bit for bit, quirk included: it RESHAPES the (frames', width) target to
+    (1, width, frames') -- a reinterpretation of the buffer, not a transpose --, cuts the last axis and reshapes each
+    cut to (target_len_segment, width).  hip_ops.segment(target, ..., time_first=True) gives the cut by rows.
+    Input convention, dtype and list results as segment_waveforms.  Raises the reference's ValueError when the two
+    cut counts differ, and ValueError for a chunk that lies inside the predictors but extends past the target (where
+    the reference returns a short chunk) or is padded in the predictors but longer than a segment in the target
+    (where the reference's pad fails).
+    '''
+    predictors, target, is_numpy = _segment_inputs("segment_task2", predictors, target)
+    if predictors.dim() != 3 or target.dim() != 2:
+        raise ValueError(f"segment_task2: expected (channels, bins, frames) predictors and a (frames, width) target, got "
+                         f"{tuple(predictors.shape)} and {tuple(target.shape)}")
+    len_p, len_t = int(predictors_len_segment), int(target_len_segment)
+    hop_p, hop_t = int(len_p * overlap), int(len_t * overlap)
+    if len_p < 1 or len_t < 1 or hop_p < 1 or hop_t < 1:
+        raise ValueError(f"segment_task2: segment lengths {len_p}, {len_t} with overlap {overlap} give no positive hop")
+    frames_p, (frames_t, width) = predictors.shape[-1], target.shape
+    count = len(range(0, frames_p, hop_p))
+    if count != len(range(0, frames_t, hop_t)):
+        raise ValueError('Predictors and test frames should be selected to produce the same amount of frames')
+    starts = np.arange(count, dtype=np.int64)
+    padded = starts * hop_p + len_p > frames_p
+    left = frames_t - starts * hop_t
+    if (np.where(padded, left > len_t, left < len_t)).any():
+        raise ValueError('segment_task2: the target chunks do not follow the predictor chunks: a chunk inside the '
+                         'predictors extends past the target, or a padded one is longer than target_len_segment')
+    X = H.segment(predictors, len_p, hop_p, segments=count)
+    # target.reshape(1, width, frames'): the same buffer read as `width` rows of frames' entries
+    Y = H.segment(target.contiguous().view(width, frames_t), len_t, hop_t, segments=count).view(count, len_t, width)
+    return _segment_lists(X, Y, is_numpy)
