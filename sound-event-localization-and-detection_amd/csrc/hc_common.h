@@ -122,8 +122,12 @@ inline int hc_validate(const seld_conv_desc* d) {
 }
 
 inline void hc_out_shape(const seld_conv_desc* d, int out[2]) {
-    for (int i = 0; i < 2; ++i)
-        out[i] = (d->in[i] + 2 * d->pad[i] - d->dil[i] * (d->k[i] - 1) - 1) / d->stride[i] + 1;
+    // span < 0: the dilated kernel is longer than the padded input.  C division truncates towards zero, so with
+    // stride > -span the quotient would be 0 and the extent 1: report 0 (every caller treats o <= 0 as SELD_EINVAL)
+    for (int i = 0; i < 2; ++i) {
+        const int span = d->in[i] + 2 * d->pad[i] - d->dil[i] * (d->k[i] - 1) - 1;
+        out[i] = span < 0 ? 0 : span / d->stride[i] + 1;
+    }
 }
 
 }  // namespace seld
