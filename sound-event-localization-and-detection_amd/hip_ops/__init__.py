@@ -7,6 +7,8 @@ from ._core import *            # noqa: F401,F403
 from .train_ops import *        # noqa: F401,F403
 from .norm_act import *         # noqa: F401,F403
 from .conv3d import *           # noqa: F401,F403
+from .weight_forms import *     # noqa: F401,F403
+from .streams import *          # noqa: F401,F403
 from .conv import *             # noqa: F401,F403
 from .conv_transpose import *   # noqa: F401,F403
 from .dwconv import *           # noqa: F401,F403
@@ -20,9 +22,10 @@ from .train_ops import _req_inplace, _unit_gradients  # noqa: F401
 from .norm_act import (_claim_grad_slots, _direct_targets, _identity_cache, _nbt, _ncs, _one_pass_ok, _Philox,  # noqa: F401
                        _rowscale, _stats_pool)
 from .conv3d import _conv3d_backward, _conv3d_weights, _triple  # noqa: F401
-from .conv import (_branch, _conv_backward, _DeferredWgrads, _hcq_ok, _hcq_wgrad_label, _hcq_wgrad_ok,  # noqa: F401
-                   _hcq_wgrad_row_bytes, _hcq_wgrad_row_label, _HcqWeights, _label, _on_side_stream, _pair_ok, _ptr2, _side,
-                   _side_enabled, _transpose_ahead, _y_shape)
+from .weight_forms import _hcq_ok, _HcqWeights  # noqa: F401
+from .streams import _on_side_stream, _side_enabled  # noqa: F401
+from .conv import (_conv_backward, _DeferredWgrads, _hcq_wgrad_label, _hcq_wgrad_ok, _hcq_wgrad_row_bytes,  # noqa: F401
+                   _hcq_wgrad_row_label, _label, _pair_ok, _ptr2, _transpose_ahead, _y_shape)
 from .dwconv import _dw_y_shape  # noqa: F401
 from .linear_mha import _mha_keep_mask  # noqa: F401
 from .first_stage import _first_stage_nostore, _fs_bytes  # noqa: F401

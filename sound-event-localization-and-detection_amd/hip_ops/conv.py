@@ -1,5 +1,6 @@
-"""2-D / 1-D hypercomplex convolution (csrc/hc_conv*.hip, csrc/hcq_*.hip): descriptors, the three entry points, the packed
-weight forms of the fast-product kernels, grouped / deferred / side-stream weight gradients, and the autograd functions."""
+"""2-D / 1-D hypercomplex convolution (csrc/hc_conv*.hip, csrc/hcq_*.hip): descriptors, the three entry points, the
+grouped / deferred weight gradients, the router that decides where a layer's weight gradient goes, and the autograd
+functions.  The packed weight forms live in weight_forms.py, the side stream in streams.py."""
 import ctypes
 import os
 
@@ -8,7 +9,9 @@ import torch
 from .. import _lib as L
 from ._core import _pair, _req, deterministic, kernel_label, memo, scratch, timed
 from .conv3d import HyperConv3dFn
-from .norm_act import _direct_targets, _ncs, channel_stats
+from .norm_act import _direct_targets, channel_stats
+from .streams import _on_side_stream, _side_enabled, side_queue
+from .weight_forms import _hcq_ok, hcq_weights
 
 
 def conv_work(desc, which):
@@ -124,6 +127,36 @@ def conv_bwd_data(desc, dy, ws, x_shape, ahead=None):
     with _timed(desc, 1):
         L.check(lib.seld_hc_conv_bwd_data_ex(ctypes.byref(desc), L.ptr(dy), L.ptr_array8(ws), L.ptr(dx), L.ptr(wsb),
                                              nbytes, L.current_stream()), "seld_hc_conv_bwd_data")
+    return dx
+
+
+def conv_pair_bwd_data(desc, dyA, dyB, wsA, wsB, x_shape, ahead=None):
+    """Sum of the data gradients of two convolutions of one input: one launch where a pair form takes the shape, else the
+    two single calls.  `ahead`: the two sets' (workspace, event) from _transpose_ahead."""
+    lib = L.lib()
+    wp = hcq_weights.get(desc, 1, wsA, wsB) if desc.algebra > 1 else None
+    if wp is None and not _pair_ok(desc, 1):
+        dx = conv_bwd_data(desc, dyA, wsA, x_shape)
+        dx += conv_bwd_data(desc, dyB, wsB, x_shape)
+        return dx
+    dx = torch.empty(x_shape, device=dyA.device, dtype=torch.float32)
+    if wp is not None:
+        with _timed(desc, 1, 2, label=lambda: hcq_label(desc, 1, 2)):
+            hcq_conv(desc, 1, dyA, wp, (dx,), x2=dyB)
+    elif ahead is not None:
+        (wtA, evA), (wtB, evB) = ahead
+        torch.cuda.current_stream().wait_event(evA)
+        torch.cuda.current_stream().wait_event(evB)
+        with _timed(desc, 1, 2):
+            L.check(lib.seld_hc_conv_pair_bwd_data_wt(ctypes.byref(desc), L.ptr(dyA), L.ptr(dyB), L.ptr(wtA), L.ptr(wtB),
+                                                      L.ptr(dx), L.current_stream()), "seld_hc_conv_pair_bwd_data_wt")
+    else:
+        nbytes = 2 * lib.seld_hc_conv_bwd_data_workspace(ctypes.byref(desc))
+        wsb = torch.empty((nbytes + 3) // 4, device=dyA.device, dtype=torch.float32)
+        with _timed(desc, 1, 2):
+            L.check(lib.seld_hc_conv_pair_bwd_data(ctypes.byref(desc), L.ptr(dyA), L.ptr(dyB), L.ptr_array8(list(wsA)),
+                                                   L.ptr_array8(list(wsB)), L.ptr(dx), L.ptr(wsb), nbytes,
+                                                   L.current_stream()), "seld_hc_conv_pair_bwd_data")
     return dx
 
 
@@ -319,108 +352,6 @@ def conv_bwd_weight(desc, x, dy, w_shape, want_bias, into=None, bias_into=None):
     return dws, dbias
 
 
-@memo
-def _hcq_ok(desc, mode, npair=1):
-    """Does the fast-product kernel take this (shape, direction)?  (cached; no weights needed)"""
-    return desc.algebra > 1 and hcq_pack_floats(desc, mode, npair) > 0
-
-
-def stacked_conv_weight(params):
-    """ONE convolution weight (sum of the Cout's, Cin, k...) over parameters that lie back to back in memory -- FlatAdam
-    re-homes a model's parameters into one flat buffer in registration order, so the attention's values / keys / queries
-    (model.py:18-20) are three consecutive row blocks of it -- or None.  With gradients enabled the gradient slots must be
-    adjacent in the same order too: the stacked weight is a fresh leaf over the same storage whose gradient the backward
-    kernels write straight into those slots (`_direct_targets`), so autograd never sees the member parameters."""
-    p0 = params[0]
-    need_grad = torch.is_grad_enabled() and any(p.requires_grad for p in params)
-    at = p0.data_ptr()
-    for p in params:
-        if p.data_ptr() != at or not p.is_contiguous() or p.shape[1:] != p0.shape[1:] or p.dtype != torch.float32:
-            return None
-        at += 4 * p.numel()
-    shape = (sum(int(p.shape[0]) for p in params),) + tuple(p0.shape[1:])
-    same_buffer = lambda ts: all(t.untyped_storage().data_ptr() == ts[0].untyped_storage().data_ptr() for t in ts)
-    if not same_buffer(params):                     # neighbours by accident of the allocator: not one tensor's memory
-        return None
-    gview = None
-    if need_grad:
-        if not all(getattr(p, "_seld_direct_grad", False) and p.grad is not None and p.requires_grad for p in params):
-            return None
-        if not same_buffer([p.grad for p in params]):
-            return None
-        gat = p0.grad.data_ptr()
-        for p in params:
-            if p.grad.data_ptr() != gat or not p.grad.is_contiguous():
-                return None
-            gat += 4 * p.numel()
-        gview = p0.grad.as_strided(shape, p0.grad.stride())
-    w = p0.detach().as_strided(shape, p0.stride())
-    if need_grad:
-        w.requires_grad_(True)
-        w._seld_base_param = p0
-        w._seld_grad = gview
-    return w
-
-
-def as_conv_weight(param, shape):
-    """A contiguous reshape of a parameter used as a convolution weight (the attention's Linear applied as a 1x1
-    convolution, model.py:46): the view remembers its parameter, so the backward kernels write that parameter's gradient
-    slot directly instead of returning a tensor for autograd to add to it."""
-    w = param.view(shape)
-    w._seld_base_param = param
-    return w
-
-
-# ---- weight gradients on a second HIP stream -------------------------------------------------------------
-# A layer's weight gradient and its data gradient both start from dy and are independent; the accumulating weight-
-# gradient kernels write only FlatAdam's gradient slots.  Issued on a side stream they overlap the data gradient and
-# the element-wise kernels that follow it on the main stream: a 70 us kernel on this GPU spends ~13 us ramping up and
-# draining, which another queue fills (measured: two independent 1x3 convolutions 142 -> 121 us).  The main stream
-# joins the side stream when the backward pass ends (autograd engine callback) and in FlatAdam.step().
-_side = {"stream": None, "dirty": False, "keep": []}
-
-
-def _side_enabled():
-    return os.environ.get("SELD_WGRAD_SIDE_STREAM", "1") != "0" and not deterministic()
-
-
-def join_side_stream():
-    """Make the current stream wait for everything issued on the side stream."""
-    if _side["dirty"]:
-        ev = torch.cuda.Event()
-        ev.record(_side["stream"])
-        torch.cuda.current_stream().wait_event(ev)
-        _side["dirty"] = False
-    _side["keep"].clear()
-
-
-def _on_side_stream(fn, *tensors):
-    """Run `fn` (kernel launches only) on the side stream, ordered after everything already on the current stream.
-    `tensors` are read there: the caching allocator must not recycle them before the side stream is done, and
-    nothing on the main stream may overwrite them before the join.  The second point is about autograd: a backward
-    that hands `dy` on as the gradient of an addend (HyperConvAddFn / HyperConvPairFn) gives the engine a tensor it
-    accumulates into IN PLACE when it holds the only reference -- while the side stream may still be reading it.
-    Holding a reference here until the join makes the engine accumulate out of place instead."""
-    if _side["stream"] is None:
-        _side["stream"] = torch.cuda.Stream()
-    st = _side["stream"]
-    ev = torch.cuda.Event()
-    ev.record(torch.cuda.current_stream())
-    st.wait_event(ev)
-    with torch.cuda.stream(st):
-        fn()
-    for t in tensors:
-        if t is not None:
-            t.record_stream(st)
-            _side["keep"].append(t)
-    if not _side["dirty"]:
-        _side["dirty"] = True
-        try:
-            torch.autograd.Variable._execution_engine.queue_callback(join_side_stream)
-        except RuntimeError:            # not inside a backward pass: join at once
-            join_side_stream()
-
-
 def _transpose_ahead(desc, ws):
     """The data gradient's weight re-layout (seld_hc_conv_transpose_weights), issued NOW on the side stream -- i.e. during
     the forward pass, where it overlaps the convolution -- instead of in front of the data-gradient kernel on the critical
@@ -430,42 +361,92 @@ def _transpose_ahead(desc, ws):
     lib = L.lib()
     nbytes = lib.seld_hc_conv_bwd_data_workspace(ctypes.byref(desc))
     wt = torch.empty((nbytes + 3) // 4, device=ws[0].device, dtype=torch.float32)
-    if _side["stream"] is None:
-        _side["stream"] = torch.cuda.Stream()
-    st = _side["stream"]
-    ev0 = torch.cuda.Event()
-    ev0.record(torch.cuda.current_stream())
-    st.wait_event(ev0)                                   # the weights may still be in flight (Adam of the last step)
-    with torch.cuda.stream(st):
+    with side_queue.fork(wt):                            # the weights may still be in flight (Adam of the last step)
         L.check(lib.seld_hc_conv_transpose_weights(ctypes.byref(desc), L.ptr_array8([_req(w, "w") for w in ws]),
                                                    L.ptr(wt), nbytes, L.current_stream()),
                 "seld_hc_conv_transpose_weights")
-        ev = torch.cuda.Event()
-        ev.record(st)
-    wt.record_stream(st)
+        ev = side_queue.event()
     return wt, ev
 
 
+@memo
+def _pair_ok(desc, which):
+    return bool(L.lib().seld_hc_conv_pair_supported(ctypes.byref(desc), which))
+
+
+def _route_wgrads(desc, x, sets, need_dx):
+    """Where the weight gradients of one convolution of `x`, or of two of the same geometry, go.  sets: [(dy, ws, bias)]
+    per weight set; need_dx: x takes a gradient too.  The first that applies:
+      1. the deferred group (issued with the other layers' when the backward pass ends): every set has gradient slots
+         (`_direct_targets`), none a bias slot, and `deferred_wgrads` takes the shape;
+      2. two sets, one launch of the fast-product kernels: slots, no bias slot, `_hcq_wgrad_ok(desc, 2)`;
+      3. two sets, one launch of the pair kernel: slots, `_pair_ok(desc, 2)`, not deterministic();
+         (2 and 3 on the side stream when it is enabled, else on the current one)
+      4. one set, the per-layer accumulating kernels on the side stream: slots, side stream enabled, need_dx;
+      5. per set, on the current stream: accumulated into the set's slots where it has them, else fresh tensors.
+    1 - 4 are issued here.  Returns a callable that issues 5, if it is left, and returns per set the (dws, dbias) autograd
+    still has to receive.  A single convolution calls it behind its data gradient; the pair routes behind its own."""
+    direct = [_direct_targets(ws, bias) for _, ws, bias in sets]
+    slots = all(d is not None for d in direct)
+    no_bias = slots and all(d[1] is None for d in direct)
+    dys = [dy for dy, _, _ in sets]
+    pair = len(sets) == 2
+    none = ([None] * desc.algebra, None)
+
+    def per_set():
+        out = []
+        for (dy, ws, bias), d in zip(sets, direct):
+            into, bias_into = d or (None, None)
+            g = conv_bwd_weight(desc, x, dy, tuple(ws[0].shape), bias is not None, into=into, bias_into=bias_into)
+            out.append(g if d is None else none)
+        return out
+
+    def pair_kernel():
+        (dwA, dbA), (dwB, dbB) = direct
+        with _timed(desc, 2, 2):
+            L.check(L.lib().seld_hc_conv_pair_bwd_weight_acc(ctypes.byref(desc), L.ptr(x), L.ptr(dys[0]), L.ptr(dys[1]),
+                                                             L.ptr_array8(dwA), L.ptr_array8(dwB), L.ptr(dbA), L.ptr(dbB),
+                                                             L.current_stream()), "seld_hc_conv_pair_bwd_weight_acc")
+
+    if no_bias and deferred_wgrads.takes(desc):
+        for dy, d in zip(dys, direct):
+            deferred_wgrads.add(desc, x, dy, d[0])
+    elif pair and no_bias and _hcq_wgrad_ok(desc, 2):
+        launch = lambda: hcq_wgrad_acc(desc, x, dys[0], direct[0][0], dys[1], direct[1][0])
+        _on_side_stream(launch, x, *dys) if _side_enabled() else launch()
+    elif pair and slots and _pair_ok(desc, 2) and not deterministic():
+        _on_side_stream(pair_kernel, x, *dys) if _side_enabled() else pair_kernel()
+    elif not pair and slots and _side_enabled() and need_dx:
+        _on_side_stream(per_set, x, *dys)
+    else:
+        return per_set
+    return lambda: [none] * len(sets)
+
+
+def _conv_forward(ctx, x, bias, ws, stride, padding, dilation, epilogue=0, addend=None, stats=None):
+    """forward() of the autograd functions of ONE convolution: y, and in ctx what _conv_backward needs."""
+    algebra = len(ws)
+    k = tuple(ws[0].shape[2:])
+    desc = make_conv_desc(tuple(x.shape), ws[0].shape[0] * algebra, algebra, k, stride, padding, dilation)
+    x = _req(x, "x")
+    y = conv_fwd(desc, x, ws, bias, epilogue=epilogue, addend=addend, stats=stats)
+    ctx.desc = desc
+    ctx.has_bias = bias is not None
+    ctx.w_params, ctx.bias_param = ws, bias
+    ctx.wt_ahead = _transpose_ahead(desc, ws) if ctx.needs_input_grad[0] else None
+    ctx.save_for_backward(x)
+    return y
+
+
 def _conv_backward(ctx, dy, first_w):
-    x = ctx.saved_tensors[0]
-    ws = ctx.w_params
+    x, ws = ctx.saved_tensors[0], ctx.w_params
     dy = _req(dy, "dy")
     dws, dbias = [None] * len(ws), None
     need_w = any(ctx.needs_input_grad[first_w:]) or (ctx.has_bias and ctx.needs_input_grad[1])
-    direct = _direct_targets(ws, ctx.bias_param) if need_w else None
-    if direct is not None and direct[1] is None and deferred_wgrads.takes(ctx.desc):
-        deferred_wgrads.add(ctx.desc, x, dy, direct[0])          # issued with the other layers' when the backward pass ends
-        need_w = False
-    elif direct is not None and _side_enabled() and ctx.needs_input_grad[0]:
-        _on_side_stream(lambda: conv_bwd_weight(ctx.desc, x, dy, tuple(ws[0].shape), ctx.has_bias, into=direct[0],
-                                                bias_into=direct[1]), x, dy)
-        need_w = False
-    dx = conv_bwd_data(ctx.desc, dy, ws, tuple(x.shape), getattr(ctx, "wt_ahead", None)) if ctx.needs_input_grad[0] else None
-    if need_w:
-        if direct is not None:
-            conv_bwd_weight(ctx.desc, x, dy, tuple(ws[0].shape), ctx.has_bias, into=direct[0], bias_into=direct[1])
-        else:
-            dws, dbias = conv_bwd_weight(ctx.desc, x, dy, tuple(ws[0].shape), ctx.has_bias)
+    rest = _route_wgrads(ctx.desc, x, [(dy, ws, ctx.bias_param)], ctx.needs_input_grad[0]) if need_w else None
+    dx = conv_bwd_data(ctx.desc, dy, ws, tuple(x.shape), ctx.wt_ahead) if ctx.needs_input_grad[0] else None
+    if rest is not None:
+        (dws, dbias), = rest()
     return dx, dbias, dws
 
 
@@ -474,17 +455,7 @@ class HyperConvFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, bias, stride, padding, dilation, *ws):
-        algebra = len(ws)
-        k = tuple(ws[0].shape[2:])
-        desc = make_conv_desc(tuple(x.shape), ws[0].shape[0] * algebra, algebra, k, stride, padding, dilation)
-        x = _req(x, "x")
-        y = conv_fwd(desc, x, ws, bias)
-        ctx.desc = desc
-        ctx.has_bias = bias is not None
-        ctx.w_params, ctx.bias_param = ws, bias
-        ctx.wt_ahead = _transpose_ahead(desc, ws) if ctx.needs_input_grad[0] else None
-        ctx.save_for_backward(x)
-        return y
+        return _conv_forward(ctx, x, bias, ws, stride, padding, dilation)
 
     @staticmethod
     def backward(ctx, dy):
@@ -501,235 +472,9 @@ def hyper_conv(x, ws, bias, stride, padding, dilation):
 # ======================================================================================
 # 8-multiplication Hamilton product kernels (csrc/hcq_conv.hip)
 # ======================================================================================
-def hcq_pack_floats(desc, mode, nsets=1):
-    """Floats of the packed weight-form buffer, 0 if the fast-product kernel does not take this shape."""
-    return int(L.lib().seld_hcq_pack_floats(ctypes.byref(desc), int(mode), int(nsets)))
-
-
-class _HcqWeights:
-    """Packed weight forms of every (layer, direction) that runs on the fast-product kernels.
-
-    The forms depend on the weights only, so they are rebuilt when the weights change, not per call:
-      * `weights_changed()` (FlatAdam.step, anything that rewrites parameters behind torch's back) starts a new epoch;
-        the first request of an epoch re-packs EVERY registered entry in one launch (seld_hcq_pack_table);
-      * an in-place edit torch knows about (load_state_dict, an eager optimiser) shows in the tensors' version counters
-        and re-packs just the entry that is asked for;
-      * parameters that moved (Module.to, FlatAdam re-homing them into its flat buffer) are noticed by their pointers.
-    Entries hold weak references: a deleted model drops out at the next full re-pack."""
-
-    def __init__(self):
-        self.entries = {}
-        self.epoch = 0
-        self.packed_epoch = -1
-        self.table = None
-        self.table_dirty = True
-        self.max_floats = 0
-        self._esize = None
-
-    def weights_changed(self):
-        self.epoch += 1
-
-    def reset(self):
-        self.entries.clear()
-        self.table, self.table_dirty, self.packed_epoch = None, True, -1
-
-    class _Entry:
-        __slots__ = ("desc", "mode", "refs", "npair", "nA", "buf", "ptrs", "vers", "epoch", "host")
-
-    @staticmethod
-    def _alive(e):
-        ws = [r() for r in e.refs]
-        return None if any(w is None for w in ws) else ws
-
-    def _fill(self, e, ws):
-        """(Re)build the table entry of `e` from the weights' current addresses."""
-        lib = L.lib()
-        if self._esize is None:
-            self._esize = int(lib.seld_hcq_pack_entry_bytes())
-        host = ctypes.create_string_buffer(self._esize)
-        wsA, wsB = ws[:e.nA], (ws[e.nA:] if e.npair == 2 else None)
-        L.check(lib.seld_hcq_pack_entry(ctypes.byref(e.desc), e.mode, e.npair, L.ptr_array8(wsA),
-                                        L.ptr_array8(wsB) if wsB is not None else None, L.ptr(e.buf), host),
-                "seld_hcq_pack_entry")
-        e.host = host.raw
-        e.ptrs = tuple(w.data_ptr() for w in ws)
-        e.vers = None
-        e.epoch = -1
-        self.table_dirty = True
-
-    def refresh_table(self):
-        """Bring the device-side table up to date with the registered entries WITHOUT packing (host work + two small
-        host-to-device copies).  train.GraphedTrainStep calls it right before recording: entries registered during the
-        warm-up step left the table dirty, and the copies are not allowed inside a stream capture."""
-        return self._collect()[0]
-
-    def _collect(self):
-        dead = []
-        versions = {}
-        for key, e in self.entries.items():
-            if e is None:
-                continue
-            ws = self._alive(e)
-            if ws is None or any(not w.is_cuda for w in ws):
-                dead.append(key)
-                continue
-            if tuple(w.data_ptr() for w in ws) != e.ptrs:
-                self._fill(e, ws)
-            versions[id(e)] = tuple(w._version for w in ws)
-        for key in dead:
-            del self.entries[key]
-            self.table_dirty = True
-        live = [e for e in self.entries.values() if e is not None]
-        if live and self.table_dirty:
-            import numpy as np
-            raw = b"".join(e.host for e in live)
-            self.table = torch.from_numpy(np.frombuffer(raw, dtype=np.uint8).copy()).to(live[0].buf.device)
-            starts = np.zeros(len(live) + 1, dtype=np.int32)
-            starts[1:] = np.cumsum([(e.buf.numel() + 255) // 256 for e in live])
-            self.starts = torch.from_numpy(starts).to(live[0].buf.device)
-            self.total_blocks = int(starts[-1])
-            self.table_dirty = False
-        return live, versions
-
-    def _pack_all(self):
-        live, versions = self._collect()
-        if not live:
-            self.packed_epoch = self.epoch
-            return
-        L.check(L.lib().seld_hcq_pack_flat(L.ptr(self.table), L.ptr(self.starts), len(live), self.total_blocks,
-                                           L.current_stream()), "seld_hcq_pack_flat")
-        # the version counters the forms were built from: an in-place edit torch knows about (load_state_dict) between now
-        # and the entry's next request shows as a mismatch there and re-packs that entry (ADVICE r2: with None recorded
-        # here, an entry that was bulk-packed and then edited was served stale)
-        for e in live:
-            e.epoch, e.vers = self.epoch, versions[id(e)]
-        self.packed_epoch = self.epoch
-
-    def pin_for_graph(self):
-        """Everything a RECORDED seld_hcq_pack_flat launch points at: the table, the block starts and the entries' form
-        buffers as they are now.  `_pack_all` never edits a table in place -- it builds new tensors when an entry is added
-        -- so a recorded step that holds these references keeps replaying against valid memory whatever shapes are
-        registered later (validation at another batch size, an eval-only pooling entry)."""
-        live = [e for e in self.entries.values() if e is not None]
-        return (self.table, getattr(self, "starts", None), [e.buf for e in live])
-
-    def get(self, desc, mode, wsA, wsB=None):
-        """Packed forms for (desc, mode) of the given component tensors, or None if the shape runs on the 16/48-product
-        kernels.  Fresh with respect to the weights as they are when the returned launch order is reached."""
-        import weakref
-        ws = list(wsA) + (list(wsB) if wsB is not None else [])
-        key = (bytes(desc), mode, tuple(id(w) for w in ws))
-        e = self.entries.get(key, 0)
-        if e is None:
-            return None
-        if e == 0 or self._alive(e) is None:
-            npair = 2 if wsB is not None else 1
-            n = hcq_pack_floats(desc, mode, npair) if all(w.is_cuda and w.dtype == torch.float32 and w.is_contiguous()
-                                                          for w in ws) else 0
-            if n == 0:
-                self.entries[key] = None
-                return None
-            e = self._Entry()
-            e.desc = L.ConvDesc.from_buffer_copy(bytes(desc))
-            e.mode, e.npair, e.nA = int(mode), npair, len(wsA)
-            e.refs = [weakref.ref(w) for w in ws]
-            e.buf = torch.empty(n, device=ws[0].device, dtype=torch.float32)
-            self._fill(e, ws)
-            self.entries[key] = e
-        ptrs = tuple(w.data_ptr() for w in ws)
-        if ptrs != e.ptrs:
-            self._fill(e, ws)
-        if self.packed_epoch != self.epoch:
-            self._pack_all()
-        vers = tuple(w._version for w in ws)
-        if e.epoch != self.epoch or (e.vers is not None and e.vers != vers):
-            wsA_, wsB_ = ws[:e.nA], (ws[e.nA:] if e.npair == 2 else None)
-            hcq_pack(desc, mode, wsA_, wsB_, out=e.buf)
-            e.epoch = self.epoch
-        e.vers = vers
-        return e.buf
-
-
-hcq_weights = _HcqWeights()
-
-
-# ---- the two branches of the two-stream model on two queues --------------------------------------------------------
-_branch = {"stream": None}
-
-
-def two_queue_branches():
-    """SELD_BRANCH_STREAMS=0 turns the second queue off (both branches then run one after the other on the caller's)."""
-    return os.environ.get("SELD_BRANCH_STREAMS", "1") != "0"
-
-
-def run_branches(fa, xa, fb, xb):
-    """(fa(xa), fb(xb)) with fb on a second HIP stream.  Used for the two ConvTC blocks of the two-stream model
-    (model.py:463-471: independent until their outputs are concatenated, and at 16 samples per GPU neither fills the
-    device by itself) and for the SED / DOA classifier heads (model.py:473-480: two chains of small-grid kernels).
-    Autograd replays each branch's backward on the stream its forward ran on and orders the streams at the fork and
-    the join; the weight forms are packed BEFORE the fork (they are packed once per step, by whoever asks first)."""
-    if not (xa.is_cuda and two_queue_branches()):
-        return fa(xa), fb(xb)
-    if hcq_weights.packed_epoch != hcq_weights.epoch:
-        hcq_weights._pack_all()
-    main = torch.cuda.current_stream()
-    if _branch["stream"] is None:
-        _branch["stream"] = torch.cuda.Stream()
-    sb = _branch["stream"]
-    sb.wait_stream(main)
-    xb.record_stream(sb)
-    ya = fa(xa)                      # host order A, B as on one queue: the dropout counters are drawn in the same order
-    with torch.cuda.stream(sb):
-        yb = fb(xb)
-    main.wait_stream(sb)
-    yb.record_stream(main)
-    return ya, yb
-
-
-class FanOut2Fn(torch.autograd.Function):
-    """x -> (x, x) for a tensor with two consumers (the SED and DOA heads, model.py:473-480): the sum of the two
-    gradients is this library's add kernel on the consumer's stream instead of the autograd engine's ATen add."""
-
-    @staticmethod
-    def forward(ctx, x):
-        return x.view_as(x), x.view_as(x)
-
-    @staticmethod
-    def backward(ctx, ga, gb):
-        if ga is None or gb is None:
-            return ga if gb is None else gb
-        ga, gb = _req(ga, "ga"), _req(gb, "gb")
-        out = torch.empty_like(ga)
-        L.check(L.lib().seld_add(L.ptr(ga), L.ptr(gb), ga.numel(), L.ptr(out), L.current_stream()), "seld_add")
-        return out
-
-
-def fan_out2(x):
-    if not (x.is_cuda and x.requires_grad and torch.is_grad_enabled()):
-        return x, x
-    return FanOut2Fn.apply(x)
-
-
-L._reload_hooks.append(hcq_weights.reset)       # the forms are packed for the kernels the switches selected
-
-
 @memo
 def hcq_label(desc, mode, npair=1):
     return kernel_label(L.lib().seld_hcq_kernel_label, ctypes.byref(desc), int(mode), int(npair), size=96)
-
-
-def hcq_pack(desc, mode, wsA, wsB=None, out=None):
-    """Weight forms F_m(W) in MFMA fragment order (seld_hcq_pack): mode 0 forward, 1 data gradient."""
-    nsets = 2 if wsB is not None else 1
-    n = hcq_pack_floats(desc, mode, nsets)
-    if n == 0:
-        return None
-    if out is None:
-        out = torch.empty(n, device=wsA[0].device, dtype=torch.float32)
-    L.check(L.lib().seld_hcq_pack(ctypes.byref(desc), int(mode), nsets, L.ptr_array8([_req(w, "w") for w in wsA]),
-                                  L.ptr_array8([_req(w, "w") for w in wsB]) if wsB is not None else None, L.ptr(out),
-                                  L.current_stream()), "seld_hcq_pack")
-    return out
 
 
 def _ptr2(a, b=None):
@@ -761,17 +506,7 @@ class HyperConvAddFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, bias, addend, stride, padding, dilation, *ws):
-        algebra = len(ws)
-        k = tuple(ws[0].shape[2:])
-        desc = make_conv_desc(tuple(x.shape), ws[0].shape[0] * algebra, algebra, k, stride, padding, dilation)
-        x = _req(x, "x")
-        y = conv_fwd(desc, x, ws, bias, epilogue=L.SELD_EPI_ADD, addend=addend)
-        ctx.desc = desc
-        ctx.has_bias = bias is not None
-        ctx.w_params, ctx.bias_param = ws, bias
-        ctx.wt_ahead = _transpose_ahead(desc, ws) if ctx.needs_input_grad[0] else None
-        ctx.save_for_backward(x)
-        return y
+        return _conv_forward(ctx, x, bias, ws, stride, padding, dilation, epilogue=L.SELD_EPI_ADD, addend=addend)
 
     @staticmethod
     def backward(ctx, dy):
@@ -786,11 +521,6 @@ def hyper_conv_add(x, ws, bias, addend, stride, padding, dilation):
 # ======================================================================================
 # two convolutions of one geometry on the same input in one launch
 # ======================================================================================
-@memo
-def _pair_ok(desc, which):
-    return bool(L.lib().seld_hc_conv_pair_supported(ctypes.byref(desc), which))
-
-
 class HyperConvPairFn(torch.autograd.Function):
     """(yA, yB) = (WA (x) x [+ addA], WB (x) x [+ addB]): conv1_filter | conv1_gate (model.py:121-122) and
     conv2_skip | conv2_residual (model.py:130-132, 210-212) of a residual block, one launch each way
@@ -828,11 +558,9 @@ class HyperConvPairFn(torch.autograd.Function):
                 conv_fwd(desc, x, wsB, biasB, out=yB, epilogue=epiB, addend=addB, stats=kstB)
             else:
                 L.check(rc, "seld_hc_conv_pair_fwd")
-        if det_stats:
-            if statsA is not None:
-                channel_stats(yA, out=statsA)
-            if statsB is not None:
-                channel_stats(yB, out=statsB)
+        for y, stats in ((yA, statsA), (yB, statsB)) if det_stats else ():
+            if stats is not None:
+                channel_stats(y, out=stats)
         ctx.desc, ctx.algebra = desc, algebra
         ctx.params = (wsA, wsB, biasA, biasB)
         ctx.wt_ahead = None
@@ -844,75 +572,14 @@ class HyperConvPairFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dyA, dyB):
-        (x,) = ctx.saved_tensors
-        desc, A = ctx.desc, ctx.algebra
+        (x,), desc = ctx.saved_tensors, ctx.desc
         wsA, wsB, biasA, biasB = ctx.params
         dyA, dyB = _req(dyA, "dy"), _req(dyB, "dy")
-        lib = L.lib()
-        dx = None
-        if ctx.needs_input_grad[0]:
-            wp = hcq_weights.get(desc, 1, wsA, wsB) if A > 1 else None
-            if wp is not None:                       # sum of both data gradients in one launch
-                dx = torch.empty(tuple(x.shape), device=x.device, dtype=torch.float32)
-                with _timed(desc, 1, 2, label=lambda: hcq_label(desc, 1, 2)):
-                    hcq_conv(desc, 1, dyA, wp, (dx,), x2=dyB)
-            elif _pair_ok(desc, 1) and ctx.wt_ahead is not None:
-                (wtA, evA), (wtB, evB) = ctx.wt_ahead
-                dx = torch.empty(tuple(x.shape), device=x.device, dtype=torch.float32)
-                torch.cuda.current_stream().wait_event(evA)
-                torch.cuda.current_stream().wait_event(evB)
-                with _timed(desc, 1, 2):
-                    L.check(lib.seld_hc_conv_pair_bwd_data_wt(ctypes.byref(desc), L.ptr(dyA), L.ptr(dyB), L.ptr(wtA),
-                                                              L.ptr(wtB), L.ptr(dx), L.current_stream()),
-                            "seld_hc_conv_pair_bwd_data_wt")
-            elif _pair_ok(desc, 1):
-                dx = torch.empty(tuple(x.shape), device=x.device, dtype=torch.float32)
-                nbytes = 2 * lib.seld_hc_conv_bwd_data_workspace(ctypes.byref(desc))
-                wsb = torch.empty((nbytes + 3) // 4, device=x.device, dtype=torch.float32)
-                with _timed(desc, 1, 2):
-                    L.check(lib.seld_hc_conv_pair_bwd_data(ctypes.byref(desc), L.ptr(dyA), L.ptr(dyB),
-                                                           L.ptr_array8(list(wsA)), L.ptr_array8(list(wsB)), L.ptr(dx),
-                                                           L.ptr(wsb), nbytes, L.current_stream()),
-                            "seld_hc_conv_pair_bwd_data")
-            else:
-                dx = conv_bwd_data(desc, dyA, wsA, tuple(x.shape))
-                dx += conv_bwd_data(desc, dyB, wsB, tuple(x.shape))
-        need_w = any(ctx.needs_input_grad[11:]) or ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
-        dwsA, dwsB, dbA, dbB = [None] * A, [None] * A, None, None
-        if need_w:
-            dirA, dirB = _direct_targets(wsA, biasA), _direct_targets(wsB, biasB)
-            if dirA is not None and dirB is not None and dirA[1] is None and dirB[1] is None and deferred_wgrads.takes(desc):
-                deferred_wgrads.add(desc, x, dyA, dirA[0])
-                deferred_wgrads.add(desc, x, dyB, dirB[0])
-            elif dirA is not None and dirB is not None and dirA[1] is None and dirB[1] is None and _hcq_wgrad_ok(desc, 2):
-                def pair_wgrad_fast():
-                    hcq_wgrad_acc(desc, x, dyA, dirA[0], dyB, dirB[0])
-                if _side_enabled():
-                    _on_side_stream(pair_wgrad_fast, x, dyA, dyB)
-                else:
-                    pair_wgrad_fast()
-            elif dirA is not None and dirB is not None and _pair_ok(desc, 2) and not deterministic():
-                def pair_wgrad():
-                    with _timed(desc, 2, 2):
-                        L.check(lib.seld_hc_conv_pair_bwd_weight_acc(ctypes.byref(desc), L.ptr(x), L.ptr(dyA), L.ptr(dyB),
-                                                                     L.ptr_array8(dirA[0]), L.ptr_array8(dirB[0]),
-                                                                     L.ptr(dirA[1]), L.ptr(dirB[1]), L.current_stream()),
-                                "seld_hc_conv_pair_bwd_weight_acc")
-                if _side_enabled():
-                    _on_side_stream(pair_wgrad, x, dyA, dyB)
-                else:
-                    pair_wgrad()
-            else:
-                for ws_, b_, dy_, tgt in ((wsA, biasA, dyA, "A"), (wsB, biasB, dyB, "B")):
-                    d_ = _direct_targets(ws_, b_)
-                    if d_ is not None:
-                        conv_bwd_weight(desc, x, dy_, tuple(ws_[0].shape), b_ is not None, into=d_[0], bias_into=d_[1])
-                    else:
-                        g, gb = conv_bwd_weight(desc, x, dy_, tuple(ws_[0].shape), b_ is not None)
-                        if tgt == "A":
-                            dwsA, dbA = g, gb
-                        else:
-                            dwsB, dbB = g, gb
+        dx = conv_pair_bwd_data(desc, dyA, dyB, wsA, wsB, tuple(x.shape), ctx.wt_ahead) if ctx.needs_input_grad[0] else None
+        grads = [([None] * ctx.algebra, None)] * 2
+        if any(ctx.needs_input_grad[11:]) or ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
+            grads = _route_wgrads(desc, x, [(dyA, wsA, biasA), (dyB, wsB, biasB)], ctx.needs_input_grad[0])()
+        (dwsA, dbA), (dwsB, dbB) = grads
         return (dx, dbA, dbB, dyA if ctx.needs_input_grad[3] else None, dyB if ctx.needs_input_grad[4] else None,
                 None, None, None, None, None, None, *dwsA, *dwsB)
 
@@ -934,7 +601,6 @@ def hyper_conv_pair(x, wsA, biasA, wsB, biasB, stride, padding, dilation, addA=N
         y = hyper_conv(x, ws, bias, stride, padding, dilation) if add is None else \
             hyper_conv_add(x, ws, bias, add, stride, padding, dilation)
         if stats is not None:
-            N, C, S = _ncs(y)
-            L.check(L.lib().seld_channel_stats(L.ptr(y), N, C, S, L.ptr(stats), L.current_stream()), "seld_channel_stats")
+            channel_stats(y, out=stats)
         return y
     return one(wsA, biasA, addA, statsA), one(wsB, biasB, addB, statsB)

@@ -6,9 +6,11 @@ import torch
 
 from .. import _lib as L
 from ._core import _req, deterministic, kernel_timer, memo
-from .conv import (_conv_backward, _side, _side_enabled, _timed, _transpose_ahead, _y_shape, conv_fwd, conv_out_shape,
-                   hcq_label, hcq_pack_floats, hcq_weights, hyper_conv, make_conv_desc)
+from .conv import (_conv_backward, _conv_forward, _timed, _y_shape, conv_fwd, conv_out_shape, hcq_label, hyper_conv,
+                   make_conv_desc)
 from .norm_act import _claim_grad_slots, _direct_targets, _nbt, axpy_, bn_prepare, dropout, new_stats, philox
+from .streams import _side_enabled, side_queue
+from .weight_forms import hcq_pack_floats, hcq_weights
 
 
 # ======================================================================================
@@ -20,17 +22,9 @@ class HyperConvStatsFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, bias, stride, padding, dilation, *ws):
-        algebra = len(ws)
-        k = tuple(ws[0].shape[2:])
-        desc = make_conv_desc(tuple(x.shape), ws[0].shape[0] * algebra, algebra, k, stride, padding, dilation)
         x = _req(x, "x")
-        stats = new_stats(desc.Cout, x.device)
-        y = conv_fwd(desc, x, ws, bias, epilogue=L.SELD_EPI_STATS, stats=stats)
-        ctx.desc = desc
-        ctx.has_bias = bias is not None
-        ctx.w_params, ctx.bias_param = ws, bias
-        ctx.wt_ahead = _transpose_ahead(desc, ws) if ctx.needs_input_grad[0] else None
-        ctx.save_for_backward(x)
+        stats = new_stats(ws[0].shape[0] * len(ws), x.device)
+        y = _conv_forward(ctx, x, bias, ws, stride, padding, dilation, epilogue=L.SELD_EPI_STATS, stats=stats)
         ctx.mark_non_differentiable(stats)
         ctx.set_materialize_grads(False)        # no zero-filled "gradient" of the statistics buffer per backward pass
         return y, stats
@@ -47,6 +41,15 @@ def hyper_conv_stats(x, ws, bias, stride, padding, dilation):
     return HyperConvStatsFn.apply(x, bias, stride, padding, dilation, *ws)
 
 
+def _draw_dropout(ctx, drop_p, like):
+    """(p, seed, offset, step state) of Dropout(drop_p) on `like`, drawn as a DropoutFn would here and kept in ctx.rng for
+    the backward pass; the kernels' "no dropout" arguments for drop_p == 0."""
+    if drop_p <= 0.0:
+        return 0.0, 0, 0, None
+    ctx.rng = (float(drop_p),) + philox.draw((like.numel() + 3) // 4, like.device)
+    return ctx.rng
+
+
 class BnReluPoolFn(torch.autograd.Function):
     """[Dropout(drop_p)](MaxPool2d(ph, pw)(ReLU(BatchNorm2d(y)))) in one pass each way (model.py:278-282)."""
 
@@ -58,13 +61,8 @@ class BnReluPoolFn(torch.autograd.Function):
         pooled = torch.empty((N, C, Hh // ph, Ww // pw), device=y.device, dtype=torch.float32)
         idx = torch.empty(pooled.shape, device=y.device, dtype=torch.uint8)
         ctx.rng = None
-        out = None
-        p_, seed, off, state = 0.0, 0, 0, None
-        if drop_p > 0.0:           # same draw as a DropoutFn on `pooled` at this point
-            p_ = float(drop_p)
-            seed, off, state = philox.draw((pooled.numel() + 3) // 4, y.device)
-            out = torch.empty_like(pooled)
-            ctx.rng = (p_, seed, off, state)
+        p_, seed, off, state = _draw_dropout(ctx, drop_p, pooled)
+        out = torch.empty_like(pooled) if p_ > 0.0 else None
         L.check(L.lib().seld_bn_relu_pool_fwd_drop(L.ptr(y), N, C, Hh, Ww, ph, pw, L.ptr(mean), L.ptr(invstd),
                                                    L.ptr(gamma), L.ptr(beta), L.ptr(pooled), L.ptr(idx), p_, seed, off,
                                                    L.ptr(state), L.ptr(out),
@@ -127,23 +125,14 @@ class ConvBnReluPoolFn(torch.autograd.Function):
         # stream WHILE the main stream packs, and joined before BatchNorm is evaluated from them.
         gws = early = None
         if (ph == 8 and algebra > 1 and training and _side_enabled() and not kernel_timer.active and
-                hcq_weights.packed_epoch != hcq_weights.epoch and _first_stage_nostore(desc) and hcq_pack_floats(desc, 2) > 0):
+                hcq_weights.repack_pending() and _first_stage_nostore(desc) and hcq_pack_floats(desc, 2) > 0):
             # (only when a re-pack is pending -- the two-stream model packs before it forks its branches; timed steps keep the
             #  stage's launches on one stream, in one bracket)
-            if _side["stream"] is None:
-                _side["stream"] = torch.cuda.Stream()
-            st = _side["stream"]
             gws = torch.empty(_fs_bytes(desc, "gram"), device=x.device, dtype=torch.uint8)
-            fork = torch.cuda.Event()
-            fork.record(torch.cuda.current_stream())
-            st.wait_event(fork)
-            with torch.cuda.stream(st):
+            with side_queue.fork(gws, x):
                 L.check(L.lib().seld_first_stage_gram(ctypes.byref(desc), L.ptr(x), L.ptr(gws), gws.numel(),
                                                       L.current_stream()), "seld_first_stage_gram")
-                early = torch.cuda.Event()
-                early.record(st)
-            gws.record_stream(st)
-            x.record_stream(st)
+                early = side_queue.event()
         wp = hcq_weights.get(desc, 2, ws) if (ph == 8 and algebra > 1) else None
         if early is not None:
             torch.cuda.current_stream().wait_event(early)
@@ -156,33 +145,27 @@ class ConvBnReluPoolFn(torch.autograd.Function):
             lib = L.lib()
             o = conv_out_shape(desc)
             N, C, Hh, Ww = _y_shape(desc, o)
-            stage_timer = _timed(desc, 0, label="first_stage_fwd(gram+bn+finishing_pool_conv)")
-            stage_timer.__enter__()
-            if early is None:
-                gws = torch.empty(_fs_bytes(desc, "gram"), device=x.device, dtype=torch.uint8)
-                L.check(lib.seld_first_stage_gram(ctypes.byref(desc), L.ptr(x), L.ptr(gws), gws.numel(),
-                                                  L.current_stream()), "seld_first_stage_gram")
-            mean = torch.empty(C, device=x.device, dtype=torch.float32)
-            invstd = torch.empty(C, device=x.device, dtype=torch.float32)
-            wg = torch.empty((C, 72), device=x.device, dtype=torch.float32)
-            L.check(lib.seld_first_stage_bn(ctypes.byref(desc), L.ptr_array8([_req(w, "w") for w in ws]),
-                                            L.ptr(_req(bias, "bias")), L.ptr(gws), eps, momentum, L.ptr(mean),
-                                            L.ptr(invstd), L.ptr(running_mean), L.ptr(running_var), L.ptr(nbt),
-                                            L.ptr(wg), L.current_stream()), "seld_first_stage_bn")
-            # raw: written (and read by the backward pass) only for channels with gamma == 0; untouched memory otherwise
-            raw = torch.empty((N, C, Hh // ph, Ww), device=x.device, dtype=torch.float32)
-            idx = torch.empty(raw.shape, device=x.device, dtype=torch.uint8)
-            result = torch.empty_like(raw)
-            p_, seed, off, state = 0.0, 0, 0, None
-            if drop_p > 0.0:
-                p_ = float(drop_p)
-                seed, off, state = philox.draw((raw.numel() + 3) // 4, x.device)
-                ctx.rng = (p_, seed, off, state)
-            L.check(lib.seld_hcq_first_pool_bn(ctypes.byref(desc), L.ptr(x), L.ptr(wp), L.ptr(_req(bias, "bias")),
-                                               L.ptr(gamma), L.ptr(beta), L.ptr(mean), L.ptr(invstd), p_, seed, off,
-                                               L.ptr(state), L.ptr(raw), L.ptr(idx), L.ptr(result),
-                                               L.current_stream()), "seld_hcq_first_pool_bn")
-            stage_timer.__exit__(None, None, None)
+            with _timed(desc, 0, label="first_stage_fwd(gram+bn+finishing_pool_conv)"):
+                if early is None:
+                    gws = torch.empty(_fs_bytes(desc, "gram"), device=x.device, dtype=torch.uint8)
+                    L.check(lib.seld_first_stage_gram(ctypes.byref(desc), L.ptr(x), L.ptr(gws), gws.numel(),
+                                                      L.current_stream()), "seld_first_stage_gram")
+                mean = torch.empty(C, device=x.device, dtype=torch.float32)
+                invstd = torch.empty(C, device=x.device, dtype=torch.float32)
+                wg = torch.empty((C, 72), device=x.device, dtype=torch.float32)
+                L.check(lib.seld_first_stage_bn(ctypes.byref(desc), L.ptr_array8([_req(w, "w") for w in ws]),
+                                                L.ptr(_req(bias, "bias")), L.ptr(gws), eps, momentum, L.ptr(mean),
+                                                L.ptr(invstd), L.ptr(running_mean), L.ptr(running_var), L.ptr(nbt),
+                                                L.ptr(wg), L.current_stream()), "seld_first_stage_bn")
+                # raw: written (and read by the backward pass) only for channels with gamma == 0; untouched memory otherwise
+                raw = torch.empty((N, C, Hh // ph, Ww), device=x.device, dtype=torch.float32)
+                idx = torch.empty(raw.shape, device=x.device, dtype=torch.uint8)
+                result = torch.empty_like(raw)
+                p_, seed, off, state = _draw_dropout(ctx, drop_p, raw)
+                L.check(lib.seld_hcq_first_pool_bn(ctypes.byref(desc), L.ptr(x), L.ptr(wp), L.ptr(_req(bias, "bias")),
+                                                   L.ptr(gamma), L.ptr(beta), L.ptr(mean), L.ptr(invstd), p_, seed, off,
+                                                   L.ptr(state), L.ptr(raw), L.ptr(idx), L.ptr(result),
+                                                   L.current_stream()), "seld_hcq_first_pool_bn")
             ctx.desc, ctx.geom = desc, (N, C, Hh, Ww, ph, training)
             ctx.params = (ws, bias, gamma, beta)
             ctx.gram = (gws, wg)
@@ -202,13 +185,8 @@ class ConvBnReluPoolFn(torch.autograd.Function):
                                                     L.ptr(idx), L.current_stream()), "seld_hcq_first_pool")
             mean, invstd = bn_prepare(y, running_mean, running_var, training, momentum, eps, stats, nbt)
             pooled = torch.empty_like(raw)
-            out = None
-            p_, seed, off, state = 0.0, 0, 0, None
-            if drop_p > 0.0:           # the stage's Dropout in the same pass (same mask as a DropoutFn at this point would draw)
-                p_ = float(drop_p)
-                seed, off, state = philox.draw((pooled.numel() + 3) // 4, x.device)
-                out = torch.empty_like(raw)
-                ctx.rng = (p_, seed, off, state)
+            p_, seed, off, state = _draw_dropout(ctx, drop_p, pooled)       # the stage's Dropout in the same pass
+            out = torch.empty_like(raw) if p_ > 0.0 else None
             L.check(L.lib().seld_bn_pool_finish(L.ptr(raw), N, C, (Hh // ph) * Ww, L.ptr(mean), L.ptr(invstd),
                                                 L.ptr(gamma), L.ptr(beta), L.ptr(pooled), p_, seed, off, L.ptr(state),
                                                 L.ptr(out), L.current_stream()),
@@ -224,11 +202,10 @@ class ConvBnReluPoolFn(torch.autograd.Function):
                     "seld_bn_relu_pool_fwd")
             out = None
             if drop_p > 0.0:
-                seed, off, state = philox.draw((pooled.numel() + 3) // 4, x.device)
+                p_, seed, off, state = _draw_dropout(ctx, drop_p, pooled)
                 out = torch.empty_like(pooled)
                 L.check(L.lib().seld_dropout_fwd(L.ptr(pooled), pooled.numel(), drop_p, seed, off, L.ptr(state),
                                                  L.ptr(out), L.current_stream()), "seld_dropout_fwd")
-                ctx.rng = (float(drop_p), seed, off, state)
         ctx.desc, ctx.geom = desc, (N, C, Hh, Ww, ph, training)
         ctx.params = (ws, bias, gamma, beta)
         ctx.save_for_backward(x, y, pooled, idx, mean, invstd)

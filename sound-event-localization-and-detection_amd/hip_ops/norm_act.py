@@ -1,5 +1,5 @@
 """BatchNorm + activation, the gate, activations, pooling, dropout and transposes (csrc/nn_ops.hip), and the optimiser's
-gradient slots as the backward kernels' targets."""
+gradient slots as the backward kernels' targets, with the stacked / reshaped convolution weights that point at them."""
 import os
 
 import torch
@@ -109,6 +109,52 @@ def _direct_targets(params, bias):
             return g if g is not None else b.grad.view(t.shape)
         return [slot(b, t) for b, t in zip(ts, params)], (bias.grad if bias is not None else None)
     return None
+
+
+def stacked_conv_weight(params):
+    """ONE convolution weight (sum of the Cout's, Cin, k...) over parameters that lie back to back in memory -- FlatAdam
+    re-homes a model's parameters into one flat buffer in registration order, so the attention's values / keys / queries
+    (model.py:18-20) are three consecutive row blocks of it -- or None.  With gradients enabled the gradient slots must be
+    adjacent in the same order too: the stacked weight is a fresh leaf over the same storage whose gradient the backward
+    kernels write straight into those slots (`_direct_targets`), so autograd never sees the member parameters."""
+    p0 = params[0]
+    need_grad = torch.is_grad_enabled() and any(p.requires_grad for p in params)
+    at = p0.data_ptr()
+    for p in params:
+        if p.data_ptr() != at or not p.is_contiguous() or p.shape[1:] != p0.shape[1:] or p.dtype != torch.float32:
+            return None
+        at += 4 * p.numel()
+    shape = (sum(int(p.shape[0]) for p in params),) + tuple(p0.shape[1:])
+    same_buffer = lambda ts: all(t.untyped_storage().data_ptr() == ts[0].untyped_storage().data_ptr() for t in ts)
+    if not same_buffer(params):                     # neighbours by accident of the allocator: not one tensor's memory
+        return None
+    gview = None
+    if need_grad:
+        if not all(getattr(p, "_seld_direct_grad", False) and p.grad is not None and p.requires_grad for p in params):
+            return None
+        if not same_buffer([p.grad for p in params]):
+            return None
+        gat = p0.grad.data_ptr()
+        for p in params:
+            if p.grad.data_ptr() != gat or not p.grad.is_contiguous():
+                return None
+            gat += 4 * p.numel()
+        gview = p0.grad.as_strided(shape, p0.grad.stride())
+    w = p0.detach().as_strided(shape, p0.stride())
+    if need_grad:
+        w.requires_grad_(True)
+        w._seld_base_param = p0
+        w._seld_grad = gview
+    return w
+
+
+def as_conv_weight(param, shape):
+    """A contiguous reshape of a parameter used as a convolution weight (the attention's Linear applied as a 1x1
+    convolution, model.py:46): the view remembers its parameter, so the backward kernels write that parameter's gradient
+    slot directly instead of returning a tensor for autograd to add to it."""
+    w = param.view(shape)
+    w._seld_base_param = param
+    return w
 
 
 def axpy_(dst_first, src, n):

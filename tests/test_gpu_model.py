@@ -277,9 +277,7 @@ def test_side_stream_lag_does_not_corrupt_gradients(monkeypatch):
         sed, doa = m(x)
         loss = T.seld_loss_fn(sed, doa, target, n_sed, 1.0, 5.0)
         if lag:
-            if H._side["stream"] is None:
-                H._side["stream"] = torch.cuda.Stream()
-            with torch.cuda.stream(H._side["stream"]):
+            with torch.cuda.stream(H.side_queue.stream()):
                 torch.cuda._sleep(400_000_000)          # ~0.2 s: the main stream finishes its whole backward first
         loss.backward()
         H.join_side_stream()
@@ -317,9 +315,7 @@ def test_two_stream_branches_on_two_queues_match_one_queue(name, monkeypatch):
         for step in range(2):
             opt.zero_grad()
             if two_queues and step == 0:
-                if H._branch["stream"] is None:
-                    H._branch["stream"] = torch.cuda.Stream()
-                with torch.cuda.stream(H._branch["stream"]):
+                with torch.cuda.stream(H.branch_queue.stream()):
                     torch.cuda._sleep(200_000_000)       # ~0.1 s: whatever the main queue does not wait for, it now overtakes
             sed, doa = m(x)
             loss = T.seld_loss_fn(sed, doa, target, n_sed, 1.0, 5.0)

@@ -104,28 +104,26 @@ def race():
     target = train_target(case).to(DEV)
 
     class NoKeep(list):
-        def append(self, t):
+        def extend(self, ts):
             pass
 
     def grads(side, lag, keep=True):
         os.environ["SELD_WGRAD_SIDE_STREAM"] = "1" if side else "0"
-        saved = H._side["keep"]
+        saved = H.side_queue.keep
         if not keep:
-            H._side["keep"] = NoKeep()
+            H.side_queue.keep = NoKeep()
         m = prepared(case).train()
         opt = T.FlatAdam(m.parameters(), lr=1e-4)
         opt.zero_grad()
         sed, doa = m(x)
         loss = T.seld_loss_fn(sed, doa, target, 42, 1.0, 5.0)
         if lag:
-            if H._side["stream"] is None:
-                H._side["stream"] = torch.cuda.Stream()
-            with torch.cuda.stream(H._side["stream"]):
+            with torch.cuda.stream(H.side_queue.stream()):
                 torch.cuda._sleep(400_000_000)
         loss.backward()
         H.join_side_stream()
         torch.cuda.synchronize()
-        H._side["keep"] = saved
+        H.side_queue.keep = saved
         return opt.flat_grad.detach().clone()
     ref = grads(False, False)
     for keep in (True, False):
