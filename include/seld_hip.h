@@ -880,6 +880,34 @@ int seld_encode_events(const int32_t* first_frame, const int32_t* last_frame, co
 int seld_segment(const void* src, int32_t dtype, int32_t layout, int64_t rows, int64_t length, int64_t seg_len,
                  int64_t hop, int64_t segments, void* dst, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Device-resident epoch loader (csrc/loader.hip): what a training step needs from a DataLoader over resident arrays,
+ * as two launches that can be recorded in a HIP graph.  Neither allocates nor synchronises.
+ *
+ * seld_gather_rows fetches one minibatch.  For b in [0, count):
+ *     p = (cursor ? cursor[0] * cursor_stride : 0) + start + b
+ *     out_x[b, :] = x_all[index[p], :]        out_y[b, :] = y_all[index[p], :]
+ *   x_all (n_rows, row_x), y_all (n_rows, row_y), out_x (B, row_x), out_y (B, row_y): contiguous fp32; index: n_index
+ *   int64 on the device; cursor: ONE int32 on the device that the kernel reads, so a recorded launch fetches another
+ *   batch at every replay with no host write in between (NULL: only `start` selects).  Either the x or the y pair may be
+ *   NULL (both pointers of the pair).  Output rows [count, B) are not touched.
+ *   A position p outside [0, n_index) or an index[p] outside [0, n_rows) reads nothing and ZERO-FILLS its output
+ *   rows: a defined, fault-free result (a cursor that ran past the epoch yields zero batches).
+ *   16-byte loads and stores where a row's source and destination are 16-byte aligned together, single floats before
+ *   and behind that part, and for a row whose two sides are aligned differently.
+ *   SELD_EINVAL: index NULL, neither pair given, half a pair, a non-positive n_index / n_rows / row length / B / count,
+ *   count > B, count > 65535, a negative cursor_stride.  Nothing is launched on refusal.
+ * seld_epoch_step_end, one thread, as the last launch of a step:
+ *     mean[0] += (loss[0] - mean[0]) / (float)(cursor[0] + 1);   cursor[0] += 1          (fp32: the epoch loop's
+ *   running mean of the loss, train.py:559, in the form train.main takes it)
+ *   loss, mean: device fp32 scalars; cursor: the device int32 above.  An epoch is then n replays with no host-to-device
+ *   traffic and no read-back.  SELD_EINVAL: a NULL pointer.
+ * ------------------------------------------------------------------------------------------ */
+int seld_gather_rows(const float* x_all, int64_t row_x, float* out_x, const float* y_all, int64_t row_y, float* out_y,
+                     const int64_t* index, int64_t n_index, int64_t n_rows, const int32_t* cursor, int64_t cursor_stride,
+                     int64_t start, int32_t B, int32_t count, void* stream);
+int seld_epoch_step_end(const float* loss, float* mean, int32_t* cursor, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

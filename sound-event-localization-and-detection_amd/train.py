@@ -195,12 +195,20 @@ class GraphedTrainStep:
         A  zero_grad, forward, loss, backward down to the front-end cut    -> all-reduce of the big bucket (async)
         B  backward of the front-end convolutions (overlaps that all-reduce) -> all-reduce of the late bucket
         C  Adam on the averaged gradients
-    The batch is static: `__call__(x, target)` copies into the recorded input buffers (same shapes)."""
+    The batch is static: `__call__(x, target)` copies into the recorded input buffers (same shapes).
 
-    def __init__(self, model, optimizer, x, target, n_sed, sed_weight=1.0, doa_weight=5.0, sync=None, warmup=2):
-        self.model, self.opt, self.sync = model, optimizer, sync
+    `loader` (a ResidentLoader; default None: everything above): the recorded input buffers ARE the loader's batch
+    buffers, the loader's gather is recorded as the first launch of the step and its `step_end` (running mean of the
+    loss, cursor += 1) as the last, so `__call__()` with no arguments trains on the next batch of the epoch: an epoch
+    is n replays with no host-to-device traffic.  `x` / `target` are then not copied (pass the loader's buffers)."""
+
+    def __init__(self, model, optimizer, x, target, n_sed, sed_weight=1.0, doa_weight=5.0, sync=None, warmup=2, loader=None):
+        self.model, self.opt, self.sync, self.loader = model, optimizer, sync, loader
         self.n_sed, self.w = n_sed, (float(sed_weight), float(doa_weight))
-        self.x, self.target = x.clone(), target.clone()
+        if loader is None:
+            self.x, self.target = x.clone(), target.clone()
+        else:
+            self.x, self.target = loader.x, loader.target
         self.state = H.philox.state(x.device)
         self.cut = sync.cut if (sync is not None and getattr(sync, "cut", None) is not None and sync.world > 1) else None
         self._lr = None
@@ -269,6 +277,8 @@ class GraphedTrainStep:
         return loss
 
     def _phase_a(self):
+        if self.loader is not None:
+            self.loader.fetch()
         self.opt.zero_grad(state=self.state)
         if self.cut is not None:
             self.cut.reset()
@@ -285,6 +295,8 @@ class GraphedTrainStep:
 
     def _phase_c(self):
         self.opt.step(grad_scale=self.sync.average_scale() if self.sync is not None else 1.0, state=self.state)
+        if self.loader is not None:
+            self.loader.step_end(self.loss)
 
     def __call__(self, x=None, target=None):
         if x is not None:
@@ -401,9 +413,13 @@ _FLAGS = [
     ('TextArgs', str, 'config/Test.txt'),
 ]
 _EVAL = ('use_cuda', 'early_stopping', 'fixed_seed', 'pool_size', 'cnn_filters', 'verbose', 'D', 'V', 'use_lr_scheduler',
-         'phase', 'use_tcn', 'use_bias_conv', 'use_bias_linear', 'fc_layers', 'parallel_magphase')
-# extensions of this implementation (not in the reference): synthetic data so the step can run without L3DAS21
-_EXTRA = [('synthetic', int, 0), ('max_steps', int, 0), ('epochs', int, 0)]
+         'phase', 'use_tcn', 'use_bias_conv', 'use_bias_linear', 'fc_layers', 'parallel_magphase',
+         'resident_loader', 'graph_step')
+# extensions of this implementation (not in the reference): synthetic data so the step can run without L3DAS21;
+# resident_loader: minibatches gathered on the device (ResidentLoader) instead of a DataLoader over the resident arrays;
+# graph_step (needs resident_loader): full batches run as replays of one recorded step (GraphedTrainStep)
+_EXTRA = [('synthetic', int, 0), ('max_steps', int, 0), ('epochs', int, 0), ('resident_loader', str, 'False'),
+          ('graph_step', str, 'False')]
 
 
 def build_parser():
@@ -603,6 +619,119 @@ def load_pickled(pred_path, target_path):
     return torch.tensor(x).float(), torch.tensor(y).float()
 
 
+def epoch_plan(n, batch_size, world=1):
+    """The minibatches of one epoch over n samples as (start, count_per_rank, graphable) triples: the batch covers
+    positions [start, start + world * count_per_rank) of the epoch's sample order and rank r takes
+    `rank_rows(start, count_per_rank, r)` of them.  `batch_size` is the GLOBAL batch.  Full batches are graphable (they
+    have the recorded shape); the last one may be partial, as with the reference's drop_last=False, and is then cut
+    down to the largest multiple of `world` (fewer than `world` samples of the epoch are left out; a batch cut to
+    nothing is dropped)."""
+    n, batch_size, world = int(n), int(batch_size), int(world)
+    if n <= 0 or batch_size <= 0 or world <= 0:
+        raise ValueError(f"epoch_plan: n, batch_size and world must be positive, got {n}, {batch_size}, {world}")
+    if batch_size % world:
+        raise ValueError(f"global batch {batch_size} is not divisible by world size {world}")
+    per = batch_size // world
+    plan = [(start, per, True) for start in range(0, n - batch_size + 1, batch_size)]
+    rest = (n % batch_size) // world
+    if rest:
+        plan.append((n - n % batch_size, rest, False))
+    return plan
+
+
+def rank_rows(start, count_per_rank, rank):
+    """(first, last + 1) positions of the epoch's sample order that `rank` takes of the batch `(start, count_per_rank, _)`."""
+    return start + rank * count_per_rank, start + (rank + 1) * count_per_rank
+
+
+def epoch_left_out(n, batch_size, world=1):
+    """Samples per epoch that `epoch_plan` leaves out (always fewer than `world`)."""
+    return n - sum(world * c for _, c, _ in epoch_plan(n, batch_size, world))
+
+
+class ResidentLoader:
+    """What `DataLoader(TensorDataset(x_all, y_all), batch_size, shuffle)` does for arrays that are resident in HBM, on
+    the device: predictors AND targets live there, one permutation per epoch goes up as a single copy of n int64, and a
+    batch is ONE launch (hip_ops.gather_rows) into the static buffers `x` / `target`.  Which batch is next is the device
+    int32 `cursor`; `step_end(loss)` folds the loss into the device fp32 `mean` (the epoch loop's running mean) and
+    advances the cursor, so a recorded step (GraphedTrainStep(loader=...)) walks through the epoch by itself.
+
+    Sample order and RNG consumption are the DataLoader's: every epoch draws the iterator's base seed and, with
+    shuffle, the RandomSampler's seed from torch's default generator, so a run with this loader visits the samples in
+    the order a run with the DataLoader visits them.  Data parallel: `batch_size` is the global batch, this rank
+    gathers its `rank_rows` of every batch; rank 0's order is broadcast, so ranks agree whatever their RNG state."""
+
+    def __init__(self, x_all, y_all, batch_size, shuffle, rank=0, world=1):
+        self.plan = epoch_plan(x_all.shape[0], batch_size, world)
+        if y_all.shape[0] != x_all.shape[0]:
+            raise ValueError(f"ResidentLoader: {x_all.shape[0]} predictors but {y_all.shape[0]} targets")
+        dev = x_all.device
+        self.x_all, self.y_all = x_all.contiguous(), y_all.to(dev).contiguous()
+        self.n, self.batch_size, self.shuffle, self.rank, self.world = x_all.shape[0], int(batch_size), bool(shuffle), rank, world
+        per = self.batch_size // world
+        self.x = torch.zeros((per,) + tuple(x_all.shape[1:]), device=dev, dtype=torch.float32)
+        self.target = torch.zeros((per,) + tuple(y_all.shape[1:]), device=dev, dtype=torch.float32)
+        self.index = torch.arange(self.n, device=dev, dtype=torch.int64)
+        self.cursor = torch.zeros(1, device=dev, dtype=torch.int32)
+        self.mean = torch.zeros(1, device=dev, dtype=torch.float32)
+
+    def __len__(self):
+        return len(self.plan)
+
+    def begin_epoch(self):
+        """New sample order (outside any capture), cursor and mean back to zero."""
+        torch.empty((), dtype=torch.int64).random_()           # the base seed a DataLoader iterator draws first
+        if self.shuffle:
+            self.index.copy_(H.epoch_permutation(self.n))
+            if self.world > 1:
+                torch.distributed.broadcast(self.index, 0)
+        self.cursor.zero_()
+        self.mean.zero_()
+
+    def fetch(self, count=None, batch=None):
+        """Gather this rank's rows of a batch into `x` / `target` and return the views of the rows that were written.
+        batch None: the batch the device cursor points at (recordable); else that batch of the plan, whatever the cursor."""
+        count = self.x.shape[0] if count is None else count
+        if batch is None:
+            H.gather_rows(self.x_all, self.y_all, self.index, self.x, self.target, cursor=self.cursor,
+                          start=self.rank * count, count=count, stride=self.batch_size)
+        else:
+            H.gather_rows(self.x_all, self.y_all, self.index, self.x, self.target,
+                          start=rank_rows(self.plan[batch][0], count, self.rank)[0], count=count)
+        return self.x[:count], self.target[:count]
+
+    def step_end(self, loss):
+        H.epoch_step_end(loss, self.mean, self.cursor)
+
+    def __iter__(self):
+        """One epoch as (x, target) batches, like the DataLoader (evaluation loops).  The batches are views of the static
+        buffers: each is valid until the next one is taken."""
+        self.begin_epoch()
+        for i, (_, count, _) in enumerate(self.plan):
+            yield self.fetch(count, batch=i)
+
+
+def training_snapshot(model, optimizer):
+    """Everything a training step changes: weights, Adam moments and step count, every module buffer (BatchNorm running
+    statistics, num_batches_tracked) and the position of the dropout RNG stream."""
+    return dict(param=optimizer.flat_param.clone(), exp_avg=optimizer.exp_avg.clone(), exp_avg_sq=optimizer.exp_avg_sq.clone(),
+                step=optimizer.step_count, buffers=[b.clone() for b in model.buffers()], philox=H.philox.get_offset())
+
+
+def training_restore(model, optimizer, snap):
+    """Put back a `training_snapshot`, in place (recorded launches keep pointing at the same memory).  After
+    GraphedTrainStep's constructor, whose warm-up steps train: the run then starts from where it stood before."""
+    with torch.no_grad():
+        optimizer.flat_param.copy_(snap["param"])
+        optimizer.exp_avg.copy_(snap["exp_avg"])
+        optimizer.exp_avg_sq.copy_(snap["exp_avg_sq"])
+        for b, saved in zip(model.buffers(), snap["buffers"]):
+            b.copy_(saved)
+    optimizer.step_count = snap["step"]         # GraphedTrainStep.sync_from_host pushes it into the step state
+    H.philox.set_offset(snap["philox"])
+    H.hcq_weights.weights_changed()
+
+
 _NORM_OFF = {'False', 'false', 'None', 'none'}
 _NORM_UNIT = {'DQ_Normalization', 'UnitNormNormalization', 'UnitNorm'}
 _DOMAIN_DQ = ['DQ', 'dq', 'dQ', 'Dual_Quaternion', 'dual_quaternion']
@@ -721,17 +850,50 @@ def evaluate(model, device, criterion_sed, criterion_doa, loader, args):
     return total
 
 
-def main(args):
-    device = torch.device('cuda:' + str(args.gpu_id)) if args.use_cuda else None
-    if device is None or not torch.cuda.is_available():
+def main(args, history=None):
+    """The reference's training loop.  --resident_loader / --graph_step: see _EXTRA.  Started under
+    `python -m torch.distributed.run --nproc-per-node N` it trains data parallel (needs --resident_loader): --batch_size
+    is the global batch, every rank takes its share of each batch; validation, the test leg, checkpoints and printing
+    are rank 0's; the training loss it prints is the mean over the ranks.  `history`: a list that receives (epoch, train
+    loss, validation loss) per epoch, unrounded (rank 0).
+    SELD_DP_BACKEND=gloo with SELD_DP_SINGLE_DEVICE=1 puts every rank on --gpu_id over gloo (RCCL refuses two ranks on one
+    device): how a machine with one GPU runs the data-parallel loop, tests/test_gpu_train_loader.py included."""
+    from . import dp as DP
+    resident, graph_step = bool(args.resident_loader), bool(args.graph_step)
+    if graph_step and not resident:
+        raise ValueError("--graph_step needs --resident_loader")
+    if not args.use_cuda or not torch.cuda.is_available():
         raise RuntimeError("this implementation has no CPU path: a HIP device is required")
+    world = int(os.environ.get("WORLD_SIZE", "1"))
+    if world > 1:                                   # every refusal before any GPU work
+        if not resident or args.synthetic:
+            raise ValueError("data-parallel training (WORLD_SIZE > 1) needs --resident_loader and pickled arrays")
+        if world > 8:
+            raise ValueError(f"at most 8 ranks, got WORLD_SIZE={world}")
+        if args.batch_size % world:
+            raise ValueError(f"--batch_size {args.batch_size} (the global batch) is not divisible by the {world} ranks")
+    rank, local, world = DP.init_from_env(os.environ.get("SELD_DP_BACKEND"))
+    if os.environ.get("SELD_DP_SINGLE_DEVICE"):
+        local = args.gpu_id
+    device = torch.device('cuda:' + str(args.gpu_id))
+    if world > 1:
+        device = torch.device('cuda', local)
+        torch.cuda.set_device(device)
+    say = print if rank == 0 else (lambda *a, **k: None)
     if args.fixed_seed:
         np.random.seed(1)
         torch.manual_seed(1)
     model = model_from_args(args).to(device)
-    print('Total paramters: ' + str(sum(int(np.prod(p.size())) for p in model.parameters())))
+    say('Total paramters: ' + str(sum(int(np.prod(p.size())) for p in model.parameters())))
     criterion_sed, criterion_doa = BCELoss(), MSELoss()
-    optimizer = FlatAdam(model.parameters(), lr=args.lr)
+    sync = None
+    if world > 1:
+        DP.seed_rank_streams(rank)
+        optimizer = FlatAdam(model.parameters(), lr=args.lr, late=DP.late_parameters(model))
+        DP.broadcast_parameters(optimizer.flat_param)
+        sync = DP.BucketedGradSync(optimizer, model)
+    else:
+        optimizer = FlatAdam(model.parameters(), lr=args.lr)
     scheduler = StepLR(optimizer, args.lr_scheduler_step_size, args.lr_scheduler_gamma) if args.use_lr_scheduler else None
     n_out = int(args.output_classes * args.class_overlaps)
 
@@ -740,49 +902,112 @@ def main(args):
                 for i in range(args.synthetic)]
         tr_data, val_data = data, data[:1]
         test_data = None
+        if resident:
+            raise ValueError("--resident_loader reads pickled arrays: not with --synthetic")
     else:
-        xs, ys = load_pickled(args.training_predictors_path, args.training_target_path)
-        xv, yv = load_pickled(args.validation_predictors_path, args.validation_target_path)
-        xs, xv = xs.to(device), xv.to(device)           # 288 GB of HBM: the arrays stay resident, loaders index them
-        print(normalize_dataset(args, xs, xv))
-        tr_data = torch.utils.data.DataLoader(torch.utils.data.TensorDataset(xs, ys), args.batch_size, shuffle=True,
-                                              pin_memory=False)
-        val_data = torch.utils.data.DataLoader(torch.utils.data.TensorDataset(xv, yv), args.batch_size, shuffle=False,
+        def loader(x, y, batch_size, shuffle, rank=0, world=1):
+            if resident:
+                return ResidentLoader(x, y, batch_size, shuffle, rank, world)
+            return torch.utils.data.DataLoader(torch.utils.data.TensorDataset(x, y), batch_size, shuffle=shuffle,
                                                pin_memory=False)
-        test_data = None
-        if os.path.isfile(str(args.test_predictors_path)) and os.path.isfile(str(args.test_target_path)):
-            xt, yt = load_pickled(args.test_predictors_path, args.test_target_path)
-            xt = xt.to(device)
-            print(normalize_dataset(args, xt))
-            test_data = torch.utils.data.DataLoader(torch.utils.data.TensorDataset(xt, yt), 1, shuffle=False)
+        xs, ys = load_pickled(args.training_predictors_path, args.training_target_path)
+        xs = xs.to(device)                              # 288 GB of HBM: the arrays stay resident, loaders index them
+        val_data = test_data = None
+        if rank == 0:
+            xv, yv = load_pickled(args.validation_predictors_path, args.validation_target_path)
+            xv = xv.to(device)
+            print(normalize_dataset(args, xs, xv))
+        else:
+            normalize_dataset(args, xs)
+        tr_data = loader(xs, ys, args.batch_size, True, rank, world)
+        if rank == 0:
+            val_data = loader(xv, yv, args.batch_size, False)
+            if os.path.isfile(str(args.test_predictors_path)) and os.path.isfile(str(args.test_target_path)):
+                xt, yt = load_pickled(args.test_predictors_path, args.test_target_path)
+                xt = xt.to(device)
+                print(normalize_dataset(args, xt))
+                test_data = loader(xt, yt, 1, False)
+        if world > 1:
+            say(f"data parallel on {world} ranks: {epoch_left_out(xs.shape[0], args.batch_size, world)} of {xs.shape[0]} "
+                "samples per epoch left out (the last batch is cut to a multiple of the ranks)")
 
     model_dir = os.path.join(args.checkpoint_dir, model.model_name)
     os.makedirs(model_dir, exist_ok=True)
     state = {"step": 0, "worse_epochs": 0, "epochs": 0, "best_loss": np.inf, "best_epoch": 0, "best_test_epoch": 0}
     epoch = 0
     if args.load_model is not None and os.path.isfile(args.load_model):
-        print("Continuing training full model from checkpoint " + str(args.load_model))
+        say("Continuing training full model from checkpoint " + str(args.load_model))
         state = load_model(model, optimizer, args.load_model, args.use_cuda, device, scheduler)
         epoch = state["epochs"]
     rotation = CheckpointRotation(model_dir, model.model_name, args.checkpoint_step, start_epoch=epoch)
+
+    def eager_step(x, target):
+        if sync is not None:
+            return DP.dp_train_step(model, optimizer, sync, x, target, n_out, seld_loss_fn, args.sed_loss_weight,
+                                    args.doa_loss_weight)
+        optimizer.zero_grad()
+        loss = seld_loss(x, target, model, criterion_sed, criterion_doa, args)
+        loss.backward()
+        optimizer.step()
+        return loss.detach()
+
+    runner = None
+    if graph_step and any(graphable for _, _, graphable in tr_data.plan):
+        # the constructor's warm-up steps TRAIN on the recorded batch: take them on the first rows of the array and put
+        # weights, Adam state, BatchNorm buffers and the dropout stream back, so that step 1 of this run (or the step a
+        # checkpoint resumes at) starts from the same state as without the recording
+        model.train()
+        snap = training_snapshot(model, optimizer)
+        tr_data.fetch(batch=0)
+        runner = GraphedTrainStep(model, optimizer, tr_data.x, tr_data.target, n_out, args.sed_loss_weight,
+                                  args.doa_loss_weight, sync=sync, warmup=1, loader=tr_data)
+        training_restore(model, optimizer, snap)
     while (state["worse_epochs"] < args.patience or epoch < args.min_n_epochs) and not (args.epochs and epoch >= args.epochs):
         epoch += 1
         state["epochs"] += 1
         model.train()
         train_loss = 0.0
         t0 = time.time()
-        for i, (x, target) in enumerate(tr_data):
-            optimizer.zero_grad()
-            loss = seld_loss(x.to(device), target.to(device), model, criterion_sed, criterion_doa, args)
-            loss.backward()
-            optimizer.step()
-            state["step"] += 1
-            train_loss += (loss.detach() - train_loss) / (i + 1)
-            if args.max_steps and state["step"] >= args.max_steps:
-                break
-        val_loss = evaluate(model, device, criterion_sed, criterion_doa, val_data, args)
+        if resident:
+            tr_data.begin_epoch()
+            for _, count, graphable in tr_data.plan:
+                if runner is not None and graphable:
+                    runner()                    # gather, step and running mean: one replay (three when data parallel)
+                else:
+                    # eager; a partial batch always (BatchNorm statistics depend on the true batch size)
+                    tr_data.step_end(eager_step(*tr_data.fetch(count)))
+                state["step"] += 1
+                if args.max_steps and state["step"] >= args.max_steps:
+                    break
+            if world > 1:                       # every rank's mean is over its own shards: print the global batch's
+                torch.distributed.all_reduce(tr_data.mean)
+                tr_data.mean /= world
+            train_loss = tr_data.mean.item()    # the epoch's one read-back
+        else:
+            for i, (x, target) in enumerate(tr_data):
+                optimizer.zero_grad()
+                loss = seld_loss(x.to(device), target.to(device), model, criterion_sed, criterion_doa, args)
+                loss.backward()
+                optimizer.step()
+                state["step"] += 1
+                train_loss += (loss.detach() - train_loss) / (i + 1)
+                if args.max_steps and state["step"] >= args.max_steps:
+                    break
+        if world > 1:
+            DP.average_bn_running_stats(model)      # rank 0's validation and checkpoint speak for all ranks
+        val_loss = evaluate(model, device, criterion_sed, criterion_doa, val_data, args) if rank == 0 else None
         if scheduler is not None and optimizer.param_groups[0]['lr'] > args.min_lr:
             scheduler.step()
+        if rank != 0:
+            # validation, the test leg and the checkpoint files are rank 0's: wait for it and take over its verdict
+            verdict = torch.zeros(1, device=device, dtype=torch.int64)
+            torch.distributed.broadcast(verdict, 0)
+            state["worse_epochs"] = int(verdict.item())
+            if args.max_steps and state["step"] >= args.max_steps:
+                break
+            continue
+        if history is not None:
+            history.append((epoch, float(train_loss), val_loss))
         print(f"epoch {epoch}: train {float(train_loss):.5f} val {val_loss:.5f} lr {optimizer.param_groups[0]['lr']:.2e} "
               f"({time.time() - t0:.1f}s)")
         if rotation.end_of_epoch(model, optimizer, scheduler, state, epoch, val_loss, periodic_copy=False):
@@ -804,6 +1029,8 @@ def main(args):
                 state = load_model(model, optimizer, live, args.use_cuda, device, scheduler)
                 state["best_test_epoch"] = best_test_epoch      # set by after_test on the state loaded for the test
         rotation.periodic_copy(state, epoch)                    # after the test leg, as train.py:671-684
+        if world > 1:
+            torch.distributed.broadcast(torch.tensor([state["worse_epochs"]], device=device, dtype=torch.int64), 0)
         if args.max_steps and state["step"] >= args.max_steps:
             break
     return state
