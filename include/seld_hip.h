@@ -791,6 +791,42 @@ int seld_metrics_accumulate(const float* sed, const float* doa, const float* tar
                             int64_t* counters, double* total_de, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Scoring event lists (csrc/event_metrics.hip): the same counters from rows instead of dense outputs.
+ * Replaces location_sensitive_detection and sed_score_computation (metrics.py:123-288) and segment_labels +
+ * SELDMetrics.update_seld_scores (Dcase21_metrics.py:239-278, 51-154) for a batch of recordings:
+ *   pred_rows (pred_count, 5), true_rows (true_count, 5)   double { frame, class, x, y, z }, recording-major:
+ *                                                          the `rows` of seld_decode_write
+ *   pred_offsets, true_offsets (recordings + 1)            int64, its `rec_offsets`
+ * Inside a recording the rows are sorted by frame (ascending; the caller sorts, stably: the order of the rows of
+ * one frame is the order of the reference's lists, and the position of an event among its frame's events of its
+ * class is its track).  Offsets are forced into [0, count] and into ascending order before use, so no row
+ * outside the lists is read whatever they hold.  ADDS to
+ *   counters[16] = the 13 of seld_metrics_accumulate, in that order, then TP, FP, FN of sed_score_computation
+ *   total_de[1]  = SELDMetrics._total_DE
+ * and WRITES
+ *   flags[0] = rows (both lists) whose frame is not an integer in [0, n_frames): the reference's KeyError.  They
+ *              take no part in counters[0..2] and [13..15].
+ *   flags[1] = (recording, frame, class) cells of either list with more than 3 events, among integer classes
+ *              below nb_classes and integer frames of a block.  The association is solved for 3 x 3 at most:
+ *              when flags[1] is not zero the call is REFUSED and adds nothing to counters and total_de.
+ * Location-sensitive detection has no limit on the events of a frame.  The block metrics run over
+ * ceil(n_frames / frames_per_block) blocks; a block covers its frames_per_block frames also beyond n_frames, as
+ * segment_labels does; classes that are no integer in [0, nb_classes) are ignored there.  nb_classes = 0 leaves
+ * the block metrics out altogether (counters[3..12] and total_de untouched, flags[1] = 0).
+ * Cartesian coordinates only.  SELD_EINVAL: nb_classes outside [0, 64], frames_per_block < 1, a negative count,
+ * n_frames < 0, a NULL pointer that is needed.  SELD_EUNSUPPORTED: a list of 2^28 rows or more (nothing is launched).
+ * A row with a NaN frame belongs to no block and is counted in flags[0] only; torch.sort puts such rows last.  Two launches and one 16-byte memset, no workspace, no host read:
+ * the call can be recorded in a graph.
+ * ------------------------------------------------------------------------------------------ */
+#define SELD_EVENT_METRIC_COUNTERS 16
+#define SELD_EVENT_METRICS_MAX_TRACKS 3
+int seld_event_metrics_accumulate(const double* pred_rows, const int64_t* pred_offsets, int64_t pred_count,
+                                  const double* true_rows, const int64_t* true_offsets, int64_t true_count,
+                                  int64_t recordings, int32_t n_frames, int32_t nb_classes, int32_t frames_per_block,
+                                  double spatial_threshold, double doa_threshold, int64_t* counters, double* total_de,
+                                  int64_t* flags, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Event decoding: the submission rows of resident network outputs (csrc/decode.hip).  Replaces
  * gen_submission_list_task2_OLD (utility_functions.py:158-181) and gen_submission_list_task2
  * (utility_functions.py:184-210), which train.py:110-116 calls on the prediction and on the target of

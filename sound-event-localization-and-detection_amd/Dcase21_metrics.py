@@ -1,0 +1,180 @@
+"""Drop-in for the reference's Dcase21_metrics.py: same names, signatures and return types.  SELDMetrics counts on the
+device (hip_ops.score_events, csrc/event_metrics.hip); segment_labels, the distance functions and early_stopping_metric
+are host functions on Python and numpy values, as in the reference.
+
+Limits of the device path: Cartesian coordinates only, at most 3 events of one class in one frame, at most 64 classes."""
+import numpy as np
+import torch
+
+from . import _lib as L
+from . import hip_ops as H
+
+eps = np.finfo(float).eps
+
+
+class SELDMetrics(object):
+    def __init__(self, doa_threshold=20, nb_classes=14):
+        '''
+            This class implements both the class-sensitive localization and location-sensitive detection metrics.
+
+        :param nb_classes: Number of sound classes.
+        :param doa_thresh: DOA threshold for location sensitive detection.
+        '''
+        self._nb_classes = nb_classes
+
+        # Variables for Location-senstive detection performance
+        self._TP = 0
+        self._FP = 0
+        self._FN = 0
+
+        self._S = 0
+        self._D = 0
+        self._I = 0
+        self._Nref = 0
+
+        self._spatial_T = doa_threshold
+
+        # Variables for Class-sensitive localization performance
+        self._total_DE = 0
+
+        self._DE_TP = 0
+        self._DE_FP = 0
+        self._DE_FN = 0
+
+    def compute_seld_scores(self):
+        '''
+        Collect the final SELD scores
+
+        :return: returns both location-sensitive detection scores and class-sensitive localization scores
+        '''
+        # Location-sensitive detection performance
+        ER = (self._S + self._D + self._I) / float(self._Nref + eps)
+        F = self._TP / (eps + self._TP + 0.5 * (self._FP + self._FN))
+
+        # Class-sensitive localization performance
+        LE = self._total_DE / float(self._DE_TP + eps) if self._DE_TP else 180     # When the total number of prediction is zero
+        LR = self._DE_TP / (eps + self._DE_TP + self._DE_FN)
+        return ER, F, LE, LR
+
+    def _add(self, acc):
+        """One read-back of the device accumulators, added to the attributes."""
+        c = acc[0].tolist()
+        for name, k in (("_TP", 3), ("_FP", 4), ("_FN", 5), ("_S", 6), ("_D", 7), ("_I", 8), ("_Nref", 9), ("_DE_TP", 10),
+                        ("_DE_FP", 11), ("_DE_FN", 12)):
+            setattr(self, name, getattr(self, name) + c[k])
+        self._total_DE += float(acc[1].item())
+
+    def update_from_events(self, pred_rows, pred_offsets, true_rows, true_offsets, max_frames, frames_per_block=10):
+        '''
+        The fast form of segment_labels + update_seld_scores for callers who hold rows: (E, 5) float64 device tensors
+        [frame, class, x, y, z] with (R + 1,) int64 offsets, as hip_ops.decode_events returns them, every recording of
+        `max_frames` frames.  No dictionary is built.
+        '''
+        on_device = torch.is_tensor(pred_rows) and pred_rows.is_cuda      # otherwise score_events' own checks raise
+        acc = H.event_metrics_new(pred_rows.device if on_device else torch.device("cuda", torch.cuda.current_device()))
+        H.score_events(acc, pred_rows, pred_offsets, true_rows, true_offsets, max_frames, nb_classes=self._nb_classes,
+                       doa_threshold=self._spatial_T, frames_per_block=frames_per_block)
+        self._add(acc)
+
+    def update_seld_scores(self, pred, gt):
+        '''
+        Implements the spatial error averaging according to equation 5 in the paper [1] (see papers in the title of the code).
+        Adds the multitrack extensions proposed in paper [2]
+
+        :param pred: dictionary containing class-wise prediction results for each N-seconds segment block
+        :param gt: dictionary containing class-wise groundtruth for each N-seconds segment block
+        (what segment_labels returns; Cartesian coordinates)
+        '''
+        nb_blocks = len(gt.keys())
+        for block_cnt in range(nb_blocks):
+            gt[block_cnt], pred[block_cnt]              # the reference's KeyError for a missing block
+        # A frame key only matters by identity inside its block: block * K + key with K above the largest key keeps that.
+        keys = [k for d in (pred, gt) for b in range(nb_blocks) for c in d[b] for k in d[b][c][0][0]]
+        if any(int(k) != k or k < 0 for k in keys):
+            raise L.SeldHipError("update_seld_scores: frame keys must be non-negative integers")
+        K = int(max(keys)) + 1 if keys else 1
+        if not torch.cuda.is_available():
+            raise L.SeldHipError("update_seld_scores: no HIP device (this package has no CPU path)")
+        dev = torch.device("cuda", torch.cuda.current_device())
+        sides = []
+        for d in (pred, gt):
+            rows = []
+            for b in range(nb_blocks):
+                for c in range(self._nb_classes):
+                    if c not in d[b]:
+                        continue
+                    frame_keys, frame_vals = d[b][c][0]
+                    for k, vals in zip(frame_keys, frame_vals):
+                        for v in vals:
+                            doa = list(v)[:-1]          # the reference's [:, :-1]: everything but the last entry
+                            if len(doa) != 3:
+                                raise L.SeldHipError(f"update_seld_scores: {len(doa)} coordinates per event; the device path "
+                                                     "takes Cartesian x, y, z (spherical input is not supported)")
+                            rows.append([b * K + k, c] + doa)
+            a = np.asarray(rows, dtype=np.float64).reshape(-1, 5)
+            a = a[np.argsort(a[:, 0], kind="stable")]
+            sides.append((torch.from_numpy(np.ascontiguousarray(a)).to(dev),
+                          torch.tensor([0, a.shape[0]], dtype=torch.int64).to(dev)))
+        acc = H.event_metrics_new(dev)
+        H.score_events(acc, sides[0][0], sides[0][1], sides[1][0], sides[1][1], nb_blocks * K, nb_classes=self._nb_classes,
+                       doa_threshold=self._spatial_T, frames_per_block=K)
+        self._add(acc)
+        return
+
+
+def distance_between_spherical_coordinates_rad(az1, ele1, az2, ele2):
+    """
+    Angular distance between two spherical coordinates
+    MORE: https://en.wikipedia.org/wiki/Great-circle_distance
+
+    :return: angular distance in degrees
+    """
+    dist = np.sin(ele1) * np.sin(ele2) + np.cos(ele1) * np.cos(ele2) * np.cos(np.abs(az1 - az2))
+    dist = np.clip(dist, -1, 1)
+    return np.arccos(dist) * 180 / np.pi
+
+
+def distance_between_cartesian_coordinates(x1, y1, z1, x2, y2, z2):
+    """
+    Angular distance between two cartesian coordinates
+    MORE: https://en.wikipedia.org/wiki/Great-circle_distance
+
+    :return: angular distance in degrees
+    """
+    N1 = np.sqrt(x1**2 + y1**2 + z1**2 + 1e-10)
+    N2 = np.sqrt(x2**2 + y2**2 + z2**2 + 1e-10)
+    x1, y1, z1, x2, y2, z2 = x1/N1, y1/N1, z1/N1, x2/N2, y2/N2, z2/N2
+    dist = x1*x2 + y1*y2 + z1*z2
+    dist = np.clip(dist, -1, 1)
+    return np.arccos(dist) * 180 / np.pi
+
+
+def early_stopping_metric(sed_error, doa_error):
+    """
+    Compute early stopping metric from sed and doa errors.
+
+    :param sed_error: [error rate (0 to 1 range), f score (0 to 1 range)]
+    :param doa_error: [doa error (in degrees), frame recall (0 to 1 range)]
+    :return: early stopping metric result
+    """
+    return np.mean([sed_error[0], 1 - sed_error[1], doa_error[0]/180, 1 - doa_error[1]])
+
+
+def segment_labels(_pred_dict, _max_frames, _nb_label_frames_1s=10):
+    '''
+        Collects class-wise sound event location information in segments of length 1s from reference dataset
+    :param _pred_dict: Dictionary containing frame-wise sound event time and location information. Output of SELD method
+    :param _max_frames: Total number of frames in the recording
+    :return: Dictionary containing class-wise sound event location information in each segment of audio
+            dictionary_name[segment-index][class-index] = [[frame-cnt-within-segment ...], [[[x, y, z, event] ...] ...]]
+    '''
+    nb_blocks = int(np.ceil(_max_frames / float(_nb_label_frames_1s)))
+    output_dict = {x: {} for x in range(nb_blocks)}
+    for block_cnt, first in enumerate(range(0, _max_frames, _nb_label_frames_1s)):
+        by_class = {}                                   # class -> {frame within the block: [event entries]}
+        for audio_frame in range(first, first + _nb_label_frames_1s):
+            for value in _pred_dict.get(audio_frame, ()):
+                by_class.setdefault(value[0], {}).setdefault(audio_frame - first, []).append(value[1:])
+        for class_cnt, frames in by_class.items():
+            output_dict[block_cnt].setdefault(class_cnt, []).append([list(frames.keys()), list(frames.values())])
+    return output_dict

@@ -18,7 +18,7 @@
 //   * the Hungarian association of <= 3 reference and <= 3 predicted DOAs of one class in one frame is solved by
 //     enumeration (first minimum in lexicographic order; scipy may pick another optimum only on exact cost ties).
 // Coordinates are float32(doa * max_loc_value) widened to double, distances in double as in the reference.
-#include "common.h"
+#include "metrics_common.h"
 
 namespace seld {
 
@@ -43,43 +43,6 @@ __device__ __forceinline__ void load_xyz(const float* loc, int slot, float max_l
     const Xyz t = *reinterpret_cast<const Xyz*>(loc + slot * 3);
 #pragma unroll
     for (int k = 0; k < 3; ++k) v[k] = (double)(t.v[k] * max_loc);
-}
-
-// Dcase21_metrics.py:171-188
-__device__ __forceinline__ double angular_distance_deg(const double a[3], const double b[3]) {
-#pragma clang fp contract(off)
-    const double n1 = sqrt(((a[0] * a[0] + a[1] * a[1]) + a[2] * a[2]) + 1e-10);
-    const double n2 = sqrt(((b[0] * b[0] + b[1] * b[1]) + b[2] * b[2]) + 1e-10);
-    double d = ((a[0] / n1) * (b[0] / n2) + (a[1] / n1) * (b[1] / n2)) + (a[2] / n1) * (b[2] / n2);
-    d = fmin(fmax(d, -1.0), 1.0);
-    return acos(d) * 180.0 / 3.141592653589793;
-}
-
-__device__ __forceinline__ unsigned long long readlane_u64(unsigned long long v, int src_lane) {
-    const unsigned lo = __builtin_amdgcn_readlane((unsigned)v, src_lane);
-    const unsigned hi = __builtin_amdgcn_readlane((unsigned)(v >> 32), src_lane);
-    return ((unsigned long long)hi << 32) | lo;
-}
-
-__device__ __forceinline__ long long wave_sum_i64(long long v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ int wave_sum_i32(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ float wave_sum_f32(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
 }
 
 // One WAVE per unit = (recording, block of fpb frames); a wave walks units u, u + total_waves, ... and keeps its
@@ -242,50 +205,7 @@ __global__ __launch_bounds__(256) void metrics_kernel(const MetricsP p) {
             // Everything below is indexed with compile-time constants (registers, no scratch): the cost matrix lives on
             // the 3 x 3 event SLOTS, absent slots are masked out of the enumeration instead of being compacted away.
             double o0 = -1.0, o1 = -1.0, o2 = -1.0;              // matched distance of reference track 0 / 1 / 2, -1 = none
-            if (g && q) {
-                const double* cs = cost_s + ((size_t)c * p.fpb + f) * 9;
-                double cost[3][3];
-#pragma unroll
-                for (int e = 0; e < 3; ++e)
-#pragma unroll
-                    for (int e2 = 0; e2 < 3; ++e2)
-                        cost[e][e2] = (((g_bits >> e) & 1u) && ((p_bits >> e2) & 1u)) ? cs[e * 3 + e2] : 0.0;
-                // all 6 row -> column maps of the slots; a map counts when it pairs min(g, q) present rows with present
-                // columns (a maximum matching); the cheapest one wins, the first on ties
-                const int need = min(g, q);
-                int best = -1;
-                double best_cost = 0.0;
-#pragma unroll
-                for (int k = 0; k < 6; ++k) {
-                    constexpr int P[6][3] = {{0, 1, 2}, {0, 2, 1}, {1, 0, 2}, {1, 2, 0}, {2, 0, 1}, {2, 1, 0}};
-                    int pairs = 0;
-                    double tot = 0.0;
-#pragma unroll
-                    for (int e = 0; e < 3; ++e) {
-                        const bool on = ((g_bits >> e) & 1u) && ((p_bits >> P[k][e]) & 1u);
-                        pairs += on ? 1 : 0;
-                        tot += on ? cost[e][P[k][e]] : 0.0;
-                    }
-                    if (pairs == need && (best < 0 || tot < best_cost)) {
-                        best = k;
-                        best_cost = tot;
-                    }
-                }
-#pragma unroll
-                for (int k = 0; k < 6; ++k) {
-                    constexpr int P[6][3] = {{0, 1, 2}, {0, 2, 1}, {1, 0, 2}, {1, 2, 0}, {2, 0, 1}, {2, 1, 0}};
-                    if (k != best) continue;
-#pragma unroll
-                    for (int e = 0; e < 3; ++e) {
-                        if (!(((g_bits >> e) & 1u) && ((p_bits >> P[k][e]) & 1u))) continue;
-                        const int rank = __popc(g_bits & ((1u << e) - 1u));      // index of slot e among the present references
-                        const double d = cost[e][P[k][e]];
-                        o0 = rank == 0 ? d : o0;
-                        o1 = rank == 1 ? d : o1;
-                        o2 = rank == 2 ? d : o2;
-                    }
-                }
-            }
+            if (g && q) assign_3x3(g_bits, p_bits, cost_s + ((size_t)c * p.fpb + f) * 9, o0, o1, o2);
             const double out[3] = {o0, o1, o2};
             double* dst = match_s + ((size_t)c * p.fpb + f) * 3;
             dst[0] = out[0];
@@ -305,10 +225,9 @@ __global__ __launch_bounds__(256) void metrics_kernel(const MetricsP p) {
                 nb_gt = max(nb_gt, __popcll((mt_s[f] >> sh) & cls_mask));
                 nb_pred = max(nb_pred, __popcll((mp_s[f] >> sh) & cls_mask));
             }
-            cnt[9] += nb_gt;
+            double s0 = 0.0, s1 = 0.0, s2 = 0.0;
+            int n0 = 0, n1 = 0, n2 = 0;
             if (nb_gt && nb_pred) {
-                double s0 = 0.0, s1 = 0.0, s2 = 0.0;
-                int n0 = 0, n1 = 0, n2 = 0;
 #pragma unroll 5
                 for (int f = 0; f < nf; ++f) {
                     const double* src = match_s + ((size_t)lane * p.fpb + f) * 3;
@@ -317,46 +236,11 @@ __global__ __launch_bounds__(256) void metrics_kernel(const MetricsP p) {
                     if (d1 >= 0.0) { s1 += d1; ++n1; }
                     if (d2 >= 0.0) { s2 += d2; ++n2; }
                 }
-                if (n0 + n1 + n2 == 0) {
-                    loc_fn += nb_pred;
-                    cnt[5] += nb_pred;
-                    cnt[12] += nb_pred;
-                } else {
-                    // (the reference adds the tracks' averages in order of first appearance; the order only moves the last
-                    //  bit of _total_DE, which the cross-block atomics reorder anyway)
-#pragma unroll
-                    for (int r = 0; r < 3; ++r) {
-                        const int tn = r == 0 ? n0 : r == 1 ? n1 : n2;
-                        if (tn == 0) continue;
-                        const double avg = (r == 0 ? s0 : r == 1 ? s1 : s2) / (double)tn;
-                        total_de += avg;
-                        cnt[10] += 1;
-                        if (avg <= p.doa_threshold) {
-                            cnt[3] += 1;
-                        } else {
-                            loc_fp += 1;
-                            cnt[4] += 1;
-                        }
-                    }
-                    if (nb_pred > nb_gt) {
-                        loc_fp += nb_pred - nb_gt;
-                        cnt[4] += nb_pred - nb_gt;
-                        cnt[11] += nb_pred - nb_gt;
-                    } else if (nb_pred < nb_gt) {
-                        loc_fn += nb_gt - nb_pred;
-                        cnt[5] += nb_gt - nb_pred;
-                        cnt[12] += nb_gt - nb_pred;
-                    }
-                }
-            } else if (nb_gt) {
-                loc_fn += nb_gt;
-                cnt[5] += nb_gt;
-                cnt[12] += nb_gt;
-            } else if (nb_pred) {
-                loc_fp += nb_pred;
-                cnt[4] += nb_pred;
-                cnt[11] += nb_pred;
             }
+            const DcaseAdd a = dcase_class_block(nb_gt, nb_pred, s0, s1, s2, n0, n1, n2, p.doa_threshold, total_de);
+            SELD_DCASE_ADD(cnt, a);
+            loc_fn = a.fn;
+            loc_fp = a.fp;
         }
         const int blk_fn = wave_sum_i32(loc_fn), blk_fp = wave_sum_i32(loc_fp);
         if (lane == 0) {

@@ -1,0 +1,150 @@
+// Device functions shared by the two metric kernel families: metrics.hip (dense network outputs) and event_metrics.hip
+// (event rows).  Both compute the DCASE21 block metrics of Dcase21_metrics.py:51-154 with the code below, so a result
+// cannot differ between them by more than the order of the final atomics.
+#pragma once
+#include "common.h"
+
+namespace seld {
+
+// Dcase21_metrics.py:171-188
+__device__ __forceinline__ double angular_distance_deg(const double a[3], const double b[3]) {
+#pragma clang fp contract(off)
+    const double n1 = sqrt(((a[0] * a[0] + a[1] * a[1]) + a[2] * a[2]) + 1e-10);
+    const double n2 = sqrt(((b[0] * b[0] + b[1] * b[1]) + b[2] * b[2]) + 1e-10);
+    double d = ((a[0] / n1) * (b[0] / n2) + (a[1] / n1) * (b[1] / n2)) + (a[2] / n1) * (b[2] / n2);
+    d = fmin(fmax(d, -1.0), 1.0);
+    return acos(d) * 180.0 / 3.141592653589793;
+}
+
+__device__ __forceinline__ unsigned long long readlane_u64(unsigned long long v, int src_lane) {
+    const unsigned lo = __builtin_amdgcn_readlane((unsigned)v, src_lane);
+    const unsigned hi = __builtin_amdgcn_readlane((unsigned)(v >> 32), src_lane);
+    return ((unsigned long long)hi << 32) | lo;
+}
+
+__device__ __forceinline__ long long wave_sum_i64(long long v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+__device__ __forceinline__ int wave_sum_i32(int v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+__device__ __forceinline__ float wave_sum_f32(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+__device__ __forceinline__ double wave_sum_d(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+// The Hungarian association of the <= 3 reference and <= 3 predicted DOAs of one class in one frame, by enumeration
+// (first minimum in lexicographic order).  g_bits / p_bits: which of the 3 slots hold an event (both non-zero); cost
+// [reference slot][predicted slot], read at present slots only.  o0 / o1 / o2 receive the matched distance of reference
+// track 0 / 1 / 2 (the rank of the slot among the present references) and are left alone for an unmatched track.
+// Everything is indexed with compile-time constants (registers, no scratch): absent slots are masked out of the
+// enumeration instead of being compacted away.
+__device__ __forceinline__ void assign_3x3(unsigned g_bits, unsigned p_bits, const double* cs, double& o0, double& o1,
+                                           double& o2) {
+    const int g = __popc(g_bits), q = __popc(p_bits);
+    double cost[3][3];
+#pragma unroll
+    for (int e = 0; e < 3; ++e)
+#pragma unroll
+        for (int e2 = 0; e2 < 3; ++e2)
+            cost[e][e2] = (((g_bits >> e) & 1u) && ((p_bits >> e2) & 1u)) ? cs[e * 3 + e2] : 0.0;
+    // all 6 row -> column maps of the slots; a map counts when it pairs min(g, q) present rows with present
+    // columns (a maximum matching); the cheapest one wins, the first on ties
+    const int need = min(g, q);
+    int best = -1;
+    double best_cost = 0.0;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+        constexpr int P[6][3] = {{0, 1, 2}, {0, 2, 1}, {1, 0, 2}, {1, 2, 0}, {2, 0, 1}, {2, 1, 0}};
+        int pairs = 0;
+        double tot = 0.0;
+#pragma unroll
+        for (int e = 0; e < 3; ++e) {
+            const bool on = ((g_bits >> e) & 1u) && ((p_bits >> P[k][e]) & 1u);
+            pairs += on ? 1 : 0;
+            tot += on ? cost[e][P[k][e]] : 0.0;
+        }
+        if (pairs == need && (best < 0 || tot < best_cost)) {
+            best = k;
+            best_cost = tot;
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+        constexpr int P[6][3] = {{0, 1, 2}, {0, 2, 1}, {1, 0, 2}, {1, 2, 0}, {2, 0, 1}, {2, 1, 0}};
+        if (k != best) continue;
+#pragma unroll
+        for (int e = 0; e < 3; ++e) {
+            if (!(((g_bits >> e) & 1u) && ((p_bits >> P[k][e]) & 1u))) continue;
+            const int rank = __popc(g_bits & ((1u << e) - 1u));      // index of slot e among the present references
+            const double d = cost[e][P[k][e]];
+            o0 = rank == 0 ? d : o0;
+            o1 = rank == 1 ? d : o1;
+            o2 = rank == 2 ? d : o2;
+        }
+    }
+}
+
+// What one class of one block adds to the DCASE21 counters (Dcase21_metrics.py:65-149).  fp and fn are also the class's
+// share of the block's loc_FP and loc_FN, which the reference raises wherever it raises _FP and _FN.
+struct DcaseAdd {
+    int tp, fp, fn, nref, de_tp, de_fp, de_fn;
+};
+
+// nb_gt / nb_pred: the longest reference / predicted list of a frame of the block; s / n: the sum and the count of the
+// matched distances of reference track 0 / 1 / 2 over the block's frames.  The tracks' averages are added to total_de.
+__device__ __forceinline__ DcaseAdd dcase_class_block(int nb_gt, int nb_pred, double s0, double s1, double s2, int n0, int n1,
+                                                      int n2, double doa_threshold, double& total_de) {
+    DcaseAdd a = {0, 0, 0, nb_gt, 0, 0, 0};
+    if (nb_gt && nb_pred) {
+        if (n0 + n1 + n2 == 0) {
+            a.fn += nb_pred;
+            a.de_fn += nb_pred;
+        } else {
+            // (the reference adds the tracks' averages in order of first appearance; the order only moves the last
+            //  bit of _total_DE, which the cross-block atomics reorder anyway)
+#pragma unroll
+            for (int r = 0; r < 3; ++r) {
+                const int tn = r == 0 ? n0 : r == 1 ? n1 : n2;
+                if (tn == 0) continue;
+                const double avg = (r == 0 ? s0 : r == 1 ? s1 : s2) / (double)tn;
+                total_de += avg;
+                a.de_tp += 1;
+                if (avg <= doa_threshold) a.tp += 1; else a.fp += 1;
+            }
+            if (nb_pred > nb_gt) {
+                a.fp += nb_pred - nb_gt;
+                a.de_fp += nb_pred - nb_gt;
+            } else if (nb_pred < nb_gt) {
+                a.fn += nb_gt - nb_pred;
+                a.de_fn += nb_gt - nb_pred;
+            }
+        }
+    } else if (nb_gt) {
+        a.fn += nb_gt;
+        a.de_fn += nb_gt;
+    } else if (nb_pred) {
+        a.fp += nb_pred;
+        a.de_fp += nb_pred;
+    }
+    return a;
+}
+
+// cnt: the counters in METRIC_COUNTERS order
+#define SELD_DCASE_ADD(cnt, a) \
+    do { \
+        cnt[3] += (a).tp; cnt[4] += (a).fp; cnt[5] += (a).fn; cnt[9] += (a).nref; \
+        cnt[10] += (a).de_tp; cnt[11] += (a).de_fp; cnt[12] += (a).de_fn; \
+    } while (0)
+
+}  // namespace seld
