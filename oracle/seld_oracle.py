@@ -334,9 +334,25 @@ def _bn(sd, prefix, x, train, stats_out):
                       sd[prefix + ".running_var"], train, stats_out=stats_out, name=prefix)
 
 
+def _dropout(x, p, dropout, kind):
+    """One dropout site.  `dropout`: False = off; True = torch's own RNG (the CPU timing baseline); a callable
+    draw(shape, p, kind) = the mask source of a parity check: it returns the factors (0 or 1 / (1 - p)) to multiply by,
+    kind "element": one per element of `shape`; kind "channel" (Dropout1d): shape (N, C, 1), broadcast over time.  The
+    HIP path's masks are a pure function of (seed, counter, p) -- tests/philox_ref.py reproduces them on the host -- so
+    a callable built from that reference makes the train-mode oracle comparable with the device, dropout on."""
+    if not dropout or not p:
+        return x
+    if callable(dropout):
+        shape = tuple(x.shape) if kind == "element" else (x.shape[0], x.shape[1], 1)
+        f = dropout(shape, p, kind)
+        return x * torch.as_tensor(f).to(x.dtype).reshape(shape)
+    if kind == "channel":
+        return F.dropout1d(x, p, training=True)
+    return F.dropout(x, p, training=True)
+
+
 def res_block(sd, prefix, cfg: SeldConfig, x, dilation, train, mode, stats_out=None, dropout=False):
-    """ResBlock.forward, model.py:109-132.  `dropout` (CPU-baseline timing only: RNG parity with the GPU is
-    impossible, so every parity check runs with it off) enables the Dropout1d of :127-128."""
+    """ResBlock.forward, model.py:109-132.  `dropout` (see _dropout) enables the Dropout1d of :127-128."""
     use_bn = cfg.batch_norm in {"BN", "BN_on_TCN", "BNonTCN"}
     k = cfg.kernel_size_dilated_conv
     pad = int(((k - 1) * dilation) / 2)
@@ -348,8 +364,7 @@ def res_block(sd, prefix, cfg: SeldConfig, x, dilation, train, mode, stats_out=N
         yf = _bn(sd, prefix + ".batch_filter2", yf, train, stats_out)
         yg = _bn(sd, prefix + ".batch_gate2", yg, train, stats_out)
     y = torch.tanh(yf) * torch.sigmoid(yg)
-    if dropout and cfg.spatial_dropout_rate:
-        y = F.dropout1d(y, cfg.spatial_dropout_rate, training=True)
+    y = _dropout(y, cfg.spatial_dropout_rate, dropout, "channel")
     skip = _conv_layer(sd, prefix + ".conv2_skip", cfg.algebra, y, 1, 0, 1, mode)
     res = _conv_layer(sd, prefix + ".conv2_residual", cfg.algebra, y, 1, 0, 1, mode)
     return x + res, skip
@@ -397,8 +412,7 @@ def conv_tc_block(sd, prefix, cfg: SeldConfig, x, train, mode, taps=None, stats_
         x = torch.relu(x)
         pool = [p[0], p[1]] if cfg.pool_time == "CNN" else [p[0], 1]
         x = F.max_pool2d(x, pool)
-        if dropout and cfg.dropout_perc:
-            x = F.dropout(x, cfg.dropout_perc, training=True)
+        x = _dropout(x, cfg.dropout_perc, dropout, "element")
         if taps is not None:
             taps[f"{prefix}.cnn.{i}"] = x
     B = x.shape[0]
@@ -423,21 +437,21 @@ def _head(sd, name, cfg: SeldConfig, x, mode, dropout=False):
             x = torch.relu(x)
             idx += 1
         if cfg.fc_dropout in {"all", "ALL", "True"}:
-            if dropout and cfg.dropout_perc:
-                x = F.dropout(x, cfg.dropout_perc, training=True)
+            x = _dropout(x, cfg.dropout_perc, dropout, "element")
             idx += 1
     if cfg.fc_dropout in {"last", "Last", "LAST"}:
-        if dropout and cfg.dropout_perc:
-            x = F.dropout(x, cfg.dropout_perc, training=True)
+        x = _dropout(x, cfg.dropout_perc, dropout, "element")
         idx += 1
     p = f"{name}.{idx}"
     return F.linear(x, sd[p + ".weight"], sd.get(p + ".bias"))
 
 
 def seld_forward(sd: Dict[str, torch.Tensor], cfg: SeldConfig, x, train=False, mode="assembled",
-                 taps: Optional[dict] = None, stats_out: Optional[dict] = None, dropout: bool = False):
+                 taps: Optional[dict] = None, stats_out: Optional[dict] = None, dropout=False):
     """SELD_Model.forward, model.py:461-480.  `sd` uses the reference's state-dict key names
-    (SURVEY App. B).  `train=True` selects batch statistics in BatchNorm; dropout is always off."""
+    (SURVEY App. B).  `train=True` selects batch statistics in BatchNorm; `dropout`: off (False), torch's RNG (True) or
+    a mask source draw(shape, p, kind), see _dropout.  The sites are visited in the order the HIP model draws: the CNN
+    stages, the residual blocks, the sed head, the doa head; branch A before branch B."""
     if cfg.two_stream:
         if cfg.parallel_magphase:
             xa = torch.cat((x[:, :4], x[:, 8:12]), 1)

@@ -77,19 +77,33 @@ def test_default_mode_differs_by_rounding_only(name, seld_env):
     assert float((d > 1e-4).float().mean()) < 2e-2, float((d > 1e-4).float().mean())     # lr = 1e-3: a flipped noise-level element moves 2e-3
 
 
-@pytest.mark.parametrize("name", ["tiny_DQ", "c3w_train"])
-def test_recorded_step_matches_eager_at_rounding_level(name, seld_env):
-    """Five steps recorded-and-replayed against five eager steps in deterministic mode, Dropout off (a replay draws its
-    masks from the device-resident counter: same masks only by construction of the counters, tested elsewhere): the
-    launches are the same launches, so the parameters agree to 1e-6 relative ('rounding-level tolerances')."""
-    seld_env.set("SELD_DETERMINISTIC", "1")
-    le, pe, re_ = _run(name, 5, "eager", dropout=False)
-    lg, pg, rg = _run(name, 5, "graph", dropout=False)
+def _recorded_against_eager(name, dropout):
+    le, pe, re_ = _run(name, 5, "eager", dropout=dropout)
+    lg, pg, rg = _run(name, 5, "graph", dropout=dropout)
     assert np.allclose(lg, le[1:], rtol=1e-6, atol=0), (lg, le)
     scale = float(pe.abs().max())
     assert float((pg - pe).abs().max()) <= 1e-6 * scale, float((pg - pe).abs().max())
     for k in re_:
         assert torch.allclose(rg[k], re_[k], rtol=1e-6, atol=1e-7 * float(re_[k].abs().max()) + 1e-12), k
+
+
+@pytest.mark.parametrize("name", ["tiny_DQ", "c3w_train"])
+def test_recorded_step_matches_eager_at_rounding_level(name, seld_env):
+    """Five steps recorded-and-replayed against five eager steps in deterministic mode, Dropout off: the launches are the
+    same launches, so the parameters agree to 1e-6 relative ('rounding-level tolerances').  Dropout on:
+    test_recorded_step_matches_eager_with_dropout below."""
+    seld_env.set("SELD_DETERMINISTIC", "1")
+    _recorded_against_eager(name, dropout=False)
+
+
+@pytest.mark.parametrize("name", ["tiny_DQ", "c3w_train"])
+def test_recorded_step_matches_eager_with_dropout(name, seld_env):
+    """The same with dropout_perc = 0.3 and spatial_dropout_rate = 0.5, same tolerances.  A replay draws its masks from the
+    device-resident counter (the base in the step state, advanced by the draws of one step, plus the offsets recorded from
+    0): replay k must draw exactly what eager step k draws, or losses and parameters differ at order 1.  That the eager
+    masks themselves are the right ones is tests/test_gpu_dropout.py."""
+    seld_env.set("SELD_DETERMINISTIC", "1")
+    _recorded_against_eager(name, dropout=True)
 
 
 def test_two_queues_match_one_queue_bitwise(seld_env, monkeypatch):
