@@ -705,6 +705,7 @@ int seld_loss_fwd_bwd(const float* sed, const float* doa, const float* target,
 /* ------------------------------------------------------------------------------------------
  * Adam (torch.optim.Adam defaults, train.py:502) over ONE flat fp32 buffer that holds every
  * parameter; grads/exp_avg/exp_avg_sq are parallel flat buffers.  step is 1-based.
+ * The gradient used is g' = fma(weight_decay, param, grad * grad_scale): coupled (L2) weight decay, one rounding.
  * ------------------------------------------------------------------------------------------ */
 int seld_adam_flat(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
                    float lr, float beta1, float beta2, float eps, float weight_decay, int32_t step,
@@ -716,7 +717,9 @@ int seld_adam_flat(float* param, const float* grad, float* exp_avg, float* exp_a
  * seld_step_begin replaces `optimizer.zero_grad()` (train.py:552): zeroes the flat gradient buffer (n floats, 16-byte
  * aligned) and, if state is non-null, advances state[1] += 1.
  * seld_adam_flat_state is seld_adam_flat with step = state[1] and lr = state[2]; as the last launch of a step it also
- * moves the Philox base past the step's draws, state[0] += state[3]. */
+ * moves the Philox base past the step's draws, state[0] += state[3].
+ * Both calls update the state for n == 0 as well (a step over no parameters is still a step: state[1] advances at its
+ * start and state[0] at its end); seld_adam_flat_state used to return early there and left the Philox base behind. */
 int seld_step_begin(float* flat_grad, int64_t n, uint64_t* state, void* stream);
 int seld_adam_flat_state(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
                          float beta1, float beta2, float eps, float weight_decay, float grad_scale,

@@ -484,8 +484,11 @@ def seld_loss(sed, doa, target, n_sed, sed_weight=1.0, doa_weight=5.0):
     return bce * sed_weight + mse * doa_weight
 
 
-def adam_step(p, g, m, v, step, lr=1e-4, b1=0.9, b2=0.999, eps=1e-8):
-    """torch.optim.Adam defaults (train.py:502): returns (p, m, v) after one update; step is 1-based."""
+def adam_step(p, g, m, v, step, lr=1e-4, b1=0.9, b2=0.999, eps=1e-8, weight_decay=0.0, grad_scale=1.0):
+    """torch.optim.Adam (train.py:502; no amsgrad): returns (p, m, v) after one update; step is 1-based.  The gradient is
+    scaled by `grad_scale` first (data-parallel averaging); `weight_decay` is L2, coupled: added to the gradient before
+    the moments.  eps is added outside the bias-corrected square root."""
+    g = g * grad_scale + weight_decay * p
     m = b1 * m + (1 - b1) * g
     v = b2 * v + (1 - b2) * g * g
     mhat = m / (1 - b1 ** step)

@@ -846,7 +846,7 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
         float grad = g[i] * gscale;
         const float pv = p[i];
-        if (wd != 0.f) grad += wd * pv;
+        if (wd != 0.f) grad = fmaf(wd, pv, grad);       // one rounding: g and wd * p may cancel
         const float mi = b1 * m[i] + (1.f - b1) * grad;
         const float vi = b2 * v[i] + (1.f - b2) * grad * grad;
         m[i] = mi;
@@ -873,7 +873,7 @@ __global__ __launch_bounds__(256) void adam_state_kernel(float* __restrict__ p, 
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
         float grad = g[i] * gscale;
         const float pv = p[i];
-        if (wd != 0.f) grad += wd * pv;
+        if (wd != 0.f) grad = fmaf(wd, pv, grad);       // one rounding: g and wd * p may cancel
         const float mi = b1 * m[i] + (1.f - b1) * grad;
         const float vi = b2 * v[i] + (1.f - b2) * grad * grad;
         m[i] = mi;
@@ -1194,7 +1194,8 @@ extern "C" int seld_adam_flat_state(float* param, const float* grad, float* exp_
                                     float beta1, float beta2, float eps, float weight_decay, float grad_scale,
                                     uint64_t* state, void* stream) {
     if (!param || !grad || !exp_avg || !exp_avg_sq || !state || n < 0) return SELD_EINVAL;
-    if (n == 0) return SELD_OK;
+    // n == 0 still launches (one workgroup): the end of the step moves the Philox base, as seld_step_begin(n == 0)
+    // still advances the step number
     hipLaunchKernelGGL(adam_state_kernel, dim3(grid_for(n)), dim3(256), 0, ST(stream), param, grad, exp_avg, exp_avg_sq,
                        (long long)n, beta1, beta2, eps, weight_decay, grad_scale, state);
     return check_launch();

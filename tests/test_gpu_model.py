@@ -140,7 +140,7 @@ def test_train_step_matches_reference(case, cfg, golden, seld_env):
         got = np.array([d.sum().item(), (d ** 2).sum().item()])
         # Adam's first step is lr * g / (|g| + 1e-8): elements whose gradient is at the fp32 noise level (|g| ~ 1e-8)
         # move by up to lr in either stack, so allow three such elements on top of the relative tolerance;
-        # the kernel itself is checked exactly in test_gpu_ops.py::test_adam_flat_matches_oracle
+        # the kernel itself is held to a per-element fp64 reference in test_gpu_train_step.py::test_adam_flat_per_element
         assert abs(got[1] - dck[i, 1]) <= gtol * 5e-3 * dck[i, 1] + 3 * (1e-4) ** 2, (n, got, dck[i])
     sd = m.state_dict()
     rnames = str(g["train.running_names"]).split("\n")
