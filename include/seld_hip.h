@@ -527,6 +527,20 @@ int seld_gate_bwd_fused(const float* dy, const float* yf, const float* yg, int32
                         const float* mean_g, const float* invstd_g, const float* gamma_g, const float* beta_g,
                         const float* mask, float* red, float* dyf, float* dyg, void* stream);
 
+/* Diagnostics: the kernel an entry point above launches for (N, C, S) under the current switches, answered by the
+ * selection code the entry point itself runs: "bn_act_bwd_channel_kernel<4>", "gate_bwd_reduce_row_kernel",
+ * "bn_act_bwd_reduce_kernel[x4, 2 chunks]" (x4 / x1: 16-byte or single-element walk; chunks: workgroups per channel
+ * that add into the result, 1 under SELD_DETERMINISTIC).  SELD_EUNSUPPORTED where the fused entry point answers so.
+ * buflen >= 48. */
+#define SELD_NORM_BN_BWD_FUSED    0
+#define SELD_NORM_BN_BWD_REDUCE   1
+#define SELD_NORM_BN_BWD_APPLY    2
+#define SELD_NORM_GATE_FWD        3
+#define SELD_NORM_GATE_BWD_FUSED  4
+#define SELD_NORM_GATE_BWD_REDUCE 5
+#define SELD_NORM_GATE_BWD_APPLY  6
+int seld_norm_kernel_label(int32_t op, int32_t N, int32_t C, int32_t S, char* buf, int32_t buflen);
+
 /* ------------------------------------------------------------------------------------------
  * Quaternion / dual-quaternion convolution by the 8-multiplication Hamilton product (csrc/hcq_conv.hip).
  * Same mathematics as seld_hc_conv_fwd / _bwd_data (quaternion_ops.py:125-147, dual_quaternion_ops.py:111-153):

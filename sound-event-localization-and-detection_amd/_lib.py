@@ -25,6 +25,8 @@ SELD_LIN_REAL, SELD_LIN_QUAT, SELD_LIN_DUALQ = 1, 4, 8
 SELD_ROT_LAYOUT_CONV, SELD_ROT_LAYOUT_LINEAR = 0, 1
 SELD_QUAT_LAYOUT_INPUT, SELD_QUAT_LAYOUT_CAT1 = 0, 1
 SELD_DECODE_F32, SELD_DECODE_F64 = 0, 1
+(SELD_NORM_BN_BWD_FUSED, SELD_NORM_BN_BWD_REDUCE, SELD_NORM_BN_BWD_APPLY, SELD_NORM_GATE_FWD, SELD_NORM_GATE_BWD_FUSED,
+ SELD_NORM_GATE_BWD_REDUCE, SELD_NORM_GATE_BWD_APPLY) = range(7)       # seld_norm_kernel_label(op, ...)
 
 
 class SeldHipError(RuntimeError):

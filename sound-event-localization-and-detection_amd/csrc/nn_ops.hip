@@ -1,6 +1,8 @@
 // BatchNorm (+ fused activations), gated activation, pooling, dropout, loss and Adam kernels
 // for gfx950.  All HBM-bound: 16-byte loads/stores along the contiguous S axis, per-channel
 // reductions by wave shuffles + one atomic per wave (guide: Appendix B "Reduction").
+#include <cstdio>
+
 #include "common.h"
 #include "env.h"
 
@@ -451,7 +453,7 @@ __global__ __launch_bounds__(256) void gate_bwd_apply_row_kernel(const float* __
 }
 
 // ---- one-pass backward forms (training mode, S % 4 == 0, a channel's N*S values fit the workgroup's registers):
-// ONE workgroup of 1024 threads owns a whole channel.  It reads dy and the saved tensors once, keeps dz and the
+// ONE workgroup of CH_THREADS (512) threads owns a whole channel.  It reads dy and the saved tensors once, keeps dz and the
 // normalised input in registers across the block-wide reduction, then writes the input gradient: the two-pass forms
 // above read every operand twice (and evaluate tanh / exp twice) -- 150 + 25 MB against 75 + 25 MB for a TCN
 // BatchNorm at B = 32, 150 + 50 against 75 + 50 for the gate.  dgamma / dbeta are ADDED to red (one writer per
@@ -915,6 +917,16 @@ using namespace seld;
 // chunks of a per-channel reduction: one (the block's single atomic add per output is then the only contribution) when
 // SELD_DETERMINISTIC is set
 static inline unsigned red_chunks(long long M) { return env().deterministic ? 1u : (unsigned)((M + RED_CHUNK - 1) / RED_CHUNK); }
+// register groups per thread of the one-pass channel kernels: the smallest instantiation (1, 2, 4, ... max_per) whose
+// CH_THREADS * PER groups of four hold the channel's G, 0 when none does
+static inline int channel_groups(long long G, int max_per) {
+    for (int p = 1; p <= max_per; p *= 2)
+        if (G <= (long long)p * CH_THREADS) return p;
+    return 0;
+}
+// the gate's one-wave-per-row forms
+static inline bool gate_rows(long long N, long long C, int S) { return S % 4 == 0 && N * C < (1LL << 31); }
+static inline bool gate_reduce_rows(long long N, long long C, int S) { return gate_rows(N, C, S) && !env().deterministic; }
 
 extern "C" int seld_channel_stats(const float* x, int32_t N, int32_t C, int32_t S, float* stats, void* stream) {
     if (!x || !stats || N <= 0 || C <= 0 || S <= 0) return SELD_EINVAL;
@@ -998,16 +1010,16 @@ extern "C" int seld_bn_act_bwd_fused(const float* dy, const float* x, const floa
                                      float* red, const float* dy2, float* dx, void* stream) {
     if (!dy || !x || !y || !red || !mean || !invstd || !gamma || N <= 0 || C <= 0 || S <= 0) return SELD_EINVAL;
     const long long G = (long long)N * S / 4;
-    if ((S & 3) || G > 16LL * CH_THREADS) return SELD_EUNSUPPORTED;
+    const int per = (S & 3) ? 0 : channel_groups(G, 16);
+    if (!per) return SELD_EUNSUPPORTED;
     const float inv_count = 1.0f / (float)((long long)N * S);
-    const int per = (int)((G + CH_THREADS - 1) / CH_THREADS);
 #define SELD_BN_CH(P)                                                                                                   \
     hipLaunchKernelGGL(bn_act_bwd_channel_kernel<P>, dim3(C), dim3(CH_THREADS), 0, ST(stream), dy, x, y, N, C, S, mean,  \
                        invstd, gamma, act, red, dy2, dx, inv_count)
-    if (per <= 1) SELD_BN_CH(1);
-    else if (per <= 2) SELD_BN_CH(2);
-    else if (per <= 4) SELD_BN_CH(4);
-    else if (per <= 8) SELD_BN_CH(8);
+    if (per == 1) SELD_BN_CH(1);
+    else if (per == 2) SELD_BN_CH(2);
+    else if (per == 4) SELD_BN_CH(4);
+    else if (per == 8) SELD_BN_CH(8);
     else SELD_BN_CH(16);
 #undef SELD_BN_CH
     return check_launch();
@@ -1025,7 +1037,7 @@ extern "C" int seld_gate_fwd(const float* yf, const float* yg, int32_t N, int32_
                              float* y, void* stream) {
     if (!yf || !yg || !y) return SELD_EINVAL;
     const long long total = (long long)N * C * S;
-    if (S % 4 == 0 && (long long)N * C < (1LL << 31))
+    if (gate_rows(N, C, S))
         hipLaunchKernelGGL(gate_fwd_row_kernel, dim3(row_grid((long long)N * C)), dim3(256), 0, ST(stream), yf, yg, N * C, C, S,
                            mk_gate(mean_f, invstd_f, gamma_f, beta_f, mean_g, invstd_g, gamma_g, beta_g), mask, y);
     else
@@ -1041,7 +1053,7 @@ extern "C" int seld_gate_bwd_reduce(const float* dy, const float* yf, const floa
     if (!dy || !yf || !yg || !red) return SELD_EINVAL;
     const long long M = (long long)N * S;
     dim3 grid(red_chunks(M), C);
-    if (S % 4 == 0 && (long long)N * C < (1LL << 31) && !env().deterministic)
+    if (gate_reduce_rows(N, C, S))
         hipLaunchKernelGGL(gate_bwd_reduce_row_kernel, dim3(row_grid((long long)N * C)), dim3(256), 0, ST(stream), dy, yf, yg,
                            N * C, C, S, mk_gate(mean_f, invstd_f, gamma_f, beta_f, mean_g, invstd_g, gamma_g, beta_g), mask, red);
     else
@@ -1058,7 +1070,7 @@ extern "C" int seld_gate_bwd_apply(const float* dy, const float* yf, const float
     if (!dy || !yf || !yg || !dyf || !dyg || (train && !red)) return SELD_EINVAL;
     const long long total = (long long)N * C * S;
     const float inv_count = 1.0f / (float)((long long)N * S);
-    if (S % 4 == 0 && (long long)N * C < (1LL << 31))
+    if (gate_rows(N, C, S))
         hipLaunchKernelGGL(gate_bwd_apply_row_kernel, dim3(row_grid((long long)N * C)), dim3(256), 0, ST(stream), dy, yf, yg,
                            N * C, C, S, mk_gate(mean_f, invstd_f, gamma_f, beta_f, mean_g, invstd_g, gamma_g, beta_g), mask, red,
                            inv_count, train, dyf, dyg);
@@ -1075,19 +1087,55 @@ extern "C" int seld_gate_bwd_fused(const float* dy, const float* yf, const float
                                    const float* mask, float* red, float* dyf, float* dyg, void* stream) {
     if (!dy || !yf || !yg || !red || !dyf || !dyg || N <= 0 || C <= 0 || S <= 0) return SELD_EINVAL;
     const long long G = (long long)N * S / 4;
-    if ((S & 3) || G > 8LL * CH_THREADS) return SELD_EUNSUPPORTED;
+    const int per = (S & 3) ? 0 : channel_groups(G, 8);
+    if (!per) return SELD_EUNSUPPORTED;
     const float inv_count = 1.0f / (float)((long long)N * S);
-    const int per = (int)((G + CH_THREADS - 1) / CH_THREADS);
     const GateBN bn = mk_gate(mean_f, invstd_f, gamma_f, beta_f, mean_g, invstd_g, gamma_g, beta_g);
 #define SELD_GATE_CH(P)                                                                                                 \
     hipLaunchKernelGGL(gate_bwd_channel_kernel<P>, dim3(C), dim3(CH_THREADS), 0, ST(stream), dy, yf, yg, N, C, S, bn,    \
                        mask, red, dyf, dyg, inv_count)
-    if (per <= 1) SELD_GATE_CH(1);
-    else if (per <= 2) SELD_GATE_CH(2);
-    else if (per <= 4) SELD_GATE_CH(4);
+    if (per == 1) SELD_GATE_CH(1);
+    else if (per == 2) SELD_GATE_CH(2);
+    else if (per == 4) SELD_GATE_CH(4);
     else SELD_GATE_CH(8);
 #undef SELD_GATE_CH
     return check_launch();
+}
+
+// Which kernel a BatchNorm / gate entry point launches for (N, C, S) under the current switches, from the same selection
+// functions the entry points use.
+extern "C" int seld_norm_kernel_label(int32_t op, int32_t N, int32_t C, int32_t S, char* buf, int32_t buflen) {
+    if (N <= 0 || C <= 0 || S <= 0 || !buf || buflen < 48) return SELD_EINVAL;
+    const long long M = (long long)N * S;
+    const int vec = (S & 3) ? 1 : 4;
+    switch (op) {
+        case SELD_NORM_BN_BWD_FUSED:
+        case SELD_NORM_GATE_BWD_FUSED: {
+            const bool bn = op == SELD_NORM_BN_BWD_FUSED;
+            const int per = (S & 3) ? 0 : channel_groups(M / 4, bn ? 16 : 8);
+            if (!per) return SELD_EUNSUPPORTED;
+            snprintf(buf, buflen, "%s_bwd_channel_kernel<%d>", bn ? "bn_act" : "gate", per);
+            return SELD_OK;
+        }
+        case SELD_NORM_BN_BWD_REDUCE:
+            snprintf(buf, buflen, "bn_act_bwd_reduce_kernel[x%d, %u chunks]", vec, red_chunks(M));
+            return SELD_OK;
+        case SELD_NORM_BN_BWD_APPLY:
+            snprintf(buf, buflen, "bn_act_bwd_apply_kernel[x%d]", vec);
+            return SELD_OK;
+        case SELD_NORM_GATE_FWD:
+            snprintf(buf, buflen, gate_rows(N, C, S) ? "gate_fwd_row_kernel" : "gate_fwd_kernel");
+            return SELD_OK;
+        case SELD_NORM_GATE_BWD_REDUCE:
+            if (gate_reduce_rows(N, C, S)) snprintf(buf, buflen, "gate_bwd_reduce_row_kernel");
+            else snprintf(buf, buflen, "gate_bwd_reduce_kernel[x%d, %u chunks]", vec, red_chunks(M));
+            return SELD_OK;
+        case SELD_NORM_GATE_BWD_APPLY:
+            snprintf(buf, buflen, gate_rows(N, C, S) ? "gate_bwd_apply_row_kernel" : "gate_bwd_apply_kernel");
+            return SELD_OK;
+        default:
+            return SELD_EINVAL;
+    }
 }
 
 extern "C" int seld_act_fwd(const float* x, int64_t n, int32_t act, float* y, void* stream) {

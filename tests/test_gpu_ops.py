@@ -96,8 +96,10 @@ def test_real_linear_large():
                                        ((32, 12, 512), 2), ((48, 8, 512), 1), ((24, 8, 2048), 2)])
 @pytest.mark.parametrize("training,two_pass", [(True, False), (True, True), (False, False)])
 def test_bn_act(shape, act, training, two_pass, monkeypatch):
-    """Training mode runs the one-workgroup-per-channel backward where a channel fits (N*S <= 32768, S % 4 == 0:
-    1, 2, 4 and 8 register groups per thread are all here) and the reduce + apply pair otherwise / when forced."""
+    """Training mode runs the one-workgroup-per-channel backward where a channel fits (N*S <= 32768, S % 4 == 0) and the
+    reduce + apply pair otherwise / when forced.  With 512 threads per channel workgroup these shapes give 100, 384, 4096
+    and 6144 groups of four, i.e. 1, 8 and 16 register groups per thread; 2 and 4, ragged last slices and the limits
+    themselves are in tests/test_gpu_norm_forms.py, which holds every form to per-element fp64 bounds."""
     if two_pass:
         monkeypatch.setenv("SELD_BN_TWO_PASS", "1")
     H, hnn = pkg().hip_ops, pkg().hip_nn
@@ -213,6 +215,68 @@ def test_maxpool(shape, ph, pw):
     (yr * cot.double()).sum().backward()
     _close(y, yr, rel=0)
     _close(xd.grad, x64.grad, rel=0)
+
+
+def _same(got, ref, what):
+    """Exactly equal, a NaN in the same place counting as equal."""
+    got, ref = got.detach().cpu().double(), ref.detach().double()
+    assert got.shape == ref.shape, (what, got.shape, ref.shape)
+    same = (got == ref) | (got.isnan() & ref.isnan())
+    assert bool(same.all()), f"{what}: {int((~same).sum())} elements differ, first at {int((~same).reshape(-1).float().argmax())}"
+
+
+@pytest.mark.parametrize("shape,ph,pw", [((3, 5, 64), 1, 2), ((2, 3, 9, 10), 2, 3), ((1, 2, 30, 34), 15, 17)])
+def test_maxpool_ties_infinities_and_nan(shape, ph, pw):
+    """In the model pooling follows ReLU, so all-zero windows are the common case: the FIRST maximum takes the whole
+    gradient (torch's rule), also when the maximum repeats at the first and the last position; a window of -inf only
+    yields -inf and its first element the gradient; a NaN in a non-first position propagates and takes the gradient.
+    15 x 17 = 255 positions is what the uint8 index can hold: a maximum at the last position, index 254."""
+    H = pkg().hip_ops
+    torch.manual_seed(4)
+    x = torch.randn(shape).abs() + 0.1                    # positive: a zero window below is all ties, not a minimum
+    v = x.view(-1, *((1,) * (4 - len(shape))), *shape[2:]) if len(shape) == 3 else x.view(-1, *shape[2:])
+    W = v.shape[-1]
+    OW = W // pw
+    win = lambda k: (k // OW * ph, k % OW * pw)           # top-left corner of window k of a plane
+    planes = v.shape[0]
+    assert planes >= 5 or OW * (v.shape[1] // ph) >= 4
+    # one special window per plane, cycling through the cases
+    cases = ("zeros", "first_last", "neg_inf", "nan", "last", "all_equal")
+    seen = set()
+    for p in range(planes):
+        for k in range(min(4, OW * (v.shape[1] // ph))):
+            case = cases[(p * 4 + k) % len(cases)]
+            seen.add(case)
+            r, c = win(k)
+            w_ = v[p, r:r + ph, c:c + pw]
+            if case == "zeros":
+                w_.zero_()
+            elif case == "first_last":
+                w_[0, 0] = w_[-1, -1] = 9.0
+            elif case == "neg_inf":
+                w_.fill_(float("-inf"))
+            elif case == "nan":
+                w_[-1, -1] = float("nan")
+            elif case == "last":
+                w_[-1, -1] = 9.0
+            else:
+                w_.fill_(0.625)
+    assert seen == set(cases)
+    xd = x.to(DEV).requires_grad_(True)
+    y = H.maxpool(xd, ph, pw)
+    cot = torch.randn(y.shape) + 3.0                      # never zero: a gradient in the wrong place cannot hide
+    y.backward(cot.to(DEV))
+    x64 = x.double().requires_grad_(True)
+    yr = F.max_pool1d(x64, pw) if len(shape) == 3 else F.max_pool2d(x64, (ph, pw))
+    yr.backward(cot.double())
+    _same(y, yr, "y")
+    _same(xd.grad, x64.grad, "dx")
+    # the rule itself, not only agreement with torch: one position per window carries the gradient, and in a window of
+    # ties it is the first
+    g = xd.grad.cpu().view(v.shape)
+    r, c = win(0)                                         # plane 0, window 0: all zeros
+    assert g[0, r, c] != 0 and int((g[0, r:r + ph, c:c + pw] != 0).sum()) == 1
+    assert int((g != 0).sum()) == y.numel()
 
 
 def test_mha_module_matches_fixture(golden):
