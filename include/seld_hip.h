@@ -844,6 +844,46 @@ int seld_event_metrics_accumulate(const double* pred_rows, const int64_t* pred_o
                                   int64_t* flags, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * seld_event_metrics_accumulate_ex: the call above with two more arguments behind frames_per_block.
+ *   coords      3: rows are (count, 5) double { frame, class, x, y, z }, as above.
+ *               2: rows are (count, 4) double { frame, class, azimuth, elevation } in DEGREES, as DCASE label
+ *                  files give them.  The distance is the reference's for two-entry DOAs, operation by operation
+ *                  with contraction off: v * pi / 180. first, then sin(e1) sin(e2) + cos(e1) cos(e2) cos(|a1 - a2|),
+ *                  clipped to [-1, 1], acos(..) * 180 / pi (distance_between_spherical_coordinates_rad).
+ *                  counters[0..2] are Euclidean and have no meaning for such rows: NOTHING is added to them;
+ *                  counters[3..12] and [13..15] are computed; nb_classes = 0 adds to [13..15] alone.
+ *   max_tracks  1 .. 8: events of one (recording, frame, class) cell the association takes; flags[1] counts
+ *               the cells with more, and a call with flags[1] != 0 is refused and adds nothing, as above.
+ * A cell of g references and q predictions costs a minimum-cost matching of min(g, q) pairs
+ * (scipy.optimize.linear_sum_assignment).  Where several matchings cost the same, the first row -> column map in
+ * lexicographic order wins, an unmatched row counting as a column above every real one.  Cells with at most 3
+ * events on both sides are solved by the same code under every max_tracks, so they give the same bits.
+ * SELD_EINVAL: coords outside {2, 3}, max_tracks outside [1, 8], and everything that is SELD_EINVAL above.
+ * seld_event_metrics_accumulate(...) is this call with coords = 3 and max_tracks = 3.
+ *
+ * seld_least_distance: least_distance_between_gt_pred (Dcase21_metrics.py:191-220) for a batch.  Problem b has
+ * gt_counts[b] reference and pred_counts[b] predicted DOAs of `coords` doubles each, the first entries of
+ * gt[b] and pred[b] in padded (problems, 8, coords) arrays: Cartesian { x, y, z } as they are, spherical
+ * { azimuth, elevation } in RADIANS, as the reference's function takes them.  Counts are forced into [0, 8] on the
+ * device (the caller refuses longer lists).  WRITES, per problem, n = min(g, q) pairs:
+ *   cost (problems, 8) double, row, col (problems, 8) int32: pair k < n is reference row[k] with prediction
+ *        col[k] at cost[k] degrees, rows ascending as scipy returns them; entries from n on are 0 / -1 / -1
+ *   pairs (problems) int32 = n
+ * by the device functions of the scoring kernel (same distances, same tie rule).  SELD_EINVAL: problems < 0,
+ * coords outside {2, 3}, a NULL pointer with problems > 0; SELD_EUNSUPPORTED: 2^28 problems or more.  One launch,
+ * no workspace, no host read.
+ * ------------------------------------------------------------------------------------------ */
+#define SELD_EVENT_METRICS_MAX_TRACKS_EX 8
+int seld_event_metrics_accumulate_ex(const double* pred_rows, const int64_t* pred_offsets, int64_t pred_count,
+                                     const double* true_rows, const int64_t* true_offsets, int64_t true_count,
+                                     int64_t recordings, int32_t n_frames, int32_t nb_classes, int32_t frames_per_block,
+                                     int32_t coords, int32_t max_tracks, double spatial_threshold, double doa_threshold,
+                                     int64_t* counters, double* total_de, int64_t* flags, void* stream);
+int seld_least_distance(const double* gt, const int32_t* gt_counts, const double* pred, const int32_t* pred_counts,
+                        int64_t problems, int32_t coords, double* cost, int32_t* row, int32_t* col, int32_t* pairs,
+                        void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Event decoding: the submission rows of resident network outputs (csrc/decode.hip).  Replaces
  * gen_submission_list_task2_OLD (utility_functions.py:158-181) and gen_submission_list_task2
  * (utility_functions.py:184-210), which train.py:110-116 calls on the prediction and on the target of

@@ -1,8 +1,12 @@
 """Drop-in for the reference's Dcase21_metrics.py: same names, signatures and return types.  SELDMetrics counts on the
-device (hip_ops.score_events, csrc/event_metrics.hip); segment_labels, the distance functions and early_stopping_metric
-are host functions on Python and numpy values, as in the reference.
+device (hip_ops.score_events, csrc/event_metrics.hip) and least_distance_between_gt_pred associates there
+(hip_ops.assign_doas); segment_labels, the distance functions and early_stopping_metric are host functions on Python and
+numpy values, as in the reference.
 
-Limits of the device path: Cartesian coordinates only, at most 3 events of one class in one frame, at most 64 classes."""
+Limits of the device path: events are Cartesian (x, y, z) or spherical (azimuth, elevation in degrees), one form per
+call; at most `max_tracks` events of one class in one frame (3 unless SELDMetrics is given more, 8 at most); at most 64
+classes; least_distance_between_gt_pred takes at most 8 DOAs a side.  Where several associations of a frame cost the
+same, the first row -> column map in lexicographic order is taken (scipy's choice among equals is its own)."""
 import numpy as np
 import torch
 
@@ -13,14 +17,16 @@ eps = np.finfo(float).eps
 
 
 class SELDMetrics(object):
-    def __init__(self, doa_threshold=20, nb_classes=14):
+    def __init__(self, doa_threshold=20, nb_classes=14, max_tracks=3):
         '''
             This class implements both the class-sensitive localization and location-sensitive detection metrics.
 
         :param nb_classes: Number of sound classes.
         :param doa_thresh: DOA threshold for location sensitive detection.
+        :param max_tracks: events of one class in one frame the device association takes (1 .. 8).
         '''
         self._nb_classes = nb_classes
+        self._max_tracks = max_tracks
 
         # Variables for Location-senstive detection performance
         self._TP = 0
@@ -68,12 +74,17 @@ class SELDMetrics(object):
         '''
         The fast form of segment_labels + update_seld_scores for callers who hold rows: (E, 5) float64 device tensors
         [frame, class, x, y, z] with (R + 1,) int64 offsets, as hip_ops.decode_events returns them, every recording of
-        `max_frames` frames.  No dictionary is built.
+        `max_frames` frames.  No dictionary is built.  Rows of 4 columns are [frame, class, azimuth, elevation] in degrees.
         '''
+        widths = {t.shape[1] for t in (pred_rows, true_rows) if torch.is_tensor(t) and t.dim() == 2 and t.numel()}
+        if len(widths) > 1:
+            raise L.SeldHipError(f"update_from_events: rows of {sorted(widths)} columns in one call")
+        coords = 2 if widths == {4} else 3              # any other width is score_events' to refuse
         on_device = torch.is_tensor(pred_rows) and pred_rows.is_cuda      # otherwise score_events' own checks raise
         acc = H.event_metrics_new(pred_rows.device if on_device else torch.device("cuda", torch.cuda.current_device()))
         H.score_events(acc, pred_rows, pred_offsets, true_rows, true_offsets, max_frames, nb_classes=self._nb_classes,
-                       doa_threshold=self._spatial_T, frames_per_block=frames_per_block)
+                       doa_threshold=self._spatial_T, frames_per_block=frames_per_block, coords=coords,
+                       max_tracks=self._max_tracks)
         self._add(acc)
 
     def update_seld_scores(self, pred, gt):
@@ -83,7 +94,7 @@ class SELDMetrics(object):
 
         :param pred: dictionary containing class-wise prediction results for each N-seconds segment block
         :param gt: dictionary containing class-wise groundtruth for each N-seconds segment block
-        (what segment_labels returns; Cartesian coordinates)
+        (what segment_labels returns; all events Cartesian, or all azimuth and elevation in degrees)
         '''
         nb_blocks = len(gt.keys())
         for block_cnt in range(nb_blocks):
@@ -97,6 +108,7 @@ class SELDMetrics(object):
             raise L.SeldHipError("update_seld_scores: no HIP device (this package has no CPU path)")
         dev = torch.device("cuda", torch.cuda.current_device())
         sides = []
+        coords = None                                   # of the first event seen; every other must agree
         for d in (pred, gt):
             rows = []
             for b in range(nb_blocks):
@@ -107,17 +119,23 @@ class SELDMetrics(object):
                     for k, vals in zip(frame_keys, frame_vals):
                         for v in vals:
                             doa = list(v)[:-1]          # the reference's [:, :-1]: everything but the last entry
-                            if len(doa) != 3:
+                            if len(doa) not in (2, 3):
                                 raise L.SeldHipError(f"update_seld_scores: {len(doa)} coordinates per event; the device path "
-                                                     "takes Cartesian x, y, z (spherical input is not supported)")
+                                                     "takes Cartesian x, y, z or azimuth, elevation in degrees")
+                            coords = len(doa) if coords is None else coords
+                            if len(doa) != coords:
+                                raise L.SeldHipError("update_seld_scores: events of two and of three coordinates in one call")
                             rows.append([b * K + k, c] + doa)
-            a = np.asarray(rows, dtype=np.float64).reshape(-1, 5)
+            sides.append(rows)
+        coords = 3 if coords is None else coords
+        for i, rows in enumerate(sides):
+            a = np.asarray(rows, dtype=np.float64).reshape(-1, 2 + coords)
             a = a[np.argsort(a[:, 0], kind="stable")]
-            sides.append((torch.from_numpy(np.ascontiguousarray(a)).to(dev),
-                          torch.tensor([0, a.shape[0]], dtype=torch.int64).to(dev)))
+            sides[i] = (torch.from_numpy(np.ascontiguousarray(a)).to(dev),
+                        torch.tensor([0, a.shape[0]], dtype=torch.int64).to(dev))
         acc = H.event_metrics_new(dev)
         H.score_events(acc, sides[0][0], sides[0][1], sides[1][0], sides[1][1], nb_blocks * K, nb_classes=self._nb_classes,
-                       doa_threshold=self._spatial_T, frames_per_block=K)
+                       doa_threshold=self._spatial_T, frames_per_block=K, coords=coords, max_tracks=self._max_tracks)
         self._add(acc)
         return
 
@@ -147,6 +165,37 @@ def distance_between_cartesian_coordinates(x1, y1, z1, x2, y2, z2):
     dist = x1*x2 + y1*y2 + z1*z2
     dist = np.clip(dist, -1, 1)
     return np.arccos(dist) * 180 / np.pi
+
+
+def least_distance_between_gt_pred(gt_list, pred_list):
+    """
+        Shortest distance between two sets of DOA coordinates: the cost matrix of every reference against every
+        predicted DOA and its least-cost association, on the device (hip_ops.assign_doas).
+        :param gt_list: (g, 3) Cartesian or (g, 2) spherical coordinates in radians, g <= 8
+        :param pred_list: (q, 3) or (q, 2) likewise, q <= 8
+        :return: cost - distances of the min(g, q) associated pairs in degrees
+        :return: row_ind, col_ind - their reference and predicted indices, rows ascending
+    """
+    gt_list, pred_list = np.asarray(gt_list, dtype=np.float64), np.asarray(pred_list, dtype=np.float64)
+    g, q = gt_list.shape[0], pred_list.shape[0]
+    if g == 0 or q == 0:
+        return np.zeros(0), np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int64)
+    M = H.EVENT_METRICS_MAX_TRACKS_EX
+    if g > M or q > M:
+        raise L.SeldHipError(f"least_distance_between_gt_pred: {g} against {q} DOAs; the device association takes {M} a side")
+    C = 3 if len(gt_list[0]) == 3 else 2                # the reference's test
+    if gt_list.ndim != 2 or pred_list.ndim != 2 or gt_list.shape[1] != C or pred_list.shape[1] != C:
+        raise L.SeldHipError(f"least_distance_between_gt_pred: DOAs of shapes {gt_list.shape} and {pred_list.shape}")
+    if not torch.cuda.is_available():
+        raise L.SeldHipError("least_distance_between_gt_pred: no HIP device (this package has no CPU path)")
+    dev = torch.device("cuda", torch.cuda.current_device())
+    padded = np.zeros((2, 1, M, C))
+    padded[0, 0, :g], padded[1, 0, :q] = gt_list, pred_list
+    both = torch.from_numpy(padded).to(dev)
+    counts = torch.tensor([[g], [q]], dtype=torch.int32).to(dev)
+    cost, row, col, _ = H.assign_doas(both[0], both[1], counts[0], counts[1], spherical=C == 2)
+    n = min(g, q)
+    return cost[0, :n].cpu().numpy(), row[0, :n].cpu().numpy().astype(np.int64), col[0, :n].cpu().numpy().astype(np.int64)
 
 
 def early_stopping_metric(sed_error, doa_error):

@@ -1,5 +1,6 @@
 // Scoring event lists on the device: the public surface of the reference's metrics.py (task 2) and
-// Dcase21_metrics.py for rows [frame, class, x, y, z] as decode.hip writes them.
+// Dcase21_metrics.py for rows [frame, class, x, y, z] as decode.hip writes them, or [frame, class, azimuth, elevation]
+// in degrees as DCASE label files give them (COORDS = 3 / 2; a row is 2 + COORDS doubles).
 //
 // Replaces, for a batch of recordings given as two row lists with CSR offsets (prediction and reference):
 //   location_sensitive_detection   metrics.py:123-208             (frame-wise TP / FP / FN with a distance threshold)
@@ -14,29 +15,35 @@
 // frame is kept as given: the position of an event in its frame's list of its class is its track.
 //
 // Two kernels per call:
-//   event_check_kernel    one thread per row: rows whose frame is no integer in [0, n_frames) -> flags[0]; the fourth
-//                         event of a (recording, frame, class) cell the DCASE part would read -> flags[1].
+//   event_check_kernel    one thread per row: rows whose frame is no integer in [0, n_frames) -> flags[0]; event
+//                         max_tracks + 1 of a (recording, frame, class) cell the DCASE part would read -> flags[1].
 //   event_metrics_kernel  starts only when flags[1] is zero (a refused call adds nothing).  One wave owns one (recording,
 //                         block) unit at a time: it finds the unit's rows by bisection of the sorted frame column, copies
 //                         them to LDS with coalesced 8-byte loads (40-byte rows: nothing wider is aligned), and works on
 //                         the copy.  A unit with more than EV_CAP rows on one side is read from memory in place by the
 //                         same code.  Counters stay in registers; 16 + 1 atomics per wave at the end.
+// The kernel is compiled for max_tracks <= 3 (every lane solves the cells of its class by enumeration, assign_3x3) and for
+// max_tracks <= 8 (WIDE: a cell with 4 to 8 events on a side is handed to the whole wave, assign_wave_8x8; a cell with at
+// most 3 on both sides still takes the enumeration, so it gives the same bits in both).
+// least_distance_kernel solves a batch of associations alone (least_distance_between_gt_pred, Dcase21_metrics.py:191-220)
+// with the same device functions.
 #include "metrics_common.h"
 
 namespace seld {
 
 constexpr int EV_COUNTERS = 16;     // the 13 of metrics.hip | TP FP FN of sed_score_computation
 constexpr int EV_CAP = 256;         // rows of one side of a unit staged in LDS (2 x 10 KB per wave)
+constexpr int EV_WIDE = 8;          // SELD_EVENT_METRICS_MAX_TRACKS_EX: events of a cell assign_wave_8x8 takes
 
 struct EventP {
-    const double* pred;             // (pred_n, 5)
+    const double* pred;             // (pred_n, 2 + COORDS)
     const long long* pred_off;      // (recordings + 1)
     long long pred_n;
     const double* tru;
     const long long* true_off;
     long long true_n;
     long long recordings, blocks;
-    int n_frames, classes, fpb;
+    int n_frames, classes, fpb, max_tracks;
     double spatial_threshold, doa_threshold;
     long long* counters;
     double* total_de;
@@ -51,18 +58,21 @@ __device__ __forceinline__ void rec_range(const long long* off, long long r, lon
 }
 
 // first row in [lo, hi) whose frame is not below `key` (a NaN frame counts as not below)
-template <class Index>
+template <int S, class Index>
 __device__ __forceinline__ Index first_frame_not_below(const double* rows, Index lo, Index hi, double key) {
     while (lo < hi) {
         const Index mid = lo + (hi - lo) / 2;
-        if (rows[mid * 5] < key) lo = mid + 1; else hi = mid;
+        if (rows[mid * S] < key) lo = mid + 1; else hi = mid;
     }
     return lo;
 }
 
 __device__ __forceinline__ bool whole_in(double f, double lo, double hi) { return f >= lo && f < hi && f == floor(f); }
 
+template <int COORDS>
 __global__ __launch_bounds__(256) void event_check_kernel(const EventP p) {
+    constexpr int S = 2 + COORDS;
+    const int mt = p.max_tracks;
     const long long total = p.pred_n + p.true_n;
     const double dcase_end = (double)p.blocks * (double)p.fpb;
     long long bad_frame = 0, bad_cell = 0;
@@ -82,12 +92,12 @@ __global__ __launch_bounds__(256) void event_check_kernel(const EventP p) {
         long long lo, hi;
         rec_range(off, a - 1, n, lo, hi);
         if (row < lo || row >= hi) continue;
-        const double f = rows[row * 5], c = rows[row * 5 + 1];
+        const double f = rows[row * S], c = rows[row * S + 1];
         if (!whole_in(f, 0.0, (double)p.n_frames)) ++bad_frame;
         if (whole_in(f, 0.0, dcase_end) && whole_in(c, 0.0, (double)p.classes)) {
             int earlier = 0;                            // events of the same cell in front of this one
-            for (long long j = row - 1; j >= lo && rows[j * 5] == f && earlier <= 3; --j) earlier += rows[j * 5 + 1] == c ? 1 : 0;
-            if (earlier == 3) ++bad_cell;               // the fourth event of its cell: every overflowing cell has one
+            for (long long j = row - 1; j >= lo && rows[j * S] == f && earlier <= mt; --j) earlier += rows[j * S + 1] == c ? 1 : 0;
+            if (earlier == mt) ++bad_cell;              // event max_tracks + 1 of its cell: every overflowing cell has one
         }
     }
     bad_frame = wave_sum_i64(bad_frame);
@@ -100,41 +110,51 @@ __global__ __launch_bounds__(256) void event_check_kernel(const EventP p) {
 
 // One unit: P (np rows) and T (nt rows) are the predictions and references of one recording whose frames lie in the
 // block [f0, f0 + fpb), each sorted by frame; in LDS or in memory (inlined once for each).
+// COORDS = 2: the Euclidean counters cnt[0..2] have no meaning and are left alone.  WIDE: h and cs are the LDS of
+// assign_wave_8x8.
+template <int COORDS, bool WIDE>
 __device__ __forceinline__ void score_unit(const double* P, int np, const double* T, int nt, const EventP& p, double f0, int lane,
-                                           long long (&cnt)[EV_COUNTERS], double& total_de) {
+                                           long long (&cnt)[EV_COUNTERS], double& total_de, double* h, double* cs) {
+    constexpr int S = 2 + COORDS;
+    constexpr int NT = WIDE ? EV_WIDE : 3;              // reference tracks a class can have
     // ---- location_sensitive_detection and sed_score_computation: lane = row ----
     // Per frame: no reference -> FP += 2 p; no prediction -> FN += 2 t; else TP += m, FN += t - m, FP += p - m.  Row by
     // row that is: a prediction adds 1 to FP (2 where its frame has no reference), a reference adds 2 to FN where its
     // frame has no prediction, else TP + 1 and FP - 1 when matched, FN + 1 when not.  cnt[13..15] the same on the class alone.
     const double lsd_end = (double)p.n_frames;
     for (int i = lane; i < np; i += 64) {
-        const double f = P[i * 5];
+        const double f = P[i * S];
         if (!whole_in(f, 0.0, lsd_end)) continue;
-        const int j = first_frame_not_below(T, 0, nt, f);
-        const int add = (j < nt && T[j * 5] == f) ? 1 : 2;
-        cnt[1] += add;
+        const int j = first_frame_not_below<S>(T, 0, nt, f);
+        const int add = (j < nt && T[j * S] == f) ? 1 : 2;
+        if constexpr (COORDS == 3) cnt[1] += add;
         cnt[14] += add;
     }
     for (int i = lane; i < nt; i += 64) {
-        const double f = T[i * 5];
+        const double f = T[i * S];
         if (!whole_in(f, 0.0, lsd_end)) continue;
-        int j = first_frame_not_below(P, 0, np, f);
-        if (!(j < np && P[j * 5] == f)) {
-            cnt[2] += 2;
+        int j = first_frame_not_below<S>(P, 0, np, f);
+        if (!(j < np && P[j * S] == f)) {
+            if constexpr (COORDS == 3) cnt[2] += 2;
             cnt[15] += 2;
             continue;
         }
-        const double c = T[i * 5 + 1], x = T[i * 5 + 2], y = T[i * 5 + 3], z = T[i * 5 + 4];
+        const double c = T[i * S + 1];
         bool near = false, same = false;
-        for (; j < np && P[j * 5] == f; ++j) {
-            if (P[j * 5 + 1] != c) continue;
-            same = true;
-            const double dx = x - P[j * 5 + 2], dy = y - P[j * 5 + 3], dz = z - P[j * 5 + 4];
-            if (sqrt(dx * dx + dy * dy + dz * dz) < p.spatial_threshold) near = true;
+        if constexpr (COORDS == 3) {
+            const double x = T[i * S + 2], y = T[i * S + 3], z = T[i * S + 4];
+            for (; j < np && P[j * S] == f; ++j) {
+                if (P[j * S + 1] != c) continue;
+                same = true;
+                const double dx = x - P[j * S + 2], dy = y - P[j * S + 3], dz = z - P[j * S + 4];
+                if (sqrt(dx * dx + dy * dy + dz * dz) < p.spatial_threshold) near = true;
+            }
+            cnt[0] += near ? 1 : 0;
+            cnt[1] -= near ? 1 : 0;
+            cnt[2] += near ? 0 : 1;
+        } else {
+            for (; j < np && P[j * S] == f; ++j) same = same || P[j * S + 1] == c;
         }
-        cnt[0] += near ? 1 : 0;
-        cnt[1] -= near ? 1 : 0;
-        cnt[2] += near ? 0 : 1;
         cnt[13] += same ? 1 : 0;
         cnt[14] -= same ? 1 : 0;
         cnt[15] += same ? 0 : 1;
@@ -143,59 +163,111 @@ __device__ __forceinline__ void score_unit(const double* P, int np, const double
 
     // ---- DCASE21 block metrics: lane = class ----
     // Every lane walks the two lists together, frame by frame in ascending order, and keeps the events of its own class:
-    // up to 3 references g and 3 predictions q of the frame in registers, the longest list of each side, and per
-    // reference track the sum and count of its matched distances.
+    // up to 3 references g and 3 predictions q of the frame in registers (spherical ones turned into radians as they are
+    // read), the longest list of each side, and per reference track the sum and count of its matched distances.
     const double mine = lane < p.classes ? (double)lane : __builtin_nan("");      // NaN equals no class
-    int ip = 0, it = 0, nb_gt = 0, nb_pred = 0, n0 = 0, n1 = 0, n2 = 0;
-    double s0 = 0.0, s1 = 0.0, s2 = 0.0;
+    int ip = 0, it = 0, nb_gt = 0, nb_pred = 0;
+    int n[NT];
+    double s[NT];
+#pragma unroll
+    for (int r = 0; r < NT; ++r) {
+        n[r] = 0;
+        s[r] = 0.0;
+    }
     while (ip < np || it < nt) {
-        const double fp = ip < np ? P[ip * 5] : __builtin_inf(), ft = it < nt ? T[it * 5] : __builtin_inf();
+        const double fp = ip < np ? P[ip * S] : __builtin_inf(), ft = it < nt ? T[it * S] : __builtin_inf();
         if (fp != fp) { ++ip; continue; }               // a NaN frame belongs to no block: stepped over, wherever it sorts
         if (ft != ft) { ++it; continue; }
         const double f = fmin(fp, ft);
         const bool frame_ok = whole_in(f, f0, f0 + (double)p.fpb);
-        double ga[3][3], qa[3][3];
+        double ga[3][COORDS], qa[3][COORDS];
         int g = 0, q = 0;
-        for (; it < nt && !(T[it * 5] > f); ++it) {      // not above: a NaN frame is stepped over, never waited for
-            if (!(frame_ok && T[it * 5] == f && T[it * 5 + 1] == mine)) continue;
+        const int it0 = it, ip0 = ip;                   // the frame's rows are [it0, it) and [ip0, ip) after the two loops
+        for (; it < nt && !(T[it * S] > f); ++it) {      // not above: a NaN frame is stepped over, never waited for
+            if (!(frame_ok && T[it * S] == f && T[it * S + 1] == mine)) continue;
 #pragma unroll
             for (int e = 0; e < 3; ++e)
                 if (g == e) {
 #pragma unroll
-                    for (int k = 0; k < 3; ++k) ga[e][k] = T[it * 5 + 2 + k];
+                    for (int k = 0; k < COORDS; ++k) ga[e][k] = COORDS == 3 ? T[it * S + 2 + k] : deg_to_rad(T[it * S + 2 + k]);
                 }
             ++g;
         }
-        for (; ip < np && !(P[ip * 5] > f); ++ip) {
-            if (!(frame_ok && P[ip * 5] == f && P[ip * 5 + 1] == mine)) continue;
+        for (; ip < np && !(P[ip * S] > f); ++ip) {
+            if (!(frame_ok && P[ip * S] == f && P[ip * S + 1] == mine)) continue;
 #pragma unroll
             for (int e = 0; e < 3; ++e)
                 if (q == e) {
 #pragma unroll
-                    for (int k = 0; k < 3; ++k) qa[e][k] = P[ip * 5 + 2 + k];
+                    for (int k = 0; k < COORDS; ++k) qa[e][k] = COORDS == 3 ? P[ip * S + 2 + k] : deg_to_rad(P[ip * S + 2 + k]);
                 }
             ++q;
         }
-        g = min(g, 3);                                  // a longer list is refused by event_check_kernel before this runs
-        q = min(q, 3);
+        g = min(g, NT);                                 // a longer list is refused by event_check_kernel before this runs
+        q = min(q, NT);
         nb_gt = max(nb_gt, g);
         nb_pred = max(nb_pred, q);
-        if (g && q) {
+        const bool wide = WIDE && g && q && (g > 3 || q > 3);
+        if (g && q && !wide) {
             double cost[9];
 #pragma unroll
             for (int e = 0; e < 3; ++e)
 #pragma unroll
-                for (int e2 = 0; e2 < 3; ++e2) cost[e * 3 + e2] = (e < g && e2 < q) ? angular_distance_deg(ga[e], qa[e2]) : 0.0;
+                for (int e2 = 0; e2 < 3; ++e2) cost[e * 3 + e2] = (e < g && e2 < q) ? doa_distance_deg<COORDS>(ga[e], qa[e2]) : 0.0;
             double o0 = -1.0, o1 = -1.0, o2 = -1.0;
             assign_3x3((1u << g) - 1u, (1u << q) - 1u, cost, o0, o1, o2);
-            if (o0 >= 0.0) { s0 += o0; ++n0; }
-            if (o1 >= 0.0) { s1 += o1; ++n1; }
-            if (o2 >= 0.0) { s2 += o2; ++n2; }
+            if (o0 >= 0.0) { s[0] += o0; ++n[0]; }
+            if (o1 >= 0.0) { s[1] += o1; ++n[1]; }
+            if (o2 >= 0.0) { s[2] += o2; ++n[2]; }
+        }
+        if constexpr (WIDE) {
+            // the classes whose cell of this frame is larger than 3 x 3, one after the other, each by the whole wave: lane
+            // 8 i + j finds reference i and prediction j of the class among the frame's rows and brings their distance
+            unsigned long long todo = __builtin_amdgcn_ballot_w64(wide);
+            while (todo) {
+                const int c = __ffsll((long long)todo) - 1;
+                todo &= todo - 1ull;
+                const int gc = __shfl(g, c, 64), qc = __shfl(q, c, 64);
+                const int i = lane >> 3, j = lane & 7;
+                const double cd = (double)c;
+                int ti = -1, pj = -1, seen = 0;
+                for (int r = it0; r < it; ++r) {
+                    if (!(T[r * S] == f && T[r * S + 1] == cd)) continue;
+                    ti = seen == i ? r : ti;
+                    ++seen;
+                }
+                seen = 0;
+                for (int r = ip0; r < ip; ++r) {
+                    if (!(P[r * S] == f && P[r * S + 1] == cd)) continue;
+                    pj = seen == j ? r : pj;
+                    ++seen;
+                }
+                double d = 0.0;
+                if (i < gc && j < qc && ti >= 0 && pj >= 0) {
+                    double a[COORDS], b[COORDS];
+#pragma unroll
+                    for (int k = 0; k < COORDS; ++k) {
+                        a[k] = COORDS == 3 ? T[ti * S + 2 + k] : deg_to_rad(T[ti * S + 2 + k]);
+                        b[k] = COORDS == 3 ? P[pj * S + 2 + k] : deg_to_rad(P[pj * S + 2 + k]);
+                    }
+                    d = doa_distance_deg<COORDS>(a, b);
+                }
+                const int col = assign_wave_8x8(gc, qc, d, lane, h, cs);
+#pragma unroll
+                for (int r = 0; r < EV_WIDE; ++r) {
+                    const int cr = __shfl(col, r, 64);                      // the column of reference track r
+                    const double dr = __shfl(d, r * 8 + (cr & 7), 64);
+                    if (lane == c && r < gc && cr < qc) {
+                        s[r] += dr;
+                        ++n[r];
+                    }
+                }
+            }
         }
     }
     int loc_fn = 0, loc_fp = 0;
     if (lane < p.classes) {
-        const DcaseAdd a = dcase_class_block(nb_gt, nb_pred, s0, s1, s2, n0, n1, n2, p.doa_threshold, total_de);
+        const DcaseAdd a = dcase_class_block_n<NT>(nb_gt, nb_pred, s, n, p.doa_threshold, total_de);
         SELD_DCASE_ADD(cnt, a);
         loc_fn = a.fn;
         loc_fp = a.fp;
@@ -208,9 +280,17 @@ __device__ __forceinline__ void score_unit(const double* P, int np, const double
     }
 }
 
+template <int COORDS, bool WIDE>
 __global__ __launch_bounds__(64) void event_metrics_kernel(const EventP p) {
-    __shared__ __attribute__((aligned(16))) double pred_s[EV_CAP * 5];
-    __shared__ __attribute__((aligned(16))) double true_s[EV_CAP * 5];
+    constexpr int S = 2 + COORDS;
+    __shared__ __attribute__((aligned(16))) double pred_s[EV_CAP * S];
+    __shared__ __attribute__((aligned(16))) double true_s[EV_CAP * S];
+    double *h = nullptr, *cs = nullptr;
+    if constexpr (WIDE) {                               // 2.5 KB more, in the instantiations that use it alone
+        __shared__ double h_s[256], cs_s[64];
+        h = h_s;
+        cs = cs_s;
+    }
     if (p.flags[1] != 0) return;                        // refused by event_check_kernel: nothing is added
     const int lane = threadIdx.x;
     long long cnt[EV_COUNTERS];
@@ -224,18 +304,18 @@ __global__ __launch_bounds__(64) void event_metrics_kernel(const EventP p) {
         long long plo = 0, phi = 0, tlo = 0, thi = 0;
         if (p.pred_n) rec_range(p.pred_off, rec, p.pred_n, plo, phi);
         if (p.true_n) rec_range(p.true_off, rec, p.true_n, tlo, thi);
-        const long long p0 = first_frame_not_below(p.pred, plo, phi, f0), p1 = first_frame_not_below(p.pred, p0, phi, f1);
-        const long long t0 = first_frame_not_below(p.tru, tlo, thi, f0), t1 = first_frame_not_below(p.tru, t0, thi, f1);
+        const long long p0 = first_frame_not_below<S>(p.pred, plo, phi, f0), p1 = first_frame_not_below<S>(p.pred, p0, phi, f1);
+        const long long t0 = first_frame_not_below<S>(p.tru, tlo, thi, f0), t1 = first_frame_not_below<S>(p.tru, t0, thi, f1);
         const int np = (int)(p1 - p0), nt = (int)(t1 - t0);
         if (np == 0 && nt == 0) continue;
         if (np <= EV_CAP && nt <= EV_CAP) {
-            for (int i = lane; i < np * 5; i += 64) pred_s[i] = p.pred[p0 * 5 + i];
-            for (int i = lane; i < nt * 5; i += 64) true_s[i] = p.tru[t0 * 5 + i];
+            for (int i = lane; i < np * S; i += 64) pred_s[i] = p.pred[p0 * S + i];
+            for (int i = lane; i < nt * S; i += 64) true_s[i] = p.tru[t0 * S + i];
             __syncthreads();
-            score_unit(pred_s, np, true_s, nt, p, f0, lane, cnt, total_de);
+            score_unit<COORDS, WIDE>(pred_s, np, true_s, nt, p, f0, lane, cnt, total_de, h, cs);
             __syncthreads();                            // the copy is rewritten by the next unit
         } else {
-            score_unit(p.pred + p0 * 5, np, p.tru + t0 * 5, nt, p, f0, lane, cnt, total_de);
+            score_unit<COORDS, WIDE>(p.pred + p0 * S, np, p.tru + t0 * S, nt, p, f0, lane, cnt, total_de, h, cs);
         }
     }
 #pragma unroll
@@ -247,18 +327,57 @@ __global__ __launch_bounds__(64) void event_metrics_kernel(const EventP p) {
     if (lane == 0 && de != 0.0) atomicAdd(p.total_de, de);
 }
 
+struct AssignP {
+    const double *gt, *pred;        // (problems, 8, COORDS)
+    const int *gt_n, *pred_n;
+    long long problems;
+    double* cost;                   // (problems, 8)
+    int *row, *col, *pairs;         // (problems, 8) twice, (problems)
+};
+
+// One wave per problem at a time.  Counts are forced into [0, 8], so nothing outside the arrays is read.
+template <int COORDS>
+__global__ __launch_bounds__(64) void least_distance_kernel(const AssignP p) {
+    __shared__ double h[256], cs[64];
+    const int lane = threadIdx.x, i = lane >> 3, j = lane & 7;
+    for (long long b = blockIdx.x; b < p.problems; b += gridDim.x) {
+        const int g = min(max(p.gt_n[b], 0), EV_WIDE), q = min(max(p.pred_n[b], 0), EV_WIDE);
+        double d = 0.0;
+        if (i < g && j < q) d = doa_distance_deg<COORDS>(p.gt + (b * 8 + i) * COORDS, p.pred + (b * 8 + j) * COORDS);
+        const int col = assign_wave_8x8(g, q, d, lane, h, cs);
+        const bool on = lane < g && col < q;            // lane = reference; g <= 8
+        const unsigned long long matched = __builtin_amdgcn_ballot_w64(on);
+        const double mine = __shfl(d, j * 8 + (col & 7), 64);
+        const int pairs = min(g, q);
+        if (on) {                                       // rows ascending, as linear_sum_assignment returns them
+            const int k = __popcll(matched & ((1ull << lane) - 1ull));
+            p.cost[b * 8 + k] = mine;
+            p.row[b * 8 + k] = lane;
+            p.col[b * 8 + k] = col;
+        }
+        if (lane >= pairs && lane < 8) {
+            p.cost[b * 8 + lane] = 0.0;
+            p.row[b * 8 + lane] = -1;
+            p.col[b * 8 + lane] = -1;
+        }
+        if (lane == 0) p.pairs[b] = pairs;
+    }
+}
+
 }  // namespace seld
 
 using namespace seld;
 
-extern "C" int seld_event_metrics_accumulate(const double* pred_rows, const int64_t* pred_offsets, int64_t pred_count,
-                                             const double* true_rows, const int64_t* true_offsets, int64_t true_count,
-                                             int64_t recordings, int32_t n_frames, int32_t nb_classes, int32_t frames_per_block,
-                                             double spatial_threshold, double doa_threshold, int64_t* counters,
-                                             double* total_de, int64_t* flags, void* stream) {
+extern "C" int seld_event_metrics_accumulate_ex(const double* pred_rows, const int64_t* pred_offsets, int64_t pred_count,
+                                                const double* true_rows, const int64_t* true_offsets, int64_t true_count,
+                                                int64_t recordings, int32_t n_frames, int32_t nb_classes,
+                                                int32_t frames_per_block, int32_t coords, int32_t max_tracks,
+                                                double spatial_threshold, double doa_threshold, int64_t* counters,
+                                                double* total_de, int64_t* flags, void* stream) {
+    if ((coords != 2 && coords != 3) || max_tracks < 1 || max_tracks > EV_WIDE) return SELD_EINVAL;
     if (recordings < 0 || pred_count < 0 || true_count < 0 || n_frames < 0 || !counters || !total_de || !flags) return SELD_EINVAL;
     if (nb_classes < 0 || nb_classes > 64 || frames_per_block < 1) return SELD_EINVAL;
-    if (pred_count > 0x0fffffff || true_count > 0x0fffffff) return SELD_EUNSUPPORTED;    // 5 * row index stays an int inside a unit
+    if (pred_count > 0x0fffffff || true_count > 0x0fffffff) return SELD_EUNSUPPORTED;    // stride * row index stays an int inside a unit
     if ((pred_count && (!pred_rows || !pred_offsets)) || (true_count && (!true_rows || !true_offsets))) return SELD_EINVAL;
     const hipError_t e = hipMemsetAsync(flags, 0, 2 * sizeof(int64_t), (hipStream_t)stream);
     if (e != hipSuccess) {
@@ -278,6 +397,7 @@ extern "C" int seld_event_metrics_accumulate(const double* pred_rows, const int6
     p.n_frames = n_frames;
     p.classes = nb_classes;
     p.fpb = frames_per_block;
+    p.max_tracks = max_tracks;
     p.spatial_threshold = spatial_threshold;
     p.doa_threshold = doa_threshold;
     p.counters = reinterpret_cast<long long*>(counters);
@@ -287,12 +407,51 @@ extern "C" int seld_event_metrics_accumulate(const double* pred_rows, const int6
     if (rows == 0) return SELD_OK;                      // nothing to check, and every unit is empty
     long long wgs = (rows + 255) / 256;
     if (wgs > 2048) wgs = 2048;
-    hipLaunchKernelGGL(event_check_kernel, dim3((unsigned)wgs), dim3(256), 0, (hipStream_t)stream, p);
+    if (coords == 3) hipLaunchKernelGGL(event_check_kernel<3>, dim3((unsigned)wgs), dim3(256), 0, (hipStream_t)stream, p);
+    else hipLaunchKernelGGL(event_check_kernel<2>, dim3((unsigned)wgs), dim3(256), 0, (hipStream_t)stream, p);
     const int rc = check_launch();
     if (rc != SELD_OK) return rc;
     const long long total = recordings * p.blocks;
     if (total == 0) return SELD_OK;
     wgs = total > 4096 ? 4096 : total;                  // 2 generations of resident waves; waves loop over their units
-    hipLaunchKernelGGL(event_metrics_kernel, dim3((unsigned)wgs), dim3(64), 0, (hipStream_t)stream, p);
+    const bool wide = max_tracks > 3;                   // up to 3 x 3 keeps the lane-per-class kernel as it was
+    const dim3 grid((unsigned)wgs), block(64);
+    if (coords == 3 && !wide) hipLaunchKernelGGL((event_metrics_kernel<3, false>), grid, block, 0, (hipStream_t)stream, p);
+    else if (coords == 3) hipLaunchKernelGGL((event_metrics_kernel<3, true>), grid, block, 0, (hipStream_t)stream, p);
+    else if (!wide) hipLaunchKernelGGL((event_metrics_kernel<2, false>), grid, block, 0, (hipStream_t)stream, p);
+    else hipLaunchKernelGGL((event_metrics_kernel<2, true>), grid, block, 0, (hipStream_t)stream, p);
+    return check_launch();
+}
+
+extern "C" int seld_event_metrics_accumulate(const double* pred_rows, const int64_t* pred_offsets, int64_t pred_count,
+                                             const double* true_rows, const int64_t* true_offsets, int64_t true_count,
+                                             int64_t recordings, int32_t n_frames, int32_t nb_classes, int32_t frames_per_block,
+                                             double spatial_threshold, double doa_threshold, int64_t* counters,
+                                             double* total_de, int64_t* flags, void* stream) {
+    return seld_event_metrics_accumulate_ex(pred_rows, pred_offsets, pred_count, true_rows, true_offsets, true_count, recordings,
+                                            n_frames, nb_classes, frames_per_block, 3, SELD_EVENT_METRICS_MAX_TRACKS,
+                                            spatial_threshold, doa_threshold, counters, total_de, flags, stream);
+}
+
+extern "C" int seld_least_distance(const double* gt, const int32_t* gt_counts, const double* pred, const int32_t* pred_counts,
+                                   int64_t problems, int32_t coords, double* cost, int32_t* row, int32_t* col, int32_t* pairs,
+                                   void* stream) {
+    if (problems < 0 || (coords != 2 && coords != 3)) return SELD_EINVAL;
+    if (problems > 0x0fffffff) return SELD_EUNSUPPORTED;                                 // 8 * coords * problem index stays small
+    if (problems == 0) return SELD_OK;
+    if (!gt || !gt_counts || !pred || !pred_counts || !cost || !row || !col || !pairs) return SELD_EINVAL;
+    AssignP p;
+    p.gt = gt;
+    p.pred = pred;
+    p.gt_n = gt_counts;
+    p.pred_n = pred_counts;
+    p.problems = problems;
+    p.cost = cost;
+    p.row = row;
+    p.col = col;
+    p.pairs = pairs;
+    const dim3 grid((unsigned)(problems > 4096 ? 4096 : problems)), block(64);
+    if (coords == 3) hipLaunchKernelGGL(least_distance_kernel<3>, grid, block, 0, (hipStream_t)stream, p);
+    else hipLaunchKernelGGL(least_distance_kernel<2>, grid, block, 0, (hipStream_t)stream, p);
     return check_launch();
 }

@@ -16,6 +16,27 @@ __device__ __forceinline__ double angular_distance_deg(const double a[3], const 
     return acos(d) * 180.0 / 3.141592653589793;
 }
 
+// Dcase21_metrics.py:157-168 on {azimuth, elevation} in radians, operation by operation
+__device__ __forceinline__ double spherical_distance_deg(const double a[2], const double b[2]) {
+#pragma clang fp contract(off)
+    double d = sin(a[1]) * sin(b[1]) + (cos(a[1]) * cos(b[1])) * cos(fabs(a[0] - b[0]));
+    d = fmin(fmax(d, -1.0), 1.0);
+    return acos(d) * 180.0 / 3.141592653589793;
+}
+
+// The distance of the reference's least_distance_between_gt_pred for DOAs of COORDS entries: 3 Cartesian, 2 spherical
+template <int COORDS>
+__device__ __forceinline__ double doa_distance_deg(const double* a, const double* b) {
+    if constexpr (COORDS == 3) return angular_distance_deg(a, b);
+    else return spherical_distance_deg(a, b);
+}
+
+// Dcase21_metrics.py:91-93: degrees to radians as `v * np.pi / 180.`
+__device__ __forceinline__ double deg_to_rad(double v) {
+#pragma clang fp contract(off)
+    return v * 3.141592653589793 / 180.0;
+}
+
 __device__ __forceinline__ unsigned long long readlane_u64(unsigned long long v, int src_lane) {
     const unsigned lo = __builtin_amdgcn_readlane((unsigned)v, src_lane);
     const unsigned hi = __builtin_amdgcn_readlane((unsigned)(v >> 32), src_lane);
@@ -95,6 +116,59 @@ __device__ __forceinline__ void assign_3x3(unsigned g_bits, unsigned p_bits, con
     }
 }
 
+// The association of g <= 8 reference with q <= 8 predicted DOAs by the whole wave of a ONE-WAVE workgroup (it uses the
+// workgroup barrier).  Lane 8 i + j brings cost[i][j] (anything where i >= g or j >= q: it is replaced by 0); g and q
+// are wave-uniform and either may be 0.  h (256 doubles) and cs (64 doubles) are LDS.  Returns, in lane r < 8,
+// the column of row r: row r is matched when r < g and the column is below q.
+//
+// The problem is padded with zero-cost rows or columns to n x n, n = max(g, q): a perfect matching of the padded matrix
+// costs what its min(g, q) real pairs cost.  h[mask] = the cheapest way to give rows n - popc(mask) .. n - 1 the columns
+// of mask, filled layer by layer of popc(mask), four masks a lane; then rows 0, 1, ... each take the LOWEST column that
+// keeps the optimum (cs[r][j] + h[mask ^ j] == h[mask], the very expression that produced h[mask]).  That is the first
+// row -> column map in lexicographic order among the cheapest, an unmatched row counting as a column above every real
+// one: assign_3x3's rule.  Sums are taken from the last row backwards.  No register array is indexed at run time.
+__device__ __forceinline__ int assign_wave_8x8(int g, int q, double c, int lane, double* h, double* cs) {
+#pragma clang fp contract(off)
+    const int n = max(g, q);
+    const unsigned full = (1u << n) - 1u;
+    cs[lane] = ((lane >> 3) < g && (lane & 7) < q) ? c : 0.0;
+    if (lane == 0) h[0] = 0.0;
+    __syncthreads();
+    for (int k = 1; k <= n; ++k) {
+        const int r = n - k;
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            const unsigned m = (unsigned)lane + 64u * t;
+            if (m > full || __popc(m) != k) continue;
+            double best = __builtin_inf();
+            for (unsigned rest = m; rest; rest &= rest - 1u) {
+                const int j = __ffs(rest) - 1;
+                const double v = cs[r * 8 + j] + h[m ^ (1u << j)];
+                best = v < best ? v : best;
+            }
+            h[m] = best;
+        }
+        __syncthreads();
+    }
+    unsigned m = full;
+    int mine = 8;
+    for (int r = 0; r < n; ++r) {
+        const double want = h[m];
+        int pick = __ffs(m) - 1;                        // (only a NaN cost leaves the search below empty-handed)
+        for (unsigned rest = m; rest; rest &= rest - 1u) {
+            const int j = __ffs(rest) - 1;
+            if (cs[r * 8 + j] + h[m ^ (1u << j)] == want) {
+                pick = j;
+                break;
+            }
+        }
+        mine = lane == r ? pick : mine;
+        m ^= 1u << pick;
+    }
+    __syncthreads();                                    // h and cs are rewritten by the next problem
+    return mine;
+}
+
 // What one class of one block adds to the DCASE21 counters (Dcase21_metrics.py:65-149).  fp and fn are also the class's
 // share of the block's loc_FP and loc_FN, which the reference raises wherever it raises _FP and _FN.
 struct DcaseAdd {
@@ -102,22 +176,26 @@ struct DcaseAdd {
 };
 
 // nb_gt / nb_pred: the longest reference / predicted list of a frame of the block; s / n: the sum and the count of the
-// matched distances of reference track 0 / 1 / 2 over the block's frames.  The tracks' averages are added to total_de.
-__device__ __forceinline__ DcaseAdd dcase_class_block(int nb_gt, int nb_pred, double s0, double s1, double s2, int n0, int n1,
-                                                      int n2, double doa_threshold, double& total_de) {
+// matched distances of reference track 0 .. N - 1 over the block's frames.  The tracks' averages are added to total_de
+// in track order.
+template <int N>
+__device__ __forceinline__ DcaseAdd dcase_class_block_n(int nb_gt, int nb_pred, const double (&s)[N], const int (&n)[N],
+                                                        double doa_threshold, double& total_de) {
     DcaseAdd a = {0, 0, 0, nb_gt, 0, 0, 0};
     if (nb_gt && nb_pred) {
-        if (n0 + n1 + n2 == 0) {
+        int matched = 0;
+#pragma unroll
+        for (int r = 0; r < N; ++r) matched += n[r];
+        if (matched == 0) {
             a.fn += nb_pred;
             a.de_fn += nb_pred;
         } else {
             // (the reference adds the tracks' averages in order of first appearance; the order only moves the last
             //  bit of _total_DE, which the cross-block atomics reorder anyway)
 #pragma unroll
-            for (int r = 0; r < 3; ++r) {
-                const int tn = r == 0 ? n0 : r == 1 ? n1 : n2;
-                if (tn == 0) continue;
-                const double avg = (r == 0 ? s0 : r == 1 ? s1 : s2) / (double)tn;
+            for (int r = 0; r < N; ++r) {
+                if (n[r] == 0) continue;
+                const double avg = s[r] / (double)n[r];
                 total_de += avg;
                 a.de_tp += 1;
                 if (avg <= doa_threshold) a.tp += 1; else a.fp += 1;
@@ -138,6 +216,13 @@ __device__ __forceinline__ DcaseAdd dcase_class_block(int nb_gt, int nb_pred, do
         a.de_fp += nb_pred;
     }
     return a;
+}
+
+__device__ __forceinline__ DcaseAdd dcase_class_block(int nb_gt, int nb_pred, double s0, double s1, double s2, int n0, int n1,
+                                                      int n2, double doa_threshold, double& total_de) {
+    const double s[3] = {s0, s1, s2};
+    const int n[3] = {n0, n1, n2};
+    return dcase_class_block_n<3>(nb_gt, nb_pred, s, n, doa_threshold, total_de);
 }
 
 // cnt: the counters in METRIC_COUNTERS order
