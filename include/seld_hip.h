@@ -975,7 +975,7 @@ int seld_segment(const void* src, int32_t dtype, int32_t layout, int64_t rows, i
 
 /* ------------------------------------------------------------------------------------------
  * Device-resident epoch loader (csrc/loader.hip): what a training step needs from a DataLoader over resident arrays,
- * as two launches that can be recorded in a HIP graph.  Neither allocates nor synchronises.
+ * as two launches that can be recorded in a HIP graph.  None of the entry points allocates or synchronises.
  *
  * seld_gather_rows fetches one minibatch.  For b in [0, count):
  *     p = (cursor ? cursor[0] * cursor_stride : 0) + start + b
@@ -990,6 +990,42 @@ int seld_segment(const void* src, int32_t dtype, int32_t layout, int64_t rows, i
  *   and behind that part, and for a row whose two sides are aligned differently.
  *   SELD_EINVAL: index NULL, neither pair given, half a pair, a non-positive n_index / n_rows / row length / B / count,
  *   count > B, count > 65535, a negative cursor_stride.  Nothing is launched on refusal.
+ * seld_gather_rows_aug is seld_gather_rows with a per-sample augmentation applied on the way: a signed permutation of
+ * the predictor channels together with the matching transform of the DOA labels, and frequency / time masks.  Same
+ * addressing, same bytes moved, one launch, recordable.  A position or index out of range ZERO-FILLS its rows and
+ * nothing else is applied to them; output rows [count, B) are not touched.
+ *   Geometry: a predictor row is (C, F, T), row_x = C * F * T, C <= 16; a target row is (T_out, y_cols) with
+ *   y_cols = 4 * n_sed = [n_sed activity | n_sed * 3 location], the location of slot s and axis a at column
+ *   n_sed + 3 * s + a (what seld_encode_events writes); row_y is a multiple of y_cols.
+ *   epoch: ONE int32 on the device, read by the kernel (a recorded launch sees a new epoch at replay).
+ *   table: K rows of 2 * C + 6 int32 on the device, 0 <= K <= 64, a row = src[C], flip[C], axis[3], sign[3]:
+ *   src[c] in [0, C), flip[c] in {0, 1, 2}, axis a permutation of 0..2, sign +-1.  K == 0 with table NULL: no channel
+ *   transform.  The CONTENT of the table is validated by the caller (hip_ops.Augment, before upload); the entry point
+ *   checks sizes only, and the kernel reads nothing outside a row whatever the table holds (a src outside [0, C) is
+ *   taken as c, an axis outside 0..2 as a, flip is taken mod 4 with 3 as 0).
+ *   Random numbers: w = philox4x32_10(counter, key) as seld_dropout_fwd uses it (counter = (low, high, 0, 0), key =
+ *   (low, high) of the 64-bit values), words w[0..3] in the order (c0, c1, c2, c3);
+ *       key = seed        counter = (uint64)epoch << 34 | (uint64)p << 2 | g        (mod 2^64)
+ *   for the sample at position p and the group g in {0, 1, 2}; int(w, n) = ((uint64)w * n) >> 32 is an integer in
+ *   [0, n); coin(w) = u01(w) < p_swap in fp32, u01(w) = (float)(w >> 8) * 2^-24.  The draws are functions of (seed,
+ *   epoch, p) alone: not of B, count, the cursor-against-start form of the call, or the grid.  The dropout stream is
+ *   not touched.
+ *   g = 0, channel transform: applied iff K > 0 and coin(w[1]); k = int(w[0], K); with the row k of the table
+ *       x'[c, f, t] = flipop(flip[c], x[src[c], f, t])
+ *       flipop(0, v) = v;  flipop(1, v) = -v;  flipop(2, v) = v <= 0 ? v + PI_F : v - PI_F, PI_F = (float)M_PI, one fp32
+ *       addition: a raw phase in (-pi, pi] turned by pi, staying in that interval
+ *       location'(s, a) = (float)sign[a] * location(s, axis[a]);  activity copied
+ *   g = 1, frequency masks: for m < n_fmask, width = int(w[2m], f_max + 1), first = int(w[2m + 1], F - width + 1),
+ *       x'[:, first : first + width, :] = fill
+ *   g = 2, time masks: the same over T with n_tmask, t_max: x'[:, :, first : first + width] = fill
+ *   Masks come after the channel transform and cover every channel; targets are not masked.
+ *   16-byte loads and stores when T % 4 == 0 and x_all and out_x are 16-byte aligned (a float4 then lies in one
+ *   (c, f) row), single floats otherwise; targets whose sample draws no transform move as in seld_gather_rows.
+ *   SELD_EINVAL: whatever seld_gather_rows refuses; n_index > 2^32; epoch NULL; K outside [0, 64]; table NULL with
+ *   K > 0 or given with K == 0; C outside [1, 16]; F or T < 1 (checked with or without the x pair); row_x != C * F * T;
+ *   y_cols < 4, no multiple of 4 or no divisor of row_y (with the y pair); p_swap outside [0, 1]; n_fmask or n_tmask
+ *   outside {0, 1, 2}; f_max outside [0, F]; t_max outside [0, T].  SELD_EUNSUPPORTED: a row of 2^31 floats or more.
+ *   Nothing is launched on refusal.
  * seld_epoch_step_end, one thread, as the last launch of a step:
  *     mean[0] += (loss[0] - mean[0]) / (float)(cursor[0] + 1);   cursor[0] += 1          (fp32: the epoch loop's
  *   running mean of the loss, train.py:559, in the form train.main takes it)
@@ -999,6 +1035,11 @@ int seld_segment(const void* src, int32_t dtype, int32_t layout, int64_t rows, i
 int seld_gather_rows(const float* x_all, int64_t row_x, float* out_x, const float* y_all, int64_t row_y, float* out_y,
                      const int64_t* index, int64_t n_index, int64_t n_rows, const int32_t* cursor, int64_t cursor_stride,
                      int64_t start, int32_t B, int32_t count, void* stream);
+int seld_gather_rows_aug(const float* x_all, int64_t row_x, float* out_x, const float* y_all, int64_t row_y, float* out_y,
+                         const int64_t* index, int64_t n_index, int64_t n_rows, const int32_t* cursor, int64_t cursor_stride,
+                         int64_t start, int32_t B, int32_t count, int32_t C, int32_t F, int32_t T, int32_t y_cols,
+                         const int32_t* epoch, uint64_t seed, const int32_t* table, int32_t K, float p_swap, int32_t n_fmask,
+                         int32_t f_max, int32_t n_tmask, int32_t t_max, float fill, void* stream);
 int seld_epoch_step_end(const float* loss, float* mean, int32_t* cursor, void* stream);
 
 #ifdef __cplusplus

@@ -3,12 +3,20 @@
 // at every replay (train.ResidentLoader, train.GraphedTrainStep).
 //
 //   seld_gather_rows      out[b, :] = all[index[cursor * stride + start + b], :] for the predictors and the targets
+//   seld_gather_rows_aug  the same gather with the per-sample augmentation applied on the way: a signed channel
+//                         permutation with the matching transform of the DOA labels, frequency and time masks
 //   seld_epoch_step_end   running mean of the loss, cursor += 1 (the last launch of a step)
 //
 // The gather is an HBM-bound copy (config 3: 2 MB per predictor row, 67 MB per batch): a row is spread over many
 // workgroups in tiles of 16 KB (256 lanes x 4 x 16 bytes, all four loads issued before the first store), the grid is
 // capped near 2048 workgroups and strides over the tiles beyond that.  The loads of `cursor` and `index` depend on the
 // workgroup's coordinates only: the compiler keeps them on the scalar unit.  No LDS.
+//
+// The augmented gather moves the same bytes.  What a sample draws (Philox words of its (seed, epoch, position)) and the
+// row of the transform table it picks depend on blockIdx.y only, so they are computed once per workgroup on the scalar
+// unit: the channel map packed 4 bits per channel, the flips 2 bits per channel, the mask bounds as four ranges.  A
+// lane then needs (c, f, t) of its output offset (two unsigned divisions by uniform divisors per 16 bytes), a shift
+// for its source channel and a few compares; with T % 4 == 0 a float4 never crosses a (c, f) row.
 #include "common.h"
 
 namespace seld {
@@ -77,6 +85,209 @@ __global__ __launch_bounds__(GATHER_THREADS) void gather_rows_kernel(GatherSide 
     }
 }
 
+// ---- augmented gather ------------------------------------------------------------------------------------------------
+constexpr int AUG_MAX_C = 16, AUG_MAX_K = 64;
+constexpr float PI_F = (float)M_PI;
+
+struct AugParams {
+    int C, F, T;                // predictor row = (C, F, T)
+    int n_sed;                  // target row = (T_out, [n_sed activity | n_sed * 3 location])
+    uint64_t seed;
+    int K;                      // rows of the table (K, 2 * C + 6): src[C], flip[C], axis[3], sign[3]
+    float p_swap;
+    int n_fmask, f_max, n_tmask, t_max;
+    float fill;
+    int vec;                    // T % 4 == 0 and both predictor arrays 16-byte aligned
+};
+
+__device__ __forceinline__ uint32_t int_below(uint32_t w, uint32_t n) { return (uint32_t)(((uint64_t)w * n) >> 32); }
+
+// up to two masks over an axis of `size` from the four words of one Philox group: [lo[m], lo[m] + width[m])
+struct MaskPair {
+    uint32_t lo[2], width[2];
+    __device__ __forceinline__ bool hit(uint32_t i) const { return (i - lo[0] < width[0]) | (i - lo[1] < width[1]); }
+};
+__device__ __forceinline__ MaskPair draw_masks(uint64_t counter, uint64_t seed, int n, int max_width, int size) {
+    MaskPair m{{0u, 0u}, {0u, 0u}};
+    if (n > 0) {
+        const uint4 w = philox4x32_10(counter, seed);
+        m.width[0] = int_below(w.x, (uint32_t)max_width + 1u);
+        m.lo[0] = int_below(w.y, (uint32_t)size - m.width[0] + 1u);
+        if (n > 1) {
+            m.width[1] = int_below(w.z, (uint32_t)max_width + 1u);
+            m.lo[1] = int_below(w.w, (uint32_t)size - m.width[1] + 1u);
+        }
+    }
+    return m;
+}
+
+__device__ __forceinline__ float aug_flip(float v, uint32_t flip) {
+    const float turned = v <= 0.f ? v + PI_F : v - PI_F;        // selects, no branches: the flip differs between lanes
+    return flip == 1u ? -v : flip == 2u ? turned : v;
+}
+
+// what a workgroup needs of its sample's draws to place one predictor element
+struct AugX {
+    uint64_t src;           // 4 bits per output channel
+    uint32_t flip;          // 2 bits per output channel
+    MaskPair fm, tm;
+    uint32_t F, T, FT;
+    float fill;
+};
+
+// one predictor element at output offset o of the row
+__device__ __forceinline__ float aug_x_element(const float* __restrict__ s, uint32_t o, const AugX& a) {
+    const uint32_t q = o / a.T, t = o - q * a.T, c = q / a.F, f = q - c * a.F;
+    if (a.fm.hit(f) || a.tm.hit(t)) return a.fill;
+    const uint32_t sc = (uint32_t)(a.src >> (4u * c)) & 15u;
+    return aug_flip(s[o - c * a.FT + sc * a.FT], (a.flip >> (2u * c)) & 3u);
+}
+
+// `len` <= GATHER_TILE floats (a multiple of 4) at row offset `off` (a multiple of 4), rows 16-byte aligned, T % 4 == 0:
+// the four floats of an access share (c, f).  All loads of the tile are issued before its first store.
+__device__ __forceinline__ void aug_x_tile_vec(const float* __restrict__ s, float* __restrict__ d, uint32_t off, int len,
+                                               const AugX& a) {
+    const int tid = threadIdx.x, nv = len >> 2;
+    float4 v[GATHER_VEC];
+    uint32_t t0[GATHER_VEC], flip[GATHER_VEC];
+    bool whole[GATHER_VEC];
+#pragma unroll
+    for (int k = 0; k < GATHER_VEC; ++k) {
+        const int i = tid + k * GATHER_THREADS;
+        const uint32_t o = off + 4u * (uint32_t)(i < nv ? i : 0);       // a lane past the tile: any offset inside the row
+        const uint32_t q = o / a.T, c = q / a.F, f = q - c * a.F;
+        t0[k] = o - q * a.T;
+        flip[k] = (a.flip >> (2u * c)) & 3u;
+        whole[k] = a.fm.hit(f);
+        const uint32_t sc = (uint32_t)(a.src >> (4u * c)) & 15u;
+        v[k] = (i < nv && !whole[k]) ? *reinterpret_cast<const float4*>(s + (o - c * a.FT + sc * a.FT))
+                                     : make_float4(a.fill, a.fill, a.fill, a.fill);
+    }
+#pragma unroll
+    for (int k = 0; k < GATHER_VEC; ++k) {
+        const int i = tid + k * GATHER_THREADS;
+        if (i >= nv) continue;
+        float4 r;
+        r.x = (whole[k] | a.tm.hit(t0[k])) ? a.fill : aug_flip(v[k].x, flip[k]);
+        r.y = (whole[k] | a.tm.hit(t0[k] + 1u)) ? a.fill : aug_flip(v[k].y, flip[k]);
+        r.z = (whole[k] | a.tm.hit(t0[k] + 2u)) ? a.fill : aug_flip(v[k].z, flip[k]);
+        r.w = (whole[k] | a.tm.hit(t0[k] + 3u)) ? a.fill : aug_flip(v[k].w, flip[k]);
+        *reinterpret_cast<float4*>(d + off + 4u * (uint32_t)i) = r;
+    }
+}
+
+// grid (gx + gy, count) as gather_rows_kernel.  Everything up to the tile loops is uniform over the workgroup; `epoch`
+// and `table` are arguments of their own (not members of AugParams) so that they carry __restrict__ and their loads
+// stay on the scalar unit.
+// 8 waves per SIMD as gather_rows_kernel has them (the second bound keeps the scalar registers of the draws under the limit).
+__global__ __launch_bounds__(GATHER_THREADS, 8) void gather_rows_aug_kernel(GatherSide x, GatherSide y, int gx,
+                                                                         const int64_t* __restrict__ index, long long n_index,
+                                                                         long long n_rows, const int32_t* __restrict__ cursor,
+                                                                         long long stride, long long start,
+                                                                         const int32_t* __restrict__ epoch,
+                                                                         const int32_t* __restrict__ table, AugParams a) {
+    const int b = blockIdx.y, tid = threadIdx.x;
+    const bool is_y = (int)blockIdx.x >= gx;
+    const GatherSide sd = is_y ? y : x;
+    const int first = is_y ? (int)blockIdx.x - gx : (int)blockIdx.x;
+    const int step = is_y ? (int)gridDim.x - gx : gx;
+    const long long p = start + b + (cursor ? (long long)cursor[0] * stride : 0);
+    long long r = -1;
+    if (p >= 0 && p < n_index) r = index[p];
+    const bool valid = r >= 0 && r < n_rows;
+    float* __restrict__ dst = sd.out + (long long)b * sd.row;
+    const float* __restrict__ src = valid ? sd.all + r * sd.row : dst;
+    const uint32_t row = (uint32_t)sd.row, first_off = (uint32_t)first * (uint32_t)GATHER_TILE;     // rows are below 2^31 floats
+    const uint64_t tile_step = (uint64_t)step * (uint64_t)GATHER_TILE;
+
+    // the draws of this sample: functions of (seed, epoch, p) alone
+    uint64_t counter = 0;
+    bool swap = false;
+    const int32_t* __restrict__ trow = table;
+    if (valid) {
+        counter = ((uint64_t)(uint32_t)epoch[0] << 34) | ((uint64_t)p << 2);
+        if (a.K > 0) {
+            const uint4 w = philox4x32_10(counter, a.seed);
+            swap = u01(w.y) < a.p_swap;
+            trow += (long long)int_below(w.x, (uint32_t)a.K) * (2 * a.C + 6);
+        }
+    }
+
+    // every load of the table comes before the first store of the kernel: the compiler then proves them unclobbered and
+    // issues scalar loads.  Unrolled with clamped indices, so that they go out together.
+    uint64_t src_map = 0xFEDCBA9876543210ull;
+    uint32_t flip_map = 0u;
+    int ax0 = 0, ax1 = 1, ax2 = 2;
+    float sg0 = 1.f, sg1 = 1.f, sg2 = 1.f;
+    if (swap && is_y) {
+        // the binding validates the table; an axis outside 0..2 still reads nothing outside its own triple
+        const int32_t* __restrict__ la = trow + 2 * a.C;
+        ax0 = (uint32_t)la[0] < 3u ? la[0] : 0, ax1 = (uint32_t)la[1] < 3u ? la[1] : 1, ax2 = (uint32_t)la[2] < 3u ? la[2] : 2;
+        sg0 = (float)la[3], sg1 = (float)la[4], sg2 = (float)la[5];
+    } else if (swap) {
+        uint32_t from[AUG_MAX_C], turn[AUG_MAX_C];
+#pragma unroll
+        for (int c = 0; c < AUG_MAX_C; ++c) {
+            const int cc = c < a.C ? c : 0;
+            from[c] = (uint32_t)trow[cc];
+            turn[c] = (uint32_t)trow[a.C + cc];
+        }
+        src_map = 0ull;
+#pragma unroll
+        for (int c = 0; c < AUG_MAX_C; ++c) {                                       // a source outside [0, C): the channel itself
+            src_map |= (uint64_t)(from[c] < (uint32_t)a.C ? from[c] : (uint32_t)(c < a.C ? c : 0)) << (4 * c);
+            flip_map |= (turn[c] & 3u) << (2 * c);
+        }
+    }
+
+    if (!valid || (is_y && !swap)) {            // zero-fill, or targets that no transform touches: the plain tiles
+        for (uint64_t off = first_off; off < row; off += tile_step) {
+            const uint32_t left = row - (uint32_t)off;
+            gather_tile(src + off, dst + off, (int)(left < GATHER_TILE ? left : GATHER_TILE), valid);
+        }
+        return;
+    }
+
+    if (is_y) {                                 // location (s, axis) <- sign[axis] * location (s, axis[axis]); activity copied
+        const uint32_t n_sed = (uint32_t)a.n_sed, cols = 4u * n_sed;
+        for (uint64_t off = first_off; off < row; off += tile_step) {
+            const uint32_t left = row - (uint32_t)off, len = left < GATHER_TILE ? left : (uint32_t)GATHER_TILE;
+            for (uint32_t i = tid; i < len; i += GATHER_THREADS) {
+                const uint32_t o = (uint32_t)off + i, j = o % cols;
+                float v;
+                if (j < n_sed) {
+                    v = src[o];
+                } else {
+                    const uint32_t ax = (j - n_sed) % 3u;
+                    const int from = ax == 0u ? ax0 : ax == 1u ? ax1 : ax2;
+                    const float sg = ax == 0u ? sg0 : ax == 1u ? sg1 : sg2;
+                    v = sg * src[o - ax + (uint32_t)from];
+                }
+                dst[o] = v;
+            }
+        }
+        return;
+    }
+
+    AugX ax;
+    ax.src = src_map;
+    ax.flip = flip_map;
+    ax.fm = draw_masks(counter | 1u, a.seed, a.n_fmask, a.f_max, a.F);
+    ax.tm = draw_masks(counter | 2u, a.seed, a.n_tmask, a.t_max, a.T);
+    ax.F = (uint32_t)a.F;
+    ax.T = (uint32_t)a.T;
+    ax.FT = ax.F * ax.T;
+    ax.fill = a.fill;
+    for (uint64_t off = first_off; off < row; off += tile_step) {
+        const uint32_t left = row - (uint32_t)off, len = left < GATHER_TILE ? left : (uint32_t)GATHER_TILE;
+        if (a.vec) {
+            aug_x_tile_vec(src, dst, (uint32_t)off, (int)len, ax);
+        } else {
+            for (uint32_t i = tid; i < len; i += GATHER_THREADS) dst[(uint32_t)off + i] = aug_x_element(src, (uint32_t)off + i, ax);
+        }
+    }
+}
+
 // one thread: the epoch loop's running mean (train.main), `mean += (loss - mean) / (i + 1)` in fp32 with i the cursor,
 // then the cursor
 __global__ void epoch_step_end_kernel(const float* __restrict__ loss, float* __restrict__ mean, int32_t* __restrict__ cursor) {
@@ -107,6 +318,37 @@ extern "C" int seld_gather_rows(const float* x_all, int64_t row_x, float* out_x,
     const GatherSide x{x_all, out_x, has_x ? (long long)row_x : 0}, y{y_all, out_y, has_y ? (long long)row_y : 0};
     hipLaunchKernelGGL(gather_rows_kernel, dim3(gx + gy, count), dim3(GATHER_THREADS), 0, (hipStream_t)stream, x, y, gx, index,
                        (long long)n_index, (long long)n_rows, cursor, (long long)cursor_stride, (long long)start);
+    return check_launch();
+}
+
+extern "C" int seld_gather_rows_aug(const float* x_all, int64_t row_x, float* out_x, const float* y_all, int64_t row_y,
+                                    float* out_y, const int64_t* index, int64_t n_index, int64_t n_rows, const int32_t* cursor,
+                                    int64_t cursor_stride, int64_t start, int32_t B, int32_t count, int32_t C, int32_t F,
+                                    int32_t T, int32_t y_cols, const int32_t* epoch, uint64_t seed, const int32_t* table,
+                                    int32_t K, float p_swap, int32_t n_fmask, int32_t f_max, int32_t n_tmask, int32_t t_max,
+                                    float fill, void* stream) {
+    const bool has_x = x_all || out_x, has_y = y_all || out_y;
+    if (!index || n_index <= 0 || n_index > (1ll << 32) || n_rows <= 0 || B <= 0 || count <= 0 || count > B || count > 65535)
+        return SELD_EINVAL;
+    if (!has_x && !has_y) return SELD_EINVAL;
+    if (has_x && (!x_all || !out_x || row_x <= 0)) return SELD_EINVAL;
+    if (has_y && (!y_all || !out_y || row_y <= 0)) return SELD_EINVAL;
+    if (cursor && cursor_stride < 0) return SELD_EINVAL;
+    if (!epoch || K < 0 || K > AUG_MAX_K || (K > 0) != (table != nullptr)) return SELD_EINVAL;
+    if (!(p_swap >= 0.f && p_swap <= 1.f)) return SELD_EINVAL;                      // a NaN fails both
+    if (C < 1 || C > AUG_MAX_C || F < 1 || T < 1) return SELD_EINVAL;
+    if (n_fmask < 0 || n_fmask > 2 || n_tmask < 0 || n_tmask > 2 || f_max < 0 || f_max > F || t_max < 0 || t_max > T) return SELD_EINVAL;
+    if (has_x && (long long)C * F * T != row_x) return SELD_EINVAL;                 // 16 * 2^31 * 2^31 fits an int64
+    if (has_y && (y_cols < 4 || y_cols % 4 || row_y % y_cols)) return SELD_EINVAL;
+    if (row_x >= (1ll << 31) || row_y >= (1ll << 31)) return SELD_EUNSUPPORTED;     // offsets inside a row are 32-bit
+    const long long cap = GATHER_MAX_BLOCKS / count > 0 ? GATHER_MAX_BLOCKS / count : 1;
+    const long long tx = has_x ? (row_x + GATHER_TILE - 1) / GATHER_TILE : 0, ty = has_y ? (row_y + GATHER_TILE - 1) / GATHER_TILE : 0;
+    const int gx = (int)(tx < cap ? tx : cap), gy = (int)(ty < cap ? ty : cap);
+    const GatherSide x{x_all, out_x, has_x ? (long long)row_x : 0}, y{y_all, out_y, has_y ? (long long)row_y : 0};
+    const int vec = has_x && T % 4 == 0 && (((uintptr_t)x_all | (uintptr_t)out_x) & 15) == 0;
+    const AugParams a{C, F, T, has_y ? y_cols / 4 : 0, seed, K, p_swap, n_fmask, f_max, n_tmask, t_max, fill, vec};
+    hipLaunchKernelGGL(gather_rows_aug_kernel, dim3(gx + gy, count), dim3(GATHER_THREADS), 0, (hipStream_t)stream, x, y, gx, index,
+                       (long long)n_index, (long long)n_rows, cursor, (long long)cursor_stride, (long long)start, epoch, table, a);
     return check_launch();
 }
 

@@ -417,9 +417,15 @@ _EVAL = ('use_cuda', 'early_stopping', 'fixed_seed', 'pool_size', 'cnn_filters',
          'resident_loader', 'graph_step')
 # extensions of this implementation (not in the reference): synthetic data so the step can run without L3DAS21;
 # resident_loader: minibatches gathered on the device (ResidentLoader) instead of a DataLoader over the resident arrays;
-# graph_step (needs resident_loader): full batches run as replays of one recorded step (GraphedTrainStep)
+# graph_step (needs resident_loader): full batches run as replays of one recorded step (GraphedTrainStep);
+# augment_* (need resident_loader; training loader only; all off by default): augmentation inside the gather launch
+# (hip_ops.gather_rows_aug) -- augment_swap: probability of a signed FOA channel permutation with its DOA labels
+# (hip_ops.foa_transforms for --n_mics / --phase); augment_freq_masks / augment_time_masks: 0..2 masks per sample of a
+# width up to augment_freq_width / augment_time_width bins; augment_seed: the key of the draws
 _EXTRA = [('synthetic', int, 0), ('max_steps', int, 0), ('epochs', int, 0), ('resident_loader', str, 'False'),
-          ('graph_step', str, 'False')]
+          ('graph_step', str, 'False'), ('augment_swap', float, 0.), ('augment_freq_masks', int, 0),
+          ('augment_freq_width', int, 0), ('augment_time_masks', int, 0), ('augment_time_width', int, 0),
+          ('augment_seed', int, 0)]
 
 
 def build_parser():
@@ -659,9 +665,14 @@ class ResidentLoader:
     Sample order and RNG consumption are the DataLoader's: every epoch draws the iterator's base seed and, with
     shuffle, the RandomSampler's seed from torch's default generator, so a run with this loader visits the samples in
     the order a run with the DataLoader visits them.  Data parallel: `batch_size` is the global batch, this rank
-    gathers its `rank_rows` of every batch; rank 0's order is broadcast, so ranks agree whatever their RNG state."""
+    gathers its `rank_rows` of every batch; rank 0's order is broadcast, so ranks agree whatever their RNG state.
 
-    def __init__(self, x_all, y_all, batch_size, shuffle, rank=0, world=1):
+    `augment` (a hip_ops.Augment; default None: exactly the launches above): every fetch is hip_ops.gather_rows_aug, still
+    one launch.  What a sample draws depends on (`seed`, the device int32 `epoch`, its position in the epoch's order):
+    ranks need no agreement, and a recorded fetch draws anew in every epoch.  `epoch` is -1 until the first
+    `begin_epoch`, which adds 1 to it."""
+
+    def __init__(self, x_all, y_all, batch_size, shuffle, rank=0, world=1, augment=None, seed=0):
         self.plan = epoch_plan(x_all.shape[0], batch_size, world)
         if y_all.shape[0] != x_all.shape[0]:
             raise ValueError(f"ResidentLoader: {x_all.shape[0]} predictors but {y_all.shape[0]} targets")
@@ -674,12 +685,14 @@ class ResidentLoader:
         self.index = torch.arange(self.n, device=dev, dtype=torch.int64)
         self.cursor = torch.zeros(1, device=dev, dtype=torch.int32)
         self.mean = torch.zeros(1, device=dev, dtype=torch.float32)
+        self.epoch = torch.full((1,), -1, device=dev, dtype=torch.int32)
+        self.augment, self.seed = augment, int(seed)
 
     def __len__(self):
         return len(self.plan)
 
     def begin_epoch(self):
-        """New sample order (outside any capture), cursor and mean back to zero."""
+        """New sample order (outside any capture), cursor and mean back to zero, the epoch number one up."""
         torch.empty((), dtype=torch.int64).random_()           # the base seed a DataLoader iterator draws first
         if self.shuffle:
             self.index.copy_(H.epoch_permutation(self.n))
@@ -687,17 +700,21 @@ class ResidentLoader:
                 torch.distributed.broadcast(self.index, 0)
         self.cursor.zero_()
         self.mean.zero_()
+        self.epoch += 1
 
     def fetch(self, count=None, batch=None):
         """Gather this rank's rows of a batch into `x` / `target` and return the views of the rows that were written.
         batch None: the batch the device cursor points at (recordable); else that batch of the plan, whatever the cursor."""
         count = self.x.shape[0] if count is None else count
         if batch is None:
-            H.gather_rows(self.x_all, self.y_all, self.index, self.x, self.target, cursor=self.cursor,
-                          start=self.rank * count, count=count, stride=self.batch_size)
+            where = dict(cursor=self.cursor, start=self.rank * count, count=count, stride=self.batch_size)
         else:
-            H.gather_rows(self.x_all, self.y_all, self.index, self.x, self.target,
-                          start=rank_rows(self.plan[batch][0], count, self.rank)[0], count=count)
+            where = dict(start=rank_rows(self.plan[batch][0], count, self.rank)[0], count=count)
+        if self.augment is None:
+            H.gather_rows(self.x_all, self.y_all, self.index, self.x, self.target, **where)
+        else:
+            H.gather_rows_aug(self.x_all, self.y_all, self.index, self.x, self.target, epoch=self.epoch, seed=self.seed,
+                              augment=self.augment, **where)
         return self.x[:count], self.target[:count]
 
     def step_end(self, loss):
@@ -773,6 +790,30 @@ def normalize_dataset(args, *predictors):
     if args.phase:
         desc += f' Dataset Normalization for {args.n_mics}Mic {2 * mag}Ch Magnitude-Phase'
     return desc
+
+
+def augment_requested(args):
+    return args.augment_swap > 0 or args.augment_freq_masks > 0 or args.augment_time_masks > 0
+
+
+def augment_from_args(args, device):
+    """The hip_ops.Augment of the --augment_* flags for the training loader, None when they are all off.  Every refusal
+    comes before the device is touched."""
+    if not augment_requested(args):
+        return None
+    if not args.resident_loader:
+        raise ValueError("--augment_* flags need --resident_loader (the augmentation is part of the device gather)")
+    swap = args.augment_swap > 0
+    mode = str(args.dataset_normalization)
+    if swap and args.phase and mode not in _NORM_OFF and mode not in _NORM_UNIT:
+        raise ValueError("--augment_swap with --phase needs raw phase (a sign flip turns the phase by pi): not with a "
+                         "standardising --dataset_normalization")
+    if swap and args.n_mics not in (1, 2):
+        raise ValueError(f"--augment_swap: the FOA transform preset is for 1 or 2 microphones, got --n_mics {args.n_mics}")
+    table = H.foa_transforms(mics=args.n_mics, phase=bool(args.phase)) if swap else None
+    return H.Augment(table=table, p_swap=args.augment_swap if swap else 0.0, freq_masks=args.augment_freq_masks,
+                     freq_width=args.augment_freq_width, time_masks=args.augment_time_masks,
+                     time_width=args.augment_time_width, device=device)
 
 
 def test_results_from_counters(counts, total_de, epoch=0):
@@ -862,6 +903,8 @@ def main(args, history=None):
     resident, graph_step = bool(args.resident_loader), bool(args.graph_step)
     if graph_step and not resident:
         raise ValueError("--graph_step needs --resident_loader")
+    if augment_requested(args) and not resident:
+        raise ValueError("--augment_* flags need --resident_loader (the augmentation is part of the device gather)")
     if not args.use_cuda or not torch.cuda.is_available():
         raise RuntimeError("this implementation has no CPU path: a HIP device is required")
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -905,11 +948,12 @@ def main(args, history=None):
         if resident:
             raise ValueError("--resident_loader reads pickled arrays: not with --synthetic")
     else:
-        def loader(x, y, batch_size, shuffle, rank=0, world=1):
+        def loader(x, y, batch_size, shuffle, rank=0, world=1, augment=None):
             if resident:
-                return ResidentLoader(x, y, batch_size, shuffle, rank, world)
+                return ResidentLoader(x, y, batch_size, shuffle, rank, world, augment=augment, seed=args.augment_seed)
             return torch.utils.data.DataLoader(torch.utils.data.TensorDataset(x, y), batch_size, shuffle=shuffle,
                                                pin_memory=False)
+        augment = augment_from_args(args, device)      # the training loader's alone: validation and test see the data as it is
         xs, ys = load_pickled(args.training_predictors_path, args.training_target_path)
         xs = xs.to(device)                              # 288 GB of HBM: the arrays stay resident, loaders index them
         val_data = test_data = None
@@ -919,7 +963,7 @@ def main(args, history=None):
             print(normalize_dataset(args, xs, xv))
         else:
             normalize_dataset(args, xs)
-        tr_data = loader(xs, ys, args.batch_size, True, rank, world)
+        tr_data = loader(xs, ys, args.batch_size, True, rank, world, augment)
         if rank == 0:
             val_data = loader(xv, yv, args.batch_size, False)
             if os.path.isfile(str(args.test_predictors_path)) and os.path.isfile(str(args.test_target_path)):

@@ -5,6 +5,9 @@ gather:  hip_ops.gather_rows of one batch (32 x 8 x 128 x 512 fp32 predictors + 
          array of --rows samples in a shuffled order, beside torch.index_select on the same tensors (predictors, then
          targets) and a device-to-device copy_ of the same bytes.  HIP events around each call, a warm-up, the median
          of --reps runs; bytes are the algorithmic ones (every batch byte read once and written once).
+         gather_rows_aug of the same batch in three settings: nothing to apply (no table, no masks), the 8-channel FOA
+         preset at p_swap = 1, and the preset at p_swap = 0.5 with two frequency masks (up to 16 bins) and two time
+         masks (up to 64 frames): the same bytes, so its time stands beside gather_rows' from the same run.
 main:    wall time per training step of train.main with config/BENCH_c3_DQSELD-TCN_8ch_F128.txt on synthetic pickles
          (--samples training samples, one validation batch), in three modes: flags off (DataLoader + eager step),
          --resident_loader, and --resident_loader --graph_step.  A step's time is the time from `model.train()` at the
@@ -60,8 +63,20 @@ def gather_part(rows, reps):
     same = bool(torch.equal(out_x, x_all[batch])) and bool(torch.equal(out_y, y_all[batch]))
     nbytes = 2 * 4 * (out_x.numel() + out_y.numel())
     src_x, src_y = x_all[:BATCH], y_all[:BATCH]
+    epoch = torch.zeros(1, device=dev, dtype=torch.int32)
+    preset = H.foa_transforms(mics=2)
+    augments = dict(gather_rows_aug_idle=H.Augment(device=dev),
+                    gather_rows_aug_swap=H.Augment(table=preset, p_swap=1.0, device=dev),
+                    gather_rows_aug_swap_masks=H.Augment(table=preset, p_swap=0.5, freq_masks=2, freq_width=16, time_masks=2,
+                                                         time_width=64, device=dev))
+
+    def aug_run(augment):
+        return lambda: H.gather_rows_aug(x_all, y_all, index, out_x, out_y, epoch=epoch, seed=1, augment=augment, cursor=cursor)
+    aug_run(augments["gather_rows_aug_idle"])()
+    same = same and bool(torch.equal(out_x, x_all[batch])) and bool(torch.equal(out_y, y_all[batch]))
     runs = dict(
         gather_rows=device_timed(lambda: H.gather_rows(x_all, y_all, index, out_x, out_y, cursor=cursor), reps),
+        **{name: device_timed(aug_run(augment), reps) for name, augment in augments.items()},
         index_select=device_timed(lambda: (torch.index_select(x_all, 0, batch, out=out_x),
                                            torch.index_select(y_all, 0, batch, out=out_y)), reps),
         copy_=device_timed(lambda: (out_x.copy_(src_x), out_y.copy_(src_y)), reps))
