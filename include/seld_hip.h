@@ -716,6 +716,24 @@ int seld_loss_fwd_bwd(const float* sed, const float* doa, const float* target,
                       int64_t rows, int32_t n_sed, int32_t n_doa, float w_sed, float w_doa,
                       float* loss, float* dsed, float* ddoa, void* stream);
 
+/* The same loss, permutation invariant over the `overlaps` (1..3) same-class track slots.  Layouts: sed[r, c * O + o],
+ * doa[r, (c * O + o) * 3 + d], target[r] = [t_sed (C * O) | t_doa (3 * C * O)].  With a = w_sed / (rows * C * O) and
+ * b = w_doa / (rows * 3 * C * O), the pair cost of prediction slot o against target slot j of a cell (r, c) is
+ *     P[o][j] = a * bce(sed[o], t_sed[j]) + b * sum_d (doa[o][d] - t_doa[j][d])^2        (logs clamped at -100)
+ * and a permutation pi (prediction slot -> target slot) costs (P[0][pi0] + P[1][pi1]) + P[2][pi2] (the terms of
+ * missing slots absent).  Permutations are numbered in lexicographic order -- O = 3: 0 (0,1,2), 1 (0,2,1), 2 (1,0,2),
+ * 3 (1,2,0), 4 (2,0,1), 5 (2,1,0); O = 2: 0 (0,1), 1 (1,0) -- and the search starts from the identity and moves on `<`
+ * only: ties go to the lowest index, a NaN cost never displaces the identity.  loss[0] is WRITTEN with the sum over
+ * cells of the chosen cost; dsed / ddoa (nullable, as above) are the plain loss's gradients with each cell's target
+ * slots permuted by the chosen pi (the choice is a constant; DOA terms are not masked by activity).
+ * perm (nullable): (rows, classes) int32, the chosen index.  parts (nullable): 2 floats, the a * BCE and b * MSE sums of
+ * the chosen pairing.  One launch.  It shares the per-device reduction scratch of seld_loss_fwd_bwd: evaluations of
+ * EITHER loss on one device must not overlap on different streams.
+ * SELD_EINVAL: NULL sed / doa / target / loss or a size <= 0; SELD_EUNSUPPORTED: overlaps > 3. */
+int seld_loss_pit_fwd_bwd(const float* sed, const float* doa, const float* target,
+                          int64_t rows, int32_t classes, int32_t overlaps, float w_sed, float w_doa,
+                          float* loss, float* dsed, float* ddoa, int32_t* perm, float* parts, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Adam (torch.optim.Adam defaults, train.py:502) over ONE flat fp32 buffer that holds every
  * parameter; grads/exp_avg/exp_avg_sq are parallel flat buffers.  step is 1-based.

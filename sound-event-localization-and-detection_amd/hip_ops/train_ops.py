@@ -59,6 +59,70 @@ def seld_loss(sed, doa, target, w_sed=1.0, w_doa=5.0):
     return SeldLossFn.apply(sed, doa, target, float(w_sed), float(w_doa))
 
 
+def _pit_call(sed, doa, target, overlaps, w_sed, w_doa, grads, perm, parts):
+    """One seld_loss_pit_fwd_bwd launch on (.., n_sed) / (.., n_doa) / (.., n_sed + n_doa) tensors.  Returns
+    (loss (1,), dsed, ddoa, perm, parts), each of the last four None unless asked for."""
+    sed2 = _req(sed.reshape(-1, sed.shape[-1]), "sed")
+    doa2 = _req(doa.reshape(-1, doa.shape[-1]), "doa")
+    tgt = _req(target.reshape(-1, target.shape[-1]), "target")
+    rows, n_sed = sed2.shape
+    overlaps = int(overlaps)
+    if overlaps < 1 or n_sed % overlaps:
+        raise L.SeldHipError(f"seld_loss_pit: {n_sed} SED outputs are not a multiple of overlaps = {overlaps}")
+    if tuple(doa2.shape) != (rows, 3 * n_sed) or tuple(tgt.shape) != (rows, 4 * n_sed):
+        raise L.SeldHipError(f"seld_loss_pit: shapes {tuple(sed2.shape)} / {tuple(doa2.shape)} / {tuple(tgt.shape)} do not match "
+                             f"(rows, {n_sed}) / (rows, {3 * n_sed}) / (rows, {4 * n_sed})")
+    classes = n_sed // overlaps
+    dev = sed2.device
+    loss = torch.empty(1, device=dev, dtype=torch.float32)              # written, not accumulated (ticketed reduction)
+    dsed, ddoa = (torch.empty_like(sed2), torch.empty_like(doa2)) if grads else (None, None)
+    perm_t = torch.empty((rows, classes), device=dev, dtype=torch.int32) if perm else None
+    parts_t = torch.empty(2, device=dev, dtype=torch.float32) if parts else None
+    L.check(L.lib().seld_loss_pit_fwd_bwd(L.ptr(sed2), L.ptr(doa2), L.ptr(tgt), rows, classes, overlaps, w_sed, w_doa,
+                                          L.ptr(loss), L.ptr(dsed), L.ptr(ddoa), L.ptr(perm_t), L.ptr(parts_t),
+                                          L.current_stream()), "seld_loss_pit_fwd_bwd")
+    return loss, dsed, ddoa, perm_t, parts_t
+
+
+class SeldLossPitFn(torch.autograd.Function):
+    """SeldLossFn with, per (frame, class) cell, the pairing of the `overlaps` prediction slots with the target slots
+    that costs least (include/seld_hip.h: seld_loss_pit_fwd_bwd); the choice is a constant of the backward pass.
+    Returns (loss, perm): perm is the (rows, classes) int32 index of the chosen permutation, or None."""
+
+    @staticmethod
+    def forward(ctx, sed, doa, target, overlaps, w_sed, w_doa, return_perm):
+        loss, dsed, ddoa, perm, _ = _pit_call(sed, doa, target, overlaps, w_sed, w_doa, True, return_perm, False)
+        ctx.shapes = (tuple(sed.shape), tuple(doa.shape))
+        ctx.save_for_backward(dsed, ddoa)
+        if perm is not None:
+            ctx.mark_non_differentiable(perm)
+        return loss.reshape(()), perm
+
+    @staticmethod
+    def backward(ctx, g, _gperm=None):
+        dsed, ddoa = ctx.saved_tensors
+        s1, s2 = ctx.shapes
+        if g.data_ptr() == unit_gradient(g.device).data_ptr():       # backward_from_loss(): d loss / d loss = 1
+            return dsed.reshape(s1), ddoa.reshape(s2), None, None, None, None, None
+        return (dsed * g).reshape(s1), (ddoa * g).reshape(s2), None, None, None, None, None
+
+
+def seld_loss_pit(sed, doa, target, overlaps, w_sed=1.0, w_doa=5.0, return_perm=False):
+    """The permutation-invariant SELD loss over the `overlaps` (1..3) same-class track slots: one launch, forward and
+    backward.  return_perm: (loss, perm) with perm (rows, classes) int32, the chosen permutation's lexicographic index."""
+    loss, perm = SeldLossPitFn.apply(sed, doa, target, int(overlaps), float(w_sed), float(w_doa), bool(return_perm))
+    return (loss, perm) if return_perm else loss
+
+
+def seld_loss_pit_parts(sed, doa, target, overlaps, w_sed=1.0, w_doa=5.0):
+    """(loss, parts, perm) without autograd and without gradients, for logging and analysis: parts = the w_sed * BCE and
+    w_doa * MSE shares of the chosen pairing (2 floats on the device), perm as in seld_loss_pit."""
+    with torch.no_grad():
+        loss, _, _, perm, parts = _pit_call(sed.detach(), doa.detach(), target, overlaps, float(w_sed), float(w_doa), False,
+                                            True, True)
+    return loss.reshape(()), parts, perm
+
+
 def adam_flat_step(param, grad, exp_avg, exp_avg_sq, step, lr=1e-4, beta1=0.9, beta2=0.999, eps=1e-8,
                    weight_decay=0.0, grad_scale=1.0):
     L.check(L.lib().seld_adam_flat(L.ptr(param), L.ptr(grad), L.ptr(exp_avg), L.ptr(exp_avg_sq), param.numel(), lr,

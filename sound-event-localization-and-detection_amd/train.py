@@ -12,6 +12,7 @@ this file restates its behaviour rather than its text.
 """
 import argparse
 import ast
+import functools
 import os
 import pickle
 import shutil
@@ -29,10 +30,19 @@ from .model import SELD_Model
 # ------------------------------------------------------------------------------------------
 # loss / optimiser
 # ------------------------------------------------------------------------------------------
-def seld_loss_fn(sed, doa, target, n_sed, sed_weight=1.0, doa_weight=5.0):
-    """BCE(sed, target[..., :n_sed]) * sed_weight + MSE(doa, target[..., n_sed:]) * doa_weight, both means."""
+def seld_loss_fn(sed, doa, target, n_sed, sed_weight=1.0, doa_weight=5.0, pit_overlaps=0):
+    """BCE(sed, target[..., :n_sed]) * sed_weight + MSE(doa, target[..., n_sed:]) * doa_weight, both means.
+    pit_overlaps > 0 (--pit_loss): the same with, per (frame, class), the cheapest pairing of the pit_overlaps prediction
+    slots with the target slots (hip_ops.seld_loss_pit); one launch either way."""
     assert target.shape[-1] == sed.shape[-1] + doa.shape[-1] and sed.shape[-1] == n_sed
+    if pit_overlaps:
+        return H.seld_loss_pit(sed, doa, target, pit_overlaps, sed_weight, doa_weight)
     return H.seld_loss(sed, doa, target, sed_weight, doa_weight)
+
+
+def pit_overlaps_from_args(args):
+    """class_overlaps under --pit_loss, else 0 (the slot-bound loss)."""
+    return int(args.class_overlaps) if getattr(args, "pit_loss", False) else 0
 
 
 class BCELoss(nn.Module):
@@ -51,7 +61,7 @@ def seld_loss(x, target, model, criterion_sed, criterion_doa, args=None):
     n_sed = int(a.output_classes * a.class_overlaps)
     sed, doa = model(x)
     if isinstance(criterion_sed, BCELoss) and isinstance(criterion_doa, MSELoss):
-        return seld_loss_fn(sed, doa, target, n_sed, a.sed_loss_weight, a.doa_loss_weight)
+        return seld_loss_fn(sed, doa, target, n_sed, a.sed_loss_weight, a.doa_loss_weight, pit_overlaps_from_args(a))
     t_sed, t_doa = target[:, :, :n_sed], target[:, :, n_sed:]
     return criterion_sed(torch.flatten(sed, 1), torch.flatten(t_sed, 1)) * a.sed_loss_weight + \
         criterion_doa(torch.flatten(doa, 1), torch.flatten(t_doa, 1)) * a.doa_loss_weight
@@ -200,11 +210,15 @@ class GraphedTrainStep:
     `loader` (a ResidentLoader; default None: everything above): the recorded input buffers ARE the loader's batch
     buffers, the loader's gather is recorded as the first launch of the step and its `step_end` (running mean of the
     loss, cursor += 1) as the last, so `__call__()` with no arguments trains on the next batch of the epoch: an epoch
-    is n replays with no host-to-device traffic.  `x` / `target` are then not copied (pass the loader's buffers)."""
+    is n replays with no host-to-device traffic.  `x` / `target` are then not copied (pass the loader's buffers).
 
-    def __init__(self, model, optimizer, x, target, n_sed, sed_weight=1.0, doa_weight=5.0, sync=None, warmup=2, loader=None):
+    `pit_overlaps` (default 0: the slot-bound loss): as in seld_loss_fn; the permutation-invariant loss is one launch
+    without a host read, so it is recorded like the plain one."""
+
+    def __init__(self, model, optimizer, x, target, n_sed, sed_weight=1.0, doa_weight=5.0, sync=None, warmup=2, loader=None,
+                 pit_overlaps=0):
         self.model, self.opt, self.sync, self.loader = model, optimizer, sync, loader
-        self.n_sed, self.w = n_sed, (float(sed_weight), float(doa_weight))
+        self.n_sed, self.w, self.pit_overlaps = n_sed, (float(sed_weight), float(doa_weight)), int(pit_overlaps)
         if loader is None:
             self.x, self.target = x.clone(), target.clone()
         else:
@@ -264,7 +278,7 @@ class GraphedTrainStep:
         if self.cut is not None:
             self.cut.reset()
         sed, doa = self.model(self.x)
-        loss = seld_loss_fn(sed, doa, self.target, self.n_sed, *self.w)
+        loss = seld_loss_fn(sed, doa, self.target, self.n_sed, *self.w, self.pit_overlaps)
         H.backward_from_loss(loss)
         if self.cut is not None:
             self.cut.finish()
@@ -283,7 +297,7 @@ class GraphedTrainStep:
         if self.cut is not None:
             self.cut.reset()
         sed, doa = self.model(self.x)
-        loss = seld_loss_fn(sed, doa, self.target, self.n_sed, *self.w)
+        loss = seld_loss_fn(sed, doa, self.target, self.n_sed, *self.w, self.pit_overlaps)
         H.backward_from_loss(loss)
         H.join_side_stream()
         return loss.detach()
@@ -414,18 +428,21 @@ _FLAGS = [
 ]
 _EVAL = ('use_cuda', 'early_stopping', 'fixed_seed', 'pool_size', 'cnn_filters', 'verbose', 'D', 'V', 'use_lr_scheduler',
          'phase', 'use_tcn', 'use_bias_conv', 'use_bias_linear', 'fc_layers', 'parallel_magphase',
-         'resident_loader', 'graph_step')
+         'resident_loader', 'graph_step', 'pit_loss')
 # extensions of this implementation (not in the reference): synthetic data so the step can run without L3DAS21;
 # resident_loader: minibatches gathered on the device (ResidentLoader) instead of a DataLoader over the resident arrays;
 # graph_step (needs resident_loader): full batches run as replays of one recorded step (GraphedTrainStep);
 # augment_* (need resident_loader; training loader only; all off by default): augmentation inside the gather launch
 # (hip_ops.gather_rows_aug) -- augment_swap: probability of a signed FOA channel permutation with its DOA labels
 # (hip_ops.foa_transforms for --n_mics / --phase); augment_freq_masks / augment_time_masks: 0..2 masks per sample of a
-# width up to augment_freq_width / augment_time_width bins; augment_seed: the key of the draws
+# width up to augment_freq_width / augment_time_width bins; augment_seed: the key of the draws;
+# pit_loss (off by default): the loss takes, per (frame, class), the cheapest pairing of the class_overlaps prediction
+# slots with the target slots (hip_ops.seld_loss_pit) instead of comparing slot o with slot o -- training steps (eager,
+# data parallel, recorded) and the validation loss alike
 _EXTRA = [('synthetic', int, 0), ('max_steps', int, 0), ('epochs', int, 0), ('resident_loader', str, 'False'),
           ('graph_step', str, 'False'), ('augment_swap', float, 0.), ('augment_freq_masks', int, 0),
           ('augment_freq_width', int, 0), ('augment_time_masks', int, 0), ('augment_time_width', int, 0),
-          ('augment_seed', int, 0)]
+          ('augment_seed', int, 0), ('pit_loss', str, 'False')]
 
 
 def build_parser():
@@ -905,6 +922,9 @@ def main(args, history=None):
         raise ValueError("--graph_step needs --resident_loader")
     if augment_requested(args) and not resident:
         raise ValueError("--augment_* flags need --resident_loader (the augmentation is part of the device gather)")
+    pit = pit_overlaps_from_args(args)
+    if pit > 3:
+        raise ValueError(f"--pit_loss searches the pairings of at most 3 slots per class, got --class_overlaps {pit}")
     if not args.use_cuda or not torch.cuda.is_available():
         raise RuntimeError("this implementation has no CPU path: a HIP device is required")
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -939,6 +959,9 @@ def main(args, history=None):
         optimizer = FlatAdam(model.parameters(), lr=args.lr)
     scheduler = StepLR(optimizer, args.lr_scheduler_step_size, args.lr_scheduler_gamma) if args.use_lr_scheduler else None
     n_out = int(args.output_classes * args.class_overlaps)
+    # bound once: the data-parallel step and the recorded step take the loss the eager step and `evaluate` reach through
+    # seld_loss(..., args)
+    loss_fn = functools.partial(seld_loss_fn, pit_overlaps=pit) if pit else seld_loss_fn
 
     if args.synthetic:
         data = [synthetic_batch(args.batch_size, args.input_channels, args.freq_dim, args.time_dim, n_out, 1234 + i, device)
@@ -987,7 +1010,7 @@ def main(args, history=None):
 
     def eager_step(x, target):
         if sync is not None:
-            return DP.dp_train_step(model, optimizer, sync, x, target, n_out, seld_loss_fn, args.sed_loss_weight,
+            return DP.dp_train_step(model, optimizer, sync, x, target, n_out, loss_fn, args.sed_loss_weight,
                                     args.doa_loss_weight)
         optimizer.zero_grad()
         loss = seld_loss(x, target, model, criterion_sed, criterion_doa, args)
@@ -1004,7 +1027,7 @@ def main(args, history=None):
         snap = training_snapshot(model, optimizer)
         tr_data.fetch(batch=0)
         runner = GraphedTrainStep(model, optimizer, tr_data.x, tr_data.target, n_out, args.sed_loss_weight,
-                                  args.doa_loss_weight, sync=sync, warmup=1, loader=tr_data)
+                                  args.doa_loss_weight, sync=sync, warmup=1, loader=tr_data, pit_overlaps=pit)
         training_restore(model, optimizer, snap)
     while (state["worse_epochs"] < args.patience or epoch < args.min_n_epochs) and not (args.epochs and epoch >= args.epochs):
         epoch += 1
