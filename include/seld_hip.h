@@ -32,10 +32,8 @@ int         seld_abi_version(void);          /* bumps on any signature change   
 const char* seld_build_arch(void);           /* "gfx950"                                           */
 int         seld_last_hip_error(void);       /* last hipError_t seen by a launch in this thread    */
 /* The SELD_* environment switches (csrc/env.h: kernel-generation selection, all result-preserving) are read once at
- * first use; seld_env_reload re-reads them.  seld_tuning_build: 1 if the library was compiled with -DSELD_TUNING,
- * which adds timing-experiment switches that produce WRONG results (never set for the shipped library). */
+ * first use; seld_env_reload re-reads them. */
 int         seld_env_reload(void);
-int         seld_tuning_build(void);
 
 /* ------------------------------------------------------------------------------------------
  * Hypercomplex convolution.  Replaces quaternion_conv (quaternion_ops.py:125-147),

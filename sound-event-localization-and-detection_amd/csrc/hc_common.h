@@ -21,7 +21,6 @@ struct ConvP {
     int srcS, dstS;
     long long Ptot;            // N * dstS
     long long src_elems;       // N * Csrc * srcS
-    int pairing;               // allow primal/dual paired channel tiles (work balance)
     int wt;                    // dgrad: component tensors are transposed to [c][o][k]
     int skip_mode;             // 0 none, 1 (fwd DQ): low-half channels x high-half K is zero, 2 (dgrad DQ): high x low
     int epilogue;
@@ -77,8 +76,35 @@ struct WgradP {
     int poolh;         // pooling window height
     DropP drop;        // FUSED: dpooled is the gradient behind the stage's Dropout; replay its mask (p == 0: none)
     int mz, nact, nt;  // tile enumeration without the zero quadrant: the first mz row tiles have nact column tiles, the rest nt
-    int dbg;           // SELD_WGRAD_DBG: timing experiments (wrong results): 1 = no loads in the loop, 2 = no LDS stores
 };
+
+// What one forward / data-gradient call launches, decided from a filled ConvP alone (hc_conv_plan, hc_conv_fwd.hip): the
+// launch, the kernel label and the pair query all read it.
+struct ConvPlan {
+    enum Kind { GENERAL, VEC, SMALLK } kind;   // hc_conv_kernel / hc_conv_vec_kernel / hc_conv_smallk_kernel
+    int ct, pt;        // channel and position tile (SMALLK: ct only)
+    int kh, kw;        // taps fixed at compile time, 0 = run-time
+    int fast;          // hc_conv_kernel's FAST instantiation applies (also what VEC falls back to at launch time)
+    int kc;            // VEC: K chunk (36 / 24)
+    int pair;          // VEC: two convolutions in one launch (PAIRS)
+};
+
+// Weight-gradient tile configurations, indexed by wgrad_cfg() (hc_wgrad.hip): waves along rows, row tiles and column
+// tiles per wave of the four waves.  The tile sizes, both template dispatches and the label text come from this table.
+struct WgradTile {
+    int wrw, rt, ctl;
+    constexpr int bm() const { return wrw * rt * 16; }
+    constexpr int bn() const { return (4 / wrw) * ctl * 16; }
+};
+constexpr WgradTile WGRAD_TILES[6] = {{2, 4, 4}, {4, 3, 5}, {2, 2, 2}, {2, 3, 4}, {4, 1, 5}, {4, 1, 10}};
+// FN<WRW, RT, CTL>(args...) for tile configuration `cfg`
+#define SELD_WGRAD_CASE(I, FN, ...) \
+    case I: FN<WGRAD_TILES[I].wrw, WGRAD_TILES[I].rt, WGRAD_TILES[I].ctl>(__VA_ARGS__); break;
+#define SELD_WGRAD_DISPATCH(cfg, FN, ...)                                                                             \
+    switch (cfg) {                                                                                                    \
+        SELD_WGRAD_CASE(0, FN, __VA_ARGS__) SELD_WGRAD_CASE(1, FN, __VA_ARGS__) SELD_WGRAD_CASE(2, FN, __VA_ARGS__)   \
+        SELD_WGRAD_CASE(3, FN, __VA_ARGS__) SELD_WGRAD_CASE(4, FN, __VA_ARGS__) SELD_WGRAD_CASE(5, FN, __VA_ARGS__)   \
+    }
 
 // blockIdx.z -> (row tile, column tile), skipping the tiles that lie wholly in the dual-quaternion zero quadrant.
 // The position split is blockIdx.x, the FAST dispatch index: workgroup ids go round-robin to the 8 XCDs, so with a

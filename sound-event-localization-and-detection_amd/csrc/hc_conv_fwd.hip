@@ -113,19 +113,12 @@ __global__ __launch_bounds__(256) void hc_conv_kernel(const ConvP p) {
     const int rowb0 = img_b + base_h * srcWb;
 
     // ---- channel tile of this workgroup -----------------------------------------------------------
-    // Dual quaternion: the first half of the channels (primal part) sees a structurally-zero K half.  So
-    // that every workgroup carries the same work, a workgroup MAY take BC/2 primal channels and the BC/2 dual
-    // channels at the same offset in the upper half (local tile j < CT/2 primal, j >= CT/2 dual) whenever
-    // the shape allows; otherwise tiles are contiguous.
+    // Dual quaternion: the first half of the channels (primal part) sees a structurally-zero K half.  Tiles are
+    // contiguous channel ranges.
     const int half_c = p.Cdst >> 1;
     const int half_k = p.Ktot >> 1;
     const bool halves_aligned = (p.skip_mode != 0) && (half_k % 16 == 0) && (half_c % 16 == 0);
-    const bool paired = p.pairing && halves_aligned && (CT % 2 == 0) && (half_c % (BC / 2) == 0);
-    auto chan_of = [&](int t) __attribute__((always_inline)) {
-        if (!paired) return c0 + t;
-        const int base = blockIdx.y * (BC / 2);
-        return t < BC / 2 ? base + t : half_c + base + (t - BC / 2);
-    };
+    auto chan_of = [&](int t) __attribute__((always_inline)) { return c0 + t; };
 
     // ---- per-lane decode of the weight rows this lane stages ---------------------------------------
     int w_a[WR], w_off[WR];        // fwd: a = output component p, off = o*CK ; dgrad: a = input component q, off = c*KK
@@ -147,14 +140,14 @@ __global__ __launch_bounds__(256) void hc_conv_kernel(const ConvP p) {
 
     // ---- K range of this workgroup (dual-quaternion zero quadrant) ----------------------------------
     int kbeg = 0, kend = p.Ktot;
-    if (halves_aligned && !paired) {
+    if (halves_aligned) {
         if (p.skip_mode == 1 && c0 + BC <= half_c) kend = half_k;      // all channels primal
         if (p.skip_mode == 2 && c0 >= half_c) kbeg = half_k;           // all channels dual
     }
     const int nchunks = (kend - kbeg + 15) >> 4;
     // workgroup whose lower tiles are primal and upper tiles dual: half of its tiles skip the zero quadrant's
     // chunks (any other straddle just multiplies by the staged zeros)
-    const bool mixed_wg = paired || (halves_aligned && (CT % 2 == 0) && (c0 + BC / 2 == half_c));
+    const bool mixed_wg = halves_aligned && (CT % 2 == 0) && (c0 + BC / 2 == half_c);
 
     // ---- scalar trackers of this wave's weight k-group start kw = kbeg + 16*chunk + 4*wave ----------
     // fwd  : kw = kq*CK + kl           (input component, local index)
@@ -495,18 +488,56 @@ __global__ void hc_transpose_w_kernel(WPtrs w, int A, int OA, int IA, int KK, fl
     out[idx] = w.p[comp][((size_t)o * IA + c) * KK + k];
 }
 
-int hc_conv_vec_try(const ConvP& p, int mode, int ct, int pt, hipStream_t st);
-int hc_conv_vec_chunk(const ConvP& p, int mode, int ct, int pt);
+int hc_conv_smallk_ct(const ConvP& p);                                        // hc_conv_smallk.hip
+int hc_conv_smallk_launch(const ConvP& p, int ct, hipStream_t st);
+int hc_conv_vec_chunk(const ConvP& p, int ct, int pt);                         // hc_conv_vec.hip
+int hc_conv_vec_launch(const ConvP& p, const ConvPlan& pl, hipStream_t st);
+
+static bool taps_specialised(const ConvP& p) {
+    return (p.KH == 1 && p.KW == 1) || (p.KH == 1 && p.KW == 3) || (p.KH == 3 && p.KW == 3);
+}
+
+// hc_conv_kernel's FAST instantiation: weight rows contiguous along K (forward, or transposed weights), component extent
+// a multiple of 4 and >= 16, no strided data gradient, taps known at compile time
+static bool conv_fast_ok(const ConvP& p) {
+    const int CK = (p.mode == MODE_FWD ? p.IA : p.OA) * p.KH * p.KW;
+    return (p.mode == MODE_FWD || p.wt) && (CK % 4 == 0) && CK >= 16 && p.SDh == 1 && p.SDw == 1 && taps_specialised(p);
+}
+
+// The one place the kernel of a forward / data-gradient call is chosen.  Needs no pointers and launches nothing: p carries
+// the geometry, the mode, the epilogue and nslots (2: a pair).  allow_smallk: the persistent short-reduction kernel may
+// take a single forward call.
+ConvPlan hc_conv_plan(const ConvP& p, bool allow_smallk) {
+    ConvPlan pl{};
+    pl.fast = conv_fast_ok(p) ? 1 : 0;
+    if (allow_smallk && p.nslots <= 1 && (pl.ct = hc_conv_smallk_ct(p)) != 0) {
+        pl.kind = ConvPlan::SMALLK;
+        const bool shaped = (p.KH == 1 || p.KH == 3) && p.KW == 3;             // 1x3 and 3x3 instances, else run-time taps
+        pl.kh = shaped ? p.KH : 0;
+        pl.kw = shaped ? p.KW : 0;
+        return pl;
+    }
+    const TileCfg c = pick_cfg(p.Cdst, p.Ptot);
+    pl.ct = c.ct;
+    pl.pt = c.pt;
+    pl.kc = hc_conv_vec_chunk(p, c.ct, c.pt);
+    if (pl.kc) {
+        pl.kind = ConvPlan::VEC;
+        pl.kh = p.KH;
+        pl.kw = p.KW;
+        pl.pair = p.nslots > 1 ? 1 : 0;
+        return pl;
+    }
+    pl.kind = ConvPlan::GENERAL;
+    pl.kh = pl.fast ? p.KH : 0;
+    pl.kw = pl.fast ? p.KW : 0;
+    return pl;
+}
 
 template <int CT, int PT, int MODE>
-static void launch_conv(const ConvP& p, hipStream_t st) {
+static void launch_conv(const ConvP& p, bool fast, hipStream_t st) {
     constexpr int BC = CT * 16, BP = PT * 64;
-    if (hc_conv_vec_try(p, MODE, CT, PT, st)) return;     // loop-invariant staging variant (hc_conv_vec.hip)
     dim3 grid((unsigned)((p.Ptot + BP - 1) / BP), (unsigned)((p.Cdst + BC - 1) / BC), 1);
-    const int KK = p.KH * p.KW;
-    const int CK = (MODE == MODE_FWD ? p.IA : p.OA) * KK;
-    const bool fast = (MODE == MODE_FWD || p.wt) && (CK % 4 == 0) && CK >= 16 && p.SDh == 1 && p.SDw == 1 &&
-                      !env().conv_nofast;
     if (fast && p.KH == 1 && p.KW == 1) hipLaunchKernelGGL((hc_conv_kernel<CT, PT, 1, 1, MODE, 1>), grid, dim3(256), 0, st, p);
     else if (fast && p.KH == 1 && p.KW == 3) hipLaunchKernelGGL((hc_conv_kernel<CT, PT, 1, 3, MODE, 1>), grid, dim3(256), 0, st, p);
     else if (fast && p.KH == 3 && p.KW == 3) hipLaunchKernelGGL((hc_conv_kernel<CT, PT, 3, 3, MODE, 1>), grid, dim3(256), 0, st, p);
@@ -514,22 +545,30 @@ static void launch_conv(const ConvP& p, hipStream_t st) {
 }
 
 template <int MODE>
-static int run_conv(ConvP& p, hipStream_t st) {
-    const TileCfg c = pick_cfg(p.Cdst, p.Ptot);
-    if (c.ct == 12 && c.pt == 2) launch_conv<12, 2, MODE>(p, st);
-    else if (c.ct == 12 && c.pt == 1) launch_conv<12, 1, MODE>(p, st);
-    else if (c.ct == 6 && c.pt == 1) launch_conv<6, 1, MODE>(p, st);
-    else if (c.ct == 2) launch_conv<2, 4, MODE>(p, st);
-    else if (c.ct == 1) launch_conv<1, 4, MODE>(p, st);
-    else launch_conv<4, 4, MODE>(p, st);
+static void launch_general(const ConvP& p, const ConvPlan& pl, hipStream_t st) {
+    if (pl.ct == 12 && pl.pt == 2) launch_conv<12, 2, MODE>(p, pl.fast, st);
+    else if (pl.ct == 12 && pl.pt == 1) launch_conv<12, 1, MODE>(p, pl.fast, st);
+    else if (pl.ct == 6 && pl.pt == 1) launch_conv<6, 1, MODE>(p, pl.fast, st);
+    else if (pl.ct == 2) launch_conv<2, 4, MODE>(p, pl.fast, st);
+    else if (pl.ct == 1) launch_conv<1, 4, MODE>(p, pl.fast, st);
+    else launch_conv<4, 4, MODE>(p, pl.fast, st);
+}
+
+// Launches what the plan says.  A pair (p.nslots == 2) runs only on the vector-staging kernel: SELD_EUNSUPPORTED
+// otherwise, and the caller issues two single calls.  The one launch-time fallback: component tensors too far apart for
+// the vector-staging kernel's 32-bit offsets (hc_conv_vec_launch) go to hc_conv_kernel.
+static int run_conv(const ConvP& p, hipStream_t st, bool allow_smallk = true) {
+    const ConvPlan pl = hc_conv_plan(p, allow_smallk);
+    if (pl.kind == ConvPlan::SMALLK) return hc_conv_smallk_launch(p, pl.ct, st);
+    if (pl.kind == ConvPlan::VEC && hc_conv_vec_launch(p, pl, st)) return check_launch();
+    if (p.nslots > 1) return SELD_EUNSUPPORTED;
+    if (p.mode == MODE_FWD) launch_general<MODE_FWD>(p, pl, st);
+    else launch_general<MODE_DGRAD>(p, pl, st);
     return check_launch();
 }
 
-int hc_conv_smallk_try(const ConvP& p, hipStream_t st, int* rc, int dry_run);
-
 static void fill_common(ConvP& p, const seld_conv_desc* d, const float* const w[8]) {
     p.algebra = d->algebra;
-    p.pairing = env().conv_pair ? 1 : 0;   // measured 5-14 % slower on the TCN layers: off by default
     p.KH = d->k[0]; p.KW = d->k[1];
     p.OA = d->Cout / d->algebra; p.IA = d->Cin / d->algebra;
     for (int i = 0; i < 8; ++i) p.w.p[i] = (w && i < d->algebra) ? w[i] : nullptr;
@@ -590,10 +629,7 @@ extern "C" int seld_hc_conv_fwd_ex(const seld_conv_desc* d, const float* x, cons
     fill_fwd(p, d, w, o);
     p.epilogue = epilogue;
     p.src = x; p.bias = bias; p.dst = y; p.addend = addend; p.stats = stats;
-    int rc2 = SELD_OK;
-    p.wt = env().smallk_dbg;          // non-zero only in -DSELD_TUNING builds (timing experiments)
-    if (hc_conv_smallk_try(p, (hipStream_t)stream, &rc2, 0)) return rc2;       // short reductions: persistent kernel
-    return run_conv<MODE_FWD>(p, (hipStream_t)stream);
+    return run_conv(p, (hipStream_t)stream);
 }
 
 extern "C" int seld_hc_conv_fwd(const seld_conv_desc* d, const float* x, const float* const w[8],
@@ -634,7 +670,7 @@ extern "C" int seld_hc_conv_bwd_data_ex(const seld_conv_desc* d, const float* dy
         for (int i = 0; i < d->algebra; ++i) p.w.p[i] = wt + (size_t)i * per;
         p.wt = 1;
     }
-    return run_conv<MODE_DGRAD>(p, (hipStream_t)stream);
+    return run_conv(p, (hipStream_t)stream);
 }
 
 // The data gradient in two steps, so that the weight re-layout can be done ahead of time (the host mirror issues it
@@ -668,7 +704,7 @@ extern "C" int seld_hc_conv_bwd_data_wt(const seld_conv_desc* d, const float* dy
     const int per = p.OA * p.IA * p.KH * p.KW;
     for (int i = 0; i < d->algebra; ++i) p.w.p[i] = (const float*)wt_workspace + (size_t)i * per;
     p.wt = 1;
-    return run_conv<MODE_DGRAD>(p, (hipStream_t)stream);
+    return run_conv(p, (hipStream_t)stream);
 }
 
 namespace seld {
@@ -686,7 +722,7 @@ int hc_conv_fwd_out(const seld_conv_desc* d, const int o[2], const float* x, con
     fill_fwd(p, d, w, o);
     p.epilogue = SELD_EPI_NONE;
     p.src = x; p.bias = nullptr; p.dst = y;
-    return run_conv<MODE_FWD>(p, st);
+    return run_conv(p, st, false);                 // the reduced extent runs on the tiled kernels only
 }
 
 int hc_wgrad_label(const seld_conv_desc* d, char* buf, int buflen);
@@ -702,14 +738,12 @@ extern "C" int seld_hc_conv_pair_supported(const seld_conv_desc* d, int32_t whic
     hc_out_shape(d, o);
     if (o[0] <= 0 || o[1] <= 0) return 0;
     if (which == 2) return hc_wgrad_pair_ok(d);
-    if (which == 0) return 1;                      // forward pairs are two launches of the single entry point
+    if (which == 0) return 1;                      // a forward pair falls back to two launches of the single entry point
     ConvP p{};
-    if (which == 0) fill_fwd(p, d, nullptr, o);
-    else { fill_dgrad(p, d, nullptr, o); p.wt = 1; }
+    fill_dgrad(p, d, nullptr, o);
+    p.wt = 1;
     p.nslots = 2;
-    if (which == 0) { int dummy; if (hc_conv_smallk_try(p, nullptr, &dummy, 1)) return 0; }
-    const TileCfg c = pick_cfg(p.Cdst, p.Ptot);
-    return hc_conv_vec_chunk(p, which, c.ct, c.pt) ? 1 : 0;
+    return hc_conv_plan(p, false).kind == ConvPlan::VEC ? 1 : 0;
 }
 
 extern "C" int seld_hc_conv_pair_fwd(const seld_conv_desc* d, const float* x, const float* const wA[8],
@@ -731,8 +765,8 @@ extern "C" int seld_hc_conv_pair_fwd(const seld_conv_desc* d, const float* x, co
     p.nslots = 2;
     for (int i = 0; i < 8; ++i) p.w2.p[i] = (i < d->algebra) ? wB[i] : nullptr;
     p.epilogue2 = epilogueB; p.src2 = x; p.bias2 = biasB; p.dst2 = yB; p.addend2 = addendB; p.stats2 = statsB;
-    const TileCfg c = pick_cfg(p.Cdst, p.Ptot);
-    if (!env().no_fwd_pair && hc_conv_vec_try(p, MODE_FWD, c.ct, c.pt, (hipStream_t)stream)) return check_launch();
+    rc = run_conv(p, (hipStream_t)stream, false);
+    if (rc != SELD_EUNSUPPORTED) return rc;
     rc = seld_hc_conv_fwd_ex(d, x, wA, biasA, yA, epilogueA, addendA, statsA, stream);
     if (rc) return rc;
     return seld_hc_conv_fwd_ex(d, x, wB, biasB, yB, epilogueB, addendB, statsB, stream);
@@ -756,9 +790,7 @@ extern "C" int seld_hc_conv_pair_bwd_data_wt(const seld_conv_desc* d, const floa
         p.w2.p[i] = (const float*)wtB + (size_t)i * per;
     }
     p.wt = 1;
-    const TileCfg c = pick_cfg(p.Cdst, p.Ptot);
-    if (!hc_conv_vec_try(p, MODE_DGRAD, c.ct, c.pt, (hipStream_t)stream)) return SELD_EUNSUPPORTED;
-    return check_launch();
+    return run_conv(p, (hipStream_t)stream);
 }
 
 // dx = dgrad(dyA, wA) + dgrad(dyB, wB).  workspace: 2 * seld_hc_conv_bwd_data_workspace(d) bytes (required).
@@ -789,9 +821,7 @@ extern "C" int seld_hc_conv_pair_bwd_data(const seld_conv_desc* d, const float* 
         for (int i = 0; i < d->algebra; ++i) (sl ? p.w2 : p.w).p[i] = out + (size_t)i * per;
     }
     p.wt = 1;
-    const TileCfg c = pick_cfg(p.Cdst, p.Ptot);
-    if (!hc_conv_vec_try(p, MODE_DGRAD, c.ct, c.pt, (hipStream_t)stream)) return SELD_EUNSUPPORTED;
-    return check_launch();
+    return run_conv(p, (hipStream_t)stream);
 }
 
 // Label of the kernel symbol a call would launch (as rocprofv3 prints the template arguments);
@@ -799,32 +829,17 @@ extern "C" int seld_hc_conv_pair_bwd_data(const seld_conv_desc* d, const float* 
 extern "C" int seld_hc_conv_kernel_label(const seld_conv_desc* d, int32_t which, char* buf, int32_t buflen) {
     int rc = hc_validate(d);
     if (rc || !buf || buflen < 48) return SELD_EINVAL;
-    if (which == 2) return hc_wgrad_label(d, buf, buflen);
-    int kh = d->k[0], kw = d->k[1];
-    if (!((kh == 1 && kw == 1) || (kh == 1 && kw == 3) || (kh == 3 && kw == 3))) kh = kw = 0;
     int o[2];
     hc_out_shape(d, o);
+    if (o[0] <= 0 || o[1] <= 0) return SELD_EINVAL;
+    if (which == 2) return hc_wgrad_label(d, buf, buflen);
     ConvP p{};
     if (which == 0) fill_fwd(p, d, nullptr, o);
     else { fill_dgrad(p, d, nullptr, o); p.wt = 1; }          // the host mirror always supplies the transposed-weight workspace
-    const long long P = p.Ptot;
-    if (which == 0 && d->stride[0] == 1 && d->stride[1] == 1) {
-        int dummy;
-        const int ct = hc_conv_smallk_try(p, nullptr, &dummy, 1);
-        if (ct) {
-            const bool t33 = d->k[0] == 3 && d->k[1] == 3, t13 = d->k[0] == 1 && d->k[1] == 3;
-            snprintf(buf, buflen, "hc_conv_smallk_kernel<%d, %d, %d>", ct, t33 ? 3 : (t13 ? 1 : 0), (t33 || t13) ? 3 : 0);
-            return SELD_OK;
-        }
-    }
-    const TileCfg c = pick_cfg(which == 0 ? d->Cout : d->Cin, P);
-    if (const int kc = hc_conv_vec_chunk(p, which, c.ct, c.pt)) {
-        snprintf(buf, buflen, "hc_conv_vec_kernel<%d, %d, %d, %d, %d, %d, %d>", c.ct, c.pt, kh, kw, which, kc, 0);
-        return SELD_OK;
-    }
-    const int CKl = ((which == 0 ? d->Cin : d->Cout) / d->algebra) * d->k[0] * d->k[1];
-    const bool fast = (CKl % 4 == 0) && CKl >= 16 && (which == 0 || (d->stride[0] == 1 && d->stride[1] == 1)) && kh != 0 &&
-                      !env().conv_nofast;
-    snprintf(buf, buflen, "hc_conv_kernel<%d, %d, %d, %d, %d, %d>", c.ct, c.pt, fast ? kh : 0, fast ? kw : 0, which, fast ? 1 : 0);
+    const ConvPlan pl = hc_conv_plan(p, true);
+    if (pl.kind == ConvPlan::SMALLK) snprintf(buf, buflen, "hc_conv_smallk_kernel<%d, %d, %d>", pl.ct, pl.kh, pl.kw);
+    else if (pl.kind == ConvPlan::VEC)
+        snprintf(buf, buflen, "hc_conv_vec_kernel<%d, %d, %d, %d, %d, %d, %d>", pl.ct, pl.pt, pl.kh, pl.kw, which, pl.kc, pl.pair);
+    else snprintf(buf, buflen, "hc_conv_kernel<%d, %d, %d, %d, %d, %d>", pl.ct, pl.pt, pl.kh, pl.kw, which, pl.fast);
     return SELD_OK;
 }

@@ -18,9 +18,9 @@
 
 namespace seld {
 
-// Waves per workgroup.  4-wave workgroups, two per CU (each with its own copy of the weights in LDS), run out of
-// phase with each other, so one workgroup's stores / gathers hide under the other's MFMAs; an 8-wave workgroup
-// per CU keeps its two waves per SIMD in lock-step.  SELD_SMALLK_NW=8 selects the latter (tuning aid).
+// Waves per workgroup: SK_NW = 4 is the one instantiation.  4-wave workgroups, two per CU (each with its own copy of
+// the weights in LDS), run out of phase with each other, so one workgroup's stores / gathers hide under the other's MFMAs;
+// an 8-wave workgroup per CU kept its two waves per SIMD in lock-step and measured slower.
 // Workgroup barrier that orders LDS traffic only.  __syncthreads() is a workgroup-scope fence over ALL address spaces: on
 // gfx9 it waits vmcnt(0), i.e. for the write acknowledgement of every global store the wave has in flight -- in a loop
 // that stores 12 KB per wave per tile that wait was a third of the kernel.  The image in LDS is the only data the waves
@@ -198,9 +198,6 @@ __global__ __launch_bounds__(SK_NW * 64, (SK_NW == 8 && NG_T) ? 4 : 1) void hc_c
         bias_t[t] = (SPLIT && p.bias) ? p.bias[ch] : 0.f;
     }
 
-    // experiment switches (wt is unused by the forward): 1 = no stores, 2 = no gathers, 4 = store after the LDS refill;
-    // the compile-time-shaped instantiation keeps only bit 4
-    const int dbg = NG_T ? (p.wt & 4) : p.wt;
     // Workgroups go round-robin to the 8 XCDs (one L2 each).  seq -> tile gives every XCD a contiguous range of position
     // tiles, so that the 64-position pieces of one 2 KB output row are written back by one L2 instead of eight.
     const bool xcd_ranges = ((ntiles | (long long)gridDim.x) & 7) == 0;
@@ -219,7 +216,7 @@ __global__ __launch_bounds__(SK_NW * 64, (SK_NW == 8 && NG_T) ? 4 : 1) void hc_c
         const long long next = has_next ? tile_of(seq + gridDim.x) : tile;
         if constexpr (SPLIT) gather_split(next);
         else if (NG_T) gather(next);                                 // unconditional: keeps the loop body one block
-        else if (has_next && !(dbg & 2)) gather(next);
+        else if (has_next) gather(next);
 
         floatx4 acc[CT];                                   // SPLIT: acc[sub * 2 QT + t], t < QT primal, t >= QT dual
 #pragma unroll
@@ -289,12 +286,12 @@ __global__ __launch_bounds__(SK_NW * 64, (SK_NW == 8 && NG_T) ? 4 : 1) void hc_c
                     const float4 o0 = make_float4(c0[0], c0[1], c0[2], c0[3]);
                     const float4 o1 = make_float4(c1[0], c1[1], c1[2], c1[3]);
                     if (ok0) {
-                        if (!(dbg & 1)) *reinterpret_cast<float4*>(drow + (size_t)ch * p.dstS) = o0;
+                        *reinterpret_cast<float4*>(drow + (size_t)ch * p.dstS) = o0;
                         s1[t] += (o0.x + o0.y) + (o0.z + o0.w);
                         s2[t] += (o0.x * o0.x + o0.y * o0.y) + (o0.z * o0.z + o0.w * o0.w);
                     }
                     if (ok1) {
-                        if (!(dbg & 1)) *reinterpret_cast<float4*>(drow + (size_t)ch * p.dstS + 16) = o1;
+                        *reinterpret_cast<float4*>(drow + (size_t)ch * p.dstS + 16) = o1;
                         s1[t] += (o1.x + o1.y) + (o1.z + o1.w);
                         s2[t] += (o1.x * o1.x + o1.y * o1.y) + (o1.z * o1.z + o1.w * o1.w);
                     }
@@ -312,14 +309,15 @@ __global__ __launch_bounds__(SK_NW * 64, (SK_NW == 8 && NG_T) ? 4 : 1) void hc_c
                     const int ch = j * 16 + fr;
                     const float bvv = p.bias ? p.bias[ch] : 0.f;
                     const float4 o = make_float4(acc[j][0] + bvv, acc[j][1] + bvv, acc[j][2] + bvv, acc[j][3] + bvv);
-                    if (!(dbg & 1)) *reinterpret_cast<float4*>(drow + (size_t)ch * p.dstS) = o;
+                    *reinterpret_cast<float4*>(drow + (size_t)ch * p.dstS) = o;
                     s1[j] += (o.x + o.y) + (o.z + o.w);
                     s2[j] += (o.x * o.x + o.y * o.y) + (o.z * o.z + o.w * o.w);
                 }
             }
         };
-        if (!(dbg & 4)) store_tile();
-        // (SELD_SMALLK_DBG bit 4 stores AFTER the LDS refill instead: 656 vs 648 us.)  What keeps stores, gathers and MFMAs
+        __builtin_amdgcn_sched_barrier(0);       // the tile's MFMAs first: scheduled into them, the stores cost the first-layer form 8 VGPRs
+        store_tile();
+        // (Storing AFTER the LDS refill instead measured 656 vs 648 us.)  What keeps stores, gathers and MFMAs
         // from overlapping is visible in the ISA: the first LDS operand reads of the next tile reuse the VGPRs that held this
         // tile's store addresses / data, and the compiler guards that reuse with s_waitcnt vmcnt(..) -- the next tile's MFMAs
         // start only when this tile's stores are acknowledged.  Stores straight from a second, alternating accumulator set
@@ -333,8 +331,6 @@ __global__ __launch_bounds__(SK_NW * 64, (SK_NW == 8 && NG_T) ? 4 : 1) void hc_c
             if (has_next) scatter(0);
             lds_barrier();
         }
-
-        if (dbg & 4) store_tile();
     }
 
     if (p.epilogue & SELD_EPI_STATS) {
@@ -379,19 +375,28 @@ __global__ __launch_bounds__(SK_NW * 64, (SK_NW == 8 && NG_T) ? 4 : 1) void hc_c
     }
 }
 
+// k-groups of 4 taps: NG in all, the first NGP needed by every channel tile (the rest lie in the dual quaternion's
+// structurally-zero K half of the primal channels)
+static void smallk_groups(const ConvP& p, int* NG, int* NGP) {
+    *NG = (p.Ktot + 3) / 4;
+    *NGP = *NG;
+    if (p.algebra == 8 && (p.Ktot / 2) % 4 == 0 && (p.Cdst / 2) % 16 == 0) *NGP = p.Ktot / 8;
+}
+
 template <int CT, int NW>
-static int launch_smallk(const ConvP& p, int NG, int NGP, hipStream_t st) {
+static int launch_smallk(const ConvP& p, hipStream_t st) {
     constexpr int TP = SkGeom<NW>::TP, NT = SkGeom<NW>::NT;
+    int NG, NGP;
+    smallk_groups(p, &NG, &NGP);
     const long long ntiles = (p.Ptot + TP - 1) / TP;
-    const size_t smem_generic = ((size_t)NG * CT * 16 * 4 + (size_t)(NW == 8 ? 2 : 1) * NG * TP * 4) * sizeof(float);
+    const size_t smem_generic = ((size_t)NG * CT * 16 * 4 + (size_t)NG * TP * 4) * sizeof(float);
 #define SELD_SK(KH_, KW_, NG_, NGP_)                                                                               \
     do {                                                                                                           \
         auto kern = hc_conv_smallk_kernel<CT, KH_, KW_, NW, NG_, NGP_>;                                            \
         constexpr bool split = NG_ && (NGP_ * 2 == NG_) && (CT % 4 == 0);                                          \
         const size_t smem = split ? ((size_t)(NGP_ * CT * 16 + (NG_ - NGP_) * CT * 8) * 4 + (size_t)NG_ * TP * 4) * sizeof(float) \
                                   : smem_generic;                                                                   \
-        long long want = (split || NW == 4) ? 512 : 256;       /* two workgroups per CU, or one 8-wave workgroup */   \
-        if (env().smallk_wgs) want = env().smallk_wgs;                                                             \
+        const long long want = 512;                            /* two workgroups per CU */                          \
         const unsigned grid = (unsigned)(ntiles < want ? ntiles : want);                                           \
         if (smem > 64 * 1024 &&                                                                                    \
             hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) \
@@ -407,36 +412,26 @@ static int launch_smallk(const ConvP& p, int NG, int NGP, hipStream_t st) {
     return check_launch();
 }
 
-// Returns the channel-tile count if the call is (dry_run: would be) handled here (rc in *rc), 0 if the general
-// kernel must be used.
-int hc_conv_smallk_try(const ConvP& p, hipStream_t st, int* rc, int dry_run) {
+// The channel-tile count (12 / 8 / 4) if this call runs here, 0 if it belongs to the tiled kernels.
+int hc_conv_smallk_ct(const ConvP& p) {
     if (env().conv_no_smallk) return 0;
     if (p.mode != MODE_FWD || p.SDh != 1 || p.SDw != 1 || p.SMh != 1 || p.SMw != 1) return 0;
     if (p.Ktot > 160 || (p.epilogue & ~SELD_EPI_STATS)) return 0;
     if (p.dstS % 4 || p.Ptot >= (1LL << 31) || p.src_elems * 4 >= (1LL << 32)) return 0;
     if (p.Ptot < 256 * 128) return 0;                         // not worth a persistent launch
-    const int NG = (p.Ktot + 3) / 4;
-    int NGP = NG;                                             // groups needed by every tile
-    if (p.algebra == 8 && (p.Ktot / 2) % 4 == 0 && (p.Cdst / 2) % 16 == 0) NGP = p.Ktot / 8;
-    int ct = 0;
-    if (p.Cdst == 192) ct = 12;
-    else if (p.Cdst == 128) ct = 8;
-    else if (p.Cdst == 64) ct = 4;
-    else return 0;
-    const int nw = env().smallk_nw;        // 8 only in -DSELD_TUNING builds (untested tuning variant)
-    const size_t smem = ((size_t)NG * ct * 16 * 4 + (size_t)(nw == 8 ? 2 : 1) * NG * nw * 16 * 4) * sizeof(float);
-    if (smem * (8 / nw) > 156 * 1024) return 0;
-    if (dry_run) return ct;
-    if (nw == 8) {
-        if (ct == 12) *rc = launch_smallk<12, 8>(p, NG, NGP, st);
-        else if (ct == 8) *rc = launch_smallk<8, 8>(p, NG, NGP, st);
-        else *rc = launch_smallk<4, 8>(p, NG, NGP, st);
-    } else {
-        if (ct == 12) *rc = launch_smallk<12, 4>(p, NG, NGP, st);
-        else if (ct == 8) *rc = launch_smallk<8, 4>(p, NG, NGP, st);
-        else *rc = launch_smallk<4, 4>(p, NG, NGP, st);
-    }
-    return ct;
+    const int ct = p.Cdst == 192 ? 12 : (p.Cdst == 128 ? 8 : (p.Cdst == 64 ? 4 : 0));
+    if (!ct) return 0;
+    int NG, NGP;
+    smallk_groups(p, &NG, &NGP);
+    // weight image + one 64-position im2col image, two workgroups per CU
+    const size_t smem = ((size_t)NG * ct * 16 * 4 + (size_t)NG * SkGeom<4>::TP * 4) * sizeof(float);
+    return 2 * smem > 156 * 1024 ? 0 : ct;
+}
+
+int hc_conv_smallk_launch(const ConvP& p, int ct, hipStream_t st) {
+    if (ct == 12) return launch_smallk<12, 4>(p, st);
+    if (ct == 8) return launch_smallk<8, 4>(p, st);
+    return launch_smallk<4, 4>(p, st);
 }
 
 }  // namespace seld

@@ -24,7 +24,7 @@
 // (masked) except at the very start / end of the tensor, where part of the access would fall outside the buffer
 // descriptor; workgroups that can reach those rows ("edge" workgroups, wave-uniform) gather per element instead.
 //
-// Eligibility is checked by hc_conv_vec_try(); everything else runs on hc_conv_kernel.
+// Eligibility is hc_conv_vec_chunk(), which hc_conv_plan (hc_conv_fwd.hip) asks; everything else runs on hc_conv_kernel.
 #include <type_traits>
 #include "hc_common.h"
 
@@ -135,11 +135,10 @@ __global__ __launch_bounds__(256) void hc_conv_vec_kernel(const ConvP p) {
         if (p.skip_mode == 1 && c0 + BC <= half_c) kend = half_k;      // all channels primal
         if (p.skip_mode == 2 && c0 >= half_c) kbeg = half_k;           // all channels dual
     }
-    // p.pairing carries SELD_VEC_DBG (timing experiments, wrong results): 4 = one chunk only, 8 = no epilogue stores,
-    // 16 = return after the setup, 32 = return after staging the first chunk.  On the 1x3 TCN layer (74 us): launch +
-    // setup 2.6 us, first load round trip 2.7, first iteration 4.7 (cold), output write-back 4.5, 23 more iterations 2.4 each
-    const int nchunks = (p.pairing & 4) ? 1 : (kend - kbeg) / KC;
-    const bool mixed_wg = !(p.pairing & 4) && halves_aligned && (CT % 2 == 0) && (c0 + BC / 2 == half_c);
+    // (Where the time goes on the 1x3 TCN layer, 74 us: launch + setup 2.6 us, first load round trip 2.7, first iteration
+    // 4.7 (cold), output write-back 4.5, 23 more iterations 2.4 each.)
+    const int nchunks = (kend - kbeg) / KC;
+    const bool mixed_wg = halves_aligned && (CT % 2 == 0) && (c0 + BC / 2 == half_c);
 
     // ---- X items: everything but the channel advance is loop-invariant ----------------------------------------
     const int quad = tid % QP;
@@ -297,7 +296,6 @@ __global__ __launch_bounds__(256) void hc_conv_vec_kernel(const ConvP p) {
     const int fk = lane >> 4;      // k group of this lane
 
     __syncthreads();               // wdelta_s visible
-    if (p.pairing & 16) return;    // SELD_VEC_DBG timing experiment: setup only
     using ETrue = std::integral_constant<bool, true>;
     using EFalse = std::integral_constant<bool, false>;
     if (nchunks > 0) {
@@ -306,7 +304,6 @@ __global__ __launch_bounds__(256) void hc_conv_vec_kernel(const ConvP p) {
         store_chunk(0);
     }
     __syncthreads();
-    if (p.pairing & 32) return;    // SELD_VEC_DBG timing experiment: setup + first chunk staged
 
     // One chunk: [component switch, rare] then ONE basic block -- prefetch of the next chunk into registers, the
     // MFMAs of this one, the registers to the other LDS buffer, barrier.  The prefetch after the last chunk reads
@@ -420,7 +417,7 @@ __global__ __launch_bounds__(256) void hc_conv_vec_kernel(const ConvP p) {
             for (int i = 0; i < PT; ++i) {
                 const long long pos = p0 + wave * (PT * 16) + i * 16 + fk * 4;
                 const floatx4 v = acc[i][j];
-                if (chok && pos < p.Ptot && !(p.pairing & 8)) {
+                if (chok && pos < p.Ptot) {
                     const size_t off = (size_t)(poff[i] + ch * p.dstS);
                     float4 o = make_float4(v[0] + bvv, v[1] + bvv, v[2] + bvv, v[3] + bvv);
                     if (epi & SELD_EPI_ADD) {
@@ -514,40 +511,36 @@ __global__ __launch_bounds__(256) void hc_conv_vec_kernel(const ConvP p) {
 }
 
 // Can this problem run on the vector-staging kernel with tile (ct, pt)?  Returns the K chunk (36 / 24) or 0.
-int hc_conv_vec_chunk(const ConvP& p, int mode, int ct, int pt) {
-    if (env().conv_novec) return 0;
+int hc_conv_vec_chunk(const ConvP& p, int ct, int pt) {
     if (!(ct == 12 || ct == 6) || pt != 1) return 0;
     if (p.nslots > 1 && p.KH != 1) return 0;                            // pairs: 1-D layers
-    if (p.nslots > 1 && mode == MODE_FWD && p.KW != 1) return 0;       // forward pairs: 1x1 layers
-    if (!(mode == MODE_FWD || p.wt)) return 0;
+    if (p.nslots > 1 && p.mode == MODE_FWD && p.KW != 1) return 0;     // forward pairs: 1x1 layers
+    if (!(p.mode == MODE_FWD || p.wt)) return 0;
     if (p.SDh != 1 || p.SDw != 1 || p.SMh != 1 || p.SMw != 1) return 0;
     if (p.dstW % 4 != 0) return 0;
     const bool t11 = p.KH == 1 && p.KW == 1, t13 = p.KH == 1 && p.KW == 3, t33 = p.KH == 3 && p.KW == 3;
     if (!(t11 || t13 || t33)) return 0;
-    const int ck = (mode == MODE_FWD ? p.IA : p.OA) * p.KH * p.KW;
+    const int ck = (p.mode == MODE_FWD ? p.IA : p.OA) * p.KH * p.KW;
     if (t33) return ck % 36 == 0 ? 36 : 0;          // (36-deep chunks on the 1x3 layers: measured 15 % slower forward)
     return ck % 24 == 0 ? 24 : 0;
-    return 0;
 }
 
 template <int CT, int MODE>
-static void launch_vec(const ConvP& p, hipStream_t st) {
+static void launch_vec(const ConvP& p, const ConvPlan& pl, hipStream_t st) {
     constexpr int BC = CT * 16, BP = 64;
     dim3 grid((unsigned)((p.Ptot + BP - 1) / BP), (unsigned)((p.Cdst + BC - 1) / BC), 1);
     constexpr int DG = (MODE == MODE_DGRAD) ? 1 : 0;
-    if (p.KH == 3) hipLaunchKernelGGL((hc_conv_vec_kernel<CT, 1, 3, 3, MODE, 36, 0>), grid, dim3(256), 0, st, p);
-    else if (DG && p.nslots > 1 && p.KW == 3) hipLaunchKernelGGL((hc_conv_vec_kernel<CT, 1, 1, 3, MODE, 24, DG>), grid, dim3(256), 0, st, p);
-    else if (p.nslots > 1) hipLaunchKernelGGL((hc_conv_vec_kernel<CT, 1, 1, 1, MODE, 24, 1>), grid, dim3(256), 0, st, p);
-    else if (p.KW == 3) hipLaunchKernelGGL((hc_conv_vec_kernel<CT, 1, 1, 3, MODE, 24, 0>), grid, dim3(256), 0, st, p);
+    if (pl.kh == 3) hipLaunchKernelGGL((hc_conv_vec_kernel<CT, 1, 3, 3, MODE, 36, 0>), grid, dim3(256), 0, st, p);
+    else if (DG && pl.pair && pl.kw == 3) hipLaunchKernelGGL((hc_conv_vec_kernel<CT, 1, 1, 3, MODE, 24, DG>), grid, dim3(256), 0, st, p);
+    else if (pl.pair) hipLaunchKernelGGL((hc_conv_vec_kernel<CT, 1, 1, 1, MODE, 24, 1>), grid, dim3(256), 0, st, p);
+    else if (pl.kw == 3) hipLaunchKernelGGL((hc_conv_vec_kernel<CT, 1, 1, 3, MODE, 24, 0>), grid, dim3(256), 0, st, p);
     else hipLaunchKernelGGL((hc_conv_vec_kernel<CT, 1, 1, 1, MODE, 24, 0>), grid, dim3(256), 0, st, p);
 }
 
-// Launches when eligible (returns 1), otherwise returns 0 and the caller falls back to hc_conv_kernel.
-int hc_conv_vec_try(const ConvP& p_in, int mode, int ct, int pt, hipStream_t st) {
-    const int kc = hc_conv_vec_chunk(p_in, mode, ct, pt);
-    if (!kc) return 0;
+// Launches a ConvPlan::VEC plan (returns 1).  Returns 0 without launching when the component tensors lie too far apart:
+// the caller falls back to hc_conv_kernel.
+int hc_conv_vec_launch(const ConvP& p_in, const ConvPlan& pl, hipStream_t st) {
     ConvP p = p_in;
-    p.pairing = env().vec_dbg;          // non-zero only in -DSELD_TUNING builds (timing experiments, wrong results)
     // the component tensors are addressed as wmin + 32-bit byte offset: they must lie within 4 GB of each other
     const size_t comp_bytes = (size_t)p.OA * p.IA * p.KH * p.KW * sizeof(float);
     uintptr_t lo = UINTPTR_MAX, hi = 0;
@@ -562,12 +555,12 @@ int hc_conv_vec_try(const ConvP& p_in, int mode, int ct, int pt, hipStream_t st)
     p.wmin = (const float*)lo;
     p.wspan = (unsigned)(hi - lo + comp_bytes);
 
-    if (mode == MODE_FWD) {
-        if (ct == 12) launch_vec<12, MODE_FWD>(p, st);
-        else launch_vec<6, MODE_FWD>(p, st);
+    if (p.mode == MODE_FWD) {
+        if (pl.ct == 12) launch_vec<12, MODE_FWD>(p, pl, st);
+        else launch_vec<6, MODE_FWD>(p, pl, st);
     } else {
-        if (ct == 12) launch_vec<12, MODE_DGRAD>(p, st);
-        else launch_vec<6, MODE_DGRAD>(p, st);
+        if (pl.ct == 12) launch_vec<12, MODE_DGRAD>(p, pl, st);
+        else launch_vec<6, MODE_DGRAD>(p, pl, st);
     }
     return 1;
 }

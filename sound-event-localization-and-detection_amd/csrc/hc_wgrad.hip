@@ -435,7 +435,7 @@ __global__ void zero_many_kernel(const ZeroP z) {
 // active workgroups (tiles outside the dual-quaternion zero quadrant) still fit in one generation -- 21 tiles x 25
 // splits = 525 workgroups on 512 slots take twice as long as 21 x 24 (measured: 2088 vs 1422 us on the 3x3 layer).
 // Short reductions are split less (at least 512 positions per workgroup) and then run several generations deep.
-static int wgrad_splits(const seld_conv_desc* d, int o[2], int bm, int bn, WgradP* p) {
+static int wgrad_splits(const seld_conv_desc* d, const int o[2], int bm, int bn, WgradP* p) {
     long long* split_len = &p->split_len;
     const long long Ptot = (long long)d->N * o[0] * o[1];
     const long long Ktot = (long long)d->Cin * d->k[0] * d->k[1];
@@ -449,8 +449,7 @@ static int wgrad_splits(const seld_conv_desc* d, int o[2], int bm, int bn, Wgrad
         if (nz > 0 && mz > 0) { p->mz = (int)mz; p->nact = (int)(nt - nz); tiles -= mz * nz; }
     }
     // resident workgroups per CU (LDS-limited): 128x128 / 192x80 / 96x128 / 64x160 -> 2, 64x80 -> 3, 64x64 -> 4
-    long long slots = (bm == 64 ? (bn == 64 ? 4 : (bn == 80 ? 3 : 2)) : 2) * 256;
-    if (env().wgrad_wgs) slots = env().wgrad_wgs;
+    const long long slots = (bm == 64 ? (bn == 64 ? 4 : (bn == 80 ? 3 : 2)) : 2) * 256;
     tiles *= (p->nslots > 1 ? 2 : 1);                     // a pair launch carries two gradients
     long long want = slots / tiles;                       // floor: stay within one generation
     if (env().deterministic) want = 1;                    // one position range per tile: a single contribution per element
@@ -466,13 +465,12 @@ static int wgrad_splits(const seld_conv_desc* d, int o[2], int bm, int bn, Wgrad
     return ns < 1 ? 1 : ns;
 }
 
-// tile configuration: 0 = 128 x 128 (waves 2 x 2), 1 = 192 x 80 for short K (first layer), 2 = 64 x 64 (small layers),
+// tile configuration (index into WGRAD_TILES): 0 = 128 x 128 (waves 2 x 2), 1 = 192 x 80 for short K (first layer), 2 = 64 x 64 (small layers),
 // 3 = 96 x 128, 4 = 64 x 80 (short K: a third of the float-atomic chain per gradient element of 192 x 80, x re-read 3x),
 // 5 = 64 x 160 (the 16-channel first layer, K = 144: ONE column tile, so the 0.8-1.6 GB dy / y operand is read once --
 // with 64 x 64 tiles it was read three times: 744 us at batch 16)
 static int wgrad_cfg(const seld_conv_desc* d) {
     const int Ktot = d->Cin * d->k[0] * d->k[1];
-    if (env().wgrad_cfg >= 0) return env().wgrad_cfg;     // tuning aid, validated 0..5
     if (Ktot <= 80 && d->Cout > 64) return (d->Cout % 64 == 0) ? 4 : 1;
     if (Ktot <= 160 && d->Cout > 64 && d->Cout % 64 == 0) return 5;
     if (d->Cout <= 64 || Ktot <= 64) return 2;
@@ -493,8 +491,24 @@ static int wgrad_cfg(const seld_conv_desc* d) {
 bool hc_wgrad_row_ok(const WgradP& p);
 void hc_wgrad_row_launch(const WgradP& p, int cfg, hipStream_t st);
 
-static bool wgrad_fast_ok(const WgradP& p) {
-    return (p.outW % 4 == 0) && p.outW >= 32 && p.sw == 1 && !env().wgrad_slow;
+// hc_wgrad32_kernel (32 positions of one output row per step) instead of hc_wgrad_kernel
+static bool wgrad_fast_ok(const WgradP& p) { return (p.outW % 4 == 0) && p.outW >= 32 && p.sw == 1; }
+
+// Geometry of one weight-gradient call over the output extent o, its tile configuration (returned) and its position
+// splits: everything the launch, the label and the pair query decide from.  nslots = 2: a pair launch.
+static int fill_wgrad(WgradP& p, const seld_conv_desc* d, const int o[2], int nslots) {
+    p.algebra = d->algebra; p.N = d->N; p.Cin = d->Cin; p.Cout = d->Cout;
+    p.inH = d->in[0]; p.inW = d->in[1]; p.outH = o[0]; p.outW = o[1];
+    p.KH = d->k[0]; p.KW = d->k[1];
+    p.sh = d->stride[0]; p.sw = d->stride[1]; p.ph = d->pad[0]; p.pw = d->pad[1]; p.dh = d->dil[0]; p.dw = d->dil[1];
+    p.Ktot = d->Cin * p.KH * p.KW;
+    p.OA = d->Cout / d->algebra; p.IA = d->Cin / d->algebra;
+    p.inS = p.inH * p.inW; p.outS = p.outH * p.outW;
+    p.Ptot = (long long)d->N * p.outS;
+    p.nslots = nslots;
+    const int cfg = wgrad_cfg(d);
+    p.nsplit = wgrad_splits(d, o, WGRAD_TILES[cfg].bm(), WGRAD_TILES[cfg].bn(), &p);
+    return cfg;
 }
 
 template <int WRW, int RT, int CTL>
@@ -530,16 +544,8 @@ static int wgrad_run2(const seld_conv_desc* d, const float* x, const float* dy, 
     if (o[0] <= 0 || o[1] <= 0 || !x || !dy || !dw) return SELD_EINVAL;
     if (dy2 && !dw2) return SELD_EINVAL;
     WgradP p{};
-    p.algebra = d->algebra; p.N = d->N; p.Cin = d->Cin; p.Cout = d->Cout;
-    p.inH = d->in[0]; p.inW = d->in[1]; p.outH = o[0]; p.outW = o[1];
-    p.KH = d->k[0]; p.KW = d->k[1];
-    p.sh = d->stride[0]; p.sw = d->stride[1]; p.ph = d->pad[0]; p.pw = d->pad[1]; p.dh = d->dil[0]; p.dw = d->dil[1];
-    p.Ktot = d->Cin * p.KH * p.KW;
-    p.OA = d->Cout / d->algebra; p.IA = d->Cin / d->algebra;
-    p.inS = p.inH * p.inW; p.outS = p.outH * p.outW;
-    p.Ptot = (long long)d->N * p.outS;
+    const int cfg = fill_wgrad(p, d, o, dy2 ? 2 : 1);
     p.x = x; p.dy = dy;
-    p.nslots = dy2 ? 2 : 1;
     p.dy2 = dy2;
     for (int i = 0; i < 8; ++i) {
         p.gw.p[i] = (i < d->algebra) ? dw[i] : nullptr;
@@ -560,17 +566,9 @@ static int wgrad_run2(const seld_conv_desc* d, const float* x, const float* dy, 
             if (rc) return rc;
         }
     }
-    const int cfg = wgrad_cfg(d);
-    static const int tile_m[6] = {128, 192, 64, 96, 64, 64}, tile_n[6] = {128, 80, 64, 128, 80, 160};
-    p.nsplit = wgrad_splits(d, o, tile_m[cfg], tile_n[cfg], &p);
     if (hc_wgrad_row_ok(p)) hc_wgrad_row_launch(p, cfg, st);           // row-chunk staging (hc_wgrad_row.hip)
     else if (dy2) return SELD_EUNSUPPORTED;                            // pairs only on the row kernel
-    else if (cfg == 0) launch_wgrad<2, 4, 4>(p, st);
-    else if (cfg == 1) launch_wgrad<4, 3, 5>(p, st);
-    else if (cfg == 3) launch_wgrad<2, 3, 4>(p, st);
-    else if (cfg == 4) launch_wgrad<4, 1, 5>(p, st);
-    else if (cfg == 5) launch_wgrad<4, 1, 10>(p, st);
-    else launch_wgrad<2, 2, 2>(p, st);
+    else SELD_WGRAD_DISPATCH(cfg, launch_wgrad, p, st)
     rc = check_launch();
     if (rc) return rc;
     for (int sl = 0; sl < p.nslots; ++sl) {
@@ -594,25 +592,22 @@ int hc_wgrad_pair_ok(const seld_conv_desc* d) {
     int o[2];
     hc_out_shape(d, o);
     WgradP p{};
-    p.KH = d->k[0]; p.KW = d->k[1]; p.sw = d->stride[1]; p.outW = o[1]; p.split_len = 32;
-    p.Cout = d->Cout; p.Cin = d->Cin; p.outS = o[0] * o[1]; p.inS = d->in[0] * d->in[1];
+    fill_wgrad(p, d, o, 2);
     return hc_wgrad_row_ok(p) ? 1 : 0;
 }
 
 int hc_wgrad_label(const seld_conv_desc* d, char* buf, int buflen) {
-    int kh = d->k[0], kw = d->k[1];
-    if (!((kh == 1 && kw == 1) || (kh == 1 && kw == 3) || (kh == 3 && kw == 3))) kh = kw = 0;
-    const int cfg = wgrad_cfg(d);
-    const char* t = cfg == 0 ? "2, 4, 4" : (cfg == 1 ? "4, 3, 5" : (cfg == 3 ? "2, 3, 4" : (cfg == 4 ? "4, 1, 5" : (cfg == 5 ? "4, 1, 10" : "2, 2, 2"))));
     int o[2];
     hc_out_shape(d, o);
-    const bool fast = (o[1] % 4 == 0) && o[1] >= 32 && d->stride[1] == 1 && !env().wgrad_slow;
     WgradP p{};
-    p.KH = d->k[0]; p.KW = d->k[1]; p.sw = d->stride[1]; p.outW = o[1]; p.split_len = 32;
-    p.Cout = d->Cout; p.Cin = d->Cin; p.outS = o[0] * o[1]; p.inS = d->in[0] * d->in[1];
-    const bool row = hc_wgrad_row_ok(p);
-    if (row) snprintf(buf, buflen, "hc_wgrad_row_kernel<%s, %d, %d, 0>", t, kh, kw);     // last argument: fused BN/pool backward
-    else snprintf(buf, buflen, "%s<%s, %d, %d>", fast ? "hc_wgrad32_kernel" : "hc_wgrad_kernel", t, kh, kw);
+    const WgradTile t = WGRAD_TILES[fill_wgrad(p, d, o, 1)];
+    const bool taps = (p.KH == 1 && p.KW == 1) || (p.KH == 1 && p.KW == 3) || (p.KH == 3 && p.KW == 3);
+    const int kh = taps ? p.KH : 0, kw = taps ? p.KW : 0;
+    if (hc_wgrad_row_ok(p))     // last argument: fused BN/pool backward
+        snprintf(buf, buflen, "hc_wgrad_row_kernel<%d, %d, %d, %d, %d, 0>", t.wrw, t.rt, t.ctl, kh, kw);
+    else
+        snprintf(buf, buflen, "%s<%d, %d, %d, %d, %d>", wgrad_fast_ok(p) ? "hc_wgrad32_kernel" : "hc_wgrad_kernel", t.wrw,
+                 t.rt, t.ctl, kh, kw);
     return SELD_OK;
 }
 
@@ -647,22 +642,11 @@ extern "C" int seld_hc_conv_bwd_weight_bnpool_drop_acc(const seld_conv_desc* d, 
     if (d->k[0] != 3 || d->k[1] != 3 || o[0] % ph != 0 || (long long)d->Cout * (o[0] / ph) * o[1] >= (1LL << 29))
         return SELD_EUNSUPPORTED;
     WgradP p{};
-    p.algebra = d->algebra; p.N = d->N; p.Cin = d->Cin; p.Cout = d->Cout;
-    p.inH = d->in[0]; p.inW = d->in[1]; p.outH = o[0]; p.outW = o[1];
-    p.KH = d->k[0]; p.KW = d->k[1];
-    p.sh = d->stride[0]; p.sw = d->stride[1]; p.ph = d->pad[0]; p.pw = d->pad[1]; p.dh = d->dil[0]; p.dw = d->dil[1];
-    p.Ktot = d->Cin * p.KH * p.KW;
-    p.OA = d->Cout / d->algebra; p.IA = d->Cin / d->algebra;
-    p.inS = p.inH * p.inW; p.outS = p.outH * p.outW;
-    p.Ptot = (long long)d->N * p.outS;
+    const int cfg = fill_wgrad(p, d, o, 1);
     p.x = x; p.dy = y;
-    p.nslots = 1;
     p.pooled = pooled; p.dpooled = dpooled; p.pidx = idx; p.coef = coef; p.poolh = ph;
     p.drop = DropP{drop_p, 1.0f / (1.0f - drop_p), seed, offset, state};
     for (int i = 0; i < 8; ++i) p.gw.p[i] = (i < d->algebra) ? dw[i] : nullptr;
-    const int cfg = wgrad_cfg(d);
-    static const int tile_m[6] = {128, 192, 64, 96, 64, 64}, tile_n[6] = {128, 80, 64, 128, 80, 160};
-    p.nsplit = wgrad_splits(d, o, tile_m[cfg], tile_n[cfg], &p);
     if (!hc_wgrad_row_ok(p)) return SELD_EUNSUPPORTED;
     hc_wgrad_row_launch(p, cfg, (hipStream_t)stream);
     return check_launch();

@@ -296,12 +296,13 @@ __global__ __launch_bounds__(256) void hc_wgrad_row_kernel(const WgradP p) {
         __syncthreads();
         for (int chunk = 0; chunk < nchunks; ++chunk) {
             const int buf = chunk & 1;
-            if (!(p.dbg & 1)) load_chunk(chunk + 2 < nchunks, S0{});
+            load_chunk(chunk + 2 < nchunks, S0{});
             // The loads must stay at the top and the LDS stores at the bottom of the step: left alone, the scheduler
             // hoists the stores (and their vmcnt wait) to the middle, which leaves the loads 48 MFMAs to land.
             __builtin_amdgcn_sched_barrier(0);
             mfma_step(buf);
-            if (!(p.dbg & 2)) store_chunk(buf ^ 1, S0{});
+            __builtin_amdgcn_sched_barrier(0);       // stores after the MFMAs: mixed in, the 128 x 128 fused form needs > 256 registers
+            store_chunk(buf ^ 1, S0{});
             __syncthreads();
         }
     }
@@ -332,7 +333,6 @@ __global__ __launch_bounds__(256) void hc_wgrad_row_kernel(const WgradP p) {
 }
 
 bool hc_wgrad_row_ok(const WgradP& p) {
-    if (env().wgrad_norow) return false;
     const bool taps = (p.KH == 1 && p.KW == 1) || (p.KH == 1 && p.KW == 3) || (p.KH == 3 && p.KW == 3);
     return taps && p.sw == 1 && (p.outW % 32 == 0) && (p.split_len % 32 == 0) &&
            (long long)p.Cout * p.outS < (1LL << 29) && (long long)p.Cin * p.inS < (1LL << 29);
@@ -348,16 +348,7 @@ static void launch_row(const WgradP& p, hipStream_t st) {
     else hipLaunchKernelGGL((hc_wgrad_row_kernel<WRW, RT, CTL, 1, 1, 0>), grid, dim3(256), 0, st, p);
 }
 
-// cfg as in wgrad_cfg(): 0 = 128 x 128, 1 = 192 x 80, 2 = 64 x 64, 3 = 96 x 128, 4 = 64 x 80, 5 = 64 x 160
-void hc_wgrad_row_launch(const WgradP& p_in, int cfg, hipStream_t st) {
-    WgradP p = p_in;
-    p.dbg = env().wgrad_dbg;            // non-zero only in -DSELD_TUNING builds (timing experiments, wrong results)
-    if (cfg == 0) launch_row<2, 4, 4>(p, st);
-    else if (cfg == 1) launch_row<4, 3, 5>(p, st);
-    else if (cfg == 3) launch_row<2, 3, 4>(p, st);
-    else if (cfg == 4) launch_row<4, 1, 5>(p, st);
-    else if (cfg == 5) launch_row<4, 1, 10>(p, st);
-    else launch_row<2, 2, 2>(p, st);
-}
+// cfg: index into WGRAD_TILES, as wgrad_cfg() picks it
+void hc_wgrad_row_launch(const WgradP& p, int cfg, hipStream_t st) { SELD_WGRAD_DISPATCH(cfg, launch_row, p, st) }
 
 }  // namespace seld

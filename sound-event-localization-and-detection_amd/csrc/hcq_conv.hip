@@ -1273,13 +1273,12 @@ static HcqPlan hcq_plan(const seld_conv_desc* d, int mode, int npair) {
     pl.smem = smem;
     // first layers: one chunk, one channel tile, one weight set -> the row-walking kernel
     constexpr int FIRST_R = 8;
-    if (mode == 0 && taps == 9 && IBC == IB && IB <= 2 && k.ytiles == 1 && nsets == 1 && !mix && Himg % FIRST_R == 0 && wext == 72 &&
-        !env().hcq_no_first) {
+    if (mode == 0 && taps == 9 && IBC == IB && IB <= 2 && k.ytiles == 1 && nsets == 1 && !mix && Himg % FIRST_R == 0 && wext == 72) {
         pl.first_rows = FIRST_R;
         pl.grid = dim3((unsigned)(ptot / 64 / FIRST_R), 1, 1);
         pl.smem = ((size_t)A * IBC * (FIRST_R + 2) * wext + 4 * NT * 4 * 64 * 2) * sizeof(float);   // rows + statistics slots
     }
-    if (pool && (!pl.first_rows || env().hcq_no_pool)) return HcqPlan{};
+    if (pool && !pl.first_rows) return HcqPlan{};
     pl.ok = 1;
     return pl;
 }

@@ -689,7 +689,7 @@ static int gw_num_wgs() {
         else
             n = 256;
     }
-    return env().wgrad_wgs ? (int)env().wgrad_wgs : n;
+    return n;
 }
 
 struct GwPlanKind {

@@ -309,7 +309,7 @@ struct HcqWrPlan {
     size_t ws_bytes;
 };
 
-static long long hcq_wr_slots() { return env().wgrad_wgs ? env().wgrad_wgs : 768; }
+static long long hcq_wr_slots() { return 768; }
 
 static HcqWrPlan hcq_wr_plan(const seld_conv_desc* d, int npair) {
     HcqWrPlan pl{};

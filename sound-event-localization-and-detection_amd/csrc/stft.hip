@@ -282,7 +282,7 @@ extern "C" int seld_stft_magphase_ws(const float* x, int32_t C, int32_t L, int32
     int logN = 0;
     while ((1 << logN) < nperseg) ++logN;
     const int half = nperseg / 2;
-    if (nperseg == 512 && !env().stft_radix2) {
+    if (nperseg == 512) {
         const size_t smem512 = sizeof(float) * ((size_t)3 * 512 + (size_t)4 * 2 * SK512 + (size_t)2 * 257 * (FT512 + 1));
         hipLaunchKernelGGL(stft512_kernel, dim3((frames + FT512 - 1) / FT512, C), dim3(256), smem512, (hipStream_t)stream, x, C, L,
                            nperseg - noverlap, frames, output_phase, cut_dc ? 1 : 0, window, out);

@@ -1,0 +1,192 @@
+"""Writes tests/golden/conv_dispatch.json: what the host-only queries of the block-matrix convolution family answer
+over a fixed descriptor grid -- output shape, kernel labels, pair support, data-gradient workspace and the transposed
+convolution's labels.  None of them touches a device.
+
+The fixture pins the dispatch: it is written ONCE, by the library of the commit that precedes a change to the launch
+plans, and tests/test_conv_dispatch_host.py holds every later build to it row by row.  Re-run it only when a dispatch
+change is intended:
+
+    python tests/golden/make_golden_conv_dispatch.py
+
+Layout (plain JSON, one line per field).  An answer has 13 fields: rc and H, W of seld_hc_conv_out_shape, three
+[rc, label] of seld_hc_conv_kernel_label, three answers of seld_hc_conv_pair_supported, the workspace bytes, three
+[rc, label] of seld_hc_conv_transpose_kernel_label (a descriptor the library refuses has rc alone).  Each field is stored as
+a column over the descriptors in the order `descriptors()` yields them: "values" are the distinct values, "blocks" the
+distinct runs of BLOCK consecutive descriptors (indices into "values"; BLOCK = the two innermost loops of the grid), and
+"envs" gives per environment the block indices, run-length coded as [index, count, index, count, ...] -- an environment
+that is absent there answers as "default" does.
+"""
+import ctypes
+import importlib
+import itertools
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+OUT = os.path.join(ROOT, "tests", "golden", "conv_dispatch.json")
+PKG = "sound-event-localization-and-detection_amd"
+
+ALGEBRAS = (1, 4, 8)
+CHANNELS = ((8, 192), (16, 192), (192, 192), (192, 384), (384, 192), (384, 384), (64, 64), (24, 48), (96, 32))
+KERNELS = ((1, 1), (1, 3), (3, 3), (1, 5), (2, 2))
+STRIDES = (1, 2)
+DILATIONS = (1, 5)
+SPATIAL = ((1, 512), (1, 40), (1, 100), (8, 512), (128, 512), (6, 16))
+BATCHES = (2, 16, 32)
+
+# Rows beyond the product grid, each for a branch the grid does not reach:
+# (algebra, Cin, Cout, k, stride, dilation, padding, in, N)
+EXTRA = (
+    (8, 192, 192, (3, 3), (2, 1), (1, 1), (1, 1), (8, 512), 16),      # row-chunk weight gradient with sh = 2, sw = 1
+    (8, 192, 192, (1, 3), (1, 2), (1, 1), (0, 1), (1, 512), 16),      # strided W only
+    (8, 192, 192, (1, 3), (1, 1), (1, 1), (0, 0), (1, 514), 16),      # valid padding, 512 outputs from 514 samples
+    (8, 192, 192, (1, 3), (1, 1), (1, 1), (0, 2), (1, 510), 16),      # output longer than the input
+    (8, 128, 128, (1, 1), (1, 1), (1, 1), (0, 0), (64, 512), 2),      # small-K: 8 channel tiles
+    (4, 16, 128, (3, 3), (1, 1), (1, 1), (1, 1), (64, 512), 2),       # small-K: 128 output channels, quaternion
+    (8, 8, 64, (3, 3), (1, 1), (1, 1), (1, 1), (128, 512), 2),        # small-K: 4 channel tiles
+    (8, 8, 192, (3, 3), (1, 1), (2, 1), (2, 1), (128, 512), 2),       # first layer with a dilated H: not the shaped instance
+    (8, 48, 192, (1, 3), (1, 1), (1, 1), (0, 1), (64, 512), 2),       # K = 144 <= 160 on the 1x3 small-K instance
+    (1, 192, 192, (1, 1), (1, 1), (1, 1), (0, 0), (1, 4), 1),         # four positions in all
+    (8, 200, 200, (1, 3), (1, 1), (1, 1), (0, 1), (1, 512), 16),      # component extent 75: no 16-byte weight rows
+    (8, 16, 16, (1, 3), (1, 1), (1, 1), (0, 1), (1, 512), 16),        # component extent 6 < 16
+    (8, 192, 192, (1, 3), (1, 1), (1, 1), (0, 1), (1, 36), 16),       # outW % 4 == 0, >= 32, % 32 != 0: hc_wgrad32_kernel
+    (8, 192, 192, (1, 3), (1, 1), (1, 1), (0, 1), (1, 28), 16),       # outW % 4 == 0, < 32: hc_wgrad_kernel
+    (8, 8, 96, (3, 3), (1, 1), (1, 1), (1, 1), (128, 512), 2),        # weight-gradient tile 1 (short K, Cout % 64 != 0)
+    (8, 192, 256, (1, 3), (1, 1), (1, 1), (0, 1), (1, 512), 32),      # weight-gradient tile 0 (Cout/2 % 96 != 0)
+)
+
+CONV_CFGS = ("12,1", "12,2", "6,1", "4,4", "2,4", "1,4")          # the candidates of pick_cfg (hc_conv_fwd.hip)
+ENVS = [("default", {}), ("SELD_CONV_NO_HCQ=1", {"SELD_CONV_NO_HCQ": "1"})] + \
+       [("SELD_CONV_CFG=" + c, {"SELD_CONV_CFG": c}) for c in CONV_CFGS]
+SWITCHES = ("SELD_CONV_NO_HCQ", "SELD_CONV_CFG")
+
+
+def descriptors():
+    """(algebra, Cin, Cout, k, stride, dilation, padding, in, N) of every row, in the fixture's order.  The product grid
+    pads like the model's layers do: d * (k - 1) // 2 on each axis."""
+    for A, (ci, co), k, s, d, hw, n in itertools.product(ALGEBRAS, CHANNELS, KERNELS, STRIDES, DILATIONS, SPATIAL, BATCHES):
+        yield A, ci, co, k, (s, s), (d, d), (d * (k[0] - 1) // 2, d * (k[1] - 1) // 2), hw, n
+    yield from EXTRA
+
+
+def _label(fn, *args):
+    buf = ctypes.create_string_buffer(96)
+    rc = fn(*args, buf, 96)
+    return [rc, buf.value.decode() if rc == 0 else ""]
+
+
+def answers(L, H, row):
+    """Everything the library says about one descriptor, as a JSON-ready list."""
+    A, ci, co, k, s, d, p, hw, n = row
+    lib = L.lib()
+    desc = H.make_conv_desc((n, ci) + tuple(hw), co, A, k, s, p, d)
+    ref = ctypes.byref(desc)
+    out = (ctypes.c_int32 * 2)()
+    rc = lib.seld_hc_conv_out_shape(ref, out)
+    if rc != 0:
+        return [rc]                                                # hc_validate (or an empty output) refuses the row
+    got = [rc, out[0], out[1]]
+    got += [_label(lib.seld_hc_conv_kernel_label, ref, w) for w in (0, 1, 2)]
+    got += [int(lib.seld_hc_conv_pair_supported(ref, w)) for w in (0, 1, 2)]
+    got.append(int(lib.seld_hc_conv_bwd_data_workspace(ref)))
+    zero = (ctypes.c_int32 * 2)(0, 0)
+    got += [_label(lib.seld_hc_conv_transpose_kernel_label, ref, zero, w) for w in (0, 1, 2)]
+    return got
+
+
+def walk(setenv):
+    """{environment name: [answers(row) for every descriptor]} from the built library.  `setenv(name, value or None)` sets
+    or removes one switch and makes the library re-read its environment."""
+    P = importlib.import_module(PKG)
+    L, H = P._lib, P.hip_ops
+    rows = list(descriptors())
+    got = {}
+    for name, switches in ENVS:
+        for sw in SWITCHES:
+            setenv(sw, switches.get(sw))
+        got[name] = [answers(L, H, row) for row in rows]
+    for sw in SWITCHES:
+        setenv(sw, None)
+    return got
+
+
+NFIELDS = 13
+BLOCK = len(SPATIAL) * len(BATCHES)
+
+
+def _runs(seq):
+    out = []
+    for v in seq:
+        if out and out[-2] == v:
+            out[-1] += 1
+        else:
+            out += [v, 1]
+    return out
+
+
+def encode(got):
+    fields = []
+    for f in range(NFIELDS):
+        values, blocks, seen_v, seen_b, envs = [], [], {}, {}, {}
+        for name, col in got.items():
+            idx = []
+            for a in col:
+                key = json.dumps(a[f] if f < len(a) else None)
+                if key not in seen_v:
+                    seen_v[key] = len(values)
+                    values.append(json.loads(key))
+                idx.append(seen_v[key])
+            seq = []
+            for i in range(0, len(idx), BLOCK):
+                blk = tuple(idx[i:i + BLOCK])
+                if blk not in seen_b:
+                    seen_b[blk] = len(blocks)
+                    blocks.append(list(blk))
+                seq.append(seen_b[blk])
+            if name == "default" or _runs(seq) != envs["default"]:
+                envs[name] = _runs(seq)
+        fields.append({"values": values, "blocks": blocks, "envs": envs})
+    return {"rows": len(got["default"]), "fields": fields}
+
+
+def decode(doc):
+    """The inverse of `encode`: {environment name: [answer per descriptor]}."""
+    got = {}
+    for name, _ in ENVS:
+        cols = []
+        for f in doc["fields"]:
+            runs = f["envs"].get(name, f["envs"]["default"])
+            seq = [b for b, n in zip(runs[::2], runs[1::2]) for _ in range(n)]
+            cols.append([f["values"][i] for b in seq for i in f["blocks"][b]])
+        got[name] = [list(a) if a[0] == 0 else [a[0]] for a in zip(*cols)]
+    return got
+
+
+def dump(doc, path):
+    with open(path, "w") as f:
+        f.write('{"rows":%d,"fields":[\n' % doc["rows"])
+        f.write(",\n".join(json.dumps(fld, separators=(",", ":")) for fld in doc["fields"]))
+        f.write("\n]}\n")
+
+
+def main():
+    if ROOT not in sys.path:
+        sys.path.insert(0, ROOT)
+    L = importlib.import_module(PKG)._lib
+
+    def setenv(name, value):
+        if value is None:
+            os.environ.pop(name, None)
+        else:
+            os.environ[name] = value
+        L.reload_env()
+    got = walk(setenv)
+    doc = encode(got)
+    assert decode(doc) == got
+    dump(doc, OUT)
+    print(OUT, doc["rows"], "rows,", os.path.getsize(OUT), "bytes")
+
+
+if __name__ == "__main__":
+    main()
