@@ -18,40 +18,54 @@
 // 2.5e-7 of max|y| against 1.8e-7 for the 16-product form).  The dual quaternion [[Q, 0], [Q2, Q]] is three such
 // products, y_p = Q x_p,  y_d = Q2 x_p + Q x_d: 24 sub-products instead of 48.
 //
-// Kernel structure (one workgroup = 4 waves = 64 positions x one channel tile, 2 workgroups per CU):
+// Kernel structure (one workgroup = 4 waves = 64 positions x one channel tile, 2 or 3 workgroups per CU):
 //   * the weight forms F_m are precomputed ONCE per step by hcq_pack_kernel, already in MFMA B-fragment order
-//     ([chunk][range][k-group pair][m][lane]); a wave reads its fragments with coalesced 8/16-byte loads straight from
-//     L2 -- no LDS, no sign logic, no component switching in the loop;
-//   * the input is staged RAW (no im2col): per K chunk of IBC block channels the 4 / 8 component rows of the tile plus
-//     their halo, [component][channel][64 + 2*dpad] floats, 16-byte aligned loads; the taps are offsets into the rows;
-//   * per k-group a lane reads its 4 component values, forms the 8 sums G_m (8 VALU) and issues 8 x tiles MFMAs
-//     (v_mfma_f32_16x16x4_f32) into accumulators indexed [tile][m];
+//     ([chunk][range][k-group pair][m][lane][tile][2]), so a workgroup's fragments are one linear stream.  The workgroup
+//     copies it unit by unit (the 8 forms of a pair of k-groups, or 4 of them) into a ring of two LDS slots with LDS-DMA
+//     and its four waves read their fragments there, form by form, two forms ahead of the MFMAs: a fragment passes the
+//     CU's vector L1 once per workgroup, not once per wave, and a wave holds 3 forms in registers, not 8;
+//   * the input is staged RAW (no im2col), also by LDS-DMA: per K chunk of IBC block channels the 4 / 8 component rows of
+//     the tile plus their halo, [component][channel][64 + 2*dpad] floats, double-buffered; the taps are offsets into rows;
+//   * per pair of k-groups a lane reads its 2 x 4 component values, forms the 2 x 8 sums G_m (16 VALU) and issues, form
+//     by form, tiles MFMAs (v_mfma_f32_16x16x4_f32) for the even and then the odd k-group into accumulators [tile][m];
+//   * one barrier per unit (see the K loop for the wait counts); the next chunk's input is requested at a chunk's first
+//     unit and has two units of MFMAs to arrive in;
 //   * two K ranges for the dual quaternion: range 0 reads the source half every output needs, range 1 the half only
 //     one half of the outputs needs (the structural zero block is never touched);
 //   * epilogue: the signed sums above, bias / addend / BatchNorm statistics, 16-byte stores.
+// Registers / LDS per workgroup (input buffers + ring) / workgroups per CU that LDS allows, at the step's shapes:
+//   cnn.1 / cnn.2  <3,3,4,1,2,2,7>      188 VGPRs (221 before the ring)   55 296 + 24 576 B   2
+//   TCN 1x3 halo 4 <1,3,8,1,1,2,5>      113 (152); mixed tiles 127 (165)  36 864 + 16 384     3
+//   TCN 1x3 halo 8, forward             113                               40 960 +  8 192     3   (half-pair slots)
+//   TCN 1x3 halo 8, data gradient       127                               40 960 + 16 384     2   (mixed tiles: see hcq_plan)
+//   TCN 1x3 halo 16, forward            global loads (GF): 49 152 B of input leave no room for a ring at 3 per CU
+//   TCN 1x1 pair   <1,1,16,1,2,2,8>     168 (198)                         65 536 + 12 288     2   (half-pair slots)
+// No instantiation spills.
 #include <string.h>
 #include <type_traits>
 #include "hc_common.h"
 
 // Phase ablation for timing experiments only (tools/hcq_ablate.sh builds variants into tools/_bin; results are WRONG with
-// any bit set): 1 = weight fragments loaded once, 2 = LDS operand reads + sums once, 4 = input staged once,
-// 8 = no per-chunk barrier.  The shipped library is built with 0.
-// Round-3 readings on cnn.1 (forward / data gradient, us): as shipped 774 / 732; 1: 636 / 591; 4: 718 / 668; 8: no change;
-// 1+2+4: 550 / 517 (the MFMA floor is 481).  The fragment loads are the largest term, and it is not their bytes, their
-// request count or their latency window that costs: loading the 4 raw components per (pair, tile) and forming the 8 sums
-// in registers (half the bytes and requests, two register stages = a whole pair of k-groups ahead) ran 773 / 745, with
-// three-wave occupancy lost on the TCN layers (177 VGPRs) -- and again 757 against 701 once both versions had their requests
-// pinned (HCQ_PIN), for the three-tile shapes only; raised wave priority (s_setprio 1) around each k-group's MFMAs 786 / 786; rotating the chunk order per workgroup (so that workgroups in
-// step do not ask the L2 for the same lines) 751 / 723 against 752 / 722; staging the input from cache-resident
-// addresses 712 against 723.  Left as it is.
+// any bit set): 1 = weight fragments requested once (every unit reads slot 0), 2 = LDS operand reads + sums once,
+// 4 = input staged twice only, 8 = no barriers.  The shipped library is built with 0.
+// Readings on cnn.1 (forward / data gradient, us).  With per-wave global fragment loads (the kernel before the ring, now
+// the GF form): as shipped 774 / 732; 1: 636 / 591; 4: 718 / 668; 8: no change; 1+2+4: 550 / 517 (the MFMA floor is 481).
+// The fragment loads were the largest term, and it was not their bytes, their request count or their latency window
+// that cost: loading the 4 raw components per (pair, tile) and forming the 8 sums in registers (half the bytes and
+// requests, two register stages = a whole pair of k-groups ahead) ran 773 / 745, with three-wave occupancy lost on the
+// TCN layers (177 VGPRs) -- and again 757 against 701 once both versions had their requests pinned (HCQ_PIN), for the
+// three-tile shapes only; raised wave priority (s_setprio 1) around each k-group's MFMAs 786 / 786; rotating the chunk
+// order per workgroup (so that workgroups in step do not ask the L2 for the same lines) 751 / 723 against 752 / 722;
+// staging the input from cache-resident addresses 712 against 723.  What cost was WHO asked: four waves fetching the same
+// fragments through one L1 (0.78 tag accesses per CU clock).  With the ring (tools/hcq_check.py, medians of three,
+// same session): cnn.1 728 / 660 against 747 / 686, L1 accesses per CU clock 0.16 against 0.78, MFMA busy 66.2 % against 65.0 %
+// (profiles/hcq_fragment_ring_counters.txt, profiles/hcq_fragment_ring_shapes.md).  The ablation variants have not been
+// re-measured with the ring.
 #ifndef HCQ_DBG
 #define HCQ_DBG 0
 #endif
 #ifndef HCQ_PIN
 #define HCQ_PIN 1
-#endif
-#ifndef HCQ_XDMA
-#define HCQ_XDMA 1          // input chunks global -> LDS with LDS-DMA (no staging registers, no ds_write), hcq_conv_kernel only
 #endif
 
 namespace seld {
@@ -84,6 +98,8 @@ struct HcqP {
     long long range_stride[2];   // floats of one (chunk, range) block of wpack
     long long ytile_stride;      // floats of one regular channel tile of wpack (all chunks of all sources)
     long long set_stride;        // floats of one weight set (regular tiles + the mixed tile's block)
+    int ring_off;                // hcq_conv_kernel: byte offset of the fragment ring in LDS (behind the input buffers)
+    int half_slots;              // ring slot = 8 forms of a pair of k-groups (0) or 4 forms (1: half the ring, one more barrier)
 };
 
 typedef unsigned int uintx4h __attribute__((ext_vector_type(4)));
@@ -122,7 +138,9 @@ __device__ __forceinline__ void xforms(const float b[4], float g[8]) {
 // descriptors: its range-0-only tile is padding, its both-range tile is descriptor slot 2 (8 channels of each half).
 // MX: the launch has mixed-tile workgroups, whose copy of the K loop leaves the padding slots out (a second copy of the
 // loop costs registers -- 186 instead of 160 for the TCN 1x3 shape -- so launches without such workgroups keep MX = false).
-template <int KH, int KW, int IBC, int NT1, int NT2, int NR, int XI, bool MX = false>
+// GF: the shapes hcq_plan keeps off the fragment ring (quaternion 1-D layers; 1-D shapes whose LDS has no room for it):
+// every wave loads its own fragments from global memory, as all launches did before the ring.
+template <int KH, int KW, int IBC, int NT1, int NT2, int NR, int XI, bool MX = false, bool GF = false>
 __global__ __launch_bounds__(256, 2) void hcq_conv_kernel(const HcqP p) {
     constexpr int TAPS = KH * KW;
     constexpr int NT = NT1 + NT2;
@@ -159,7 +177,6 @@ __global__ __launch_bounds__(256, 2) void hcq_conv_kernel(const HcqP p) {
     const unsigned S = (unsigned)(p.Himg * p.W);
     const unsigned src_bytes = (unsigned)p.N * (unsigned)p.Csrc * S * 4u;
     const unsigned OOB = 0xFFFFFFF0u;
-    __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p.src, 0, src_bytes, 0x00020000);
     unsigned xoff[XI];
     int xlds[XI];
     const unsigned xadv = (unsigned)IBC * S * 4u;
@@ -189,7 +206,6 @@ __global__ __launch_bounds__(256, 2) void hcq_conv_kernel(const HcqP p) {
             if (quad >= qw) { quad -= qw; ++row; }
         }
     }
-#if HCQ_XDMA
     // Input chunks go global -> LDS directly (buffer_load ... lds): the LDS image is linear in the item index (item f at byte
     // 16 f), so instruction i of wave w fills the contiguous KiB at 16 (256 i + 64 w); no staging registers (28 of them for
     // the 3x3 layers), no ds_write.  load_x(buf) requests the next chunk into `buf`; store_x waits for the wave's requests.
@@ -213,31 +229,6 @@ __global__ __launch_bounds__(256, 2) void hcq_conv_kernel(const HcqP p) {
         xbuf ^= 1;
     };
     auto store_x = [&](int) __attribute__((always_inline)) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); };
-#else
-    floatx4 xr[XI];
-    int xchunk = 0;                                    // chunks requested so far
-    auto load_x = [&]() __attribute__((always_inline)) {
-        if (xchunk == p.nch) {                         // second source of a pair: same offsets, other tensor
-            rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p.src2, 0, src_bytes, 0x00020000);
-#pragma unroll
-            for (int i = 0; i < XI; ++i) xoff[i] = xoff[i] == OOB ? OOB : xoff[i] - (unsigned)p.nch * xadv;
-        }
-        ++xchunk;
-#pragma unroll
-        for (int i = 0; i < XI; ++i) {
-            const uintx4h v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, xoff[i], 0, 0);
-            xr[i][0] = __uint_as_float(v[0]); xr[i][1] = __uint_as_float(v[1]);
-            xr[i][2] = __uint_as_float(v[2]); xr[i][3] = __uint_as_float(v[3]);
-            xoff[i] = xoff[i] == OOB ? OOB : xoff[i] + xadv;
-        }
-    };
-    auto store_x = [&](int buf) __attribute__((always_inline)) {
-        float* b = lds + buf * buf_floats;
-#pragma unroll
-        for (int i = 0; i < XI; ++i)
-            if (xlds[i] >= 0) *reinterpret_cast<float4*>(b + xlds[i]) = make_float4(xr[i][0], xr[i][1], xr[i][2], xr[i][3]);
-    };
-#endif
 
     // ---- A-operand addresses: k-group g, this lane's k = 4g + fk -> (ibl, kh, kw); component stride = IBC*KH*wext ----
     int aoff[NG];
@@ -357,7 +348,7 @@ __global__ __launch_bounds__(256, 2) void hcq_conv_kernel(const HcqP p) {
                     // keep the request HERE: between two scheduling barriers the compiler moves loads towards their use
                     // (register pressure), i.e. to the end of this k-group -- a few MFMAs ahead of the wait instead of
                     // seven forms
-                    if (HCQ_PIN && (NT >= 3 || HCQ_XDMA)) __builtin_amdgcn_sched_barrier(0);
+                    if (HCQ_PIN) __builtin_amdgcn_sched_barrier(0);
                 }
             }
             if (!last && !(HCQ_DBG & 2)) xforms(raw, gm[gst ^ 1]);
@@ -367,12 +358,166 @@ __global__ __launch_bounds__(256, 2) void hcq_conv_kernel(const HcqP p) {
         if (!(HCQ_DBG & 8)) __syncthreads();
     }
     };
+
+    // ---- K loop with the fragment ring ------------------------------------------------------------------------------
+    // The packed fragments of a workgroup are ONE linear stream: [chunk][range][pair][form m][lane][tile][2].  It is cut
+    // into units of 8 forms (a pair of k-groups: 4 KB x tiles of the range) or 4 forms (p.half_slots); unit u is copied by
+    // the whole workgroup into ring slot u & 1 with LDS-DMA (a linear copy: instruction i of wave w moves the KiB 4 i + w),
+    // so a fragment passes the vector L1 once per workgroup instead of once per wave.
+    //   open(u):   s_waitcnt vmcnt -- this wave's copy of unit u has landed;  s_waitcnt lgkmcnt(0) + s_barrier -- so has
+    //              everybody's, and everybody has finished reading unit u - 1 (and, at a chunk's first unit, the previous
+    //              chunk's input buffer);
+    //   then:      request unit u + 1 into the slot of unit u - 1; at a chunk's first unit request the NEXT chunk's input
+    //              behind it; read the 2 x 4 raw component values of the pair, form the sums; per form read the lane's
+    //              2 x tiles floats from the slot two forms ahead of their MFMAs (three register stages instead of the
+    //              eight of the global-load loop).
+    // vmcnt retires in order.  Requests of a wave between two opens:   open(first unit of chunk): F(u+1), X(next chunk) [XI]
+    //                                                                  open(second unit):          F(u+2)
+    // so the second unit's open waits with vmcnt(XI) (only F(u+1) has to be there, the XI input requests behind it stay in
+    // flight) and every other open with vmcnt(0): the input of the next chunk has two units of MFMAs to arrive in.  A wave
+    // whose last staging instruction has no lane to serve (its count is not XI) waits with vmcnt(0) there, too.
+    // An accumulator sees its k-groups in the order of the global-load loop (a pair's even group, then its odd one), so the
+    // results are the same bits.
+    auto kring = [&](auto mixc) __attribute__((always_inline)) {
+    constexpr bool MIX = decltype(mixc)::value;
+    const bool half = p.half_slots != 0;                        // workgroup-uniform
+    const unsigned tile_bytes = half ? 2048u : 4096u;           // one tile's share of a unit
+    const unsigned slot_bytes = tile_bytes * NT;
+    const unsigned ring0 = lds0 + (unsigned)p.ring_off;
+    const float* const ringf = lds + (p.ring_off >> 2);
+    const int4h frs = hcq_rsrc(wbase, (unsigned)p.ytile_stride * 4u);     // this channel tile's fragments, all chunks and sources
+    unsigned foff = 1024u * (unsigned)wave + 16u * (unsigned)lane;        // of the next unit to request
+    unsigned fslot = 0;                                          // slot the next request fills
+    unsigned rslot = 0;                                          // slot of the unit being read
+    bool freq = false;
+    const bool xfull = 256 * (XI - 1) + 64 * wave < total_items; // this wave issues all XI staging instructions of a chunk
+    auto load_f = [&](auto ntrc) __attribute__((always_inline)) {
+        constexpr int NTRn = decltype(ntrc)::value;
+        const unsigned nbytes = tile_bytes * NTRn;
+        if (!((HCQ_DBG & 1) && freq)) {
+            const unsigned dst = ring0 + fslot * slot_bytes + 1024u * (unsigned)wave;
+#pragma unroll
+            for (int i = 0; i < NTRn; ++i)
+                if (4096u * i + 1024u * (unsigned)wave < nbytes) hcq_dma16(dst + 4096u * i, foff + 4096u * i, frs);   // wave-uniform
+        }
+        freq = true;
+        foff += nbytes;
+        fslot ^= 1u;
+    };
+    // counted: XI younger requests (the next chunk's input) may stay in flight
+    auto open_unit = [&](bool counted) __attribute__((always_inline)) {
+        if (counted) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(XI) : "memory");
+        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        if (HCQ_DBG & 8) return;
+        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    };
+    float ga[8], gb[8];
+    float2 fb[3][NT];
+    load_x();                                                    // chunk 0
+    load_f(INT{});                                               // unit 0
+    bool dbg_raw = false;
+    for (int ch = 0; ch < nchunks; ++ch) {
+        const bool more = ch + 1 < nchunks;
+        const float* xb = lds + (ch & 1) * buf_floats;
+        const float* xs0 = xb + p.half_src[0] * 4 * comp_stride;
+        const float* xs1 = xb + p.half_src[1] * 4 * comp_stride;
+        bool xreq = false;                                       // the next chunk's input was requested at this chunk's first open
+#pragma unroll
+        for (int pc = 0; pc < NPC; ++pc) {
+            const int r = pc / NPAIR, j = pc - r * NPAIR;
+            const int g0 = 2 * j;
+            const bool two = g0 + 1 < NG;                        // (the last pair of an odd NG holds one k-group)
+            const int ntr = r == 0 ? NT : NT2;
+            const int t0 = (r == 0 && MIX) ? NT1 : 0;
+            const int ab = r == 0 ? 0 : NT1;                     // accumulator slot of the range's first tile
+            // the unit after this pair's last one: the next pair's first (next range, next chunk)
+            auto request_next_pair = [&]() __attribute__((always_inline)) {
+                if (pc + 1 < NPC) {
+                    if ((pc + 1) / NPAIR == 0) load_f(INT{});
+                    else load_f(INT2{});
+                } else if (more) {
+                    load_f(INT{});
+                }
+            };
+            // ---- open the pair's first unit; second unit of the chunk when pc == 1 and slots hold whole pairs
+            open_unit(pc == 1 && !half && xreq && xfull);        // vmcnt: F(this unit) | X x XI, or everything
+            if (half) {
+                if (r == 0) load_f(INT{});
+                else load_f(INT2{});
+            } else {
+                request_next_pair();
+            }
+            if (pc == 0 && more && !((HCQ_DBG & 4) && ch > 0)) { load_x(); xreq = true; }
+            const float* fsl = ringf + rslot * (slot_bytes >> 2);
+            auto read_form = [&](int idx, int st) __attribute__((always_inline)) {
+                const float2* q = reinterpret_cast<const float2*>(fsl) + (idx * 64 + lane) * ntr;
+#pragma unroll
+                for (int t = 0; t < NT; ++t)
+                    if (t >= t0 && t < ntr) fb[st][t] = q[t];
+            };
+            read_form(0, 0);
+            read_form(1, 1);
+            if (!((HCQ_DBG & 2) && dbg_raw)) {
+                float ra[4], rb[4];
+                const float* xs = r == 0 ? xs0 : xs1;
+#pragma unroll
+                for (int q = 0; q < 4; ++q) ra[q] = xs[aoff[g0] + q * comp_stride];
+                if (two) {
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) rb[q] = xs[aoff[two ? g0 + 1 : g0] + q * comp_stride];
+                }
+                xforms(ra, ga);
+                if (two) xforms(rb, gb);
+                dbg_raw = true;
+            }
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int m = 0; m < 8; ++m) {
+                if (m == 4 && half) {
+                    // ---- the pair's second unit (4-form slots): second unit of the chunk when pc == 0
+                    open_unit(pc == 0 && xreq && xfull);         // vmcnt: F(this unit) | X x XI, or everything
+                    request_next_pair();
+                    rslot ^= 1u;
+                    fsl = ringf + rslot * (slot_bytes >> 2);
+                    read_form(0, 4 % 3);
+                    read_form(1, 5 % 3);
+                }
+                if (m + 2 < 8) {
+                    if (m + 2 < 4 || m >= 4) read_form(half ? (m + 2) & 3 : m + 2, (m + 2) % 3);
+                    else if (!half) read_form(m + 2, (m + 2) % 3);      // forms 4, 5 of a whole-pair slot
+                }
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int t = 0; t < NT; ++t)
+                    if (t >= t0 && t < ntr)
+                        acc[ab + t][m] = __builtin_amdgcn_mfma_f32_16x16x4f32(ga[m], fb[m % 3][t].x, acc[ab + t][m], 0, 0, 0);
+                if (two) {
+#pragma unroll
+                    for (int t = 0; t < NT; ++t)
+                        if (t >= t0 && t < ntr)
+                            acc[ab + t][m] = __builtin_amdgcn_mfma_f32_16x16x4f32(gb[m], fb[m % 3][t].y, acc[ab + t][m], 0, 0, 0);
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            rslot ^= 1u;
+            if (HCQ_DBG & 1) rslot = 0;
+        }
+    }
+    // the statistics scratch of the epilogue overlays the staging area: not before everybody's last reads
+    if (p.epilogue[set] & SELD_EPI_STATS) __syncthreads();
+    };
     if constexpr (MX) {
         static_assert(NR == 2 && NT1 == 1 && NT2 == 1, "the only layout with mixed-tile workgroups");
-        if (mix_wg) kloop(std::true_type{});
-        else kloop(std::false_type{});
+        if constexpr (GF) {
+            if (mix_wg) kloop(std::true_type{});
+            else kloop(std::false_type{});
+        } else {
+            if (mix_wg) kring(std::true_type{});
+            else kring(std::false_type{});
+        }
     } else {
-        kloop(std::false_type{});
+        if constexpr (GF) kloop(std::false_type{});
+        else kring(std::false_type{});
     }
 
     // ---- epilogue ------------------------------------------------------------------------------------------------
@@ -1150,6 +1295,7 @@ __global__ __launch_bounds__(256) void hcq_pack_table_kernel(const HcqPackP* __r
 struct HcqPlan {
     int ok;
     int KH, KW, IBC, NT1, NT2, NR, XI, mix;
+    int gf;                      // hcq_conv_kernel with per-wave global fragment loads (no ring)
     int first_rows;              // > 0: hcq_first_kernel walks this many image rows per workgroup
     HcqP kp;
     HcqPackP pp;
@@ -1186,7 +1332,7 @@ static HcqPlan hcq_plan(const seld_conv_desc* d, int mode, int npair) {
     const int dil = KW == 3 ? d->dil[1] : 0;
     const int dpad = KW == 3 ? (dil + 3) / 4 * 4 : 0;
     const int wext = 64 + 2 * dpad;
-    // K chunk: candidates in order of preference; two workgroups per CU must fit (78 KB each)
+    // K chunk: candidates in order of preference; the input buffers of two workgroups per CU must fit (78 KB each)
     static const int cand11[] = {16, 24, 8, 0}, cand13[] = {8, 4, 0}, cand33[] = {4, 2, 1, 0};
     const int* cand = taps == 1 ? cand11 : (taps == 3 ? cand13 : cand33);
     int IBC = 0;
@@ -1205,10 +1351,6 @@ static HcqPlan hcq_plan(const seld_conv_desc* d, int mode, int npair) {
     // 342 -> 225.
     if (!pool && mode == 0 && taps == 9 && A == 8 && IB == 1 && Cdst == 192 && (long long)d->N * Himg * W >= 256 * 128 &&
         !env().conv_no_smallk) return pl;
-    const int rows = A * IBC * KH;
-    const int items = rows * (wext / 4);
-    const int XI = (items + 255) / 256;
-    if (smem < 8 * 1024) smem = 8 * 1024;                                     // statistics scratch of the epilogue
     // channel tiles
     HcqP& k = pl.kp;
     int NT1, NT2, NR, nreg, ob_step, mix = 0;
@@ -1247,8 +1389,39 @@ static HcqPlan hcq_plan(const seld_conv_desc* d, int mode, int npair) {
         else return pl;
         for (int t = 0; t < NT1; ++t) { k.tile_ob[t][0] = 16 * t; k.tile_ob[t][1] = 16 * t + 8; }
     }
-    const int NG = (IBC * taps + 3) / 4, NPAIR = (NG + 1) / 2;
     const int NT = NT1 + NT2;
+    // LDS of hcq_conv_kernel = input buffers + fragment ring of two slots (a slot: the 8 forms of a pair of k-groups,
+    // 4 KB per tile, or 4 forms).  The chunk stays the one chosen above (with two K ranges the chunk size decides the
+    // order in which an accumulator meets them, i.e. the bits of the result).  The ring must not cost a resident workgroup
+    // per CU (160 KB; registers allow 3 at most): whole pairs if they keep the count, else half pairs if they do (one
+    // more barrier per pair).  Two exceptions, both measured (profiles/hcq_fragment_ring_shapes.md):
+    //   * launches with mixed-tile workgroups (a third of their workgroups run one tile in range 0: 8 MFMAs per half-pair
+    //     unit) are faster with whole pairs at two workgroups per CU than with half pairs at three: TCN 1x3 data
+    //     gradient, halo 8, 39.8 us against 43.4 (41 to 42 before the ring);
+    //   * quaternion 1-D layers keep per-wave global loads (GF): one range, one or two tiles and few chunks -- launches
+    //     of about 10 us in which a barrier per pair costs what the L1 traffic saves (+0.2 ... -1.5 us with the ring).
+    // A 1-D shape that no ring fits without losing a workgroup (1x3 forward, halo 12 to 16 or above 56) keeps global
+    // loads as well; a 3x3 shape would take half pairs regardless (none does at the networks' widths).
+    int half_slots = 0;
+    bool gf = A == 4 && KH == 1;
+    if (!pool && !gf) {
+        const auto wgs = [](size_t bytes) { const size_t n = (size_t)160 * 1024 / (bytes < 8192 ? 8192 : bytes); return n > 3 ? (size_t)3 : n; };
+        const size_t wgs0 = wgs(smem);
+        const size_t whole = (size_t)2 * 4096 * NT, halves = (size_t)2 * 2048 * NT;
+        if (wgs(smem + whole) >= wgs0 || (mix && wgs(smem + whole) >= 2)) half_slots = 0;
+        else if (wgs(smem + halves) >= wgs0 || KH != 1) half_slots = 1;
+        else gf = true;
+        if (!gf) {
+            k.ring_off = (int)smem;
+            k.half_slots = half_slots;
+            smem += half_slots ? halves : whole;
+        }
+    }
+    const int rows = A * IBC * KH;
+    const int items = rows * (wext / 4);
+    const int XI = (items + 255) / 256;
+    if (smem < 8 * 1024) smem = 8 * 1024;                                     // statistics scratch of the epilogue
+    const int NG = (IBC * taps + 3) / 4, NPAIR = (NG + 1) / 2;
     k.A = A; k.N = d->N; k.Csrc = Csrc; k.Cdst = Cdst; k.IB = IB; k.OB = OB;
     k.W = W; k.Himg = Himg; k.dil = dil; k.dpad = dpad; k.wext = wext; k.nch = IB / IBC;
     k.nsrc = nsrc;
@@ -1268,6 +1441,7 @@ static HcqPlan hcq_plan(const seld_conv_desc* d, int mode, int npair) {
     q.range_stride[0] = k.range_stride[0]; q.range_stride[1] = k.range_stride[1];
     q.ytile_stride = k.ytile_stride; q.set_stride = k.set_stride; q.total = (long long)pl.pack_floats;
     pl.KH = KH; pl.KW = KW; pl.IBC = IBC; pl.NT1 = NT1; pl.NT2 = NT2; pl.NR = NR; pl.XI = XI; pl.mix = mix;
+    pl.gf = gf ? 1 : 0;
     const long long ptot = (long long)d->N * Himg * W;
     pl.grid = dim3((unsigned)(ptot / 64), (unsigned)(k.ytiles * nsets), 1);
     pl.smem = smem;
@@ -1305,9 +1479,9 @@ static int hcq_pick(const HcqPlan& pl, HcqKern* k) {
     return 1;
 }
 
-template <int KH, int KW, int IBC, int NT1, int NT2, int NR, int XI, bool MX = false>
+template <int KH, int KW, int IBC, int NT1, int NT2, int NR, int XI, bool MX = false, bool GF = false>
 static int hcq_launch_one(const HcqPlan& pl, hipStream_t st) {
-    auto kern = hcq_conv_kernel<KH, KW, IBC, NT1, NT2, NR, XI, MX>;
+    auto kern = hcq_conv_kernel<KH, KW, IBC, NT1, NT2, NR, XI, MX, GF>;
     if (pl.smem > 64 * 1024 &&
         hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.smem) != hipSuccess)
         return SELD_ELAUNCH;
@@ -1319,11 +1493,23 @@ template <int KH, int KW, int IBC, int XI8, int XI4>
 static int hcq_launch_cfg(const HcqPlan& pl, const HcqKern& k, hipStream_t st) {
     if (k.NR == 2) {
         if (k.XI != XI8) return SELD_EUNSUPPORTED;
+        if constexpr (KH == 1) {                              // the global-load form exists for the shapes hcq_plan gives it to
+            if (pl.gf) {
+                if (k.NT2 == 2) return hcq_launch_one<KH, KW, IBC, 1, 2, 2, XI8, false, true>(pl, st);
+                if (pl.mix) return hcq_launch_one<KH, KW, IBC, 1, 1, 2, XI8, true, true>(pl, st);
+                return hcq_launch_one<KH, KW, IBC, 1, 1, 2, XI8, false, true>(pl, st);
+            }
+        }
         if (k.NT2 == 2) return hcq_launch_one<KH, KW, IBC, 1, 2, 2, XI8>(pl, st);
         if (pl.mix) return hcq_launch_one<KH, KW, IBC, 1, 1, 2, XI8, true>(pl, st);
         return hcq_launch_one<KH, KW, IBC, 1, 1, 2, XI8>(pl, st);
     }
     if (k.XI != XI4) return SELD_EUNSUPPORTED;
+    if constexpr (KH == 1) {
+        if (pl.gf)
+            return k.NT1 == 2 ? hcq_launch_one<KH, KW, IBC, 2, 0, 1, XI4, false, true>(pl, st)
+                              : hcq_launch_one<KH, KW, IBC, 1, 0, 1, XI4, false, true>(pl, st);
+    }
     return k.NT1 == 2 ? hcq_launch_one<KH, KW, IBC, 2, 0, 1, XI4>(pl, st)
                       : hcq_launch_one<KH, KW, IBC, 1, 0, 1, XI4>(pl, st);
 }
@@ -1400,8 +1586,8 @@ extern "C" int seld_hcq_kernel_label(const seld_conv_desc* d, int32_t mode, int3
     else if (pl.first_rows && hcq_first_takes(pl))   // (label of the plain / statistics epilogue: what the first layer runs)
         snprintf(buf, buflen, "hcq_first_kernel<%d, %d, %d, %d, %d>", k.IBC, k.NT1, k.NT2, k.NR, pl.first_rows);
     else
-        snprintf(buf, buflen, "hcq_conv_kernel<%d, %d, %d, %d, %d, %d, %d, %s>", k.KH, k.KW, k.IBC, k.NT1, k.NT2, k.NR, k.XI,
-                 (pl.mix && k.NR == 2 && k.NT2 == 1) ? "true" : "false");
+        snprintf(buf, buflen, "hcq_conv_kernel<%d, %d, %d, %d, %d, %d, %d, %s, %s>", k.KH, k.KW, k.IBC, k.NT1, k.NT2, k.NR, k.XI,
+                 (pl.mix && k.NR == 2 && k.NT2 == 1) ? "true" : "false", pl.gf ? "true" : "false");
     return SELD_OK;
 }
 

@@ -13,6 +13,7 @@ dev = torch.device("cuda:0")
 SHAPES = [
     ("tcn_k3_d5", 8, (32, 192, 512), 384, (3,), 5, 5),
     ("tcn_k3_d1", 8, (32, 192, 512), 384, (3,), 1, 1),
+    ("tcn_k3_d13", 8, (32, 192, 512), 384, (3,), 13, 13),     # halo 16: the forward keeps per-wave global loads (hcq_plan)
     ("tcn_k3_d55", 8, (32, 192, 512), 384, (3,), 55, 55),
     ("tcn_k1", 8, (32, 384, 512), 192, (1,), 0, 1),
     ("cnn1", 8, (32, 192, 16, 512), 192, (3, 3), 1, 1),
