@@ -561,38 +561,33 @@ int seld_hcq_pack(const seld_conv_desc* desc, int32_t mode, int32_t npair, const
 int seld_hcq_conv(const seld_conv_desc* desc, int32_t mode, int32_t npair, const float* x, const float* x2,
                   const float* wpack, float* const y[2], const float* const bias[2], const int32_t epilogue[2],
                   const float* const addend[2], float* const stats[2], void* stream);
+int seld_hcq_kernel_label(const seld_conv_desc* desc, int32_t mode, int32_t npair, char* buf, int32_t buflen);
+/* Host-only: the launch behind that label -- out = grid x, grid y, dynamic LDS bytes, byte offset of the fragment ring in
+ * LDS and its slot kind (1: half pairs; both 0 without a ring), image rows per workgroup (0: not a first-layer kernel).
+ * mode 2: the launch of seld_hcq_first_pool. */
+int seld_hcq_launch_shape(const seld_conv_desc* desc, int32_t mode, int32_t npair, int32_t out[6]);
 /* Every layer's weight forms in ONE launch per optimiser step: the caller builds a table of entries
  * (seld_hcq_pack_entry fills one entry of seld_hcq_pack_entry_bytes() bytes in host memory), copies it to the device
- * once, and calls seld_hcq_pack_table(table, entries, floats of the largest entry) after every weight update. */
-int seld_hcq_kernel_label(const seld_conv_desc* desc, int32_t mode, int32_t npair, char* buf, int32_t buflen);
+ * once, and calls seld_hcq_pack_flat after every weight update: starts_dev[e] = first 256-float block of entry e (prefix
+ * sums of ceil(floats_e / 256)), starts_dev[nentries] = total_blocks. */
 size_t seld_hcq_pack_entry_bytes(void);
 int seld_hcq_pack_entry(const seld_conv_desc* desc, int32_t mode, int32_t npair, const float* const wA[8],
                         const float* const wB[8], float* wpack, void* entry_host);
-int seld_hcq_pack_table(const void* table_dev, int32_t nentries, int64_t max_floats, void* stream);
-/* the same, balanced over the entries: starts_dev[e] = first 256-float block of entry e (prefix sums of
- * ceil(floats_e / 256)), starts_dev[nentries] = total_blocks */
 int seld_hcq_pack_flat(const void* table_dev, const int32_t* starts_dev, int32_t nentries, int32_t total_blocks,
                        void* stream);
 
-/* Weight gradient on the fast product (csrc/hcq_wgrad.hip): dW = sum over positions of dy (x) conj(x) is again a Hamilton
- * product per (output block channel, input block channel, tap): 8 (24 for the dual quaternion) real sub-products
- * instead of 16 (48).  dwA[c] += gradient of conv(x; W_A) given dyA; npair == 2: also dwB[c] += that of a second
- * convolution of the same input given dyB (conv1_filter | conv1_gate, conv2_skip | conv2_residual).  Accumulating (the
+/* Weight gradient of the quaternion layers on the fast product (csrc/hcq_wgrad.hip): dW = sum over positions of
+ * dy (x) conj(x) is again a Hamilton product per (output block channel, input block channel, tap): 8 real sub-products
+ * instead of 16.  (Dual quaternion: seld_hcq_wgrad_group, or seld_hc_conv_bwd_weight_acc.)  dwA[c] += gradient of
+ * conv(x; W_A) given dyA; npair == 2: also dwB[c] += that of a second convolution of the same input given dyB
+ * (conv1_filter | conv1_gate, conv2_skip | conv2_residual).  Accumulating (the
  * caller's buffers are FlatAdam's gradient slices, train.py:557); no bias gradient (use seld_hc_conv_bwd_weight_acc).
- * seld_hcq_wgrad_supported: 1 if the shape is taken ('same' stride-1 1x1 / 1x3 / 3x3, row length a multiple of 32). */
+ * seld_hcq_wgrad_supported: 1 if the shape is taken (algebra 4, 'same' stride-1 1x1 / 1x3 / 3x3, row length a multiple of
+ * 32, Cout/4 a multiple of 16). */
 int seld_hcq_wgrad_supported(const seld_conv_desc* desc, int32_t npair);
 int seld_hcq_wgrad_label(const seld_conv_desc* desc, int32_t npair, char* buf, int32_t buflen);
 int seld_hcq_wgrad_acc(const seld_conv_desc* desc, int32_t npair, const float* x, const float* dyA, const float* dyB,
                        float* const dwA[8], float* const dwB[8], void* stream);
-
-/* The dual-quaternion weight gradient with 24 instead of 48 block products on the row-chunk GEMM (csrc/hcq_wgrad_row.hip;
- * dual_quaternion_ops.py:122-153 differentiated).  seld_hcq_wgrad_row_workspace: bytes of fp32 scratch for (desc, npair),
- * 0 = shape not taken.  The scratch must be zero before the first call; every call hands it back zeroed (one buffer per
- * stream serves all layers).  npair == 2: two convolutions of the same input (dwB[c] += ...), one launch family. */
-size_t seld_hcq_wgrad_row_workspace(const seld_conv_desc* desc, int32_t npair);
-int seld_hcq_wgrad_row_label(const seld_conv_desc* desc, int32_t npair, char* buf, int32_t buflen);
-int seld_hcq_wgrad_row_acc(const seld_conv_desc* desc, int32_t npair, const float* x, const float* dyA, const float* dyB,
-                           float* const dwA[8], float* const dwB[8], void* workspace, size_t workspace_bytes, void* stream);
 
 /* SELD_DETERMINISTIC=1 (read with the other switches, seld_env_reload): reductions that are normally split over workgroups and
  * folded with float atomics -- BatchNorm statistics (seld_channel_stats), the two-pass BatchNorm / gate / pooling backward

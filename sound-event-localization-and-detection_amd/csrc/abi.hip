@@ -22,8 +22,6 @@ static void load_env_locked() {
     }
     e.conv_no_smallk = flag("SELD_CONV_NO_SMALLK");
     e.conv_no_hcq = flag("SELD_CONV_NO_HCQ");
-    e.hcq_wgrad_dq = flag("SELD_HCQ_WGRAD_DQ");
-    e.hcq_wgrad_row = flag("SELD_HCQ_WGRAD_ROW");
     e.deterministic = flag("SELD_DETERMINISTIC");
     e.mha_no_mfma = flag("SELD_MHA_NO_MFMA");
     g_env = e;

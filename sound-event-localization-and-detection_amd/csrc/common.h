@@ -25,8 +25,8 @@ typedef float floatx4 __attribute__((ext_vector_type(4)));
 //   sign negative at (0,1) (0,2) (0,3) (1,2) (2,3) (3,1)      -> bit p*4+q of 0x284E
 // Dual quaternion [[Q, 0], [Q2, Q]]: halves hp = p>>2, hq = q>>2; block is zero for hp=0,hq=1,
 // uses the second weight set (+4) for hp=1,hq=0.
-__host__ __device__ __forceinline__ int quat_comp(int p, int q) { return (p ^ q) & 3; }
-__host__ __device__ __forceinline__ float quat_sign(int p, int q) {
+__host__ __device__ __forceinline__ constexpr int quat_comp(int p, int q) { return (p ^ q) & 3; }
+__host__ __device__ __forceinline__ constexpr float quat_sign(int p, int q) {
     return ((0x284Eu >> (((p & 3) << 2) | (q & 3))) & 1u) ? -1.0f : 1.0f;
 }
 // returns component index in [0, A) or -1 for a structural zero; *sign receives +-1

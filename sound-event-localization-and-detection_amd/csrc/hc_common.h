@@ -156,4 +156,20 @@ inline void hc_out_shape(const seld_conv_desc* d, int out[2]) {
     }
 }
 
+// What the fast-product kernels (hcq_conv.hip, hcq_wgrad.hip) take: a 'same' convolution -- stride 1, no dilation along
+// H, output extent = input extent by symmetric padding -- with 1x1, 1x3 (dilated) or 3x3 taps, both tensors below 4 GB
+// (the kernels address them with 32-bit byte offsets).
+inline bool hcq_same_geometry(const seld_conv_desc* d) {
+    if (d->stride[0] != 1 || d->stride[1] != 1 || d->dil[0] != 1) return false;
+    int o[2];
+    hc_out_shape(d, o);
+    if (o[0] != d->in[0] || o[1] != d->in[1]) return false;
+    const int KH = d->k[0], KW = d->k[1];
+    if (!((KH == 1 && (KW == 1 || KW == 3)) || (KH == 3 && KW == 3))) return false;
+    if (2 * d->pad[1] != d->dil[1] * (KW - 1) || 2 * d->pad[0] != (KH - 1)) return false;
+    if (KW == 1 && d->dil[1] != 1) return false;
+    const long long S = (long long)d->N * d->in[0] * d->in[1] * 4;
+    return S * d->Cin < 0xFFFFFFF0ll && S * d->Cout < 0xFFFFFFF0ll;
+}
+
 }  // namespace seld

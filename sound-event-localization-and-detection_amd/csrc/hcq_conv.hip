@@ -2,13 +2,9 @@
 // gradient of the 1-D layers (1x3 dilated, 1x1) and the 3x3 layers.
 //
 // A Hamilton product w (x) x costs 16 real sub-products when it is evaluated as the 4 x 4 block matrix the reference
-// assembles (quaternion_ops.py:131-135).  It is a bilinear map of rank 8: with
-//
-//     P0 = (a3 + a1)(b1 + b2)   P1 = (a0 - a2)(b0 + b3)   P2 = (a0 + a2)(b0 - b3)   P3 = (a3 - a1)(b1 - b2)
-//     P4 = (a3 - a2)(b2 - b3)   P5 = (a1 + a0)(b1 + b0)   P6 = (a0 - a1)(b2 + b3)   P7 = (a3 + a2)(b1 - b0)
-//
-//     c0 = (-P0 + P1 + P2 + P3)/2 + P4      c1 = (-P0 - P1 - P2 + P3)/2 + P5
-//     c2 = ( P0 - P1 + P2 + P3)/2 + P6      c3 = ( P0 + P1 - P2 + P3)/2 - P7
+// assembles (quaternion_ops.py:131-135).  It is a bilinear map of rank 8: eight products P_m = F_m(a) G_m(b) of sums of
+// two components, recombined into the four components of c (the forms, the recombination and the proof that they are
+// the Hamilton product: hcq_forms.h)
 //
 // (a = weight components r,i,j,k; b = input components; c = output components; the a's always stand on the left, so
 // the identities hold for matrix-valued components, i.e. for convolutions).  The convolution therefore splits into 8
@@ -44,6 +40,7 @@
 #include <string.h>
 #include <type_traits>
 #include "hc_common.h"
+#include "hcq_forms.h"
 
 // Phase ablation for timing experiments only (tools/hcq_ablate.sh builds variants into tools/_bin; results are WRONG with
 // any bit set): 1 = weight fragments requested once (every unit reads slot 0), 2 = LDS operand reads + sums once,
@@ -70,6 +67,19 @@
 
 namespace seld {
 
+// The channel-tile layout of a launch, shared by the convolution kernels and the kernel that packs their weights.
+struct HcqTiles {
+    int NT1, NT2, NR;            // tiles active in range 0 only / in both ranges; K ranges (1 quaternion, 2 dual quaternion)
+    int nreg, mix;               // regular channel tiles per weight set; 1: a mixed 8 + 8 tile follows them
+    int ob_step;                 // block channels a channel tile advances by (16 / 32, or 0 for the single-tile layout)
+    int half_src[2];             // source half (0 primal, 1 dual) read by range 0 / range 1
+    int tile_half[3][2];         // tile t, 8-channel group g: destination half ...
+    int tile_ob[3][2];           // ... and first block channel (-1: padding, nothing stored); tile 2 = the mixed tile
+    long long range_stride[2];   // floats of one (chunk, range) block of the packed weights
+    long long ytile_stride;      // floats of one regular channel tile (all chunks of all sources)
+    long long set_stride;        // floats of one weight set (regular tiles + the mixed tile's block)
+};
+
 struct HcqP {
     const float* src;
     const float* src2;           // data gradient of a pair: dst = dgrad(src, W_0) + dgrad(src2, W_1), the K loop runs over both
@@ -90,47 +100,16 @@ struct HcqP {
     int dil, dpad;               // dilation along W, padded up to a multiple of 4 (the halo each side of a tile)
     int wext;                    // 64 + 2 * dpad
     int nch;                     // K chunks per range (IB / IBC)
-    int half_src[2];             // source half (0 primal, 1 dual) read by range 0 / range 1
-    int ytiles;                  // channel tiles per weight set
-    int ob_step;                 // block channels a channel tile advances by (16, or 0 for the single-tile layout)
-    int tile_half[3][2];         // tile t, 8-channel group g: destination half ...
-    int tile_ob[3][2];           // ... and first block channel (-1: padding, nothing stored); tile 2 = the mixed tile
-    long long range_stride[2];   // floats of one (chunk, range) block of wpack
-    long long ytile_stride;      // floats of one regular channel tile of wpack (all chunks of all sources)
-    long long set_stride;        // floats of one weight set (regular tiles + the mixed tile's block)
+    int ytiles;                  // channel tiles per weight set (t.nreg + t.mix)
+    HcqTiles t;
     int ring_off;                // hcq_conv_kernel: byte offset of the fragment ring in LDS (behind the input buffers)
     int half_slots;              // ring slot = 8 forms of a pair of k-groups (0) or 4 forms (1: half the ring, one more barrier)
 };
 
 typedef unsigned int uintx4h __attribute__((ext_vector_type(4)));
-typedef int int4h __attribute__((ext_vector_type(4)));
-
-// One 16-byte-per-lane LDS-DMA: LDS[lds_addr + 16 * lane ..] <- buffer[voff ..] (zeros when voff is out of range); lanes that
-// are switched off write nothing.  M0 is saved and restored in the statement.  (csrc/hcq_wgrad_grp.hip uses the same.)
-__device__ __forceinline__ void hcq_dma16(unsigned lds_addr, unsigned voff, int4h rsrc) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tbuffer_load_dwordx4 %2, %3, 0 offen lds\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "s"(lds_addr), "v"(voff), "s"(rsrc) : "memory");
-}
-__device__ __forceinline__ int4h hcq_rsrc(const float* base, unsigned bytes) {
-    const unsigned long long a = (unsigned long long)base;
-    return (int4h){(int)(unsigned)a, (int)((unsigned)(a >> 32) & 0xFFFFu), (int)bytes, 0x00020000};
-}
 
 // n / d for 0 <= n < 2^20 with a precomputed 1.0f / d (exact: see hc_conv_vec.hip)
 __device__ __forceinline__ int small_div_h(int n, float inv_d) { return (int)(((float)n + 0.5f) * inv_d); }
-
-// X-form m from the 4 component values (see the header)
-__device__ __forceinline__ void xforms(const float b[4], float g[8]) {
-    g[0] = b[1] + b[2];
-    g[1] = b[0] + b[3];
-    g[2] = b[0] - b[3];
-    g[3] = b[1] - b[2];
-    g[4] = b[2] - b[3];
-    g[5] = b[1] + b[0];
-    g[6] = b[2] + b[3];
-    g[7] = b[1] - b[0];
-}
 
 // KH x KW taps (1x1, 1x3, 3x3), IBC block channels per K chunk, NT1 tiles active in range 0 only + NT2 tiles active
 // in both ranges (NR = 1: quaternion, one range), XI staging items per thread.
@@ -244,8 +223,8 @@ __global__ __launch_bounds__(256, 2) void hcq_conv_kernel(const HcqP p) {
     const int comp_stride = IBC * KH * wext;
 
     // ---- weight fragments ------------------------------------------------------------------------------------------
-    const float* wbase = p.wpack + (long long)set * p.set_stride + (long long)ytile * p.ytile_stride;
-    const long long chunk_stride = p.range_stride[0] + (NR > 1 ? p.range_stride[1] : 0);
+    const float* wbase = p.wpack + (long long)set * p.t.set_stride + (long long)ytile * p.t.ytile_stride;
+    const long long chunk_stride = p.t.range_stride[0] + (NR > 1 ? p.t.range_stride[1] : 0);
 
     floatx4 acc[NT][8];
 #pragma unroll
@@ -305,11 +284,11 @@ __global__ __launch_bounds__(256, 2) void hcq_conv_kernel(const HcqP p) {
         const float* wc = wbase + (long long)ch * chunk_stride;
         const bool more = ch + 1 < nchunks;
         const float* wn = wc + chunk_stride;
-        const float* xs0 = xb + p.half_src[0] * 4 * comp_stride;
-        const float* xs1 = xb + p.half_src[1] * 4 * comp_stride;
+        const float* xs0 = xb + p.t.half_src[0] * 4 * comp_stride;
+        const float* xs1 = xb + p.t.half_src[1] * 4 * comp_stride;
         read_raw(xs0, 0);
-        if (!(HCQ_DBG & 2) || !dbg_started) xforms(raw, gm[0]);
-        if ((HCQ_DBG & 2) && !dbg_started) xforms(raw, gm[1]);
+        if (!(HCQ_DBG & 2) || !dbg_started) hcq_xforms(raw, gm[0]);
+        if ((HCQ_DBG & 2) && !dbg_started) hcq_xforms(raw, gm[1]);
         dbg_started = true;
 #pragma unroll
         for (int s = 0; s < NR * NG; ++s) {                   // k-groups of the chunk, both ranges
@@ -341,7 +320,7 @@ __global__ __launch_bounds__(256, 2) void hcq_conv_kernel(const HcqP p) {
                     if (pn < NPC) {
                         const int rn = pn / NPAIR, jn = pn - rn * NPAIR;
                         if (rn == 0) load_b1(wc, jn, m, INT{}, IT0{});
-                        else load_b1(wc + p.range_stride[0], jn, m, INT2{}, I0{});
+                        else load_b1(wc + p.t.range_stride[0], jn, m, INT2{}, I0{});
                     } else if (more) {
                         load_b1(wn, 0, m, INT{}, IT0{});
                     }
@@ -351,7 +330,7 @@ __global__ __launch_bounds__(256, 2) void hcq_conv_kernel(const HcqP p) {
                     if (HCQ_PIN) __builtin_amdgcn_sched_barrier(0);
                 }
             }
-            if (!last && !(HCQ_DBG & 2)) xforms(raw, gm[gst ^ 1]);
+            if (!last && !(HCQ_DBG & 2)) hcq_xforms(raw, gm[gst ^ 1]);
             __builtin_amdgcn_sched_barrier(0);
         }
         if (ch + 1 < nchunks && !(HCQ_DBG & 4)) store_x(buf ^ 1);
@@ -385,7 +364,7 @@ __global__ __launch_bounds__(256, 2) void hcq_conv_kernel(const HcqP p) {
     const unsigned slot_bytes = tile_bytes * NT;
     const unsigned ring0 = lds0 + (unsigned)p.ring_off;
     const float* const ringf = lds + (p.ring_off >> 2);
-    const int4h frs = hcq_rsrc(wbase, (unsigned)p.ytile_stride * 4u);     // this channel tile's fragments, all chunks and sources
+    const int4h frs = hcq_rsrc(wbase, (unsigned)p.t.ytile_stride * 4u);     // this channel tile's fragments, all chunks and sources
     unsigned foff = 1024u * (unsigned)wave + 16u * (unsigned)lane;        // of the next unit to request
     unsigned fslot = 0;                                          // slot the next request fills
     unsigned rslot = 0;                                          // slot of the unit being read
@@ -419,8 +398,8 @@ __global__ __launch_bounds__(256, 2) void hcq_conv_kernel(const HcqP p) {
     for (int ch = 0; ch < nchunks; ++ch) {
         const bool more = ch + 1 < nchunks;
         const float* xb = lds + (ch & 1) * buf_floats;
-        const float* xs0 = xb + p.half_src[0] * 4 * comp_stride;
-        const float* xs1 = xb + p.half_src[1] * 4 * comp_stride;
+        const float* xs0 = xb + p.t.half_src[0] * 4 * comp_stride;
+        const float* xs1 = xb + p.t.half_src[1] * 4 * comp_stride;
         bool xreq = false;                                       // the next chunk's input was requested at this chunk's first open
 #pragma unroll
         for (int pc = 0; pc < NPC; ++pc) {
@@ -466,8 +445,8 @@ __global__ __launch_bounds__(256, 2) void hcq_conv_kernel(const HcqP p) {
 #pragma unroll
                     for (int q = 0; q < 4; ++q) rb[q] = xs[aoff[two ? g0 + 1 : g0] + q * comp_stride];
                 }
-                xforms(ra, ga);
-                if (two) xforms(rb, gb);
+                hcq_xforms(ra, ga);
+                if (two) hcq_xforms(rb, gb);
                 dbg_raw = true;
             }
             __builtin_amdgcn_sched_barrier(0);
@@ -537,19 +516,12 @@ __global__ __launch_bounds__(256, 2) void hcq_conv_kernel(const HcqP p) {
         for (int t = 0; t < NT; ++t) {
             // a mixed-tile workgroup: accumulator slot NT1 is descriptor slot 2, the other slots are padding
             const int ds = mix_wg ? 2 : t;
-            const int ob0 = (mix_wg && t != NT1) ? -1 : p.tile_ob[ds][grp];
-            const int half = p.tile_half[ds][grp];
+            const int ob0 = (mix_wg && t != NT1) ? -1 : p.t.tile_ob[ds][grp];
+            const int half = p.t.tile_half[ds][grp];
             const bool chok = ob0 >= 0;
-            const int ob = (chok ? ob0 : 0) + (mix_wg ? 0 : ytile * p.ob_step) + (fr & 7);
+            const int ob = (chok ? ob0 : 0) + (mix_wg ? 0 : ytile * p.t.ob_step) + (fr & 7);
             floatx4 c[4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const float h0_ = 0.5f * acc[t][0][r], h1 = 0.5f * acc[t][1][r], h2 = 0.5f * acc[t][2][r], h3 = 0.5f * acc[t][3][r];
-                c[0][r] = (h3 - h0_) + (h1 + h2) + acc[t][4][r];
-                c[1][r] = (h3 - h0_) - (h1 + h2) + acc[t][5][r];
-                c[2][r] = (h3 + h0_) + (h2 - h1) + acc[t][6][r];
-                c[3][r] = (h3 + h0_) + (h1 - h2) - acc[t][7][r];
-            }
+            hcq_recombine4(acc[t], c);
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const int chn = (half * 4 + q) * p.OB + ob;           // component-major channel index
@@ -597,9 +569,9 @@ __global__ __launch_bounds__(256, 2) void hcq_conv_kernel(const HcqP p) {
             const int fr_ = e & 15, q = (e >> 4) & 3, t = e >> 6;
             const int g_ = fr_ >> 3;
             const int ds = mix_wg ? 2 : t;
-            const int ob0 = (mix_wg && t != NT1) ? -1 : p.tile_ob[ds][g_];
+            const int ob0 = (mix_wg && t != NT1) ? -1 : p.t.tile_ob[ds][g_];
             if (ob0 < 0) continue;
-            const int chn = (p.tile_half[ds][g_] * 4 + q) * p.OB + ob0 + (mix_wg ? 0 : ytile * p.ob_step) + (fr_ & 7);
+            const int chn = (p.t.tile_half[ds][g_] * 4 + q) * p.OB + ob0 + (mix_wg ? 0 : ytile * p.t.ob_step) + (fr_ & 7);
             float a1 = 0.f, a2 = 0.f;
 #pragma unroll
             for (int wv = 0; wv < 4; ++wv) {
@@ -732,8 +704,8 @@ __global__ __launch_bounds__(256, 2) void hcq_first_kernel(const HcqP p) {
     int chbase[NT];                                     // first-component channel of this lane in tile t, -1: padding
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
-        const int ob0 = p.tile_ob[t][grp];
-        chbase[t] = ob0 >= 0 ? p.tile_half[t][grp] * 4 * p.OB + ob0 + (fr & 7) : -1;
+        const int ob0 = p.t.tile_ob[t][grp];
+        chbase[t] = ob0 >= 0 ? p.t.tile_half[t][grp] * 4 * p.OB + ob0 + (fr & 7) : -1;
     }
 
 #pragma unroll
@@ -752,10 +724,10 @@ __global__ __launch_bounds__(256, 2) void hcq_first_kernel(const HcqP p) {
         // the row loop (414 VGPRs wanted)
         const float* wrow = wbase;
         asm volatile("" : "+s"(wrow));
-        const float* xs0 = lds + r * wext + p.half_src[0] * 4 * comp_stride;
-        const float* xs1 = lds + r * wext + p.half_src[1] * 4 * comp_stride;
+        const float* xs0 = lds + r * wext + p.t.half_src[0] * 4 * comp_stride;
+        const float* xs1 = lds + r * wext + p.t.half_src[1] * 4 * comp_stride;
         read_raw(xs0, 0);
-        xforms(raw, gm[0]);
+        hcq_xforms(raw, gm[0]);
 #pragma unroll
         for (int s = 0; s < NR * NG; ++s) {
             const int rr = s / NG, g = s - rr * NG;
@@ -786,13 +758,13 @@ __global__ __launch_bounds__(256, 2) void hcq_first_kernel(const HcqP p) {
                     if (pn < NPC) {
                         const int rn = pn / NPAIR, jn = pn - rn * NPAIR;
                         if (rn == 0) load_b1(wrow, jn, m, INT{});
-                        else load_b1(wrow + p.range_stride[0], jn, m, INT2{});
+                        else load_b1(wrow + p.t.range_stride[0], jn, m, INT2{});
                     } else if (more) {
                         load_b1(wrow, 0, m, INT{});               // the next row starts with the same fragments
                     }
                 }
             }
-            if (!last) xforms(raw, gm[gst ^ 1]);
+            if (!last) hcq_xforms(raw, gm[gst ^ 1]);
             __builtin_amdgcn_sched_barrier(0);
         }
         // ---- this row's results ------------------------------------------------------------------------------------
@@ -800,14 +772,7 @@ __global__ __launch_bounds__(256, 2) void hcq_first_kernel(const HcqP p) {
 #pragma unroll
         for (int t = 0; t < NT; ++t) {
             floatx4 c[4];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const float h0_ = 0.5f * acc[t][0][e], h1 = 0.5f * acc[t][1][e], h2 = 0.5f * acc[t][2][e], h3 = 0.5f * acc[t][3][e];
-                c[0][e] = (h3 - h0_) + (h1 + h2) + acc[t][4][e];
-                c[1][e] = (h3 - h0_) - (h1 + h2) + acc[t][5][e];
-                c[2][e] = (h3 + h0_) + (h2 - h1) + acc[t][6][e];
-                c[3][e] = (h3 + h0_) + (h1 - h2) - acc[t][7][e];
-            }
+            hcq_recombine4(acc[t], c);
             if (chbase[t] >= 0) {
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
@@ -832,9 +797,9 @@ __global__ __launch_bounds__(256, 2) void hcq_first_kernel(const HcqP p) {
         for (int e = tid; e < NT * 4 * 16; e += 256) {
             const int fr_ = e & 15, q = (e >> 4) & 3, t = e >> 6;
             const int g_ = fr_ >> 3;
-            const int ob0 = p.tile_ob[t][g_];
+            const int ob0 = p.t.tile_ob[t][g_];
             if (ob0 < 0) continue;
-            const int chn = (p.tile_half[t][g_] * 4 + q) * p.OB + ob0 + (fr_ & 7);
+            const int chn = (p.t.tile_half[t][g_] * 4 + q) * p.OB + ob0 + (fr_ & 7);
             float a1 = 0.f, a2 = 0.f;
 #pragma unroll
             for (int wv = 0; wv < 4; ++wv)
@@ -986,8 +951,8 @@ __global__ __launch_bounds__(256, 3) void hcq_first_pool_kernel(const HcqP p, co
         constexpr bool BOTH = NR == 2 && T >= NT1;            // this tile's channels take the second K range too
         constexpr int NRT = BOTH ? 2 : 1;
         constexpr int NPCT = NRT * NPAIR;
-        const int ob0 = p.tile_ob[T][grp];
-        const int chb = ob0 >= 0 ? p.tile_half[T][grp] * 4 * p.OB + ob0 + (fr & 7) : -1;
+        const int ob0 = p.t.tile_ob[T][grp];
+        const int chb = ob0 >= 0 ? p.t.tile_half[T][grp] * 4 * p.OB + ob0 + (fr & 7) : -1;
         // fragments of tile T only (range 0 blocks hold NT tiles per (pair, form, lane), range 1 blocks NT2): into LDS
         __syncthreads();                                  // everybody is done with the previous tile's fragments
         {
@@ -1000,7 +965,7 @@ __global__ __launch_bounds__(256, 3) void hcq_first_pool_kernel(const HcqP p, co
                 const int e = tid + 256 * it;
                 const int ln = e & 63, jm = e >> 6;       // jm = pair * 8 + form over both ranges
                 const int rr = jm / (NPAIR * 8), jm0 = jm - rr * (NPAIR * 8);
-                const float* blk = rr == 0 ? wbase : wbase + p.range_stride[0];
+                const float* blk = rr == 0 ? wbase : wbase + p.t.range_stride[0];
                 const int ntr = rr == 0 ? NT : NT2, tt = rr == 0 ? T : T - NT1;
                 tmp[it] = *reinterpret_cast<const float2*>(blk + ((long long)jm0 * 64 + ln) * (2 * ntr) + 2 * tt);
             }
@@ -1028,10 +993,10 @@ __global__ __launch_bounds__(256, 3) void hcq_first_pool_kernel(const HcqP p, co
 #pragma unroll
             for (int m = 0; m < 8; ++m) acc[m] = (floatx4){0.f, 0.f, 0.f, 0.f};
             const bool more = r + 1 < R;
-            const float* xs0 = lds + r * wext + p.half_src[0] * 4 * comp_stride;
-            const float* xs1 = lds + r * wext + p.half_src[1] * 4 * comp_stride;
+            const float* xs0 = lds + r * wext + p.t.half_src[0] * 4 * comp_stride;
+            const float* xs1 = lds + r * wext + p.t.half_src[1] * 4 * comp_stride;
             read_raw(xs0, 0);
-            xforms(raw, gm[0]);
+            hcq_xforms(raw, gm[0]);
 #pragma unroll
             for (int s = 0; s < NRT * NG; ++s) {
                 const int rr = s / NG, g = s - rr * NG;
@@ -1053,19 +1018,12 @@ __global__ __launch_bounds__(256, 3) void hcq_first_pool_kernel(const HcqP p, co
                         else if (more) load_b1(0, m);
                     }
                 }
-                if (!last) xforms(raw, gm[gst ^ 1]);
+                if (!last) hcq_xforms(raw, gm[gst ^ 1]);
                 __builtin_amdgcn_sched_barrier(0);
             }
             // ---- this row of this tile: components, store, statistics, window maximum ------------------------------
             floatx4 c[4];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const float h0_ = 0.5f * acc[0][e], h1 = 0.5f * acc[1][e], h2 = 0.5f * acc[2][e], h3 = 0.5f * acc[3][e];
-                c[0][e] = (h3 - h0_) + (h1 + h2) + acc[4][e];
-                c[1][e] = (h3 - h0_) - (h1 + h2) + acc[5][e];
-                c[2][e] = (h3 + h0_) + (h2 - h1) + acc[6][e];
-                c[3][e] = (h3 + h0_) + (h1 - h2) - acc[7][e];
-            }
+            hcq_recombine4(acc, c);
             if (chb >= 0) {
                 const unsigned pos_off = (unsigned)(h0 + r) * (unsigned)p.W + (unsigned)(w0 + wave * 16 + fk * 4);
 #pragma unroll
@@ -1149,9 +1107,9 @@ __global__ __launch_bounds__(256, 3) void hcq_first_pool_kernel(const HcqP p, co
         for (int e = tid; e < NT * 4 * 16; e += 256) {
             const int fr_ = e & 15, q = (e >> 4) & 3, t = e >> 6;
             const int g_ = fr_ >> 3;
-            const int ob0 = p.tile_ob[t][g_];
+            const int ob0 = p.t.tile_ob[t][g_];
             if (ob0 < 0) continue;
-            const int chn = (p.tile_half[t][g_] * 4 + q) * p.OB + ob0 + (fr_ & 7);
+            const int chn = (p.t.tile_half[t][g_] * 4 + q) * p.OB + ob0 + (fr_ & 7);
             float a1 = 0.f, a2 = 0.f;
 #pragma unroll
             for (int wv = 0; wv < 4; ++wv) {
@@ -1177,35 +1135,31 @@ struct HcqPackP {
     float* out;
     int A, mode;
     int OA, IA, taps;            // of the CONVOLUTION (not swapped for the data gradient)
-    int IBC, nch, NR, NT1, NT2, NG, NPAIR;
-    int half_src[2];
-    int nreg;                    // regular channel tiles per set
-    int has_mix;
+    int IBC, nch, NG, NPAIR;
     int nsets;                   // forward pairs: separate outputs
     int nsrc;                    // gradient pairs: two (source, weight set) along K
-    int ob_step;
-    int tile_half[3][2], tile_ob[3][2];
-    long long range_stride[2], ytile_stride, set_stride, total;
+    HcqTiles t;
+    long long total;
 };
 
 __device__ __forceinline__ float hcq_pack_value(const HcqPackP& p, long long idx) {
     // 32-bit index arithmetic (the host keeps every buffer below 2^31 floats): the 64-bit divisions this decode started
     // with were most of the kernel's 60 us
-    const int NT = p.NT1 + p.NT2;
-    const unsigned set_stride = (unsigned)p.set_stride, ytile_stride = (unsigned)p.ytile_stride;
+    const int NT = p.t.NT1 + p.t.NT2;
+    const unsigned set_stride = (unsigned)p.t.set_stride, ytile_stride = (unsigned)p.t.ytile_stride;
     const unsigned set = (unsigned)idx / set_stride;
     unsigned r0 = (unsigned)idx - set * set_stride;
     const int ytile = (int)(r0 / ytile_stride);
     r0 -= (unsigned)ytile * ytile_stride;
-    const bool mix = p.has_mix && ytile == p.nreg;          // the mixed channel tile: same layout, other descriptors
-    const unsigned rs[2] = {(unsigned)p.range_stride[0], (unsigned)p.range_stride[1]};
-    const unsigned chunk_stride = rs[0] + (p.NR > 1 ? rs[1] : 0);
+    const bool mix = p.t.mix && ytile == p.t.nreg;          // the mixed channel tile: same layout, other descriptors
+    const unsigned rs[2] = {(unsigned)p.t.range_stride[0], (unsigned)p.t.range_stride[1]};
+    const unsigned chunk_stride = rs[0] + (p.t.NR > 1 ? rs[1] : 0);
     const int chs = (int)(r0 / chunk_stride);            // chunk over all sources
     r0 -= (unsigned)chs * chunk_stride;
     const int srcsel = chs / p.nch, ch = chs - srcsel * p.nch;
     const int range = (r0 >= rs[0]) ? 1 : 0;
     if (range) r0 -= rs[0];
-    const int ntr = range ? p.NT2 : NT;
+    const int ntr = range ? p.t.NT2 : NT;
     const int per_m = 64 * 2 * ntr;
     const int per_pair = 8 * per_m;
     const int j = (int)(r0 / (unsigned)per_pair);
@@ -1220,16 +1174,16 @@ __device__ __forceinline__ float hcq_pack_value(const HcqPackP& p, long long idx
     if (g >= p.NG) return 0.f;
     const int kq = 4 * g + k;
     if (kq >= p.IBC * p.taps) return 0.f;                  // padding of the last k-group
-    const int tf = range ? p.NT1 + t : t;                  // tile (accumulator slot) of the workgroup
+    const int tf = range ? p.t.NT1 + t : t;                  // tile (accumulator slot) of the workgroup
     const int ds = mix ? 2 : tf;                           // descriptor slot: a mixed workgroup's slot NT1 is the mixed
     const int grp = n >> 3;                                // tile, its other slots are padding
-    const int ob0 = (mix && tf != p.NT1) ? -1 : p.tile_ob[ds][grp];
+    const int ob0 = (mix && tf != p.t.NT1) ? -1 : p.t.tile_ob[ds][grp];
     if (ob0 < 0) return 0.f;
-    const int dblk = ob0 + (mix ? 0 : ytile * p.ob_step) + (n & 7);     // destination block channel
+    const int dblk = ob0 + (mix ? 0 : ytile * p.t.ob_step) + (n & 7);     // destination block channel
     const int kbl = kq / p.taps;
     const int tap = kq - kbl * p.taps;
     const int sblk = ch * p.IBC + kbl;                                  // source block channel
-    const int hd = p.tile_half[ds][grp], hs = p.half_src[range];
+    const int hd = p.t.tile_half[ds][grp], hs = p.t.half_src[range];
     // which quaternion of the dual quaternion couples (source half hs) -> (destination half hd)
     int qsel = 0;                                                        // 0: Q, 1: Q2, -1: structural zero
     if (p.A == 8) {
@@ -1247,16 +1201,7 @@ __device__ __forceinline__ float hcq_pack_value(const HcqPackP& p, long long idx
 #pragma unroll
     for (int c = 0; c < 4; ++c) a[c] = w.p[qsel * 4 + c][e];
     if (p.mode == 1) { a[1] = -a[1]; a[2] = -a[2]; a[3] = -a[3]; }      // conjugate
-    switch (m) {
-        case 0: return a[3] + a[1];
-        case 1: return a[0] - a[2];
-        case 2: return a[0] + a[2];
-        case 3: return a[3] - a[1];
-        case 4: return a[3] - a[2];
-        case 5: return a[1] + a[0];
-        case 6: return a[0] - a[1];
-        default: return a[3] + a[2];
-    }
+    return hcq_form_f(m, a);
 }
 
 __global__ __launch_bounds__(256) void hcq_pack_kernel(const HcqPackP p) {
@@ -1280,23 +1225,51 @@ __global__ __launch_bounds__(256) void hcq_pack_flat_kernel(const HcqPackP* __re
     if (idx < p.total) p.out[idx] = hcq_pack_value(p, idx);
 }
 
-// (the (blocks, entries) form: blockIdx.y = table entry, blockIdx.x = 256-float block of that entry's buffer)
-__global__ __launch_bounds__(256) void hcq_pack_table_kernel(const HcqPackP* __restrict__ table, int nentries) {
-    const int e = blockIdx.y;
-    if (e >= nentries) return;
-    const HcqPackP& p = table[e];
-    for (long long idx = (long long)blockIdx.x * 256 + threadIdx.x; idx < p.total; idx += (long long)gridDim.x * 256)
-        p.out[idx] = hcq_pack_value(p, idx);
-}
-
 // ---------------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------------
+// The instantiations, once: taps, K chunk, staging items per thread of the dual-quaternion and of the quaternion kernels
+// (0: none).  XI is fixed by (taps, IBC, algebra) except for the dilated 1x3 layers (halo width): a plan takes the first
+// row whose XI is enough.
+struct HcqInst { int KH, KW, IBC, XI8, XI4; };
+constexpr HcqInst HCQ_INST[] = {{1, 3, 8, 5, 3},  {1, 3, 8, 7, 5},   {1, 3, 8, 9, 0}, {1, 3, 4, 6, 3}, {1, 1, 16, 8, 4},
+                                  {1, 1, 24, 12, 6}, {1, 1, 8, 4, 2},   {3, 3, 4, 7, 4}, {3, 3, 2, 4, 2}, {3, 3, 1, 2, 1}};
+// ... and the channel-tile programs every row exists in (MX: launches with mixed-tile workgroups)
+struct HcqTileV { int NT1, NT2, NR; bool MX; };
+constexpr HcqTileV HCQ_TILEV[] = {{1, 2, 2, false}, {1, 1, 2, true}, {1, 1, 2, false}, {2, 0, 1, false}, {1, 0, 1, false}};
+constexpr int HCQ_FIRST_R = 8;   // image rows per workgroup of hcq_first_kernel / hcq_first_pool_kernel (a pooling window)
+
+constexpr int HCQ_NINST = sizeof(HCQ_INST) / sizeof(HCQ_INST[0]), HCQ_NTILEV = sizeof(HCQ_TILEV) / sizeof(HCQ_TILEV[0]);
+
+// FN<row, variant>::run(args...) for the (row, variant) a plan resolved
+static_assert(HCQ_NINST == 10 && HCQ_NTILEV == 5, "SELD_HCQ_DISPATCH lists the rows 0..9 and the tile programs 0..4");
+#define SELD_HCQ_V(I, FN, ...)                                                          \
+    case I:                                                                             \
+        switch (pl.variant) {                                                           \
+            case 0: return FN<I, 0>::run(__VA_ARGS__);                                  \
+            case 1: return FN<I, 1>::run(__VA_ARGS__);                                  \
+            case 2: return FN<I, 2>::run(__VA_ARGS__);                                  \
+            case 3: return FN<I, 3>::run(__VA_ARGS__);                                  \
+            case 4: return FN<I, 4>::run(__VA_ARGS__);                                  \
+        }                                                                               \
+        break;
+#define SELD_HCQ_DISPATCH(FN, ...)                                                                                     \
+    switch (pl.row) {                                                                                                  \
+        SELD_HCQ_V(0, FN, __VA_ARGS__) SELD_HCQ_V(1, FN, __VA_ARGS__) SELD_HCQ_V(2, FN, __VA_ARGS__)                   \
+        SELD_HCQ_V(3, FN, __VA_ARGS__) SELD_HCQ_V(4, FN, __VA_ARGS__) SELD_HCQ_V(5, FN, __VA_ARGS__)                   \
+        SELD_HCQ_V(6, FN, __VA_ARGS__) SELD_HCQ_V(7, FN, __VA_ARGS__) SELD_HCQ_V(8, FN, __VA_ARGS__)                   \
+        SELD_HCQ_V(9, FN, __VA_ARGS__)                                                                                 \
+    }
+
+// Everything the entry points need to know about (desc, mode, npair): which kernel, its grid and LDS, its arguments and
+// the arguments of the kernel that packs its weights.
 struct HcqPlan {
     int ok;
-    int KH, KW, IBC, NT1, NT2, NR, XI, mix;
-    int gf;                      // hcq_conv_kernel with per-wave global fragment loads (no ring)
-    int first_rows;              // > 0: hcq_first_kernel walks this many image rows per workgroup
+    int row, variant;            // HCQ_INST / HCQ_TILEV
+    int XI;                      // of the instantiation
+    bool gf;                     // hcq_conv_kernel with per-wave global fragment loads (no ring)
+    int first_rows;              // > 0: hcq_first_kernel (pool: hcq_first_pool_kernel) walks this many image rows per workgroup
+    bool pool;
     HcqP kp;
     HcqPackP pp;
     size_t pack_floats;
@@ -1308,25 +1281,18 @@ struct HcqPlan {
 // mode 1 data gradient (npair: 1, or 2 = sum of the gradients of two convolutions w.r.t. their common input).
 // mode 2 = mode 0 for the pooling first-stage kernel (hcq_first_pool_kernel): same packed forms, and the 8-channel
 // dual-quaternion layer is NOT left to the short-K kernel.
-static HcqPlan hcq_plan(const seld_conv_desc* d, int mode, int npair) {
+// first_ok = false: never the row-walking first-layer kernel (it takes no addend / accumulate epilogue).
+static HcqPlan hcq_plan(const seld_conv_desc* d, int mode, int npair, bool first_ok = true) {
     HcqPlan pl{};
     const bool pool = mode == 2;
     if (pool) mode = 0;
     const int A = d->algebra;
-    if (A != 4 && A != 8) return pl;
-    if (d->stride[0] != 1 || d->stride[1] != 1 || d->dil[0] != 1) return pl;
-    int o[2];
-    hc_out_shape(d, o);
-    if (o[0] != d->in[0] || o[1] != d->in[1]) return pl;                     // 'same' convolutions only
+    if ((A != 4 && A != 8) || !hcq_same_geometry(d)) return pl;
     const int KH = d->k[0], KW = d->k[1];
-    if (!((KH == 1 && (KW == 1 || KW == 3)) || (KH == 3 && KW == 3))) return pl;
-    if (2 * d->pad[1] != d->dil[1] * (KW - 1) || 2 * d->pad[0] != (KH - 1)) return pl;
-    if (KW == 1 && d->dil[1] != 1) return pl;
     const int W = d->in[1], Himg = d->in[0];
     if (W % 64) return pl;
     const int Csrc = mode == 0 ? d->Cin : d->Cout, Cdst = mode == 0 ? d->Cout : d->Cin;
     const int IB = Csrc / A, OB = Cdst / A;
-    if ((long long)d->N * Csrc * Himg * W * 4 >= 0xFFFFFFF0ll || (long long)d->N * Cdst * Himg * W * 4 >= 0xFFFFFFF0ll) return pl;
     const int taps = KH * KW;
     const int nsets = mode == 0 ? npair : 1, nsrc = mode == 1 ? npair : 1;
     const int dil = KW == 3 ? d->dil[1] : 0;
@@ -1353,224 +1319,192 @@ static HcqPlan hcq_plan(const seld_conv_desc* d, int mode, int npair) {
         !env().conv_no_smallk) return pl;
     // channel tiles
     HcqP& k = pl.kp;
-    int NT1, NT2, NR, nreg, ob_step, mix = 0;
-    for (int t = 0; t < 3; ++t)
-        for (int g = 0; g < 2; ++g) { k.tile_half[t][g] = 0; k.tile_ob[t][g] = -1; }
+    HcqTiles& t = k.t;
+    for (int i = 0; i < 3; ++i)
+        for (int g = 0; g < 2; ++g) { t.tile_half[i][g] = 0; t.tile_ob[i][g] = -1; }
     if (A == 8) {
-        NR = 2;
+        t.NR = 2;
         // forward: range 0 = primal source (both destination halves), range 1 = dual source (dual destination only)
         // gradient: range 0 = dual source (both halves), range 1 = primal source (primal destination only)
         const int both = mode == 0 ? 1 : 0;           // destination half active in both ranges
         const int once = 1 - both;
-        k.half_src[0] = mode == 0 ? 0 : 1;
-        k.half_src[1] = 1 - k.half_src[0];
+        t.half_src[0] = mode == 0 ? 0 : 1;
+        t.half_src[1] = 1 - t.half_src[0];
         if (OB % 16 != 0 && OB % 16 != 8) return pl;
-        NT1 = 1; NT2 = 1; nreg = OB / 16; ob_step = 16;
-        k.tile_half[0][0] = k.tile_half[0][1] = once; k.tile_ob[0][0] = 0; k.tile_ob[0][1] = 8;
-        k.tile_half[1][0] = k.tile_half[1][1] = both; k.tile_ob[1][0] = 0; k.tile_ob[1][1] = 8;
+        t.NT1 = 1; t.NT2 = 1; t.nreg = OB / 16; t.ob_step = 16;
+        t.tile_half[0][0] = t.tile_half[0][1] = once; t.tile_ob[0][0] = 0; t.tile_ob[0][1] = 8;
+        t.tile_half[1][0] = t.tile_half[1][1] = both; t.tile_ob[1][0] = 0; t.tile_ob[1][1] = 8;
         if (OB % 16 == 8) {                           // the last 8 block channels of both halves share one tile
-            k.tile_half[2][0] = once; k.tile_ob[2][0] = OB - 8;
-            k.tile_half[2][1] = both; k.tile_ob[2][1] = OB - 8;
+            t.tile_half[2][0] = once; t.tile_ob[2][0] = OB - 8;
+            t.tile_half[2][1] = both; t.tile_ob[2][1] = OB - 8;
             // 24 block channels: either ONE workgroup per position tile with three tiles (24 accumulators, the input
             // staged once: cnn.1 949 us against 1139), or the mixed tile in workgroups of its own (twice the
             // workgroups for layers with few position tiles: TCN data gradient 47.5 us against 68.6).  A forward PAIR
             // brings its own factor of two (two weight sets): skip || residual at batch 32 (256 position tiles) 39.8 ->
             // 32.3 us as 512 three-tile workgroups instead of 1024 two-tile ones, a third of them half padding
             const long long ptiles = (long long)d->N * Himg * W / 64;
-            if (OB == 24 && ptiles * nsets >= 512) { NT2 = 2; ob_step = 0; }
-            else mix = 1;
+            if (OB == 24 && ptiles * nsets >= 512) { t.NT2 = 2; t.ob_step = 0; }
+            else t.mix = 1;
         }
-        if (nreg == 0) return pl;
+        if (t.nreg == 0) return pl;
     } else {
-        NR = 1; NT2 = 0;
-        k.half_src[0] = k.half_src[1] = 0;
-        if (OB % 32 == 0) { NT1 = 2; nreg = OB / 32; ob_step = 32; }
-        else if (OB % 16 == 0) { NT1 = 1; nreg = OB / 16; ob_step = 16; }
+        t.NR = 1; t.NT2 = 0;
+        t.half_src[0] = t.half_src[1] = 0;
+        if (OB % 32 == 0) { t.NT1 = 2; t.nreg = OB / 32; t.ob_step = 32; }
+        else if (OB % 16 == 0) { t.NT1 = 1; t.nreg = OB / 16; t.ob_step = 16; }
         else return pl;
-        for (int t = 0; t < NT1; ++t) { k.tile_ob[t][0] = 16 * t; k.tile_ob[t][1] = 16 * t + 8; }
+        for (int i = 0; i < t.NT1; ++i) { t.tile_ob[i][0] = 16 * i; t.tile_ob[i][1] = 16 * i + 8; }
     }
-    const int NT = NT1 + NT2;
-    // LDS of hcq_conv_kernel = input buffers + fragment ring of two slots (a slot: the 8 forms of a pair of k-groups,
-    // 4 KB per tile, or 4 forms).  The chunk stays the one chosen above (with two K ranges the chunk size decides the
-    // order in which an accumulator meets them, i.e. the bits of the result).  The ring must not cost a resident workgroup
-    // per CU (160 KB; registers allow 3 at most): whole pairs if they keep the count, else half pairs if they do (one
-    // more barrier per pair).  Two exceptions, both measured (profiles/hcq_fragment_ring_shapes.md):
-    //   * launches with mixed-tile workgroups (a third of their workgroups run one tile in range 0: 8 MFMAs per half-pair
-    //     unit) are faster with whole pairs at two workgroups per CU than with half pairs at three: TCN 1x3 data
-    //     gradient, halo 8, 39.8 us against 43.4 (41 to 42 before the ring);
-    //   * quaternion 1-D layers keep per-wave global loads (GF): one range, one or two tiles and few chunks -- launches
-    //     of about 10 us in which a barrier per pair costs what the L1 traffic saves (+0.2 ... -1.5 us with the ring).
-    // A 1-D shape that no ring fits without losing a workgroup (1x3 forward, halo 12 to 16 or above 56) keeps global
-    // loads as well; a 3x3 shape would take half pairs regardless (none does at the networks' widths).
-    int half_slots = 0;
-    bool gf = A == 4 && KH == 1;
-    if (!pool && !gf) {
-        const auto wgs = [](size_t bytes) { const size_t n = (size_t)160 * 1024 / (bytes < 8192 ? 8192 : bytes); return n > 3 ? (size_t)3 : n; };
-        const size_t wgs0 = wgs(smem);
-        const size_t whole = (size_t)2 * 4096 * NT, halves = (size_t)2 * 2048 * NT;
-        if (wgs(smem + whole) >= wgs0 || (mix && wgs(smem + whole) >= 2)) half_slots = 0;
-        else if (wgs(smem + halves) >= wgs0 || KH != 1) half_slots = 1;
-        else gf = true;
-        if (!gf) {
-            k.ring_off = (int)smem;
-            k.half_slots = half_slots;
-            smem += half_slots ? halves : whole;
-        }
+    const int NT = t.NT1 + t.NT2, mix = t.mix;
+    // ---- the instantiation: tile program and table row ---------------------------------------------------------------
+    pl.variant = t.NR == 2 ? (t.NT2 == 2 ? 0 : (mix ? 1 : 2)) : (t.NT1 == 2 ? 3 : 4);
+    const int XI = (A * IBC * KH * (wext / 4) + 255) / 256;                   // staging items per thread
+    pl.row = -1;
+    for (int i = 0; i < HCQ_NINST && pl.row < 0; ++i) {
+        const HcqInst& r = HCQ_INST[i];
+        if (r.KH == KH && r.KW == KW && r.IBC == IBC && XI <= (t.NR == 2 ? r.XI8 : r.XI4)) pl.row = i;
     }
-    const int rows = A * IBC * KH;
-    const int items = rows * (wext / 4);
-    const int XI = (items + 255) / 256;
-    if (smem < 8 * 1024) smem = 8 * 1024;                                     // statistics scratch of the epilogue
+    if (pl.row < 0) return pl;
+    pl.XI = t.NR == 2 ? HCQ_INST[pl.row].XI8 : HCQ_INST[pl.row].XI4;
+    k.ytiles = t.nreg + mix; k.mix_ytile = mix ? t.nreg : -1;
+    const long long ptot = (long long)d->N * Himg * W;
     const int NG = (IBC * taps + 3) / 4, NPAIR = (NG + 1) / 2;
+    // first layers: one chunk, one channel tile, one weight set -> the row-walking kernels
+    if (first_ok && mode == 0 && taps == 9 && IBC == IB && IB <= 2 && k.ytiles == 1 && nsets == 1 && !mix && Himg % HCQ_FIRST_R == 0 &&
+        wext == 72) {
+        pl.first_rows = HCQ_FIRST_R;
+        pl.grid = dim3((unsigned)(ptot / 64 / HCQ_FIRST_R), 1, 1);
+        const size_t rows = (size_t)A * IBC * (HCQ_FIRST_R + 2) * wext;
+        pl.smem = pool ? (rows + (size_t)NT * 4 * 4 * 16 * 2 + (size_t)t.NR * NPAIR * 8 * 64 * 2) * sizeof(float)   // + statistics + one tile's fragments
+                       : (rows + 4 * NT * 4 * 64 * 2) * sizeof(float);                                              // + statistics slots
+    } else {
+        if (pool) return pl;
+        // LDS of hcq_conv_kernel = input buffers + fragment ring of two slots (a slot: the 8 forms of a pair of k-groups,
+        // 4 KB per tile, or 4 forms).  The chunk stays the one chosen above (with two K ranges the chunk size decides the
+        // order in which an accumulator meets them, i.e. the bits of the result).  The ring must not cost a resident workgroup
+        // per CU (160 KB; registers allow 3 at most): whole pairs if they keep the count, else half pairs if they do (one
+        // more barrier per pair).  Two exceptions, both measured (profiles/hcq_fragment_ring_shapes.md):
+        //   * launches with mixed-tile workgroups (a third of their workgroups run one tile in range 0: 8 MFMAs per half-pair
+        //     unit) are faster with whole pairs at two workgroups per CU than with half pairs at three: TCN 1x3 data
+        //     gradient, halo 8, 39.8 us against 43.4 (41 to 42 before the ring);
+        //   * quaternion 1-D layers keep per-wave global loads (GF): one range, one or two tiles and few chunks -- launches
+        //     of about 10 us in which a barrier per pair costs what the L1 traffic saves (+0.2 ... -1.5 us with the ring).
+        // A 1-D shape that no ring fits without losing a workgroup (1x3 forward, halo 12 to 16 or above 56) keeps global
+        // loads as well; a 3x3 shape would take half pairs regardless (none does at the networks' widths).
+        pl.gf = A == 4 && KH == 1;
+        if (!pl.gf) {
+            const auto wgs = [](size_t bytes) { const size_t n = (size_t)160 * 1024 / (bytes < 8192 ? 8192 : bytes); return n > 3 ? (size_t)3 : n; };
+            const size_t wgs0 = wgs(smem);
+            const size_t whole = (size_t)2 * 4096 * NT, halves = (size_t)2 * 2048 * NT;
+            int half_slots = 0;
+            if (wgs(smem + whole) >= wgs0 || (mix && wgs(smem + whole) >= 2)) half_slots = 0;
+            else if (wgs(smem + halves) >= wgs0 || KH != 1) half_slots = 1;
+            else pl.gf = true;
+            if (!pl.gf) {
+                k.ring_off = (int)smem;
+                k.half_slots = half_slots;
+                smem += half_slots ? halves : whole;
+            }
+        }
+        if (smem < 8 * 1024) smem = 8 * 1024;                                 // statistics scratch of the epilogue
+        pl.grid = dim3((unsigned)(ptot / 64), (unsigned)(k.ytiles * nsets), 1);
+        pl.smem = smem;
+    }
+    pl.pool = pool;
     k.A = A; k.N = d->N; k.Csrc = Csrc; k.Cdst = Cdst; k.IB = IB; k.OB = OB;
     k.W = W; k.Himg = Himg; k.dil = dil; k.dpad = dpad; k.wext = wext; k.nch = IB / IBC;
     k.nsrc = nsrc;
-    k.ytiles = nreg + mix; k.mix_ytile = mix ? nreg : -1; k.ob_step = ob_step;
-    k.range_stride[0] = (long long)NPAIR * 8 * 64 * 2 * NT;
-    k.range_stride[1] = (long long)NPAIR * 8 * 64 * 2 * NT2;
-    k.ytile_stride = (long long)nsrc * k.nch * (k.range_stride[0] + (NR > 1 ? k.range_stride[1] : 0));
-    k.set_stride = (long long)(nreg + mix) * k.ytile_stride;
-    pl.pack_floats = (size_t)k.set_stride * nsets;
+    t.range_stride[0] = (long long)NPAIR * 8 * 64 * 2 * NT;
+    t.range_stride[1] = (long long)NPAIR * 8 * 64 * 2 * t.NT2;
+    t.ytile_stride = (long long)nsrc * k.nch * (t.range_stride[0] + (t.NR > 1 ? t.range_stride[1] : 0));
+    t.set_stride = (long long)k.ytiles * t.ytile_stride;
+    pl.pack_floats = (size_t)t.set_stride * nsets;
     HcqPackP& q = pl.pp;
     q.A = A; q.mode = mode; q.OA = d->Cout / A; q.IA = d->Cin / A; q.taps = taps;
-    q.IBC = IBC; q.nch = k.nch; q.NR = NR; q.NT1 = NT1; q.NT2 = NT2; q.NG = NG; q.NPAIR = NPAIR;
-    q.half_src[0] = k.half_src[0]; q.half_src[1] = k.half_src[1];
-    q.nreg = nreg; q.has_mix = mix; q.nsets = nsets; q.nsrc = nsrc; q.ob_step = ob_step;
-    for (int t = 0; t < 3; ++t)
-        for (int g = 0; g < 2; ++g) { q.tile_half[t][g] = k.tile_half[t][g]; q.tile_ob[t][g] = k.tile_ob[t][g]; }
-    q.range_stride[0] = k.range_stride[0]; q.range_stride[1] = k.range_stride[1];
-    q.ytile_stride = k.ytile_stride; q.set_stride = k.set_stride; q.total = (long long)pl.pack_floats;
-    pl.KH = KH; pl.KW = KW; pl.IBC = IBC; pl.NT1 = NT1; pl.NT2 = NT2; pl.NR = NR; pl.XI = XI; pl.mix = mix;
-    pl.gf = gf ? 1 : 0;
-    const long long ptot = (long long)d->N * Himg * W;
-    pl.grid = dim3((unsigned)(ptot / 64), (unsigned)(k.ytiles * nsets), 1);
-    pl.smem = smem;
-    // first layers: one chunk, one channel tile, one weight set -> the row-walking kernel
-    constexpr int FIRST_R = 8;
-    if (mode == 0 && taps == 9 && IBC == IB && IB <= 2 && k.ytiles == 1 && nsets == 1 && !mix && Himg % FIRST_R == 0 && wext == 72) {
-        pl.first_rows = FIRST_R;
-        pl.grid = dim3((unsigned)(ptot / 64 / FIRST_R), 1, 1);
-        pl.smem = ((size_t)A * IBC * (FIRST_R + 2) * wext + 4 * NT * 4 * 64 * 2) * sizeof(float);   // rows + statistics slots
-    }
-    if (pool && !pl.first_rows) return HcqPlan{};
+    q.IBC = IBC; q.nch = k.nch; q.NG = NG; q.NPAIR = NPAIR; q.nsets = nsets; q.nsrc = nsrc;
+    q.t = t;
+    q.total = (long long)pl.pack_floats;
     pl.ok = 1;
     return pl;
 }
 
-// The instantiation a plan runs: staging items per thread are fixed by (taps, IBC, algebra) except for the dilated 1x3
-// layers (halo width).  Returns 0 if there is none.
-struct HcqKern { int KH, KW, IBC, NT1, NT2, NR, XI; };
-static int hcq_pick(const HcqPlan& pl, HcqKern* k) {
-    int xi8 = 0, xi4 = 0;
-    if (pl.KH == 1 && pl.KW == 3 && pl.IBC == 8) {
-        xi8 = pl.XI <= 5 ? 5 : (pl.XI <= 7 ? 7 : 9);
-        xi4 = pl.XI <= 3 ? 3 : 5;
-    } else if (pl.KH == 1 && pl.KW == 3 && pl.IBC == 4) { xi8 = 6; xi4 = 3; }
-    else if (pl.KH == 1 && pl.KW == 1 && pl.IBC == 16) { xi8 = 8; xi4 = 4; }
-    else if (pl.KH == 1 && pl.KW == 1 && pl.IBC == 24) { xi8 = 12; xi4 = 6; }
-    else if (pl.KH == 1 && pl.KW == 1 && pl.IBC == 8) { xi8 = 4; xi4 = 2; }
-    else if (pl.KH == 3 && pl.KW == 3 && pl.IBC == 4) { xi8 = 7; xi4 = 4; }
-    else if (pl.KH == 3 && pl.KW == 3 && pl.IBC == 2) { xi8 = 4; xi4 = 2; }
-    else if (pl.KH == 3 && pl.KW == 3 && pl.IBC == 1) { xi8 = 2; xi4 = 1; }
-    else return 0;
-    const int xi = pl.NR == 2 ? xi8 : xi4;
-    if (pl.XI > xi) return 0;
-    *k = HcqKern{pl.KH, pl.KW, pl.IBC, pl.NT1, pl.NT2, pl.NR, xi};
-    return 1;
-}
-
-template <int KH, int KW, int IBC, int NT1, int NT2, int NR, int XI, bool MX = false, bool GF = false>
-static int hcq_launch_one(const HcqPlan& pl, hipStream_t st) {
-    auto kern = hcq_conv_kernel<KH, KW, IBC, NT1, NT2, NR, XI, MX, GF>;
+template <typename Kern, typename... Args>
+static int hcq_launch_kernel(Kern kern, const HcqPlan& pl, hipStream_t st, const Args&... args) {
     if (pl.smem > 64 * 1024 &&
         hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.smem) != hipSuccess)
         return SELD_ELAUNCH;
-    hipLaunchKernelGGL(kern, pl.grid, dim3(256), pl.smem, st, pl.kp);
+    hipLaunchKernelGGL(kern, pl.grid, dim3(256), pl.smem, st, args...);
     return check_launch();
 }
 
-template <int KH, int KW, int IBC, int XI8, int XI4>
-static int hcq_launch_cfg(const HcqPlan& pl, const HcqKern& k, hipStream_t st) {
-    if (k.NR == 2) {
-        if (k.XI != XI8) return SELD_EUNSUPPORTED;
-        if constexpr (KH == 1) {                              // the global-load form exists for the shapes hcq_plan gives it to
-            if (pl.gf) {
-                if (k.NT2 == 2) return hcq_launch_one<KH, KW, IBC, 1, 2, 2, XI8, false, true>(pl, st);
-                if (pl.mix) return hcq_launch_one<KH, KW, IBC, 1, 1, 2, XI8, true, true>(pl, st);
-                return hcq_launch_one<KH, KW, IBC, 1, 1, 2, XI8, false, true>(pl, st);
+// XI of (row, variant), 0: not instantiated
+template <int I, int V> constexpr int hcq_xi() { return HCQ_TILEV[V].NR == 2 ? HCQ_INST[I].XI8 : HCQ_INST[I].XI4; }
+
+template <int I, int V>
+struct HcqLaunchConv {
+    static int run(const HcqPlan& pl, hipStream_t st) {
+        constexpr HcqInst R = HCQ_INST[I];
+        constexpr HcqTileV T = HCQ_TILEV[V];
+        constexpr int XI = hcq_xi<I, V>();
+        if constexpr (XI > 0) {
+            if constexpr (R.KH == 1) {                        // the global-load form exists for the shapes hcq_plan gives it to
+                if (pl.gf) return hcq_launch_kernel(hcq_conv_kernel<R.KH, R.KW, R.IBC, T.NT1, T.NT2, T.NR, XI, T.MX, true>, pl, st, pl.kp);
             }
+            return hcq_launch_kernel(hcq_conv_kernel<R.KH, R.KW, R.IBC, T.NT1, T.NT2, T.NR, XI, T.MX, false>, pl, st, pl.kp);
         }
-        if (k.NT2 == 2) return hcq_launch_one<KH, KW, IBC, 1, 2, 2, XI8>(pl, st);
-        if (pl.mix) return hcq_launch_one<KH, KW, IBC, 1, 1, 2, XI8, true>(pl, st);
-        return hcq_launch_one<KH, KW, IBC, 1, 1, 2, XI8>(pl, st);
+        return SELD_EUNSUPPORTED;
     }
-    if (k.XI != XI4) return SELD_EUNSUPPORTED;
-    if constexpr (KH == 1) {
-        if (pl.gf)
-            return k.NT1 == 2 ? hcq_launch_one<KH, KW, IBC, 2, 0, 1, XI4, false, true>(pl, st)
-                              : hcq_launch_one<KH, KW, IBC, 1, 0, 1, XI4, false, true>(pl, st);
+};
+
+// the first layers' kernels: 3x3 with one or two block channels, no mixed-tile workgroups
+template <int I, int V> constexpr bool hcq_is_first() { return HCQ_INST[I].KH == 3 && HCQ_INST[I].IBC <= 2 && !HCQ_TILEV[V].MX; }
+
+template <int I, int V>
+struct HcqLaunchFirst {
+    static int run(const HcqPlan& pl, hipStream_t st) {
+        constexpr HcqTileV T = HCQ_TILEV[V];
+        if constexpr (hcq_is_first<I, V>())
+            return hcq_launch_kernel(hcq_first_kernel<HCQ_INST[I].IBC, T.NT1, T.NT2, T.NR, HCQ_FIRST_R>, pl, st, pl.kp);
+        return SELD_EUNSUPPORTED;
     }
-    return k.NT1 == 2 ? hcq_launch_one<KH, KW, IBC, 2, 0, 1, XI4>(pl, st)
-                      : hcq_launch_one<KH, KW, IBC, 1, 0, 1, XI4>(pl, st);
-}
+};
 
-template <int IBC, int NT1, int NT2, int NR>
-static int hcq_launch_first(const HcqPlan& pl, hipStream_t st) {
-    auto kern = hcq_first_kernel<IBC, NT1, NT2, NR, 8>;
-    if (pl.smem > 64 * 1024 &&
-        hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.smem) != hipSuccess)
-        return SELD_ELAUNCH;
-    hipLaunchKernelGGL(kern, pl.grid, dim3(256), pl.smem, st, pl.kp);
-    return check_launch();
-}
-
-// The row-walking first-layer kernel takes no addend / accumulate epilogue (the first layer has none).
-static bool hcq_first_takes(const HcqPlan& pl) {
-    if (!pl.first_rows || pl.first_rows != 8) return false;
-    if (pl.kp.epilogue[0] & ~SELD_EPI_STATS) return false;
-    if (pl.NR == 2) return pl.NT1 == 1 && (pl.NT2 == 2 || pl.NT2 == 1);
-    return pl.NT2 == 0 && (pl.NT1 == 1 || pl.NT1 == 2);
-}
+// fin: BatchNorm + ReLU + Dropout applied to the window value; else y is written (with statistics) or not at all
+template <int I, int V>
+struct HcqLaunchPool {
+    static int run(const HcqPlan& pl, const HcqPoolP& pp, bool fin, hipStream_t st) {
+        constexpr HcqTileV T = HCQ_TILEV[V];
+        if constexpr (hcq_is_first<I, V>()) {
+            constexpr int IBC = HCQ_INST[I].IBC;
+            if (fin) return hcq_launch_kernel(hcq_first_pool_kernel<IBC, T.NT1, T.NT2, T.NR, HCQ_FIRST_R, false, true>, pl, st, pl.kp, pp);
+            if (pl.kp.dst[0]) return hcq_launch_kernel(hcq_first_pool_kernel<IBC, T.NT1, T.NT2, T.NR, HCQ_FIRST_R, true>, pl, st, pl.kp, pp);
+            return hcq_launch_kernel(hcq_first_pool_kernel<IBC, T.NT1, T.NT2, T.NR, HCQ_FIRST_R, false>, pl, st, pl.kp, pp);
+        }
+        return SELD_EUNSUPPORTED;
+    }
+};
 
 static int hcq_launch(const HcqPlan& pl, hipStream_t st) {
-    HcqKern k;
-    if (!hcq_pick(pl, &k)) return SELD_EUNSUPPORTED;
-    if (hcq_first_takes(pl)) {
-        if (k.IBC == 1) {
-            if (k.NR == 2) return k.NT2 == 2 ? hcq_launch_first<1, 1, 2, 2>(pl, st) : hcq_launch_first<1, 1, 1, 2>(pl, st);
-            return k.NT1 == 2 ? hcq_launch_first<1, 2, 0, 1>(pl, st) : hcq_launch_first<1, 1, 0, 1>(pl, st);
-        }
-        if (k.NR == 2) return k.NT2 == 2 ? hcq_launch_first<2, 1, 2, 2>(pl, st) : hcq_launch_first<2, 1, 1, 2>(pl, st);
-        return k.NT1 == 2 ? hcq_launch_first<2, 2, 0, 1>(pl, st) : hcq_launch_first<2, 1, 0, 1>(pl, st);
+    if (pl.first_rows) {
+        SELD_HCQ_DISPATCH(HcqLaunchFirst, pl, st)
+    } else {
+        SELD_HCQ_DISPATCH(HcqLaunchConv, pl, st)
     }
-    if (k.KW == 3 && k.KH == 1 && k.IBC == 8) {
-        if (k.NR == 2) {
-            if (k.XI == 5) return hcq_launch_cfg<1, 3, 8, 5, 3>(pl, k, st);
-            if (k.XI == 7) return hcq_launch_cfg<1, 3, 8, 7, 3>(pl, k, st);
-            return hcq_launch_cfg<1, 3, 8, 9, 3>(pl, k, st);
-        }
-        if (k.XI == 3) return hcq_launch_cfg<1, 3, 8, 5, 3>(pl, k, st);
-        return hcq_launch_cfg<1, 3, 8, 7, 5>(pl, k, st);
-    }
-    if (k.KH == 1 && k.KW == 3) return hcq_launch_cfg<1, 3, 4, 6, 3>(pl, k, st);
-    if (k.KH == 1 && k.IBC == 16) return hcq_launch_cfg<1, 1, 16, 8, 4>(pl, k, st);
-    if (k.KH == 1 && k.IBC == 24) return hcq_launch_cfg<1, 1, 24, 12, 6>(pl, k, st);
-    if (k.KH == 1 && k.IBC == 8) return hcq_launch_cfg<1, 1, 8, 4, 2>(pl, k, st);
-    if (k.IBC == 2) return hcq_launch_cfg<3, 3, 2, 4, 2>(pl, k, st);
-    if (k.IBC == 1) return hcq_launch_cfg<3, 3, 1, 2, 1>(pl, k, st);
-    return hcq_launch_cfg<3, 3, 4, 7, 4>(pl, k, st);
+    return SELD_EUNSUPPORTED;
 }
 
 }  // namespace seld
 
 using namespace seld;
 
+static bool hcq_args_ok(const seld_conv_desc* d, int32_t mode, int32_t npair) {
+    return hc_validate(d) == SELD_OK && mode >= 0 && mode <= 2 && npair >= 1 && npair <= 2;
+}
+
 extern "C" size_t seld_hcq_pack_floats(const seld_conv_desc* d, int32_t mode, int32_t npair) {
-    if (hc_validate(d) != SELD_OK || mode < 0 || mode > 2 || npair < 1 || npair > 2) return 0;
-    if (env().conv_no_hcq) return 0;
+    if (!hcq_args_ok(d, mode, npair) || env().conv_no_hcq) return 0;
     const HcqPlan pl = hcq_plan(d, mode, npair);
-    HcqKern k;
-    return (pl.ok && hcq_pick(pl, &k)) ? pl.pack_floats : 0;
+    return pl.ok ? pl.pack_floats : 0;
 }
 
 extern "C" size_t seld_hcq_pack_entry_bytes(void) { return sizeof(HcqPackP); }
@@ -1579,23 +1513,32 @@ extern "C" size_t seld_hcq_pack_entry_bytes(void) { return sizeof(HcqPackP); }
 extern "C" int seld_hcq_kernel_label(const seld_conv_desc* d, int32_t mode, int32_t npair, char* buf, int32_t buflen) {
     if (hc_validate(d) != SELD_OK || !buf || buflen < 64) return SELD_EINVAL;
     const HcqPlan pl = hcq_plan(d, mode, npair);
-    HcqKern k;
-    if (!pl.ok || !hcq_pick(pl, &k)) return SELD_EUNSUPPORTED;
-    if (mode == 2)
-        snprintf(buf, buflen, "hcq_first_pool_kernel<%d, %d, %d, %d, 8>", k.IBC, k.NT1, k.NT2, k.NR);
-    else if (pl.first_rows && hcq_first_takes(pl))   // (label of the plain / statistics epilogue: what the first layer runs)
-        snprintf(buf, buflen, "hcq_first_kernel<%d, %d, %d, %d, %d>", k.IBC, k.NT1, k.NT2, k.NR, pl.first_rows);
+    if (!pl.ok) return SELD_EUNSUPPORTED;
+    const HcqInst& r = HCQ_INST[pl.row];
+    const HcqTileV& v = HCQ_TILEV[pl.variant];
+    if (pl.first_rows)   // (hcq_first_pool_kernel: the WY / FIN arguments depend on the entry point's pointers)
+        snprintf(buf, buflen, pl.pool ? "hcq_first_pool_kernel<%d, %d, %d, %d, %d>" : "hcq_first_kernel<%d, %d, %d, %d, %d>", r.IBC,
+                 v.NT1, v.NT2, v.NR, pl.first_rows);
     else
-        snprintf(buf, buflen, "hcq_conv_kernel<%d, %d, %d, %d, %d, %d, %d, %s, %s>", k.KH, k.KW, k.IBC, k.NT1, k.NT2, k.NR, k.XI,
-                 (pl.mix && k.NR == 2 && k.NT2 == 1) ? "true" : "false", pl.gf ? "true" : "false");
+        snprintf(buf, buflen, "hcq_conv_kernel<%d, %d, %d, %d, %d, %d, %d, %s, %s>", r.KH, r.KW, r.IBC, v.NT1, v.NT2, v.NR, pl.XI,
+                 v.MX ? "true" : "false", pl.gf ? "true" : "false");
     return SELD_OK;
 }
 
-/* Fill one table entry (host memory, seld_hcq_pack_entry_bytes() bytes) for seld_hcq_pack_table. */
+/* Host-only: the launch seld_hcq_conv (mode 0 / 1) or seld_hcq_first_pool (mode 2) makes for (desc, mode, npair). */
+extern "C" int seld_hcq_launch_shape(const seld_conv_desc* d, int32_t mode, int32_t npair, int32_t out[6]) {
+    if (!hcq_args_ok(d, mode, npair) || !out) return SELD_EINVAL;
+    const HcqPlan pl = hcq_plan(d, mode, npair);
+    if (!pl.ok) return SELD_EUNSUPPORTED;
+    out[0] = (int32_t)pl.grid.x; out[1] = (int32_t)pl.grid.y; out[2] = (int32_t)pl.smem;
+    out[3] = pl.kp.ring_off; out[4] = pl.kp.half_slots; out[5] = pl.first_rows;
+    return SELD_OK;
+}
+
+/* Fill one table entry (host memory, seld_hcq_pack_entry_bytes() bytes) for seld_hcq_pack_flat. */
 extern "C" int seld_hcq_pack_entry(const seld_conv_desc* d, int32_t mode, int32_t npair, const float* const wA[8],
                                    const float* const wB[8], float* wpack, void* entry) {
-    if (hc_validate(d) != SELD_OK || !wA || !wpack || !entry) return SELD_EINVAL;
-    if (mode < 0 || mode > 2 || npair < 1 || npair > 2 || (npair == 2 && !wB)) return SELD_EINVAL;
+    if (!hcq_args_ok(d, mode, npair) || !wA || !wpack || !entry || (npair == 2 && !wB)) return SELD_EINVAL;
     HcqPlan pl = hcq_plan(d, mode, npair);
     if (!pl.ok) return SELD_EUNSUPPORTED;
     for (int i = 0; i < 8; ++i) {
@@ -1617,17 +1560,8 @@ extern "C" int seld_hcq_pack(const seld_conv_desc* d, int32_t mode, int32_t npai
     return check_launch();
 }
 
-/* All entries of a DEVICE table in one launch; max_floats = the largest entry's float count. */
-extern "C" int seld_hcq_pack_table(const void* table_dev, int32_t nentries, int64_t max_floats, void* stream) {
-    if (!table_dev || nentries <= 0 || max_floats <= 0) return SELD_EINVAL;
-    long long bx = (max_floats + 255) / 256;
-    if (bx > 512) bx = 512;
-    hipLaunchKernelGGL(hcq_pack_table_kernel, dim3((unsigned)bx, (unsigned)nentries), dim3(256), 0, (hipStream_t)stream,
-                       (const HcqPackP*)table_dev, nentries);
-    return check_launch();
-}
-
-/* The balanced form: starts_dev[e] = first 256-float block of entry e, starts_dev[nentries] = total_blocks. */
+/* Every entry of a DEVICE table in one launch: starts_dev[e] = first 256-float block of entry e, starts_dev[nentries] =
+ * total_blocks. */
 extern "C" int seld_hcq_pack_flat(const void* table_dev, const int32_t* starts_dev, int32_t nentries, int32_t total_blocks,
                                   void* stream) {
     if (!table_dev || !starts_dev || nentries <= 0 || total_blocks <= 0) return SELD_EINVAL;
@@ -1643,7 +1577,8 @@ extern "C" int seld_hcq_conv(const seld_conv_desc* d, int32_t mode, int32_t npai
     if (hc_validate(d) != SELD_OK || !x || !wpack || !y || !y[0]) return SELD_EINVAL;
     if ((mode != 0 && mode != 1) || npair < 1 || npair > 2) return SELD_EINVAL;
     if (mode == 1 && npair == 2 && !x2) return SELD_EINVAL;
-    HcqPlan pl = hcq_plan(d, mode, npair);
+    // (same packed weights for both kernels of a first-layer shape)
+    HcqPlan pl = hcq_plan(d, mode, npair, !(epilogue && (epilogue[0] & ~SELD_EPI_STATS)));
     if (!pl.ok) return SELD_EUNSUPPORTED;
     const int nsets = mode == 0 ? npair : 1;
     for (int s = 0; s < 2; ++s) {
@@ -1672,32 +1607,11 @@ extern "C" int seld_hcq_conv(const seld_conv_desc* d, int32_t mode, int32_t npai
 static int hcq_first_pool_impl(const seld_conv_desc* d, const float* x, const float* wpack, const float* bias,
                                int32_t want_stats, float* y, float* stats, const HcqPoolP& pp, bool fin, void* stream) {
     HcqPlan pl = hcq_plan(d, 2, 1);
-    HcqKern k;
-    if (!pl.ok || !hcq_pick(pl, &k) || pl.first_rows != 8) return SELD_EUNSUPPORTED;
+    if (!pl.ok) return SELD_EUNSUPPORTED;
     pl.kp.src = x; pl.kp.src2 = nullptr; pl.kp.wpack = wpack;
     pl.kp.dst[0] = y; pl.kp.bias[0] = bias; pl.kp.epilogue[0] = want_stats ? SELD_EPI_STATS : 0; pl.kp.stats[0] = stats;
-    const int NT = pl.NT1 + pl.NT2;
-    const int npair = ((pl.IBC * 9 + 3) / 4 + 1) / 2;
-    const size_t smem = ((size_t)pl.kp.A * pl.IBC * 10 * 72 + (size_t)NT * 4 * 4 * 16 * 2 +
-                         (size_t)pl.NR * npair * 8 * 64 * 2) * sizeof(float);    // rows + statistics + one tile's fragments
-    hipStream_t st = (hipStream_t)stream;
-#define SELD_FP(IBC_, NT1_, NT2_, NR_)                                                                                  \
-    do {                                                                                                                \
-        auto kern = fin ? hcq_first_pool_kernel<IBC_, NT1_, NT2_, NR_, 8, false, true>                                  \
-                        : (y ? hcq_first_pool_kernel<IBC_, NT1_, NT2_, NR_, 8, true> : hcq_first_pool_kernel<IBC_, NT1_, NT2_, NR_, 8, false>); \
-        if (smem > 64 * 1024 &&                                                                                         \
-            hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) \
-            return SELD_ELAUNCH;                                                                                        \
-        hipLaunchKernelGGL(kern, pl.grid, dim3(256), smem, st, pl.kp, pp);                                              \
-        return check_launch();                                                                                          \
-    } while (0)
-    if (k.IBC == 1) {
-        if (k.NR == 2) { if (k.NT2 == 2) SELD_FP(1, 1, 2, 2); else SELD_FP(1, 1, 1, 2); }
-        if (k.NT1 == 2) SELD_FP(1, 2, 0, 1); else SELD_FP(1, 1, 0, 1);
-    }
-    if (k.NR == 2) { if (k.NT2 == 2) SELD_FP(2, 1, 2, 2); else SELD_FP(2, 1, 1, 2); }
-    if (k.NT1 == 2) SELD_FP(2, 2, 0, 1); else SELD_FP(2, 1, 0, 1);
-#undef SELD_FP
+    SELD_HCQ_DISPATCH(HcqLaunchPool, pl, pp, fin, (hipStream_t)stream)
+    return SELD_EUNSUPPORTED;
 }
 
 extern "C" int seld_hcq_first_pool(const seld_conv_desc* d, const float* x, const float* wpack, const float* bias,

@@ -1,31 +1,27 @@
-// Weight gradient of the quaternion / dual-quaternion convolutions with the 8-multiplication Hamilton product (gfx950).
+// Weight gradient of the quaternion convolutions with the 8-multiplication Hamilton product (gfx950).
 //
 // For y = W (x) x the gradient is dW = sum over positions of dy (x) conj(x) -- again a Hamilton product per (output block
-// channel, input block channel, tap), so the identities of hcq_conv.hip apply with a = dy, b = conj(x): 8 real GEMMs
+// channel, input block channel, tap), so the identities of hcq_forms.h apply with a = dy, b = conj(x): 8 real GEMMs
 //     P_m[o][c] = sum_pos F_m(dy)[o][pos] * G_m(conj x)[c][pos],      c = (input block channel, tap)
-// instead of 16, recombined once at the end.  Dual quaternion (y_p = Q x_p, y_d = Q2 x_p + Q x_d):
-//     dQ = dy_p (x) conj(x_p) + dy_d (x) conj(x_d)        dQ2 = dy_d (x) conj(x_p)
-// i.e. three products, two of which share their accumulators: 24 sub-products instead of 48.
+// instead of 16, recombined once at the end.  (The dual quaternion's weight gradients run on hcq_wgrad_grp.hip or the
+// block-matrix kernels: this kernel with three products per tile was measured slower than those)
 //
 // Work decomposition: the reduction runs over N*H*W positions and the result is tiny, so the grid is
 // (position splits) x (column groups) x (row tiles); one wave owns a 16 (block channels o) x 16 (columns c) tile of all
-// 8 forms of dQ and dQ2 (16 accumulators), a workgroup = NW waves on NW neighbouring column tiles of one row tile.
+// 8 forms (8 accumulators), a workgroup = NW waves on NW neighbouring column tiles of one row tile.
 // Per 32-position chunk a workgroup stages the RAW component rows it needs (dy: 16 rows, x: the block channels its
-// columns touch, with halo) in LDS; per group of 4 positions a lane reads its 8 dy and 8 x component values, forms the
-// 16 + 16 sums in registers (one group ahead of their use) and issues 24 MFMAs.  Partial results of the splits are
+// columns touch, with halo) in LDS; per group of 4 positions a lane reads its 4 dy and 4 x component values, forms the
+// 8 + 8 sums in registers (one group ahead of their use) and issues 8 MFMAs.  Partial results of the splits are
 // combined with float atomics straight into the gradient tensors (FlatAdam's slices), after the 8 -> 4 recombination.
-// Block-channel counts that are 8 (mod 16): the last 8 block channels of the primal and the dual half share one row
-// tile (rows 0-7 read dy_p, rows 8-15 dy_d): two products instead of three, of which one is half used.
-#include <type_traits>
 #include "hc_common.h"
+#include "hcq_forms.h"
 
 namespace seld {
 
 struct HcqWgP {
     const float* x;
     const float* dy[2];          // one or two convolutions of the same input (pair)
-    float* dw[2][8];             // component gradients, accumulated into
-    int A;
+    float* dw[2][4];             // component gradients, accumulated into
     int N, Cin, Cout;
     int IB, OB;
     int H, W;
@@ -33,39 +29,15 @@ struct HcqWgP {
     int ncol;                    // IB * KH * KW
     int xp;                      // LDS pitch of an x row: 32 + 2*dpad + 2
     int nib_max;                 // x block channels staged per column group
-    int row_tiles;               // row tiles per convolution in THIS launch (regular tiles; 1 for the mixed-tile launch)
+    int row_tiles;               // row tiles per convolution
     long long nchunks;           // 32-position chunks in total
     long long chunks_per_split;
 };
 
 typedef unsigned int uintx4w __attribute__((ext_vector_type(4)));
 
-// sums of two components (see hcq_conv.hip): F of the left operand a = dy, G of the right operand b = conj(x)
-__device__ __forceinline__ void fforms(const float a[4], float f[8]) {
-    f[0] = a[3] + a[1];
-    f[1] = a[0] - a[2];
-    f[2] = a[0] + a[2];
-    f[3] = a[3] - a[1];
-    f[4] = a[3] - a[2];
-    f[5] = a[1] + a[0];
-    f[6] = a[0] - a[1];
-    f[7] = a[3] + a[2];
-}
-__device__ __forceinline__ void gforms_conj(const float x[4], float g[8]) {
-    // b = (x0, -x1, -x2, -x3):  b1+b2, b0+b3, b0-b3, b1-b2, b2-b3, b1+b0, b2+b3, b1-b0
-    g[0] = -(x[1] + x[2]);
-    g[1] = x[0] - x[3];
-    g[2] = x[0] + x[3];
-    g[3] = x[2] - x[1];
-    g[4] = x[3] - x[2];
-    g[5] = x[0] - x[1];
-    g[6] = -(x[2] + x[3]);
-    g[7] = -(x[1] + x[0]);
-}
-
-// NW waves per workgroup (column tiles per group); DI / XI: staging items per thread (dy / x), upper bounds;
-// KIND 0: quaternion, 1: dual quaternion regular row tiles, 2: the mixed row tile (a launch of its own)
-template <int KH, int KW, int NW, int DI, int XI, int KIND>
+// NW waves per workgroup (column tiles per group); DI / XI: staging items per thread (dy / x), upper bounds
+template <int KH, int KW, int NW, int DI, int XI>
 __global__ __launch_bounds__(64 * NW, 2) void hcq_wgrad_kernel(const HcqWgP p) {
     constexpr int NTH = 64 * NW;
     constexpr int TAPS = KH * KW;
@@ -75,15 +47,13 @@ __global__ __launch_bounds__(64 * NW, 2) void hcq_wgrad_kernel(const HcqWgP p) {
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int fr = lane & 15, fk = lane >> 4;
-    constexpr int A = KIND == 0 ? 4 : 8;
-    constexpr int halves = A / 4;                                // 1 quaternion, 2 dual quaternion
+    constexpr int A = 4;
 
     // ---- which tile -----------------------------------------------------------------------------------------------
     const int rt_all = blockIdx.z;
     const int conv = rt_all / p.row_tiles;                       // which convolution of a pair
     const int rt = rt_all - conv * p.row_tiles;
-    constexpr bool mix = KIND == 2;
-    const int o0 = mix ? p.OB - 8 : rt * 16;
+    const int o0 = rt * 16;
     const int cg = blockIdx.y;
     const int c_lo = cg * (16 * NW);
     const int ib_lo = c_lo / TAPS;
@@ -122,7 +92,6 @@ __global__ __launch_bounds__(64 * NW, 2) void hcq_wgrad_kernel(const HcqWgP p) {
         const int ff = in ? f : 0;
         const int quad = ff & 7, row = (ff >> 3) & 15, comp = ff >> 7;
         int o = o0 + row;
-        if (mix && row >= 8) o = p.OB - 1;                       // rows 8..15 of the mixed tile's image are not used
         if (o >= p.OB) o = p.OB - 1;
         d_inv[i] = (unsigned)((((long long)(comp * p.OB + o)) * S + 4 * quad) * 4);
         d_lds[i] = in ? (comp * 16 + row) * DP + 4 * quad : -1;
@@ -143,10 +112,8 @@ __global__ __launch_bounds__(64 * NW, 2) void hcq_wgrad_kernel(const HcqWgP p) {
     }
 
     // ---- operand addresses ---------------------------------------------------------------------------------------------
-    // A (dy): row fr, position 4g + fk.  Mixed tile: rows 0-7 read the primal components, rows 8-15 the dual ones at row - 8
-    const int arow = (mix && fr >= 8) ? fr - 8 : fr;
-    const int a_half = (mix && fr >= 8) ? 1 : 0;
-    const int a_off = arow * DP + fk;
+    // A (dy): row fr, position 4g + fk
+    const int a_off = fr * DP + fk;
     const int a_cs = 16 * DP;                                     // component stride
     // B (x): column c = c_lo + 16*wave + fr -> (ib, kh, kw); invalid columns read column ncol-1 (never stored)
     int c = c_lo + 16 * wave + fr;
@@ -158,54 +125,24 @@ __global__ __launch_bounds__(64 * NW, 2) void hcq_wgrad_kernel(const HcqWgP p) {
     const int b_cs = nib * KH * xp;
     const bool wave_on = c_lo + 16 * wave < p.ncol;               // a wave whose column tile lies outside does no MFMAs
 
-    floatx4 acc0[8], acc1[8];
+    floatx4 acc[8];
 #pragma unroll
-    for (int m = 0; m < 8; ++m) { acc0[m] = (floatx4){0.f, 0.f, 0.f, 0.f}; acc1[m] = (floatx4){0.f, 0.f, 0.f, 0.f}; }
+    for (int m = 0; m < 8; ++m) acc[m] = (floatx4){0.f, 0.f, 0.f, 0.f};
 
-    float fa[2][2][8], gb[2][2][8];                                // [stage][half][form]
+    float fa[2][8], gb[2][8];                                      // [stage][form]
 
     auto read_forms = [&](int g, int st) __attribute__((always_inline)) {
         float a[4], b[4];
-        if (mix) {
 #pragma unroll
-            for (int q = 0; q < 4; ++q) a[q] = dys[a_off + 4 * g + (a_half * 4 + q) * a_cs];
-            fforms(a, fa[st][0]);
-        } else {
+        for (int q = 0; q < 4; ++q) a[q] = dys[a_off + 4 * g + q * a_cs];
+        hcq_fforms(a, fa[st]);
 #pragma unroll
-            for (int h = 0; h < 2; ++h)
-                if (h < halves) {
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) a[q] = dys[a_off + 4 * g + (h * 4 + q) * a_cs];
-                    fforms(a, fa[st][h]);
-                }
-        }
-#pragma unroll
-        for (int h = 0; h < 2; ++h)
-            if (h < halves) {
-#pragma unroll
-                for (int q = 0; q < 4; ++q) b[q] = xs[b_off + 4 * g + (h * 4 + q) * b_cs];
-                gforms_conj(b, gb[st][h]);
-            }
+        for (int q = 0; q < 4; ++q) b[q] = xs[b_off + 4 * g + q * b_cs];
+        hcq_gforms_conj(b, gb[st]);
     };
     auto mfmas = [&](int st) __attribute__((always_inline)) {
-        if (halves == 1) {
 #pragma unroll
-            for (int m = 0; m < 8; ++m) acc0[m] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[st][0][m], gb[st][0][m], acc0[m], 0, 0, 0);
-        } else if (mix) {
-#pragma unroll
-            for (int m = 0; m < 8; ++m) {
-                acc0[m] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[st][0][m], gb[st][0][m], acc0[m], 0, 0, 0);   // . conj(x_p)
-                acc1[m] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[st][0][m], gb[st][1][m], acc1[m], 0, 0, 0);   // . conj(x_d)
-            }
-        } else {
-            // three passes over the forms: an accumulator is not touched by two MFMAs in a row
-#pragma unroll
-            for (int m = 0; m < 8; ++m) acc0[m] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[st][0][m], gb[st][0][m], acc0[m], 0, 0, 0);   // dQ  += dy_p conj(x_p)
-#pragma unroll
-            for (int m = 0; m < 8; ++m) acc1[m] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[st][1][m], gb[st][0][m], acc1[m], 0, 0, 0);   // dQ2 += dy_d conj(x_p)
-#pragma unroll
-            for (int m = 0; m < 8; ++m) acc0[m] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[st][1][m], gb[st][1][m], acc0[m], 0, 0, 0);   // dQ  += dy_d conj(x_d)
-        }
+        for (int m = 0; m < 8; ++m) acc[m] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[st][m], gb[st][m], acc[m], 0, 0, 0);
     };
 
     // ---- chunk loop -------------------------------------------------------------------------------------------------
@@ -267,79 +204,45 @@ __global__ __launch_bounds__(64 * NW, 2) void hcq_wgrad_kernel(const HcqWgP p) {
     }
 
     // ---- recombination + atomics -----------------------------------------------------------------------------------
-    // lane: column c, rows 4*fk + r.  regular: acc0 -> dQ, acc1 -> dQ2 (rows o0 + row).  mixed: acc0 rows 0-7 -> dQ,
-    // rows 8-15 -> dQ2; acc1 rows 8-15 -> dQ (rows 0-7 dropped).  quaternion: acc0 -> dW.
+    // lane: column c, rows 4*fk + r
     if (!wave_on || !c_ok) return;
-    auto combine = [&](const floatx4* ac, floatx4* out) __attribute__((always_inline)) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const float h0_ = 0.5f * ac[0][r], h1 = 0.5f * ac[1][r], h2 = 0.5f * ac[2][r], h3 = 0.5f * ac[3][r];
-            out[0][r] = (h3 - h0_) + (h1 + h2) + ac[4][r];
-            out[1][r] = (h3 - h0_) - (h1 + h2) + ac[5][r];
-            out[2][r] = (h3 + h0_) + (h2 - h1) + ac[6][r];
-            out[3][r] = (h3 + h0_) + (h1 - h2) - ac[7][r];
-        }
-    };
-    floatx4 c0[4], c1[4];
-    combine(acc0, c0);
-    if (halves == 2) combine(acc1, c1);
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-        const int row = 4 * fk + r;
+        const int o = o0 + 4 * fk + r;
+        const HcqQuat c4 = hcq_recombine(acc[0][r], acc[1][r], acc[2][r], acc[3][r], acc[4][r], acc[5][r], acc[6][r], acc[7][r]);
 #pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            if (halves == 1) {
-                const int o = o0 + row;
-                if (o < p.OB) atomicAdd(p.dw[conv][q] + (size_t)o * p.ncol + c, c0[q][r]);
-            } else if (!mix) {
-                const int o = o0 + row;
-                if (o < p.OB) {
-                    atomicAdd(p.dw[conv][q] + (size_t)o * p.ncol + c, c0[q][r]);
-                    atomicAdd(p.dw[conv][4 + q] + (size_t)o * p.ncol + c, c1[q][r]);
-                }
-            } else {
-                const int o = o0 + (row & 7);
-                if (row < 8) atomicAdd(p.dw[conv][q] + (size_t)o * p.ncol + c, c0[q][r]);
-                else {
-                    atomicAdd(p.dw[conv][4 + q] + (size_t)o * p.ncol + c, c0[q][r]);
-                    atomicAdd(p.dw[conv][q] + (size_t)o * p.ncol + c, c1[q][r]);
-                }
-            }
-        }
+        for (int q = 0; q < 4; ++q)
+            if (o < p.OB) atomicAdd(p.dw[conv][q] + (size_t)o * p.ncol + c, c4.c[q]);
     }
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
+// The launch of (desc, npair): seld_hcq_wgrad_supported, the label and seld_hcq_wgrad_acc all read this.
 struct HcqWgPlan {
-    int ok, KH, KW, NW, DI, XI, mix, npair;
+    int ok, KH, KW, NW;
+    int DI, XI;                  // staging items per thread of the INSTANTIATION (hcq_wgrad_bucket)
     HcqWgP kp;
     dim3 grid;
     size_t smem;
 };
 
+// The instantiations: per (taps, NW) one DI (enough for 8 x 128 dy items: the count the kernel was built with when it
+// also staged dual-quaternion rows; the quaternion's 512 items leave the upper iterations idle) and XI 4 or 8.
+constexpr int hcq_wgrad_di(int nw) { return (8 * 128 + 64 * nw - 1) / (64 * nw); }
+constexpr int HCQ_WGRAD_XI[2] = {4, 8};
+
 static HcqWgPlan hcq_wgrad_plan(const seld_conv_desc* d, int npair) {
     HcqWgPlan pl{};
     if (env().conv_no_hcq) return pl;
-    const int A = d->algebra;
-    if (A != 4 && A != 8) return pl;
-    // Measured against the 16/48-product weight-gradient kernels (tools/hcq_wgrad_check.py): the quaternion layers win
-    // (3x3: 164 vs 214 us, 1x3: 18.6 vs 26.0), the dual-quaternion layers of config 3 do not yet (TCN 1x3 88 vs 75 us,
-    // cnn.1 1400 vs 1159): the old kernels already run at 65-73 % of their roof, this one at ~35 % of its own.  The dual
-    // quaternion therefore takes this kernel only on request (SELD_HCQ_WGRAD_DQ, a selection switch: same results).
-    if (A == 8 && !env().hcq_wgrad_dq) return pl;
-    if (d->stride[0] != 1 || d->stride[1] != 1 || d->dil[0] != 1) return pl;
-    int o[2];
-    hc_out_shape(d, o);
-    if (o[0] != d->in[0] || o[1] != d->in[1]) return pl;
+    // Measured against the 16-product weight-gradient kernels: 3x3 164 vs 214 us, 1x3 18.6 vs 26.0.  (The dual-quaternion
+    // layers did not win here -- TCN 1x3 88 vs 75 us, cnn.1 1400 vs 1159 -- which is why hcq_wgrad_grp.hip exists.)
+    constexpr int A = 4;
+    if (d->algebra != A || !hcq_same_geometry(d)) return pl;
     const int KH = d->k[0], KW = d->k[1];
-    if (!((KH == 1 && (KW == 1 || KW == 3)) || (KH == 3 && KW == 3))) return pl;
-    if (2 * d->pad[1] != d->dil[1] * (KW - 1) || 2 * d->pad[0] != (KH - 1)) return pl;
-    if (KW == 1 && d->dil[1] != 1) return pl;
     const int W = d->in[1], H = d->in[0];
     if (W % 32) return pl;
     const int IB = d->Cin / A, OB = d->Cout / A;
-    if ((long long)d->N * d->Cin * H * W * 4 >= 0xFFFFFFF0ll || (long long)d->N * d->Cout * H * W * 4 >= 0xFFFFFFF0ll) return pl;
-    if (A == 8 ? !(OB % 16 == 0 || (OB % 16 == 8 && OB > 8)) : (OB % 16 != 0)) return pl;
+    if (OB % 16 != 0) return pl;
     const int taps = KH * KW, ncol = IB * taps;
     const int dil = KW == 3 ? d->dil[1] : 0, dpad = KW == 3 ? (dil + 3) / 4 * 4 : 0;
     const int xp = 32 + 2 * dpad + 2;
@@ -356,7 +259,7 @@ static HcqWgPlan hcq_wgrad_plan(const seld_conv_desc* d, int npair) {
         const size_t smem = ((size_t)A * 16 * 34 + (size_t)A * nib * KH * xp) * sizeof(float);
         if (smem > 78 * 1024) continue;
         if ((long long)A * nib * KH * ((32 + 2 * dpad) / 4) > 8LL * 64 * nw) continue;      // staging items per thread <= 8
-        if ((32 + 2 * dpad) / 4 - 0 > 128 || xp * (long long)A * nib * KH >= (1 << 19)) continue;   // packed item fields
+        if ((32 + 2 * dpad) / 4 > 128 || xp * (long long)A * nib * KH >= (1 << 19)) continue;   // packed item fields
         const int groups = (coltiles + nw - 1) / nw;
         const double use = (double)coltiles / (groups * nw);
         const double score = use + 0.02 * nw;
@@ -368,15 +271,14 @@ static HcqWgPlan hcq_wgrad_plan(const seld_conv_desc* d, int npair) {
     const int dy_items = A * 16 * 8;
     const int x_items = A * best_nib * KH * ((32 + 2 * dpad) / 4);
     const int DI = (dy_items + NTH - 1) / NTH, XI = (x_items + NTH - 1) / NTH;
+    if (DI > hcq_wgrad_di(NW) || XI > HCQ_WGRAD_XI[1]) return pl;
     HcqWgP& k = pl.kp;
-    k.A = A; k.N = d->N; k.Cin = d->Cin; k.Cout = d->Cout; k.IB = IB; k.OB = OB; k.H = H; k.W = W;
+    k.N = d->N; k.Cin = d->Cin; k.Cout = d->Cout; k.IB = IB; k.OB = OB; k.H = H; k.W = W;
     k.KH = KH; k.KW = KW; k.dil = dil; k.dpad = dpad; k.ncol = ncol; k.xp = xp; k.nib_max = best_nib;
-    const int reg_tiles = OB / 16, mix = (A == 8 && OB % 16 == 8) ? 1 : 0;
-    k.row_tiles = reg_tiles;
-    pl.mix = mix;
+    k.row_tiles = OB / 16;
     k.nchunks = (long long)d->N * H * W / 32;
     const int groups = (coltiles + NW - 1) / NW;
-    const long long tiles = (long long)groups * (reg_tiles + mix) * npair;
+    const long long tiles = (long long)groups * k.row_tiles * npair;
     // position splits: about four workgroups per CU in flight, at least 4 chunks per split
     long long splits = (1024 + tiles - 1) / tiles;
     if (splits > k.nchunks / 4) splits = k.nchunks / 4;
@@ -384,60 +286,32 @@ static HcqWgPlan hcq_wgrad_plan(const seld_conv_desc* d, int npair) {
     k.chunks_per_split = (k.nchunks + splits - 1) / splits;
     splits = (k.nchunks + k.chunks_per_split - 1) / k.chunks_per_split;
     pl.grid = dim3((unsigned)splits, (unsigned)groups, (unsigned)(k.row_tiles * npair));
-    pl.npair = npair;
     pl.smem = best_smem;
-    pl.KH = KH; pl.KW = KW; pl.NW = NW; pl.DI = DI; pl.XI = XI;
+    pl.KH = KH; pl.KW = KW; pl.NW = NW;
+    pl.DI = hcq_wgrad_di(NW);
+    pl.XI = XI <= HCQ_WGRAD_XI[0] ? HCQ_WGRAD_XI[0] : HCQ_WGRAD_XI[1];
     pl.ok = 1;
     return pl;
 }
 
-template <int KH, int KW, int NW, int DI, int XI, int KIND>
-static int hcq_wgrad_launch_kind(const HcqWgPlan& pl, const HcqWgP& kp, dim3 grid, hipStream_t st) {
-    auto kern = hcq_wgrad_kernel<KH, KW, NW, DI, XI, KIND>;
+template <int KH, int KW, int NW, int XI>
+static int hcq_wgrad_launch_one(const HcqWgPlan& pl, hipStream_t st) {
+    auto kern = hcq_wgrad_kernel<KH, KW, NW, hcq_wgrad_di(NW), XI>;
     if (pl.smem > 64 * 1024 &&
         hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.smem) != hipSuccess)
         return SELD_ELAUNCH;
-    hipLaunchKernelGGL(kern, grid, dim3(64 * NW), pl.smem, st, kp);
+    hipLaunchKernelGGL(kern, pl.grid, dim3(64 * NW), pl.smem, st, pl.kp);
     return check_launch();
-}
-
-template <int KH, int KW, int NW, int DI, int XI>
-static int hcq_wgrad_launch_one(const HcqWgPlan& pl, hipStream_t st) {
-    if (pl.kp.A == 4) return hcq_wgrad_launch_kind<KH, KW, NW, DI, XI, 0>(pl, pl.kp, pl.grid, st);
-    int rc = SELD_OK;
-    if (pl.kp.row_tiles > 0) rc = hcq_wgrad_launch_kind<KH, KW, NW, DI, XI, 1>(pl, pl.kp, pl.grid, st);
-    if (rc == SELD_OK && pl.mix) {                    // the mixed row tile: a launch of its own (other program)
-        HcqWgP kp = pl.kp;
-        kp.row_tiles = 1;
-        rc = hcq_wgrad_launch_kind<KH, KW, NW, DI, XI, 2>(pl, kp, dim3(pl.grid.x, pl.grid.y, (unsigned)pl.npair), st);
-    }
-    return rc;
-}
-
-// (DI, XI) buckets per wave count: DI = ceil(A*128 / (64 NW)), XI bounded by the LDS budget
-template <int KH, int KW, int NW>
-static int hcq_wgrad_launch_nw(const HcqWgPlan& pl, hipStream_t st) {
-    constexpr int DIM = (8 * 128 + 64 * NW - 1) / (64 * NW);
-    if (pl.DI > DIM) return SELD_EUNSUPPORTED;
-    if (pl.XI <= 4) return hcq_wgrad_launch_one<KH, KW, NW, DIM, 4>(pl, st);
-    if (pl.XI <= 8) return hcq_wgrad_launch_one<KH, KW, NW, DIM, 8>(pl, st);
-    return SELD_EUNSUPPORTED;
 }
 
 template <int KH, int KW>
 static int hcq_wgrad_launch_k(const HcqWgPlan& pl, hipStream_t st) {
-    switch (pl.NW) {
-        case 5: return hcq_wgrad_launch_nw<KH, KW, 5>(pl, st);
-        case 4: return hcq_wgrad_launch_nw<KH, KW, 4>(pl, st);
-        case 3: return hcq_wgrad_launch_nw<KH, KW, 3>(pl, st);
-        case 2: return hcq_wgrad_launch_nw<KH, KW, 2>(pl, st);
-    }
+#define SELD_HCQ_WG(NW_)                                                                                     \
+    case NW_: return pl.XI == HCQ_WGRAD_XI[0] ? hcq_wgrad_launch_one<KH, KW, NW_, HCQ_WGRAD_XI[0]>(pl, st)    \
+                                              : hcq_wgrad_launch_one<KH, KW, NW_, HCQ_WGRAD_XI[1]>(pl, st);
+    switch (pl.NW) { SELD_HCQ_WG(5) SELD_HCQ_WG(4) SELD_HCQ_WG(3) SELD_HCQ_WG(2) }
+#undef SELD_HCQ_WG
     return SELD_EUNSUPPORTED;
-}
-
-static bool hcq_wgrad_launchable(const HcqWgPlan& pl) {
-    const int dim = (8 * 128 + 64 * pl.NW - 1) / (64 * pl.NW);
-    return pl.ok && pl.DI <= dim && pl.XI <= 8;
 }
 
 }  // namespace seld
@@ -447,16 +321,14 @@ using namespace seld;
 /* 1 if seld_hcq_wgrad_acc takes (desc, npair), else 0 (use seld_hc_conv_bwd_weight_acc). */
 extern "C" int seld_hcq_wgrad_supported(const seld_conv_desc* d, int32_t npair) {
     if (hc_validate(d) != SELD_OK || npair < 1 || npair > 2) return 0;
-    return hcq_wgrad_launchable(hcq_wgrad_plan(d, npair)) ? 1 : 0;
+    return hcq_wgrad_plan(d, npair).ok;
 }
 
 extern "C" int seld_hcq_wgrad_label(const seld_conv_desc* d, int32_t npair, char* buf, int32_t buflen) {
     if (hc_validate(d) != SELD_OK || !buf || buflen < 64) return SELD_EINVAL;
     const HcqWgPlan pl = hcq_wgrad_plan(d, npair);
-    if (!hcq_wgrad_launchable(pl)) return SELD_EUNSUPPORTED;
-    const int dim = (8 * 128 + 64 * pl.NW - 1) / (64 * pl.NW);
-    snprintf(buf, buflen, "hcq_wgrad_kernel<%d, %d, %d, %d, %d, %d>", pl.KH, pl.KW, pl.NW, dim, pl.XI <= 4 ? 4 : 8,
-             pl.kp.A == 4 ? 0 : 1);
+    if (!pl.ok) return SELD_EUNSUPPORTED;
+    snprintf(buf, buflen, "hcq_wgrad_kernel<%d, %d, %d, %d, %d>", pl.KH, pl.KW, pl.NW, pl.DI, pl.XI);
     return SELD_OK;
 }
 
@@ -467,13 +339,13 @@ extern "C" int seld_hcq_wgrad_acc(const seld_conv_desc* d, int32_t npair, const 
     if (hc_validate(d) != SELD_OK || !x || !dyA || !dwA || npair < 1 || npair > 2) return SELD_EINVAL;
     if (npair == 2 && (!dyB || !dwB)) return SELD_EINVAL;
     HcqWgPlan pl = hcq_wgrad_plan(d, npair);
-    if (!hcq_wgrad_launchable(pl)) return SELD_EUNSUPPORTED;
+    if (!pl.ok) return SELD_EUNSUPPORTED;
     pl.kp.x = x;
     pl.kp.dy[0] = dyA;
     pl.kp.dy[1] = npair == 2 ? dyB : nullptr;
-    for (int i = 0; i < 8; ++i) {
-        pl.kp.dw[0][i] = i < d->algebra ? dwA[i] : nullptr;
-        pl.kp.dw[1][i] = (npair == 2 && i < d->algebra) ? dwB[i] : nullptr;
+    for (int i = 0; i < 4; ++i) {
+        pl.kp.dw[0][i] = dwA[i];
+        pl.kp.dw[1][i] = npair == 2 ? dwB[i] : nullptr;
     }
     hipStream_t st = (hipStream_t)stream;
     if (pl.KH == 1 && pl.KW == 1) return hcq_wgrad_launch_k<1, 1>(pl, st);

@@ -3,10 +3,10 @@
 //     dQ  = dy_p (x) conj(x_p) + dy_d (x) conj(x_d)        dQ2 = dy_d (x) conj(x_p)
 //
 // (dual_quaternion_ops.py:122-153 differentiated; quaternion_ops.py:131-147 for the Hamilton product (x)).  Each product
-// has rank 8 (hcq_conv.hip): P_m = F_m(dy) G_m(conj x)^T, m = 0..7, are independent real GEMMs over the positions and the
+// has rank 8 (hcq_forms.h): P_m = F_m(dy) G_m(conj x)^T, m = 0..7, are independent real GEMMs over the positions and the
 // component gradients are signed sums of the P_m.
 //
-// Why a new kernel: the row-chunk kernels (hc_wgrad_row.hip, hcq_wgrad_row.hip) sit at ~4.4 us per
+// Why a new kernel: the row-chunk kernels (hc_wgrad_row.hip, and the fast-product variant of it that this kernel replaced) sit at ~4.4 us per
 // 32-position step whatever their MFMA count -- 36-72 MFMAs per wave and step are shorter than the staging round trip,
 // and every layer's launch is one resident generation with its own ramp, drain and atomic fold.  Here the shape of the
 // problem is turned round:
@@ -32,6 +32,7 @@
 #include <type_traits>
 #include <vector>
 #include "hc_common.h"
+#include "hcq_forms.h"
 
 // GW_DBG: timing experiments of tools/gw_micro.cpp ONLY (parts of the kernel switched off, WRONG results); the library is
 // always built with 0.   1 = no LDS-DMA   2 = no LDS fragment reads   4 = no MFMAs   8 = no barriers
@@ -41,7 +42,6 @@
 
 namespace seld {
 
-typedef int int4v __attribute__((ext_vector_type(4)));
 typedef float floatx2 __attribute__((ext_vector_type(2)));
 
 constexpr int GW_MAXJ = 56;
@@ -65,22 +65,21 @@ struct GwP {
     int total;             // all steps
 };
 
-// The forms (hcq_conv.hip; the tables of hcq_wgrad_row.hip), one nibble / bit per m:
-//   F_m(a)      = a[c1] + s2 * a[c2]          c1 = {3,0,0,3,3,1,0,3}  c2 = {1,2,2,1,2,0,1,2}  s2 = {+,-,+,-,-,+,-,+}
-//   G_m(conj x) = s1 * (x[c1] + t * x[c2])    c1 = {1,0,0,2,3,0,2,1}  c2 = {2,3,3,1,2,1,3,0}
-//                 s1 = {-,+,+,+,+,+,-,-}, s2 = {-,-,+,-,-,-,-,-}, t = s2 * s1 = {+,-,+,-,-,-,+,+}; s1 is applied by the fold
-constexpr unsigned GW_FC1 = 0x30133003u, GW_FC2 = 0x21021221u, GW_FS2 = 0x5Au;
-constexpr unsigned GW_GC1 = 0x12032001u, GW_GC2 = 0x03121332u, GW_GT = 0x3Au, GW_GS1 = 0xC1u;
-constexpr bool gw_nibbles_are(unsigned v, int a0, int a1, int a2, int a3, int a4, int a5, int a6, int a7) {
-    return ((v >> 0) & 15) == (unsigned)a0 && ((v >> 4) & 15) == (unsigned)a1 && ((v >> 8) & 15) == (unsigned)a2 &&
-           ((v >> 12) & 15) == (unsigned)a3 && ((v >> 16) & 15) == (unsigned)a4 && ((v >> 20) & 15) == (unsigned)a5 &&
-           ((v >> 24) & 15) == (unsigned)a6 && ((v >> 28) & 15) == (unsigned)a7;
+// The forms of hcq_forms.h, one nibble / bit per m (a wave's form index is a run-time value: it shifts these words):
+//   F_m(a)      = a[c1] + s2 * a[c2]
+//   G_m(conj x) = s1 * (x[c1] + t * x[c2])         (hcq_split; s1 is applied by the fold)
+template <typename Fn>
+constexpr unsigned gw_pack(int bits, Fn field) {
+    unsigned w = 0;
+    for (int m = 0; m < 8; ++m) w |= (unsigned)field(m) << (bits * m);
+    return w;
 }
-static_assert(gw_nibbles_are(GW_FC1, 3, 0, 0, 3, 3, 1, 0, 3) && gw_nibbles_are(GW_FC2, 1, 2, 2, 1, 2, 0, 1, 2), "F_m components");
-static_assert(gw_nibbles_are(GW_GC1, 1, 0, 0, 2, 3, 0, 2, 1) && gw_nibbles_are(GW_GC2, 2, 3, 3, 1, 2, 1, 3, 0), "G_m components");
-static_assert(GW_FS2 == ((1u << 1) | (1u << 3) | (1u << 4) | (1u << 6)), "F_m second sign negative at m = 1, 3, 4, 6");
-static_assert(GW_GS1 == ((1u << 0) | (1u << 6) | (1u << 7)), "G_m first sign negative at m = 0, 6, 7");
-static_assert(GW_GT == ((1u << 1) | (1u << 3) | (1u << 4) | (1u << 5)), "G_m sign ratio negative at m = 1, 3, 4, 5");
+constexpr HcqSplit gw_g(int m) { return hcq_split(hcq_conj(HCQ_G[m])); }
+constexpr unsigned GW_FC1 = gw_pack(4, [](int m) { return HCQ_F[m].c1; }), GW_FC2 = gw_pack(4, [](int m) { return HCQ_F[m].c2; });
+constexpr unsigned GW_FS2 = gw_pack(1, [](int m) { return HCQ_F[m].s2 < 0; });
+constexpr unsigned GW_GC1 = gw_pack(4, [](int m) { return gw_g(m).c1; }), GW_GC2 = gw_pack(4, [](int m) { return gw_g(m).c2; });
+constexpr unsigned GW_GT = gw_pack(1, [](int m) { return gw_g(m).t < 0; }), GW_GS1 = gw_pack(1, [](int m) { return gw_g(m).s1 < 0; });
+static_assert(gw_pack(1, [](int m) { return HCQ_F[m].s1 < 0; }) == 0, "F_m's first term is positive: the loader applies s2 alone");
 __device__ __forceinline__ void gw_f_form(int m, int* c1, int* c2, float* s2) {
     *c1 = (GW_FC1 >> (4 * m)) & 3;
     *c2 = (GW_FC2 >> (4 * m)) & 3;
@@ -130,15 +129,7 @@ struct GwShape {
     __host__ __device__ static constexpr int tileq(int set, int i, int j) { return (set * RT + i) * CT + j; }
 };
 
-// One 16-byte-per-lane LDS-DMA: LDS[lds_addr + 16 * lane ..] <- buffer[voff ..] (zero when voff is out of range).  Inline
-// asm: the compiler's waitcnt pass would otherwise put vmcnt(0) in front of every LDS read that follows (it cannot tell
-// the two stages apart); the kernel counts these loads itself (gw_wait_dma).  M0 is saved and restored in the statement.
-__device__ __forceinline__ void gw_dma16(unsigned lds_addr, unsigned voff, int4v rsrc, unsigned soff) {
-    if (GW_DBG & 1) return;
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tbuffer_load_dwordx4 %2, %3, %4 offen lds\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "s"(lds_addr), "v"(voff), "s"(rsrc), "s"(soff) : "memory");
-}
+// (the kernel counts its LDS-DMA loads, hcq_dma16, itself)
 template <int N>
 __device__ __forceinline__ void gw_wait_dma_and_barrier() {
     if (GW_DBG & 8) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N) : "memory");
@@ -165,10 +156,6 @@ template <typename T>
 __device__ __forceinline__ T gw_lds(const unsigned char* base, unsigned off) {
     if (GW_DBG & 2) { T v; for (int i = 0; i < (int)(sizeof(T) / 4); ++i) v[i] = __uint_as_float(off + i); return v; }
     return *reinterpret_cast<const T*>(base + off);
-}
-__device__ __forceinline__ int4v gw_rsrc(const float* base) {
-    const unsigned long long a = (unsigned long long)base;
-    return (int4v){(int)(unsigned)a, (int)((unsigned)(a >> 32) & 0xFFFFu), (int)0x80000000u, 0x00020000};
 }
 
 // NSTG = stages of the LDS ring (2, or more where a stage is small: the 1x1 layers' steps are too short for one stage of
@@ -302,7 +289,7 @@ __global__ __launch_bounds__(512, 2) void hcq_wgrad_grp_kernel(const GwP p) {
         int al[KW];                                                     // first column of tap t's window, relative to w0
 #pragma unroll
         for (int t = 0; t < KW; ++t) al[t] = (J.woff0 + t * J.wstep) & ~3;
-        int4v dyr, xr;
+        int4h dyr, xr;
         int lo[KW], hi[KW];                                             // valid pieces of tap t's rows in the step being loaded
         auto load_begin = [&]() __attribute__((always_inline)) {
             const int w0 = l_wi << 4;
@@ -310,8 +297,8 @@ __global__ __launch_bounds__(512, 2) void hcq_wgrad_grp_kernel(const GwP p) {
             const int hi_ = l_h + J.hoff;
             const bool rowok = (unsigned)hi_ < (unsigned)H;
             const float* xb = J.x + (long long)l_n * x_img + (long long)hi_ * W + (w0 - GW_BIAS);
-            dyr = gw_rsrc(dyb);
-            xr = gw_rsrc(xb);
+            dyr = hcq_rsrc(dyb, 0x80000000u);
+            xr = hcq_rsrc(xb, 0x80000000u);
 #pragma unroll
             for (int t = 0; t < KW; ++t) {
                 const int c0 = w0 + al[t];                            // a multiple of 4; piece ch covers columns c0 + 4ch .. +3
@@ -334,14 +321,15 @@ __global__ __launch_bounds__(512, 2) void hcq_wgrad_grp_kernel(const GwP p) {
             constexpr int Q0 = 4 * K;
             if constexpr (Q0 < S::NDYI) {
                 const unsigned q = (unsigned)(Q0 + wave);
-                gw_dma16(lds0 + STG * S::DYB + q * 1024u, ldy, dyr, q * 16u * dy_rs);
+                if (!(GW_DBG & 1)) hcq_dma16(lds0 + STG * S::DYB + q * 1024u, ldy, dyr, q * 16u * dy_rs);
             } else {
                 constexpr int T = (Q0 - S::NDYI) / S::XTI;
                 const unsigned e = (unsigned)(Q0 - S::NDYI - T * S::XTI + wave);        // row block inside the tap image
                 unsigned v = (e == S::XTI - 1) ? lx_last : lx;
                 v = ((unsigned)(lch - lo[T]) <= (unsigned)hi[T]) ? v : GW_OOB;
-                gw_dma16(lds0 + XBASE + STG * S::XB + T * S::XTB + e * (unsigned)(S::XR * S::XC * 16), v, xr,
-                         e * x_blk + (unsigned)((GW_BIAS + al[T]) * 4));
+                if (!(GW_DBG & 1))
+                    hcq_dma16(lds0 + XBASE + STG * S::XB + T * S::XTB + e * (unsigned)(S::XR * S::XC * 16), v, xr,
+                              e * x_blk + (unsigned)((GW_BIAS + al[T]) * 4));
             }
         };
         // DMAs [K0, K1) -- compile-time range
@@ -633,15 +621,13 @@ __global__ __launch_bounds__(256) void hcq_gw_fold_kernel(const GwFoldP p) {
         else v = set == 0 ? at(mf, 0, 0) + at(mf, 1, 1) : at(mf, 1, 0);
         P[mf] = gw_g_sign(mf) * v;
     }
-    const float h0 = 0.5f * P[0], h1 = 0.5f * P[1], h2 = 0.5f * P[2], h3 = 0.5f * P[3];
-    const float c[4] = {(h3 - h0) + (h1 + h2) + P[4], (h3 - h0) - (h1 + h2) + P[5], (h3 + h0) + (h2 - h1) + P[6],
-                        (h3 + h0) + (h1 - h2) - P[7]};
+    const HcqQuat c = hcq_recombine(P[0], P[1], P[2], P[3], P[4], P[5], P[6], P[7]);
     // sub-job -> (kh, first kw) of the convolution's kernel
     const int kws = cv.KWfull / cv.subKW;                            // sub-jobs per kernel row
     const int kh = sub / kws, kw = (sub - kh * kws) * cv.subKW + t;
     const size_t e = (((size_t)o * IB + ib) * cv.KH + kh) * cv.KWfull + kw;
 #pragma unroll
-    for (int q = 0; q < 4; ++q) cv.dw[set * 4 + q][e] += c[q];
+    for (int q = 0; q < 4; ++q) cv.dw[set * 4 + q][e] += c.c[q];
 }
 
 // ---------------------------------------------------------------------------------------------------------------------

@@ -26,8 +26,8 @@ from .norm_act import (_claim_grad_slots, _direct_targets, _identity_cache, _nbt
 from .conv3d import _conv3d_backward, _conv3d_weights, _triple  # noqa: F401
 from .weight_forms import _hcq_ok, _HcqWeights  # noqa: F401
 from .streams import _on_side_stream, _side_enabled  # noqa: F401
-from .conv import (_conv_backward, _DeferredWgrads, _hcq_wgrad_label, _hcq_wgrad_ok, _hcq_wgrad_row_bytes,  # noqa: F401
-                   _hcq_wgrad_row_label, _label, _pair_ok, _ptr2, _transpose_ahead, _y_shape)
+from .conv import (_conv_backward, _DeferredWgrads, _hcq_wgrad_label, _hcq_wgrad_ok, _label,  # noqa: F401
+                   _pair_ok, _ptr2, _transpose_ahead, _y_shape)
 from .dwconv import _dw_y_shape  # noqa: F401
 from .linear_mha import _mha_keep_mask  # noqa: F401
 from .first_stage import _first_stage_nostore, _fs_bytes  # noqa: F401

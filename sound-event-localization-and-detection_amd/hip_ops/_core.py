@@ -103,20 +103,16 @@ L._reload_hooks.append(_drop_kernel_choice_caches)
 _scratch_pools = collections.defaultdict(dict)       # pool name -> {(device, stream): buffer}
 
 
-def scratch(pool, nbytes, device, zeroed=False):
-    """At least `nbytes` of scratch from the named pool's buffer of (device, current stream), grown by reallocation.
-    zeroed=False: uint8, contents undefined (the kernels rewrite it fully per call).  zeroed=True: fp32, zero when
-    created; the kernels that use it hand it back zeroed."""
-    if not zeroed and torch.cuda.is_current_stream_capturing():
+def scratch(pool, nbytes, device):
+    """At least `nbytes` of scratch (uint8, contents undefined: the kernels rewrite it fully per call) from the named
+    pool's buffer of (device, current stream), grown by reallocation."""
+    if torch.cuda.is_current_stream_capturing():
         # a recorded step: the scratch comes from (and stays in) the graph's own memory pool
         return torch.empty(nbytes, device=device, dtype=torch.uint8)
     key = (device, torch.cuda.current_stream(device).cuda_stream)
     t = _scratch_pools[pool].get(key)
     if t is None or t.numel() * t.element_size() < nbytes:
-        if zeroed:
-            t = torch.zeros((nbytes + 3) // 4, device=device, dtype=torch.float32)
-        else:
-            t = torch.empty(nbytes, device=device, dtype=torch.uint8)
+        t = torch.empty(nbytes, device=device, dtype=torch.uint8)
         _scratch_pools[pool][key] = t
     return t
 

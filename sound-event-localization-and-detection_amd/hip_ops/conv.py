@@ -168,8 +168,7 @@ def _hcq_wgrad_ok(desc, npair=1):
 
 @memo
 def _hcq_wgrad_taken(desc, npair):
-    return desc.algebra > 1 and (_hcq_wgrad_row_bytes(desc, npair) > 0 or
-                                 bool(L.lib().seld_hcq_wgrad_supported(ctypes.byref(desc), int(npair))))
+    return bool(L.lib().seld_hcq_wgrad_supported(ctypes.byref(desc), int(npair)))
 
 
 @memo
@@ -177,30 +176,10 @@ def _hcq_wgrad_label(desc, npair=1):
     return kernel_label(L.lib().seld_hcq_wgrad_label, ctypes.byref(desc), int(npair), size=96)
 
 
-@memo
-def _hcq_wgrad_row_bytes(desc, npair=1):
-    """Scratch bytes of the 24-product dual-quaternion weight gradient (csrc/hcq_wgrad_row.hip), 0 = shape not taken."""
-    return int(L.lib().seld_hcq_wgrad_row_workspace(ctypes.byref(desc), int(npair))) if desc.algebra == 8 else 0
-
-
-@memo
-def _hcq_wgrad_row_label(desc, npair=1):
-    return kernel_label(L.lib().seld_hcq_wgrad_row_label, ctypes.byref(desc), int(npair), size=96)
-
-
 def hcq_wgrad_acc(desc, x, dyA, dwA, dyB=None, dwB=None):
-    """dwA[c] += wgrad(x, dyA) [, dwB[c] += wgrad(x, dyB)] on the fast-product kernels: the row-chunk GEMM on forms for
-    the dual quaternion (seld_hcq_wgrad_row_acc), else seld_hcq_wgrad_acc."""
+    """dwA[c] += wgrad(x, dyA) [, dwB[c] += wgrad(x, dyB)] on the fast-product kernel of the quaternion layers
+    (seld_hcq_wgrad_acc)."""
     npair = 2 if dyB is not None else 1
-    nbytes = _hcq_wgrad_row_bytes(desc, npair)
-    if nbytes:
-        ws = scratch("wgrad_row", nbytes, x.device, zeroed=True)       # every call hands it back zeroed
-        with _timed(desc, 2, npair, label=lambda: _hcq_wgrad_row_label(desc, npair)):
-            L.check(L.lib().seld_hcq_wgrad_row_acc(ctypes.byref(desc), npair, L.ptr(x), L.ptr(dyA), L.ptr(dyB),
-                                                   L.ptr_array8(dwA), L.ptr_array8(dwB) if dwB is not None else None,
-                                                   L.ptr(ws), ws.numel() * 4, L.current_stream()),
-                    "seld_hcq_wgrad_row_acc")
-        return
     with _timed(desc, 2, npair, label=lambda: _hcq_wgrad_label(desc, npair)):
         L.check(L.lib().seld_hcq_wgrad_acc(ctypes.byref(desc), npair, L.ptr(x), L.ptr(dyA), L.ptr(dyB), L.ptr_array8(dwA),
                                            L.ptr_array8(dwB) if dwB is not None else None, L.current_stream()),

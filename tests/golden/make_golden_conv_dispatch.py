@@ -125,9 +125,9 @@ def _runs(seq):
     return out
 
 
-def encode(got):
+def encode(got, nfields=NFIELDS, block=BLOCK):
     fields = []
-    for f in range(NFIELDS):
+    for f in range(nfields):
         values, blocks, seen_v, seen_b, envs = [], [], {}, {}, {}
         for name, col in got.items():
             idx = []
@@ -138,8 +138,8 @@ def encode(got):
                     values.append(json.loads(key))
                 idx.append(seen_v[key])
             seq = []
-            for i in range(0, len(idx), BLOCK):
-                blk = tuple(idx[i:i + BLOCK])
+            for i in range(0, len(idx), block):
+                blk = tuple(idx[i:i + block])
                 if blk not in seen_b:
                     seen_b[blk] = len(blocks)
                     blocks.append(list(blk))
@@ -150,10 +150,10 @@ def encode(got):
     return {"rows": len(got["default"]), "fields": fields}
 
 
-def decode(doc):
+def decode(doc, envs=ENVS):
     """The inverse of `encode`: {environment name: [answer per descriptor]}."""
     got = {}
-    for name, _ in ENVS:
+    for name, _ in envs:
         cols = []
         for f in doc["fields"]:
             runs = f["envs"].get(name, f["envs"]["default"])

@@ -155,7 +155,7 @@ def _labels(H, case):
     for which in (0, 1):
         out.append(H.hcq_label(d, which) if H._hcq_ok(d, which) else H._label(d, which))
     if not case["bias"] and H._hcq_wgrad_ok(d):
-        out.append(H._hcq_wgrad_row_label(d) if H._hcq_wgrad_row_bytes(d) else H._hcq_wgrad_label(d))
+        out.append(H._hcq_wgrad_label(d))
     else:
         out.append(H._label(d, 2))
     return out
