@@ -1053,6 +1053,62 @@ int seld_gather_rows_aug(const float* x_all, int64_t row_x, float* out_x, const 
                          int32_t f_max, int32_t n_tmask, int32_t t_max, float fill, void* stream);
 int seld_epoch_step_end(const float* loss, float* mean, int32_t* cursor, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Whole-recording inference (csrc/ensemble.hip): sliding windows over resident recordings, each window under every row
+ * of a transform table, and the members' outputs combined into one track per recording.  Neither entry point allocates
+ * or synchronises; both can be recorded in a HIP graph; a refused call launches nothing and writes nothing.
+ *
+ * Notation: recordings x (R, C, F, L) fp32; windows of T input frames every `hop` frames, S per recording; a transform
+ * table of K rows of 2 * C + 6 int32 in the layout of seld_gather_rows_aug (src[C], flip[C], axis[3], sign[3]), its
+ * CONTENT validated by the caller as there.  K == 0 with table NULL is the identity alone and counts as K = 1 below.
+ * Members are numbered m = (r * S + s) * K + k.
+ *
+ * seld_window_batch cuts and transforms the members [m0, m0 + count) in one launch.  For b < count, m = m0 + b:
+ *     out[b, c, f, j] = flipop(flip_k[c], t < L ? x[r, src_k[c], f, t] : 0),      t = s * hop + j,  0 <= j < T
+ *   flipop as documented for seld_gather_rows_aug, applied to the padding zero as well (flip 2 makes it PI_F): the
+ *   bytes of seld_segment followed by the training transform.  out is (B, C, F, T); rows [count, B) are not touched.  A
+ *   src outside [0, C) is taken as c, flip is taken mod 4 with 3 as 0.
+ *   One read and one write per output byte.  16-byte loads and stores when T, hop and L are multiples of 4 and x and
+ *   out are 16-byte aligned (a float4 then lies in one (c, f) row and wholly inside or wholly past L), single floats
+ *   otherwise.
+ *   SELD_EINVAL: x or out NULL; R, F, L, T, hop, S, B or count < 1; C outside [1, 16]; count > B; count > 65535;
+ *   K outside [0, 64]; table NULL with K > 0 or given with K == 0; m0 < 0 or m0 + count > R * S * K.
+ *   SELD_EUNSUPPORTED: C * F * T or C * F * L of 2^31 floats or more.
+ *
+ * seld_ensemble_combine takes the members' outputs sed (M, T_out, n) and doa (M, T_out, 3 * n), M = R * S * K,
+ * n = classes * overlaps <= 64, slot c * O + o (O = overlaps) and axis a at doa[.., 3 * (c * O + o) + a] (the model's
+ * and the loss's layout); hop_out, the hop in output frames; frames, the output frames of a recording; win, T_out
+ * positive finite fp32 weights on the device (validated by the caller); the table (C its channel count: the row
+ * stride; ignored with K == 0); align, 0 or 1.  It writes out_sed (R, frames, n), out_doa (R, frames, 3 * n) and, if
+ * non-NULL, perm (M, T_out, classes) int32.  For each cell (r, t, c), t < frames:
+ *   - the covering windows are the s < S with 0 <= j = t - s * hop_out < T_out; the members of the cell are those
+ *     windows x every k, visited s ascending, then k ascending;
+ *   - a member's values are mapped back through its row:  p_m[o] = sed_m[j, c * O + o]  and
+ *         q_m[o][axis_k[a]] = (float)sign_k[a] * doa_m[j, 3 * (c * O + o) + a]
+ *     the inverse of location'[a] = sign[a] * location[axis[a]] (whatever the row holds, nothing outside it is read);
+ *   - the anchor A is the member (s*, k = 0), s* the covering window with the largest win[j], the lowest s of equals;
+ *   - with align and O > 1 every member picks a slot permutation pi, output slot o taking member slot pi(o), that
+ *     minimises  cost(pi) = (P[0][pi0] + P[1][pi1]) + P[2][pi2]  (the terms of missing slots absent) with
+ *         P[o][i] = (((p_m[i] - p_A[o])^2 + (q_m[i][0] - q_A[o][0])^2) + (q_m[i][1] - q_A[o][1])^2) + (q_m[i][2] - q_A[o][2])^2
+ *     in fp32, products and sums rounded separately.  Permutations are numbered in lexicographic order as for
+ *     seld_loss_pit_fwd_bwd; the search starts from the identity and moves on `<` only: ties and NaN costs keep the
+ *     lower index.  Without align, or with O == 1, pi is the identity (index 0);
+ *   - out[o] = (sum_m w_m * v_m[pi_m(o)]) / (sum_m w_m),  w_m = win[j], for the activity and each of the three axes:
+ *     fp32 products and sums in member order from 0, one division.  One writer per element, no atomics: two runs give
+ *     the same bytes.  A frame that no window covers is written as zeros.
+ *   perm[m, j, c] is the chosen index, and -1 where s * hop_out + j >= frames (every entry of perm is written).
+ *   One launch, one thread per cell, contiguous reads of a frame's n / 3 * n values, no LDS.
+ *   SELD_EINVAL: sed, doa, win, out_sed or out_doa NULL; R, S, T_out, hop_out, frames, classes or overlaps < 1;
+ *   K outside [0, 64]; table NULL with K > 0 or given with K == 0; C outside [1, 16] with K > 0; align not 0 or 1.
+ *   SELD_EUNSUPPORTED: classes * overlaps > 64; align with overlaps > 3; 2^31 workgroups or more.
+ * ------------------------------------------------------------------------------------------ */
+int seld_window_batch(const float* x, int64_t R, int32_t C, int32_t F, int32_t L, int32_t T, int32_t hop, int32_t S,
+                      const int32_t* table, int32_t K, int64_t m0, int32_t B, int32_t count, float* out, void* stream);
+int seld_ensemble_combine(const float* sed, const float* doa, int64_t R, int32_t S, int32_t K, int32_t T_out,
+                          int32_t hop_out, int32_t frames, int32_t classes, int32_t overlaps, const float* win,
+                          const int32_t* table, int32_t C, int32_t align, float* out_sed, float* out_doa, int32_t* perm,
+                          void* stream);
+
 #ifdef __cplusplus
 }
 #endif

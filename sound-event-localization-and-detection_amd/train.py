@@ -438,11 +438,15 @@ _EVAL = ('use_cuda', 'early_stopping', 'fixed_seed', 'pool_size', 'cnn_filters',
 # width up to augment_freq_width / augment_time_width bins; augment_seed: the key of the draws;
 # pit_loss (off by default): the loss takes, per (frame, class), the cheapest pairing of the class_overlaps prediction
 # slots with the target slots (hip_ops.seld_loss_pit) instead of comparing slot o with slot o -- training steps (eager,
-# data parallel, recorded) and the validation loss alike
+# data parallel, recorded) and the validation loss alike;
+# test_hop / test_tta (both 0 by default: the test leg is evaluate_test over pre-cut samples): the test leg runs whole
+# recordings (evaluate_recordings) -- windows of time_dim frames every test_hop frames (0: time_dim, no overlap), each
+# under the 8 (z fixed) or 16 signed FOA axis permutations of hip_ops.foa_transforms for --n_mics / --phase when
+# test_tta is 8 or 16, stitched back on the device (hip_ops.window_batch, hip_ops.ensemble_combine)
 _EXTRA = [('synthetic', int, 0), ('max_steps', int, 0), ('epochs', int, 0), ('resident_loader', str, 'False'),
           ('graph_step', str, 'False'), ('augment_swap', float, 0.), ('augment_freq_masks', int, 0),
           ('augment_freq_width', int, 0), ('augment_time_masks', int, 0), ('augment_time_width', int, 0),
-          ('augment_seed', int, 0), ('pit_loss', str, 'False')]
+          ('augment_seed', int, 0), ('pit_loss', str, 'False'), ('test_hop', int, 0), ('test_tta', int, 0)]
 
 
 def build_parser():
@@ -854,6 +858,14 @@ def test_results_from_counters(counts, total_de, epoch=0):
             ER_dcase21, F_dcase21, LE_dcase21, LR_dcase21]
 
 
+def _print_test_results(results):
+    print('*******************************\nRESULTS')
+    for label, v in (('TP: ', results[5]), ('FP: ', results[6]), ('FN: ', results[7]), ('Global SELD score: ', results[10]),
+                     ('LSD score: ', results[9]), ('CSL score: ', results[8]), ('F score: ', results[1]),
+                     ('ER score: ', results[2]), ('LE: ', results[14]), ('LR: ', results[15])):
+        print(label, v)
+
+
 def evaluate_test(model, device, dataloader, epoch=0, max_loc_value=2., num_frames=600, spatial_threshold=2., args=None):
     """train.py:84-166: same arguments, same 16-entry result list.  The network outputs never leave the device: each
     batch's decode + counting is one kernel (hip_ops.metrics_accumulate) and the counters are read back once."""
@@ -870,11 +882,7 @@ def evaluate_test(model, device, dataloader, epoch=0, max_loc_value=2., num_fram
                                  spatial_threshold, doa_threshold)
     counts = dict(zip(H.METRIC_COUNTERS, acc[0].cpu().tolist()))
     results = test_results_from_counters(counts, float(acc[1].item()), epoch)
-    print('*******************************\nRESULTS')
-    for label, v in (('TP: ', results[5]), ('FP: ', results[6]), ('FN: ', results[7]), ('Global SELD score: ', results[10]),
-                     ('LSD score: ', results[9]), ('CSL score: ', results[8]), ('F score: ', results[1]),
-                     ('ER score: ', results[2]), ('LE: ', results[14]), ('LR: ', results[15])):
-        print(label, v)
+    _print_test_results(results)
     return results
 
 
@@ -894,6 +902,113 @@ def predict_test(model, device, dataloader, max_loc_value=2., num_frames=600):
             rows, offsets = rows.cpu().numpy(), offsets.cpu().tolist()
             out.extend(rows[a:b] for a, b in zip(offsets[:-1], offsets[1:]))
     return out
+
+
+MEMBER_BUFFER_BYTES = 1 << 30       # predict_recordings: recordings are taken in chunks whose member outputs stay below this
+
+
+def ensemble_requested(args):
+    return args.test_hop != 0 or args.test_tta != 0
+
+
+def ensemble_from_args(args):
+    """dict(hop=, table=) of the --test_hop / --test_tta flags for evaluate_recordings (the table on the host, None
+    without test-time augmentation), None when both are 0.  Every refusal comes before the device is touched."""
+    if not ensemble_requested(args):
+        return None
+    if args.test_hop < 0:
+        raise ValueError(f"--test_hop must not be negative, got {args.test_hop}")
+    if args.test_tta not in (0, 8, 16):
+        raise ValueError(f"--test_tta is 0, 8 (the z axis fixed) or 16 transforms, got {args.test_tta}")
+    table = None
+    if args.test_tta:
+        mode = str(args.dataset_normalization)
+        if args.phase and mode not in _NORM_OFF and mode not in _NORM_UNIT:
+            raise ValueError("--test_tta with --phase needs raw phase (a sign flip turns the phase by pi): not with a "
+                             "standardising --dataset_normalization")
+        if args.n_mics not in (1, 2):
+            raise ValueError(f"--test_tta: the FOA transform preset is for 1 or 2 microphones, got --n_mics {args.n_mics}")
+        table = H.foa_transforms(mics=args.n_mics, phase=bool(args.phase), elevation=args.test_tta == 16)
+    return dict(hop=args.test_hop or args.time_dim, table=table)
+
+
+def predict_recordings(model, x, *, seg_len, hop, table=None, window="triangular", align=True, batch=32, frames=None):
+    """Whole recordings through the model: x (R, C, F, L) resident on the device -> (sed (R, frames, n), doa (R, frames, 3n))
+    on the device.  Windows of seg_len frames every hop frames (hip_ops.window_count of them per recording), each under
+    every row of `table` (K of them; None: the window as it is), go through the model `batch` members at a time
+    (hip_ops.window_batch cuts and transforms a batch in one launch; the last batch is partial); one
+    hip_ops.ensemble_combine per chunk of recordings then maps the DOAs back, aligns the slots of every (frame, class)
+    (`align`, for models trained with --pit_loss a must) and averages with the weights `window`.  The pooling factor
+    P = seg_len / T_out is read from the first forward: hop must be a multiple of it, frames defaults to L // P.
+    n = classes * overlaps is split as 14 classes x n / 14 overlaps, the way predict_test reads it."""
+    seg_len, hop, batch = int(seg_len), int(hop), int(batch)
+    if x.dim() != 4 or not x.is_cuda:
+        raise H.L.SeldHipError(f"predict_recordings: x must be a device tensor (R, C, F, L), got {tuple(x.shape)} on {x.device}")
+    if batch < 1 or seg_len < 1 or hop < 1:
+        raise H.L.SeldHipError(f"predict_recordings: seg_len, hop and batch must be positive, got {seg_len}, {hop}, {batch}")
+    x = x.contiguous()
+    R, C, F, length = x.shape
+    S = H.window_count(length, seg_len, hop)
+    if table is not None:
+        table = H.ensemble_table(table, x.device, C)
+    K = 1 if table is None else table.shape[0]
+    model.eval()
+    xb = torch.zeros((batch, C, F, seg_len), device=x.device)
+
+    def forward(r0, rc, first, count):
+        H.window_batch(x[r0:r0 + rc], xb, seg_len=seg_len, hop=hop, segments=S, table=table, first=first, count=count)
+        return model(xb[:count])
+
+    with torch.no_grad():
+        count0 = min(batch, R * S * K)
+        sed0, doa0 = forward(0, R, 0, count0)           # the first forward names the geometry
+        t_out, n = sed0.shape[1], sed0.shape[2]
+        if seg_len % t_out or hop % (seg_len // t_out):
+            raise H.L.SeldHipError(f"predict_recordings: the model pools {seg_len} frames to {t_out}; hop {hop} must be a "
+                                   f"multiple of {seg_len / t_out:g}")
+        if n % 14:
+            raise H.L.SeldHipError(f"predict_recordings: {n} activity outputs are not 14 classes x overlaps")
+        pool = seg_len // t_out
+        frames = length // pool if frames is None else int(frames)
+        per_chunk = max(1, min(R, MEMBER_BUFFER_BYTES // (16 * S * K * t_out * n)))     # 4 n floats per member frame
+        sed_m = torch.empty((per_chunk * S * K, t_out, n), device=x.device)
+        doa_m = torch.empty((per_chunk * S * K, t_out, 3 * n), device=x.device)
+        out_sed = torch.empty((R, frames, n), device=x.device)
+        out_doa = torch.empty((R, frames, 3 * n), device=x.device)
+        for r0 in range(0, R, per_chunk):
+            rc = min(per_chunk, R - r0)
+            members = rc * S * K
+            for first in range(0, members, batch):
+                count = min(batch, members - first)
+                # members are numbered inside their chunk: the first forward is chunk 0's first batch unless the chunk is
+                # smaller than that batch
+                sed, doa = (sed0, doa0) if r0 == 0 and first == 0 and count == count0 else forward(r0, rc, first, count)
+                sed_m[first:first + count] = sed
+                doa_m[first:first + count] = doa
+            sed_c, doa_c = H.ensemble_combine(sed_m[:members], doa_m[:members], recordings=rc, segments=S, hop_out=hop // pool,
+                                              frames=frames, classes=14, overlaps=n // 14, table=table, window=window,
+                                              align=align)
+            out_sed[r0:r0 + rc] = sed_c
+            out_doa[r0:r0 + rc] = doa_c
+    return out_sed, out_doa
+
+
+def evaluate_recordings(model, device, x_all, y_all, args, *, hop, table, epoch=0, window="triangular", align=True,
+                        batch=32, max_loc_value=2., num_frames=600, spatial_threshold=2.):
+    """evaluate_test over whole recordings: x_all (R, C, F, L) and the targets y_all (R, frames, 4n) go through
+    predict_recordings (seg_len = args.time_dim, `hop`, `table`) and the stitched outputs through
+    hip_ops.metrics_accumulate; the same 16-entry result list, printed the same way."""
+    x_all = x_all.to(device)
+    sed, doa = predict_recordings(model, x_all, seg_len=args.time_dim, hop=hop, table=table, window=window, align=align,
+                                  batch=batch, frames=y_all.shape[1])
+    acc = H.metrics_new(device)
+    for r in range(sed.shape[0]):                       # one recording per launch, as evaluate_test's loader gives them
+        H.metrics_accumulate(acc, sed[r:r + 1], doa[r:r + 1], y_all[r:r + 1].to(device), num_frames, 14, args.class_overlaps,
+                             max_loc_value, spatial_threshold, args.Dcase21_metrics_DOA_threshold)
+    counts = dict(zip(H.METRIC_COUNTERS, acc[0].cpu().tolist()))
+    results = test_results_from_counters(counts, float(acc[1].item()), epoch)
+    _print_test_results(results)
+    return results
 
 
 def evaluate(model, device, criterion_sed, criterion_doa, loader, args):
@@ -922,6 +1037,7 @@ def main(args, history=None):
         raise ValueError("--graph_step needs --resident_loader")
     if augment_requested(args) and not resident:
         raise ValueError("--augment_* flags need --resident_loader (the augmentation is part of the device gather)")
+    ensemble = ensemble_from_args(args)
     pit = pit_overlaps_from_args(args)
     if pit > 3:
         raise ValueError(f"--pit_loss searches the pairings of at most 3 slots per class, got --class_overlaps {pit}")
@@ -994,6 +1110,7 @@ def main(args, history=None):
                 xt = xt.to(device)
                 print(normalize_dataset(args, xt))
                 test_data = loader(xt, yt, 1, False)
+                test_arrays = (xt, yt)
         if world > 1:
             say(f"data parallel on {world} ranks: {epoch_left_out(xs.shape[0], args.batch_size, world)} of {xs.shape[0]} "
                 "samples per epoch left out (the last batch is cut to a multiple of the ranks)")
@@ -1085,9 +1202,15 @@ def main(args, history=None):
                 live = os.path.join(model_dir, "checkpoint")
                 state = load_model(model, optimizer, path, args.use_cuda, device, scheduler)
                 at_epoch = state['best_epoch'] if at_epoch is None else at_epoch
-            results = evaluate_test(model, device, test_data, epoch=epoch if path is None else at_epoch,
-                                    max_loc_value=args.max_loc_value, num_frames=args.num_frames,
-                                    spatial_threshold=args.spatial_threshold, args=args)
+            if ensemble is None:
+                results = evaluate_test(model, device, test_data, epoch=epoch if path is None else at_epoch,
+                                        max_loc_value=args.max_loc_value, num_frames=args.num_frames,
+                                        spatial_threshold=args.spatial_threshold, args=args)
+            else:
+                results = evaluate_recordings(model, device, *test_arrays, args, epoch=epoch if path is None else at_epoch,
+                                              align=args.class_overlaps <= 3, max_loc_value=args.max_loc_value,
+                                              num_frames=args.num_frames, spatial_threshold=args.spatial_threshold,
+                                              **ensemble)
             rotation.after_test(model, optimizer, scheduler, state, epoch, results, args.test_mode)
             if path is not None:
                 # the reference reloads args.load_model here (train.py:667), which only exists when resuming; the live
