@@ -1109,6 +1109,73 @@ int seld_ensemble_combine(const float* sed, const float* doa, int64_t R, int32_t
                           const int32_t* table, int32_t C, int32_t align, float* out_sed, float* out_doa, int32_t* perm,
                           void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Track post-processing (csrc/smooth.hip): what SELD systems apply between the network's frame-wise outputs and the
+ * event list -- a median filter on the activity, two thresholds with hysteresis, gap filling, a minimum duration and
+ * one DOA per event -- and the event list of any track.  Nothing here allocates; a refused call launches nothing and
+ * writes nothing.
+ *
+ * Notation: a track is sed (R, T, n) and doa (R, T, 3 * n), contiguous fp32, n = classes * overlaps: the layout of the
+ * model, of seld_ensemble_combine and of seld_decode_*.  A COLUMN is one (r, j), j < n, over its T frames; its DOA at
+ * frame t is doa[r, t, 3j : 3j + 3].  A RUN is a maximal stretch of frames of a column with one value of a flag.
+ *
+ * seld_smooth_tracks writes out_sed (R, T, n), out_doa (R, T, 3 * n) and, if non-NULL, out_prob (R, T, n), in ONE launch
+ * on `stream`, no host read: it can be recorded in a HIP graph.  Per column, independently of every other:
+ *   1. p[t] = the median of sed over the frames t - h .. t + h, h = (median - 1) / 2, frame indices clamped to
+ *      [0, T - 1] (edge replication inside the recording: scipy.ndimage.median_filter(mode='nearest') along time).
+ *      median is odd, 1 <= median <= SELD_SMOOTH_MAX_MEDIAN; median == 1 gives p = sed.  The median is an element of
+ *      the window, so p is exact.  Nothing is promised for NaN.  out_prob = p.
+ *   2. hysteresis: c[t] = p[t] > off; a run of c = 1 is kept iff it holds a frame with p[t] > on.  Both comparisons are
+ *      strict (with on = off = 0.5 and p in [0, 1] this is the decoder's rint, for which 0.5 is off) and in fp32: `on`
+ *      and `off` are floats.  The result is a1.
+ *   3. gap fill: a run of a1 = 0 with an active frame on both sides (so it touches neither frame 0 nor frame T - 1) of
+ *      at most max_gap frames becomes active.  The result is a2.
+ *   4. minimum duration: a run of a2 = 1 of fewer than min_frames frames becomes inactive, at a recording's ends as
+ *      anywhere else.  The result is a3.
+ *   5. out_sed[t] = a3[t] ? 1.0f : 0.0f.
+ *   6. doa_mode SELD_SMOOTH_DOA_FRAME: out_doa = doa everywhere.  SELD_SMOOTH_DOA_MEAN (w = 1) and
+ *      SELD_SMOOTH_DOA_WEIGHTED (w = p[t]): every run of a3 = 1 gets, per axis, (float)(sum w[t] * d[t] / sum w[t]) over
+ *      ITS frames -- products and sums in double, in a fixed order (frame order inside each of the kernel's chunks of
+ *      consecutive frames, then the chunks in order), one division, one rounding to float; no term from outside the run
+ *      enters, so each sum is within run length * 2^-53 of exact, relatively.  sum w > 0: a surviving run holds a frame
+ *      with p > on >= 0.  The value goes to every frame of the run; frames with a3 = 0 copy doa.
+ *   One writer per element, no atomics: two runs give the same bytes.  out_* may not alias the inputs.
+ *   One 256-thread workgroup per column with the column in LDS (9 T + 12352 bytes); the rules are scans over frames.
+ *   SELD_EINVAL: sed, doa, out_sed or out_doa NULL; R, T or n < 1; median even or outside 1 .. SELD_SMOOTH_MAX_MEDIAN;
+ *   on or off not finite or not 0 <= off <= on <= 1; min_frames < 1; max_gap < 0; an unknown doa_mode.
+ *   SELD_EUNSUPPORTED: T > SELD_SMOOTH_MAX_FRAMES (the column no longer fits the CU's LDS); R * n of 2^31 or more.
+ *
+ * seld_track_events_*: the event list of a track, by the two calls of seld_decode_* with one 8-byte device-to-host read
+ * between them.  A frame of a column is active when sed > 0.5: for the 0/1 output above and for probabilities in [0, 1]
+ * that is the decoder's rule; outside [0, 1] it is NOT rint (1.5 rounds to 2 and is active either way, but -0.6 is
+ * active for the decoder and inactive here), and the decoder's frame-sum rule is not applied.  Every run of active frames
+ * gives one row of 8 doubles
+ *     { recording, class = j / overlaps, slot = j % overlaps, onset, offset (exclusive), x, y, z }
+ *   x, y, z = (sum of the run's DOAs in double, frame order) / length * max_loc_value, all in double.  Rows are ordered
+ *   recording-major, then column, then onset; rec_offsets (R + 1) int64, CSR style.
+ *   seld_track_events_workspace  bytes of workspace both calls need (0 for a refused shape)
+ *   seld_track_events_count      reads sed once; leaves the row count E as an int64 in the first 8 bytes of the workspace
+ *   seld_track_events_write      takes the SAME workspace, untouched since the count call on the same sed and shape,
+ *                                rows (capacity, 8) and rec_offsets (R + 1); capacity >= E; rows beyond capacity are
+ *                                not written; rows may be NULL when capacity is 0
+ *   No atomics.  SELD_EINVAL: a NULL pointer, a size < 1, a negative capacity; SELD_EUNSUPPORTED: R * n * ceil(T / 64)
+ *   of 2^31 or more; SELD_EWORKSPACE: a missing or short workspace.
+ * ------------------------------------------------------------------------------------------ */
+#define SELD_SMOOTH_MAX_MEDIAN 31
+#define SELD_SMOOTH_MAX_FRAMES 16384   /* 27 minutes of 100 ms frames */
+#define SELD_SMOOTH_DOA_FRAME 0
+#define SELD_SMOOTH_DOA_MEAN 1
+#define SELD_SMOOTH_DOA_WEIGHTED 2
+int seld_smooth_tracks(const float* sed, const float* doa, int64_t R, int32_t T, int32_t n, int32_t median, float on,
+                       float off, int32_t min_frames, int32_t max_gap, int32_t doa_mode, float* out_sed, float* out_doa,
+                       float* out_prob /* may be NULL */, void* stream);
+size_t seld_track_events_workspace(int64_t R, int32_t T, int32_t n);
+int seld_track_events_count(const float* sed, int64_t R, int32_t T, int32_t n, void* workspace, size_t workspace_bytes,
+                            void* stream);
+int seld_track_events_write(const float* sed, const float* doa, int64_t R, int32_t T, int32_t classes, int32_t overlaps,
+                            double max_loc_value, const void* workspace, size_t workspace_bytes, double* rows,
+                            int64_t capacity, int64_t* rec_offsets, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -442,11 +442,18 @@ _EVAL = ('use_cuda', 'early_stopping', 'fixed_seed', 'pool_size', 'cnn_filters',
 # test_hop / test_tta (both 0 by default: the test leg is evaluate_test over pre-cut samples): the test leg runs whole
 # recordings (evaluate_recordings) -- windows of time_dim frames every test_hop frames (0: time_dim, no overlap), each
 # under the 8 (z fixed) or 16 signed FOA axis permutations of hip_ops.foa_transforms for --n_mics / --phase when
-# test_tta is 8 or 16, stitched back on the device (hip_ops.window_batch, hip_ops.ensemble_combine)
+# test_tta is 8 or 16, stitched back on the device (hip_ops.window_batch, hip_ops.ensemble_combine);
+# post_* (all off by default: then nothing is launched): the test leg post-processes the network's or the ensemble's track
+# on the device before it is scored (hip_ops.smooth_tracks) -- post_median: odd window of a median filter on the activity;
+# post_on / post_off: hysteresis, a stretch above post_off is an event iff it holds a frame above post_on;
+# post_max_gap: gaps of at most so many frames between two events are filled; post_min_frames: shorter events are
+# dropped; post_doa: frame, mean or weighted -- one DOA per event
 _EXTRA = [('synthetic', int, 0), ('max_steps', int, 0), ('epochs', int, 0), ('resident_loader', str, 'False'),
           ('graph_step', str, 'False'), ('augment_swap', float, 0.), ('augment_freq_masks', int, 0),
           ('augment_freq_width', int, 0), ('augment_time_masks', int, 0), ('augment_time_width', int, 0),
-          ('augment_seed', int, 0), ('pit_loss', str, 'False'), ('test_hop', int, 0), ('test_tta', int, 0)]
+          ('augment_seed', int, 0), ('pit_loss', str, 'False'), ('test_hop', int, 0), ('test_tta', int, 0),
+          ('post_median', int, 1), ('post_on', float, 0.5), ('post_off', float, 0.5), ('post_min_frames', int, 1),
+          ('post_max_gap', int, 0), ('post_doa', str, 'frame')]
 
 
 def build_parser():
@@ -872,11 +879,14 @@ def evaluate_test(model, device, dataloader, epoch=0, max_loc_value=2., num_fram
     output_classes = args.output_classes if args is not None else 14
     class_overlaps = args.class_overlaps if args is not None else 3
     doa_threshold = args.Dcase21_metrics_DOA_threshold if args is not None else 20
+    post = postprocess_from_args(args) if args is not None else None
     model.eval()
     acc = H.metrics_new(device)
     with torch.no_grad():
         for x, target in dataloader:
             sed, doa = model(x.to(device))
+            if post is not None:
+                sed, doa = H.smooth_tracks(sed, doa, **post.kwargs())
             # gen_submission_list_task2 is called with its default num_classes = 14 (train.py:110-116)
             H.metrics_accumulate(acc, sed, doa, target.to(device), num_frames, 14, class_overlaps, max_loc_value,
                                  spatial_threshold, doa_threshold)
@@ -891,6 +901,17 @@ def predict_test(model, device, dataloader, max_loc_value=2., num_frames=600):
     decoded on the device (hip_ops.decode_events, with gen_submission_list_task2's default of 14 classes as the
     reference's call has it), and one (E_i, 5) float64 array of [frame, class, x, y, z] rows per recording, in loader
     order.  `num_frames` is accepted and ignored, as gen_submission_list_task2 does."""
+    return _predict_test(model, device, dataloader, max_loc_value, None)
+
+
+def predict_test_post(model, device, dataloader, max_loc_value=2., num_frames=600, post=None):
+    """predict_test with post-processing: `post`, a hip_ops.PostProcess (or a dict of its settings), is applied to every
+    batch's outputs on the device (hip_ops.smooth_tracks) before they are decoded.  None or the identity: nothing is
+    launched and the rows are predict_test's."""
+    return _predict_test(model, device, dataloader, max_loc_value, _active_post(post))
+
+
+def _predict_test(model, device, dataloader, max_loc_value, post):
     model.eval()
     out = []
     with torch.no_grad():
@@ -898,6 +919,8 @@ def predict_test(model, device, dataloader, max_loc_value=2., num_frames=600):
             sed, doa = model(x.to(device))
             if sed.shape[-1] % 14:
                 raise H.L.SeldHipError(f"predict_test: {sed.shape[-1]} activity outputs are not 14 classes x overlaps")
+            if post is not None:
+                sed, doa = H.smooth_tracks(sed, doa, **post.kwargs())
             rows, _, offsets = H.decode_events(sed, doa, max_loc_value, 14, sed.shape[-1] // 14)
             rows, offsets = rows.cpu().numpy(), offsets.cpu().tolist()
             out.extend(rows[a:b] for a, b in zip(offsets[:-1], offsets[1:]))
@@ -930,6 +953,35 @@ def ensemble_from_args(args):
             raise ValueError(f"--test_tta: the FOA transform preset is for 1 or 2 microphones, got --n_mics {args.n_mics}")
         table = H.foa_transforms(mics=args.n_mics, phase=bool(args.phase), elevation=args.test_tta == 16)
     return dict(hop=args.test_hop or args.time_dim, table=table)
+
+
+def postprocess_requested(args):
+    return (getattr(args, "post_median", 1) != 1 or getattr(args, "post_on", 0.5) != 0.5
+            or getattr(args, "post_off", 0.5) != 0.5 or getattr(args, "post_min_frames", 1) != 1
+            or getattr(args, "post_max_gap", 0) != 0 or getattr(args, "post_doa", "frame") != "frame")
+
+
+def postprocess_from_args(args):
+    """The hip_ops.PostProcess of the --post_* flags for the test leg, None when they are all at their defaults (an args
+    object without them counts as that).  Every refusal comes before the device is touched."""
+    if not postprocess_requested(args):
+        return None
+    try:
+        return H.PostProcess(median=args.post_median, on=args.post_on, off=args.post_off, min_frames=args.post_min_frames,
+                             max_gap=args.post_max_gap, doa=args.post_doa)
+    except ValueError as err:
+        raise ValueError(f"--post_*: {err}") from None
+
+
+def _active_post(post):
+    """`post` (a hip_ops.PostProcess, a dict of its settings or None) as a PostProcess, None when there is nothing to do."""
+    if post is None:
+        return None
+    if isinstance(post, dict):
+        post = H.PostProcess(**post)
+    if not isinstance(post, H.PostProcess):
+        raise TypeError(f"post must be a hip_ops.PostProcess, a dict of its settings or None, got {type(post).__name__}")
+    return None if post.is_identity else post
 
 
 def predict_recordings(model, x, *, seg_len, hop, table=None, window="triangular", align=True, batch=32, frames=None):
@@ -994,13 +1046,18 @@ def predict_recordings(model, x, *, seg_len, hop, table=None, window="triangular
 
 
 def evaluate_recordings(model, device, x_all, y_all, args, *, hop, table, epoch=0, window="triangular", align=True,
-                        batch=32, max_loc_value=2., num_frames=600, spatial_threshold=2.):
+                        batch=32, max_loc_value=2., num_frames=600, spatial_threshold=2., post=None):
     """evaluate_test over whole recordings: x_all (R, C, F, L) and the targets y_all (R, frames, 4n) go through
     predict_recordings (seg_len = args.time_dim, `hop`, `table`) and the stitched outputs through
-    hip_ops.metrics_accumulate; the same 16-entry result list, printed the same way."""
+    hip_ops.metrics_accumulate; the same 16-entry result list, printed the same way.  `post`: a hip_ops.PostProcess
+    applied to the stitched track (hip_ops.smooth_tracks, one launch for all recordings) before it is scored; None or the
+    identity: nothing is launched."""
+    post = _active_post(post)
     x_all = x_all.to(device)
     sed, doa = predict_recordings(model, x_all, seg_len=args.time_dim, hop=hop, table=table, window=window, align=align,
                                   batch=batch, frames=y_all.shape[1])
+    if post is not None:
+        sed, doa = H.smooth_tracks(sed, doa, **post.kwargs())
     acc = H.metrics_new(device)
     for r in range(sed.shape[0]):                       # one recording per launch, as evaluate_test's loader gives them
         H.metrics_accumulate(acc, sed[r:r + 1], doa[r:r + 1], y_all[r:r + 1].to(device), num_frames, 14, args.class_overlaps,
@@ -1038,6 +1095,7 @@ def main(args, history=None):
     if augment_requested(args) and not resident:
         raise ValueError("--augment_* flags need --resident_loader (the augmentation is part of the device gather)")
     ensemble = ensemble_from_args(args)
+    post = postprocess_from_args(args)
     pit = pit_overlaps_from_args(args)
     if pit > 3:
         raise ValueError(f"--pit_loss searches the pairings of at most 3 slots per class, got --class_overlaps {pit}")
@@ -1210,7 +1268,7 @@ def main(args, history=None):
                 results = evaluate_recordings(model, device, *test_arrays, args, epoch=epoch if path is None else at_epoch,
                                               align=args.class_overlaps <= 3, max_loc_value=args.max_loc_value,
                                               num_frames=args.num_frames, spatial_threshold=args.spatial_threshold,
-                                              **ensemble)
+                                              **ensemble, **({} if post is None else dict(post=post)))
             rotation.after_test(model, optimizer, scheduler, state, epoch, results, args.test_mode)
             if path is not None:
                 # the reference reloads args.load_model here (train.py:667), which only exists when resuming; the live
