@@ -1176,6 +1176,62 @@ int seld_track_events_write(const float* sed, const float* doa, int64_t R, int32
                             double max_loc_value, const void* workspace, size_t workspace_bytes, double* rows,
                             int64_t capacity, int64_t* rec_offsets, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Squeeze-and-excitation (csrc/squeeze_excite.hip): a per-sample channel gate.  x is (N, C, S) fp32 contiguous, S >= 1 the
+ * product of the spatial extents.  A in {1, 4, 8} hypercomplex components, C % A == 0, Cg = C / A gated channels; the
+ * component blocks are contiguous along the channel axis (channel c = k Cg + g), so ONE gate multiplies a whole
+ * (dual) quaternion by a real scalar.  Hd >= 1 hidden units.  W1 (Hd, Cg), b1 (Hd), W2 (Cg, Hd), b2 (Cg), row-major.
+ *
+ *   z[n,g]   = (1 / (A S)) sum_k sum_s x[n, k Cg + g, s]
+ *   h[n,r]   = relu(sum_g W1[r,g] z[n,g] + b1[r])
+ *   s[n,g]   = sigmoid(sum_r W2[g,r] h[n,r] + b2[g])
+ *   y[n,c,:] = x[n,c,:] s[n, c mod Cg]
+ *
+ *   q[n,g]   = sum_k sum_s dy x        dp2 = q s (1 - s)        dh = (W2^T dp2) [h > 0]
+ *   dW2 = sum_n dp2 (x) h    db2 = sum_n dp2    dW1 = sum_n dh (x) z    db1 = sum_n dh    dz = W1^T dh
+ *   dx[n,c,:] = dy[n,c,:] s[n,g] + dz[n,g] / (A S)
+ *
+ * 1 / (A S) is ONE float, (float)(1.0 / ((double)A * S)), multiplied in; the sigmoid is 1.0f / (1.0f + expf(-p)).
+ * The six calls, each on `stream`, no host read, no allocation (they record into a HIP graph):
+ *   seld_se_squeeze      rowsum[row] = sum_s x[row, s] for the rows = N C rows of S floats
+ *   seld_se_excite_fwd   folds the A row sums of a gated channel (k = 0, 1, ...), writes z (N, Cg), h (N, Hd), s (N, Cg)
+ *   seld_se_scale        y = x s
+ *   seld_se_bwd_reduce   q[row] = sum_s dy[row, s] x[row, s]
+ *   seld_se_excite_bwd   folds q like the row sums; writes dp2 (N, Cg), dh (N, Hd), dz (N, Cg) and the four parameter
+ *                        gradients, each summed over n = 0, 1, ... in order by one thread; accumulate != 0 adds the sum
+ *                        to what dw1 / db1 / dw2 / db2 hold (an optimiser's gradient slots), 0 overwrites
+ *   seld_se_bwd_apply    dx = dy s + dz / (A S)
+ * The two calls that sum (squeeze, bwd_reduce) give every row one owner: the row form (one wave per row) for
+ * S < SELD_SE_BLOCK_MIN_S and the block form (one 256-thread workgroup per row) from there on.  The two that write (scale,
+ * bwd_apply) take the chunk form: one wave per 256 floats of a row.  All use 16-byte accesses between a row's head and
+ * tail whatever S % 4 is; when the tensors of one call sit at different offsets from a 16-byte boundary they walk single
+ * elements (seld_se_kernel_label: "<op>_<row|block|chunk>_kernel[x4|x1]", same_phase != 0 for equal offsets).  Row and
+ * element offsets are 64-bit.  There is no float atomic: every sum has one owner and a fixed order
+ * (csrc/squeeze_excite.hip states it), so two runs give the same bytes with and without SELD_DETERMINISTIC.  Outputs may
+ * not alias inputs.
+ *   SELD_EINVAL: a NULL pointer, an extent < 1, A outside {1, 4, 8}, C % A != 0.
+ *   SELD_EUNSUPPORTED (nothing is launched or written): Cg > SELD_SE_MAX_GATED or Hd > SELD_SE_MAX_HIDDEN -- z / dp2 and
+ *   h / dh of a sample are held in 20 KiB of LDS; scale / bwd_apply on 2^32 chunks (4 TiB of floats) or more.
+ * ------------------------------------------------------------------------------------------ */
+#define SELD_SE_MAX_GATED 4096
+#define SELD_SE_MAX_HIDDEN 1024
+#define SELD_SE_BLOCK_MIN_S 1024
+#define SELD_SE_SQUEEZE 0              /* seld_se_kernel_label(op, ...) */
+#define SELD_SE_SCALE 1
+#define SELD_SE_BWD_REDUCE 2
+#define SELD_SE_BWD_APPLY 3
+int seld_se_squeeze(const float* x, int64_t rows, int32_t S, float* rowsum, void* stream);
+int seld_se_excite_fwd(const float* rowsum, int32_t N, int32_t C, int32_t S, int32_t A, int32_t Hd, const float* w1,
+                       const float* b1, const float* w2, const float* b2, float* z, float* h, float* s, void* stream);
+int seld_se_scale(const float* x, int32_t N, int32_t C, int32_t S, int32_t A, const float* s, float* y, void* stream);
+int seld_se_bwd_reduce(const float* dy, const float* x, int64_t rows, int32_t S, float* q, void* stream);
+int seld_se_excite_bwd(const float* q, int32_t N, int32_t C, int32_t A, int32_t Hd, const float* w1, const float* w2,
+                       const float* z, const float* h, const float* s, float* dp2, float* dh, float* dz, float* dw1,
+                       float* db1, float* dw2, float* db2, int32_t accumulate, void* stream);
+int seld_se_bwd_apply(const float* dy, int32_t N, int32_t C, int32_t S, int32_t A, const float* s, const float* dz,
+                      float* dx, void* stream);
+int seld_se_kernel_label(int32_t op, int32_t S, int32_t same_phase, char* buf, int32_t buflen);
+
 #ifdef __cplusplus
 }
 #endif

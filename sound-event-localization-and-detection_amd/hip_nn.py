@@ -101,3 +101,30 @@ class Dropout1d(nn.Dropout1d):
             return x
         mask = H.channel_dropout_mask(x.shape[0], x.shape[1], self.p, x.device)
         return H.RowScaleFn.apply(x, mask)
+
+
+class SqueezeExcite(nn.Module):
+    """Squeeze-and-excitation gate over `channels` channels of `components` (1, 4 or 8) contiguous hypercomplex component
+    blocks: one gate per hypercomplex channel and sample, hidden width max(1, (channels // components) // reduction).
+    fc1 / fc2 hold the two layers' parameters with torch.nn.Linear's default initialisation (drawn at construction from
+    the global RNG); the forward is hip_ops.squeeze_excite on an (N, channels, *spatial) tensor."""
+
+    def __init__(self, channels, reduction, components=1):
+        super().__init__()
+        if components not in H.SE_COMPONENTS:
+            raise ValueError(f"components must be one of {H.SE_COMPONENTS}, got {components!r}")
+        if int(reduction) < 1:
+            raise ValueError(f"reduction must be at least 1, got {reduction!r}")
+        if channels < components or channels % components:
+            raise ValueError(f"{channels} channels are not a positive multiple of {components} components")
+        self.channels, self.reduction, self.components = int(channels), int(reduction), int(components)
+        self.gated = self.channels // self.components
+        self.hidden = max(1, self.gated // self.reduction)
+        self.fc1 = nn.Linear(self.gated, self.hidden)
+        self.fc2 = nn.Linear(self.hidden, self.gated)
+
+    def extra_repr(self):
+        return f"channels={self.channels}, reduction={self.reduction}, components={self.components}"
+
+    def forward(self, x):
+        return H.squeeze_excite(x, self.fc1.weight, self.fc1.bias, self.fc2.weight, self.fc2.bias, self.components)

@@ -32,6 +32,20 @@ from .quaternion.quaternion_layers import QuaternionConv, QuaternionLinear
 _TCN_BN = {'BN', 'BN_on_TCN', 'BNonTCN'}
 _CNN_BN = {'BN', 'BN_on_CNN', 'BNonCNN'}
 _TWO_STREAM = {'2Parallel', '2BParallel', '2ParallelBranches', '2PB'}
+SE_MODES = ('cnn', 'tcn', 'both')
+_SE_COMPONENTS = {'Q': 4, 'DQ': 8}
+
+
+def _se_check(se_reduction, se_mode):
+    if isinstance(se_reduction, bool) or not isinstance(se_reduction, int) or se_reduction < 0:
+        raise ValueError(f"se_reduction must be a non-negative integer (0: no squeeze-and-excitation), got {se_reduction!r}")
+    if se_mode not in SE_MODES:
+        raise ValueError(f"se_mode must be one of {', '.join(SE_MODES)}, got {se_mode!r}")
+
+
+def _make_se(domain, channels, se_reduction):
+    """One gate per hypercomplex channel: 4 components for domain 'Q', 8 for 'DQ', 1 otherwise."""
+    return hnn.SqueezeExcite(channels, se_reduction, _SE_COMPONENTS.get(domain, 1))
 
 
 def _components(conv):
@@ -121,8 +135,10 @@ class ResBlock(nn.Module):
     """Pre-activation gated dilated residual block (model.py:53-132)."""
 
     def __init__(self, in_channels, domain='DQ', G=128, U=128, kernel_size_dilated_conv=3, dilation=1, stride=1,
-                 spatial_dropout_rate=0.5, use_bias_conv=True, batch_norm='BN', verbose=False):
+                 spatial_dropout_rate=0.5, use_bias_conv=True, batch_norm='BN', verbose=False, se_reduction=0,
+                 se_mode='both'):
         super().__init__()
+        _se_check(se_reduction, se_mode)
         self.verbose, self.batch_norm, self.domain = verbose, batch_norm, domain
         self.spatial_dropout_rate = spatial_dropout_rate
         padding = int(((kernel_size_dilated_conv - 1) * dilation) / 2)
@@ -140,6 +156,10 @@ class ResBlock(nn.Module):
             self.dropout = hnn.Dropout1d(p=spatial_dropout_rate)
         self.conv2_skip = _make_conv(domain, 1, G, U, 1, 1, 0, 1, use_bias_conv)
         self.conv2_residual = _make_conv(domain, 1, G, Lc, 1, 1, 0, 1, use_bias_conv)
+        if se_reduction and se_mode in ('tcn', 'both'):         # registered last: every other parameter keeps its RNG draw
+            self.se = _make_se(domain, G, se_reduction)
+        else:
+            self.se = None
 
     def _conv(self, conv, x, addend=None):
         s, p, d = _geom(conv)
@@ -180,6 +200,8 @@ class ResBlock(nn.Module):
             y = H.gate(yf, yg, self.batch_filter2, self.batch_gate2, mask, st_f, st_g)
         else:
             y = H.gate_plain(yf, yg, mask)
+        if self.se is not None:
+            y = self.se(y)
         res_stats = None
         if need_residual:
             if want_res_stats and train_stats:
@@ -200,8 +222,9 @@ class TC_Block(nn.Module):
     def __init__(self, in_channels, domain='DQ', G=128, U=128, V=[128, 128], V_kernel_size=3,
                  pool_size=[[8, 2], [8, 2], [2, 2]], D=[10], spatial_dropout_rate=0.5, use_bias_conv=True,
                  dilation_mode='fibonacci', pool_time='TCN', batch_norm='BN', kernel_size_dilated_conv=3,
-                 verbose=False, attention_type=None, key_size=None, value_size=None):
+                 verbose=False, attention_type=None, key_size=None, value_size=None, se_reduction=0, se_mode='both'):
         super().__init__()
+        _se_check(se_reduction, se_mode)
         self.verbose, self.D, self.pool_time, self.domain = verbose, D, pool_time, domain
         self._gate_channels = G
         self.ResBlocks = nn.ModuleList()
@@ -209,7 +232,8 @@ class TC_Block(nn.Module):
             self.ResBlocks.append(ResBlock(in_channels=in_channels, domain=domain, G=G, U=U,
                                            kernel_size_dilated_conv=kernel_size_dilated_conv, dilation=d,
                                            spatial_dropout_rate=spatial_dropout_rate, use_bias_conv=use_bias_conv,
-                                           batch_norm=batch_norm, verbose=verbose))
+                                           batch_norm=batch_norm, verbose=verbose, se_reduction=se_reduction,
+                                           se_mode=se_mode))
         self.relu1 = hnn.ReLU()
         if self.pool_time == 'TCN':
             self.maxpool1 = hnn.MaxPool1d(pool_size[0][1])
@@ -283,10 +307,18 @@ class TC_Block(nn.Module):
 
 class _CnnStage(nn.Sequential):
     """[conv3x3, BatchNorm2d, ReLU, MaxPool2d, Dropout] with the reference's sub-module indices (model.py:269-283);
-    `forward` runs the fused path: conv (+ batch statistics in its epilogue) -> BN+ReLU+MaxPool in one pass -> dropout."""
+    `forward` runs the fused path: conv (+ batch statistics in its epilogue) -> BN+ReLU+MaxPool in one pass -> dropout.
+    With squeeze-and-excitation on, a SqueezeExcite registered as sub-module '5' gates the stage's output."""
 
     def forward(self, x):
         mods = list(self)
+        if isinstance(mods[-1], hnn.SqueezeExcite):
+            se = mods.pop()
+            return se(self._stage(mods, x))
+        return self._stage(mods, x)
+
+    @staticmethod
+    def _stage(mods, x):
         conv = mods[0]
         if isinstance(mods[1], hnn.BatchNorm2d):
             bn, pool = mods[1], mods[3]
@@ -312,8 +344,9 @@ class ConvTC_Block(nn.Module):
                  kernel_size_cnn_blocks=3, pool_size=[[8, 2], [8, 2], [2, 2]], pool_time='TCN', D=[10],
                  dilation_mode='fibonacci', G=128, U=128, kernel_size_dilated_conv=3, spatial_dropout_rate=0.5,
                  V=[128, 128], V_kernel_size=3, dropout_perc=0.3, use_bias_conv=True, batch_norm='noBN',
-                 attention_type=None, key_size=None, value_size=None, verbose=False):
+                 attention_type=None, key_size=None, value_size=None, verbose=False, se_reduction=0, se_mode='both'):
         super().__init__()
+        _se_check(se_reduction, se_mode)
         self.time_dim, self.freq_dim, self.domain, self.verbose = time_dim, freq_dim, domain, verbose
         self.D, self.kernel_size_dilated_conv, self.dilation_mode = D, kernel_size_dilated_conv, dilation_mode
         self.attenyion_type = attention_type          # (sic) attribute name of the reference, model.py:250
@@ -332,6 +365,9 @@ class ConvTC_Block(nn.Module):
                 layers.append(hnn.BatchNorm2d(c))
             layers += [hnn.ReLU(), hnn.MaxPool2d(pool), hnn.Dropout(dropout_perc)]
             stages.append(_CnnStage(*layers))
+            if se_reduction and se_mode in ('cnn', 'both'):
+                # always key '5', behind the reference's indices 0-4 (a stage without BatchNorm has no index 4)
+                stages[-1].add_module('5', _make_se(domain, c, se_reduction))
             in_chans = c
         self.cnn = nn.Sequential(*stages)
         Lc = int(freq_dim / np.prod(np.array(pool_size), axis=0)[0] * cnn_filters[-1])
@@ -339,7 +375,8 @@ class ConvTC_Block(nn.Module):
                             pool_size=pool_size, D=D, spatial_dropout_rate=spatial_dropout_rate,
                             use_bias_conv=use_bias_conv, dilation_mode=dilation_mode, pool_time=pool_time,
                             batch_norm=batch_norm, kernel_size_dilated_conv=kernel_size_dilated_conv, verbose=verbose,
-                            attention_type=attention_type, key_size=key_size, value_size=value_size)
+                            attention_type=attention_type, key_size=key_size, value_size=value_size,
+                            se_reduction=se_reduction, se_mode=se_mode)
 
     def forward(self, x):
         x = self.cnn(x)
@@ -363,8 +400,10 @@ class SELD_Model(nn.Module):
                  kernel_size_dilated_conv=3, spatial_dropout_rate=0.5, V=[128, 128], V_kernel_size=3, fc_layers=[128],
                  fc_activations='Linear', fc_dropout='all', dropout_perc=0.3, class_overlaps=3., use_bias_conv=False,
                  use_bias_linear=True, batch_norm='BN', parallel_ConvTC_block='False', parallel_magphase=False,
-                 extra_name='', attention_type=None, key_size=None, value_size=None, verbose=False):
+                 extra_name='', attention_type=None, key_size=None, value_size=None, verbose=False, se_reduction=0,
+                 se_mode='both'):
         super().__init__()
+        _se_check(se_reduction, se_mode)
         self.input_channels, self.time_dim, self.freq_dim = input_channels, time_dim, freq_dim
         self.domain, self.verbose, self.D = domain, verbose, D
         self.kernel_size_dilated_conv, self.dilation_mode = kernel_size_dilated_conv, dilation_mode
@@ -380,7 +419,8 @@ class SELD_Model(nn.Module):
                         kernel_size_cnn_blocks=kernel_size_cnn_blocks, pool_size=pool_size, pool_time=pool_time, D=D,
                         dilation_mode=dilation_mode, G=G, U=U, kernel_size_dilated_conv=kernel_size_dilated_conv,
                         spatial_dropout_rate=spatial_dropout_rate, V=V, V_kernel_size=V_kernel_size,
-                        dropout_perc=dropout_perc, use_bias_conv=use_bias_conv, batch_norm=batch_norm, verbose=False)
+                        dropout_perc=dropout_perc, use_bias_conv=use_bias_conv, batch_norm=batch_norm, verbose=False,
+                        se_reduction=se_reduction, se_mode=se_mode)
         if parallel_ConvTC_block in _TWO_STREAM:
             self.branch_A = ConvTC_Block(input_channels=input_channels // 2, **block_kw)
             self.branch_B = ConvTC_Block(input_channels=input_channels // 2, **block_kw)

@@ -24,7 +24,7 @@ import torch
 import torch.nn as nn
 
 from . import hip_ops as H
-from .model import SELD_Model
+from .model import SE_MODES, SELD_Model
 
 
 # ------------------------------------------------------------------------------------------
@@ -453,7 +453,7 @@ _EXTRA = [('synthetic', int, 0), ('max_steps', int, 0), ('epochs', int, 0), ('re
           ('augment_freq_width', int, 0), ('augment_time_masks', int, 0), ('augment_time_width', int, 0),
           ('augment_seed', int, 0), ('pit_loss', str, 'False'), ('test_hop', int, 0), ('test_tta', int, 0),
           ('post_median', int, 1), ('post_on', float, 0.5), ('post_off', float, 0.5), ('post_min_frames', int, 1),
-          ('post_max_gap', int, 0), ('post_doa', str, 'frame')]
+          ('post_max_gap', int, 0), ('post_doa', str, 'frame'), ('se_reduction', int, 0), ('se_mode', str, 'both')]
 
 
 def build_parser():
@@ -479,8 +479,19 @@ def parse_args(argv=None):
     return args
 
 
+def se_from_args(args):
+    """dict(se_reduction=, se_mode=) of the --se_reduction / --se_mode flags for SELD_Model (squeeze-and-excitation blocks;
+    reduction 0, also for an args object without the flags: none).  Every refusal comes before the device is touched."""
+    reduction, mode = getattr(args, "se_reduction", 0), getattr(args, "se_mode", "both")
+    if isinstance(reduction, bool) or not isinstance(reduction, int) or reduction < 0:
+        raise ValueError(f"--se_reduction must be a non-negative integer (0: no squeeze-and-excitation), got {reduction!r}")
+    if mode not in SE_MODES:
+        raise ValueError(f"--se_mode must be one of {', '.join(SE_MODES)}, got {mode!r}")
+    return dict(se_reduction=reduction, se_mode=mode)
+
+
 def model_from_args(args):
-    """train.py:448-465."""
+    """train.py:448-465, plus the squeeze-and-excitation flags."""
     return SELD_Model(time_dim=args.time_dim, freq_dim=args.freq_dim, input_channels=args.input_channels,
                       output_classes=args.output_classes, domain=args.domain, domain_classifier=args.domain_classifier,
                       cnn_filters=args.cnn_filters, kernel_size_cnn_blocks=args.kernel_size_cnn_blocks,
@@ -491,7 +502,7 @@ def model_from_args(args):
                       dropout_perc=args.dropout_perc, class_overlaps=args.class_overlaps, use_bias_conv=args.use_bias_conv,
                       use_bias_linear=args.use_bias_linear, batch_norm=args.batch_norm,
                       parallel_ConvTC_block=args.parallel_ConvTC_block, parallel_magphase=args.parallel_magphase,
-                      extra_name=args.model_extra_name, verbose=args.verbose)
+                      extra_name=args.model_extra_name, verbose=args.verbose, **se_from_args(args))
 
 
 # ------------------------------------------------------------------------------------------
@@ -1097,6 +1108,7 @@ def main(args, history=None):
     ensemble = ensemble_from_args(args)
     post = postprocess_from_args(args)
     pit = pit_overlaps_from_args(args)
+    se_from_args(args)
     if pit > 3:
         raise ValueError(f"--pit_loss searches the pairings of at most 3 slots per class, got --class_overlaps {pit}")
     if not args.use_cuda or not torch.cuda.is_available():
