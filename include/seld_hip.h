@@ -64,7 +64,7 @@ typedef struct seld_conv_desc {
 
 /* Layout of every `stats` buffer: SELD_STATS_REPLICAS rows of 2*C floats [sum(C) | sum of squares(C)];
  * producers add to row (workgroup index % replicas) so that thousands of workgroups do not serialise on
- * 2*C addresses; seld_bn_finalize sums the rows.  The caller zero-fills the buffer before use. */
+ * 2*C addresses; seld_bn_finalize_ex sums the rows.  The caller zero-fills the buffer before use. */
 #define SELD_STATS_REPLICAS 64
 
 int seld_hc_conv_out_shape(const seld_conv_desc* d, int32_t out[2]);
@@ -359,14 +359,10 @@ int seld_hc_linear_bwd(int32_t kind, int32_t rows, int32_t in_features, int32_t 
 /* per-channel sum / sum of squares of x (N, C, S) into a stats buffer (layout above) */
 int seld_channel_stats(const float* x, int32_t N, int32_t C, int32_t S, float* stats, void* stream);
 
-/* from raw sums: mean/invstd (saved for backward) and the running-stat update (train mode) */
-int seld_bn_finalize(const float* stats, int32_t C, int64_t count, float eps, float momentum,
-                     float* mean, float* invstd, float* running_mean /* nullable */,
-                     float* running_var /* nullable */, void* stream);
-
-/* same, plus the rest of torch.nn.BatchNorm's train-mode bookkeeping in the one launch: *num_batches_tracked += 1
- * (nullable; `_BatchNorm.forward` does it as a separate op) and, if clear_stats != 0, the stats buffer is left
- * zero-filled so that the caller can reuse it without another fill. */
+/* from raw sums: mean/invstd (saved for backward) and the running-stat update (train mode), plus the rest of
+ * torch.nn.BatchNorm's train-mode bookkeeping in the one launch: *num_batches_tracked += 1 (nullable;
+ * `_BatchNorm.forward` does it as a separate op) and, if clear_stats != 0, the stats buffer is left zero-filled so that
+ * the caller can reuse it without another fill. */
 int seld_bn_finalize_ex(float* stats, int32_t C, int64_t count, float eps, float momentum,
                         float* mean, float* invstd, float* running_mean /* nullable */,
                         float* running_var /* nullable */, int64_t* num_batches_tracked /* nullable */,
@@ -452,7 +448,9 @@ int seld_bn_act_bwd_apply(const float* dy, const float* x, const float* y, int32
 /* One-pass training-mode backward of the same op: dgamma / dbeta are ADDED to dgamma_dbeta (it need not be zero),
  * dx = BatchNorm-backward((dy [+ dy2]) * act'(y))  (dx nullable: parameter gradients only; dy2 nullable: the gradient
  * from y's second consumer -- the residual sum x_hat + conv2_residual(..) of model.py:132 -- added on load instead of
- * by a separate kernel).  SELD_EUNSUPPORTED when S % 4 != 0 or N*S > 32768: use the reduce + apply pair. */
+ * by a separate kernel).  SELD_EUNSUPPORTED when S % 4 != 0 or N*S > SELD_BN_ONE_PASS_MAX: use the reduce + apply
+ * pair. */
+#define SELD_BN_ONE_PASS_MAX 32768
 int seld_bn_act_bwd_fused(const float* dy, const float* x, const float* y, int32_t N, int32_t C, int32_t S,
                           const float* mean, const float* invstd, const float* gamma, int32_t act,
                           float* dgamma_dbeta, const float* dy2, float* dx, void* stream);
@@ -519,7 +517,9 @@ int seld_bn_pool_finish(const float* raw, int32_t N, int32_t C, int32_t S /* poo
                         const float* invstd, const float* gamma, const float* beta, float* pooled, float p, uint64_t seed,
                         uint64_t offset, const uint64_t* state, float* out, void* stream);
 
-/* One-pass training-mode backward of the gate (adds into red[4C]; SELD_EUNSUPPORTED when S % 4 != 0 or N*S > 16384). */
+/* One-pass training-mode backward of the gate (adds into red[4C]; SELD_EUNSUPPORTED when S % 4 != 0 or
+ * N*S > SELD_GATE_ONE_PASS_MAX). */
+#define SELD_GATE_ONE_PASS_MAX 16384
 int seld_gate_bwd_fused(const float* dy, const float* yf, const float* yg, int32_t N, int32_t C, int32_t S,
                         const float* mean_f, const float* invstd_f, const float* gamma_f, const float* beta_f,
                         const float* mean_g, const float* invstd_g, const float* gamma_g, const float* beta_g,

@@ -27,6 +27,7 @@ SELD_QUAT_LAYOUT_INPUT, SELD_QUAT_LAYOUT_CAT1 = 0, 1
 SELD_DECODE_F32, SELD_DECODE_F64 = 0, 1
 (SELD_NORM_BN_BWD_FUSED, SELD_NORM_BN_BWD_REDUCE, SELD_NORM_BN_BWD_APPLY, SELD_NORM_GATE_FWD, SELD_NORM_GATE_BWD_FUSED,
  SELD_NORM_GATE_BWD_REDUCE, SELD_NORM_GATE_BWD_APPLY) = range(7)       # seld_norm_kernel_label(op, ...)
+SELD_BN_ONE_PASS_MAX, SELD_GATE_ONE_PASS_MAX = 32768, 16384             # largest N*S of the one-pass backward kernels
 
 
 class SeldHipError(RuntimeError):

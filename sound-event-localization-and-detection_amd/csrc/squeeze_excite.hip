@@ -113,7 +113,7 @@ __global__ __launch_bounds__(256) void se_bwd_reduce_kernel(const float* __restr
 // out[row, :] = a[row, :] * s[n, c mod Cg] + (add ? add[n, c mod Cg] * inv_as : 0): y = x * s, and dx = dy * s + dz / (A S).
 // Nothing is summed, so a row needs no owner: one WAVE per chunk of a row -- 64 aligned groups of four (x4: chunk 0 also
 // takes the row's head elements, the last chunk its tail) or 256 single elements (x1) -- and one access per lane, as the
-// element walks of nn_ops.hip have it, but with two scalar divisions per chunk instead of a 64-bit one per lane.
+// element walks of norm.hip have it, but with two scalar divisions per chunk instead of a 64-bit one per lane.
 // The chunk index is 32 bits (a 64-bit division is emulated in about a hundred instructions and sits in front of the wave's
 // first load; 2^32 chunks are 4 TiB of floats); element offsets are 64 bits.  log2A: A = 1, 4, 8 as a shift.
 template <bool VEC>

@@ -1,4 +1,4 @@
-"""The first CNN stage fused (csrc/first_stage.hip, csrc/hcq_conv.hip, csrc/nn_ops.hip)."""
+"""The first CNN stage fused (csrc/first_stage.hip, csrc/hcq_conv.hip, csrc/norm.hip, csrc/elementwise.hip)."""
 import ctypes
 import os
 

@@ -1,5 +1,6 @@
-"""BatchNorm + activation, the gate, activations, pooling, dropout and transposes (csrc/nn_ops.hip), and the optimiser's
-gradient slots as the backward kernels' targets, with the stacked / reshaped convolution weights that point at them."""
+"""BatchNorm + activation and the gate (csrc/norm.hip), activations, pooling, dropout and transposes
+(csrc/elementwise.hip), and the optimiser's gradient slots as the backward kernels' targets, with the stacked / reshaped
+convolution weights that point at them."""
 import os
 
 import torch
@@ -163,7 +164,7 @@ def axpy_(dst_first, src, n):
 
 
 def _one_pass_ok(N, S, limit):
-    """The one-workgroup-per-channel backward kernels (csrc/nn_ops.hip) hold a channel's N*S values in registers."""
+    """The one-workgroup-per-channel backward kernels (csrc/norm.hip) hold a channel's N*S values in registers."""
     return S % 4 == 0 and N * S <= limit and not os.environ.get("SELD_BN_TWO_PASS")
 
 
@@ -203,7 +204,7 @@ class BnActFn(torch.autograd.Function):
         N, C, S = _ncs(x)
         slot, clean = _claim_grad_slots((gamma, beta))
         st = L.current_stream()
-        if ctx.training and _one_pass_ok(N, S, 32768):
+        if ctx.training and _one_pass_ok(N, S, L.SELD_BN_ONE_PASS_MAX):
             # one workgroup per channel: reads every operand once and ADDS [dgamma | dbeta] to `red`
             red = slot if slot is not None else torch.zeros(2 * C, device=x.device, dtype=torch.float32)
             dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
@@ -280,7 +281,7 @@ class GateFn(torch.autograd.Function):
         N, C, S = _ncs(yf)
         slot, clean = _claim_grad_slots((gf, bf, gg, bg))
         st = L.current_stream()
-        if ctx.training and _one_pass_ok(N, S, 16384):
+        if ctx.training and _one_pass_ok(N, S, L.SELD_GATE_ONE_PASS_MAX):
             red = slot if slot is not None else torch.zeros(4 * C, device=yf.device, dtype=torch.float32)
             dyf, dyg = torch.empty_like(yf), torch.empty_like(yg)
             L.check(L.lib().seld_gate_bwd_fused(L.ptr(dy), L.ptr(yf), L.ptr(yg), N, C, S, L.ptr(mf), L.ptr(isf),

@@ -1,4 +1,4 @@
-"""Every kernel form of BatchNorm + activation and of the gate (csrc/nn_ops.hip), element by element against fp64
+"""Every kernel form of BatchNorm + activation and of the gate (csrc/norm.hip), element by element against fp64
 expressions written here, plus the plain activations on a saturation sweep.  (Pooling ties: tests/test_gpu_ops.py.)
 
 The kernels are called through the C ABI with fp32 mean / invstd / gamma / beta chosen by the test, and the backward
@@ -74,7 +74,7 @@ LARGEST ERROR / BOUND ON THE MI355X (printed by the tests; above 1 is a defect, 
   H.bn_act / H.gate end to end                   y 0.486 / 0.317 | sums 0.002 | dx 0.193 | dyf 0.165 | dyg 0.107
   gradient slots, all rounds                     slot 0.032 | dx 0.262 (BatchNorm), 0.191 (gate)
 
-No ratio is above 1: these tests found no defect in the kernels, and nothing in csrc/nn_ops.hip changed but the selection
+No ratio is above 1: these tests found no defect in the kernels, and nothing in csrc/norm.hip changed but the selection
 code, which the entry points now share with seld_norm_kernel_label.  gate_tanh and gate_sig keep their 3e-7 with room:
 where the other factor is exactly 1 the sweep sees at most 1.5e-7.  dx(eval) sits near 1 by construction: a dz is one
 rounding, and an element just above a power of two uses all of u.  The elementwise bounds are used to between a seventh
@@ -98,7 +98,7 @@ U = 2.0 ** -24
 TINY = 2.0 ** -126
 SLACK = 1.0 + 2.0 ** -10
 SENTINEL = -1234.5
-GATE_ABS = 3e-7                      # csrc/nn_ops.hip, above gate_sig / gate_tanh
+GATE_ABS = 3e-7                      # csrc/norm.hip, above gate_sig / gate_tanh
 EUNSUPPORTED = -4
 ACT_NAMES = ("none", "relu", "tanh", "sigmoid")
 ACT_REL = (0.0, 0.0, 4 * U, 4 * U)

@@ -826,7 +826,7 @@ def test_linear_backward_row_splits(kind, fin, fout, rows):
 
 
 def test_loss_needs_no_zeroed_scalar_and_repeats_bit_for_bit():
-    """seld_loss_fwd_bwd WRITES the loss (ticketed ordered reduction, csrc/nn_ops.hip): a poisoned output buffer, many
+    """seld_loss_fwd_bwd WRITES the loss (ticketed ordered reduction, csrc/train_step.hip): a poisoned output buffer, many
     evaluations back to back, sizes from one workgroup to the 256-workgroup cap."""
     P = pkg()
     L = P._lib

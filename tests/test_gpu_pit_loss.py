@@ -1,4 +1,4 @@
-"""The permutation-invariant SELD loss (csrc/nn_ops.hip: loss_pit_kernel; hip_ops.seld_loss_pit; train.py --pit_loss)
+"""The permutation-invariant SELD loss (csrc/train_step.hip: loss_pit_kernel; hip_ops.seld_loss_pit; train.py --pit_loss)
 against the fp64 brute force of tests/pit_loss_ref.py, which also makes the inputs.
 
 Bounds, those tests/test_gpu_train_step.py holds the plain loss to (u = 2^-24, floor of one fp32 denormal):

@@ -1,4 +1,4 @@
-"""The four kernels every training step ends in (csrc/nn_ops.hip: loss_kernel, adam_kernel, adam_state_kernel,
+"""The four kernels every training step ends in (csrc/train_step.hip: loss_kernel, adam_kernel, adam_state_kernel,
 step_begin_kernel), element by element against fp64 expressions written here.
 
 Both sides start from the same fp32 inputs and the same fp32-rounded hyper-parameters, so only the kernel's arithmetic

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Times the two loss kernels (csrc/nn_ops.hip: loss_kernel, loss_pit_kernel<3>) through the C ABI, forward + backward
+"""Times the two loss kernels (csrc/train_step.hip: loss_kernel, loss_pit_kernel<3>) through the C ABI, forward + backward
 as the training step calls them (perm and parts not requested), at the config-3 step (2048 rows = 32 x 64 frames, 14
 classes x 3 slots) and at 32 times that.
 

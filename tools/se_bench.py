@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Times the squeeze-and-excitation kernels (csrc/squeeze_excite.hip) on the activations of the benchmark's default
 workload (bench.py c3: DQ, batch 32, 192 CNN filters, G = 384, 128 mel x 512 frames, --se_reduction 4): the three CNN stage
-outputs and the residual blocks' gated y.  Each streaming kernel is timed against a kernel of csrc/nn_ops.hip with the same
+outputs and the residual blocks' gated y.  Each streaming kernel is timed against a kernel of csrc/norm.hip with the same
 traffic on the same tensor:
 
   se_scale, se_bwd_apply   bn_act_fwd          read 1, write 1
