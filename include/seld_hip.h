@@ -779,6 +779,40 @@ size_t seld_stft_workspace(int32_t nperseg);
 int seld_stft_magphase_ws(const float* x, int32_t C, int32_t L, int32_t nperseg, int32_t noverlap,
                           int32_t output_phase, int32_t cut_dc, int32_t cut_last_timeframe,
                           const float* window, float* out, void* workspace, size_t workspace_bytes, void* stream);
+/* seld_stft_magphase_ws, but out (2C, bins, frames): plane c = Re Z of channel c, plane C + c = Im Z (same scaling:
+ * the window divided by its sum).  Same refusals, nothing launched on refusal. */
+int seld_stft_complex_ws(const float* x, int32_t C, int32_t L, int32_t nperseg, int32_t noverlap,
+                         int32_t cut_dc, int32_t cut_last_timeframe, const float* window, float* out,
+                         void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Log-power and first-order-Ambisonics intensity-vector features of complex spectra, linear in
+ * frequency or projected onto bands (a mel filterbank); csrc/spatial_features.hip.
+ * z (2C, bins, frames) as seld_stft_complex_ws writes it.
+ * kind:   0 LOGPOWER     out (C, bands, frames)          log(P + eps) per channel
+ *         1 IV           out (3C/4, bands, frames)       per group of 4 channels [W, D1, D2, D3]: three components
+ *         2 LOGPOWER_IV  layout 0: out (C + 3C/4, ...)   all log-power planes, then the IV planes of group 0, 1, ...
+ *                        layout 1: out (C, ...)          per group [log-power of W, I1, I2, I3] (one quaternion)
+ * Per bin k: p_c = |Z_c|^2;  E = eps + |W|^2 + (|D1|^2 + |D2|^2 + |D3|^2) / 3;  i_d = Re(conj(W) D_d) / E.
+ * fb == NULL: bands == bins, P = p, I_d = i_d.
+ * fb (bands, bins) fp32, band_lo / band_hi (bands) int32 = first and one-past-last bin of each band that may be
+ *   nonzero:  P[m] = sum_k fb[m,k] p[k],  I_d[m] = sum_k fb[m,k] i_d[k]  (normalised per bin, then projected: the
+ *   DCASE baseline's order), sums over band_lo[m] <= k < band_hi[m], clamped to [0, bins) by the kernel, taken in
+ *   the order of k.  No atomics: results are run-to-run identical.
+ * SELD_EINVAL, before any HIP call: z or out NULL; C, bins, frames or bands < 1; an unknown kind or layout; an IV kind
+ *   with C % 4 != 0; layout 1 with kind != 2; eps <= 0 or NaN; fb without band_lo / band_hi; fb == NULL with
+ *   bands != bins.  SELD_EUNSUPPORTED: a plane of z or out of 2^31 floats or more, more than 65535 channels (kind 0)
+ *   or groups.  A refused call launches nothing and writes nothing.
+ * ------------------------------------------------------------------------------------------ */
+#define SELD_FEAT_LOGPOWER     0
+#define SELD_FEAT_IV           1
+#define SELD_FEAT_LOGPOWER_IV  2
+#define SELD_FEAT_LAYOUT_GROUPED     0
+#define SELD_FEAT_LAYOUT_QUATERNION  1
+int seld_spatial_features_channels(int32_t C, int32_t kind, int32_t layout);      /* planes of out, or SELD_EINVAL */
+int seld_spatial_features(const float* z, int32_t C, int32_t bins, int32_t frames, int32_t kind, int32_t layout,
+                          const float* fb, const int32_t* band_lo, const int32_t* band_hi, int32_t bands,
+                          float eps, float* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Dataset normalisation, in place on a resident predictor array x (items, channels, hw) fp32

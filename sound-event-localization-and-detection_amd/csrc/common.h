@@ -17,6 +17,9 @@ inline int check_launch() {
     return SELD_OK;
 }
 
+// third value of the STFT kernels' `output_phase` (stft.hip, stft_any.hip): the complex spectrum itself
+constexpr int kStftComplex = 2;
+
 typedef float floatx4 __attribute__((ext_vector_type(4)));
 
 // ---- Hamilton product block structure --------------------------------------

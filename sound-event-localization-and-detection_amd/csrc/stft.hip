@@ -11,6 +11,7 @@
 // LDS (N/2 butterflies per pass, twiddles from an LDS table built with sincospif), collects
 // |Z| / angle(Z) in an LDS tile [bin][frame] and writes it with the frame index fastest, which is
 // the output's contiguous axis.
+// seld_stft_complex_ws runs the same kernels with Re Z / Im Z in the places of |Z| / angle(Z).
 #include "common.h"
 #include "env.h"
 
@@ -19,7 +20,10 @@ namespace seld {
 constexpr int FT = 16;
 
 // bin0: first bin kept (1 = DC dropped, the reference's cut_dc=True; 0 = all N/2 + 1 bins), nbins = N/2 + 1 - bin0.
+// output_phase: 0 = |Z|, 1 = |Z| and angle(Z), kStftComplex = Re Z and Im Z in the places of |Z| and angle(Z): CPLX, an
+// instantiation of its own, so that the other two values run the code they always ran.
 // window_g (nullable): N window values already divided by their sum; null = periodic Hamming.
+template <bool CPLX>
 __global__ __launch_bounds__(256) void stft_kernel(const float* __restrict__ x, int C, int L, int N, int logN, int hop,
                                                    int frames_out, int output_phase, int bin0,
                                                    const float* __restrict__ window_g, float* __restrict__ out) {
@@ -78,8 +82,13 @@ __global__ __launch_bounds__(256) void stft_kernel(const float* __restrict__ x, 
         // bins bin0 .. N/2
         for (int b = tid; b < nbins; b += blockDim.x) {
             const float2 z = src[b + bin0];
-            mag[b * (FT + 1) + f] = sqrtf(z.x * z.x + z.y * z.y);
-            if (output_phase) pha[b * (FT + 1) + f] = atan2f(z.y, z.x);
+            if constexpr (CPLX) {
+                mag[b * (FT + 1) + f] = z.x;
+                pha[b * (FT + 1) + f] = z.y;
+            } else {
+                mag[b * (FT + 1) + f] = sqrtf(z.x * z.x + z.y * z.y);
+                if (output_phase) pha[b * (FT + 1) + f] = atan2f(z.y, z.x);
+            }
         }
         __syncthreads();
     }
@@ -132,6 +141,7 @@ constexpr int FT512 = 16;                 // frames per workgroup
 constexpr int SK512 = 512 + 64;           // one skewed 512-float array: element i lives at i + (i >> 3)
 __device__ __forceinline__ int sk(int i) { return i + (i >> 3); }
 
+template <bool CPLX>
 __global__ __launch_bounds__(256) void stft512_kernel(const float* __restrict__ x, int C, int L, int hop, int frames_out,
                                                       int output_phase, int bin0, const float* __restrict__ window_g,
                                                       float* __restrict__ out) {
@@ -214,11 +224,18 @@ __global__ __launch_bounds__(256) void stft512_kernel(const float* __restrict__ 
             const float ar = 0.5f * (zr + yr), ai = 0.5f * (zi - yi);
             const float br = 0.5f * (zi + yi), bi = -0.5f * (zr - yr);
             const int f = 2 * pr;
-            mag[b * (FT512 + 1) + f] = sqrtf(ar * ar + ai * ai);
-            mag[b * (FT512 + 1) + f + 1] = sqrtf(br * br + bi * bi);
-            if (output_phase) {
-                pha[b * (FT512 + 1) + f] = atan2f(ai, ar);
-                pha[b * (FT512 + 1) + f + 1] = atan2f(bi, br);
+            if constexpr (CPLX) {
+                mag[b * (FT512 + 1) + f] = ar;
+                mag[b * (FT512 + 1) + f + 1] = br;
+                pha[b * (FT512 + 1) + f] = ai;
+                pha[b * (FT512 + 1) + f + 1] = bi;
+            } else {
+                mag[b * (FT512 + 1) + f] = sqrtf(ar * ar + ai * ai);
+                mag[b * (FT512 + 1) + f + 1] = sqrtf(br * br + bi * bi);
+                if (output_phase) {
+                    pha[b * (FT512 + 1) + f] = atan2f(ai, ar);
+                    pha[b * (FT512 + 1) + f + 1] = atan2f(bi, br);
+                }
             }
         }
         __builtin_amdgcn_wave_barrier();                 // the scratch is rewritten by the wave's next pair
@@ -268,10 +285,10 @@ extern "C" size_t seld_stft_workspace(int32_t nperseg) {
     return stft_any_workspace(nperseg);
 }
 
-extern "C" int seld_stft_magphase_ws(const float* x, int32_t C, int32_t L, int32_t nperseg, int32_t noverlap,
-                                     int32_t output_phase, int32_t cut_dc, int32_t cut_last_timeframe,
-                                     const float* window, float* out, void* workspace, size_t workspace_bytes,
-                                     void* stream) {
+// every STFT entry point: validate, pick the kernel of the segment length, launch (nothing is launched on refusal)
+static int stft_run(const float* x, int32_t C, int32_t L, int32_t nperseg, int32_t noverlap, int output_phase,
+                    int32_t cut_dc, int32_t cut_last_timeframe, const float* window, float* out, void* workspace,
+                    size_t workspace_bytes, void* stream) {
     if (!x || !out || C <= 0 || L <= 0 || nperseg <= 1 || noverlap < 0 || noverlap >= nperseg) return SELD_EINVAL;
     if (nperseg > 4096) return SELD_EUNSUPPORTED;
     const int frames = frames_total(L, nperseg, noverlap) - (cut_last_timeframe ? 1 : 0);
@@ -282,20 +299,36 @@ extern "C" int seld_stft_magphase_ws(const float* x, int32_t C, int32_t L, int32
     int logN = 0;
     while ((1 << logN) < nperseg) ++logN;
     const int half = nperseg / 2;
+    const bool cplx = output_phase == kStftComplex;
     if (nperseg == 512) {
         const size_t smem512 = sizeof(float) * ((size_t)3 * 512 + (size_t)4 * 2 * SK512 + (size_t)2 * 257 * (FT512 + 1));
-        hipLaunchKernelGGL(stft512_kernel, dim3((frames + FT512 - 1) / FT512, C), dim3(256), smem512, (hipStream_t)stream, x, C, L,
+        const auto kernel = cplx ? stft512_kernel<true> : stft512_kernel<false>;
+        hipLaunchKernelGGL(kernel, dim3((frames + FT512 - 1) / FT512, C), dim3(256), smem512, (hipStream_t)stream, x, C, L,
                            nperseg - noverlap, frames, output_phase, cut_dc ? 1 : 0, window, out);
         return check_launch();
     }
     const size_t smem = sizeof(float) * ((size_t)2 * nperseg * 2 + (size_t)half * 2 + nperseg + (size_t)2 * (half + 1) * (FT + 1));
+    const auto kernel = cplx ? stft_kernel<true> : stft_kernel<false>;
     if (smem > 64 * 1024 &&       // N = 1024: 94 KB
-        hipFuncSetAttribute((const void*)stft_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess)
+        hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess)
         return SELD_ELAUNCH;
     dim3 grid((frames + FT - 1) / FT, C);
-    hipLaunchKernelGGL(stft_kernel, grid, dim3(256), smem, (hipStream_t)stream, x, C, L, nperseg, logN,
+    hipLaunchKernelGGL(kernel, grid, dim3(256), smem, (hipStream_t)stream, x, C, L, nperseg, logN,
                        nperseg - noverlap, frames, output_phase, cut_dc ? 1 : 0, window, out);
     return check_launch();
+}
+extern "C" int seld_stft_magphase_ws(const float* x, int32_t C, int32_t L, int32_t nperseg, int32_t noverlap,
+                                     int32_t output_phase, int32_t cut_dc, int32_t cut_last_timeframe,
+                                     const float* window, float* out, void* workspace, size_t workspace_bytes,
+                                     void* stream) {
+    return stft_run(x, C, L, nperseg, noverlap, output_phase ? 1 : 0, cut_dc, cut_last_timeframe, window, out, workspace,
+                    workspace_bytes, stream);
+}
+extern "C" int seld_stft_complex_ws(const float* x, int32_t C, int32_t L, int32_t nperseg, int32_t noverlap,
+                                    int32_t cut_dc, int32_t cut_last_timeframe, const float* window, float* out,
+                                    void* workspace, size_t workspace_bytes, void* stream) {
+    return stft_run(x, C, L, nperseg, noverlap, kStftComplex, cut_dc, cut_last_timeframe, window, out, workspace,
+                    workspace_bytes, stream);
 }
 extern "C" int seld_stft_magphase_ex(const float* x, int32_t C, int32_t L, int32_t nperseg, int32_t noverlap,
                                      int32_t output_phase, int32_t cut_dc, int32_t cut_last_timeframe,

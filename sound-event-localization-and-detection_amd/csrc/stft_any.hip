@@ -199,11 +199,13 @@ __global__ __launch_bounds__(256) void stft_chirp_kernel(int N, int M, unsigned 
     for (int j = tid; j < M; j += 256) spec[j] = make_float2(res[j].x * inv_m, res[j].y * inv_m);
 }
 
+// output_phase: 0 = |Z|, 1 = |Z| and angle(Z), kStftComplex = Re Z and Im Z in their places: CPLX, an instantiation of
+// its own, so that the other two values run the code they always ran.
 // bin0: first bin kept (1 = DC dropped); window_g (nullable): N window values already divided by their sum, null =
 // periodic Hamming.  P: FFT length (N, or M for BLUE); ntr transforms of 2 frames each, transform t at t * ts in both
 // LDS buffers.  BLUE: chirp / spec from stft_chirp_kernel.  Twiddles: the W_N table in LDS, or (BLUE) the two short
 // tables of TwSplit.
-template <bool BLUE>
+template <bool BLUE, bool CPLX>
 __global__ __launch_bounds__(256) void stft_any_kernel(const float* __restrict__ x, int C, int L, int N, int hop,
                                                        int frames_out, int output_phase, int bin0,
                                                        const float* __restrict__ window_g, int P,
@@ -282,8 +284,13 @@ __global__ __launch_bounds__(256) void stft_any_kernel(const float* __restrict__
         float re, im;
         if ((f & 1) == 0) { re = 0.5f * (z.x + y.x); im = 0.5f * (z.y - y.y); }
         else { re = 0.5f * (z.y + y.y); im = -0.5f * (z.x - y.x); }
-        out[((size_t)c * nbins + b) * frames_out + m0 + f] = sqrtf(re * re + im * im);
-        if (output_phase) out[((size_t)(C + c) * nbins + b) * frames_out + m0 + f] = atan2f(im, re);
+        if constexpr (CPLX) {
+            out[((size_t)c * nbins + b) * frames_out + m0 + f] = re;
+            out[((size_t)(C + c) * nbins + b) * frames_out + m0 + f] = im;
+        } else {
+            out[((size_t)c * nbins + b) * frames_out + m0 + f] = sqrtf(re * re + im * im);
+            if (output_phase) out[((size_t)(C + c) * nbins + b) * frames_out + m0 + f] = atan2f(im, re);
+        }
     }
 }
 
@@ -377,21 +384,24 @@ int stft_any_launch(const float* x, int C, int L, int N, int hop, int frames, in
     float2* spec = g.blue ? reinterpret_cast<float2*>(ws) : nullptr;
     float2* chirp = g.blue ? reinterpret_cast<float2*>(ws + g.off_chirp) : nullptr;
     const dim3 grid((frames + 2 * g.ntr - 1) / (2 * g.ntr), C);
+    const bool cplx = output_phase == kStftComplex;
     if (g.blue) {
+        const auto kernel = cplx ? stft_any_kernel<true, true> : stft_any_kernel<true, false>;
         int rc = set_lds((const void*)stft_chirp_kernel, g.smem_chirp);
-        if (rc == SELD_OK) rc = set_lds((const void*)stft_any_kernel<true>, g.smem);
+        if (rc == SELD_OK) rc = set_lds((const void*)kernel, g.smem);
         if (rc != SELD_OK) return rc;
         hipLaunchKernelGGL(stft_chirp_kernel, dim3(1), dim3(256), g.smem_chirp, stream, N, g.P, g.radices, g.npass, chirp,
                            spec);
         rc = check_launch();
         if (rc != SELD_OK) return rc;
-        hipLaunchKernelGGL(stft_any_kernel<true>, grid, dim3(256), g.smem, stream, x, C, L, N, hop, frames, output_phase,
+        hipLaunchKernelGGL(kernel, grid, dim3(256), g.smem, stream, x, C, L, N, hop, frames, output_phase,
                            bin0, window, g.P, g.radices, g.npass, g.ntr, g.ts, chirp, spec, out);
         return check_launch();
     }
-    const int rc = set_lds((const void*)stft_any_kernel<false>, g.smem);
+    const auto kernel = cplx ? stft_any_kernel<false, true> : stft_any_kernel<false, false>;
+    const int rc = set_lds((const void*)kernel, g.smem);
     if (rc != SELD_OK) return rc;
-    hipLaunchKernelGGL(stft_any_kernel<false>, grid, dim3(256), g.smem, stream, x, C, L, N, hop, frames, output_phase,
+    hipLaunchKernelGGL(kernel, grid, dim3(256), g.smem, stream, x, C, L, N, hop, frames, output_phase,
                        bin0, window, g.P, g.radices, g.npass, g.ntr, g.ts, chirp, spec, out);
     return check_launch();
 }

@@ -21,6 +21,7 @@ from .event_metrics import *    # noqa: F401,F403
 from .ensemble import *         # noqa: F401,F403
 from .smooth import *           # noqa: F401,F403
 from .squeeze_excite import *   # noqa: F401,F403
+from .features import *         # noqa: F401,F403
 # `import *` skips underscore names: the ones train.py, the tests and tools/ reach, and the rest of the module surface
 from ._core import _drop_kernel_choice_caches, _pair, _req, _scratch_pools  # noqa: F401
 from .train_ops import _req_inplace, _unit_gradients  # noqa: F401
@@ -36,3 +37,4 @@ from .linear_mha import _mha_keep_mask  # noqa: F401
 from .first_stage import _first_stage_nostore, _fs_bytes  # noqa: F401
 from .quat import (_quat_cat1_shape, _quat_modulus_sum, _quat_summed_shape, _quat_ws, _QuatUnaryFn, _rot_check,  # noqa: F401
                    _rot_dims)
+from .features import _band_tables, _feature_form, _features_of_planes, _mel_tables  # noqa: F401

@@ -5,6 +5,9 @@ which turn the network's outputs into the challenge's submission rows, and `csv_
 `segment_task2` (utility_functions.py:212-342), which build the dense target from a label file and cut features, targets
 and waveforms into training segments.
 
+`stft_complex` and `seld_features` go beyond the reference: the complex spectra themselves, and the log-(mel-)power /
+FOA intensity-vector features of them (csrc/spatial_features.hip through hip_ops.spatial_features).
+
 Same names, same arguments, same result layout.  The transform runs on the GPU (csrc/stft.hip, csrc/stft_any.hip through
 seld_stft_magphase_ws) for every segment length 2 <= nperseg <= 4096, the decoding through csrc/decode.hip
 (hip_ops.decode_events), the target encoding and the segmentation through csrc/labels.hip (hip_ops.encode_events,
@@ -80,33 +83,103 @@ def spectrum_fast(x, nperseg=512, noverlap=128, window='hamming', cut_dc=True, o
     t = torch.as_tensor(np.ascontiguousarray(x, dtype=np.float32)) if is_numpy else x
     if t.dim() != 2:
         raise ValueError(f"spectrum_fast expects (channels, samples), got shape {tuple(t.shape)}")
+    out = _stft_planes("spectrum_fast", t, nperseg, noverlap, window, cut_dc, cut_last_timeframe, int(bool(output_phase)))
+    if is_numpy:
+        return out.cpu().numpy().astype(out_dtype)
+    return out
+
+
+def _launch_device(what, t):
     if not torch.cuda.is_available():
-        raise L.SeldHipError("spectrum_fast: no HIP device (this package has no CPU path)")
-    dev = t.device if t.is_cuda else torch.device("cuda", torch.cuda.current_device())
+        raise L.SeldHipError(f"{what}: no HIP device (this package has no CPU path)")
+    return t.device if t.is_cuda else torch.device("cuda", torch.cuda.current_device())
+
+
+def _stft_planes(what, t, nperseg, noverlap, window, cut_dc, cut_last_timeframe, form):
+    """What every transform here shares: the argument checks, the window table, the workspace and the launch.
+    t (rows, samples), a tensor on the host or the device; form 0: |Z|, 1: |Z| then angle(Z) (seld_stft_magphase_ws),
+    'complex': Re Z then Im Z (seld_stft_complex_ws).  Returns the float32 device tensor (rows or 2 rows, bins, frames)."""
+    dev = _launch_device(what, t)
     t = t.to(device=dev, dtype=torch.float32).contiguous()
     C, n = t.shape
     nperseg, noverlap = int(nperseg), int(noverlap)
     if noverlap >= nperseg:
         raise ValueError('noverlap must be less than nperseg.')          # scipy's message
     if nperseg > MAX_NPERSEG:
-        raise L.SeldHipError(f"spectrum_fast: nperseg={nperseg} is longer than the longest segment the HIP STFT "
+        raise L.SeldHipError(f"{what}: nperseg={nperseg} is longer than the longest segment the HIP STFT "
                              f"transforms ({MAX_NPERSEG})")
     lib = L.lib()
     frames = lib.seld_stft_frames_ex(n, nperseg, noverlap, int(bool(cut_last_timeframe)))
     if frames <= 0:
-        raise L.SeldHipError("spectrum_fast: invalid segment parameters")
+        raise L.SeldHipError(f"{what}: invalid segment parameters")
     bins = nperseg // 2 + 1 - int(bool(cut_dc))
     win = _window_values(window, nperseg, dev)
-    out = torch.empty(((2 if output_phase else 1) * C, bins, frames), device=dev, dtype=torch.float32)
+    out = torch.empty(((1 if form == 0 else 2) * C, bins, frames), device=dev, dtype=torch.float32)
     ws = stft_workspace(nperseg, dev)
+    tail = (int(bool(cut_dc)), int(bool(cut_last_timeframe)), L.ptr(win), L.ptr(out), L.ptr(ws),
+            0 if ws is None else ws.numel(), L.current_stream())
     with torch.cuda.device(dev):
-        L.check(lib.seld_stft_magphase_ws(L.ptr(t), C, n, nperseg, noverlap, int(bool(output_phase)), int(bool(cut_dc)),
-                                          int(bool(cut_last_timeframe)), L.ptr(win), L.ptr(out), L.ptr(ws),
-                                          0 if ws is None else ws.numel(), L.current_stream()),
-                "seld_stft_magphase_ws")
-    if is_numpy:
-        return out.cpu().numpy().astype(out_dtype)
+        if form == 'complex':
+            L.check(lib.seld_stft_complex_ws(L.ptr(t), C, n, nperseg, noverlap, *tail), "seld_stft_complex_ws")
+        else:
+            L.check(lib.seld_stft_magphase_ws(L.ptr(t), C, n, nperseg, noverlap, int(form), *tail), "seld_stft_magphase_ws")
     return out
+
+
+def _rows(what, x):
+    """x (..., channels, samples), a numpy array or a tensor -> (float32 tensor (rows, samples) with the leading axes
+    flattened onto the channel axis, the shape of those axes channels included, whether x was numpy)."""
+    is_numpy = not torch.is_tensor(x)
+    if is_numpy:
+        x = torch.as_tensor(np.ascontiguousarray(x, dtype=np.float32))
+    if x.dim() < 2 or x.is_complex():
+        raise ValueError(f"{what} expects real (..., channels, samples), got shape {tuple(x.shape)}")
+    return x.reshape((-1, x.shape[-1])), tuple(x.shape[:-1]), is_numpy
+
+
+def stft_complex(x, nperseg=512, noverlap=128, window='hamming', cut_dc=True, cut_last_timeframe=True):
+    '''
+    The complex spectra spectrum_fast takes the modulus and angle of: scipy.signal.stft(x, window, nperseg, noverlap)
+    [-> DC bin dropped] [-> last frame dropped], the window divided by its sum, for every 2 <= nperseg <= 4096.
+
+    x: (..., channels, samples), numpy array or tensor; leading axes are batch (flattened onto the channel axis for the
+    launch; unlike spectrum_fast's literal batched form, the two cuts always act on the bin and frame axes).  Returns a
+    complex64 tensor (..., channels, nperseg/2 + 1 - cut_dc, frames - cut_last_timeframe) on the device.  The kernels
+    write planes of real and imaginary parts; they are interleaved once here.
+    '''
+    rows, lead, _ = _rows("stft_complex", x)
+    planes = _stft_planes("stft_complex", rows, nperseg, noverlap, window, cut_dc, cut_last_timeframe, 'complex')
+    R = rows.shape[0]
+    return torch.complex(planes[:R], planes[R:]).view(lead + tuple(planes.shape[1:]))
+
+
+def seld_features(x, kind='logpower_iv', layout='grouped', nperseg=512, noverlap=128, window='hamming', n_mels=0,
+                  sr=32000, fmin=0.0, fmax=None, cut_dc=True, cut_last_timeframe=True, eps=1e-10):
+    '''
+    Log-(mel-)power and first-order-Ambisonics intensity-vector features of a multichannel recording, in two launches:
+    the STFT in its complex form (stft_complex's transform) and hip_ops.spatial_features' kernel on its planes.
+
+    x: (..., channels, samples); every four channels are one FOA microphone [W, D1, D2, D3].  kind, layout, eps:
+    hip_ops.spatial_features.  n_mels=0 keeps linear frequency; otherwise the bins are projected onto
+    hip_ops.mel_filterbank(sr, nperseg, n_mels, fmin, fmax) (Slaney scale and normalisation; its DC column dropped with
+    cut_dc).  Returns (..., C_out, n_mels or bins, frames): a float32 numpy array for numpy input, a float32 device
+    tensor for a tensor.  layout='quaternion' turns the eight channels of two FOA microphones into eight feature
+    channels [log-power of W, I1, I2, I3] x 2: one dual quaternion, the input of domain='DQ'.
+    '''
+    what = "seld_features"
+    rows, lead, is_numpy = _rows(what, x)
+    k, l = H._feature_form(what, kind, layout, lead[-1], eps)
+    n_mels = int(n_mels)
+    if n_mels < 0:
+        raise ValueError(f"{what}: n_mels must be 0 (linear frequency) or positive, got {n_mels}")
+    dev = _launch_device(what, rows)
+    tables = None
+    if n_mels:
+        tables = H._mel_tables(float(sr), int(nperseg), n_mels, float(fmin), None if fmax is None else float(fmax),
+                               bool(cut_dc), dev)
+    planes = _stft_planes(what, rows, nperseg, noverlap, window, cut_dc, cut_last_timeframe, 'complex')
+    out = H._features_of_planes(what, planes, lead[:-1], lead[-1], k, l, tables, eps)
+    return out.cpu().numpy() if is_numpy else out
 
 
 def _decode_one(sed, doa, max_loc_value, num_classes, max_overlaps):
