@@ -1071,6 +1071,36 @@ int seld_segment(const void* src, int32_t dtype, int32_t layout, int64_t rows, i
  *   y_cols < 4, no multiple of 4 or no divisor of row_y (with the y pair); p_swap outside [0, 1]; n_fmask or n_tmask
  *   outside {0, 1, 2}; f_max outside [0, F]; t_max outside [0, T].  SELD_EUNSUPPORTED: a row of 2^31 floats or more.
  *   Nothing is launched on refusal.
+ * seld_gather_rows_rot is seld_gather_rows with a per-sample ROTATION of the sound field applied on the way, for
+ * predictors whose directional channels are intensity-vector components (seld_spatial_features, kind IV, or kind
+ * LOGPOWER_IV in the quaternion layout): a real 3-vector per (f, t) that a rotation R of the sound field turns into
+ * R times itself, the normaliser E being invariant.  Addressing, zero-fill of invalid positions, untouched rows
+ * [count, B), geometry (C, F, T, y_cols), epoch, seed, the counter and the masks are those of seld_gather_rows_aug; one
+ * launch, recordable.
+ *   triples: n_triples in [1, 5] channel triples (cx, cy, cz), the x, y and z component of one intensity vector each,
+ *   passed BY VALUE, 4 bits per entry: entry 3 * k + a (a = 0, 1, 2 for cx, cy, cz of triple k) in bits
+ *   [4 * (3k + a), 4 * (3k + a) + 4).  The entries are distinct and inside [0, C); bits above the last entry are 0.
+ *   Every channel outside the triples is copied.
+ *   g = 3, rotation (a group seld_gather_rows_aug does not draw; g = 0 is not drawn here):
+ *       w = philox4x32_10(counter | 3, seed);  applied iff u01(w[1]) < p_rot
+ *       u = u01(w[0]);  (s, c) = sincospif(2 * u)   (2 * u is exact in fp32: no argument-reduction error)
+ *       mirror = rot_mirror && (w[2] >> 31);  zflip = rot_zflip && (w[3] >> 31)
+ *       R = diag(1, mirror ? -1 : 1, zflip ? -1 : 1) . [[c, -s, 0], [s, c, 0], [0, 0, 1]]
+ *     a rotation about the vertical axis by a uniform angle, optionally mirrored in y and in z.
+ *   matrices (nullable): (count, 9) fp32 on the device, row-major.  Sample b then takes matrices[b] as R whatever
+ *     p_rot says, and group 3 is not drawn.  The matrix is applied as given: orthogonality is the caller's business.
+ *   A rotated sample, per triple and (f, t), and per label slot s:
+ *       x'[c_a] = fma(R[a][2], x[cz], fma(R[a][1], x[cy], R[a][0] * x[cx]))                          a = 0, 1, 2
+ *       location'(s, a) = fma(R[a][2], location(s, 2), fma(R[a][1], location(s, 1), R[a][0] * location(s, 0)))
+ *     in fp32; activity copied.  A sample that draws no rotation, and every channel outside the triples, moves as bits.
+ *   g = 1, g = 2: the masks of seld_gather_rows_aug, after the rotation, over every channel, filled with `fill`.
+ *   Every predictor byte is read once and written once: a lane that owns a 16-byte piece of a triple loads its three
+ *   channels and stores three.  16-byte accesses when T % 4 == 0 and x_all and out_x are 16-byte aligned, single floats
+ *   otherwise.  No LDS, no atomics: results are run-to-run identical.
+ *   SELD_EINVAL: whatever seld_gather_rows_aug refuses of the arguments they share (epoch NULL among them, with or
+ *   without matrices; count > B); n_triples outside [1, 5]; 3 * n_triples > C; an entry of triples outside [0, C) or
+ *   given twice, a set bit above the last entry; p_rot outside [0, 1].  SELD_EUNSUPPORTED: a row of 2^31 floats or
+ *   more.  Nothing is launched on refusal.
  * seld_epoch_step_end, one thread, as the last launch of a step:
  *     mean[0] += (loss[0] - mean[0]) / (float)(cursor[0] + 1);   cursor[0] += 1          (fp32: the epoch loop's
  *   running mean of the loss, train.py:559, in the form train.main takes it)
@@ -1085,6 +1115,12 @@ int seld_gather_rows_aug(const float* x_all, int64_t row_x, float* out_x, const 
                          int64_t start, int32_t B, int32_t count, int32_t C, int32_t F, int32_t T, int32_t y_cols,
                          const int32_t* epoch, uint64_t seed, const int32_t* table, int32_t K, float p_swap, int32_t n_fmask,
                          int32_t f_max, int32_t n_tmask, int32_t t_max, float fill, void* stream);
+int seld_gather_rows_rot(const float* x_all, int64_t row_x, float* out_x, const float* y_all, int64_t row_y, float* out_y,
+                         const int64_t* index, int64_t n_index, int64_t n_rows, const int32_t* cursor, int64_t cursor_stride,
+                         int64_t start, int32_t B, int32_t count, int32_t C, int32_t F, int32_t T, int32_t y_cols,
+                         const int32_t* epoch, uint64_t seed, uint64_t triples, int32_t n_triples, float p_rot,
+                         int32_t rot_mirror, int32_t rot_zflip, const float* matrices, int32_t n_fmask, int32_t f_max,
+                         int32_t n_tmask, int32_t t_max, float fill, void* stream);
 int seld_epoch_step_end(const float* loss, float* mean, int32_t* cursor, void* stream);
 
 /* ------------------------------------------------------------------------------------------

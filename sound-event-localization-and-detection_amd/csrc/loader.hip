@@ -5,6 +5,8 @@
 //   seld_gather_rows      out[b, :] = all[index[cursor * stride + start + b], :] for the predictors and the targets
 //   seld_gather_rows_aug  the same gather with the per-sample augmentation applied on the way: a signed channel
 //                         permutation with the matching transform of the DOA labels, frequency and time masks
+//   seld_gather_rows_rot  the same gather with a per-sample rotation of the sound field: a 3x3 matrix mixes the three
+//                         channels of every intensity vector and the DOA labels, then the masks
 //   seld_epoch_step_end   running mean of the loss, cursor += 1 (the last launch of a step)
 //
 // The gather is an HBM-bound copy (config 3: 2 MB per predictor row, 67 MB per batch): a row is spread over many
@@ -288,6 +290,211 @@ __global__ __launch_bounds__(GATHER_THREADS, 8) void gather_rows_aug_kernel(Gath
     }
 }
 
+// ---- gather with a rotation of the sound field -------------------------------------------------------------------------
+// Channels come in two kinds: the members of a triple (cx, cy, cz), the three components of one intensity vector, and
+// the others, which pass.  A predictor row is cut into ITEMS of 16 bytes (4 bytes on the scalar path): a triple item
+// is the same piece of its three channels, loaded, mixed by R and stored as three accesses; a pass item is one piece of
+// one channel.  Triple items are numbered first, in tiles of ROT_TILE_A (two per lane: six 16-byte loads in flight),
+// pass items behind them in tiles of ROT_TILE_B (four per lane, as the other gathers), so whether a tile mixes is
+// uniform over the workgroup.  A sample that draws no rotation has pass items only: it moves as bits.
+constexpr int ROT_MAX_TRIPLES = 5;
+constexpr int ROT_VEC_A = 2, ROT_VEC_B = GATHER_VEC;
+constexpr uint32_t ROT_TILE_A = GATHER_THREADS * ROT_VEC_A, ROT_TILE_B = GATHER_THREADS * ROT_VEC_B;     // items per tile
+
+struct RotParams {
+    int C, F, T;                // predictor row = (C, F, T)
+    int n_sed;                  // target row = (T_out, [n_sed activity | n_sed * 3 location])
+    uint64_t seed;
+    int n_triples, n_pass;
+    uint64_t triples;           // 4 bits per entry: cx, cy, cz of triple 0, of triple 1, ...
+    uint64_t pass;              // 4 bits per entry: the channels outside the triples, ascending
+    float p_rot;
+    int mirror, zflip;
+    int n_fmask, f_max, n_tmask, t_max;
+    float fill;
+    int vec;                    // T % 4 == 0 and both predictor arrays 16-byte aligned
+};
+
+struct RotX {
+    float r[9];                 // row-major
+    MaskPair fm, tm;
+    uint32_t T, FT, P;          // P: items per channel
+    float fill;
+};
+
+template <bool VEC> __device__ __forceinline__ float4 rot_load(const float* __restrict__ p) {
+    if (VEC) return *reinterpret_cast<const float4*>(p);
+    return make_float4(p[0], 0.f, 0.f, 0.f);
+}
+template <bool VEC> __device__ __forceinline__ void rot_store(float* __restrict__ p, float4 v) {
+    if (VEC) *reinterpret_cast<float4*>(p) = v;
+    else p[0] = v.x;
+}
+__device__ __forceinline__ float rot_mix(float r0, float r1, float r2, float x, float y, float z) {
+    return fmaf(r2, z, fmaf(r1, y, r0 * x));
+}
+__device__ __forceinline__ float4 rot_mix4(const float* __restrict__ r, float4 x, float4 y, float4 z) {
+    return make_float4(rot_mix(r[0], r[1], r[2], x.x, y.x, z.x), rot_mix(r[0], r[1], r[2], x.y, y.y, z.y),
+                       rot_mix(r[0], r[1], r[2], x.z, y.z, z.z), rot_mix(r[0], r[1], r[2], x.w, y.w, z.w));
+}
+// the time mask over the (up to) four frames of a piece that starts at frame t0; `whole`: its frequency row is masked
+__device__ __forceinline__ float4 rot_masked(float4 v, bool whole, uint32_t t0, const RotX& a) {
+    return make_float4((whole | a.tm.hit(t0)) ? a.fill : v.x, (whole | a.tm.hit(t0 + 1u)) ? a.fill : v.y,
+                       (whole | a.tm.hit(t0 + 2u)) ? a.fill : v.z, (whole | a.tm.hit(t0 + 3u)) ? a.fill : v.w);
+}
+
+// items [first, first + ROT_TILE_A) of the n triple items: item i is piece i % P of triple i / P
+template <bool VEC> __device__ __forceinline__ void rot_tile_triples(const float* __restrict__ s, float* __restrict__ d, uint32_t first,
+                                                                     uint32_t n, uint64_t triples, const RotX& a) {
+    constexpr uint32_t W = VEC ? 4u : 1u;
+    float4 vx[ROT_VEC_A], vy[ROT_VEC_A], vz[ROT_VEC_A];
+    uint32_t ox[ROT_VEC_A], oy[ROT_VEC_A], oz[ROT_VEC_A], t0[ROT_VEC_A];
+    bool whole[ROT_VEC_A];
+#pragma unroll
+    for (int k = 0; k < ROT_VEC_A; ++k) {
+        const uint32_t i = first + threadIdx.x + (uint32_t)k * GATHER_THREADS, ii = i < n ? i : 0u;    // a lane past the end: item 0
+        const uint32_t u = ii / a.P, e = (ii - u * a.P) * W, f = e / a.T;
+        const uint32_t m = (uint32_t)(triples >> (12u * u));
+        t0[k] = e - f * a.T;
+        whole[k] = a.fm.hit(f);
+        ox[k] = (m & 15u) * a.FT + e, oy[k] = ((m >> 4) & 15u) * a.FT + e, oz[k] = ((m >> 8) & 15u) * a.FT + e;
+        const bool load = i < n && !whole[k];
+        const float4 none = make_float4(0.f, 0.f, 0.f, 0.f);
+        vx[k] = load ? rot_load<VEC>(s + ox[k]) : none;
+        vy[k] = load ? rot_load<VEC>(s + oy[k]) : none;
+        vz[k] = load ? rot_load<VEC>(s + oz[k]) : none;
+    }
+#pragma unroll
+    for (int k = 0; k < ROT_VEC_A; ++k) {
+        if (first + threadIdx.x + (uint32_t)k * GATHER_THREADS >= n) continue;
+        rot_store<VEC>(d + ox[k], rot_masked(rot_mix4(a.r, vx[k], vy[k], vz[k]), whole[k], t0[k], a));
+        rot_store<VEC>(d + oy[k], rot_masked(rot_mix4(a.r + 3, vx[k], vy[k], vz[k]), whole[k], t0[k], a));
+        rot_store<VEC>(d + oz[k], rot_masked(rot_mix4(a.r + 6, vx[k], vy[k], vz[k]), whole[k], t0[k], a));
+    }
+}
+
+// items [first, first + ROT_TILE_B) of the n pass items: item i is piece i % P of the channel in entry i / P of `pass`
+template <bool VEC> __device__ __forceinline__ void rot_tile_pass(const float* __restrict__ s, float* __restrict__ d, uint32_t first,
+                                                                  uint32_t n, uint64_t pass, const RotX& a) {
+    constexpr uint32_t W = VEC ? 4u : 1u;
+    float4 v[ROT_VEC_B];
+    uint32_t o[ROT_VEC_B], t0[ROT_VEC_B];
+    bool whole[ROT_VEC_B];
+#pragma unroll
+    for (int k = 0; k < ROT_VEC_B; ++k) {
+        const uint32_t i = first + threadIdx.x + (uint32_t)k * GATHER_THREADS, ii = i < n ? i : 0u;
+        const uint32_t u = ii / a.P, e = (ii - u * a.P) * W, f = e / a.T;
+        t0[k] = e - f * a.T;
+        whole[k] = a.fm.hit(f);
+        o[k] = ((uint32_t)(pass >> (4u * u)) & 15u) * a.FT + e;
+        v[k] = (i < n && !whole[k]) ? rot_load<VEC>(s + o[k]) : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+#pragma unroll
+    for (int k = 0; k < ROT_VEC_B; ++k) {
+        if (first + threadIdx.x + (uint32_t)k * GATHER_THREADS >= n) continue;
+        rot_store<VEC>(d + o[k], rot_masked(v[k], whole[k], t0[k], a));
+    }
+}
+
+// the predictor row of one sample: tiles [first, ...) in steps of `step`, triple tiles before pass tiles
+template <bool VEC> __device__ __forceinline__ void rot_x_row(const float* __restrict__ s, float* __restrict__ d, uint32_t first,
+                                                              uint32_t step, uint32_t n_a, uint32_t n_b, uint64_t triples,
+                                                              uint64_t pass, const RotX& a) {
+    const uint32_t tiles_a = (n_a + ROT_TILE_A - 1u) / ROT_TILE_A, tiles_b = (n_b + ROT_TILE_B - 1u) / ROT_TILE_B;
+    for (uint32_t tile = first; tile < tiles_a + tiles_b; tile += step) {
+        if (tile < tiles_a) rot_tile_triples<VEC>(s, d, tile * ROT_TILE_A, n_a, triples, a);
+        else rot_tile_pass<VEC>(s, d, (tile - tiles_a) * ROT_TILE_B, n_b, pass, a);
+    }
+}
+
+// grid (gx + gy, count) as gather_rows_kernel.  Everything up to the tile loops is uniform over the workgroup: the draws,
+// the nine entries of R (computed, or loaded from `matrices` before the first store: scalar loads), the mask bounds.
+__global__ __launch_bounds__(GATHER_THREADS, 8) void gather_rows_rot_kernel(GatherSide x, GatherSide y, int gx,
+                                                                         const int64_t* __restrict__ index, long long n_index,
+                                                                         long long n_rows, const int32_t* __restrict__ cursor,
+                                                                         long long stride, long long start,
+                                                                         const int32_t* __restrict__ epoch,
+                                                                         const float* __restrict__ matrices, RotParams a) {
+    const int b = blockIdx.y, tid = threadIdx.x;
+    const bool is_y = (int)blockIdx.x >= gx;
+    const GatherSide sd = is_y ? y : x;
+    const int first = is_y ? (int)blockIdx.x - gx : (int)blockIdx.x;
+    const int step = is_y ? (int)gridDim.x - gx : gx;
+    const long long p = start + b + (cursor ? (long long)cursor[0] * stride : 0);
+    long long r = -1;
+    if (p >= 0 && p < n_index) r = index[p];
+    const bool valid = r >= 0 && r < n_rows;
+    float* __restrict__ dst = sd.out + (long long)b * sd.row;
+    const float* __restrict__ src = valid ? sd.all + r * sd.row : dst;
+    const uint32_t row = (uint32_t)sd.row;                                  // rows are below 2^31 floats
+
+    // the draws of this sample: functions of (seed, epoch, p) alone; an explicit matrix takes their place
+    uint64_t counter = 0;
+    bool rotate = false;
+    RotX ax;
+    ax.r[0] = 1.f, ax.r[1] = 0.f, ax.r[2] = 0.f, ax.r[3] = 0.f, ax.r[4] = 1.f, ax.r[5] = 0.f, ax.r[6] = 0.f, ax.r[7] = 0.f, ax.r[8] = 1.f;
+    if (valid) {
+        counter = ((uint64_t)(uint32_t)epoch[0] << 34) | ((uint64_t)p << 2);
+        if (matrices) {
+            rotate = true;
+            const float* __restrict__ m = matrices + 9ll * b;
+#pragma unroll
+            for (int i = 0; i < 9; ++i) ax.r[i] = m[i];
+        } else if (a.p_rot > 0.f) {
+            const uint4 w = philox4x32_10(counter | 3u, a.seed);
+            rotate = u01(w.y) < a.p_rot;
+            float s, c;
+            sincospif(2.f * u01(w.x), &s, &c);
+            const float my = (a.mirror && (w.z >> 31)) ? -1.f : 1.f, mz = (a.zflip && (w.w >> 31)) ? -1.f : 1.f;
+            ax.r[0] = c, ax.r[1] = -s, ax.r[3] = my * s, ax.r[4] = my * c, ax.r[8] = mz;
+        }
+    }
+
+    if (!valid || (is_y && !rotate)) {          // zero-fill, or targets that no rotation touches: the plain tiles
+        const uint64_t tile_step = (uint64_t)step * (uint64_t)GATHER_TILE;
+        for (uint64_t off = (uint64_t)first * (uint64_t)GATHER_TILE; off < row; off += tile_step) {
+            const uint32_t left = row - (uint32_t)off;
+            gather_tile(src + off, dst + off, (int)(left < GATHER_TILE ? left : GATHER_TILE), valid);
+        }
+        return;
+    }
+
+    if (is_y) {                                 // location (s, a) <- sum_b R[a][b] location (s, b); activity copied
+        const uint32_t n_sed = (uint32_t)a.n_sed, cols = 4u * n_sed;
+        const uint64_t tile_step = (uint64_t)step * (uint64_t)GATHER_TILE;
+        for (uint64_t off = (uint64_t)first * (uint64_t)GATHER_TILE; off < row; off += tile_step) {
+            const uint32_t left = row - (uint32_t)off, len = left < GATHER_TILE ? left : (uint32_t)GATHER_TILE;
+            for (uint32_t i = tid; i < len; i += GATHER_THREADS) {
+                const uint32_t o = (uint32_t)off + i, j = o % cols;
+                float v;
+                if (j < n_sed) {
+                    v = src[o];
+                } else {
+                    const uint32_t axis = (j - n_sed) % 3u, o0 = o - axis;
+                    const float r0 = axis == 0u ? ax.r[0] : axis == 1u ? ax.r[3] : ax.r[6];
+                    const float r1 = axis == 0u ? ax.r[1] : axis == 1u ? ax.r[4] : ax.r[7];
+                    const float r2 = axis == 0u ? ax.r[2] : axis == 1u ? ax.r[5] : ax.r[8];
+                    v = rot_mix(r0, r1, r2, src[o0], src[o0 + 1u], src[o0 + 2u]);
+                }
+                dst[o] = v;
+            }
+        }
+        return;
+    }
+
+    ax.fm = draw_masks(counter | 1u, a.seed, a.n_fmask, a.f_max, a.F);
+    ax.tm = draw_masks(counter | 2u, a.seed, a.n_tmask, a.t_max, a.T);
+    ax.T = (uint32_t)a.T;
+    ax.FT = (uint32_t)a.F * ax.T;
+    ax.P = a.vec ? ax.FT >> 2 : ax.FT;
+    ax.fill = a.fill;
+    const uint32_t n_a = rotate ? (uint32_t)a.n_triples * ax.P : 0u;
+    const uint32_t n_b = (uint32_t)(rotate ? a.n_pass : a.C) * ax.P;
+    const uint64_t pass = rotate ? a.pass : 0xFEDCBA9876543210ull;
+    if (a.vec) rot_x_row<true>(src, dst, (uint32_t)first, (uint32_t)step, n_a, n_b, a.triples, pass, ax);
+    else rot_x_row<false>(src, dst, (uint32_t)first, (uint32_t)step, n_a, n_b, a.triples, pass, ax);
+}
+
 // one thread: the epoch loop's running mean (train.main), `mean += (loss - mean) / (i + 1)` in fp32 with i the cursor,
 // then the cursor
 __global__ void epoch_step_end_kernel(const float* __restrict__ loss, float* __restrict__ mean, int32_t* __restrict__ cursor) {
@@ -321,6 +528,23 @@ extern "C" int seld_gather_rows(const float* x_all, int64_t row_x, float* out_x,
     return check_launch();
 }
 
+// what seld_gather_rows_aug and seld_gather_rows_rot refuse (SELD_EINVAL) of the arguments they share
+static bool aug_gather_refused(const float* x_all, int64_t row_x, const float* out_x, const float* y_all, int64_t row_y,
+                               const float* out_y, const int64_t* index, int64_t n_index, int64_t n_rows, const int32_t* cursor,
+                               int64_t cursor_stride, int32_t B, int32_t count, int32_t C, int32_t F, int32_t T, int32_t y_cols,
+                               const int32_t* epoch, int32_t n_fmask, int32_t f_max, int32_t n_tmask, int32_t t_max) {
+    const bool has_x = x_all || out_x, has_y = y_all || out_y;
+    if (!index || n_index <= 0 || n_index > (1ll << 32) || n_rows <= 0 || B <= 0 || count <= 0 || count > B || count > 65535) return true;
+    if (!has_x && !has_y) return true;
+    if (has_x && (!x_all || !out_x || row_x <= 0)) return true;
+    if (has_y && (!y_all || !out_y || row_y <= 0)) return true;
+    if (cursor && cursor_stride < 0) return true;
+    if (!epoch || C < 1 || C > AUG_MAX_C || F < 1 || T < 1) return true;
+    if (n_fmask < 0 || n_fmask > 2 || n_tmask < 0 || n_tmask > 2 || f_max < 0 || f_max > F || t_max < 0 || t_max > T) return true;
+    if (has_x && (long long)C * F * T != row_x) return true;                        // 16 * 2^31 * 2^31 fits an int64
+    return has_y && (y_cols < 4 || y_cols % 4 || row_y % y_cols);
+}
+
 extern "C" int seld_gather_rows_aug(const float* x_all, int64_t row_x, float* out_x, const float* y_all, int64_t row_y,
                                     float* out_y, const int64_t* index, int64_t n_index, int64_t n_rows, const int32_t* cursor,
                                     int64_t cursor_stride, int64_t start, int32_t B, int32_t count, int32_t C, int32_t F,
@@ -328,18 +552,11 @@ extern "C" int seld_gather_rows_aug(const float* x_all, int64_t row_x, float* ou
                                     int32_t K, float p_swap, int32_t n_fmask, int32_t f_max, int32_t n_tmask, int32_t t_max,
                                     float fill, void* stream) {
     const bool has_x = x_all || out_x, has_y = y_all || out_y;
-    if (!index || n_index <= 0 || n_index > (1ll << 32) || n_rows <= 0 || B <= 0 || count <= 0 || count > B || count > 65535)
+    if (aug_gather_refused(x_all, row_x, out_x, y_all, row_y, out_y, index, n_index, n_rows, cursor, cursor_stride, B, count, C, F, T,
+                           y_cols, epoch, n_fmask, f_max, n_tmask, t_max))
         return SELD_EINVAL;
-    if (!has_x && !has_y) return SELD_EINVAL;
-    if (has_x && (!x_all || !out_x || row_x <= 0)) return SELD_EINVAL;
-    if (has_y && (!y_all || !out_y || row_y <= 0)) return SELD_EINVAL;
-    if (cursor && cursor_stride < 0) return SELD_EINVAL;
-    if (!epoch || K < 0 || K > AUG_MAX_K || (K > 0) != (table != nullptr)) return SELD_EINVAL;
+    if (K < 0 || K > AUG_MAX_K || (K > 0) != (table != nullptr)) return SELD_EINVAL;
     if (!(p_swap >= 0.f && p_swap <= 1.f)) return SELD_EINVAL;                      // a NaN fails both
-    if (C < 1 || C > AUG_MAX_C || F < 1 || T < 1) return SELD_EINVAL;
-    if (n_fmask < 0 || n_fmask > 2 || n_tmask < 0 || n_tmask > 2 || f_max < 0 || f_max > F || t_max < 0 || t_max > T) return SELD_EINVAL;
-    if (has_x && (long long)C * F * T != row_x) return SELD_EINVAL;                 // 16 * 2^31 * 2^31 fits an int64
-    if (has_y && (y_cols < 4 || y_cols % 4 || row_y % y_cols)) return SELD_EINVAL;
     if (row_x >= (1ll << 31) || row_y >= (1ll << 31)) return SELD_EUNSUPPORTED;     // offsets inside a row are 32-bit
     const long long cap = GATHER_MAX_BLOCKS / count > 0 ? GATHER_MAX_BLOCKS / count : 1;
     const long long tx = has_x ? (row_x + GATHER_TILE - 1) / GATHER_TILE : 0, ty = has_y ? (row_y + GATHER_TILE - 1) / GATHER_TILE : 0;
@@ -349,6 +566,48 @@ extern "C" int seld_gather_rows_aug(const float* x_all, int64_t row_x, float* ou
     const AugParams a{C, F, T, has_y ? y_cols / 4 : 0, seed, K, p_swap, n_fmask, f_max, n_tmask, t_max, fill, vec};
     hipLaunchKernelGGL(gather_rows_aug_kernel, dim3(gx + gy, count), dim3(GATHER_THREADS), 0, (hipStream_t)stream, x, y, gx, index,
                        (long long)n_index, (long long)n_rows, cursor, (long long)cursor_stride, (long long)start, epoch, table, a);
+    return check_launch();
+}
+
+extern "C" int seld_gather_rows_rot(const float* x_all, int64_t row_x, float* out_x, const float* y_all, int64_t row_y,
+                                    float* out_y, const int64_t* index, int64_t n_index, int64_t n_rows, const int32_t* cursor,
+                                    int64_t cursor_stride, int64_t start, int32_t B, int32_t count, int32_t C, int32_t F,
+                                    int32_t T, int32_t y_cols, const int32_t* epoch, uint64_t seed, uint64_t triples,
+                                    int32_t n_triples, float p_rot, int32_t rot_mirror, int32_t rot_zflip, const float* matrices,
+                                    int32_t n_fmask, int32_t f_max, int32_t n_tmask, int32_t t_max, float fill, void* stream) {
+    const bool has_x = x_all || out_x, has_y = y_all || out_y;
+    if (aug_gather_refused(x_all, row_x, out_x, y_all, row_y, out_y, index, n_index, n_rows, cursor, cursor_stride, B, count, C, F, T,
+                           y_cols, epoch, n_fmask, f_max, n_tmask, t_max))
+        return SELD_EINVAL;
+    if (n_triples < 1 || n_triples > ROT_MAX_TRIPLES || 3 * n_triples > C) return SELD_EINVAL;
+    if (!(p_rot >= 0.f && p_rot <= 1.f)) return SELD_EINVAL;                        // a NaN fails both
+    if (row_x >= (1ll << 31) || row_y >= (1ll << 31)) return SELD_EUNSUPPORTED;     // offsets inside a row are 32-bit
+    // the triples travel by value, so their content is checked here: the kernel then indexes with them as they are
+    uint32_t used = 0u;
+    for (int i = 0; i < 3 * n_triples; ++i) {
+        const uint32_t c = (uint32_t)(triples >> (4 * i)) & 15u;
+        if (c >= (uint32_t)C || (used >> c & 1u)) return SELD_EINVAL;
+        used |= 1u << c;
+    }
+    if ((triples >> (12 * n_triples)) != 0) return SELD_EINVAL;                     // at most 60 bits are entries
+    uint64_t pass = 0;
+    int n_pass = 0;
+    for (int c = 0; c < C; ++c)
+        if (!(used >> c & 1u)) pass |= (uint64_t)c << (4 * n_pass++);
+    const int vec = has_x && T % 4 == 0 && (((uintptr_t)x_all | (uintptr_t)out_x) & 15) == 0;
+    // the grid of seld_gather_rows_aug over the tiles of this kernel: the larger of a rotated and an unrotated sample's
+    const long long P = has_x ? (vec ? (long long)F * T / 4 : (long long)F * T) : 0;
+    const long long cap = GATHER_MAX_BLOCKS / count > 0 ? GATHER_MAX_BLOCKS / count : 1;
+    const long long t_rot = (n_triples * P + ROT_TILE_A - 1) / ROT_TILE_A + (n_pass * P + ROT_TILE_B - 1) / ROT_TILE_B;
+    const long long t_plain = (C * P + ROT_TILE_B - 1) / ROT_TILE_B;
+    const long long tx = t_rot > t_plain ? t_rot : t_plain;
+    const long long ty = has_y ? (row_y + GATHER_TILE - 1) / GATHER_TILE : 0;
+    const int gx = (int)(tx < cap ? tx : cap), gy = (int)(ty < cap ? ty : cap);
+    const GatherSide x{x_all, out_x, has_x ? (long long)row_x : 0}, y{y_all, out_y, has_y ? (long long)row_y : 0};
+    const RotParams a{C, F, T, has_y ? y_cols / 4 : 0, seed, n_triples, n_pass, triples, pass, p_rot, rot_mirror != 0, rot_zflip != 0,
+                      n_fmask, f_max, n_tmask, t_max, fill, vec};
+    hipLaunchKernelGGL(gather_rows_rot_kernel, dim3(gx + gy, count), dim3(GATHER_THREADS), 0, (hipStream_t)stream, x, y, gx, index,
+                       (long long)n_index, (long long)n_rows, cursor, (long long)cursor_stride, (long long)start, epoch, matrices, a);
     return check_launch();
 }
 

@@ -11,8 +11,9 @@ import torch
 from .. import _lib as L
 from ._core import _req, timed
 
-__all__ = ["gather_rows", "gather_rows_aug", "Augment", "foa_transforms", "epoch_step_end", "epoch_permutation"]
-AUG_MAX_CHANNELS, AUG_MAX_TRANSFORMS = 16, 64
+__all__ = ["gather_rows", "gather_rows_aug", "gather_rows_rot", "Augment", "foa_transforms", "foa_triples", "epoch_step_end",
+           "epoch_permutation"]
+AUG_MAX_CHANNELS, AUG_MAX_TRANSFORMS, ROT_MAX_TRIPLES = 16, 64, 5
 
 
 def _rows(t, name):
@@ -80,7 +81,40 @@ def gather_rows(x_all, y_all, index, out_x, out_y, *, cursor=None, start=0, coun
 _AXES = "XYZ"
 
 
-def foa_transforms(order="WYZX", mics=1, phase=False, elevation=True):
+_LAYOUTS = ("magphase", "quaternion", "iv", "logpower_iv")
+
+
+def _intensity_channels(what, order, mics, layout):
+    """[[channel of the x, y, z intensity component] per microphone] of an intensity layout, after the checks the layouts
+    share: `order` names a group [W, D1, D2, D3] as hip_ops.spatial_features reads it, so W comes first."""
+    if layout not in _LAYOUTS:
+        raise L.SeldHipError(f"{what}: layout is one of {', '.join(_LAYOUTS)}, got {layout!r}")
+    order = str(order).upper()
+    if sorted(order) != sorted("W" + _AXES):
+        raise L.SeldHipError(f"{what}: order must name W, X, Y and Z once each, got {order!r}")
+    if mics not in (1, 2):
+        raise L.SeldHipError(f"{what}: 1 or 2 microphones, got {mics}")
+    if order[0] != "W":
+        raise L.SeldHipError(f"{what}: the {layout} layout is made of groups [W, D1, D2, D3]: order starts with W, got {order!r}")
+    comp = [order.index(ch) - 1 for ch in _AXES]            # which of I1, I2, I3 is the component along axis a
+    if layout == "quaternion":
+        return [[4 * g + 1 + comp[a] for a in range(3)] for g in range(mics)]
+    base = 4 * mics if layout == "logpower_iv" else 0
+    return [[base + 3 * g + comp[a] for a in range(3)] for g in range(mics)]
+
+
+def foa_triples(order="WYZX", mics=1, layout="quaternion"):
+    """The channel triples (cx, cy, cz) of `Augment(rot_triples=...)` for the layouts in which every directional channel is
+    an intensity component: 'quaternion' (C = 4 * mics, per microphone [log-power W, I1, I2, I3]) and 'iv' (C = 3 * mics).
+    One triple per microphone; `order` says which of X, Y, Z the components are.  'magphase' and 'logpower_iv' are
+    refused: a magnitude, a phase or the log-power of a directional channel is not covariant under a general rotation."""
+    if layout in ("magphase", "logpower_iv"):
+        raise L.SeldHipError(f"foa_triples: a rotation is not defined on the {layout} layout (it holds directional channels "
+                             "that are no intensity components)")
+    return [tuple(t) for t in _intensity_channels("foa_triples", order, mics, layout)]
+
+
+def foa_transforms(order="WYZX", mics=1, phase=False, elevation=True, layout="magphase"):
     """The preset transform table of first-order Ambisonics predictors for `Augment`, on the host: int32 (K, 2 * C + 6),
     a row = src[C], flip[C], axis[3], sign[3] (include/seld_hip.h, seld_gather_rows_aug).
 
@@ -95,7 +129,33 @@ def foa_transforms(order="WYZX", mics=1, phase=False, elevation=True):
     Magnitude channels get flip 0 (a magnitude has no sign).  Phase channels get flip 2 where the sign is -1: the
     phase turned by pi.  Flip 2 is valid on RAW phase only, values in (-pi, pi]; on standardised phase it is wrong,
     and train.main refuses that combination.  With two spaced microphones one rotation for both blocks is an
-    approximation (the arrays do not share a centre): the caller chooses it by passing mics=2."""
+    approximation (the arrays do not share a centre): the caller chooses it by passing mics=2.
+
+    `layout` other than 'magphase': the same rows, in the same order, for the channel layouts hip_ops.spatial_features
+    writes for `mics` groups [W, D1, D2, D3] (`order` starts with W; `phase` is refused):
+      'quaternion'   C = 4 * mics, per microphone [log-power W, I1, I2, I3]
+      'iv'           C = 3 * mics, per microphone [I1, I2, I3]
+      'logpower_iv'  C = 7 * mics, the 4 * mics log-power planes, then the intensity planes group by group
+    An intensity component is a signed quantity: its channel gets flip 1 (negate) where the sign is -1.  Log-power
+    planes are permuted like magnitudes, flip 0."""
+    if layout != "magphase":
+        iv = _intensity_channels("foa_transforms", order, mics, layout)
+        if phase:
+            raise L.SeldHipError(f"foa_transforms: the {layout!r} layout has no phase channels")
+        pos = [str(order).upper().index(ch) for ch in _AXES]
+        C = {"quaternion": 4, "iv": 3, "logpower_iv": 7}[layout] * mics
+        rows = []
+        for swap, sz, sy, sx in itertools.product((False, True), (1, -1) if elevation else (1,), (1, -1), (1, -1)):
+            axis, sign = ([1, 0, 2] if swap else [0, 1, 2]), [sx, sy, sz]
+            src, flip = list(range(C)), [0] * C
+            for g in range(mics):
+                for a in range(3):
+                    src[iv[g][a]] = iv[g][axis[a]]
+                    flip[iv[g][a]] = 1 if sign[a] < 0 else 0
+                    if layout == "logpower_iv":
+                        src[4 * g + pos[a]] = 4 * g + pos[axis[a]]
+            rows.append(src + flip + axis + sign)
+        return np.asarray(rows, dtype=np.int32)
     order = str(order).upper()
     if sorted(order) != sorted("W" + _AXES):
         raise L.SeldHipError(f"foa_transforms: order must name W, X, Y and Z once each, got {order!r}")
@@ -140,6 +200,18 @@ def _check_table(table, channels):
     return np.ascontiguousarray(t, dtype=np.int32)
 
 
+def _check_triples(triples):
+    """((cx, cy, cz), ...) of 1..5 channel triples; raises SeldHipError unless they are distinct channels in [0, 16)."""
+    t = np.asarray(triples.cpu() if torch.is_tensor(triples) else triples)
+    if t.ndim != 2 or t.shape[1] != 3 or not 1 <= t.shape[0] <= ROT_MAX_TRIPLES or not np.issubdtype(t.dtype, np.integer):
+        raise L.SeldHipError(f"Augment: rot_triples must be 1..{ROT_MAX_TRIPLES} integer triples (cx, cy, cz), got {t.dtype} {t.shape}")
+    if t.min() < 0 or t.max() >= AUG_MAX_CHANNELS:
+        raise L.SeldHipError(f"Augment: a rot_triples channel outside [0, {AUG_MAX_CHANNELS})")
+    if len(set(t.ravel().tolist())) != t.size:
+        raise L.SeldHipError("Augment: a channel appears twice in rot_triples")
+    return tuple(tuple(int(c) for c in row) for row in t)
+
+
 @dataclasses.dataclass(frozen=True)
 class Augment:
     """What seld_gather_rows_aug applies to every sample (include/seld_hip.h has the draws).
@@ -147,7 +219,14 @@ class Augment:
     table: a transform table (K, 2 * C + 6), e.g. `foa_transforms(...)`, or None for no channel transform; it is
     validated here and held as an int32 tensor on `device`.  p_swap: probability that a sample takes one of the K
     transforms (uniformly).  freq_masks / time_masks: 0, 1 or 2 masks per sample of a width drawn uniformly from
-    [0, freq_width] / [0, time_width], filled with `fill`.  A bad table or range raises SeldHipError."""
+    [0, freq_width] / [0, time_width], filled with `fill`.  A bad table or range raises SeldHipError.
+
+    What seld_gather_rows_rot applies (hip_ops.gather_rows_rot): p_rot, the probability that a sample's sound field is
+    rotated about the vertical axis by a uniform angle, mirrored in y with probability 1/2 if rot_mirror and in z with
+    probability 1/2 if rot_zflip; rot_triples, 1..5 channel triples (cx, cy, cz) of intensity vectors, e.g.
+    `foa_triples(...)`, held as a tuple of tuples.  p_rot > 0 needs triples and excludes p_swap > 0 (the rotations with
+    mirror and z-flip contain the signed permutations: one channel transform per sample).  Everything is checked before
+    the table goes to the device."""
     table: object = None
     p_swap: float = 0.0
     freq_masks: int = 0
@@ -156,12 +235,13 @@ class Augment:
     time_width: int = 0
     fill: float = 0.0
     device: object = "cuda"
+    p_rot: float = 0.0
+    rot_triples: object = None
+    rot_mirror: bool = True
+    rot_zflip: bool = True
 
     def __post_init__(self):
-        table = None
-        if self.table is not None:
-            table = torch.from_numpy(_check_table(self.table, None)).to(self.device)
-        object.__setattr__(self, "table", table)
+        host = None if self.table is None else _check_table(self.table, None)
         if not 0.0 <= float(self.p_swap) <= 1.0:
             raise L.SeldHipError(f"Augment: p_swap {self.p_swap} is no probability")
         for name in ("freq_masks", "time_masks"):
@@ -169,6 +249,26 @@ class Augment:
                 raise L.SeldHipError(f"Augment: {name} must be 0, 1 or 2, got {getattr(self, name)}")
         if int(self.freq_width) < 0 or int(self.time_width) < 0:
             raise L.SeldHipError("Augment: a negative mask width")
+        if not 0.0 <= float(self.p_rot) <= 1.0:
+            raise L.SeldHipError(f"Augment: p_rot {self.p_rot} is no probability")
+        if self.rot_triples is not None:
+            object.__setattr__(self, "rot_triples", _check_triples(self.rot_triples))
+        if float(self.p_rot) > 0.0 and self.rot_triples is None:
+            raise L.SeldHipError("Augment: p_rot > 0 needs rot_triples, the channels of the intensity vectors")
+        if float(self.p_rot) > 0.0 and float(self.p_swap) > 0.0:
+            raise L.SeldHipError("Augment: p_rot > 0 together with p_swap > 0 (one channel transform per sample)")
+        object.__setattr__(self, "table", None if host is None else torch.from_numpy(host).to(self.device))
+
+    @property
+    def rot_channels(self):
+        """The least number of channels the triples need, None without triples."""
+        return None if self.rot_triples is None else 1 + max(max(t) for t in self.rot_triples)
+
+    @property
+    def rot_packed(self):
+        """The triples as seld_gather_rows_rot takes them: 4 bits per entry."""
+        flat = [c for t in self.rot_triples for c in t]
+        return sum(c << (4 * i) for i, c in enumerate(flat))
 
     @property
     def channels(self):
@@ -215,6 +315,54 @@ def gather_rows_aug(x_all, y_all, index, out_x, out_y, *, epoch, seed, augment, 
                 L.ptr(table), augment.transforms, float(augment.p_swap), int(augment.freq_masks), int(augment.freq_width),
                 int(augment.time_masks), int(augment.time_width), float(augment.fill), L.current_stream()),
                 "seld_gather_rows_aug")
+    return out_x, out_y
+
+
+def gather_rows_rot(x_all, y_all, index, out_x, out_y, *, epoch, seed, augment, matrices=None, cursor=None, start=0, count=None,
+                    stride=None):
+    """`gather_rows` with a rotation of the sound field applied to every sample on the way, then the masks of `augment`, in
+    ONE launch (seld_gather_rows_rot; include/seld_hip.h has the draws).  The channels of `augment.rot_triples` are the
+    x, y, z components of intensity vectors: a rotated sample gets x'[c_a] = sum_j R[a][j] x[c_j] per triple and
+    location'(s, a) = sum_j R[a][j] location(s, j); every other channel and the activity are copied.  R is drawn per
+    sample with probability augment.p_rot from (seed, epoch, position), or, with `matrices` (fp32 device tensor (count, 9)
+    or (count, 3, 3), row-major), sample b takes matrices[b] as it is.  augment.table and p_swap are not used.
+    Geometry, epoch, cursor, start, count, stride and the zero rows of invalid positions as in `gather_rows_aug`."""
+    what = "gather_rows_rot"
+    if not isinstance(augment, Augment):
+        raise L.SeldHipError(f"{what}: augment must be an Augment, got {type(augment).__name__}")
+    if augment.rot_triples is None:
+        raise L.SeldHipError(f"{what}: the Augment has no rot_triples")
+    x_all, row_x, y_all, row_y, out_x, out_y, n_rows, dev, B, count, stride = _gather_args(
+        what, x_all, y_all, index, out_x, out_y, cursor, count, stride)
+    if _scalar(epoch, f"{what}: epoch", torch.int32).device != dev:
+        raise L.SeldHipError(f"{what}: epoch on another device")
+    C, F, T = augment.rot_channels, 1, 1                # targets alone: as many channels as the triples name
+    if x_all is not None:
+        if x_all.dim() != 4:
+            raise L.SeldHipError(f"{what}: predictors must be (n, C, F, T), got {tuple(x_all.shape)}")
+        C, F, T = x_all.shape[1:]
+        if augment.rot_channels > C:
+            raise L.SeldHipError(f"{what}: rot_triples name channel {augment.rot_channels - 1}, the predictors have {C}")
+    y_cols = 4
+    if y_all is not None:
+        if y_all.dim() < 2:
+            raise L.SeldHipError(f"{what}: targets must be (n, ..., 4 * n_sed), got {tuple(y_all.shape)}")
+        y_cols = y_all.shape[-1]
+    if matrices is not None:
+        if (not torch.is_tensor(matrices) or _req(matrices, f"{what}: matrices") is not matrices or matrices.device != dev
+                or matrices.dim() < 2 or matrices.shape[0] < count
+                or tuple(matrices.shape[1:]) not in ((9,), (3, 3))):
+            raise L.SeldHipError(f"{what}: matrices must be a contiguous fp32 tensor ({count}, 9) or ({count}, 3, 3) on {dev}, "
+                                 f"got {getattr(matrices, 'shape', type(matrices).__name__)}")
+    with torch.cuda.device(dev):
+        with timed("gather_rows_rot_kernel", lambda: (0.0, float(8 * count * (row_x + row_y)))):
+            L.check(L.lib().seld_gather_rows_rot(
+                L.ptr(x_all), row_x, L.ptr(out_x), L.ptr(y_all), row_y, L.ptr(out_y), L.ptr(index), index.numel(), n_rows,
+                L.ptr(cursor), stride, int(start), B, count, C, F, T, y_cols, L.ptr(epoch), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                augment.rot_packed, len(augment.rot_triples), float(augment.p_rot), int(bool(augment.rot_mirror)),
+                int(bool(augment.rot_zflip)), L.ptr(matrices), int(augment.freq_masks), int(augment.freq_width),
+                int(augment.time_masks), int(augment.time_width), float(augment.fill), L.current_stream()),
+                "seld_gather_rows_rot")
     return out_x, out_y
 
 

@@ -436,6 +436,11 @@ _EVAL = ('use_cuda', 'early_stopping', 'fixed_seed', 'pool_size', 'cnn_filters',
 # (hip_ops.gather_rows_aug) -- augment_swap: probability of a signed FOA channel permutation with its DOA labels
 # (hip_ops.foa_transforms for --n_mics / --phase); augment_freq_masks / augment_time_masks: 0..2 masks per sample of a
 # width up to augment_freq_width / augment_time_width bins; augment_seed: the key of the draws;
+# feature_layout (magphase by default): the channel layout of the predictors for augment_swap and test_tta -- quaternion, iv
+# or logpower_iv for the intensity features of hip_ops.spatial_features, whose components are negated, not turned by pi;
+# augment_rotate (needs a feature_layout of quaternion or iv; not with augment_swap): probability that a sample's sound
+# field is rotated about the vertical axis by a random angle, with random mirrors in y and z, and its DOA labels with it
+# (hip_ops.gather_rows_rot, the same single launch);
 # pit_loss (off by default): the loss takes, per (frame, class), the cheapest pairing of the class_overlaps prediction
 # slots with the target slots (hip_ops.seld_loss_pit) instead of comparing slot o with slot o -- training steps (eager,
 # data parallel, recorded) and the validation loss alike;
@@ -451,7 +456,8 @@ _EVAL = ('use_cuda', 'early_stopping', 'fixed_seed', 'pool_size', 'cnn_filters',
 _EXTRA = [('synthetic', int, 0), ('max_steps', int, 0), ('epochs', int, 0), ('resident_loader', str, 'False'),
           ('graph_step', str, 'False'), ('augment_swap', float, 0.), ('augment_freq_masks', int, 0),
           ('augment_freq_width', int, 0), ('augment_time_masks', int, 0), ('augment_time_width', int, 0),
-          ('augment_seed', int, 0), ('pit_loss', str, 'False'), ('test_hop', int, 0), ('test_tta', int, 0),
+          ('augment_seed', int, 0), ('feature_layout', str, 'magphase'), ('augment_rotate', float, 0.),
+          ('pit_loss', str, 'False'), ('test_hop', int, 0), ('test_tta', int, 0),
           ('post_median', int, 1), ('post_on', float, 0.5), ('post_off', float, 0.5), ('post_min_frames', int, 1),
           ('post_max_gap', int, 0), ('post_doa', str, 'frame'), ('se_reduction', int, 0), ('se_mode', str, 'both')]
 
@@ -706,8 +712,8 @@ class ResidentLoader:
     the order a run with the DataLoader visits them.  Data parallel: `batch_size` is the global batch, this rank
     gathers its `rank_rows` of every batch; rank 0's order is broadcast, so ranks agree whatever their RNG state.
 
-    `augment` (a hip_ops.Augment; default None: exactly the launches above): every fetch is hip_ops.gather_rows_aug, still
-    one launch.  What a sample draws depends on (`seed`, the device int32 `epoch`, its position in the epoch's order):
+    `augment` (a hip_ops.Augment; default None: exactly the launches above): every fetch is hip_ops.gather_rows_aug, or
+    hip_ops.gather_rows_rot when its p_rot > 0, still one launch.  What a sample draws depends on (`seed`, the device int32 `epoch`, its position in the epoch's order):
     ranks need no agreement, and a recorded fetch draws anew in every epoch.  `epoch` is -1 until the first
     `begin_epoch`, which adds 1 to it."""
 
@@ -751,6 +757,9 @@ class ResidentLoader:
             where = dict(start=rank_rows(self.plan[batch][0], count, self.rank)[0], count=count)
         if self.augment is None:
             H.gather_rows(self.x_all, self.y_all, self.index, self.x, self.target, **where)
+        elif self.augment.p_rot > 0:
+            H.gather_rows_rot(self.x_all, self.y_all, self.index, self.x, self.target, epoch=self.epoch, seed=self.seed,
+                              augment=self.augment, **where)
         else:
             H.gather_rows_aug(self.x_all, self.y_all, self.index, self.x, self.target, epoch=self.epoch, seed=self.seed,
                               augment=self.augment, **where)
@@ -831,8 +840,23 @@ def normalize_dataset(args, *predictors):
     return desc
 
 
+FEATURE_LAYOUTS = ('magphase', 'quaternion', 'iv', 'logpower_iv')
+
+
+def feature_layout(args, flag):
+    """--feature_layout, checked for the flag that needs it (args without it: magphase).  The intensity layouts hold no
+    phase channels and come from 1 or 2 groups of [W, D1, D2, D3]."""
+    layout = getattr(args, 'feature_layout', 'magphase')
+    if layout not in FEATURE_LAYOUTS:
+        raise ValueError(f"--feature_layout is one of {', '.join(FEATURE_LAYOUTS)}, got {layout!r}")
+    if layout != 'magphase' and args.phase:
+        raise ValueError(f"{flag} with --feature_layout={layout}: that layout has no phase channels, not with --phase")
+    return layout
+
+
 def augment_requested(args):
-    return args.augment_swap > 0 or args.augment_freq_masks > 0 or args.augment_time_masks > 0
+    return (args.augment_swap > 0 or args.augment_freq_masks > 0 or args.augment_time_masks > 0
+            or getattr(args, 'augment_rotate', 0.) > 0)
 
 
 def augment_from_args(args, device):
@@ -842,17 +866,29 @@ def augment_from_args(args, device):
         return None
     if not args.resident_loader:
         raise ValueError("--augment_* flags need --resident_loader (the augmentation is part of the device gather)")
-    swap = args.augment_swap > 0
+    swap, rotate = args.augment_swap > 0, getattr(args, 'augment_rotate', 0.)
+    if not 0. <= rotate <= 1.:
+        raise ValueError(f"--augment_rotate is a probability, got {rotate}")
+    if rotate > 0 and swap:
+        raise ValueError("--augment_rotate with --augment_swap: the rotations with their mirrors contain the signed "
+                         "permutations, one channel transform per sample")
+    layout = feature_layout(args, "--augment_swap" if swap else "--augment_rotate") if swap or rotate > 0 else 'magphase'
+    if rotate > 0 and layout not in ('quaternion', 'iv'):
+        raise ValueError(f"--augment_rotate needs --feature_layout=quaternion or iv (every directional channel an intensity "
+                         f"component), got {layout}")
+    if rotate > 0 and args.n_mics not in (1, 2):
+        raise ValueError(f"--augment_rotate: the FOA layouts are for 1 or 2 microphones, got --n_mics {args.n_mics}")
     mode = str(args.dataset_normalization)
     if swap and args.phase and mode not in _NORM_OFF and mode not in _NORM_UNIT:
         raise ValueError("--augment_swap with --phase needs raw phase (a sign flip turns the phase by pi): not with a "
                          "standardising --dataset_normalization")
     if swap and args.n_mics not in (1, 2):
         raise ValueError(f"--augment_swap: the FOA transform preset is for 1 or 2 microphones, got --n_mics {args.n_mics}")
-    table = H.foa_transforms(mics=args.n_mics, phase=bool(args.phase)) if swap else None
+    table = H.foa_transforms(mics=args.n_mics, phase=bool(args.phase), layout=layout) if swap else None
+    triples = H.foa_triples(mics=args.n_mics, layout=layout) if rotate > 0 else None
     return H.Augment(table=table, p_swap=args.augment_swap if swap else 0.0, freq_masks=args.augment_freq_masks,
                      freq_width=args.augment_freq_width, time_masks=args.augment_time_masks,
-                     time_width=args.augment_time_width, device=device)
+                     time_width=args.augment_time_width, device=device, p_rot=rotate, rot_triples=triples)
 
 
 def test_results_from_counters(counts, total_de, epoch=0):
@@ -956,13 +992,14 @@ def ensemble_from_args(args):
         raise ValueError(f"--test_tta is 0, 8 (the z axis fixed) or 16 transforms, got {args.test_tta}")
     table = None
     if args.test_tta:
+        layout = feature_layout(args, "--test_tta")
         mode = str(args.dataset_normalization)
         if args.phase and mode not in _NORM_OFF and mode not in _NORM_UNIT:
             raise ValueError("--test_tta with --phase needs raw phase (a sign flip turns the phase by pi): not with a "
                              "standardising --dataset_normalization")
         if args.n_mics not in (1, 2):
             raise ValueError(f"--test_tta: the FOA transform preset is for 1 or 2 microphones, got --n_mics {args.n_mics}")
-        table = H.foa_transforms(mics=args.n_mics, phase=bool(args.phase), elevation=args.test_tta == 16)
+        table = H.foa_transforms(mics=args.n_mics, phase=bool(args.phase), elevation=args.test_tta == 16, layout=layout)
     return dict(hop=args.test_hop or args.time_dim, table=table)
 
 
