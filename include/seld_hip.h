@@ -1101,6 +1101,37 @@ int seld_segment(const void* src, int32_t dtype, int32_t layout, int64_t rows, i
  *   without matrices; count > B); n_triples outside [1, 5]; 3 * n_triples > C; an entry of triples outside [0, C) or
  *   given twice, a set bit above the last entry; p_rot outside [0, 1].  SELD_EUNSUPPORTED: a row of 2^31 floats or
  *   more.  Nothing is launched on refusal.
+ * seld_gather_rows_polar is seld_gather_rows_rot for predictors stored as [magnitude channels | phase channels]: magnitude
+ * and phase of one STFT bin are one complex number and the STFT is linear, so a rotation R of the FOA waveform turns the
+ * complex 3-vector Z = (X, Y, Z) of every (f, t) into R Z; W stays.  Addressing, cursor / start / count / stride,
+ * zero-fill of invalid positions, untouched rows [count, B), geometry (C, F, T, y_cols), epoch, seed, the counter, group
+ * 3 (the rotation draw, word for word), groups 1 and 2 (the masks), the `matrices` override and the label rotation (the
+ * same fma order) are those of seld_gather_rows_rot; one launch, recordable.
+ *   groups: n_groups in [1, 2] channel groups (mx, my, mz, px, py, pz), magnitude and phase of the x, y and z channel
+ *   of one microphone, passed BY VALUE, 4 bits per entry: entry 6 * k + e (e = 0..5 in the order above) in bits
+ *   [4 * (6k + e), 4 * (6k + e) + 4).  The entries are distinct and inside [0, C); bits above the last entry are 0.
+ *   Every other channel, magnitude and phase of W among them, is copied as bits.
+ *   stats (nullable): 4 fp32 on the device, (mean_m, sd_m, mean_p, sd_p): the predictors hold (magnitude - mean_m) / sd_m
+ *   and (phase - mean_p) / sd_p (seld_group_standardize over the two halves).  The kernel reads them; NULL: raw
+ *   magnitude and phase.  Their CONTENT is the caller's business (finite, sd > 0: hip_ops.gather_rows_polar checks it
+ *   once per tensor), like the content of a transform table.
+ *   A rotated sample, per group and (f, t), in fp32 (j = x, y, z; a = 0, 1, 2):
+ *       m_j  = fma(x[m_j], sd_m, mean_m)         phi_j = fma(x[p_j], sd_p, mean_p)
+ *       (s_j, c_j) = sincosf(phi_j);   re_j = m_j * c_j;   im_j = m_j * s_j
+ *       re'_a = fma(R[a][2], re_z, fma(R[a][1], re_y, R[a][0] * re_x))           im'_a alike
+ *       m'_a = sqrtf(fma(im'_a, im'_a, re'_a * re'_a))       phi'_a = atan2f(im'_a, re'_a)
+ *       x'[m_a] = __fdiv_rn(m'_a - mean_m, sd_m)             x'[p_a] = __fdiv_rn(phi'_a - mean_p, sd_p)
+ *     With stats NULL the two affine steps on either side are SKIPPED (not computed with 0 and 1): x'[m_a] = m'_a >= 0 and
+ *     x'[p_a] = phi'_a, which lies in [-PI_F, PI_F]; atan2f(0, 0) = 0 as numpy's angle.  Labels as seld_gather_rows_rot.
+ *     A sample that draws no rotation, and every channel outside the groups, moves as bits.
+ *   g = 1, g = 2: the masks of seld_gather_rows_aug, after the rotation, over every channel, filled with `fill`.
+ *   Every predictor byte is read once and written once: a lane that owns a 16-byte piece of a group loads its six
+ *   channels and stores six; group tiles are numbered before the tiles of the other channels.  16-byte accesses when
+ *   T % 4 == 0 and x_all and out_x are 16-byte aligned, single floats otherwise.  No LDS, no atomics: results are
+ *   run-to-run identical.
+ *   SELD_EINVAL: whatever seld_gather_rows_rot refuses of the arguments they share; n_groups outside [1, 2];
+ *   6 * n_groups > C; an entry of groups outside [0, C) or given twice, a set bit above the last entry.
+ *   SELD_EUNSUPPORTED: a row of 2^31 floats or more.  Nothing is launched on refusal.
  * seld_epoch_step_end, one thread, as the last launch of a step:
  *     mean[0] += (loss[0] - mean[0]) / (float)(cursor[0] + 1);   cursor[0] += 1          (fp32: the epoch loop's
  *   running mean of the loss, train.py:559, in the form train.main takes it)
@@ -1121,6 +1152,12 @@ int seld_gather_rows_rot(const float* x_all, int64_t row_x, float* out_x, const 
                          const int32_t* epoch, uint64_t seed, uint64_t triples, int32_t n_triples, float p_rot,
                          int32_t rot_mirror, int32_t rot_zflip, const float* matrices, int32_t n_fmask, int32_t f_max,
                          int32_t n_tmask, int32_t t_max, float fill, void* stream);
+int seld_gather_rows_polar(const float* x_all, int64_t row_x, float* out_x, const float* y_all, int64_t row_y,
+                           float* out_y, const int64_t* index, int64_t n_index, int64_t n_rows, const int32_t* cursor,
+                           int64_t cursor_stride, int64_t start, int32_t B, int32_t count, int32_t C, int32_t F, int32_t T,
+                           int32_t y_cols, const int32_t* epoch, uint64_t seed, uint64_t groups, int32_t n_groups,
+                           const float* stats, float p_rot, int32_t rot_mirror, int32_t rot_zflip, const float* matrices,
+                           int32_t n_fmask, int32_t f_max, int32_t n_tmask, int32_t t_max, float fill, void* stream);
 int seld_epoch_step_end(const float* loss, float* mean, int32_t* cursor, void* stream);
 
 /* ------------------------------------------------------------------------------------------

@@ -7,6 +7,8 @@
 //                         permutation with the matching transform of the DOA labels, frequency and time masks
 //   seld_gather_rows_rot  the same gather with a per-sample rotation of the sound field: a 3x3 matrix mixes the three
 //                         channels of every intensity vector and the DOA labels, then the masks
+//   seld_gather_rows_polar  the rotating gather for magnitude / phase predictors: R mixes the complex value m e^(i phi) of
+//                         the three directional channels of every group (polar to Cartesian, mix, back), then the masks
 //   seld_epoch_step_end   running mean of the loss, cursor += 1 (the last launch of a step)
 //
 // The gather is an HBM-bound copy (config 3: 2 MB per predictor row, 67 MB per batch): a row is spread over many
@@ -407,6 +409,60 @@ template <bool VEC> __device__ __forceinline__ void rot_x_row(const float* __res
     }
 }
 
+// what a sample draws of group 3, or its explicit matrix: R (row-major) and whether it applies.  Uniform over the
+// workgroup; the loads of `matrices` precede the first store of the kernel (scalar loads).
+__device__ __forceinline__ bool rot_draw(bool valid, long long p, int b, const int32_t* __restrict__ epoch,
+                                         const float* __restrict__ matrices, uint64_t seed, float p_rot, int mirror, int zflip,
+                                         uint64_t& counter, RotX& ax) {
+    float* r = ax.r;
+    bool rotate = false;
+    r[0] = 1.f, r[1] = 0.f, r[2] = 0.f, r[3] = 0.f, r[4] = 1.f, r[5] = 0.f, r[6] = 0.f, r[7] = 0.f, r[8] = 1.f;
+    if (valid) {
+        counter = ((uint64_t)(uint32_t)epoch[0] << 34) | ((uint64_t)p << 2);
+        if (matrices) {
+            rotate = true;
+            const float* __restrict__ m = matrices + 9ll * b;
+#pragma unroll
+            for (int i = 0; i < 9; ++i) r[i] = m[i];
+        } else if (p_rot > 0.f) {
+            const uint4 w = philox4x32_10(counter | 3u, seed);
+            rotate = u01(w.y) < p_rot;
+            float s, c;
+            sincospif(2.f * u01(w.x), &s, &c);
+            const float my = (mirror && (w.z >> 31)) ? -1.f : 1.f, mz = (zflip && (w.w >> 31)) ? -1.f : 1.f;
+            r[0] = c, r[1] = -s, r[3] = my * s, r[4] = my * c, r[8] = mz;
+        }
+    }
+    return rotate;
+}
+
+// the target row of a rotated sample: location (s, a) <- sum_b R[a][b] location (s, b); activity copied
+__device__ __forceinline__ void rot_y_row(const float* __restrict__ src, float* __restrict__ dst, uint32_t row, uint32_t first,
+                                          uint32_t step, uint32_t n_sed, const RotX& ax) {
+    // the nine entries by name: selects between values, not between addresses (an address select keeps R in memory)
+    const float r00 = ax.r[0], r01 = ax.r[1], r02 = ax.r[2], r10 = ax.r[3], r11 = ax.r[4], r12 = ax.r[5], r20 = ax.r[6], r21 = ax.r[7],
+                r22 = ax.r[8];
+    const uint32_t cols = 4u * n_sed;
+    const uint64_t tile_step = (uint64_t)step * (uint64_t)GATHER_TILE;
+    for (uint64_t off = (uint64_t)first * (uint64_t)GATHER_TILE; off < row; off += tile_step) {
+        const uint32_t left = row - (uint32_t)off, len = left < GATHER_TILE ? left : (uint32_t)GATHER_TILE;
+        for (uint32_t i = threadIdx.x; i < len; i += GATHER_THREADS) {
+            const uint32_t o = (uint32_t)off + i, j = o % cols;
+            float v;
+            if (j < n_sed) {
+                v = src[o];
+            } else {
+                const uint32_t axis = (j - n_sed) % 3u, o0 = o - axis;
+                const float r0 = axis == 0u ? r00 : axis == 1u ? r10 : r20;
+                const float r1 = axis == 0u ? r01 : axis == 1u ? r11 : r21;
+                const float r2 = axis == 0u ? r02 : axis == 1u ? r12 : r22;
+                v = rot_mix(r0, r1, r2, src[o0], src[o0 + 1u], src[o0 + 2u]);
+            }
+            dst[o] = v;
+        }
+    }
+}
+
 // grid (gx + gy, count) as gather_rows_kernel.  Everything up to the tile loops is uniform over the workgroup: the draws,
 // the nine entries of R (computed, or loaded from `matrices` before the first store: scalar loads), the mask bounds.
 __global__ __launch_bounds__(GATHER_THREADS, 8) void gather_rows_rot_kernel(GatherSide x, GatherSide y, int gx,
@@ -415,7 +471,7 @@ __global__ __launch_bounds__(GATHER_THREADS, 8) void gather_rows_rot_kernel(Gath
                                                                          long long stride, long long start,
                                                                          const int32_t* __restrict__ epoch,
                                                                          const float* __restrict__ matrices, RotParams a) {
-    const int b = blockIdx.y, tid = threadIdx.x;
+    const int b = blockIdx.y;
     const bool is_y = (int)blockIdx.x >= gx;
     const GatherSide sd = is_y ? y : x;
     const int first = is_y ? (int)blockIdx.x - gx : (int)blockIdx.x;
@@ -430,25 +486,8 @@ __global__ __launch_bounds__(GATHER_THREADS, 8) void gather_rows_rot_kernel(Gath
 
     // the draws of this sample: functions of (seed, epoch, p) alone; an explicit matrix takes their place
     uint64_t counter = 0;
-    bool rotate = false;
     RotX ax;
-    ax.r[0] = 1.f, ax.r[1] = 0.f, ax.r[2] = 0.f, ax.r[3] = 0.f, ax.r[4] = 1.f, ax.r[5] = 0.f, ax.r[6] = 0.f, ax.r[7] = 0.f, ax.r[8] = 1.f;
-    if (valid) {
-        counter = ((uint64_t)(uint32_t)epoch[0] << 34) | ((uint64_t)p << 2);
-        if (matrices) {
-            rotate = true;
-            const float* __restrict__ m = matrices + 9ll * b;
-#pragma unroll
-            for (int i = 0; i < 9; ++i) ax.r[i] = m[i];
-        } else if (a.p_rot > 0.f) {
-            const uint4 w = philox4x32_10(counter | 3u, a.seed);
-            rotate = u01(w.y) < a.p_rot;
-            float s, c;
-            sincospif(2.f * u01(w.x), &s, &c);
-            const float my = (a.mirror && (w.z >> 31)) ? -1.f : 1.f, mz = (a.zflip && (w.w >> 31)) ? -1.f : 1.f;
-            ax.r[0] = c, ax.r[1] = -s, ax.r[3] = my * s, ax.r[4] = my * c, ax.r[8] = mz;
-        }
-    }
+    const bool rotate = rot_draw(valid, p, b, epoch, matrices, a.seed, a.p_rot, a.mirror, a.zflip, counter, ax);
 
     if (!valid || (is_y && !rotate)) {          // zero-fill, or targets that no rotation touches: the plain tiles
         const uint64_t tile_step = (uint64_t)step * (uint64_t)GATHER_TILE;
@@ -459,26 +498,8 @@ __global__ __launch_bounds__(GATHER_THREADS, 8) void gather_rows_rot_kernel(Gath
         return;
     }
 
-    if (is_y) {                                 // location (s, a) <- sum_b R[a][b] location (s, b); activity copied
-        const uint32_t n_sed = (uint32_t)a.n_sed, cols = 4u * n_sed;
-        const uint64_t tile_step = (uint64_t)step * (uint64_t)GATHER_TILE;
-        for (uint64_t off = (uint64_t)first * (uint64_t)GATHER_TILE; off < row; off += tile_step) {
-            const uint32_t left = row - (uint32_t)off, len = left < GATHER_TILE ? left : (uint32_t)GATHER_TILE;
-            for (uint32_t i = tid; i < len; i += GATHER_THREADS) {
-                const uint32_t o = (uint32_t)off + i, j = o % cols;
-                float v;
-                if (j < n_sed) {
-                    v = src[o];
-                } else {
-                    const uint32_t axis = (j - n_sed) % 3u, o0 = o - axis;
-                    const float r0 = axis == 0u ? ax.r[0] : axis == 1u ? ax.r[3] : ax.r[6];
-                    const float r1 = axis == 0u ? ax.r[1] : axis == 1u ? ax.r[4] : ax.r[7];
-                    const float r2 = axis == 0u ? ax.r[2] : axis == 1u ? ax.r[5] : ax.r[8];
-                    v = rot_mix(r0, r1, r2, src[o0], src[o0 + 1u], src[o0 + 2u]);
-                }
-                dst[o] = v;
-            }
-        }
+    if (is_y) {
+        rot_y_row(src, dst, row, (uint32_t)first, (uint32_t)step, (uint32_t)a.n_sed, ax);
         return;
     }
 
@@ -493,6 +514,173 @@ __global__ __launch_bounds__(GATHER_THREADS, 8) void gather_rows_rot_kernel(Gath
     const uint64_t pass = rotate ? a.pass : 0xFEDCBA9876543210ull;
     if (a.vec) rot_x_row<true>(src, dst, (uint32_t)first, (uint32_t)step, n_a, n_b, a.triples, pass, ax);
     else rot_x_row<false>(src, dst, (uint32_t)first, (uint32_t)step, n_a, n_b, a.triples, pass, ax);
+}
+
+// ---- gather with a rotation of the sound field, magnitude / phase predictors ----------------------------------------------
+// Channels come as GROUPS of six, (mx, my, mz, px, py, pz): magnitude and phase of the three directional channels of one
+// microphone.  A bin of the STFT is the complex number m e^(i phi) and the STFT is linear, so the rotation is the real
+// matrix R applied to the complex 3-vector of every (f, t): polar to Cartesian, mix, back.  With `stats` the stored values
+// are standardised, (value - mean) / sd per kind, and the kernel undoes and redoes that around the rotation.  Group
+// items are numbered before pass items as the triples of gather_rows_rot_kernel are, in tiles of POLAR_TILE: one item per
+// lane, six 16-byte loads in flight ahead of six stores.  sincosf (with its large-argument reduction) and atan2f, inlined
+// three times each per position, fill the registers: 108 VGPRs on gfx950, so the kernel is bounded to 4 waves per SIMD
+// (under the 8 of the other gathers it spills); a second item per lane would add 48 registers of data and drop to 3.
+// Pass tiles, the masks, the draws and the labels are gather_rows_rot_kernel's.
+constexpr int POLAR_MAX_GROUPS = 2;
+constexpr int POLAR_VEC = 1;
+constexpr uint32_t POLAR_TILE = GATHER_THREADS * POLAR_VEC;            // items per tile
+
+struct PolarParams {
+    int C, F, T;                // predictor row = (C, F, T)
+    int n_sed;                  // target row = (T_out, [n_sed activity | n_sed * 3 location])
+    uint64_t seed;
+    int n_groups, n_pass;
+    uint64_t groups;            // 4 bits per entry: mx, my, mz, px, py, pz of group 0, of group 1
+    uint64_t pass;              // 4 bits per entry: the channels outside the groups, ascending
+    float p_rot;
+    int mirror, zflip;
+    int n_fmask, f_max, n_tmask, t_max;
+    float fill;
+    int vec;                    // T % 4 == 0 and both predictor arrays 16-byte aligned
+};
+
+struct PolarStats {
+    float mean_m, sd_m, mean_p, sd_p;
+};
+
+// one (f, t) of one group, in place: m[j], ph[j] (j = x, y, z) as stored -> as stored after the rotation
+template <bool STATS> __device__ __forceinline__ void polar_mix(const float* __restrict__ r, const PolarStats& st, float* m, float* ph) {
+#pragma clang fp contract(off)
+    float re[3], im[3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        const float mag = STATS ? fmaf(m[j], st.sd_m, st.mean_m) : m[j];
+        const float phi = STATS ? fmaf(ph[j], st.sd_p, st.mean_p) : ph[j];
+        float s, c;
+        sincosf(phi, &s, &c);
+        re[j] = mag * c;
+        im[j] = mag * s;
+    }
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const float ra = rot_mix(r[3 * a], r[3 * a + 1], r[3 * a + 2], re[0], re[1], re[2]);
+        const float ia = rot_mix(r[3 * a], r[3 * a + 1], r[3 * a + 2], im[0], im[1], im[2]);
+        const float mag = sqrtf(fmaf(ia, ia, ra * ra)), phi = atan2f(ia, ra);
+        m[a] = STATS ? __fdiv_rn(mag - st.mean_m, st.sd_m) : mag;
+        ph[a] = STATS ? __fdiv_rn(phi - st.mean_p, st.sd_p) : phi;
+    }
+}
+
+// items [first, first + POLAR_TILE) of the n group items: item i is piece i % P of group i / P
+template <bool VEC, bool STATS> __device__ __forceinline__ void polar_tile_groups(const float* __restrict__ s, float* __restrict__ d,
+                                                                                  uint32_t first, uint32_t n, uint64_t groups,
+                                                                                  const RotX& a, const PolarStats& st) {
+    constexpr uint32_t W = VEC ? 4u : 1u;
+    float4 v[POLAR_VEC][6];
+    uint32_t o[POLAR_VEC][6], t0[POLAR_VEC];
+    bool whole[POLAR_VEC];
+#pragma unroll
+    for (int k = 0; k < POLAR_VEC; ++k) {
+        const uint32_t i = first + threadIdx.x + (uint32_t)k * GATHER_THREADS, ii = i < n ? i : 0u;    // a lane past the end: item 0
+        const uint32_t u = ii / a.P, e = (ii - u * a.P) * W, f = e / a.T;
+        const uint32_t g = (uint32_t)(groups >> (24u * u));
+        t0[k] = e - f * a.T;
+        whole[k] = a.fm.hit(f);
+        const bool load = i < n && !whole[k];
+#pragma unroll
+        for (int j = 0; j < 6; ++j) {
+            o[k][j] = ((g >> (4 * j)) & 15u) * a.FT + e;
+            v[k][j] = load ? rot_load<VEC>(s + o[k][j]) : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < POLAR_VEC; ++k) {
+        if (first + threadIdx.x + (uint32_t)k * GATHER_THREADS >= n) continue;
+        float* lane[6];
+#pragma unroll
+        for (int j = 0; j < 6; ++j) lane[j] = reinterpret_cast<float*>(&v[k][j]);
+#pragma unroll
+        for (int q = 0; q < (int)W; ++q) {
+            float m[3] = {lane[0][q], lane[1][q], lane[2][q]}, ph[3] = {lane[3][q], lane[4][q], lane[5][q]};
+            polar_mix<STATS>(a.r, st, m, ph);
+#pragma unroll
+            for (int j = 0; j < 3; ++j) lane[j][q] = m[j], lane[3 + j][q] = ph[j];
+        }
+#pragma unroll
+        for (int j = 0; j < 6; ++j) rot_store<VEC>(d + o[k][j], rot_masked(v[k][j], whole[k], t0[k], a));
+    }
+}
+
+// the predictor row of one sample: tiles [first, ...) in steps of `step`, group tiles before pass tiles
+template <bool VEC, bool STATS> __device__ __forceinline__ void polar_x_row(const float* __restrict__ s, float* __restrict__ d,
+                                                                            uint32_t first, uint32_t step, uint32_t n_a, uint32_t n_b,
+                                                                            uint64_t groups, uint64_t pass, const RotX& a,
+                                                                            const PolarStats& st) {
+    const uint32_t tiles_a = (n_a + POLAR_TILE - 1u) / POLAR_TILE, tiles_b = (n_b + ROT_TILE_B - 1u) / ROT_TILE_B;
+    for (uint32_t tile = first; tile < tiles_a + tiles_b; tile += step) {
+        if (tile < tiles_a) polar_tile_groups<VEC, STATS>(s, d, tile * POLAR_TILE, n_a, groups, a, st);
+        else rot_tile_pass<VEC>(s, d, (tile - tiles_a) * ROT_TILE_B, n_b, pass, a);
+    }
+}
+
+// grid (gx + gy, count) as gather_rows_kernel.  Uniform over the workgroup as in gather_rows_rot_kernel; the four
+// statistics are loaded before the first store as well (one scalar load).
+__global__ __launch_bounds__(GATHER_THREADS, 4) void gather_rows_polar_kernel(GatherSide x, GatherSide y, int gx,
+                                                                           const int64_t* __restrict__ index, long long n_index,
+                                                                           long long n_rows, const int32_t* __restrict__ cursor,
+                                                                           long long stride, long long start,
+                                                                           const int32_t* __restrict__ epoch,
+                                                                           const float* __restrict__ matrices,
+                                                                           const float* __restrict__ stats, PolarParams a) {
+    const int b = blockIdx.y;
+    const bool is_y = (int)blockIdx.x >= gx;
+    const GatherSide sd = is_y ? y : x;
+    const int first = is_y ? (int)blockIdx.x - gx : (int)blockIdx.x;
+    const int step = is_y ? (int)gridDim.x - gx : gx;
+    const long long p = start + b + (cursor ? (long long)cursor[0] * stride : 0);
+    long long r = -1;
+    if (p >= 0 && p < n_index) r = index[p];
+    const bool valid = r >= 0 && r < n_rows;
+    float* __restrict__ dst = sd.out + (long long)b * sd.row;
+    const float* __restrict__ src = valid ? sd.all + r * sd.row : dst;
+    const uint32_t row = (uint32_t)sd.row;                                  // rows are below 2^31 floats
+
+    uint64_t counter = 0;
+    RotX ax;
+    const bool rotate = rot_draw(valid, p, b, epoch, matrices, a.seed, a.p_rot, a.mirror, a.zflip, counter, ax);
+    PolarStats st{0.f, 1.f, 0.f, 1.f};
+    if (stats && rotate && !is_y) st = PolarStats{stats[0], stats[1], stats[2], stats[3]};
+
+    if (!valid || (is_y && !rotate)) {          // zero-fill, or targets that no rotation touches: the plain tiles
+        const uint64_t tile_step = (uint64_t)step * (uint64_t)GATHER_TILE;
+        for (uint64_t off = (uint64_t)first * (uint64_t)GATHER_TILE; off < row; off += tile_step) {
+            const uint32_t left = row - (uint32_t)off;
+            gather_tile(src + off, dst + off, (int)(left < GATHER_TILE ? left : GATHER_TILE), valid);
+        }
+        return;
+    }
+
+    if (is_y) {
+        rot_y_row(src, dst, row, (uint32_t)first, (uint32_t)step, (uint32_t)a.n_sed, ax);
+        return;
+    }
+
+    ax.fm = draw_masks(counter | 1u, a.seed, a.n_fmask, a.f_max, a.F);
+    ax.tm = draw_masks(counter | 2u, a.seed, a.n_tmask, a.t_max, a.T);
+    ax.T = (uint32_t)a.T;
+    ax.FT = (uint32_t)a.F * ax.T;
+    ax.P = a.vec ? ax.FT >> 2 : ax.FT;
+    ax.fill = a.fill;
+    const uint32_t n_a = rotate ? (uint32_t)a.n_groups * ax.P : 0u;
+    const uint32_t n_b = (uint32_t)(rotate ? a.n_pass : a.C) * ax.P;
+    const uint64_t pass = rotate ? a.pass : 0xFEDCBA9876543210ull;
+    if (stats) {
+        if (a.vec) polar_x_row<true, true>(src, dst, (uint32_t)first, (uint32_t)step, n_a, n_b, a.groups, pass, ax, st);
+        else polar_x_row<false, true>(src, dst, (uint32_t)first, (uint32_t)step, n_a, n_b, a.groups, pass, ax, st);
+    } else {
+        if (a.vec) polar_x_row<true, false>(src, dst, (uint32_t)first, (uint32_t)step, n_a, n_b, a.groups, pass, ax, st);
+        else polar_x_row<false, false>(src, dst, (uint32_t)first, (uint32_t)step, n_a, n_b, a.groups, pass, ax, st);
+    }
 }
 
 // one thread: the epoch loop's running mean (train.main), `mean += (loss - mean) / (i + 1)` in fp32 with i the cursor,
@@ -545,6 +733,23 @@ static bool aug_gather_refused(const float* x_all, int64_t row_x, const float* o
     return has_y && (y_cols < 4 || y_cols % 4 || row_y % y_cols);
 }
 
+// `n` (at most 15) channel entries packed 4 bits each: refused unless they are distinct, inside [0, C) and the bits above
+// them 0.  `pass` receives the other channels of [0, C), ascending, packed the same way.
+static bool packed_channels_refused(uint64_t packed, int n, int C, uint64_t& pass, int& n_pass) {
+    uint32_t used = 0u;
+    for (int i = 0; i < n; ++i) {
+        const uint32_t c = (uint32_t)(packed >> (4 * i)) & 15u;
+        if (c >= (uint32_t)C || (used >> c & 1u)) return true;
+        used |= 1u << c;
+    }
+    if ((packed >> (4 * n)) != 0) return true;
+    pass = 0;
+    n_pass = 0;
+    for (int c = 0; c < C; ++c)
+        if (!(used >> c & 1u)) pass |= (uint64_t)c << (4 * n_pass++);
+    return false;
+}
+
 extern "C" int seld_gather_rows_aug(const float* x_all, int64_t row_x, float* out_x, const float* y_all, int64_t row_y,
                                     float* out_y, const int64_t* index, int64_t n_index, int64_t n_rows, const int32_t* cursor,
                                     int64_t cursor_stride, int64_t start, int32_t B, int32_t count, int32_t C, int32_t F,
@@ -583,17 +788,9 @@ extern "C" int seld_gather_rows_rot(const float* x_all, int64_t row_x, float* ou
     if (!(p_rot >= 0.f && p_rot <= 1.f)) return SELD_EINVAL;                        // a NaN fails both
     if (row_x >= (1ll << 31) || row_y >= (1ll << 31)) return SELD_EUNSUPPORTED;     // offsets inside a row are 32-bit
     // the triples travel by value, so their content is checked here: the kernel then indexes with them as they are
-    uint32_t used = 0u;
-    for (int i = 0; i < 3 * n_triples; ++i) {
-        const uint32_t c = (uint32_t)(triples >> (4 * i)) & 15u;
-        if (c >= (uint32_t)C || (used >> c & 1u)) return SELD_EINVAL;
-        used |= 1u << c;
-    }
-    if ((triples >> (12 * n_triples)) != 0) return SELD_EINVAL;                     // at most 60 bits are entries
     uint64_t pass = 0;
     int n_pass = 0;
-    for (int c = 0; c < C; ++c)
-        if (!(used >> c & 1u)) pass |= (uint64_t)c << (4 * n_pass++);
+    if (packed_channels_refused(triples, 3 * n_triples, C, pass, n_pass)) return SELD_EINVAL;      // at most 60 bits are entries
     const int vec = has_x && T % 4 == 0 && (((uintptr_t)x_all | (uintptr_t)out_x) & 15) == 0;
     // the grid of seld_gather_rows_aug over the tiles of this kernel: the larger of a rotated and an unrotated sample's
     const long long P = has_x ? (vec ? (long long)F * T / 4 : (long long)F * T) : 0;
@@ -608,6 +805,42 @@ extern "C" int seld_gather_rows_rot(const float* x_all, int64_t row_x, float* ou
                       n_fmask, f_max, n_tmask, t_max, fill, vec};
     hipLaunchKernelGGL(gather_rows_rot_kernel, dim3(gx + gy, count), dim3(GATHER_THREADS), 0, (hipStream_t)stream, x, y, gx, index,
                        (long long)n_index, (long long)n_rows, cursor, (long long)cursor_stride, (long long)start, epoch, matrices, a);
+    return check_launch();
+}
+
+extern "C" int seld_gather_rows_polar(const float* x_all, int64_t row_x, float* out_x, const float* y_all, int64_t row_y,
+                                      float* out_y, const int64_t* index, int64_t n_index, int64_t n_rows, const int32_t* cursor,
+                                      int64_t cursor_stride, int64_t start, int32_t B, int32_t count, int32_t C, int32_t F,
+                                      int32_t T, int32_t y_cols, const int32_t* epoch, uint64_t seed, uint64_t groups,
+                                      int32_t n_groups, const float* stats, float p_rot, int32_t rot_mirror, int32_t rot_zflip,
+                                      const float* matrices, int32_t n_fmask, int32_t f_max, int32_t n_tmask, int32_t t_max,
+                                      float fill, void* stream) {
+    const bool has_x = x_all || out_x, has_y = y_all || out_y;
+    if (aug_gather_refused(x_all, row_x, out_x, y_all, row_y, out_y, index, n_index, n_rows, cursor, cursor_stride, B, count, C, F, T,
+                           y_cols, epoch, n_fmask, f_max, n_tmask, t_max))
+        return SELD_EINVAL;
+    if (n_groups < 1 || n_groups > POLAR_MAX_GROUPS || 6 * n_groups > C) return SELD_EINVAL;
+    if (!(p_rot >= 0.f && p_rot <= 1.f)) return SELD_EINVAL;                        // a NaN fails both
+    if (row_x >= (1ll << 31) || row_y >= (1ll << 31)) return SELD_EUNSUPPORTED;     // offsets inside a row are 32-bit
+    // the groups travel by value, so their content is checked here: the kernel then indexes with them as they are
+    uint64_t pass = 0;
+    int n_pass = 0;
+    if (packed_channels_refused(groups, 6 * n_groups, C, pass, n_pass)) return SELD_EINVAL;        // at most 48 bits are entries
+    const int vec = has_x && T % 4 == 0 && (((uintptr_t)x_all | (uintptr_t)out_x) & 15) == 0;
+    // the grid of seld_gather_rows_rot over the tiles of this kernel: the larger of a rotated and an unrotated sample's
+    const long long P = has_x ? (vec ? (long long)F * T / 4 : (long long)F * T) : 0;
+    const long long cap = GATHER_MAX_BLOCKS / count > 0 ? GATHER_MAX_BLOCKS / count : 1;
+    const long long t_rot = (n_groups * P + POLAR_TILE - 1) / POLAR_TILE + (n_pass * P + ROT_TILE_B - 1) / ROT_TILE_B;
+    const long long t_plain = (C * P + ROT_TILE_B - 1) / ROT_TILE_B;
+    const long long tx = t_rot > t_plain ? t_rot : t_plain;
+    const long long ty = has_y ? (row_y + GATHER_TILE - 1) / GATHER_TILE : 0;
+    const int gx = (int)(tx < cap ? tx : cap), gy = (int)(ty < cap ? ty : cap);
+    const GatherSide x{x_all, out_x, has_x ? (long long)row_x : 0}, y{y_all, out_y, has_y ? (long long)row_y : 0};
+    const PolarParams a{C, F, T, has_y ? y_cols / 4 : 0, seed, n_groups, n_pass, groups, pass, p_rot, rot_mirror != 0, rot_zflip != 0,
+                        n_fmask, f_max, n_tmask, t_max, fill, vec};
+    hipLaunchKernelGGL(gather_rows_polar_kernel, dim3(gx + gy, count), dim3(GATHER_THREADS), 0, (hipStream_t)stream, x, y, gx, index,
+                       (long long)n_index, (long long)n_rows, cursor, (long long)cursor_stride, (long long)start, epoch, matrices, stats,
+                       a);
     return check_launch();
 }
 

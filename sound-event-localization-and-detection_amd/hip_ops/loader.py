@@ -4,6 +4,7 @@ frequency and time masks), the per-step running mean of the loss, and the epoch'
 would draw it."""
 import dataclasses
 import itertools
+import weakref
 
 import numpy as np
 import torch
@@ -11,9 +12,9 @@ import torch
 from .. import _lib as L
 from ._core import _req, timed
 
-__all__ = ["gather_rows", "gather_rows_aug", "gather_rows_rot", "Augment", "foa_transforms", "foa_triples", "epoch_step_end",
-           "epoch_permutation"]
-AUG_MAX_CHANNELS, AUG_MAX_TRANSFORMS, ROT_MAX_TRIPLES = 16, 64, 5
+__all__ = ["gather_rows", "gather_rows_aug", "gather_rows_rot", "gather_rows_polar", "Augment", "foa_transforms", "foa_triples",
+           "foa_polar", "epoch_step_end", "epoch_permutation"]
+AUG_MAX_CHANNELS, AUG_MAX_TRANSFORMS, ROT_MAX_TRIPLES, POLAR_MAX_GROUPS = 16, 64, 5, 2
 
 
 def _rows(t, name):
@@ -107,11 +108,26 @@ def foa_triples(order="WYZX", mics=1, layout="quaternion"):
     """The channel triples (cx, cy, cz) of `Augment(rot_triples=...)` for the layouts in which every directional channel is
     an intensity component: 'quaternion' (C = 4 * mics, per microphone [log-power W, I1, I2, I3]) and 'iv' (C = 3 * mics).
     One triple per microphone; `order` says which of X, Y, Z the components are.  'magphase' and 'logpower_iv' are
-    refused: a magnitude, a phase or the log-power of a directional channel is not covariant under a general rotation."""
+    refused: a magnitude, a phase or the log-power of a directional channel is not covariant under a general rotation
+    (magnitude and phase TOGETHER are: `foa_polar`, `gather_rows_polar`)."""
     if layout in ("magphase", "logpower_iv"):
         raise L.SeldHipError(f"foa_triples: a rotation is not defined on the {layout} layout (it holds directional channels "
                              "that are no intensity components)")
     return [tuple(t) for t in _intensity_channels("foa_triples", order, mics, layout)]
+
+
+def foa_polar(order="WYZX", mics=1):
+    """The channel groups (mx, my, mz, px, py, pz) of `Augment(rot_polar=...)` for magnitude-phase predictors in the layout
+    [magnitude mic A | magnitude mic B | phase mic A | phase mic B] (C = 8 * mics: what `foa_transforms(phase=True)` and
+    train.normalize_dataset assume): magnitude and phase channel of the x, y and z axis, one group per microphone.
+    `order` names the channels of a 4-channel block; W may sit anywhere in it and is in no group (it is copied)."""
+    order = str(order).upper()
+    if sorted(order) != sorted("W" + _AXES):
+        raise L.SeldHipError(f"foa_polar: order must name W, X, Y and Z once each, got {order!r}")
+    if mics not in (1, 2):
+        raise L.SeldHipError(f"foa_polar: 1 or 2 microphones, got {mics}")
+    pos = [order.index(ch) for ch in _AXES]
+    return [tuple(4 * g + pos[a] for a in range(3)) + tuple(4 * (mics + g) + pos[a] for a in range(3)) for g in range(mics)]
 
 
 def foa_transforms(order="WYZX", mics=1, phase=False, elevation=True, layout="magphase"):
@@ -212,6 +228,19 @@ def _check_triples(triples):
     return tuple(tuple(int(c) for c in row) for row in t)
 
 
+def _check_polar(groups):
+    """((mx, my, mz, px, py, pz), ...) of 1..2 channel groups; raises SeldHipError unless they are distinct channels in [0, 16)."""
+    t = np.asarray(groups.cpu() if torch.is_tensor(groups) else groups)
+    if t.ndim != 2 or t.shape[1] != 6 or not 1 <= t.shape[0] <= POLAR_MAX_GROUPS or not np.issubdtype(t.dtype, np.integer):
+        raise L.SeldHipError(f"Augment: rot_polar must be 1..{POLAR_MAX_GROUPS} integer groups (mx, my, mz, px, py, pz), "
+                             f"got {t.dtype} {t.shape}")
+    if t.min() < 0 or t.max() >= AUG_MAX_CHANNELS:
+        raise L.SeldHipError(f"Augment: a rot_polar channel outside [0, {AUG_MAX_CHANNELS})")
+    if len(set(t.ravel().tolist())) != t.size:
+        raise L.SeldHipError("Augment: a channel appears twice in rot_polar")
+    return tuple(tuple(int(c) for c in row) for row in t)
+
+
 @dataclasses.dataclass(frozen=True)
 class Augment:
     """What seld_gather_rows_aug applies to every sample (include/seld_hip.h has the draws).
@@ -226,7 +255,11 @@ class Augment:
     probability 1/2 if rot_zflip; rot_triples, 1..5 channel triples (cx, cy, cz) of intensity vectors, e.g.
     `foa_triples(...)`, held as a tuple of tuples.  p_rot > 0 needs triples and excludes p_swap > 0 (the rotations with
     mirror and z-flip contain the signed permutations: one channel transform per sample).  Everything is checked before
-    the table goes to the device."""
+    the table goes to the device.
+
+    What seld_gather_rows_polar applies (hip_ops.gather_rows_polar): the same p_rot, rot_mirror and rot_zflip on
+    magnitude-phase predictors; rot_polar, 1..2 channel groups (mx, my, mz, px, py, pz), e.g. `foa_polar(...)`, held as a
+    tuple of tuples.  p_rot > 0 needs exactly one of rot_triples and rot_polar."""
     table: object = None
     p_swap: float = 0.0
     freq_masks: int = 0
@@ -239,6 +272,7 @@ class Augment:
     rot_triples: object = None
     rot_mirror: bool = True
     rot_zflip: bool = True
+    rot_polar: object = None
 
     def __post_init__(self):
         host = None if self.table is None else _check_table(self.table, None)
@@ -253,8 +287,13 @@ class Augment:
             raise L.SeldHipError(f"Augment: p_rot {self.p_rot} is no probability")
         if self.rot_triples is not None:
             object.__setattr__(self, "rot_triples", _check_triples(self.rot_triples))
-        if float(self.p_rot) > 0.0 and self.rot_triples is None:
-            raise L.SeldHipError("Augment: p_rot > 0 needs rot_triples, the channels of the intensity vectors")
+        if self.rot_polar is not None:
+            object.__setattr__(self, "rot_polar", _check_polar(self.rot_polar))
+        if float(self.p_rot) > 0.0 and self.rot_triples is None and self.rot_polar is None:
+            raise L.SeldHipError("Augment: p_rot > 0 needs rot_triples, the channels of the intensity vectors, or rot_polar, "
+                                 "the magnitude and phase channels")
+        if float(self.p_rot) > 0.0 and self.rot_triples is not None and self.rot_polar is not None:
+            raise L.SeldHipError("Augment: p_rot > 0 with both rot_triples and rot_polar (one kind of predictors per loader)")
         if float(self.p_rot) > 0.0 and float(self.p_swap) > 0.0:
             raise L.SeldHipError("Augment: p_rot > 0 together with p_swap > 0 (one channel transform per sample)")
         object.__setattr__(self, "table", None if host is None else torch.from_numpy(host).to(self.device))
@@ -268,6 +307,17 @@ class Augment:
     def rot_packed(self):
         """The triples as seld_gather_rows_rot takes them: 4 bits per entry."""
         flat = [c for t in self.rot_triples for c in t]
+        return sum(c << (4 * i) for i, c in enumerate(flat))
+
+    @property
+    def polar_channels(self):
+        """The least number of channels the groups need, None without groups."""
+        return None if self.rot_polar is None else 1 + max(max(g) for g in self.rot_polar)
+
+    @property
+    def polar_packed(self):
+        """The groups as seld_gather_rows_polar takes them: 4 bits per entry."""
+        flat = [c for g in self.rot_polar for c in g]
         return sum(c << (4 * i) for i, c in enumerate(flat))
 
     @property
@@ -318,6 +368,32 @@ def gather_rows_aug(x_all, y_all, index, out_x, out_y, *, epoch, seed, augment, 
     return out_x, out_y
 
 
+def _rot_geometry(what, field, channels, x_all, y_all, epoch, matrices, dev, count):
+    """The checks the two rotating gathers make of epoch, geometry and matrices: (C, F, T, y_cols).  `channels`: the least
+    number of channels the Augment's `field` needs (targets alone: the C of the call)."""
+    if _scalar(epoch, f"{what}: epoch", torch.int32).device != dev:
+        raise L.SeldHipError(f"{what}: epoch on another device")
+    C, F, T = channels, 1, 1
+    if x_all is not None:
+        if x_all.dim() != 4:
+            raise L.SeldHipError(f"{what}: predictors must be (n, C, F, T), got {tuple(x_all.shape)}")
+        C, F, T = x_all.shape[1:]
+        if channels > C:
+            raise L.SeldHipError(f"{what}: {field} name channel {channels - 1}, the predictors have {C}")
+    y_cols = 4
+    if y_all is not None:
+        if y_all.dim() < 2:
+            raise L.SeldHipError(f"{what}: targets must be (n, ..., 4 * n_sed), got {tuple(y_all.shape)}")
+        y_cols = y_all.shape[-1]
+    if matrices is not None:
+        if (not torch.is_tensor(matrices) or _req(matrices, f"{what}: matrices") is not matrices or matrices.device != dev
+                or matrices.dim() < 2 or matrices.shape[0] < count
+                or tuple(matrices.shape[1:]) not in ((9,), (3, 3))):
+            raise L.SeldHipError(f"{what}: matrices must be a contiguous fp32 tensor ({count}, 9) or ({count}, 3, 3) on {dev}, "
+                                 f"got {getattr(matrices, 'shape', type(matrices).__name__)}")
+    return C, F, T, y_cols
+
+
 def gather_rows_rot(x_all, y_all, index, out_x, out_y, *, epoch, seed, augment, matrices=None, cursor=None, start=0, count=None,
                     stride=None):
     """`gather_rows` with a rotation of the sound field applied to every sample on the way, then the masks of `augment`, in
@@ -334,26 +410,7 @@ def gather_rows_rot(x_all, y_all, index, out_x, out_y, *, epoch, seed, augment, 
         raise L.SeldHipError(f"{what}: the Augment has no rot_triples")
     x_all, row_x, y_all, row_y, out_x, out_y, n_rows, dev, B, count, stride = _gather_args(
         what, x_all, y_all, index, out_x, out_y, cursor, count, stride)
-    if _scalar(epoch, f"{what}: epoch", torch.int32).device != dev:
-        raise L.SeldHipError(f"{what}: epoch on another device")
-    C, F, T = augment.rot_channels, 1, 1                # targets alone: as many channels as the triples name
-    if x_all is not None:
-        if x_all.dim() != 4:
-            raise L.SeldHipError(f"{what}: predictors must be (n, C, F, T), got {tuple(x_all.shape)}")
-        C, F, T = x_all.shape[1:]
-        if augment.rot_channels > C:
-            raise L.SeldHipError(f"{what}: rot_triples name channel {augment.rot_channels - 1}, the predictors have {C}")
-    y_cols = 4
-    if y_all is not None:
-        if y_all.dim() < 2:
-            raise L.SeldHipError(f"{what}: targets must be (n, ..., 4 * n_sed), got {tuple(y_all.shape)}")
-        y_cols = y_all.shape[-1]
-    if matrices is not None:
-        if (not torch.is_tensor(matrices) or _req(matrices, f"{what}: matrices") is not matrices or matrices.device != dev
-                or matrices.dim() < 2 or matrices.shape[0] < count
-                or tuple(matrices.shape[1:]) not in ((9,), (3, 3))):
-            raise L.SeldHipError(f"{what}: matrices must be a contiguous fp32 tensor ({count}, 9) or ({count}, 3, 3) on {dev}, "
-                                 f"got {getattr(matrices, 'shape', type(matrices).__name__)}")
+    C, F, T, y_cols = _rot_geometry(what, "rot_triples", augment.rot_channels, x_all, y_all, epoch, matrices, dev, count)
     with torch.cuda.device(dev):
         with timed("gather_rows_rot_kernel", lambda: (0.0, float(8 * count * (row_x + row_y)))):
             L.check(L.lib().seld_gather_rows_rot(
@@ -363,6 +420,61 @@ def gather_rows_rot(x_all, y_all, index, out_x, out_y, *, epoch, seed, augment, 
                 int(bool(augment.rot_zflip)), L.ptr(matrices), int(augment.freq_masks), int(augment.freq_width),
                 int(augment.time_masks), int(augment.time_width), float(augment.fill), L.current_stream()),
                 "seld_gather_rows_rot")
+    return out_x, out_y
+
+
+_stats_checked = {}     # id(tensor) -> (weak reference, _version) of the statistics tensors whose content has been read back
+
+
+def _check_stats(stats, dev, what):
+    """`stats` as seld_gather_rows_polar reads it: 4 contiguous fp32 on `dev`, finite, both standard deviations > 0.  The
+    content costs a read-back (a synchronisation), so it is looked at once per tensor, and again after an in-place change."""
+    if not torch.is_tensor(stats) or _req(stats, f"{what}: stats") is not stats or stats.device != dev or stats.numel() != 4:
+        raise L.SeldHipError(f"{what}: stats must be a contiguous fp32 tensor of 4 values (mean_m, sd_m, mean_p, sd_p) on {dev}, "
+                             f"got {getattr(stats, 'shape', type(stats).__name__)}")
+    seen = _stats_checked.get(id(stats))
+    if seen is None or seen[0]() is not stats or seen[1] != stats._version:
+        if torch.cuda.is_current_stream_capturing():
+            raise L.SeldHipError(f"{what}: the first call with a statistics tensor reads it back: make it outside the capture")
+        mean_m, sd_m, mean_p, sd_p = (float(v) for v in stats.reshape(4).tolist())
+        if not all(np.isfinite(v) for v in (mean_m, sd_m, mean_p, sd_p)) or sd_m <= 0 or sd_p <= 0:
+            raise L.SeldHipError(f"{what}: stats must be finite with both standard deviations > 0, got "
+                                 f"{(mean_m, sd_m, mean_p, sd_p)}")
+        key = id(stats)
+        _stats_checked[key] = (weakref.ref(stats, lambda _, key=key: _stats_checked.pop(key, None)), stats._version)
+    return stats
+
+
+def gather_rows_polar(x_all, y_all, index, out_x, out_y, *, epoch, seed, augment, stats=None, matrices=None, cursor=None, start=0,
+                      count=None, stride=None):
+    """`gather_rows_rot` for magnitude-phase predictors, in ONE launch (seld_gather_rows_polar; include/seld_hip.h has the
+    formula).  The channels of `augment.rot_polar` are (mx, my, mz, px, py, pz) per microphone: a rotated sample gets, per
+    group and (f, t), the complex 3-vector m e^(i phi) of its directional channels multiplied by R and written back as
+    magnitude and phase; location'(s, a) = sum_j R[a][j] location(s, j); every other channel (W among them) and the
+    activity are copied; then the masks of `augment`.  stats: fp32 device tensor (mean_m, sd_m, mean_p, sd_p) when the
+    predictors are standardised per half as train.normalize_dataset leaves them (the kernel undoes and redoes it around
+    the rotation), None for raw magnitude and phase; its content is checked at the first call with that tensor.  R,
+    `matrices`, geometry, epoch, cursor, start, count, stride and the zero rows of invalid positions as in
+    `gather_rows_rot`.  augment.table, p_swap and rot_triples are not used."""
+    what = "gather_rows_polar"
+    if not isinstance(augment, Augment):
+        raise L.SeldHipError(f"{what}: augment must be an Augment, got {type(augment).__name__}")
+    if augment.rot_polar is None:
+        raise L.SeldHipError(f"{what}: the Augment has no rot_polar")
+    x_all, row_x, y_all, row_y, out_x, out_y, n_rows, dev, B, count, stride = _gather_args(
+        what, x_all, y_all, index, out_x, out_y, cursor, count, stride)
+    C, F, T, y_cols = _rot_geometry(what, "rot_polar", augment.polar_channels, x_all, y_all, epoch, matrices, dev, count)
+    if stats is not None:
+        _check_stats(stats, dev, what)
+    with torch.cuda.device(dev):
+        with timed("gather_rows_polar_kernel", lambda: (0.0, float(8 * count * (row_x + row_y)))):
+            L.check(L.lib().seld_gather_rows_polar(
+                L.ptr(x_all), row_x, L.ptr(out_x), L.ptr(y_all), row_y, L.ptr(out_y), L.ptr(index), index.numel(), n_rows,
+                L.ptr(cursor), stride, int(start), B, count, C, F, T, y_cols, L.ptr(epoch), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                augment.polar_packed, len(augment.rot_polar), L.ptr(stats), float(augment.p_rot), int(bool(augment.rot_mirror)),
+                int(bool(augment.rot_zflip)), L.ptr(matrices), int(augment.freq_masks), int(augment.freq_width),
+                int(augment.time_masks), int(augment.time_width), float(augment.fill), L.current_stream()),
+                "seld_gather_rows_polar")
     return out_x, out_y
 
 

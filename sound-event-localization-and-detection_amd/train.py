@@ -438,9 +438,14 @@ _EVAL = ('use_cuda', 'early_stopping', 'fixed_seed', 'pool_size', 'cnn_filters',
 # width up to augment_freq_width / augment_time_width bins; augment_seed: the key of the draws;
 # feature_layout (magphase by default): the channel layout of the predictors for augment_swap and test_tta -- quaternion, iv
 # or logpower_iv for the intensity features of hip_ops.spatial_features, whose components are negated, not turned by pi;
-# augment_rotate (needs a feature_layout of quaternion or iv; not with augment_swap): probability that a sample's sound
-# field is rotated about the vertical axis by a random angle, with random mirrors in y and z, and its DOA labels with it
-# (hip_ops.gather_rows_rot, the same single launch);
+# augment_rotate (needs a feature_layout of quaternion or iv, or magphase with --phase=True; not with augment_swap):
+# probability that a sample's sound field is rotated about the vertical axis by a random angle, with random mirrors in y
+# and z, and its DOA labels with it (hip_ops.gather_rows_rot, the same single launch).  On magphase predictors with
+# phase (hip_ops.gather_rows_polar) magnitude and phase of a bin are one complex number and the STFT is linear: per
+# microphone and (f, t) the complex vector (X, Y, Z) = m e^(i phi) becomes R (X, Y, Z), W stays; a standardising
+# dataset_normalization is undone and redone around it with the training array's statistics; two spaced microphones
+# share one R, the approximation hip_ops.foa_transforms documents for mics=2.  Magnitudes alone are not covariant and stay
+# refused; test_tta and augment_swap keep their rules (augment_swap with phase still needs raw phase);
 # pit_loss (off by default): the loss takes, per (frame, class), the cheapest pairing of the class_overlaps prediction
 # slots with the target slots (hip_ops.seld_loss_pit) instead of comparing slot o with slot o -- training steps (eager,
 # data parallel, recorded) and the validation loss alike;
@@ -715,9 +720,11 @@ class ResidentLoader:
     `augment` (a hip_ops.Augment; default None: exactly the launches above): every fetch is hip_ops.gather_rows_aug, or
     hip_ops.gather_rows_rot when its p_rot > 0, still one launch.  What a sample draws depends on (`seed`, the device int32 `epoch`, its position in the epoch's order):
     ranks need no agreement, and a recorded fetch draws anew in every epoch.  `epoch` is -1 until the first
-    `begin_epoch`, which adds 1 to it."""
+    `begin_epoch`, which adds 1 to it.  An `augment` with rot_polar and p_rot > 0 (magnitude-phase predictors) fetches
+    with hip_ops.gather_rows_polar; `polar_stats` is then the fp32 device tensor (mean_m, sd_m, mean_p, sd_p) with which
+    `x_all` was standardised (`polar_stats_from`), None for raw magnitude and phase."""
 
-    def __init__(self, x_all, y_all, batch_size, shuffle, rank=0, world=1, augment=None, seed=0):
+    def __init__(self, x_all, y_all, batch_size, shuffle, rank=0, world=1, augment=None, seed=0, polar_stats=None):
         self.plan = epoch_plan(x_all.shape[0], batch_size, world)
         if y_all.shape[0] != x_all.shape[0]:
             raise ValueError(f"ResidentLoader: {x_all.shape[0]} predictors but {y_all.shape[0]} targets")
@@ -731,7 +738,7 @@ class ResidentLoader:
         self.cursor = torch.zeros(1, device=dev, dtype=torch.int32)
         self.mean = torch.zeros(1, device=dev, dtype=torch.float32)
         self.epoch = torch.full((1,), -1, device=dev, dtype=torch.int32)
-        self.augment, self.seed = augment, int(seed)
+        self.augment, self.seed, self.polar_stats = augment, int(seed), polar_stats
 
     def __len__(self):
         return len(self.plan)
@@ -757,6 +764,9 @@ class ResidentLoader:
             where = dict(start=rank_rows(self.plan[batch][0], count, self.rank)[0], count=count)
         if self.augment is None:
             H.gather_rows(self.x_all, self.y_all, self.index, self.x, self.target, **where)
+        elif self.augment.p_rot > 0 and self.augment.rot_polar is not None:
+            H.gather_rows_polar(self.x_all, self.y_all, self.index, self.x, self.target, epoch=self.epoch, seed=self.seed,
+                                augment=self.augment, stats=self.polar_stats, **where)
         elif self.augment.p_rot > 0:
             H.gather_rows_rot(self.x_all, self.y_all, self.index, self.x, self.target, epoch=self.epoch, seed=self.seed,
                               augment=self.augment, **where)
@@ -802,7 +812,7 @@ _NORM_UNIT = {'DQ_Normalization', 'UnitNormNormalization', 'UnitNorm'}
 _DOMAIN_DQ = ['DQ', 'dq', 'dQ', 'Dual_Quaternion', 'dual_quaternion']
 
 
-def normalize_dataset(args, *predictors):
+def normalize_dataset(args, *predictors, stats=None):
     """Dataset normalisation of train.py:242-408, in place on device-resident predictor arrays
     (items, channels, F, T) - the reference's training / validation / test predictors, each normalised with its
     OWN statistics as the reference does.  Returns the description the reference appends to `dataset_string`.
@@ -814,30 +824,45 @@ def normalize_dataset(args, *predictors):
       anything else ('True')                        -> (g - mean) / std over the magnitude channels
                                                        (first 4 for 1 mic, first 8 for 2 mics) and, with --phase,
                                                        separately over the remaining channels (train.py:341-405)
+
+    `stats`: a list that receives one entry per predictor array, in order: the (mean, std) device tensors of the groups
+    `group_standardize_` applied to it (one, or two with --phase), or None where the array was left raw or got another
+    normalisation (what ResidentLoader(polar_stats=...) wants to know of the training array).
     """
+    desc, entries = _normalize_dataset(args, predictors)
+    if stats is not None:
+        stats.extend(entries)
+    return desc
+
+
+def _normalize_dataset(args, predictors):
+    """(description, [what normalize_dataset reports per array])."""
+    untouched = [None] * len(predictors)
     mode = str(args.dataset_normalization)
     if mode in _NORM_OFF:
-        return ''
+        return '', untouched
     if mode in _NORM_UNIT:
         if args.n_mics == 2 and args.domain in _DOMAIN_DQ:
             if args.phase:
                 raise ValueError('DATASET NORMALIZATION FOR PHASE DUAL QUATERNION NOT YET IMPLEMENTED')
             for x in predictors:
                 H.dq_unit_norm_(x)
-            return ' Dataset Normalization for 2Mic 8Ch Magnitude Dual Quaternion UnitNorm'
-        return ''
+            return ' Dataset Normalization for 2Mic 8Ch Magnitude Dual Quaternion UnitNorm', untouched
+        return '', untouched
     if args.n_mics not in (1, 2):
-        return ''
+        return '', untouched
     mag = 4 * args.n_mics
+    entries = []
     for x in predictors:
-        H.group_standardize_(x, 0, mag)
+        applied = [H.group_standardize_(x, 0, mag)]
         if args.phase:
-            H.group_standardize_(x, mag, x.shape[1])
+            applied.append(H.group_standardize_(x, mag, x.shape[1]))
+        entries.append(tuple(applied))
     what = f'{args.n_mics}Mic {mag}Ch Magnitude'
     desc = ' Dataset Normalization for ' + what
     if args.phase:
         desc += f' Dataset Normalization for {args.n_mics}Mic {2 * mag}Ch Magnitude-Phase'
-    return desc
+    return desc, entries
 
 
 FEATURE_LAYOUTS = ('magphase', 'quaternion', 'iv', 'logpower_iv')
@@ -873,9 +898,12 @@ def augment_from_args(args, device):
         raise ValueError("--augment_rotate with --augment_swap: the rotations with their mirrors contain the signed "
                          "permutations, one channel transform per sample")
     layout = feature_layout(args, "--augment_swap" if swap else "--augment_rotate") if swap or rotate > 0 else 'magphase'
-    if rotate > 0 and layout not in ('quaternion', 'iv'):
+    polar = rotate > 0 and layout == 'magphase' and bool(args.phase)
+    if rotate > 0 and not polar and layout not in ('quaternion', 'iv'):
         raise ValueError(f"--augment_rotate needs --feature_layout=quaternion or iv (every directional channel an intensity "
-                         f"component), got {layout}")
+                         f"component) or magphase with --phase=True, got {layout}"
+                         + (": magnitudes alone cannot be rotated, magnitude and phase together (--phase=True) can"
+                            if layout == 'magphase' else ""))
     if rotate > 0 and args.n_mics not in (1, 2):
         raise ValueError(f"--augment_rotate: the FOA layouts are for 1 or 2 microphones, got --n_mics {args.n_mics}")
     mode = str(args.dataset_normalization)
@@ -885,10 +913,21 @@ def augment_from_args(args, device):
     if swap and args.n_mics not in (1, 2):
         raise ValueError(f"--augment_swap: the FOA transform preset is for 1 or 2 microphones, got --n_mics {args.n_mics}")
     table = H.foa_transforms(mics=args.n_mics, phase=bool(args.phase), layout=layout) if swap else None
-    triples = H.foa_triples(mics=args.n_mics, layout=layout) if rotate > 0 else None
+    triples = H.foa_triples(mics=args.n_mics, layout=layout) if rotate > 0 and not polar else None
+    groups = H.foa_polar(mics=args.n_mics) if polar else None
     return H.Augment(table=table, p_swap=args.augment_swap if swap else 0.0, freq_masks=args.augment_freq_masks,
                      freq_width=args.augment_freq_width, time_masks=args.augment_time_masks,
-                     time_width=args.augment_time_width, device=device, p_rot=rotate, rot_triples=triples)
+                     time_width=args.augment_time_width, device=device, p_rot=rotate, rot_triples=triples, rot_polar=groups)
+
+
+def polar_stats_from(entry, device):
+    """What ResidentLoader(polar_stats=...) takes, from the entry normalize_dataset(..., stats=[]) reports for the training
+    array: the fp32 device tensor (mean_m, sd_m, mean_p, sd_p) of a standardised magnitude-phase array, None for a raw one."""
+    if entry is None:
+        return None
+    if len(entry) != 2:
+        raise ValueError("--augment_rotate on magnitude-phase predictors needs the statistics of both halves (--phase=True)")
+    return torch.cat([e.reshape(2).to(device=device, dtype=torch.float32) for e in entry]).contiguous()
 
 
 def test_results_from_counters(counts, total_de, epoch=0):
@@ -1194,22 +1233,28 @@ def main(args, history=None):
         if resident:
             raise ValueError("--resident_loader reads pickled arrays: not with --synthetic")
     else:
-        def loader(x, y, batch_size, shuffle, rank=0, world=1, augment=None):
+        def loader(x, y, batch_size, shuffle, rank=0, world=1, augment=None, polar_stats=None):
             if resident:
-                return ResidentLoader(x, y, batch_size, shuffle, rank, world, augment=augment, seed=args.augment_seed)
+                return ResidentLoader(x, y, batch_size, shuffle, rank, world, augment=augment, seed=args.augment_seed,
+                                      polar_stats=polar_stats)
             return torch.utils.data.DataLoader(torch.utils.data.TensorDataset(x, y), batch_size, shuffle=shuffle,
                                                pin_memory=False)
         augment = augment_from_args(args, device)      # the training loader's alone: validation and test see the data as it is
         xs, ys = load_pickled(args.training_predictors_path, args.training_target_path)
         xs = xs.to(device)                              # 288 GB of HBM: the arrays stay resident, loaders index them
         val_data = test_data = None
+        norm_stats = []
         if rank == 0:
             xv, yv = load_pickled(args.validation_predictors_path, args.validation_target_path)
             xv = xv.to(device)
-            print(normalize_dataset(args, xs, xv))
+            print(normalize_dataset(args, xs, xv, stats=norm_stats))
         else:
-            normalize_dataset(args, xs)
-        tr_data = loader(xs, ys, args.batch_size, True, rank, world, augment)
+            normalize_dataset(args, xs, stats=norm_stats)
+        # the rotating gather of magnitude-phase predictors undoes and redoes the standardisation: it takes the training
+        # array's own statistics, which every rank computed from the same array
+        polar = augment is not None and augment.p_rot > 0 and augment.rot_polar is not None
+        tr_data = loader(xs, ys, args.batch_size, True, rank, world, augment,
+                         polar_stats_from(norm_stats[0], device) if polar else None)
         if rank == 0:
             val_data = loader(xv, yv, args.batch_size, False)
             if os.path.isfile(str(args.test_predictors_path)) and os.path.isfile(str(args.test_target_path)):
