@@ -5,32 +5,21 @@
 //   seld_ensemble_combine  the members' outputs stitched back: DOAs mapped back through their row, the slots of a
 //                          (frame, class) aligned to an anchor member, a weighted mean over windows and transforms
 //
-// window_batch is the copy of loader.hip's augmented gather with another address: tiles of 16 KB (256 lanes x 4 x 16
-// bytes, every load of a tile issued before its first store), a grid capped near 2048 workgroups.  Recording, window
-// and table row depend on blockIdx.y alone and stay on the scalar unit: the channel map packed 4 bits per channel, the
-// flips 2 bits per channel.  A lane needs (c, f, j) of its output offset (two unsigned divisions by uniform divisors per
-// 16 bytes); with T, hop and L multiples of 4 a float4 lies in one (c, f) row and wholly inside or wholly past L.
+// window_batch moves data as loader.hip's augmented gather does, with another address, and shares its tile geometry, the
+// packed channel map of a table row and flipop with it (channel_map.h).  Recording, window and table row depend on
+// blockIdx.y alone and stay on the scalar unit.  A lane needs (c, f, j) of its output offset (two unsigned divisions by
+// uniform divisors per 16 bytes); with T, hop and L multiples of 4 a float4 lies in one (c, f) row and wholly inside or
+// wholly past L.
 //
 // ensemble_combine is small (config 3 at K = 16: 14 MB of members per recording) and bound by latency and reads: one
 // thread per (recording, frame, class) walks the covering members in order, so neighbouring lanes read neighbouring
 // slots of one frame and every sum has one writer and one order.  A member's table row is the same for every lane:
 // scalar loads.  No LDS, no atomics.
-#include "common.h"
+#include "channel_map.h"
 
 namespace seld {
 
-constexpr int WIN_THREADS = 256;
-constexpr int WIN_VEC = 4;                                              // 16-byte accesses per lane and tile
-constexpr uint32_t WIN_TILE = (uint32_t)WIN_THREADS * WIN_VEC * 4;      // floats per tile
-constexpr int WIN_MAX_BLOCKS = 2048;
-constexpr int ENS_MAX_C = 16, ENS_MAX_K = 64, ENS_MAX_N = 64;
-constexpr float ENS_PI_F = (float)M_PI;
-
-// flipop of seld_gather_rows_aug
-__device__ __forceinline__ float ens_flip(float v, uint32_t flip) {
-    const float turned = v <= 0.f ? v + ENS_PI_F : v - ENS_PI_F;
-    return flip == 1u ? -v : flip == 2u ? turned : v;
-}
+constexpr int ENS_MAX_N = 64;
 
 struct WinParams {
     int C, F, L, T, hop, S, K;
@@ -39,7 +28,7 @@ struct WinParams {
 };
 
 // grid (gx, count): workgroup x of a row takes the tiles x, x + gx, ... of output row blockIdx.y
-__global__ __launch_bounds__(WIN_THREADS, 8) void window_batch_kernel(const float* __restrict__ x, float* __restrict__ out,
+__global__ __launch_bounds__(TILE_THREADS, 8) void window_batch_kernel(const float* __restrict__ x, float* __restrict__ out,
                                                                       const int32_t* __restrict__ table, WinParams a) {
     const int tid = threadIdx.x;
     const long long m = a.m0 + blockIdx.y;
@@ -56,60 +45,44 @@ __global__ __launch_bounds__(WIN_THREADS, 8) void window_batch_kernel(const floa
     const float* __restrict__ src = x + r * ((long long)a.C * a.F * a.L) + (live ? t0 : 0);
     float* __restrict__ dst = out + (long long)blockIdx.y * row;
 
-    // the row of the table before the first store of the kernel: scalar loads, unrolled with clamped indices
-    uint64_t src_map = 0xFEDCBA9876543210ull;
-    uint32_t flip_map = 0u;
-    if (a.K > 0) {
-        const int32_t* __restrict__ trow = table + (long long)k * (2 * a.C + 6);
-        uint32_t from[ENS_MAX_C], turn[ENS_MAX_C];
-#pragma unroll
-        for (int c = 0; c < ENS_MAX_C; ++c) {
-            const int cc = c < a.C ? c : 0;
-            from[c] = (uint32_t)trow[cc];
-            turn[c] = (uint32_t)trow[a.C + cc];
-        }
-        src_map = 0ull;
-#pragma unroll
-        for (int c = 0; c < ENS_MAX_C; ++c) {                           // a source outside [0, C): the channel itself
-            src_map |= (uint64_t)(from[c] < (uint32_t)a.C ? from[c] : (uint32_t)(c < a.C ? c : 0)) << (4 * c);
-            flip_map |= (turn[c] & 3u) << (2 * c);
-        }
-    }
+    // the row of the table before the first store of the kernel: scalar loads
+    ChannelMap map;
+    if (a.K > 0) map = load_channel_map(table + (long long)k * (2 * a.C + 6), a.C);
 
-    for (uint64_t off = (uint64_t)blockIdx.x * WIN_TILE; off < row; off += (uint64_t)gridDim.x * WIN_TILE) {
-        const uint32_t left = row - (uint32_t)off, len = left < WIN_TILE ? left : WIN_TILE;
+    for (uint64_t off = (uint64_t)blockIdx.x * TILE_FLOATS; off < row; off += (uint64_t)gridDim.x * TILE_FLOATS) {
+        const uint32_t left = row - (uint32_t)off, len = left < TILE_FLOATS ? left : TILE_FLOATS;
         if (a.vec) {                            // row and off are multiples of 4: so is len
             const int nv = (int)(len >> 2);
-            float4 v[WIN_VEC];
-            uint32_t flip[WIN_VEC];
+            float4 v[TILE_VEC];
+            uint32_t flip[TILE_VEC];
 #pragma unroll
-            for (int i = 0; i < WIN_VEC; ++i) {
-                const int e = tid + i * WIN_THREADS;
+            for (int i = 0; i < TILE_VEC; ++i) {
+                const int e = tid + i * TILE_THREADS;
                 const uint32_t o = (uint32_t)off + 4u * (uint32_t)(e < nv ? e : 0);
                 const uint32_t q = o / T, j = o - q * T, c = q / F, f = q - c * F;
-                const uint32_t sc = (uint32_t)(src_map >> (4u * c)) & 15u;
-                flip[i] = (flip_map >> (2u * c)) & 3u;
+                const uint32_t sc = map.source(c);
+                flip[i] = map.flip_of(c);
                 v[i] = (e < nv && j < live) ? *reinterpret_cast<const float4*>(src + (sc * FL + f * L + j))
                                             : make_float4(0.f, 0.f, 0.f, 0.f);
             }
 #pragma unroll
-            for (int i = 0; i < WIN_VEC; ++i) {
-                const int e = tid + i * WIN_THREADS;
+            for (int i = 0; i < TILE_VEC; ++i) {
+                const int e = tid + i * TILE_THREADS;
                 if (e >= nv) continue;
                 float4 w;
-                w.x = ens_flip(v[i].x, flip[i]);
-                w.y = ens_flip(v[i].y, flip[i]);
-                w.z = ens_flip(v[i].z, flip[i]);
-                w.w = ens_flip(v[i].w, flip[i]);
+                w.x = flipop(v[i].x, flip[i]);
+                w.y = flipop(v[i].y, flip[i]);
+                w.z = flipop(v[i].z, flip[i]);
+                w.w = flipop(v[i].w, flip[i]);
                 *reinterpret_cast<float4*>(dst + (uint32_t)off + 4u * (uint32_t)e) = w;
             }
         } else {
-            for (uint32_t i = tid; i < len; i += WIN_THREADS) {
+            for (uint32_t i = tid; i < len; i += TILE_THREADS) {
                 const uint32_t o = (uint32_t)off + i;
                 const uint32_t q = o / T, j = o - q * T, c = q / F, f = q - c * F;
-                const uint32_t sc = (uint32_t)(src_map >> (4u * c)) & 15u;
+                const uint32_t sc = map.source(c);
                 const float v = j < live ? src[sc * FL + f * L + j] : 0.f;
-                dst[o] = ens_flip(v, (flip_map >> (2u * c)) & 3u);
+                dst[o] = flipop(v, map.flip_of(c));
             }
         }
     }
@@ -306,19 +279,19 @@ using namespace seld;
 extern "C" int seld_window_batch(const float* x, int64_t R, int32_t C, int32_t F, int32_t L, int32_t T, int32_t hop, int32_t S,
                                  const int32_t* table, int32_t K, int64_t m0, int32_t B, int32_t count, float* out,
                                  void* stream) {
-    if (!x || !out || R <= 0 || C < 1 || C > ENS_MAX_C || F < 1 || L < 1 || T < 1 || hop < 1 || S < 1) return SELD_EINVAL;
+    if (!x || !out || R <= 0 || C < 1 || C > MAP_MAX_C || F < 1 || L < 1 || T < 1 || hop < 1 || S < 1) return SELD_EINVAL;
     if (B <= 0 || count <= 0 || count > B || count > 65535) return SELD_EINVAL;
-    if (K < 0 || K > ENS_MAX_K || (K > 0) != (table != nullptr)) return SELD_EINVAL;
+    if (K < 0 || K > MAP_MAX_K || (K > 0) != (table != nullptr)) return SELD_EINVAL;
     if ((long long)C * F * T >= (1ll << 31) || (long long)C * F * L >= (1ll << 31)) return SELD_EUNSUPPORTED;   // 32-bit offsets in a row
-    if (R > (1ll << 62) / S / ENS_MAX_K) return SELD_EUNSUPPORTED;
+    if (R > (1ll << 62) / S / MAP_MAX_K) return SELD_EUNSUPPORTED;
     const long long members = (long long)R * S * (K > 0 ? K : 1);
     if (m0 < 0 || m0 > members - count) return SELD_EINVAL;
     const long long row = (long long)C * F * T;
-    const long long tiles = (row + WIN_TILE - 1) / WIN_TILE, cap = WIN_MAX_BLOCKS / count > 0 ? WIN_MAX_BLOCKS / count : 1;
+    const long long tiles = (row + TILE_FLOATS - 1) / TILE_FLOATS, cap = TILE_MAX_BLOCKS / count > 0 ? TILE_MAX_BLOCKS / count : 1;
     const int gx = (int)(tiles < cap ? tiles : cap);
     const int vec = T % 4 == 0 && hop % 4 == 0 && L % 4 == 0 && (((uintptr_t)x | (uintptr_t)out) & 15) == 0;
     const WinParams a{C, F, L, T, hop, S, K, (long long)m0, vec};
-    hipLaunchKernelGGL(window_batch_kernel, dim3(gx, count), dim3(WIN_THREADS), 0, (hipStream_t)stream, x, out, table, a);
+    hipLaunchKernelGGL(window_batch_kernel, dim3(gx, count), dim3(TILE_THREADS), 0, (hipStream_t)stream, x, out, table, a);
     return check_launch();
 }
 
@@ -328,7 +301,7 @@ extern "C" int seld_ensemble_combine(const float* sed, const float* doa, int64_t
                                      int32_t* perm, void* stream) {
     if (!sed || !doa || !win || !out_sed || !out_doa) return SELD_EINVAL;
     if (R <= 0 || S < 1 || T_out < 1 || hop_out < 1 || frames < 1 || classes < 1 || overlaps < 1) return SELD_EINVAL;
-    if (K < 0 || K > ENS_MAX_K || (K > 0) != (table != nullptr) || (K > 0 && (C < 1 || C > ENS_MAX_C))) return SELD_EINVAL;
+    if (K < 0 || K > MAP_MAX_K || (K > 0) != (table != nullptr) || (K > 0 && (C < 1 || C > MAP_MAX_C))) return SELD_EINVAL;
     if (align != 0 && align != 1) return SELD_EINVAL;
     if ((long long)classes * overlaps > ENS_MAX_N) return SELD_EUNSUPPORTED;
     if (align && overlaps > 3) return SELD_EUNSUPPORTED;

@@ -12,23 +12,26 @@
 //   seld_epoch_step_end   running mean of the loss, cursor += 1 (the last launch of a step)
 //
 // The gather is an HBM-bound copy (config 3: 2 MB per predictor row, 67 MB per batch): a row is spread over many
-// workgroups in tiles of 16 KB (256 lanes x 4 x 16 bytes, all four loads issued before the first store), the grid is
-// capped near 2048 workgroups and strides over the tiles beyond that.  The loads of `cursor` and `index` depend on the
-// workgroup's coordinates only: the compiler keeps them on the scalar unit.  No LDS.
+// workgroups in tiles of 16 KB (channel_map.h has the geometry, shared with ensemble.hip), the grid is capped near 2048
+// workgroups and strides over the tiles beyond that.  No LDS.
 //
-// The augmented gather moves the same bytes.  What a sample draws (Philox words of its (seed, epoch, position)) and the
-// row of the transform table it picks depend on blockIdx.y only, so they are computed once per workgroup on the scalar
-// unit: the channel map packed 4 bits per channel, the flips 2 bits per channel, the mask bounds as four ranges.  A
-// lane then needs (c, f, t) of its output offset (two unsigned divisions by uniform divisors per 16 bytes), a shift
-// for its source channel and a few compares; with T % 4 == 0 a float4 never crosses a (c, f) row.
-#include "common.h"
+// How the four kernels are put together.  Each starts with the same preamble, `resolve_row`: which side, which tiles and
+// which resident row a workgroup has, from its coordinates, `cursor` and `index` alone, so the compiler keeps those loads
+// on the scalar unit.  Rows that nothing transforms (zero rows, targets of an untransformed sample, everything in
+// gather_rows_kernel) go through one copy loop, `plain_row`.  What a sample draws are Philox words of its
+// `sample_counter` (seed, epoch, position): they depend on blockIdx.y only and are computed once per workgroup on the
+// scalar unit, as are the mask bounds (four ranges) and, in the augmented gather, the channel map of the table row.
+// The two rotating kernels are ONE body, `rot_gather`, instantiated with the kind of tile that mixes: channel triples
+// (gather_rows_rot_kernel) or magnitude / phase groups with their statistics (gather_rows_polar_kernel); the draw of R,
+// the label rows, the masks, the pass tiles and the walk over "mixing tiles, then pass tiles" are the body's.
+//
+// Two things that look alike stay apart on purpose: the signed permutation of gather_rows_aug_kernel (labels sign * v,
+// channels moved and flipped) and the 3x3 matrix of the rotating kernels (fmaf(r2, z, fmaf(r1, y, r0 * x))).  A
+// permutation matrix through the fma chain gives another sign of zero and 0 * inf = NaN beside a non-finite neighbour;
+// include/seld_hip.h specifies each formula as it is.
+#include "channel_map.h"
 
 namespace seld {
-
-constexpr int GATHER_THREADS = 256;
-constexpr int GATHER_VEC = 4;                                           // 16-byte accesses per lane and tile
-constexpr long long GATHER_TILE = (long long)GATHER_THREADS * GATHER_VEC * 4;   // floats per tile
-constexpr int GATHER_MAX_BLOCKS = 2048;
 
 struct GatherSide {
     const float* all;   // (n_rows, row)
@@ -36,14 +39,14 @@ struct GatherSide {
     long long row;
 };
 
-// `len` <= GATHER_TILE floats from s to d (zeros when !valid; s is then not read).  16-byte accesses over the part where
+// `len` <= TILE_FLOATS floats from s to d (zeros when !valid; s is then not read).  16-byte accesses over the part where
 // source and destination are 16-byte aligned TOGETHER, single floats before and behind it; when the two are aligned
 // differently (a row length that is no multiple of 4 puts every other row there) the whole tile moves float by float.
 __device__ __forceinline__ void gather_tile(const float* __restrict__ s, float* __restrict__ d, int len, bool valid) {
     const int tid = threadIdx.x;
     const uintptr_t da = (uintptr_t)d, sa = valid ? (uintptr_t)s : (uintptr_t)d;
     if ((da ^ sa) & 15) {
-        for (int i = tid; i < len; i += GATHER_THREADS) d[i] = s[i];
+        for (int i = tid; i < len; i += TILE_THREADS) d[i] = s[i];
         return;
     }
     int head = (int)(((16 - (da & 15)) & 15) >> 2);
@@ -52,57 +55,82 @@ __device__ __forceinline__ void gather_tile(const float* __restrict__ s, float* 
     const int nv = (len - head) >> 2;
     const float4* __restrict__ s4 = reinterpret_cast<const float4*>(s + head);
     float4* __restrict__ d4 = reinterpret_cast<float4*>(d + head);
-    float4 v[GATHER_VEC];
+    float4 v[TILE_VEC];
 #pragma unroll
-    for (int k = 0; k < GATHER_VEC; ++k) {
-        const int i = tid + k * GATHER_THREADS;
+    for (int k = 0; k < TILE_VEC; ++k) {
+        const int i = tid + k * TILE_THREADS;
         v[k] = (valid && i < nv) ? s4[i] : make_float4(0.f, 0.f, 0.f, 0.f);
     }
 #pragma unroll
-    for (int k = 0; k < GATHER_VEC; ++k) {
-        const int i = tid + k * GATHER_THREADS;
+    for (int k = 0; k < TILE_VEC; ++k) {
+        const int i = tid + k * TILE_THREADS;
         if (i < nv) d4[i] = v[k];
     }
     const int done = head + 4 * nv;
     if (tid < len - done) d[done + tid] = valid ? s[done + tid] : 0.f;
 }
 
-// grid (gx + gy, count): workgroups [0, gx) of a row copy the predictors, the rest the targets
-__global__ __launch_bounds__(GATHER_THREADS) void gather_rows_kernel(GatherSide x, GatherSide y, int gx,
-                                                                     const int64_t* __restrict__ index, long long n_index,
-                                                                     long long n_rows, const int32_t* __restrict__ cursor,
-                                                                     long long stride, long long start) {
+// What a workgroup of the grid (gx + gy, count) has to do: workgroups [0, gx) of a row copy the predictors, the rest the
+// targets; a side's workgroup `first` takes the tiles first, first + step, ... of batch row blockIdx.y.
+struct GatherRow {
+    bool is_y, valid;           // valid: the position and its index exist; anything else is zero-filled, nothing is read
+    int first, step;
+    long long p, row;           // position in `index`; floats in a row of this side
+    const float* src;           // the resident row (dst when !valid)
+    float* dst;
+};
+
+// `index` and `cursor` are __restrict__ arguments of the kernels, and their loads depend on the workgroup's coordinates
+// only and precede every store: scalar loads.
+__device__ __forceinline__ GatherRow resolve_row(const GatherSide& x, const GatherSide& y, int gx, const int64_t* __restrict__ index,
+                                                 long long n_index, long long n_rows, const int32_t* __restrict__ cursor,
+                                                 long long stride, long long start) {
+    GatherRow w;
     const int b = blockIdx.y;
-    const bool is_y = (int)blockIdx.x >= gx;
-    const GatherSide sd = is_y ? y : x;
-    const int first = is_y ? (int)blockIdx.x - gx : (int)blockIdx.x;
-    const int step = is_y ? (int)gridDim.x - gx : gx;
-    const long long p = start + b + (cursor ? (long long)cursor[0] * stride : 0);
+    w.is_y = (int)blockIdx.x >= gx;
+    const GatherSide sd = w.is_y ? y : x;
+    w.first = w.is_y ? (int)blockIdx.x - gx : (int)blockIdx.x;
+    w.step = w.is_y ? (int)gridDim.x - gx : gx;
+    w.p = start + b + (cursor ? (long long)cursor[0] * stride : 0);
     long long r = -1;
-    if (p >= 0 && p < n_index) r = index[p];
-    const bool valid = r >= 0 && r < n_rows;        // anything else: the row is zero-filled, nothing is read
-    float* dst = sd.out + (long long)b * sd.row;
-    const float* src = valid ? sd.all + r * sd.row : dst;
-    for (long long off = (long long)first * GATHER_TILE; off < sd.row; off += (long long)step * GATHER_TILE) {
-        const long long left = sd.row - off;
-        gather_tile(src + off, dst + off, (int)(left < GATHER_TILE ? left : GATHER_TILE), valid);
+    if (w.p >= 0 && w.p < n_index) r = index[w.p];
+    w.valid = r >= 0 && r < n_rows;
+    w.row = sd.row;
+    w.dst = sd.out + (long long)b * sd.row;
+    w.src = w.valid ? sd.all + r * sd.row : w.dst;
+    return w;
+}
+
+// the tiles of a row that only moves (or is zero-filled); 64-bit offsets: the plain gather takes rows of 2^31 floats and more
+__device__ __forceinline__ void plain_row(const GatherRow& w) {
+    for (long long off = (long long)w.first * TILE_FLOATS; off < w.row; off += (long long)w.step * TILE_FLOATS) {
+        const long long left = w.row - off;
+        gather_tile(w.src + off, w.dst + off, (int)(left < TILE_FLOATS ? left : TILE_FLOATS), w.valid);
     }
 }
 
-// ---- augmented gather ------------------------------------------------------------------------------------------------
-constexpr int AUG_MAX_C = 16, AUG_MAX_K = 64;
-constexpr float PI_F = (float)M_PI;
+__global__ __launch_bounds__(TILE_THREADS) void gather_rows_kernel(GatherSide x, GatherSide y, int gx,
+                                                                   const int64_t* __restrict__ index, long long n_index,
+                                                                   long long n_rows, const int32_t* __restrict__ cursor,
+                                                                   long long stride, long long start) {
+    plain_row(resolve_row(x, y, gx, index, n_index, n_rows, cursor, stride, start));
+}
 
+// ---- what the three augmenting gathers share -----------------------------------------------------------------------------
 struct AugParams {
     int C, F, T;                // predictor row = (C, F, T)
     int n_sed;                  // target row = (T_out, [n_sed activity | n_sed * 3 location])
     uint64_t seed;
-    int K;                      // rows of the table (K, 2 * C + 6): src[C], flip[C], axis[3], sign[3]
-    float p_swap;
     int n_fmask, f_max, n_tmask, t_max;
     float fill;
     int vec;                    // T % 4 == 0 and both predictor arrays 16-byte aligned
 };
+
+// The Philox counter of the sample at position p: its draws are functions of (seed, epoch, p) alone; the two low bits
+// number the group of four words.  `epoch` is a __restrict__ argument of the kernels: a scalar load.
+__device__ __forceinline__ uint64_t sample_counter(const int32_t* __restrict__ epoch, long long p) {
+    return ((uint64_t)(uint32_t)epoch[0] << 34) | ((uint64_t)p << 2);
+}
 
 __device__ __forceinline__ uint32_t int_below(uint32_t w, uint32_t n) { return (uint32_t)(((uint64_t)w * n) >> 32); }
 
@@ -125,15 +153,13 @@ __device__ __forceinline__ MaskPair draw_masks(uint64_t counter, uint64_t seed, 
     return m;
 }
 
-__device__ __forceinline__ float aug_flip(float v, uint32_t flip) {
-    const float turned = v <= 0.f ? v + PI_F : v - PI_F;        // selects, no branches: the flip differs between lanes
-    return flip == 1u ? -v : flip == 2u ? turned : v;
-}
+// ---- augmented gather ------------------------------------------------------------------------------------------------
+// A lane needs (c, f, t) of its output offset (two unsigned divisions by uniform divisors per 16 bytes), a shift for its
+// source channel and a few compares; with T % 4 == 0 a float4 never crosses a (c, f) row.
 
 // what a workgroup needs of its sample's draws to place one predictor element
 struct AugX {
-    uint64_t src;           // 4 bits per output channel
-    uint32_t flip;          // 2 bits per output channel
+    ChannelMap map;
     MaskPair fm, tm;
     uint32_t F, T, FT;
     float fill;
@@ -143,129 +169,104 @@ struct AugX {
 __device__ __forceinline__ float aug_x_element(const float* __restrict__ s, uint32_t o, const AugX& a) {
     const uint32_t q = o / a.T, t = o - q * a.T, c = q / a.F, f = q - c * a.F;
     if (a.fm.hit(f) || a.tm.hit(t)) return a.fill;
-    const uint32_t sc = (uint32_t)(a.src >> (4u * c)) & 15u;
-    return aug_flip(s[o - c * a.FT + sc * a.FT], (a.flip >> (2u * c)) & 3u);
+    return flipop(s[o - c * a.FT + a.map.source(c) * a.FT], a.map.flip_of(c));
 }
 
-// `len` <= GATHER_TILE floats (a multiple of 4) at row offset `off` (a multiple of 4), rows 16-byte aligned, T % 4 == 0:
+// `len` <= TILE_FLOATS floats (a multiple of 4) at row offset `off` (a multiple of 4), rows 16-byte aligned, T % 4 == 0:
 // the four floats of an access share (c, f).  All loads of the tile are issued before its first store.
 __device__ __forceinline__ void aug_x_tile_vec(const float* __restrict__ s, float* __restrict__ d, uint32_t off, int len,
                                                const AugX& a) {
     const int tid = threadIdx.x, nv = len >> 2;
-    float4 v[GATHER_VEC];
-    uint32_t t0[GATHER_VEC], flip[GATHER_VEC];
-    bool whole[GATHER_VEC];
+    float4 v[TILE_VEC];
+    uint32_t t0[TILE_VEC], flip[TILE_VEC];
+    bool whole[TILE_VEC];
 #pragma unroll
-    for (int k = 0; k < GATHER_VEC; ++k) {
-        const int i = tid + k * GATHER_THREADS;
+    for (int k = 0; k < TILE_VEC; ++k) {
+        const int i = tid + k * TILE_THREADS;
         const uint32_t o = off + 4u * (uint32_t)(i < nv ? i : 0);       // a lane past the tile: any offset inside the row
         const uint32_t q = o / a.T, c = q / a.F, f = q - c * a.F;
         t0[k] = o - q * a.T;
-        flip[k] = (a.flip >> (2u * c)) & 3u;
+        flip[k] = a.map.flip_of(c);
         whole[k] = a.fm.hit(f);
-        const uint32_t sc = (uint32_t)(a.src >> (4u * c)) & 15u;
-        v[k] = (i < nv && !whole[k]) ? *reinterpret_cast<const float4*>(s + (o - c * a.FT + sc * a.FT))
+        v[k] = (i < nv && !whole[k]) ? *reinterpret_cast<const float4*>(s + (o - c * a.FT + a.map.source(c) * a.FT))
                                      : make_float4(a.fill, a.fill, a.fill, a.fill);
     }
 #pragma unroll
-    for (int k = 0; k < GATHER_VEC; ++k) {
-        const int i = tid + k * GATHER_THREADS;
+    for (int k = 0; k < TILE_VEC; ++k) {
+        const int i = tid + k * TILE_THREADS;
         if (i >= nv) continue;
         float4 r;
-        r.x = (whole[k] | a.tm.hit(t0[k])) ? a.fill : aug_flip(v[k].x, flip[k]);
-        r.y = (whole[k] | a.tm.hit(t0[k] + 1u)) ? a.fill : aug_flip(v[k].y, flip[k]);
-        r.z = (whole[k] | a.tm.hit(t0[k] + 2u)) ? a.fill : aug_flip(v[k].z, flip[k]);
-        r.w = (whole[k] | a.tm.hit(t0[k] + 3u)) ? a.fill : aug_flip(v[k].w, flip[k]);
+        r.x = (whole[k] | a.tm.hit(t0[k])) ? a.fill : flipop(v[k].x, flip[k]);
+        r.y = (whole[k] | a.tm.hit(t0[k] + 1u)) ? a.fill : flipop(v[k].y, flip[k]);
+        r.z = (whole[k] | a.tm.hit(t0[k] + 2u)) ? a.fill : flipop(v[k].z, flip[k]);
+        r.w = (whole[k] | a.tm.hit(t0[k] + 3u)) ? a.fill : flipop(v[k].w, flip[k]);
         *reinterpret_cast<float4*>(d + off + 4u * (uint32_t)i) = r;
     }
 }
 
-// grid (gx + gy, count) as gather_rows_kernel.  Everything up to the tile loops is uniform over the workgroup; `epoch`
-// and `table` are arguments of their own (not members of AugParams) so that they carry __restrict__ and their loads
-// stay on the scalar unit.
+// grid (gx + gy, count).  Everything up to the tile loops is uniform over the workgroup; `epoch` and `table` are
+// arguments of their own (not members of a struct) so that they carry __restrict__ and their loads stay on the scalar
+// unit.  K rows in the table (K, 2 * C + 6): src[C], flip[C], axis[3], sign[3].
 // 8 waves per SIMD as gather_rows_kernel has them (the second bound keeps the scalar registers of the draws under the limit).
-__global__ __launch_bounds__(GATHER_THREADS, 8) void gather_rows_aug_kernel(GatherSide x, GatherSide y, int gx,
-                                                                         const int64_t* __restrict__ index, long long n_index,
-                                                                         long long n_rows, const int32_t* __restrict__ cursor,
-                                                                         long long stride, long long start,
-                                                                         const int32_t* __restrict__ epoch,
-                                                                         const int32_t* __restrict__ table, AugParams a) {
-    const int b = blockIdx.y, tid = threadIdx.x;
-    const bool is_y = (int)blockIdx.x >= gx;
-    const GatherSide sd = is_y ? y : x;
-    const int first = is_y ? (int)blockIdx.x - gx : (int)blockIdx.x;
-    const int step = is_y ? (int)gridDim.x - gx : gx;
-    const long long p = start + b + (cursor ? (long long)cursor[0] * stride : 0);
-    long long r = -1;
-    if (p >= 0 && p < n_index) r = index[p];
-    const bool valid = r >= 0 && r < n_rows;
-    float* __restrict__ dst = sd.out + (long long)b * sd.row;
-    const float* __restrict__ src = valid ? sd.all + r * sd.row : dst;
-    const uint32_t row = (uint32_t)sd.row, first_off = (uint32_t)first * (uint32_t)GATHER_TILE;     // rows are below 2^31 floats
-    const uint64_t tile_step = (uint64_t)step * (uint64_t)GATHER_TILE;
+__global__ __launch_bounds__(TILE_THREADS, 8) void gather_rows_aug_kernel(GatherSide x, GatherSide y, int gx,
+                                                                       const int64_t* __restrict__ index, long long n_index,
+                                                                       long long n_rows, const int32_t* __restrict__ cursor,
+                                                                       long long stride, long long start,
+                                                                       const int32_t* __restrict__ epoch,
+                                                                       const int32_t* __restrict__ table, AugParams a, int K,
+                                                                       float p_swap) {
+    const GatherRow w = resolve_row(x, y, gx, index, n_index, n_rows, cursor, stride, start);
+    const int tid = threadIdx.x;
+    float* __restrict__ dst = w.dst;
+    const float* __restrict__ src = w.src;
+    const uint32_t row = (uint32_t)w.row, first_off = (uint32_t)w.first * TILE_FLOATS;      // rows are below 2^31 floats
+    const uint64_t tile_step = (uint64_t)w.step * (uint64_t)TILE_FLOATS;
 
-    // the draws of this sample: functions of (seed, epoch, p) alone
+    // the draws of this sample
     uint64_t counter = 0;
     bool swap = false;
     const int32_t* __restrict__ trow = table;
-    if (valid) {
-        counter = ((uint64_t)(uint32_t)epoch[0] << 34) | ((uint64_t)p << 2);
-        if (a.K > 0) {
-            const uint4 w = philox4x32_10(counter, a.seed);
-            swap = u01(w.y) < a.p_swap;
-            trow += (long long)int_below(w.x, (uint32_t)a.K) * (2 * a.C + 6);
+    if (w.valid) {
+        counter = sample_counter(epoch, w.p);
+        if (K > 0) {
+            const uint4 d = philox4x32_10(counter, a.seed);
+            swap = u01(d.y) < p_swap;
+            trow += (long long)int_below(d.x, (uint32_t)K) * (2 * a.C + 6);
         }
     }
 
-    // every load of the table comes before the first store of the kernel: the compiler then proves them unclobbered and
-    // issues scalar loads.  Unrolled with clamped indices, so that they go out together.
-    uint64_t src_map = 0xFEDCBA9876543210ull;
-    uint32_t flip_map = 0u;
+    // every load of the table comes before the first store of the kernel (scalar loads)
+    AugX ax;
     int ax0 = 0, ax1 = 1, ax2 = 2;
     float sg0 = 1.f, sg1 = 1.f, sg2 = 1.f;
-    if (swap && is_y) {
+    if (swap && w.is_y) {
         // the binding validates the table; an axis outside 0..2 still reads nothing outside its own triple
         const int32_t* __restrict__ la = trow + 2 * a.C;
         ax0 = (uint32_t)la[0] < 3u ? la[0] : 0, ax1 = (uint32_t)la[1] < 3u ? la[1] : 1, ax2 = (uint32_t)la[2] < 3u ? la[2] : 2;
         sg0 = (float)la[3], sg1 = (float)la[4], sg2 = (float)la[5];
     } else if (swap) {
-        uint32_t from[AUG_MAX_C], turn[AUG_MAX_C];
-#pragma unroll
-        for (int c = 0; c < AUG_MAX_C; ++c) {
-            const int cc = c < a.C ? c : 0;
-            from[c] = (uint32_t)trow[cc];
-            turn[c] = (uint32_t)trow[a.C + cc];
-        }
-        src_map = 0ull;
-#pragma unroll
-        for (int c = 0; c < AUG_MAX_C; ++c) {                                       // a source outside [0, C): the channel itself
-            src_map |= (uint64_t)(from[c] < (uint32_t)a.C ? from[c] : (uint32_t)(c < a.C ? c : 0)) << (4 * c);
-            flip_map |= (turn[c] & 3u) << (2 * c);
-        }
+        ax.map = load_channel_map(trow, a.C);
     }
 
-    if (!valid || (is_y && !swap)) {            // zero-fill, or targets that no transform touches: the plain tiles
-        for (uint64_t off = first_off; off < row; off += tile_step) {
-            const uint32_t left = row - (uint32_t)off;
-            gather_tile(src + off, dst + off, (int)(left < GATHER_TILE ? left : GATHER_TILE), valid);
-        }
+    if (!w.valid || (w.is_y && !swap)) {        // zero-fill, or targets that no transform touches
+        plain_row(w);
         return;
     }
 
-    if (is_y) {                                 // location (s, axis) <- sign[axis] * location (s, axis[axis]); activity copied
+    if (w.is_y) {                               // location (s, axis) <- sign[axis] * location (s, axis[axis]); activity copied
         const uint32_t n_sed = (uint32_t)a.n_sed, cols = 4u * n_sed;
         for (uint64_t off = first_off; off < row; off += tile_step) {
-            const uint32_t left = row - (uint32_t)off, len = left < GATHER_TILE ? left : (uint32_t)GATHER_TILE;
-            for (uint32_t i = tid; i < len; i += GATHER_THREADS) {
+            const uint32_t left = row - (uint32_t)off, len = left < TILE_FLOATS ? left : TILE_FLOATS;
+            for (uint32_t i = tid; i < len; i += TILE_THREADS) {
                 const uint32_t o = (uint32_t)off + i, j = o % cols;
                 float v;
                 if (j < n_sed) {
                     v = src[o];
                 } else {
-                    const uint32_t ax = (j - n_sed) % 3u;
-                    const int from = ax == 0u ? ax0 : ax == 1u ? ax1 : ax2;
-                    const float sg = ax == 0u ? sg0 : ax == 1u ? sg1 : sg2;
-                    v = sg * src[o - ax + (uint32_t)from];
+                    const uint32_t axis = (j - n_sed) % 3u;
+                    const int from = axis == 0u ? ax0 : axis == 1u ? ax1 : ax2;
+                    const float sg = axis == 0u ? sg0 : axis == 1u ? sg1 : sg2;
+                    v = sg * src[o - axis + (uint32_t)from];
                 }
                 dst[o] = v;
             }
@@ -273,9 +274,6 @@ __global__ __launch_bounds__(GATHER_THREADS, 8) void gather_rows_aug_kernel(Gath
         return;
     }
 
-    AugX ax;
-    ax.src = src_map;
-    ax.flip = flip_map;
     ax.fm = draw_masks(counter | 1u, a.seed, a.n_fmask, a.f_max, a.F);
     ax.tm = draw_masks(counter | 2u, a.seed, a.n_tmask, a.t_max, a.T);
     ax.F = (uint32_t)a.F;
@@ -283,38 +281,35 @@ __global__ __launch_bounds__(GATHER_THREADS, 8) void gather_rows_aug_kernel(Gath
     ax.FT = ax.F * ax.T;
     ax.fill = a.fill;
     for (uint64_t off = first_off; off < row; off += tile_step) {
-        const uint32_t left = row - (uint32_t)off, len = left < GATHER_TILE ? left : (uint32_t)GATHER_TILE;
+        const uint32_t left = row - (uint32_t)off, len = left < TILE_FLOATS ? left : TILE_FLOATS;
         if (a.vec) {
             aug_x_tile_vec(src, dst, (uint32_t)off, (int)len, ax);
         } else {
-            for (uint32_t i = tid; i < len; i += GATHER_THREADS) dst[(uint32_t)off + i] = aug_x_element(src, (uint32_t)off + i, ax);
+            for (uint32_t i = tid; i < len; i += TILE_THREADS) dst[(uint32_t)off + i] = aug_x_element(src, (uint32_t)off + i, ax);
         }
     }
 }
 
-// ---- gather with a rotation of the sound field -------------------------------------------------------------------------
-// Channels come in two kinds: the members of a triple (cx, cy, cz), the three components of one intensity vector, and
-// the others, which pass.  A predictor row is cut into ITEMS of 16 bytes (4 bytes on the scalar path): a triple item
-// is the same piece of its three channels, loaded, mixed by R and stored as three accesses; a pass item is one piece of
-// one channel.  Triple items are numbered first, in tiles of ROT_TILE_A (two per lane: six 16-byte loads in flight),
-// pass items behind them in tiles of ROT_TILE_B (four per lane, as the other gathers), so whether a tile mixes is
-// uniform over the workgroup.  A sample that draws no rotation has pass items only: it moves as bits.
-constexpr int ROT_MAX_TRIPLES = 5;
-constexpr int ROT_VEC_A = 2, ROT_VEC_B = GATHER_VEC;
-constexpr uint32_t ROT_TILE_A = GATHER_THREADS * ROT_VEC_A, ROT_TILE_B = GATHER_THREADS * ROT_VEC_B;     // items per tile
+// ---- gathers with a rotation of the sound field ---------------------------------------------------------------------------
+// Channels come in two kinds: the members of a SET that R mixes, and the others, which pass.  A set is a triple
+// (cx, cy, cz), the three components of one intensity vector (gather_rows_rot_kernel), or a group of six
+// (mx, my, mz, px, py, pz), magnitude and phase of the three directional channels of one microphone
+// (gather_rows_polar_kernel).  A predictor row is cut into ITEMS of 16 bytes (4 bytes on the scalar path): a set item is the
+// same piece of every channel of its set, loaded, mixed and stored as three or six accesses; a pass item is one piece of
+// one channel.  Set items are numbered first, in tiles of their kind (Triples, Groups below), pass items behind them in
+// tiles of ROT_TILE_B (four per lane, as the other gathers), so whether a tile mixes is uniform over the workgroup.  A
+// sample that draws no rotation has pass items only: it moves as bits.
+constexpr int ROT_MAX_TRIPLES = 5, POLAR_MAX_GROUPS = 2;
+constexpr int ROT_VEC_A = 2, ROT_VEC_B = TILE_VEC, POLAR_VEC = 1;
+constexpr uint32_t ROT_TILE_A = TILE_THREADS * ROT_VEC_A, ROT_TILE_B = TILE_THREADS * ROT_VEC_B,
+                   POLAR_TILE = TILE_THREADS * POLAR_VEC;              // items per tile
 
 struct RotParams {
-    int C, F, T;                // predictor row = (C, F, T)
-    int n_sed;                  // target row = (T_out, [n_sed activity | n_sed * 3 location])
-    uint64_t seed;
-    int n_triples, n_pass;
-    uint64_t triples;           // 4 bits per entry: cx, cy, cz of triple 0, of triple 1, ...
-    uint64_t pass;              // 4 bits per entry: the channels outside the triples, ascending
+    int n_sets, n_pass;
+    uint64_t sets;              // 4 bits per entry: the channels of set 0, of set 1, ...
+    uint64_t pass;              // 4 bits per entry: the channels outside the sets, ascending
     float p_rot;
     int mirror, zflip;
-    int n_fmask, f_max, n_tmask, t_max;
-    float fill;
-    int vec;                    // T % 4 == 0 and both predictor arrays 16-byte aligned
 };
 
 struct RotX {
@@ -322,6 +317,10 @@ struct RotX {
     MaskPair fm, tm;
     uint32_t T, FT, P;          // P: items per channel
     float fill;
+};
+
+struct PolarStats {
+    float mean_m, sd_m, mean_p, sd_p;
 };
 
 template <bool VEC> __device__ __forceinline__ float4 rot_load(const float* __restrict__ p) {
@@ -345,66 +344,147 @@ __device__ __forceinline__ float4 rot_masked(float4 v, bool whole, uint32_t t0, 
                        (whole | a.tm.hit(t0 + 2u)) ? a.fill : v.z, (whole | a.tm.hit(t0 + 3u)) ? a.fill : v.w);
 }
 
-// items [first, first + ROT_TILE_A) of the n triple items: item i is piece i % P of triple i / P
-template <bool VEC> __device__ __forceinline__ void rot_tile_triples(const float* __restrict__ s, float* __restrict__ d, uint32_t first,
-                                                                     uint32_t n, uint64_t triples, const RotX& a) {
-    constexpr uint32_t W = VEC ? 4u : 1u;
-    float4 vx[ROT_VEC_A], vy[ROT_VEC_A], vz[ROT_VEC_A];
-    uint32_t ox[ROT_VEC_A], oy[ROT_VEC_A], oz[ROT_VEC_A], t0[ROT_VEC_A];
-    bool whole[ROT_VEC_A];
+// item i of n (set items or pass items): piece i % P of unit i / P (a set, or an entry of `pass`); a lane past the end
+// looks at item 0 and neither loads nor stores
+struct RotItem {
+    uint32_t u, e, t0;          // the unit, the offset of the piece inside a channel, its first frame
+    bool whole, live;           // the frequency row is masked; i < n
+};
+template <bool VEC> __device__ __forceinline__ RotItem rot_item(uint32_t first, int k, uint32_t n, const RotX& a) {
+    const uint32_t i = first + threadIdx.x + (uint32_t)k * TILE_THREADS, ii = i < n ? i : 0u;
+    RotItem it;
+    it.u = ii / a.P;
+    it.e = (ii - it.u * a.P) * (VEC ? 4u : 1u);
+    const uint32_t f = it.e / a.T;
+    it.t0 = it.e - f * a.T;
+    it.whole = a.fm.hit(f);
+    it.live = i < n;
+    return it;
+}
+
+// The two kinds of tile that mix: items [first, first + TILE) of the n set items.
+
+// channel triples: two items per lane, six 16-byte loads in flight
+struct Triples {
+    static constexpr uint32_t TILE = ROT_TILE_A;
+    template <bool VEC, bool STATS>
+    static __device__ __forceinline__ void tile(const float* __restrict__ s, float* __restrict__ d, uint32_t first, uint32_t n,
+                                                uint64_t triples, const RotX& a, const PolarStats&) {
+        float4 vx[ROT_VEC_A], vy[ROT_VEC_A], vz[ROT_VEC_A];
+        uint32_t ox[ROT_VEC_A], oy[ROT_VEC_A], oz[ROT_VEC_A];
+        RotItem it[ROT_VEC_A];
 #pragma unroll
-    for (int k = 0; k < ROT_VEC_A; ++k) {
-        const uint32_t i = first + threadIdx.x + (uint32_t)k * GATHER_THREADS, ii = i < n ? i : 0u;    // a lane past the end: item 0
-        const uint32_t u = ii / a.P, e = (ii - u * a.P) * W, f = e / a.T;
-        const uint32_t m = (uint32_t)(triples >> (12u * u));
-        t0[k] = e - f * a.T;
-        whole[k] = a.fm.hit(f);
-        ox[k] = (m & 15u) * a.FT + e, oy[k] = ((m >> 4) & 15u) * a.FT + e, oz[k] = ((m >> 8) & 15u) * a.FT + e;
-        const bool load = i < n && !whole[k];
-        const float4 none = make_float4(0.f, 0.f, 0.f, 0.f);
-        vx[k] = load ? rot_load<VEC>(s + ox[k]) : none;
-        vy[k] = load ? rot_load<VEC>(s + oy[k]) : none;
-        vz[k] = load ? rot_load<VEC>(s + oz[k]) : none;
+        for (int k = 0; k < ROT_VEC_A; ++k) {
+            it[k] = rot_item<VEC>(first, k, n, a);
+            const uint32_t m = (uint32_t)(triples >> (12u * it[k].u));
+            ox[k] = (m & 15u) * a.FT + it[k].e, oy[k] = ((m >> 4) & 15u) * a.FT + it[k].e, oz[k] = ((m >> 8) & 15u) * a.FT + it[k].e;
+            const bool load = it[k].live && !it[k].whole;
+            const float4 none = make_float4(0.f, 0.f, 0.f, 0.f);
+            vx[k] = load ? rot_load<VEC>(s + ox[k]) : none;
+            vy[k] = load ? rot_load<VEC>(s + oy[k]) : none;
+            vz[k] = load ? rot_load<VEC>(s + oz[k]) : none;
+        }
+#pragma unroll
+        for (int k = 0; k < ROT_VEC_A; ++k) {
+            if (!it[k].live) continue;
+            rot_store<VEC>(d + ox[k], rot_masked(rot_mix4(a.r, vx[k], vy[k], vz[k]), it[k].whole, it[k].t0, a));
+            rot_store<VEC>(d + oy[k], rot_masked(rot_mix4(a.r + 3, vx[k], vy[k], vz[k]), it[k].whole, it[k].t0, a));
+            rot_store<VEC>(d + oz[k], rot_masked(rot_mix4(a.r + 6, vx[k], vy[k], vz[k]), it[k].whole, it[k].t0, a));
+        }
+    }
+};
+
+// Magnitude / phase groups.  A bin of the STFT is the complex number m e^(i phi) and the STFT is linear, so the rotation is
+// the real matrix R applied to the complex 3-vector of every (f, t): polar to Cartesian, mix, back.  With `stats` the
+// stored values are standardised, (value - mean) / sd per kind, and the kernel undoes and redoes that around the rotation.
+// One (f, t) of one group, in place: m[j], ph[j] (j = x, y, z) as stored -> as stored after the rotation
+template <bool STATS> __device__ __forceinline__ void polar_mix(const float* __restrict__ r, const PolarStats& st, float* m, float* ph) {
+#pragma clang fp contract(off)
+    float re[3], im[3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        const float mag = STATS ? fmaf(m[j], st.sd_m, st.mean_m) : m[j];
+        const float phi = STATS ? fmaf(ph[j], st.sd_p, st.mean_p) : ph[j];
+        float s, c;
+        sincosf(phi, &s, &c);
+        re[j] = mag * c;
+        im[j] = mag * s;
     }
 #pragma unroll
-    for (int k = 0; k < ROT_VEC_A; ++k) {
-        if (first + threadIdx.x + (uint32_t)k * GATHER_THREADS >= n) continue;
-        rot_store<VEC>(d + ox[k], rot_masked(rot_mix4(a.r, vx[k], vy[k], vz[k]), whole[k], t0[k], a));
-        rot_store<VEC>(d + oy[k], rot_masked(rot_mix4(a.r + 3, vx[k], vy[k], vz[k]), whole[k], t0[k], a));
-        rot_store<VEC>(d + oz[k], rot_masked(rot_mix4(a.r + 6, vx[k], vy[k], vz[k]), whole[k], t0[k], a));
+    for (int a = 0; a < 3; ++a) {
+        const float ra = rot_mix(r[3 * a], r[3 * a + 1], r[3 * a + 2], re[0], re[1], re[2]);
+        const float ia = rot_mix(r[3 * a], r[3 * a + 1], r[3 * a + 2], im[0], im[1], im[2]);
+        const float mag = sqrtf(fmaf(ia, ia, ra * ra)), phi = atan2f(ia, ra);
+        m[a] = STATS ? __fdiv_rn(mag - st.mean_m, st.sd_m) : mag;
+        ph[a] = STATS ? __fdiv_rn(phi - st.mean_p, st.sd_p) : phi;
     }
 }
+
+// one item per lane: six 16-byte loads in flight ahead of six stores
+struct Groups {
+    static constexpr uint32_t TILE = POLAR_TILE;
+    template <bool VEC, bool STATS>
+    static __device__ __forceinline__ void tile(const float* __restrict__ s, float* __restrict__ d, uint32_t first, uint32_t n,
+                                                uint64_t groups, const RotX& a, const PolarStats& st) {
+        float4 v[POLAR_VEC][6];
+        uint32_t o[POLAR_VEC][6];
+        RotItem it[POLAR_VEC];
+#pragma unroll
+        for (int k = 0; k < POLAR_VEC; ++k) {
+            it[k] = rot_item<VEC>(first, k, n, a);
+            const uint32_t g = (uint32_t)(groups >> (24u * it[k].u));
+            const bool load = it[k].live && !it[k].whole;
+#pragma unroll
+            for (int j = 0; j < 6; ++j) {
+                o[k][j] = ((g >> (4 * j)) & 15u) * a.FT + it[k].e;
+                v[k][j] = load ? rot_load<VEC>(s + o[k][j]) : make_float4(0.f, 0.f, 0.f, 0.f);
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < POLAR_VEC; ++k) {
+            if (!it[k].live) continue;
+            float* lane[6];
+#pragma unroll
+            for (int j = 0; j < 6; ++j) lane[j] = reinterpret_cast<float*>(&v[k][j]);
+#pragma unroll
+            for (int q = 0; q < (VEC ? 4 : 1); ++q) {
+                float m[3] = {lane[0][q], lane[1][q], lane[2][q]}, ph[3] = {lane[3][q], lane[4][q], lane[5][q]};
+                polar_mix<STATS>(a.r, st, m, ph);
+#pragma unroll
+                for (int j = 0; j < 3; ++j) lane[j][q] = m[j], lane[3 + j][q] = ph[j];
+            }
+#pragma unroll
+            for (int j = 0; j < 6; ++j) rot_store<VEC>(d + o[k][j], rot_masked(v[k][j], it[k].whole, it[k].t0, a));
+        }
+    }
+};
 
 // items [first, first + ROT_TILE_B) of the n pass items: item i is piece i % P of the channel in entry i / P of `pass`
 template <bool VEC> __device__ __forceinline__ void rot_tile_pass(const float* __restrict__ s, float* __restrict__ d, uint32_t first,
                                                                   uint32_t n, uint64_t pass, const RotX& a) {
-    constexpr uint32_t W = VEC ? 4u : 1u;
     float4 v[ROT_VEC_B];
-    uint32_t o[ROT_VEC_B], t0[ROT_VEC_B];
-    bool whole[ROT_VEC_B];
+    uint32_t o[ROT_VEC_B];
+    RotItem it[ROT_VEC_B];
 #pragma unroll
     for (int k = 0; k < ROT_VEC_B; ++k) {
-        const uint32_t i = first + threadIdx.x + (uint32_t)k * GATHER_THREADS, ii = i < n ? i : 0u;
-        const uint32_t u = ii / a.P, e = (ii - u * a.P) * W, f = e / a.T;
-        t0[k] = e - f * a.T;
-        whole[k] = a.fm.hit(f);
-        o[k] = ((uint32_t)(pass >> (4u * u)) & 15u) * a.FT + e;
-        v[k] = (i < n && !whole[k]) ? rot_load<VEC>(s + o[k]) : make_float4(0.f, 0.f, 0.f, 0.f);
+        it[k] = rot_item<VEC>(first, k, n, a);
+        o[k] = ((uint32_t)(pass >> (4u * it[k].u)) & 15u) * a.FT + it[k].e;
+        v[k] = (it[k].live && !it[k].whole) ? rot_load<VEC>(s + o[k]) : make_float4(0.f, 0.f, 0.f, 0.f);
     }
 #pragma unroll
     for (int k = 0; k < ROT_VEC_B; ++k) {
-        if (first + threadIdx.x + (uint32_t)k * GATHER_THREADS >= n) continue;
-        rot_store<VEC>(d + o[k], rot_masked(v[k], whole[k], t0[k], a));
+        if (!it[k].live) continue;
+        rot_store<VEC>(d + o[k], rot_masked(v[k], it[k].whole, it[k].t0, a));
     }
 }
 
-// the predictor row of one sample: tiles [first, ...) in steps of `step`, triple tiles before pass tiles
-template <bool VEC> __device__ __forceinline__ void rot_x_row(const float* __restrict__ s, float* __restrict__ d, uint32_t first,
-                                                              uint32_t step, uint32_t n_a, uint32_t n_b, uint64_t triples,
-                                                              uint64_t pass, const RotX& a) {
-    const uint32_t tiles_a = (n_a + ROT_TILE_A - 1u) / ROT_TILE_A, tiles_b = (n_b + ROT_TILE_B - 1u) / ROT_TILE_B;
+// the predictor row of one sample: tiles [first, ...) in steps of `step`, the tiles of the sets before the pass tiles
+template <class Kind, bool VEC, bool STATS>
+__device__ __forceinline__ void rot_x_row(const float* __restrict__ s, float* __restrict__ d, uint32_t first, uint32_t step, uint32_t n_a,
+                                          uint32_t n_b, uint64_t sets, uint64_t pass, const RotX& a, const PolarStats& st) {
+    const uint32_t tiles_a = (n_a + Kind::TILE - 1u) / Kind::TILE, tiles_b = (n_b + ROT_TILE_B - 1u) / ROT_TILE_B;
     for (uint32_t tile = first; tile < tiles_a + tiles_b; tile += step) {
-        if (tile < tiles_a) rot_tile_triples<VEC>(s, d, tile * ROT_TILE_A, n_a, triples, a);
+        if (tile < tiles_a) Kind::template tile<VEC, STATS>(s, d, tile * Kind::TILE, n_a, sets, a, st);
         else rot_tile_pass<VEC>(s, d, (tile - tiles_a) * ROT_TILE_B, n_b, pass, a);
     }
 }
@@ -418,7 +498,7 @@ __device__ __forceinline__ bool rot_draw(bool valid, long long p, int b, const i
     bool rotate = false;
     r[0] = 1.f, r[1] = 0.f, r[2] = 0.f, r[3] = 0.f, r[4] = 1.f, r[5] = 0.f, r[6] = 0.f, r[7] = 0.f, r[8] = 1.f;
     if (valid) {
-        counter = ((uint64_t)(uint32_t)epoch[0] << 34) | ((uint64_t)p << 2);
+        counter = sample_counter(epoch, p);
         if (matrices) {
             rotate = true;
             const float* __restrict__ m = matrices + 9ll * b;
@@ -443,10 +523,10 @@ __device__ __forceinline__ void rot_y_row(const float* __restrict__ src, float* 
     const float r00 = ax.r[0], r01 = ax.r[1], r02 = ax.r[2], r10 = ax.r[3], r11 = ax.r[4], r12 = ax.r[5], r20 = ax.r[6], r21 = ax.r[7],
                 r22 = ax.r[8];
     const uint32_t cols = 4u * n_sed;
-    const uint64_t tile_step = (uint64_t)step * (uint64_t)GATHER_TILE;
-    for (uint64_t off = (uint64_t)first * (uint64_t)GATHER_TILE; off < row; off += tile_step) {
-        const uint32_t left = row - (uint32_t)off, len = left < GATHER_TILE ? left : (uint32_t)GATHER_TILE;
-        for (uint32_t i = threadIdx.x; i < len; i += GATHER_THREADS) {
+    const uint64_t tile_step = (uint64_t)step * (uint64_t)TILE_FLOATS;
+    for (uint64_t off = (uint64_t)first * (uint64_t)TILE_FLOATS; off < row; off += tile_step) {
+        const uint32_t left = row - (uint32_t)off, len = left < TILE_FLOATS ? left : TILE_FLOATS;
+        for (uint32_t i = threadIdx.x; i < len; i += TILE_THREADS) {
             const uint32_t o = (uint32_t)off + i, j = o % cols;
             float v;
             if (j < n_sed) {
@@ -463,224 +543,73 @@ __device__ __forceinline__ void rot_y_row(const float* __restrict__ src, float* 
     }
 }
 
-// grid (gx + gy, count) as gather_rows_kernel.  Everything up to the tile loops is uniform over the workgroup: the draws,
-// the nine entries of R (computed, or loaded from `matrices` before the first store: scalar loads), the mask bounds.
-__global__ __launch_bounds__(GATHER_THREADS, 8) void gather_rows_rot_kernel(GatherSide x, GatherSide y, int gx,
+// The body of both rotating kernels after the preamble.  Everything up to the tile loops is uniform over the workgroup:
+// the draws, the nine entries of R (computed, or loaded from `matrices`), the four statistics (one load; nullptr where
+// the Kind has none), the mask bounds.  `epoch`, `matrices` and `stats` are __restrict__ arguments of the kernels and
+// are read before the first store: scalar loads.
+template <class Kind>
+__device__ __forceinline__ void rot_gather(const GatherRow& w, const int32_t* __restrict__ epoch, const float* __restrict__ matrices,
+                                           const float* __restrict__ stats, const AugParams& a, const RotParams& q) {
+    float* __restrict__ dst = w.dst;
+    const float* __restrict__ src = w.src;
+
+    // the draws of this sample; an explicit matrix takes their place
+    uint64_t counter = 0;
+    RotX ax;
+    const bool rotate = rot_draw(w.valid, w.p, blockIdx.y, epoch, matrices, a.seed, q.p_rot, q.mirror, q.zflip, counter, ax);
+    PolarStats st{0.f, 1.f, 0.f, 1.f};
+    if (stats && rotate && !w.is_y) st = PolarStats{stats[0], stats[1], stats[2], stats[3]};
+
+    if (!w.valid || (w.is_y && !rotate)) {      // zero-fill, or targets that no rotation touches
+        plain_row(w);
+        return;
+    }
+
+    if (w.is_y) {
+        rot_y_row(src, dst, (uint32_t)w.row, (uint32_t)w.first, (uint32_t)w.step, (uint32_t)a.n_sed, ax);   // rows are below 2^31 floats
+        return;
+    }
+
+    ax.fm = draw_masks(counter | 1u, a.seed, a.n_fmask, a.f_max, a.F);
+    ax.tm = draw_masks(counter | 2u, a.seed, a.n_tmask, a.t_max, a.T);
+    ax.T = (uint32_t)a.T;
+    ax.FT = (uint32_t)a.F * ax.T;
+    ax.P = a.vec ? ax.FT >> 2 : ax.FT;
+    ax.fill = a.fill;
+    const uint32_t first = (uint32_t)w.first, step = (uint32_t)w.step;
+    const uint32_t n_a = rotate ? (uint32_t)q.n_sets * ax.P : 0u;
+    const uint32_t n_b = (uint32_t)(rotate ? q.n_pass : a.C) * ax.P;
+    const uint64_t pass = rotate ? q.pass : 0xFEDCBA9876543210ull;
+    if (stats) {
+        if (a.vec) rot_x_row<Kind, true, true>(src, dst, first, step, n_a, n_b, q.sets, pass, ax, st);
+        else rot_x_row<Kind, false, true>(src, dst, first, step, n_a, n_b, q.sets, pass, ax, st);
+    } else {
+        if (a.vec) rot_x_row<Kind, true, false>(src, dst, first, step, n_a, n_b, q.sets, pass, ax, st);
+        else rot_x_row<Kind, false, false>(src, dst, first, step, n_a, n_b, q.sets, pass, ax, st);
+    }
+}
+
+// grid (gx + gy, count); 8 waves per SIMD as the other gathers
+__global__ __launch_bounds__(TILE_THREADS, 8) void gather_rows_rot_kernel(GatherSide x, GatherSide y, int gx,
+                                                                       const int64_t* __restrict__ index, long long n_index,
+                                                                       long long n_rows, const int32_t* __restrict__ cursor,
+                                                                       long long stride, long long start,
+                                                                       const int32_t* __restrict__ epoch,
+                                                                       const float* __restrict__ matrices, AugParams a, RotParams q) {
+    rot_gather<Triples>(resolve_row(x, y, gx, index, n_index, n_rows, cursor, stride, start), epoch, matrices, nullptr, a, q);
+}
+
+// grid (gx + gy, count).  sincosf (with its large-argument reduction) and atan2f, inlined three times each per position,
+// fill the registers: 108 VGPRs on gfx950, so the kernel is bounded to 4 waves per SIMD (under the 8 of the other gathers
+// it spills); a second item per lane would add 48 registers of data and drop to 3.
+__global__ __launch_bounds__(TILE_THREADS, 4) void gather_rows_polar_kernel(GatherSide x, GatherSide y, int gx,
                                                                          const int64_t* __restrict__ index, long long n_index,
                                                                          long long n_rows, const int32_t* __restrict__ cursor,
                                                                          long long stride, long long start,
                                                                          const int32_t* __restrict__ epoch,
-                                                                         const float* __restrict__ matrices, RotParams a) {
-    const int b = blockIdx.y;
-    const bool is_y = (int)blockIdx.x >= gx;
-    const GatherSide sd = is_y ? y : x;
-    const int first = is_y ? (int)blockIdx.x - gx : (int)blockIdx.x;
-    const int step = is_y ? (int)gridDim.x - gx : gx;
-    const long long p = start + b + (cursor ? (long long)cursor[0] * stride : 0);
-    long long r = -1;
-    if (p >= 0 && p < n_index) r = index[p];
-    const bool valid = r >= 0 && r < n_rows;
-    float* __restrict__ dst = sd.out + (long long)b * sd.row;
-    const float* __restrict__ src = valid ? sd.all + r * sd.row : dst;
-    const uint32_t row = (uint32_t)sd.row;                                  // rows are below 2^31 floats
-
-    // the draws of this sample: functions of (seed, epoch, p) alone; an explicit matrix takes their place
-    uint64_t counter = 0;
-    RotX ax;
-    const bool rotate = rot_draw(valid, p, b, epoch, matrices, a.seed, a.p_rot, a.mirror, a.zflip, counter, ax);
-
-    if (!valid || (is_y && !rotate)) {          // zero-fill, or targets that no rotation touches: the plain tiles
-        const uint64_t tile_step = (uint64_t)step * (uint64_t)GATHER_TILE;
-        for (uint64_t off = (uint64_t)first * (uint64_t)GATHER_TILE; off < row; off += tile_step) {
-            const uint32_t left = row - (uint32_t)off;
-            gather_tile(src + off, dst + off, (int)(left < GATHER_TILE ? left : GATHER_TILE), valid);
-        }
-        return;
-    }
-
-    if (is_y) {
-        rot_y_row(src, dst, row, (uint32_t)first, (uint32_t)step, (uint32_t)a.n_sed, ax);
-        return;
-    }
-
-    ax.fm = draw_masks(counter | 1u, a.seed, a.n_fmask, a.f_max, a.F);
-    ax.tm = draw_masks(counter | 2u, a.seed, a.n_tmask, a.t_max, a.T);
-    ax.T = (uint32_t)a.T;
-    ax.FT = (uint32_t)a.F * ax.T;
-    ax.P = a.vec ? ax.FT >> 2 : ax.FT;
-    ax.fill = a.fill;
-    const uint32_t n_a = rotate ? (uint32_t)a.n_triples * ax.P : 0u;
-    const uint32_t n_b = (uint32_t)(rotate ? a.n_pass : a.C) * ax.P;
-    const uint64_t pass = rotate ? a.pass : 0xFEDCBA9876543210ull;
-    if (a.vec) rot_x_row<true>(src, dst, (uint32_t)first, (uint32_t)step, n_a, n_b, a.triples, pass, ax);
-    else rot_x_row<false>(src, dst, (uint32_t)first, (uint32_t)step, n_a, n_b, a.triples, pass, ax);
-}
-
-// ---- gather with a rotation of the sound field, magnitude / phase predictors ----------------------------------------------
-// Channels come as GROUPS of six, (mx, my, mz, px, py, pz): magnitude and phase of the three directional channels of one
-// microphone.  A bin of the STFT is the complex number m e^(i phi) and the STFT is linear, so the rotation is the real
-// matrix R applied to the complex 3-vector of every (f, t): polar to Cartesian, mix, back.  With `stats` the stored values
-// are standardised, (value - mean) / sd per kind, and the kernel undoes and redoes that around the rotation.  Group
-// items are numbered before pass items as the triples of gather_rows_rot_kernel are, in tiles of POLAR_TILE: one item per
-// lane, six 16-byte loads in flight ahead of six stores.  sincosf (with its large-argument reduction) and atan2f, inlined
-// three times each per position, fill the registers: 108 VGPRs on gfx950, so the kernel is bounded to 4 waves per SIMD
-// (under the 8 of the other gathers it spills); a second item per lane would add 48 registers of data and drop to 3.
-// Pass tiles, the masks, the draws and the labels are gather_rows_rot_kernel's.
-constexpr int POLAR_MAX_GROUPS = 2;
-constexpr int POLAR_VEC = 1;
-constexpr uint32_t POLAR_TILE = GATHER_THREADS * POLAR_VEC;            // items per tile
-
-struct PolarParams {
-    int C, F, T;                // predictor row = (C, F, T)
-    int n_sed;                  // target row = (T_out, [n_sed activity | n_sed * 3 location])
-    uint64_t seed;
-    int n_groups, n_pass;
-    uint64_t groups;            // 4 bits per entry: mx, my, mz, px, py, pz of group 0, of group 1
-    uint64_t pass;              // 4 bits per entry: the channels outside the groups, ascending
-    float p_rot;
-    int mirror, zflip;
-    int n_fmask, f_max, n_tmask, t_max;
-    float fill;
-    int vec;                    // T % 4 == 0 and both predictor arrays 16-byte aligned
-};
-
-struct PolarStats {
-    float mean_m, sd_m, mean_p, sd_p;
-};
-
-// one (f, t) of one group, in place: m[j], ph[j] (j = x, y, z) as stored -> as stored after the rotation
-template <bool STATS> __device__ __forceinline__ void polar_mix(const float* __restrict__ r, const PolarStats& st, float* m, float* ph) {
-#pragma clang fp contract(off)
-    float re[3], im[3];
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        const float mag = STATS ? fmaf(m[j], st.sd_m, st.mean_m) : m[j];
-        const float phi = STATS ? fmaf(ph[j], st.sd_p, st.mean_p) : ph[j];
-        float s, c;
-        sincosf(phi, &s, &c);
-        re[j] = mag * c;
-        im[j] = mag * s;
-    }
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        const float ra = rot_mix(r[3 * a], r[3 * a + 1], r[3 * a + 2], re[0], re[1], re[2]);
-        const float ia = rot_mix(r[3 * a], r[3 * a + 1], r[3 * a + 2], im[0], im[1], im[2]);
-        const float mag = sqrtf(fmaf(ia, ia, ra * ra)), phi = atan2f(ia, ra);
-        m[a] = STATS ? __fdiv_rn(mag - st.mean_m, st.sd_m) : mag;
-        ph[a] = STATS ? __fdiv_rn(phi - st.mean_p, st.sd_p) : phi;
-    }
-}
-
-// items [first, first + POLAR_TILE) of the n group items: item i is piece i % P of group i / P
-template <bool VEC, bool STATS> __device__ __forceinline__ void polar_tile_groups(const float* __restrict__ s, float* __restrict__ d,
-                                                                                  uint32_t first, uint32_t n, uint64_t groups,
-                                                                                  const RotX& a, const PolarStats& st) {
-    constexpr uint32_t W = VEC ? 4u : 1u;
-    float4 v[POLAR_VEC][6];
-    uint32_t o[POLAR_VEC][6], t0[POLAR_VEC];
-    bool whole[POLAR_VEC];
-#pragma unroll
-    for (int k = 0; k < POLAR_VEC; ++k) {
-        const uint32_t i = first + threadIdx.x + (uint32_t)k * GATHER_THREADS, ii = i < n ? i : 0u;    // a lane past the end: item 0
-        const uint32_t u = ii / a.P, e = (ii - u * a.P) * W, f = e / a.T;
-        const uint32_t g = (uint32_t)(groups >> (24u * u));
-        t0[k] = e - f * a.T;
-        whole[k] = a.fm.hit(f);
-        const bool load = i < n && !whole[k];
-#pragma unroll
-        for (int j = 0; j < 6; ++j) {
-            o[k][j] = ((g >> (4 * j)) & 15u) * a.FT + e;
-            v[k][j] = load ? rot_load<VEC>(s + o[k][j]) : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < POLAR_VEC; ++k) {
-        if (first + threadIdx.x + (uint32_t)k * GATHER_THREADS >= n) continue;
-        float* lane[6];
-#pragma unroll
-        for (int j = 0; j < 6; ++j) lane[j] = reinterpret_cast<float*>(&v[k][j]);
-#pragma unroll
-        for (int q = 0; q < (int)W; ++q) {
-            float m[3] = {lane[0][q], lane[1][q], lane[2][q]}, ph[3] = {lane[3][q], lane[4][q], lane[5][q]};
-            polar_mix<STATS>(a.r, st, m, ph);
-#pragma unroll
-            for (int j = 0; j < 3; ++j) lane[j][q] = m[j], lane[3 + j][q] = ph[j];
-        }
-#pragma unroll
-        for (int j = 0; j < 6; ++j) rot_store<VEC>(d + o[k][j], rot_masked(v[k][j], whole[k], t0[k], a));
-    }
-}
-
-// the predictor row of one sample: tiles [first, ...) in steps of `step`, group tiles before pass tiles
-template <bool VEC, bool STATS> __device__ __forceinline__ void polar_x_row(const float* __restrict__ s, float* __restrict__ d,
-                                                                            uint32_t first, uint32_t step, uint32_t n_a, uint32_t n_b,
-                                                                            uint64_t groups, uint64_t pass, const RotX& a,
-                                                                            const PolarStats& st) {
-    const uint32_t tiles_a = (n_a + POLAR_TILE - 1u) / POLAR_TILE, tiles_b = (n_b + ROT_TILE_B - 1u) / ROT_TILE_B;
-    for (uint32_t tile = first; tile < tiles_a + tiles_b; tile += step) {
-        if (tile < tiles_a) polar_tile_groups<VEC, STATS>(s, d, tile * POLAR_TILE, n_a, groups, a, st);
-        else rot_tile_pass<VEC>(s, d, (tile - tiles_a) * ROT_TILE_B, n_b, pass, a);
-    }
-}
-
-// grid (gx + gy, count) as gather_rows_kernel.  Uniform over the workgroup as in gather_rows_rot_kernel; the four
-// statistics are loaded before the first store as well (one scalar load).
-__global__ __launch_bounds__(GATHER_THREADS, 4) void gather_rows_polar_kernel(GatherSide x, GatherSide y, int gx,
-                                                                           const int64_t* __restrict__ index, long long n_index,
-                                                                           long long n_rows, const int32_t* __restrict__ cursor,
-                                                                           long long stride, long long start,
-                                                                           const int32_t* __restrict__ epoch,
-                                                                           const float* __restrict__ matrices,
-                                                                           const float* __restrict__ stats, PolarParams a) {
-    const int b = blockIdx.y;
-    const bool is_y = (int)blockIdx.x >= gx;
-    const GatherSide sd = is_y ? y : x;
-    const int first = is_y ? (int)blockIdx.x - gx : (int)blockIdx.x;
-    const int step = is_y ? (int)gridDim.x - gx : gx;
-    const long long p = start + b + (cursor ? (long long)cursor[0] * stride : 0);
-    long long r = -1;
-    if (p >= 0 && p < n_index) r = index[p];
-    const bool valid = r >= 0 && r < n_rows;
-    float* __restrict__ dst = sd.out + (long long)b * sd.row;
-    const float* __restrict__ src = valid ? sd.all + r * sd.row : dst;
-    const uint32_t row = (uint32_t)sd.row;                                  // rows are below 2^31 floats
-
-    uint64_t counter = 0;
-    RotX ax;
-    const bool rotate = rot_draw(valid, p, b, epoch, matrices, a.seed, a.p_rot, a.mirror, a.zflip, counter, ax);
-    PolarStats st{0.f, 1.f, 0.f, 1.f};
-    if (stats && rotate && !is_y) st = PolarStats{stats[0], stats[1], stats[2], stats[3]};
-
-    if (!valid || (is_y && !rotate)) {          // zero-fill, or targets that no rotation touches: the plain tiles
-        const uint64_t tile_step = (uint64_t)step * (uint64_t)GATHER_TILE;
-        for (uint64_t off = (uint64_t)first * (uint64_t)GATHER_TILE; off < row; off += tile_step) {
-            const uint32_t left = row - (uint32_t)off;
-            gather_tile(src + off, dst + off, (int)(left < GATHER_TILE ? left : GATHER_TILE), valid);
-        }
-        return;
-    }
-
-    if (is_y) {
-        rot_y_row(src, dst, row, (uint32_t)first, (uint32_t)step, (uint32_t)a.n_sed, ax);
-        return;
-    }
-
-    ax.fm = draw_masks(counter | 1u, a.seed, a.n_fmask, a.f_max, a.F);
-    ax.tm = draw_masks(counter | 2u, a.seed, a.n_tmask, a.t_max, a.T);
-    ax.T = (uint32_t)a.T;
-    ax.FT = (uint32_t)a.F * ax.T;
-    ax.P = a.vec ? ax.FT >> 2 : ax.FT;
-    ax.fill = a.fill;
-    const uint32_t n_a = rotate ? (uint32_t)a.n_groups * ax.P : 0u;
-    const uint32_t n_b = (uint32_t)(rotate ? a.n_pass : a.C) * ax.P;
-    const uint64_t pass = rotate ? a.pass : 0xFEDCBA9876543210ull;
-    if (stats) {
-        if (a.vec) polar_x_row<true, true>(src, dst, (uint32_t)first, (uint32_t)step, n_a, n_b, a.groups, pass, ax, st);
-        else polar_x_row<false, true>(src, dst, (uint32_t)first, (uint32_t)step, n_a, n_b, a.groups, pass, ax, st);
-    } else {
-        if (a.vec) polar_x_row<true, false>(src, dst, (uint32_t)first, (uint32_t)step, n_a, n_b, a.groups, pass, ax, st);
-        else polar_x_row<false, false>(src, dst, (uint32_t)first, (uint32_t)step, n_a, n_b, a.groups, pass, ax, st);
-    }
+                                                                         const float* __restrict__ matrices,
+                                                                         const float* __restrict__ stats, AugParams a, RotParams q) {
+    rot_gather<Groups>(resolve_row(x, y, gx, index, n_index, n_rows, cursor, stride, start), epoch, matrices, stats, a, q);
 }
 
 // one thread: the epoch loop's running mean (train.main), `mean += (loss - mean) / (i + 1)` in fp32 with i the cursor,
@@ -698,39 +627,90 @@ __global__ void epoch_step_end_kernel(const float* __restrict__ loss, float* __r
 
 using namespace seld;
 
-extern "C" int seld_gather_rows(const float* x_all, int64_t row_x, float* out_x, const float* y_all, int64_t row_y,
-                                float* out_y, const int64_t* index, int64_t n_index, int64_t n_rows, const int32_t* cursor,
-                                int64_t cursor_stride, int64_t start, int32_t B, int32_t count, void* stream) {
-    const bool has_x = x_all || out_x, has_y = y_all || out_y;
-    if (!index || n_index <= 0 || n_rows <= 0 || B <= 0 || count <= 0 || count > B || count > 65535) return SELD_EINVAL;
-    if (!has_x && !has_y) return SELD_EINVAL;
-    if (has_x && (!x_all || !out_x || row_x <= 0)) return SELD_EINVAL;
-    if (has_y && (!y_all || !out_y || row_y <= 0)) return SELD_EINVAL;
-    if (cursor && cursor_stride < 0) return SELD_EINVAL;
-    const long long cap = GATHER_MAX_BLOCKS / count > 0 ? GATHER_MAX_BLOCKS / count : 1;
-    const long long tx = has_x ? (row_x + GATHER_TILE - 1) / GATHER_TILE : 0, ty = has_y ? (row_y + GATHER_TILE - 1) / GATHER_TILE : 0;
+// ---- host side ------------------------------------------------------------------------------------------------------------
+// the arguments every gather takes, in the order of the C ABI
+struct GatherArgs {
+    const float* x_all;
+    int64_t row_x;
+    float* out_x;
+    const float* y_all;
+    int64_t row_y;
+    float* out_y;
+    const int64_t* index;
+    int64_t n_index, n_rows;
+    const int32_t* cursor;
+    int64_t cursor_stride, start;
+    int32_t B, count;
+    bool has_x() const { return x_all || out_x; }
+    bool has_y() const { return y_all || out_y; }
+};
+
+// what all four entry points refuse (SELD_EINVAL)
+static bool gather_refused(const GatherArgs& g) {
+    if (!g.index || g.n_index <= 0 || g.n_rows <= 0 || g.B <= 0 || g.count <= 0 || g.count > g.B || g.count > 65535) return true;
+    if (!g.has_x() && !g.has_y()) return true;
+    if (g.has_x() && (!g.x_all || !g.out_x || g.row_x <= 0)) return true;
+    if (g.has_y() && (!g.y_all || !g.out_y || g.row_y <= 0)) return true;
+    return g.cursor && g.cursor_stride < 0;
+}
+
+// on top of it, what the augmenting entry points refuse (SELD_EINVAL) of the arguments they share
+static bool aug_gather_refused(const GatherArgs& g, const AugParams& a, int32_t y_cols, const int32_t* epoch) {
+    if (gather_refused(g) || g.n_index > (1ll << 32)) return true;
+    if (!epoch || a.C < 1 || a.C > MAP_MAX_C || a.F < 1 || a.T < 1) return true;
+    if (a.n_fmask < 0 || a.n_fmask > 2 || a.n_tmask < 0 || a.n_tmask > 2 || a.f_max < 0 || a.f_max > a.F || a.t_max < 0 || a.t_max > a.T)
+        return true;
+    if (g.has_x() && (long long)a.C * a.F * a.T != g.row_x) return true;            // 16 * 2^31 * 2^31 fits an int64
+    return g.has_y() && (y_cols < 4 || y_cols % 4 || g.row_y % y_cols);
+}
+
+// and what they do not support: offsets inside a row are 32-bit
+static bool long_rows(const GatherArgs& g) { return g.row_x >= (1ll << 31) || g.row_y >= (1ll << 31); }
+
+// the shared members of the augmenting kernels' parameters
+static AugParams aug_params(const GatherArgs& g, int32_t C, int32_t F, int32_t T, int32_t y_cols, uint64_t seed, int32_t n_fmask,
+                            int32_t f_max, int32_t n_tmask, int32_t t_max, float fill) {
+    const int vec = g.has_x() && T % 4 == 0 && (((uintptr_t)g.x_all | (uintptr_t)g.out_x) & 15) == 0;
+    return AugParams{C, F, T, g.has_y() && y_cols >= 4 ? y_cols / 4 : 0, seed, n_fmask, f_max, n_tmask, t_max, fill, vec};
+}
+
+static long long tiles_of(long long items, long long tile) { return (items + tile - 1) / tile; }
+
+// The launch plan of every gather: a predictor row of `tiles_x` tiles and a target row of row_y floats over the grid
+// (gx + gy, count), each side capped so that the grid stays near TILE_MAX_BLOCKS workgroups.  `tail`: what the kernel
+// takes behind the arguments all of them share.
+template <class Kernel, class... Tail>
+static int launch_gather(Kernel kernel, const GatherArgs& g, long long tiles_x, void* stream, Tail... tail) {
+    const long long cap = TILE_MAX_BLOCKS / g.count > 0 ? TILE_MAX_BLOCKS / g.count : 1;
+    const long long tx = g.has_x() ? tiles_x : 0, ty = g.has_y() ? tiles_of(g.row_y, TILE_FLOATS) : 0;
     const int gx = (int)(tx < cap ? tx : cap), gy = (int)(ty < cap ? ty : cap);
-    const GatherSide x{x_all, out_x, has_x ? (long long)row_x : 0}, y{y_all, out_y, has_y ? (long long)row_y : 0};
-    hipLaunchKernelGGL(gather_rows_kernel, dim3(gx + gy, count), dim3(GATHER_THREADS), 0, (hipStream_t)stream, x, y, gx, index,
-                       (long long)n_index, (long long)n_rows, cursor, (long long)cursor_stride, (long long)start);
+    const GatherSide x{g.x_all, g.out_x, g.has_x() ? (long long)g.row_x : 0}, y{g.y_all, g.out_y, g.has_y() ? (long long)g.row_y : 0};
+    hipLaunchKernelGGL(kernel, dim3(gx + gy, g.count), dim3(TILE_THREADS), 0, (hipStream_t)stream, x, y, gx, g.index, (long long)g.n_index,
+                       (long long)g.n_rows, g.cursor, (long long)g.cursor_stride, (long long)g.start, tail...);
     return check_launch();
 }
 
-// what seld_gather_rows_aug and seld_gather_rows_rot refuse (SELD_EINVAL) of the arguments they share
-static bool aug_gather_refused(const float* x_all, int64_t row_x, const float* out_x, const float* y_all, int64_t row_y,
-                               const float* out_y, const int64_t* index, int64_t n_index, int64_t n_rows, const int32_t* cursor,
-                               int64_t cursor_stride, int32_t B, int32_t count, int32_t C, int32_t F, int32_t T, int32_t y_cols,
-                               const int32_t* epoch, int32_t n_fmask, int32_t f_max, int32_t n_tmask, int32_t t_max) {
-    const bool has_x = x_all || out_x, has_y = y_all || out_y;
-    if (!index || n_index <= 0 || n_index > (1ll << 32) || n_rows <= 0 || B <= 0 || count <= 0 || count > B || count > 65535) return true;
-    if (!has_x && !has_y) return true;
-    if (has_x && (!x_all || !out_x || row_x <= 0)) return true;
-    if (has_y && (!y_all || !out_y || row_y <= 0)) return true;
-    if (cursor && cursor_stride < 0) return true;
-    if (!epoch || C < 1 || C > AUG_MAX_C || F < 1 || T < 1) return true;
-    if (n_fmask < 0 || n_fmask > 2 || n_tmask < 0 || n_tmask > 2 || f_max < 0 || f_max > F || t_max < 0 || t_max > T) return true;
-    if (has_x && (long long)C * F * T != row_x) return true;                        // 16 * 2^31 * 2^31 fits an int64
-    return has_y && (y_cols < 4 || y_cols % 4 || row_y % y_cols);
+extern "C" int seld_gather_rows(const float* x_all, int64_t row_x, float* out_x, const float* y_all, int64_t row_y,
+                                float* out_y, const int64_t* index, int64_t n_index, int64_t n_rows, const int32_t* cursor,
+                                int64_t cursor_stride, int64_t start, int32_t B, int32_t count, void* stream) {
+    const GatherArgs g{x_all, row_x, out_x, y_all, row_y, out_y, index, n_index, n_rows, cursor, cursor_stride, start, B, count};
+    if (gather_refused(g)) return SELD_EINVAL;
+    return launch_gather(gather_rows_kernel, g, tiles_of(row_x, TILE_FLOATS), stream);
+}
+
+extern "C" int seld_gather_rows_aug(const float* x_all, int64_t row_x, float* out_x, const float* y_all, int64_t row_y,
+                                    float* out_y, const int64_t* index, int64_t n_index, int64_t n_rows, const int32_t* cursor,
+                                    int64_t cursor_stride, int64_t start, int32_t B, int32_t count, int32_t C, int32_t F,
+                                    int32_t T, int32_t y_cols, const int32_t* epoch, uint64_t seed, const int32_t* table,
+                                    int32_t K, float p_swap, int32_t n_fmask, int32_t f_max, int32_t n_tmask, int32_t t_max,
+                                    float fill, void* stream) {
+    const GatherArgs g{x_all, row_x, out_x, y_all, row_y, out_y, index, n_index, n_rows, cursor, cursor_stride, start, B, count};
+    const AugParams a = aug_params(g, C, F, T, y_cols, seed, n_fmask, f_max, n_tmask, t_max, fill);
+    if (aug_gather_refused(g, a, y_cols, epoch)) return SELD_EINVAL;
+    if (K < 0 || K > MAP_MAX_K || (K > 0) != (table != nullptr)) return SELD_EINVAL;
+    if (!(p_swap >= 0.f && p_swap <= 1.f)) return SELD_EINVAL;                      // a NaN fails both
+    if (long_rows(g)) return SELD_EUNSUPPORTED;
+    return launch_gather(gather_rows_aug_kernel, g, tiles_of(row_x, TILE_FLOATS), stream, epoch, table, a, (int)K, p_swap);
 }
 
 // `n` (at most 15) channel entries packed 4 bits each: refused unless they are distinct, inside [0, C) and the bits above
@@ -750,28 +730,22 @@ static bool packed_channels_refused(uint64_t packed, int n, int C, uint64_t& pas
     return false;
 }
 
-extern "C" int seld_gather_rows_aug(const float* x_all, int64_t row_x, float* out_x, const float* y_all, int64_t row_y,
-                                    float* out_y, const int64_t* index, int64_t n_index, int64_t n_rows, const int32_t* cursor,
-                                    int64_t cursor_stride, int64_t start, int32_t B, int32_t count, int32_t C, int32_t F,
-                                    int32_t T, int32_t y_cols, const int32_t* epoch, uint64_t seed, const int32_t* table,
-                                    int32_t K, float p_swap, int32_t n_fmask, int32_t f_max, int32_t n_tmask, int32_t t_max,
-                                    float fill, void* stream) {
-    const bool has_x = x_all || out_x, has_y = y_all || out_y;
-    if (aug_gather_refused(x_all, row_x, out_x, y_all, row_y, out_y, index, n_index, n_rows, cursor, cursor_stride, B, count, C, F, T,
-                           y_cols, epoch, n_fmask, f_max, n_tmask, t_max))
-        return SELD_EINVAL;
-    if (K < 0 || K > AUG_MAX_K || (K > 0) != (table != nullptr)) return SELD_EINVAL;
-    if (!(p_swap >= 0.f && p_swap <= 1.f)) return SELD_EINVAL;                      // a NaN fails both
-    if (row_x >= (1ll << 31) || row_y >= (1ll << 31)) return SELD_EUNSUPPORTED;     // offsets inside a row are 32-bit
-    const long long cap = GATHER_MAX_BLOCKS / count > 0 ? GATHER_MAX_BLOCKS / count : 1;
-    const long long tx = has_x ? (row_x + GATHER_TILE - 1) / GATHER_TILE : 0, ty = has_y ? (row_y + GATHER_TILE - 1) / GATHER_TILE : 0;
-    const int gx = (int)(tx < cap ? tx : cap), gy = (int)(ty < cap ? ty : cap);
-    const GatherSide x{x_all, out_x, has_x ? (long long)row_x : 0}, y{y_all, out_y, has_y ? (long long)row_y : 0};
-    const int vec = has_x && T % 4 == 0 && (((uintptr_t)x_all | (uintptr_t)out_x) & 15) == 0;
-    const AugParams a{C, F, T, has_y ? y_cols / 4 : 0, seed, K, p_swap, n_fmask, f_max, n_tmask, t_max, fill, vec};
-    hipLaunchKernelGGL(gather_rows_aug_kernel, dim3(gx + gy, count), dim3(GATHER_THREADS), 0, (hipStream_t)stream, x, y, gx, index,
-                       (long long)n_index, (long long)n_rows, cursor, (long long)cursor_stride, (long long)start, epoch, table, a);
-    return check_launch();
+// What the two rotating entry points do alike, from the check of their sets on: `n_sets` sets (at most `max_sets`) of
+// `width` channels each, mixed in tiles of `tile` items.  The sets travel by value, so their content is checked here: the
+// kernel then indexes with them as they are.  The grid covers the larger of a rotated and an unrotated sample's tiling.
+template <class Kernel, class... Stats>
+static int launch_rotating(Kernel kernel, const GatherArgs& g, const AugParams& a, int32_t y_cols, const int32_t* epoch, uint64_t sets,
+                           int32_t n_sets, int max_sets, int width, uint32_t tile, float p_rot, int32_t mirror, int32_t zflip,
+                           const float* matrices, void* stream, Stats... stats) {
+    if (aug_gather_refused(g, a, y_cols, epoch)) return SELD_EINVAL;
+    if (n_sets < 1 || n_sets > max_sets || width * n_sets > a.C) return SELD_EINVAL;
+    if (!(p_rot >= 0.f && p_rot <= 1.f)) return SELD_EINVAL;                        // a NaN fails both
+    if (long_rows(g)) return SELD_EUNSUPPORTED;
+    RotParams q{n_sets, 0, sets, 0, p_rot, mirror != 0, zflip != 0};
+    if (packed_channels_refused(sets, width * n_sets, a.C, q.pass, q.n_pass)) return SELD_EINVAL;      // at most 60 bits are entries
+    const long long P = a.vec ? (long long)a.F * a.T / 4 : (long long)a.F * a.T;
+    const long long t_rot = tiles_of(n_sets * P, tile) + tiles_of(q.n_pass * P, ROT_TILE_B), t_plain = tiles_of(a.C * P, ROT_TILE_B);
+    return launch_gather(kernel, g, t_rot > t_plain ? t_rot : t_plain, stream, epoch, matrices, stats..., a, q);
 }
 
 extern "C" int seld_gather_rows_rot(const float* x_all, int64_t row_x, float* out_x, const float* y_all, int64_t row_y,
@@ -780,32 +754,10 @@ extern "C" int seld_gather_rows_rot(const float* x_all, int64_t row_x, float* ou
                                     int32_t T, int32_t y_cols, const int32_t* epoch, uint64_t seed, uint64_t triples,
                                     int32_t n_triples, float p_rot, int32_t rot_mirror, int32_t rot_zflip, const float* matrices,
                                     int32_t n_fmask, int32_t f_max, int32_t n_tmask, int32_t t_max, float fill, void* stream) {
-    const bool has_x = x_all || out_x, has_y = y_all || out_y;
-    if (aug_gather_refused(x_all, row_x, out_x, y_all, row_y, out_y, index, n_index, n_rows, cursor, cursor_stride, B, count, C, F, T,
-                           y_cols, epoch, n_fmask, f_max, n_tmask, t_max))
-        return SELD_EINVAL;
-    if (n_triples < 1 || n_triples > ROT_MAX_TRIPLES || 3 * n_triples > C) return SELD_EINVAL;
-    if (!(p_rot >= 0.f && p_rot <= 1.f)) return SELD_EINVAL;                        // a NaN fails both
-    if (row_x >= (1ll << 31) || row_y >= (1ll << 31)) return SELD_EUNSUPPORTED;     // offsets inside a row are 32-bit
-    // the triples travel by value, so their content is checked here: the kernel then indexes with them as they are
-    uint64_t pass = 0;
-    int n_pass = 0;
-    if (packed_channels_refused(triples, 3 * n_triples, C, pass, n_pass)) return SELD_EINVAL;      // at most 60 bits are entries
-    const int vec = has_x && T % 4 == 0 && (((uintptr_t)x_all | (uintptr_t)out_x) & 15) == 0;
-    // the grid of seld_gather_rows_aug over the tiles of this kernel: the larger of a rotated and an unrotated sample's
-    const long long P = has_x ? (vec ? (long long)F * T / 4 : (long long)F * T) : 0;
-    const long long cap = GATHER_MAX_BLOCKS / count > 0 ? GATHER_MAX_BLOCKS / count : 1;
-    const long long t_rot = (n_triples * P + ROT_TILE_A - 1) / ROT_TILE_A + (n_pass * P + ROT_TILE_B - 1) / ROT_TILE_B;
-    const long long t_plain = (C * P + ROT_TILE_B - 1) / ROT_TILE_B;
-    const long long tx = t_rot > t_plain ? t_rot : t_plain;
-    const long long ty = has_y ? (row_y + GATHER_TILE - 1) / GATHER_TILE : 0;
-    const int gx = (int)(tx < cap ? tx : cap), gy = (int)(ty < cap ? ty : cap);
-    const GatherSide x{x_all, out_x, has_x ? (long long)row_x : 0}, y{y_all, out_y, has_y ? (long long)row_y : 0};
-    const RotParams a{C, F, T, has_y ? y_cols / 4 : 0, seed, n_triples, n_pass, triples, pass, p_rot, rot_mirror != 0, rot_zflip != 0,
-                      n_fmask, f_max, n_tmask, t_max, fill, vec};
-    hipLaunchKernelGGL(gather_rows_rot_kernel, dim3(gx + gy, count), dim3(GATHER_THREADS), 0, (hipStream_t)stream, x, y, gx, index,
-                       (long long)n_index, (long long)n_rows, cursor, (long long)cursor_stride, (long long)start, epoch, matrices, a);
-    return check_launch();
+    const GatherArgs g{x_all, row_x, out_x, y_all, row_y, out_y, index, n_index, n_rows, cursor, cursor_stride, start, B, count};
+    const AugParams a = aug_params(g, C, F, T, y_cols, seed, n_fmask, f_max, n_tmask, t_max, fill);
+    return launch_rotating(gather_rows_rot_kernel, g, a, y_cols, epoch, triples, n_triples, ROT_MAX_TRIPLES, 3, ROT_TILE_A, p_rot,
+                           rot_mirror, rot_zflip, matrices, stream);
 }
 
 extern "C" int seld_gather_rows_polar(const float* x_all, int64_t row_x, float* out_x, const float* y_all, int64_t row_y,
@@ -815,33 +767,10 @@ extern "C" int seld_gather_rows_polar(const float* x_all, int64_t row_x, float* 
                                       int32_t n_groups, const float* stats, float p_rot, int32_t rot_mirror, int32_t rot_zflip,
                                       const float* matrices, int32_t n_fmask, int32_t f_max, int32_t n_tmask, int32_t t_max,
                                       float fill, void* stream) {
-    const bool has_x = x_all || out_x, has_y = y_all || out_y;
-    if (aug_gather_refused(x_all, row_x, out_x, y_all, row_y, out_y, index, n_index, n_rows, cursor, cursor_stride, B, count, C, F, T,
-                           y_cols, epoch, n_fmask, f_max, n_tmask, t_max))
-        return SELD_EINVAL;
-    if (n_groups < 1 || n_groups > POLAR_MAX_GROUPS || 6 * n_groups > C) return SELD_EINVAL;
-    if (!(p_rot >= 0.f && p_rot <= 1.f)) return SELD_EINVAL;                        // a NaN fails both
-    if (row_x >= (1ll << 31) || row_y >= (1ll << 31)) return SELD_EUNSUPPORTED;     // offsets inside a row are 32-bit
-    // the groups travel by value, so their content is checked here: the kernel then indexes with them as they are
-    uint64_t pass = 0;
-    int n_pass = 0;
-    if (packed_channels_refused(groups, 6 * n_groups, C, pass, n_pass)) return SELD_EINVAL;        // at most 48 bits are entries
-    const int vec = has_x && T % 4 == 0 && (((uintptr_t)x_all | (uintptr_t)out_x) & 15) == 0;
-    // the grid of seld_gather_rows_rot over the tiles of this kernel: the larger of a rotated and an unrotated sample's
-    const long long P = has_x ? (vec ? (long long)F * T / 4 : (long long)F * T) : 0;
-    const long long cap = GATHER_MAX_BLOCKS / count > 0 ? GATHER_MAX_BLOCKS / count : 1;
-    const long long t_rot = (n_groups * P + POLAR_TILE - 1) / POLAR_TILE + (n_pass * P + ROT_TILE_B - 1) / ROT_TILE_B;
-    const long long t_plain = (C * P + ROT_TILE_B - 1) / ROT_TILE_B;
-    const long long tx = t_rot > t_plain ? t_rot : t_plain;
-    const long long ty = has_y ? (row_y + GATHER_TILE - 1) / GATHER_TILE : 0;
-    const int gx = (int)(tx < cap ? tx : cap), gy = (int)(ty < cap ? ty : cap);
-    const GatherSide x{x_all, out_x, has_x ? (long long)row_x : 0}, y{y_all, out_y, has_y ? (long long)row_y : 0};
-    const PolarParams a{C, F, T, has_y ? y_cols / 4 : 0, seed, n_groups, n_pass, groups, pass, p_rot, rot_mirror != 0, rot_zflip != 0,
-                        n_fmask, f_max, n_tmask, t_max, fill, vec};
-    hipLaunchKernelGGL(gather_rows_polar_kernel, dim3(gx + gy, count), dim3(GATHER_THREADS), 0, (hipStream_t)stream, x, y, gx, index,
-                       (long long)n_index, (long long)n_rows, cursor, (long long)cursor_stride, (long long)start, epoch, matrices, stats,
-                       a);
-    return check_launch();
+    const GatherArgs g{x_all, row_x, out_x, y_all, row_y, out_y, index, n_index, n_rows, cursor, cursor_stride, start, B, count};
+    const AugParams a = aug_params(g, C, F, T, y_cols, seed, n_fmask, f_max, n_tmask, t_max, fill);
+    return launch_rotating(gather_rows_polar_kernel, g, a, y_cols, epoch, groups, n_groups, POLAR_MAX_GROUPS, 6, POLAR_TILE, p_rot,
+                           rot_mirror, rot_zflip, matrices, stream, stats);
 }
 
 extern "C" int seld_epoch_step_end(const float* loss, float* mean, int32_t* cursor, void* stream) {

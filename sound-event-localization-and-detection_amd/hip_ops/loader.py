@@ -3,6 +3,7 @@ with or without augmentation on the way (signed channel permutations of first-or
 frequency and time masks), the per-step running mean of the loss, and the epoch's sample order as torch's RandomSampler
 would draw it."""
 import dataclasses
+import functools
 import itertools
 import weakref
 
@@ -17,27 +18,30 @@ __all__ = ["gather_rows", "gather_rows_aug", "gather_rows_rot", "gather_rows_pol
 AUG_MAX_CHANNELS, AUG_MAX_TRANSFORMS, ROT_MAX_TRIPLES, POLAR_MAX_GROUPS = 16, 64, 5, 2
 
 
-def _rows(t, name):
-    """(tensor, row length) of a contiguous fp32 device array (rows, ...); None passes."""
+def _rows(t, what, name):
+    """(tensor, row length) of a contiguous fp32 device array (rows, ...); None passes.  The label of an error is put
+    together only when there is one: this runs at every fetch."""
     if t is None:
         return None, 0
-    if _req(t, name) is not t or t.dim() < 1:
-        raise L.SeldHipError(f"{name}: expected a contiguous array of rows, got {tuple(t.shape)} contiguous={t.is_contiguous()}")
+    if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.dim() >= 1):
+        _req(t, f"{what}: {name}")              # a host tensor or another dtype: its message
+        raise L.SeldHipError(f"{what}: {name}: expected a contiguous array of rows, got {tuple(t.shape)} contiguous={t.is_contiguous()}")
     return t, (t.numel() // t.shape[0] if t.shape[0] else 0)
 
 
-def _scalar(t, name, dtype):
+def _scalar(t, what, name, dtype):
     if not torch.is_tensor(t) or not t.is_cuda or t.dtype != dtype or t.numel() != 1:
-        raise L.SeldHipError(f"{name}: expected a device tensor of one {dtype} element")
+        raise L.SeldHipError(f"{what}: {name}: expected a device tensor of one {dtype} element")
     return t
 
 
-def _gather_args(what, x_all, y_all, index, out_x, out_y, cursor, count, stride):
-    """The checks both gathers make: (x_all, row_x, y_all, row_y, out_x, out_y, n_rows, device, B, count, stride)."""
-    x_all, row_x = _rows(x_all, f"{what}: x_all")
-    y_all, row_y = _rows(y_all, f"{what}: y_all")
-    out_x, orow_x = _rows(out_x, f"{what}: out_x")
-    out_y, orow_y = _rows(out_y, f"{what}: out_y")
+def _gather_args(what, x_all, y_all, index, out_x, out_y, cursor, start, count, stride):
+    """The checks every gather makes: (x_all, y_all, out_x, out_y, dev, count, bytes moved, lead), `lead` being the arguments
+    every entry point of the C ABI starts with."""
+    x_all, row_x = _rows(x_all, what, "x_all")
+    y_all, row_y = _rows(y_all, what, "y_all")
+    out_x, orow_x = _rows(out_x, what, "out_x")
+    out_y, orow_y = _rows(out_y, what, "out_y")
     if (x_all is None) != (out_x is None) or (y_all is None) != (out_y is None):
         raise L.SeldHipError(f"{what}: an array and its batch buffer are given together or not at all")
     arrays = [t for t in (x_all, y_all) if t is not None]
@@ -53,12 +57,23 @@ def _gather_args(what, x_all, y_all, index, out_x, out_y, cursor, count, stride)
     dev = arrays[0].device
     if any(t.device != dev for t in arrays + outs + [index]):
         raise L.SeldHipError(f"{what}: tensors on different devices")
-    if cursor is not None and _scalar(cursor, f"{what}: cursor", torch.int32).device != dev:
+    if cursor is not None and _scalar(cursor, what, "cursor", torch.int32).device != dev:
         raise L.SeldHipError(f"{what}: cursor on another device")
     B = outs[0].shape[0]
     count = B if count is None else int(count)
     stride = B if stride is None else int(stride)
-    return x_all, row_x, y_all, row_y, out_x, out_y, arrays[0].shape[0], dev, B, count, stride
+    lead = (L.ptr(x_all), row_x, L.ptr(out_x), L.ptr(y_all), row_y, L.ptr(out_y), L.ptr(index), index.numel(), arrays[0].shape[0],
+            L.ptr(cursor), stride, int(start), B, count)
+    return x_all, y_all, out_x, out_y, dev, count, float(8 * count * (row_x + row_y)), lead
+
+
+def _launch(what, g, own=()):
+    """seld_<what>(lead, own, stream) under the timer label <what>_kernel; returns the two batch buffers."""
+    _, _, out_x, out_y, dev, _, nbytes, lead = g
+    with torch.cuda.device(dev):
+        with timed(what + "_kernel", lambda: (0.0, nbytes)):
+            L.check(getattr(L.lib(), "seld_" + what)(*lead, *own, L.current_stream()), "seld_" + what)
+    return out_x, out_y
 
 
 def gather_rows(x_all, y_all, index, out_x, out_y, *, cursor=None, start=0, count=None, stride=None):
@@ -69,20 +84,21 @@ def gather_rows(x_all, y_all, index, out_x, out_y, *, cursor=None, start=0, coun
     int32 of one element, read by the kernel: the launch can be recorded and fetches another batch at every replay)
     p = cursor * stride + start; stride defaults to B.  count defaults to B; rows [count, B) of the buffers are left
     alone.  A position outside `index` or an index outside [0, n) zero-fills its rows."""
-    x_all, row_x, y_all, row_y, out_x, out_y, n_rows, dev, B, count, stride = _gather_args(
-        "gather_rows", x_all, y_all, index, out_x, out_y, cursor, count, stride)
-    with torch.cuda.device(dev):
-        with timed("gather_rows_kernel", lambda: (0.0, float(8 * count * (row_x + row_y)))):
-            L.check(L.lib().seld_gather_rows(L.ptr(x_all), row_x, L.ptr(out_x), L.ptr(y_all), row_y, L.ptr(out_y),
-                                             L.ptr(index), index.numel(), n_rows, L.ptr(cursor), stride,
-                                             int(start), B, count, L.current_stream()), "seld_gather_rows")
-    return out_x, out_y
+    return _launch("gather_rows", _gather_args("gather_rows", x_all, y_all, index, out_x, out_y, cursor, start, count, stride))
 
 
 _AXES = "XYZ"
-
-
 _LAYOUTS = ("magphase", "quaternion", "iv", "logpower_iv")
+
+
+def _axis_positions(what, order, mics):
+    """[position of X, of Y, of Z in a 4-channel block] after the checks every preset makes of `order` and `mics`."""
+    order = str(order).upper()
+    if sorted(order) != sorted("W" + _AXES):
+        raise L.SeldHipError(f"{what}: order must name W, X, Y and Z once each, got {order!r}")
+    if mics not in (1, 2):
+        raise L.SeldHipError(f"{what}: 1 or 2 microphones, got {mics}")
+    return [order.index(ch) for ch in _AXES]
 
 
 def _intensity_channels(what, order, mics, layout):
@@ -90,18 +106,14 @@ def _intensity_channels(what, order, mics, layout):
     share: `order` names a group [W, D1, D2, D3] as hip_ops.spatial_features reads it, so W comes first."""
     if layout not in _LAYOUTS:
         raise L.SeldHipError(f"{what}: layout is one of {', '.join(_LAYOUTS)}, got {layout!r}")
-    order = str(order).upper()
-    if sorted(order) != sorted("W" + _AXES):
-        raise L.SeldHipError(f"{what}: order must name W, X, Y and Z once each, got {order!r}")
-    if mics not in (1, 2):
-        raise L.SeldHipError(f"{what}: 1 or 2 microphones, got {mics}")
-    if order[0] != "W":
-        raise L.SeldHipError(f"{what}: the {layout} layout is made of groups [W, D1, D2, D3]: order starts with W, got {order!r}")
-    comp = [order.index(ch) - 1 for ch in _AXES]            # which of I1, I2, I3 is the component along axis a
+    pos = _axis_positions(what, order, mics)
+    if 0 in pos:
+        raise L.SeldHipError(f"{what}: the {layout} layout is made of groups [W, D1, D2, D3]: order starts with W, "
+                             f"got {str(order).upper()!r}")
     if layout == "quaternion":
-        return [[4 * g + 1 + comp[a] for a in range(3)] for g in range(mics)]
+        return [[4 * g + p for p in pos] for g in range(mics)]
     base = 4 * mics if layout == "logpower_iv" else 0
-    return [[base + 3 * g + comp[a] for a in range(3)] for g in range(mics)]
+    return [[base + 3 * g + p - 1 for p in pos] for g in range(mics)]   # which of I1, I2, I3 is the component along an axis
 
 
 def foa_triples(order="WYZX", mics=1, layout="quaternion"):
@@ -121,13 +133,8 @@ def foa_polar(order="WYZX", mics=1):
     [magnitude mic A | magnitude mic B | phase mic A | phase mic B] (C = 8 * mics: what `foa_transforms(phase=True)` and
     train.normalize_dataset assume): magnitude and phase channel of the x, y and z axis, one group per microphone.
     `order` names the channels of a 4-channel block; W may sit anywhere in it and is in no group (it is copied)."""
-    order = str(order).upper()
-    if sorted(order) != sorted("W" + _AXES):
-        raise L.SeldHipError(f"foa_polar: order must name W, X, Y and Z once each, got {order!r}")
-    if mics not in (1, 2):
-        raise L.SeldHipError(f"foa_polar: 1 or 2 microphones, got {mics}")
-    pos = [order.index(ch) for ch in _AXES]
-    return [tuple(4 * g + pos[a] for a in range(3)) + tuple(4 * (mics + g) + pos[a] for a in range(3)) for g in range(mics)]
+    pos = _axis_positions("foa_polar", order, mics)
+    return [tuple(4 * g + p for p in pos) + tuple(4 * (mics + g) + p for p in pos) for g in range(mics)]
 
 
 def foa_transforms(order="WYZX", mics=1, phase=False, elevation=True, layout="magphase"):
@@ -154,41 +161,28 @@ def foa_transforms(order="WYZX", mics=1, phase=False, elevation=True, layout="ma
       'logpower_iv'  C = 7 * mics, the 4 * mics log-power planes, then the intensity planes group by group
     An intensity component is a signed quantity: its channel gets flip 1 (negate) where the sign is -1.  Log-power
     planes are permuted like magnitudes, flip 0."""
-    if layout != "magphase":
-        iv = _intensity_channels("foa_transforms", order, mics, layout)
+    # what a row moves: (the channels of the x, y, z axis, the flip of one whose sign is -1)
+    if layout == "magphase":
+        pos = _axis_positions("foa_transforms", order, mics)
+        blocks = mics * (2 if phase else 1)
+        C = 4 * blocks
+        moved = [([4 * blk + p for p in pos], 2 if blk >= mics else 0) for blk in range(blocks)]     # blocks >= mics hold phases
+    else:
+        moved = [(t, 1) for t in _intensity_channels("foa_transforms", order, mics, layout)]
         if phase:
             raise L.SeldHipError(f"foa_transforms: the {layout!r} layout has no phase channels")
-        pos = [str(order).upper().index(ch) for ch in _AXES]
         C = {"quaternion": 4, "iv": 3, "logpower_iv": 7}[layout] * mics
-        rows = []
-        for swap, sz, sy, sx in itertools.product((False, True), (1, -1) if elevation else (1,), (1, -1), (1, -1)):
-            axis, sign = ([1, 0, 2] if swap else [0, 1, 2]), [sx, sy, sz]
-            src, flip = list(range(C)), [0] * C
-            for g in range(mics):
-                for a in range(3):
-                    src[iv[g][a]] = iv[g][axis[a]]
-                    flip[iv[g][a]] = 1 if sign[a] < 0 else 0
-                    if layout == "logpower_iv":
-                        src[4 * g + pos[a]] = 4 * g + pos[axis[a]]
-            rows.append(src + flip + axis + sign)
-        return np.asarray(rows, dtype=np.int32)
-    order = str(order).upper()
-    if sorted(order) != sorted("W" + _AXES):
-        raise L.SeldHipError(f"foa_transforms: order must name W, X, Y and Z once each, got {order!r}")
-    if mics not in (1, 2):
-        raise L.SeldHipError(f"foa_transforms: 1 or 2 microphones, got {mics}")
-    pos = [order.index(ch) for ch in _AXES]                 # channel of axis a inside a block
-    blocks = mics * (2 if phase else 1)
-    C = 4 * blocks
+        if layout == "logpower_iv":
+            pos = _axis_positions("foa_transforms", order, mics)
+            moved += [([4 * g + p for p in pos], 0) for g in range(mics)]
     rows = []
     for swap, sz, sy, sx in itertools.product((False, True), (1, -1) if elevation else (1,), (1, -1), (1, -1)):
         axis, sign = ([1, 0, 2] if swap else [0, 1, 2]), [sx, sy, sz]
         src, flip = list(range(C)), [0] * C
-        for blk in range(blocks):
+        for chans, turned in moved:
             for a in range(3):
-                src[4 * blk + pos[a]] = 4 * blk + pos[axis[a]]
-                if blk >= mics and sign[a] < 0:             # a phase block
-                    flip[4 * blk + pos[a]] = 2
+                src[chans[a]] = chans[axis[a]]
+                flip[chans[a]] = turned if sign[a] < 0 else 0
         rows.append(src + flip + axis + sign)
     return np.asarray(rows, dtype=np.int32)
 
@@ -216,29 +210,30 @@ def _check_table(table, channels):
     return np.ascontiguousarray(t, dtype=np.int32)
 
 
-def _check_triples(triples):
-    """((cx, cy, cz), ...) of 1..5 channel triples; raises SeldHipError unless they are distinct channels in [0, 16)."""
-    t = np.asarray(triples.cpu() if torch.is_tensor(triples) else triples)
-    if t.ndim != 2 or t.shape[1] != 3 or not 1 <= t.shape[0] <= ROT_MAX_TRIPLES or not np.issubdtype(t.dtype, np.integer):
-        raise L.SeldHipError(f"Augment: rot_triples must be 1..{ROT_MAX_TRIPLES} integer triples (cx, cy, cz), got {t.dtype} {t.shape}")
+def _check_channel_sets(sets, name, width, max_sets):
+    """((c, ...), ...) of 1..max_sets channel sets of `width` entries each, the value of the Augment field `name`; raises
+    SeldHipError unless they are distinct channels in [0, 16)."""
+    kind = {3: "triples (cx, cy, cz)", 6: "groups (mx, my, mz, px, py, pz)"}[width]
+    t = np.asarray(sets.cpu() if torch.is_tensor(sets) else sets)
+    if t.ndim != 2 or t.shape[1] != width or not 1 <= t.shape[0] <= max_sets or not np.issubdtype(t.dtype, np.integer):
+        raise L.SeldHipError(f"Augment: {name} must be 1..{max_sets} integer {kind}, got {t.dtype} {t.shape}")
     if t.min() < 0 or t.max() >= AUG_MAX_CHANNELS:
-        raise L.SeldHipError(f"Augment: a rot_triples channel outside [0, {AUG_MAX_CHANNELS})")
+        raise L.SeldHipError(f"Augment: a {name} channel outside [0, {AUG_MAX_CHANNELS})")
     if len(set(t.ravel().tolist())) != t.size:
-        raise L.SeldHipError("Augment: a channel appears twice in rot_triples")
+        raise L.SeldHipError(f"Augment: a channel appears twice in {name}")
     return tuple(tuple(int(c) for c in row) for row in t)
 
 
-def _check_polar(groups):
-    """((mx, my, mz, px, py, pz), ...) of 1..2 channel groups; raises SeldHipError unless they are distinct channels in [0, 16)."""
-    t = np.asarray(groups.cpu() if torch.is_tensor(groups) else groups)
-    if t.ndim != 2 or t.shape[1] != 6 or not 1 <= t.shape[0] <= POLAR_MAX_GROUPS or not np.issubdtype(t.dtype, np.integer):
-        raise L.SeldHipError(f"Augment: rot_polar must be 1..{POLAR_MAX_GROUPS} integer groups (mx, my, mz, px, py, pz), "
-                             f"got {t.dtype} {t.shape}")
-    if t.min() < 0 or t.max() >= AUG_MAX_CHANNELS:
-        raise L.SeldHipError(f"Augment: a rot_polar channel outside [0, {AUG_MAX_CHANNELS})")
-    if len(set(t.ravel().tolist())) != t.size:
-        raise L.SeldHipError("Augment: a channel appears twice in rot_polar")
-    return tuple(tuple(int(c) for c in row) for row in t)
+@functools.lru_cache(maxsize=None)
+def _least_channels(sets):
+    """The least number of channels the sets need, None without sets."""
+    return None if sets is None else 1 + max(max(s) for s in sets)
+
+
+@functools.lru_cache(maxsize=None)
+def _packed(sets):
+    """Channel sets as the C ABI takes them: 4 bits per entry."""
+    return sum(c << (4 * i) for i, c in enumerate(c for s in sets for c in s))
 
 
 @dataclasses.dataclass(frozen=True)
@@ -285,10 +280,9 @@ class Augment:
             raise L.SeldHipError("Augment: a negative mask width")
         if not 0.0 <= float(self.p_rot) <= 1.0:
             raise L.SeldHipError(f"Augment: p_rot {self.p_rot} is no probability")
-        if self.rot_triples is not None:
-            object.__setattr__(self, "rot_triples", _check_triples(self.rot_triples))
-        if self.rot_polar is not None:
-            object.__setattr__(self, "rot_polar", _check_polar(self.rot_polar))
+        for name, width, max_sets in (("rot_triples", 3, ROT_MAX_TRIPLES), ("rot_polar", 6, POLAR_MAX_GROUPS)):
+            if getattr(self, name) is not None:
+                object.__setattr__(self, name, _check_channel_sets(getattr(self, name), name, width, max_sets))
         if float(self.p_rot) > 0.0 and self.rot_triples is None and self.rot_polar is None:
             raise L.SeldHipError("Augment: p_rot > 0 needs rot_triples, the channels of the intensity vectors, or rot_polar, "
                                  "the magnitude and phase channels")
@@ -299,26 +293,32 @@ class Augment:
         object.__setattr__(self, "table", None if host is None else torch.from_numpy(host).to(self.device))
 
     @property
+    def kind(self):
+        """Which gather a loader fetches with: 'polar' (gather_rows_polar) or 'rot' (gather_rows_rot) when p_rot > 0, by the
+        channel sets given; otherwise 'swap' (gather_rows_aug: table and masks)."""
+        if float(self.p_rot) > 0.0:
+            return "polar" if self.rot_polar is not None else "rot"
+        return "swap"
+
+    @property
     def rot_channels(self):
         """The least number of channels the triples need, None without triples."""
-        return None if self.rot_triples is None else 1 + max(max(t) for t in self.rot_triples)
+        return _least_channels(self.rot_triples)
 
     @property
     def rot_packed(self):
         """The triples as seld_gather_rows_rot takes them: 4 bits per entry."""
-        flat = [c for t in self.rot_triples for c in t]
-        return sum(c << (4 * i) for i, c in enumerate(flat))
+        return _packed(self.rot_triples)
 
     @property
     def polar_channels(self):
         """The least number of channels the groups need, None without groups."""
-        return None if self.rot_polar is None else 1 + max(max(g) for g in self.rot_polar)
+        return _least_channels(self.rot_polar)
 
     @property
     def polar_packed(self):
         """The groups as seld_gather_rows_polar takes them: 4 bits per entry."""
-        flat = [c for g in self.rot_polar for c in g]
-        return sum(c << (4 * i) for i, c in enumerate(flat))
+        return _packed(self.rot_polar)
 
     @property
     def channels(self):
@@ -329,69 +329,62 @@ class Augment:
         return 0 if self.table is None else self.table.shape[0]
 
 
-def gather_rows_aug(x_all, y_all, index, out_x, out_y, *, epoch, seed, augment, cursor=None, start=0, count=None, stride=None):
-    """`gather_rows` with `augment` (an Augment) applied to every sample on the way, in ONE launch
-    (seld_gather_rows_aug).  x_all (n, C, F, T) and y_all (n, T_out, 4 * n_sed) name the geometry.  epoch: a device int32
-    of one element, read by the kernel; seed: the key of the draws, which depend on (seed, epoch, position in `index`)
-    and nothing else.  Rows of invalid positions or indices are zero-filled and not augmented."""
-    what = "gather_rows_aug"
+def _launch_aug(what, gather, epoch, seed, augment, field, own, matrices=None, stats=None):
+    """What the three augmenting gathers do alike.  The checks of `_gather_args` (`gather`: its arguments behind `what`), of
+    `augment`, `epoch` and the geometry: predictors (n, C, F, T), targets (n, ..., 4 * n_sed).  `field` names the channel
+    sets of a rotating gather, which must be there and fit into C (None: the table, which must be for C channels);
+    without predictors C is what the sets or the table need.  `matrices` and `stats` as the rotating entry points read
+    them.  Then the launch with `own()`, the arguments of this entry point alone, between (C, F, T, y_cols, epoch, seed)
+    and the masks."""
     if not isinstance(augment, Augment):
         raise L.SeldHipError(f"{what}: augment must be an Augment, got {type(augment).__name__}")
-    x_all, row_x, y_all, row_y, out_x, out_y, n_rows, dev, B, count, stride = _gather_args(
-        what, x_all, y_all, index, out_x, out_y, cursor, count, stride)
-    if _scalar(epoch, f"{what}: epoch", torch.int32).device != dev:
+    if field is not None and getattr(augment, field) is None:
+        raise L.SeldHipError(f"{what}: the Augment has no {field}")
+    channels = augment.channels if field is None else _least_channels(getattr(augment, field))
+    g = _gather_args(what, *gather)
+    x_all, y_all, _, _, dev, count, _, _ = g
+    if _scalar(epoch, what, "epoch", torch.int32).device != dev:
         raise L.SeldHipError(f"{what}: epoch on another device")
-    C, F, T = 1, 1, 1
+    C, F, T = (1 if channels is None else channels), 1, 1
     if x_all is not None:
         if x_all.dim() != 4:
             raise L.SeldHipError(f"{what}: predictors must be (n, C, F, T), got {tuple(x_all.shape)}")
         C, F, T = x_all.shape[1:]
-    y_cols = 4
-    if y_all is not None:
-        if y_all.dim() < 2:
-            raise L.SeldHipError(f"{what}: targets must be (n, ..., 4 * n_sed), got {tuple(y_all.shape)}")
-        y_cols = y_all.shape[-1]
-    table = augment.table
-    if x_all is None and table is not None:
-        C = augment.channels                    # targets alone: the row length of the table
-    if table is not None and (table.device != dev or augment.channels != C):
-        raise L.SeldHipError(f"{what}: the transform table is for {augment.channels} channels on {table.device}, "
-                             f"the predictors have {C} on {dev}")
-    with torch.cuda.device(dev):
-        with timed("gather_rows_aug_kernel", lambda: (0.0, float(8 * count * (row_x + row_y)))):
-            L.check(L.lib().seld_gather_rows_aug(
-                L.ptr(x_all), row_x, L.ptr(out_x), L.ptr(y_all), row_y, L.ptr(out_y), L.ptr(index), index.numel(), n_rows,
-                L.ptr(cursor), stride, int(start), B, count, C, F, T, y_cols, L.ptr(epoch), int(seed) & 0xFFFFFFFFFFFFFFFF,
-                L.ptr(table), augment.transforms, float(augment.p_swap), int(augment.freq_masks), int(augment.freq_width),
-                int(augment.time_masks), int(augment.time_width), float(augment.fill), L.current_stream()),
-                "seld_gather_rows_aug")
-    return out_x, out_y
-
-
-def _rot_geometry(what, field, channels, x_all, y_all, epoch, matrices, dev, count):
-    """The checks the two rotating gathers make of epoch, geometry and matrices: (C, F, T, y_cols).  `channels`: the least
-    number of channels the Augment's `field` needs (targets alone: the C of the call)."""
-    if _scalar(epoch, f"{what}: epoch", torch.int32).device != dev:
-        raise L.SeldHipError(f"{what}: epoch on another device")
-    C, F, T = channels, 1, 1
-    if x_all is not None:
-        if x_all.dim() != 4:
-            raise L.SeldHipError(f"{what}: predictors must be (n, C, F, T), got {tuple(x_all.shape)}")
-        C, F, T = x_all.shape[1:]
-        if channels > C:
+        if field is not None and channels > C:
             raise L.SeldHipError(f"{what}: {field} name channel {channels - 1}, the predictors have {C}")
     y_cols = 4
     if y_all is not None:
         if y_all.dim() < 2:
             raise L.SeldHipError(f"{what}: targets must be (n, ..., 4 * n_sed), got {tuple(y_all.shape)}")
         y_cols = y_all.shape[-1]
+    table = augment.table
+    if field is None and table is not None and (table.device != dev or channels != C):
+        raise L.SeldHipError(f"{what}: the transform table is for {channels} channels on {table.device}, "
+                             f"the predictors have {C} on {dev}")
     if matrices is not None:
         if (not torch.is_tensor(matrices) or _req(matrices, f"{what}: matrices") is not matrices or matrices.device != dev
                 or matrices.dim() < 2 or matrices.shape[0] < count
                 or tuple(matrices.shape[1:]) not in ((9,), (3, 3))):
             raise L.SeldHipError(f"{what}: matrices must be a contiguous fp32 tensor ({count}, 9) or ({count}, 3, 3) on {dev}, "
                                  f"got {getattr(matrices, 'shape', type(matrices).__name__)}")
-    return C, F, T, y_cols
+    if stats is not None:
+        _check_stats(stats, dev, what)
+    return _launch(what, g, (C, F, T, y_cols, L.ptr(epoch), int(seed) & 0xFFFFFFFFFFFFFFFF, *own(), int(augment.freq_masks),
+                             int(augment.freq_width), int(augment.time_masks), int(augment.time_width), float(augment.fill)))
+
+
+def gather_rows_aug(x_all, y_all, index, out_x, out_y, *, epoch, seed, augment, cursor=None, start=0, count=None, stride=None):
+    """`gather_rows` with `augment` (an Augment) applied to every sample on the way, in ONE launch
+    (seld_gather_rows_aug).  x_all (n, C, F, T) and y_all (n, T_out, 4 * n_sed) name the geometry.  epoch: a device int32
+    of one element, read by the kernel; seed: the key of the draws, which depend on (seed, epoch, position in `index`)
+    and nothing else.  Rows of invalid positions or indices are zero-filled and not augmented."""
+    return _launch_aug("gather_rows_aug", (x_all, y_all, index, out_x, out_y, cursor, start, count, stride), epoch, seed, augment, None,
+                       lambda: (L.ptr(augment.table), augment.transforms, float(augment.p_swap)))
+
+
+def _rotation_args(augment, matrices):
+    """(p_rot, rot_mirror, rot_zflip, matrices) as the rotating entry points take them."""
+    return float(augment.p_rot), int(bool(augment.rot_mirror)), int(bool(augment.rot_zflip)), L.ptr(matrices)
 
 
 def gather_rows_rot(x_all, y_all, index, out_x, out_y, *, epoch, seed, augment, matrices=None, cursor=None, start=0, count=None,
@@ -403,24 +396,9 @@ def gather_rows_rot(x_all, y_all, index, out_x, out_y, *, epoch, seed, augment, 
     sample with probability augment.p_rot from (seed, epoch, position), or, with `matrices` (fp32 device tensor (count, 9)
     or (count, 3, 3), row-major), sample b takes matrices[b] as it is.  augment.table and p_swap are not used.
     Geometry, epoch, cursor, start, count, stride and the zero rows of invalid positions as in `gather_rows_aug`."""
-    what = "gather_rows_rot"
-    if not isinstance(augment, Augment):
-        raise L.SeldHipError(f"{what}: augment must be an Augment, got {type(augment).__name__}")
-    if augment.rot_triples is None:
-        raise L.SeldHipError(f"{what}: the Augment has no rot_triples")
-    x_all, row_x, y_all, row_y, out_x, out_y, n_rows, dev, B, count, stride = _gather_args(
-        what, x_all, y_all, index, out_x, out_y, cursor, count, stride)
-    C, F, T, y_cols = _rot_geometry(what, "rot_triples", augment.rot_channels, x_all, y_all, epoch, matrices, dev, count)
-    with torch.cuda.device(dev):
-        with timed("gather_rows_rot_kernel", lambda: (0.0, float(8 * count * (row_x + row_y)))):
-            L.check(L.lib().seld_gather_rows_rot(
-                L.ptr(x_all), row_x, L.ptr(out_x), L.ptr(y_all), row_y, L.ptr(out_y), L.ptr(index), index.numel(), n_rows,
-                L.ptr(cursor), stride, int(start), B, count, C, F, T, y_cols, L.ptr(epoch), int(seed) & 0xFFFFFFFFFFFFFFFF,
-                augment.rot_packed, len(augment.rot_triples), float(augment.p_rot), int(bool(augment.rot_mirror)),
-                int(bool(augment.rot_zflip)), L.ptr(matrices), int(augment.freq_masks), int(augment.freq_width),
-                int(augment.time_masks), int(augment.time_width), float(augment.fill), L.current_stream()),
-                "seld_gather_rows_rot")
-    return out_x, out_y
+    return _launch_aug("gather_rows_rot", (x_all, y_all, index, out_x, out_y, cursor, start, count, stride), epoch, seed, augment,
+                       "rot_triples", lambda: (augment.rot_packed, len(augment.rot_triples)) + _rotation_args(augment, matrices),
+                       matrices)
 
 
 _stats_checked = {}     # id(tensor) -> (weak reference, _version) of the statistics tensors whose content has been read back
@@ -456,34 +434,18 @@ def gather_rows_polar(x_all, y_all, index, out_x, out_y, *, epoch, seed, augment
     the rotation), None for raw magnitude and phase; its content is checked at the first call with that tensor.  R,
     `matrices`, geometry, epoch, cursor, start, count, stride and the zero rows of invalid positions as in
     `gather_rows_rot`.  augment.table, p_swap and rot_triples are not used."""
-    what = "gather_rows_polar"
-    if not isinstance(augment, Augment):
-        raise L.SeldHipError(f"{what}: augment must be an Augment, got {type(augment).__name__}")
-    if augment.rot_polar is None:
-        raise L.SeldHipError(f"{what}: the Augment has no rot_polar")
-    x_all, row_x, y_all, row_y, out_x, out_y, n_rows, dev, B, count, stride = _gather_args(
-        what, x_all, y_all, index, out_x, out_y, cursor, count, stride)
-    C, F, T, y_cols = _rot_geometry(what, "rot_polar", augment.polar_channels, x_all, y_all, epoch, matrices, dev, count)
-    if stats is not None:
-        _check_stats(stats, dev, what)
-    with torch.cuda.device(dev):
-        with timed("gather_rows_polar_kernel", lambda: (0.0, float(8 * count * (row_x + row_y)))):
-            L.check(L.lib().seld_gather_rows_polar(
-                L.ptr(x_all), row_x, L.ptr(out_x), L.ptr(y_all), row_y, L.ptr(out_y), L.ptr(index), index.numel(), n_rows,
-                L.ptr(cursor), stride, int(start), B, count, C, F, T, y_cols, L.ptr(epoch), int(seed) & 0xFFFFFFFFFFFFFFFF,
-                augment.polar_packed, len(augment.rot_polar), L.ptr(stats), float(augment.p_rot), int(bool(augment.rot_mirror)),
-                int(bool(augment.rot_zflip)), L.ptr(matrices), int(augment.freq_masks), int(augment.freq_width),
-                int(augment.time_masks), int(augment.time_width), float(augment.fill), L.current_stream()),
-                "seld_gather_rows_polar")
-    return out_x, out_y
+    return _launch_aug("gather_rows_polar", (x_all, y_all, index, out_x, out_y, cursor, start, count, stride), epoch, seed, augment,
+                       "rot_polar",
+                       lambda: (augment.polar_packed, len(augment.rot_polar), L.ptr(stats)) + _rotation_args(augment, matrices),
+                       matrices, stats)
 
 
 def epoch_step_end(loss, mean, cursor):
     """mean += (loss - mean) / (cursor + 1); cursor += 1 on the device (seld_epoch_step_end): the running mean of
     train.main's epoch loop without a read-back.  loss, mean: fp32 device scalars; cursor: the int32 device scalar of gather_rows."""
-    _scalar(loss, "epoch_step_end: loss", torch.float32)
-    _scalar(mean, "epoch_step_end: mean", torch.float32)
-    _scalar(cursor, "epoch_step_end: cursor", torch.int32)
+    _scalar(loss, "epoch_step_end", "loss", torch.float32)
+    _scalar(mean, "epoch_step_end", "mean", torch.float32)
+    _scalar(cursor, "epoch_step_end", "cursor", torch.int32)
     with torch.cuda.device(loss.device):
         L.check(L.lib().seld_epoch_step_end(L.ptr(loss), L.ptr(mean), L.ptr(cursor), L.current_stream()),
                 "seld_epoch_step_end")

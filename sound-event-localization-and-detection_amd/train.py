@@ -764,15 +764,12 @@ class ResidentLoader:
             where = dict(start=rank_rows(self.plan[batch][0], count, self.rank)[0], count=count)
         if self.augment is None:
             H.gather_rows(self.x_all, self.y_all, self.index, self.x, self.target, **where)
-        elif self.augment.p_rot > 0 and self.augment.rot_polar is not None:
-            H.gather_rows_polar(self.x_all, self.y_all, self.index, self.x, self.target, epoch=self.epoch, seed=self.seed,
-                                augment=self.augment, stats=self.polar_stats, **where)
-        elif self.augment.p_rot > 0:
-            H.gather_rows_rot(self.x_all, self.y_all, self.index, self.x, self.target, epoch=self.epoch, seed=self.seed,
-                              augment=self.augment, **where)
         else:
-            H.gather_rows_aug(self.x_all, self.y_all, self.index, self.x, self.target, epoch=self.epoch, seed=self.seed,
-                              augment=self.augment, **where)
+            kind = self.augment.kind
+            gather = {"swap": H.gather_rows_aug, "rot": H.gather_rows_rot, "polar": H.gather_rows_polar}[kind]
+            own = dict(stats=self.polar_stats) if kind == "polar" else {}
+            gather(self.x_all, self.y_all, self.index, self.x, self.target, epoch=self.epoch, seed=self.seed, augment=self.augment,
+                   **own, **where)
         return self.x[:count], self.target[:count]
 
     def step_end(self, loss):
@@ -1252,7 +1249,7 @@ def main(args, history=None):
             normalize_dataset(args, xs, stats=norm_stats)
         # the rotating gather of magnitude-phase predictors undoes and redoes the standardisation: it takes the training
         # array's own statistics, which every rank computed from the same array
-        polar = augment is not None and augment.p_rot > 0 and augment.rot_polar is not None
+        polar = augment is not None and augment.kind == "polar"
         tr_data = loader(xs, ys, args.batch_size, True, rank, world, augment,
                          polar_stats_from(norm_stats[0], device) if polar else None)
         if rank == 0:

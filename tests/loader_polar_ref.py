@@ -203,7 +203,13 @@ def inputs(name, stats_i):
     """(x stored fp32 (n, C, F, T), y fp32 (n, 3, 24), groups) of a case: magnitudes |N(0, 1)| * 3, phases uniform in
     (-pi, pi], standardised with STATS[stats_i] in fp32; engineered positions in every row and group at f = 0:
     t = 0: z_y = -z_x (the mix cancels); t = 1: all three magnitudes 0; t = 2: the x phase exactly fp32 pi."""
-    (n, C, F, T), mics, _ = CASES[name]
+    return make_inputs(*CASES[name][:2], stats_i)
+
+
+@functools.lru_cache(maxsize=None)
+def make_inputs(shape, mics, stats_i):
+    """`inputs` for any (n, C, F, T) in the magnitude-phase layout of `mics` microphones (C = 8 * mics)."""
+    n, C, F, T = shape
     stats = STATS[stats_i]
     groups = polar_groups(mics)
     rng = np.random.default_rng(n * C + F * T + stats_i)

@@ -9,10 +9,9 @@ import torch
 
 from tests import loader_aug_ref as R
 from tests.helpers import build_model, pkg
+from tests.loader_helpers import DEV, SENTINEL, buffers, epoch as _epoch
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-SENTINEL = -7.5
 N_ROWS, B = 7, 5
 SHAPES = [(4, 5, 8),            # a row smaller than one tile
           (8, 6, 516),          # 16-byte path, F * T = 3096: tiles straddle channels
@@ -45,12 +44,8 @@ def _table(kind, C):
     return _hand_table(C) if kind == "hand" else None
 
 
-def _epoch(value):
-    return torch.tensor([value], device=DEV, dtype=torch.int32)
-
-
 def _buffers(shape, target):
-    return (torch.full((B,) + shape, SENTINEL, device=DEV), torch.full((B, target[0], 4 * target[1]), SENTINEL, device=DEV))
+    return buffers(shape, (target[0], 4 * target[1]), B)
 
 
 def _check(shape, target, index, first, count, aug_kw, table, *, seed=3, epoch=0, via_cursor=False):

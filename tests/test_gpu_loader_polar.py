@@ -19,28 +19,20 @@ import torch
 
 from tests import loader_polar_ref as P
 from tests.helpers import build_model, pkg
+from tests.loader_helpers import DEV, SENTINEL, bits as _bits, buffers, epoch as _epoch, hold_polar as _hold_x, shifted
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-SENTINEL = -7.5
 B = 4
 K, U24, TINY = P.K, P.U24, P.TINY
 CASES, STATS, TARGET = P.CASES, P.STATS, P.TARGET
-PI32 = float(np.float32(np.pi))
 _resident = {}
-_seen = {"ratio": 0.0}
 
 
 def _data(name, si):
     """(x, y, groups, x on the device (shifted off alignment where the case says so), y on the device), made once."""
     if (name, si) not in _resident:
         x, y, groups = P.inputs(name, si)
-        shift = CASES[name][2]
-        flat = torch.zeros(x.size + shift, device=DEV)
-        flat[shift:] = torch.tensor(x).reshape(-1).to(DEV)
-        xd = flat[shift:].view(x.shape)
-        assert xd.is_contiguous() and xd.data_ptr() % 16 == 4 * shift
-        _resident[(name, si)] = (x, y, groups, xd, torch.tensor(y).to(DEV))
+        _resident[(name, si)] = (x, y, groups, shifted(x, CASES[name][2]), torch.tensor(y).to(DEV))
     return _resident[(name, si)]
 
 
@@ -48,36 +40,8 @@ def _stats_tensor(stats):
     return None if stats is None else torch.tensor(stats, device=DEV, dtype=torch.float32)
 
 
-def _epoch(value):
-    return torch.tensor([value], device=DEV, dtype=torch.int32)
-
-
 def _buffers(x, y, rows=B):
-    return (torch.full((rows,) + tuple(x.shape[1:]), SENTINEL, device=DEV), torch.full((rows,) + tuple(y.shape[1:]), SENTINEL, device=DEV))
-
-
-def _bits(t):
-    return t.contiguous().view(torch.int32)
-
-
-def _hold_x(got, side, groups, stats, what):
-    """Exact positions as bits; the complex value of the others within K * 2^-24 * Wt + TINY; the ranges."""
-    got = got.cpu().numpy()
-    exact = side["exact"]
-    assert P.bits_equal(got, side["ref"])[exact].all(), what
-    if exact.all():
-        return
-    z, M, Ph = P.complex_of(got, groups, stats)
-    err = np.abs(z - side["z"])[~exact]
-    bound = (K * U24 * side["weight"] + TINY)[~exact]
-    ratio = P.error_ratio(got, side, groups, stats)
-    _seen["ratio"] = max(_seen["ratio"], ratio)
-    print(what, "largest |got - ref| / (2^-24 Wt):", ratio, "largest so far:", _seen["ratio"])
-    assert (err <= bound).all(), (what, ratio)
-    mean_m, _, mean_p, _ = P.NO_STATS if stats is None else stats
-    slack_m = 0.0 if stats is None else 2.0 ** -23 * (np.abs(M[~exact]) + abs(mean_m))
-    slack_p = 0.0 if stats is None else 2.0 ** -23 * (np.pi + abs(mean_p))
-    assert (M[~exact] >= -slack_m).all() and (np.abs(Ph[~exact]) <= PI32 + slack_p).all(), what
+    return buffers(x.shape[1:], y.shape[1:], rows)
 
 
 def _labels_of_the_rot_kernel(yd, idx, like, **kw):

@@ -16,10 +16,9 @@ import torch
 from tests import loader_aug_ref as A
 from tests import loader_rot_ref as R
 from tests.helpers import build_model, pkg
+from tests.loader_helpers import DEV, SENTINEL, bits as _bits, buffers, epoch as _epoch, hold_rot as _hold, shifted
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-SENTINEL = -7.5
 N_ROWS, B = 5, 4
 U24, TINY = R.U24, R.TINY
 IV5 = [(3 * g, 3 * g + 2, 3 * g + 1) for g in range(5)]           # five groups [I1, I2, I3] of the order W X Z Y
@@ -43,36 +42,14 @@ def _data(name, target):
     y = rng.standard_normal((N_ROWS, target[0], 4 * target[1])).astype(np.float32)
     n_sed = target[1]
     y[:, 0, n_sed:n_sed + 6] = [1.0, 0.25, 0.5, -0.5, 1.0, 0.75]    # slots 0 and 1 of frame 0: they name the rotation (test 3)
-    flat = torch.zeros(x.size + shift, device=DEV)
-    flat[shift:] = torch.from_numpy(x).reshape(-1).to(DEV)
-    xd = flat[shift:].view(x.shape)
-    assert xd.is_contiguous() and xd.data_ptr() % 16 == 4 * shift
-    yd = torch.from_numpy(y).to(DEV)
+    xd, yd = shifted(x, shift), torch.from_numpy(y).to(DEV)
     x.setflags(write=False)
     y.setflags(write=False)
     return x, y, xd, yd
 
 
-def _epoch(value):
-    return torch.tensor([value], device=DEV, dtype=torch.int32)
-
-
 def _buffers(shape, target, rows=B):
-    return (torch.full((rows,) + tuple(shape), SENTINEL, device=DEV), torch.full((rows, target[0], 4 * target[1]), SENTINEL, device=DEV))
-
-
-def _bits(t):
-    return t.contiguous().view(torch.int32)
-
-
-def _hold(got, side, factor, key, what):
-    """Exact positions as bits, the others within factor * 2^-24 * side[key] + TINY of the float64 reference."""
-    got = got.cpu().numpy()
-    exact = side["exact"]
-    assert R.bits_equal(got, side["ref"])[exact].all(), what
-    err = np.abs(got.astype(np.float64) - side["ref"])[~exact]
-    bound = (factor * U24 * side[key] + TINY)[~exact]
-    assert (err <= bound).all(), (what, float((err / bound).max()))
+    return buffers(shape, (target[0], 4 * target[1]), rows)
 
 
 def _call(name, target, first, count, aug_kw, *, matrices=None, seed=3, epoch=0, index=INDEX, rows=B, via_cursor=False):
