@@ -929,6 +929,51 @@ int seld_least_distance(const double* gt, const int32_t* gt_counts, const double
                         void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The same counters broken down by recording and class.  For R recordings and C = nb_classes
+ * (0 .. 64) both calls below WRITE (not add to; nothing needs zeroing) the tables
+ *   counters (R, C + 2, 16) int64    in the order of seld_event_metrics_accumulate's counters
+ *   total_de (R, C + 2)     double
+ * Row c < C of a recording is what class c contributes; row C ("other") takes the list rows whose class is no integer
+ * in [0, C): they take part in counters 0..2 and 13..15 alone, so counters 3..12 and total_de of that row are 0;
+ * row C + 1 ("all") is what the plain call adds for this recording alone.
+ *   counters 3, 4, 5, 9..12, total_de   what the class adds in each block (row "all": the sum over the classes)
+ *   counters 6, 7, 8 (S, D, I)          class rows: min(fp, fn), max(0, fn - fp), max(0, fp - fn) of the class's own
+ *                                       loc_FP / loc_FN in each block (the class-wise definition of DCASE's macro
+ *                                       average); row "all": the reference's, loc_FP / loc_FN summed over the classes
+ *                                       of the block first.  The only counters whose row "all" is not the sum of rows 0..C.
+ *   counters 0..2 and 13..15            row by row: a prediction adds 1 to the FP of its class (2 where its frame has
+ *                                       no reference row at all); a reference adds 2 to the FN of its class where its
+ *                                       frame has no prediction row at all, else TP + 1 and FP - 1 when matched (by a
+ *                                       prediction of its class), FN + 1 when not.  A class's FP can be negative.
+ * Every (recording, block) unit writes a slab of (C + 2) x 17 eight-byte words into `workspace`, and a second kernel
+ * adds the slabs of a recording in ascending block order: no atomics on memory, integer entries exact, total_de
+ * entries the same bits every run.  The matching is the code of the plain calls, so the tables cannot disagree with
+ * the totals about a match.
+ *   seld_metrics_breakdown_workspace   bytes of workspace: recordings * ceil(n_frames / frames_per_block) * (C + 2) *
+ *                                      17 * 8 (0 for arguments the calls refuse).  For the dense call, recordings =
+ *                                      clips, n_frames = frames, nb_classes = classes.
+ *   seld_event_metrics_breakdown       the arguments, flags, refusals and error codes of
+ *                                      seld_event_metrics_accumulate_ex; coords = 2 leaves counters 0..2 zero; a call
+ *                                      refused for an overflowing cell (flags[1] != 0) writes both tables as zeros.
+ *   seld_metrics_breakdown             the arguments and error codes of seld_metrics_accumulate (clips are the
+ *                                      recordings); counters 13..15 and row "other" stay zero.  SELD_EUNSUPPORTED also
+ *                                      where the slab no longer fits the workgroup's LDS beside the wave's slice.
+ * SELD_EWORKSPACE: workspace NULL or smaller than the query's answer; nothing is launched.  No host read: the calls
+ * can be recorded in a graph (the workspace then belongs to the graph).
+ * ------------------------------------------------------------------------------------------ */
+size_t seld_metrics_breakdown_workspace(int64_t recordings, int32_t n_frames, int32_t nb_classes, int32_t frames_per_block);
+int seld_event_metrics_breakdown(const double* pred_rows, const int64_t* pred_offsets, int64_t pred_count,
+                                 const double* true_rows, const int64_t* true_offsets, int64_t true_count,
+                                 int64_t recordings, int32_t n_frames, int32_t nb_classes, int32_t frames_per_block,
+                                 int32_t coords, int32_t max_tracks, double spatial_threshold, double doa_threshold,
+                                 int64_t* counters, double* total_de, void* workspace, size_t workspace_bytes,
+                                 int64_t* flags, void* stream);
+int seld_metrics_breakdown(const float* sed, const float* doa, const float* target, int32_t clips, int32_t frames,
+                           int32_t num_frames, int32_t classes, int32_t overlaps, float max_loc_value,
+                           double spatial_threshold, double doa_threshold, int32_t frames_per_block,
+                           int64_t* counters, double* total_de, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Event decoding: the submission rows of resident network outputs (csrc/decode.hip).  Replaces
  * gen_submission_list_task2_OLD (utility_functions.py:158-181) and gen_submission_list_task2
  * (utility_functions.py:184-210), which train.py:110-116 calls on the prediction and on the target of

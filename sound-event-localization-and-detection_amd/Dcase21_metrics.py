@@ -7,16 +7,33 @@ Limits of the device path: events are Cartesian (x, y, z) or spherical (azimuth,
 call; at most `max_tracks` events of one class in one frame (3 unless SELDMetrics is given more, 8 at most); at most 64
 classes; least_distance_between_gt_pred takes at most 8 DOAs a side.  Where several associations of a frame cost the
 same, the first row -> column map in lexicographic order is taken (scipy's choice among equals is its own)."""
+import functools
+
 import numpy as np
 import torch
 
 from . import _lib as L
+from . import class_metrics as CM
 from . import hip_ops as H
 
 eps = np.finfo(float).eps
 
 
+def _takes_average(init):
+    """SELDMetrics(..., average='micro' | 'macro'): a keyword of this package beside the reference's constructor, whose own
+    parameter list (what inspect.signature reports) stays the reference's plus max_tracks."""
+    @functools.wraps(init)
+    def __init__(self, *args, average="micro", **kwargs):
+        if average not in ("micro", "macro"):
+            raise L.SeldHipError(f"SELDMetrics: average must be 'micro' or 'macro', got {average!r}")
+        init(self, *args, **kwargs)
+        self._average = average
+        self._tables = []                               # 'macro': the (counters, total_de) tables of update_from_events
+    return __init__
+
+
 class SELDMetrics(object):
+    @_takes_average
     def __init__(self, doa_threshold=20, nb_classes=14, max_tracks=3):
         '''
             This class implements both the class-sensitive localization and location-sensitive detection metrics.
@@ -52,7 +69,11 @@ class SELDMetrics(object):
         Collect the final SELD scores
 
         :return: returns both location-sensitive detection scores and class-sensitive localization scores
+        (average='macro': their class-wise macro averages over the classes of the reference, class_metrics.macro_scores)
         '''
+        if self._average == "macro":
+            m = CM.macro_scores(*self.table())
+            return m["ER"], m["F"], m["LE"], m["LR"]
         # Location-sensitive detection performance
         ER = (self._S + self._D + self._I) / float(self._Nref + eps)
         F = self._TP / (eps + self._TP + 0.5 * (self._FP + self._FN))
@@ -70,6 +91,23 @@ class SELDMetrics(object):
             setattr(self, name, getattr(self, name) + c[k])
         self._total_DE += float(acc[1].item())
 
+    def table(self):
+        """average='macro': the breakdown of everything scored so far, (counters (R, C + 2, 16), total_de (R, C + 2)) numpy
+        arrays, one slab per recording in the order they were given."""
+        if self._average != "macro":
+            raise L.SeldHipError("SELDMetrics: the per-class table is kept under average='macro' only")
+        if not self._tables:
+            return np.zeros((0, self._nb_classes + 2, 16), dtype=np.int64), np.zeros((0, self._nb_classes + 2))
+        return np.concatenate([t[0] for t in self._tables]), np.concatenate([t[1] for t in self._tables])
+
+    def class_scores(self):
+        """average='macro': class_metrics.class_scores of everything scored so far."""
+        return CM.class_scores(*self.table())
+
+    def jackknife(self, score=CM.macro_score_vector):
+        """average='macro': class_metrics.jackknife over the recordings scored so far (at least two)."""
+        return CM.jackknife(*self.table(), score)
+
     def update_from_events(self, pred_rows, pred_offsets, true_rows, true_offsets, max_frames, frames_per_block=10):
         '''
         The fast form of segment_labels + update_seld_scores for callers who hold rows: (E, 5) float64 device tensors
@@ -81,6 +119,15 @@ class SELDMetrics(object):
             raise L.SeldHipError(f"update_from_events: rows of {sorted(widths)} columns in one call")
         coords = 2 if widths == {4} else 3              # any other width is score_events' to refuse
         on_device = torch.is_tensor(pred_rows) and pred_rows.is_cuda      # otherwise score_events' own checks raise
+        if self._average == "macro":
+            counters, total_de = H.score_events_by(pred_rows, pred_offsets, true_rows, true_offsets, max_frames,
+                                                   nb_classes=self._nb_classes, doa_threshold=self._spatial_T,
+                                                   frames_per_block=frames_per_block, coords=coords,
+                                                   max_tracks=self._max_tracks)
+            counters, total_de = counters.cpu().numpy(), total_de.cpu().numpy()      # one read-back
+            self._tables.append((counters, total_de))
+            self._add((counters[:, -1].sum(0), total_de[:, -1].sum()))               # the attributes stay the micro totals
+            return
         acc = H.event_metrics_new(pred_rows.device if on_device else torch.device("cuda", torch.cuda.current_device()))
         H.score_events(acc, pred_rows, pred_offsets, true_rows, true_offsets, max_frames, nb_classes=self._nb_classes,
                        doa_threshold=self._spatial_T, frames_per_block=frames_per_block, coords=coords,
@@ -96,6 +143,9 @@ class SELDMetrics(object):
         :param gt: dictionary containing class-wise groundtruth for each N-seconds segment block
         (what segment_labels returns; all events Cartesian, or all azimuth and elevation in degrees)
         '''
+        if self._average == "macro":
+            raise L.SeldHipError("update_seld_scores: the dictionary form keeps no per-recording table; under "
+                                 "average='macro' score rows with update_from_events")
         nb_blocks = len(gt.keys())
         for block_cnt in range(nb_blocks):
             gt[block_cnt], pred[block_cnt]              # the reference's KeyError for a missing block

@@ -25,6 +25,9 @@
 // The kernel is compiled for max_tracks <= 3 (every lane solves the cells of its class by enumeration, assign_3x3) and for
 // max_tracks <= 8 (WIDE: a cell with 4 to 8 events on a side is handed to the whole wave, assign_wave_8x8; a cell with at
 // most 3 on both sides still takes the enumeration, so it gives the same bits in both).
+// seld_event_metrics_breakdown keeps the counters apart by recording and class: event_breakdown_kernel is
+// event_metrics_kernel around the same score_unit (BY = true), every unit leaving a slab in a workspace instead of adding to
+// the totals, and breakdown_reduce_kernel (metrics_common.h) adds the slabs of a recording in block order.
 // least_distance_kernel solves a batch of associations alone (least_distance_between_gt_pred, Dcase21_metrics.py:191-220)
 // with the same device functions.
 #include "metrics_common.h"
@@ -69,6 +72,9 @@ __device__ __forceinline__ Index first_frame_not_below(const double* rows, Index
 
 __device__ __forceinline__ bool whole_in(double f, double lo, double hi) { return f >= lo && f < hi && f == floor(f); }
 
+// the slab row of a list row's class: the class itself, or row "other" for one that is no integer in [0, classes)
+__device__ __forceinline__ int class_row(double c, int classes) { return whole_in(c, 0.0, (double)classes) ? (int)c : classes; }
+
 template <int COORDS>
 __global__ __launch_bounds__(256) void event_check_kernel(const EventP p) {
     constexpr int S = 2 + COORDS;
@@ -111,10 +117,12 @@ __global__ __launch_bounds__(256) void event_check_kernel(const EventP p) {
 // One unit: P (np rows) and T (nt rows) are the predictions and references of one recording whose frames lie in the
 // block [f0, f0 + fpb), each sorted by frame; in LDS or in memory (inlined once for each).
 // COORDS = 2: the Euclidean counters cnt[0..2] have no meaning and are left alone.  WIDE: h and cs are the LDS of
-// assign_wave_8x8.
-template <int COORDS, bool WIDE>
+// assign_wave_8x8.  BY: `slab` is the unit's zeroed LDS slab (metrics_common.h) and cnt / total_de hold this unit alone:
+// whatever a row or a class adds to cnt goes into its class row of the slab as well.
+template <int COORDS, bool WIDE, bool BY>
 __device__ __forceinline__ void score_unit(const double* P, int np, const double* T, int nt, const EventP& p, double f0, int lane,
-                                           long long (&cnt)[EV_COUNTERS], double& total_de, double* h, double* cs) {
+                                           long long (&cnt)[EV_COUNTERS], double& total_de, double* h, double* cs,
+                                           long long* slab) {
     constexpr int S = 2 + COORDS;
     constexpr int NT = WIDE ? EV_WIDE : 3;              // reference tracks a class can have
     // ---- location_sensitive_detection and sed_score_computation: lane = row ----
@@ -129,6 +137,11 @@ __device__ __forceinline__ void score_unit(const double* P, int np, const double
         const int add = (j < nt && T[j * S] == f) ? 1 : 2;
         if constexpr (COORDS == 3) cnt[1] += add;
         cnt[14] += add;
+        if constexpr (BY) {
+            const int row = class_row(P[i * S + 1], p.classes);
+            if constexpr (COORDS == 3) slab_add(slab, row, 1, add);
+            slab_add(slab, row, 14, add);
+        }
     }
     for (int i = lane; i < nt; i += 64) {
         const double f = T[i * S];
@@ -137,6 +150,11 @@ __device__ __forceinline__ void score_unit(const double* P, int np, const double
         if (!(j < np && P[j * S] == f)) {
             if constexpr (COORDS == 3) cnt[2] += 2;
             cnt[15] += 2;
+            if constexpr (BY) {
+                const int row = class_row(T[i * S + 1], p.classes);
+                if constexpr (COORDS == 3) slab_add(slab, row, 2, 2);
+                slab_add(slab, row, 15, 2);
+            }
             continue;
         }
         const double c = T[i * S + 1];
@@ -152,12 +170,22 @@ __device__ __forceinline__ void score_unit(const double* P, int np, const double
             cnt[0] += near ? 1 : 0;
             cnt[1] -= near ? 1 : 0;
             cnt[2] += near ? 0 : 1;
+            if constexpr (BY) {
+                const int row = class_row(c, p.classes);
+                slab_add(slab, row, near ? 0 : 2, 1);
+                if (near) slab_add(slab, row, 1, -1);
+            }
         } else {
             for (; j < np && P[j * S] == f; ++j) same = same || P[j * S + 1] == c;
         }
         cnt[13] += same ? 1 : 0;
         cnt[14] -= same ? 1 : 0;
         cnt[15] += same ? 0 : 1;
+        if constexpr (BY) {
+            const int row = class_row(c, p.classes);
+            slab_add(slab, row, same ? 13 : 15, 1);
+            if (same) slab_add(slab, row, 14, -1);
+        }
     }
     if (p.classes == 0) return;
 
@@ -271,6 +299,7 @@ __device__ __forceinline__ void score_unit(const double* P, int np, const double
         SELD_DCASE_ADD(cnt, a);
         loc_fn = a.fn;
         loc_fp = a.fp;
+        if constexpr (BY) slab_put_dcase(slab, lane, a, total_de);
     }
     const int blk_fn = wave_sum_i32(loc_fn), blk_fp = wave_sum_i32(loc_fp);
     if (lane == 0) {
@@ -312,10 +341,10 @@ __global__ __launch_bounds__(64) void event_metrics_kernel(const EventP p) {
             for (int i = lane; i < np * S; i += 64) pred_s[i] = p.pred[p0 * S + i];
             for (int i = lane; i < nt * S; i += 64) true_s[i] = p.tru[t0 * S + i];
             __syncthreads();
-            score_unit<COORDS, WIDE>(pred_s, np, true_s, nt, p, f0, lane, cnt, total_de, h, cs);
+            score_unit<COORDS, WIDE, false>(pred_s, np, true_s, nt, p, f0, lane, cnt, total_de, h, cs, nullptr);
             __syncthreads();                            // the copy is rewritten by the next unit
         } else {
-            score_unit<COORDS, WIDE>(p.pred + p0 * S, np, p.tru + t0 * S, nt, p, f0, lane, cnt, total_de, h, cs);
+            score_unit<COORDS, WIDE, false>(p.pred + p0 * S, np, p.tru + t0 * S, nt, p, f0, lane, cnt, total_de, h, cs, nullptr);
         }
     }
 #pragma unroll
@@ -325,6 +354,59 @@ __global__ __launch_bounds__(64) void event_metrics_kernel(const EventP p) {
     }
     const double de = wave_sum_d(total_de);
     if (lane == 0 && de != 0.0) atomicAdd(p.total_de, de);
+}
+
+// event_metrics_kernel with the closing sums kept apart: every (recording, block) unit, an empty one too, leaves its
+// slab (metrics_common.h) in p.work, and breakdown_reduce_kernel adds them up.  The scoring is score_unit's.
+template <int COORDS, bool WIDE>
+__global__ __launch_bounds__(64) void event_breakdown_kernel(const EventP p, long long* work) {
+    constexpr int S = 2 + COORDS;
+    __shared__ __attribute__((aligned(16))) double pred_s[EV_CAP * S];
+    __shared__ __attribute__((aligned(16))) double true_s[EV_CAP * S];
+    __shared__ long long slab[(64 + 2) * BY_ROW];
+    double *h = nullptr, *cs = nullptr;
+    if constexpr (WIDE) {
+        __shared__ double h_s[256], cs_s[64];
+        h = h_s;
+        cs = cs_s;
+    }
+    if (p.flags[1] != 0) return;                        // refused: the reduction writes zeros and reads no slab
+    const int lane = threadIdx.x;
+    const int words = (p.classes + 2) * BY_ROW;
+    const long long total = p.recordings * p.blocks;
+    for (long long u = blockIdx.x; u < total; u += gridDim.x) {
+        const long long rec = u / p.blocks, blk = u % p.blocks;
+        const double f0 = (double)blk * (double)p.fpb, f1 = f0 + (double)p.fpb;
+        long long plo = 0, phi = 0, tlo = 0, thi = 0;
+        if (p.pred_n) rec_range(p.pred_off, rec, p.pred_n, plo, phi);
+        if (p.true_n) rec_range(p.true_off, rec, p.true_n, tlo, thi);
+        const long long p0 = first_frame_not_below<S>(p.pred, plo, phi, f0), p1 = first_frame_not_below<S>(p.pred, p0, phi, f1);
+        const long long t0 = first_frame_not_below<S>(p.tru, tlo, thi, f0), t1 = first_frame_not_below<S>(p.tru, t0, thi, f1);
+        const int np = (int)(p1 - p0), nt = (int)(t1 - t0);
+        long long* dst = work + u * words;
+        if (np == 0 && nt == 0) {
+            for (int i = lane; i < words; i += 64) dst[i] = 0;      // (the bits of 0.0 as well)
+            continue;
+        }
+        for (int i = lane; i < words; i += 64) slab[i] = 0;
+        long long cnt[EV_COUNTERS];
+#pragma unroll
+        for (int i = 0; i < EV_COUNTERS; ++i) cnt[i] = 0;
+        double total_de = 0.0;
+        if (np <= EV_CAP && nt <= EV_CAP) {
+            for (int i = lane; i < np * S; i += 64) pred_s[i] = p.pred[p0 * S + i];
+            for (int i = lane; i < nt * S; i += 64) true_s[i] = p.tru[t0 * S + i];
+            __syncthreads();
+            score_unit<COORDS, WIDE, true>(pred_s, np, true_s, nt, p, f0, lane, cnt, total_de, h, cs, slab);
+        } else {
+            __syncthreads();
+            score_unit<COORDS, WIDE, true>(p.pred + p0 * S, np, p.tru + t0 * S, nt, p, f0, lane, cnt, total_de, h, cs, slab);
+        }
+        slab_put_all(slab, p.classes + 1, lane, cnt, total_de);
+        __syncthreads();
+        for (int i = lane; i < words; i += 64) dst[i] = slab[i];
+        __syncthreads();                                // the slab and the copy are rewritten by the next unit
+    }
 }
 
 struct AssignP {
@@ -368,24 +450,16 @@ __global__ __launch_bounds__(64) void least_distance_kernel(const AssignP p) {
 
 using namespace seld;
 
-extern "C" int seld_event_metrics_accumulate_ex(const double* pred_rows, const int64_t* pred_offsets, int64_t pred_count,
-                                                const double* true_rows, const int64_t* true_offsets, int64_t true_count,
-                                                int64_t recordings, int32_t n_frames, int32_t nb_classes,
-                                                int32_t frames_per_block, int32_t coords, int32_t max_tracks,
-                                                double spatial_threshold, double doa_threshold, int64_t* counters,
-                                                double* total_de, int64_t* flags, void* stream) {
+// The checks both scoring calls make before anything is launched, and the kernels' arguments (without the outputs)
+static int event_args(const double* pred_rows, const int64_t* pred_offsets, int64_t pred_count, const double* true_rows,
+                      const int64_t* true_offsets, int64_t true_count, int64_t recordings, int32_t n_frames, int32_t nb_classes,
+                      int32_t frames_per_block, int32_t coords, int32_t max_tracks, double spatial_threshold,
+                      double doa_threshold, const void* out0, const void* out1, int64_t* flags, EventP& p) {
     if ((coords != 2 && coords != 3) || max_tracks < 1 || max_tracks > EV_WIDE) return SELD_EINVAL;
-    if (recordings < 0 || pred_count < 0 || true_count < 0 || n_frames < 0 || !counters || !total_de || !flags) return SELD_EINVAL;
+    if (recordings < 0 || pred_count < 0 || true_count < 0 || n_frames < 0 || !out0 || !out1 || !flags) return SELD_EINVAL;
     if (nb_classes < 0 || nb_classes > 64 || frames_per_block < 1) return SELD_EINVAL;
     if (pred_count > 0x0fffffff || true_count > 0x0fffffff) return SELD_EUNSUPPORTED;    // stride * row index stays an int inside a unit
     if ((pred_count && (!pred_rows || !pred_offsets)) || (true_count && (!true_rows || !true_offsets))) return SELD_EINVAL;
-    const hipError_t e = hipMemsetAsync(flags, 0, 2 * sizeof(int64_t), (hipStream_t)stream);
-    if (e != hipSuccess) {
-        g_last_hip_error = (int)e;
-        return SELD_ELAUNCH;
-    }
-    if (recordings == 0) return SELD_OK;
-    EventP p;
     p.pred = pred_rows;
     p.pred_off = reinterpret_cast<const long long*>(pred_offsets);
     p.pred_n = pred_count;
@@ -400,20 +474,50 @@ extern "C" int seld_event_metrics_accumulate_ex(const double* pred_rows, const i
     p.max_tracks = max_tracks;
     p.spatial_threshold = spatial_threshold;
     p.doa_threshold = doa_threshold;
+    p.counters = nullptr;
+    p.total_de = nullptr;
+    p.flags = reinterpret_cast<long long*>(flags);
+    return SELD_OK;
+}
+
+static int zero_flags(int64_t* flags, hipStream_t stream) {
+    const hipError_t e = hipMemsetAsync(flags, 0, 2 * sizeof(int64_t), stream);
+    if (e != hipSuccess) {
+        g_last_hip_error = (int)e;
+        return SELD_ELAUNCH;
+    }
+    return SELD_OK;
+}
+
+static int launch_event_check(const EventP& p, int32_t coords, hipStream_t stream) {
+    long long wgs = (p.pred_n + p.true_n + 255) / 256;
+    if (wgs > 2048) wgs = 2048;
+    if (coords == 3) hipLaunchKernelGGL(event_check_kernel<3>, dim3((unsigned)wgs), dim3(256), 0, stream, p);
+    else hipLaunchKernelGGL(event_check_kernel<2>, dim3((unsigned)wgs), dim3(256), 0, stream, p);
+    return check_launch();
+}
+
+extern "C" int seld_event_metrics_accumulate_ex(const double* pred_rows, const int64_t* pred_offsets, int64_t pred_count,
+                                                const double* true_rows, const int64_t* true_offsets, int64_t true_count,
+                                                int64_t recordings, int32_t n_frames, int32_t nb_classes,
+                                                int32_t frames_per_block, int32_t coords, int32_t max_tracks,
+                                                double spatial_threshold, double doa_threshold, int64_t* counters,
+                                                double* total_de, int64_t* flags, void* stream) {
+    EventP p;
+    int rc = event_args(pred_rows, pred_offsets, pred_count, true_rows, true_offsets, true_count, recordings, n_frames, nb_classes,
+                        frames_per_block, coords, max_tracks, spatial_threshold, doa_threshold, counters, total_de, flags, p);
+    if (rc != SELD_OK) return rc;
+    rc = zero_flags(flags, (hipStream_t)stream);
+    if (rc != SELD_OK) return rc;
+    if (recordings == 0) return SELD_OK;
     p.counters = reinterpret_cast<long long*>(counters);
     p.total_de = total_de;
-    p.flags = reinterpret_cast<long long*>(flags);
-    const long long rows = pred_count + true_count;
-    if (rows == 0) return SELD_OK;                      // nothing to check, and every unit is empty
-    long long wgs = (rows + 255) / 256;
-    if (wgs > 2048) wgs = 2048;
-    if (coords == 3) hipLaunchKernelGGL(event_check_kernel<3>, dim3((unsigned)wgs), dim3(256), 0, (hipStream_t)stream, p);
-    else hipLaunchKernelGGL(event_check_kernel<2>, dim3((unsigned)wgs), dim3(256), 0, (hipStream_t)stream, p);
-    const int rc = check_launch();
+    if (pred_count + true_count == 0) return SELD_OK;   // nothing to check, and every unit is empty
+    rc = launch_event_check(p, coords, (hipStream_t)stream);
     if (rc != SELD_OK) return rc;
     const long long total = recordings * p.blocks;
     if (total == 0) return SELD_OK;
-    wgs = total > 4096 ? 4096 : total;                  // 2 generations of resident waves; waves loop over their units
+    const long long wgs = total > 4096 ? 4096 : total;  // 2 generations of resident waves; waves loop over their units
     const bool wide = max_tracks > 3;                   // up to 3 x 3 keeps the lane-per-class kernel as it was
     const dim3 grid((unsigned)wgs), block(64);
     if (coords == 3 && !wide) hipLaunchKernelGGL((event_metrics_kernel<3, false>), grid, block, 0, (hipStream_t)stream, p);
@@ -421,6 +525,56 @@ extern "C" int seld_event_metrics_accumulate_ex(const double* pred_rows, const i
     else if (!wide) hipLaunchKernelGGL((event_metrics_kernel<2, false>), grid, block, 0, (hipStream_t)stream, p);
     else hipLaunchKernelGGL((event_metrics_kernel<2, true>), grid, block, 0, (hipStream_t)stream, p);
     return check_launch();
+}
+
+extern "C" size_t seld_metrics_breakdown_workspace(int64_t recordings, int32_t n_frames, int32_t nb_classes,
+                                                   int32_t frames_per_block) {
+    if (recordings < 0 || n_frames < 0 || nb_classes < 0 || nb_classes > 64 || frames_per_block < 1) return 0;
+    return breakdown_workspace_bytes(recordings, ((long long)n_frames + frames_per_block - 1) / frames_per_block, nb_classes);
+}
+
+extern "C" int seld_event_metrics_breakdown(const double* pred_rows, const int64_t* pred_offsets, int64_t pred_count,
+                                            const double* true_rows, const int64_t* true_offsets, int64_t true_count,
+                                            int64_t recordings, int32_t n_frames, int32_t nb_classes, int32_t frames_per_block,
+                                            int32_t coords, int32_t max_tracks, double spatial_threshold, double doa_threshold,
+                                            int64_t* counters, double* total_de, void* workspace, size_t workspace_bytes,
+                                            int64_t* flags, void* stream) {
+    EventP p;
+    int rc = event_args(pred_rows, pred_offsets, pred_count, true_rows, true_offsets, true_count, recordings, n_frames, nb_classes,
+                        frames_per_block, coords, max_tracks, spatial_threshold, doa_threshold, counters, total_de, flags, p);
+    if (rc != SELD_OK) return rc;
+    const size_t need = breakdown_workspace_bytes(recordings, p.blocks, nb_classes);
+    if (need && (!workspace || workspace_bytes < need)) return SELD_EWORKSPACE;
+    rc = zero_flags(flags, (hipStream_t)stream);
+    if (rc != SELD_OK) return rc;
+    if (recordings == 0) return SELD_OK;
+    BreakdownP b;
+    b.work = reinterpret_cast<const long long*>(workspace);
+    b.flags = p.flags;
+    b.recordings = recordings;
+    b.blocks = p.blocks;
+    b.rows = nb_classes + 2;
+    b.counters = reinterpret_cast<long long*>(counters);
+    b.total_de = total_de;
+    const long long total = recordings * p.blocks;
+    if (pred_count + true_count == 0) b.blocks = 0;     // every unit is empty: the table is zeros, no slab is written or read
+    else {
+        rc = launch_event_check(p, coords, (hipStream_t)stream);
+        if (rc != SELD_OK) return rc;
+    }
+    if (b.blocks) {
+        const long long wgs = total > 4096 ? 4096 : total;
+        const bool wide = max_tracks > 3;
+        const dim3 grid((unsigned)wgs), block(64);
+        long long* work = reinterpret_cast<long long*>(workspace);
+        if (coords == 3 && !wide) hipLaunchKernelGGL((event_breakdown_kernel<3, false>), grid, block, 0, (hipStream_t)stream, p, work);
+        else if (coords == 3) hipLaunchKernelGGL((event_breakdown_kernel<3, true>), grid, block, 0, (hipStream_t)stream, p, work);
+        else if (!wide) hipLaunchKernelGGL((event_breakdown_kernel<2, false>), grid, block, 0, (hipStream_t)stream, p, work);
+        else hipLaunchKernelGGL((event_breakdown_kernel<2, true>), grid, block, 0, (hipStream_t)stream, p, work);
+        rc = check_launch();
+        if (rc != SELD_OK) return rc;
+    }
+    return launch_breakdown_reduce(b, (hipStream_t)stream);
 }
 
 extern "C" int seld_event_metrics_accumulate(const double* pred_rows, const int64_t* pred_offsets, int64_t pred_count,

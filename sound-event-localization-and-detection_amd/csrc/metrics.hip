@@ -54,8 +54,12 @@ __device__ __forceinline__ void load_xyz(const float* loc, int slot, float max_l
 //   3. location_sensitive_detection: lane j = reference slot j looks for a prediction of its class within the threshold;
 //   4. DCASE21 block metrics: lane c = class c walks the block's frames (<= 3 x 3 association per frame);
 //      loc_FP / loc_FN are summed over the classes with a wave reduction before S / D / I.
-__global__ __launch_bounds__(256) void metrics_kernel(const MetricsP p) {
-    extern __shared__ __attribute__((aligned(16))) float smem[];
+//
+// BY (seld_metrics_breakdown): the same walk with the closing sums kept apart.  `slab_s` is a slab of LDS in front of the
+// wave's slice (one wave a workgroup), zeroed per unit; the counters hold one unit at a time; whatever a (frame, slot) or
+// a class adds goes into its class row as well, and the finished slab into slab u of `work` (metrics_common.h).
+template <bool BY>
+__device__ __forceinline__ void metrics_body(const MetricsP& p, float* smem, long long* slab_s, long long* work) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int n = p.classes * p.overlaps;
     // masks (u64) | costs (f64 [class][frame][3][3]) | pair list (u32), later matches (f64 [class][frame][3])
@@ -74,6 +78,12 @@ __global__ __launch_bounds__(256) void metrics_kernel(const MetricsP p) {
     const unsigned long long cls_mask = (1ull << p.overlaps) - 1ull;
 
     for (long long u = (long long)blockIdx.x * (blockDim.x >> 6) + wave; u < total; u += n_waves) {
+        if constexpr (BY) {
+#pragma unroll
+            for (int i = 0; i < NUM_COUNTERS; ++i) cnt[i] = 0;
+            total_de = 0.0;
+            for (int i = lane; i < (p.classes + 2) * BY_ROW; i += 64) slab_s[i] = 0;
+        }
         const int clip = (int)(u / p.blocks), blk = (int)(u % p.blocks);
         const int f0 = blk * p.fpb;
         const int nf = min(p.fpb, p.frames - f0);
@@ -120,6 +130,21 @@ __global__ __launch_bounds__(256) void metrics_kernel(const MetricsP p) {
                 cnt[1] += n_p;
             }
         }
+        if constexpr (BY) {                             // the same three cases, lane = (class, frame)
+            for (int item = lane; item < p.classes * nf; item += 64) {
+                const int c = item / nf, f = item - c * nf;
+                const unsigned long long mp_f = mp_s[f], mt_f = mt_s[f];
+                const int c_p = __popcll((mp_f >> (c * p.overlaps)) & cls_mask), c_t = __popcll((mt_f >> (c * p.overlaps)) & cls_mask);
+                if (mt_f == 0ull) {
+                    if (c_p) slab_add(slab_s, c, 1, 2 * c_p);
+                } else if (mp_f == 0ull) {
+                    if (c_t) slab_add(slab_s, c, 2, 2 * c_t);
+                } else {
+                    if (c_t) slab_add(slab_s, c, 2, c_t);
+                    if (c_p) slab_add(slab_s, c, 1, c_p);
+                }
+            }
+        }
         // per (frame, reference slot): is there a prediction of its class within the threshold?  All twelve coordinate
         // loads of an item are issued together (clamped addresses, results masked): one memory latency per item.
         for (int base = 0; base < nf * n; base += 64) {
@@ -151,6 +176,11 @@ __global__ __launch_bounds__(256) void metrics_kernel(const MetricsP p) {
                 cnt[0] += 1;
                 cnt[2] -= 1;
                 cnt[1] -= 1;
+                if constexpr (BY) {
+                    slab_add(slab_s, c, 0, 1);
+                    slab_add(slab_s, c, 2, -1);
+                    slab_add(slab_s, c, 1, -1);
+                }
             }
         }
         // ---- DCASE21 segment metrics ----
@@ -241,6 +271,7 @@ __global__ __launch_bounds__(256) void metrics_kernel(const MetricsP p) {
             SELD_DCASE_ADD(cnt, a);
             loc_fn = a.fn;
             loc_fp = a.fp;
+            if constexpr (BY) slab_put_dcase(slab_s, lane, a, total_de);
         }
         const int blk_fn = wave_sum_i32(loc_fn), blk_fp = wave_sum_i32(loc_fp);
         if (lane == 0) {
@@ -248,8 +279,15 @@ __global__ __launch_bounds__(256) void metrics_kernel(const MetricsP p) {
             cnt[7] += max(0, blk_fn - blk_fp);
             cnt[8] += max(0, blk_fp - blk_fn);
         }
+        if constexpr (BY) {
+            slab_put_all(slab_s, p.classes + 1, lane, cnt, total_de);
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_s_waitcnt(0xc07f);
+            for (int i = lane; i < (p.classes + 2) * BY_ROW; i += 64) work[u * ((p.classes + 2) * BY_ROW) + i] = slab_s[i];
+        }
         __builtin_amdgcn_wave_barrier();                // the slice is rewritten by the next unit
     }
+    if constexpr (BY) return;
 
 #pragma unroll
     for (int i = 0; i < NUM_COUNTERS; ++i) {
@@ -260,21 +298,32 @@ __global__ __launch_bounds__(256) void metrics_kernel(const MetricsP p) {
     if (lane == 0 && de != 0.0) atomicAdd(p.total_de, de);
 }
 
+__global__ __launch_bounds__(256) void metrics_kernel(const MetricsP p) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    metrics_body<false>(p, smem, nullptr, nullptr);
+}
+
+__global__ __launch_bounds__(64) void metrics_breakdown_kernel(const MetricsP p, long long* work) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    long long* slab_s = reinterpret_cast<long long*>(smem);
+    metrics_body<true>(p, smem + 2 * (p.classes + 2) * BY_ROW, slab_s, work);
+}
+
 }  // namespace seld
 
 using namespace seld;
 
-extern "C" int seld_metrics_accumulate(const float* sed, const float* doa, const float* target, int32_t clips, int32_t frames,
-                                       int32_t num_frames, int32_t classes, int32_t overlaps, float max_loc_value,
-                                       double spatial_threshold, double doa_threshold, int32_t frames_per_block,
-                                       int64_t* counters, double* total_de, void* stream) {
-    if (clips < 0 || frames < 0 || classes <= 0 || overlaps <= 0 || frames_per_block <= 0 || !counters || !total_de)
+// The checks both calls make and the kernel's arguments (without the outputs).  SELD_OK with p.clips == 0: nothing to do.
+static int metrics_args(const float* sed, const float* doa, const float* target, int32_t clips, int32_t frames, int32_t num_frames,
+                        int32_t classes, int32_t overlaps, float max_loc_value, double spatial_threshold, double doa_threshold,
+                        int32_t frames_per_block, const void* out0, const void* out1, MetricsP& p, size_t& slice) {
+    if (clips < 0 || frames < 0 || classes <= 0 || overlaps <= 0 || frames_per_block <= 0 || !out0 || !out1)
         return SELD_EINVAL;
     if (frames > num_frames) return SELD_EINVAL;       // the reference indexes frames[i[0]] with i[0] < n_frames only
     if (overlaps > 3 || classes * overlaps > 64 || frames_per_block > 64) return SELD_EUNSUPPORTED;   // masks, pair descriptors
+    p.clips = 0;
     if (clips == 0 || frames == 0) return SELD_OK;
     if (!sed || !doa || !target) return SELD_EINVAL;
-    MetricsP p;
     p.sed = sed;
     p.doa = doa;
     p.target = target;
@@ -287,12 +336,26 @@ extern "C" int seld_metrics_accumulate(const float* sed, const float* doa, const
     p.max_loc = max_loc_value;
     p.spatial_threshold = spatial_threshold;
     p.doa_threshold = doa_threshold;
+    p.counters = nullptr;
+    p.total_de = nullptr;
+    // per wave: 2 fpb masks (u64), 9 classes fpb costs (f64), 9 classes fpb pair descriptors / 3 classes fpb matched
+    // distances (f64)
+    slice = (4 * (size_t)frames_per_block + 27 * (size_t)classes * frames_per_block) * sizeof(float);
+    return SELD_OK;
+}
+
+extern "C" int seld_metrics_accumulate(const float* sed, const float* doa, const float* target, int32_t clips, int32_t frames,
+                                       int32_t num_frames, int32_t classes, int32_t overlaps, float max_loc_value,
+                                       double spatial_threshold, double doa_threshold, int32_t frames_per_block,
+                                       int64_t* counters, double* total_de, void* stream) {
+    MetricsP p;
+    size_t slice = 0;
+    const int rc = metrics_args(sed, doa, target, clips, frames, num_frames, classes, overlaps, max_loc_value, spatial_threshold,
+                                doa_threshold, frames_per_block, counters, total_de, p, slice);
+    if (rc != SELD_OK || p.clips == 0) return rc;
     p.counters = reinterpret_cast<long long*>(counters);
     p.total_de = total_de;
     const long long total = (long long)clips * p.blocks;
-    // per wave: 2 fpb masks (u64), 9 classes fpb costs (f64), 9 classes fpb pair descriptors / 3 classes fpb matched
-    // distances (f64)
-    const size_t slice = (4 * (size_t)frames_per_block + 27 * (size_t)classes * frames_per_block) * sizeof(float);
     const int wpw = 1;                                   // waves per workgroup (15 KB of LDS at 14 x 3 x 10: 10 workgroups per CU)
     const size_t smem = wpw * slice;
     if (smem > 64 * 1024) return SELD_EUNSUPPORTED;
@@ -300,4 +363,36 @@ extern "C" int seld_metrics_accumulate(const float* sed, const float* doa, const
     if (wgs > 4096) wgs = 4096;                          // 2 generations of resident waves; waves loop over their units
     hipLaunchKernelGGL(metrics_kernel, dim3((unsigned)wgs), dim3(64 * wpw), smem, (hipStream_t)stream, p);
     return check_launch();
+}
+
+extern "C" int seld_metrics_breakdown(const float* sed, const float* doa, const float* target, int32_t clips, int32_t frames,
+                                      int32_t num_frames, int32_t classes, int32_t overlaps, float max_loc_value,
+                                      double spatial_threshold, double doa_threshold, int32_t frames_per_block,
+                                      int64_t* counters, double* total_de, void* workspace, size_t workspace_bytes, void* stream) {
+    MetricsP p;
+    size_t slice = 0;
+    const int rc = metrics_args(sed, doa, target, clips, frames, num_frames, classes, overlaps, max_loc_value, spatial_threshold,
+                                doa_threshold, frames_per_block, counters, total_de, p, slice);
+    if (rc != SELD_OK || clips == 0) return rc;
+    BreakdownP b;
+    b.work = reinterpret_cast<const long long*>(workspace);
+    b.flags = nullptr;
+    b.recordings = clips;
+    b.blocks = p.clips ? p.blocks : 0;                   // no frames: the table is zeros
+    b.rows = classes + 2;
+    b.counters = reinterpret_cast<long long*>(counters);
+    b.total_de = total_de;
+    const size_t need = breakdown_workspace_bytes(b.recordings, b.blocks, classes);
+    if (need && (!workspace || workspace_bytes < need)) return SELD_EWORKSPACE;
+    if (b.blocks) {
+        const size_t smem = slice + (size_t)(classes + 2) * BY_ROW * sizeof(long long);
+        if (smem > 64 * 1024) return SELD_EUNSUPPORTED;  // the slab beside the slice; the plain call's limit is the slice alone
+        long long wgs = (long long)clips * p.blocks;
+        if (wgs > 4096) wgs = 4096;
+        hipLaunchKernelGGL(metrics_breakdown_kernel, dim3((unsigned)wgs), dim3(64), smem, (hipStream_t)stream, p,
+                           reinterpret_cast<long long*>(workspace));
+        const int rc2 = check_launch();
+        if (rc2 != SELD_OK) return rc2;
+    }
+    return launch_breakdown_reduce(b, (hipStream_t)stream);
 }

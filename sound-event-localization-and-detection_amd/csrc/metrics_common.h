@@ -1,6 +1,7 @@
 // Device functions shared by the two metric kernel families: metrics.hip (dense network outputs) and event_metrics.hip
 // (event rows).  Both compute the DCASE21 block metrics of Dcase21_metrics.py:51-154 with the code below, so a result
-// cannot differ between them by more than the order of the final atomics.
+// cannot differ between them by more than the order of the final atomics.  The second half of the file is what their
+// breakdowns by recording and class share: the slab a unit writes and the kernel that adds the slabs up.
 #pragma once
 #include "common.h"
 
@@ -231,5 +232,88 @@ __device__ __forceinline__ DcaseAdd dcase_class_block(int nb_gt, int nb_pred, do
         cnt[3] += (a).tp; cnt[4] += (a).fp; cnt[5] += (a).fn; cnt[9] += (a).nref; \
         cnt[10] += (a).de_tp; cnt[11] += (a).de_fp; cnt[12] += (a).de_fn; \
     } while (0)
+
+// ---- the breakdown by recording and class (seld_event_metrics_breakdown, seld_metrics_breakdown) ----
+// A slab is what one (recording, block) unit adds, one row per class, then "other", then "all": BY_ROW 8-byte words a
+// row, the 16 counters in EVENT_METRIC_COUNTERS order and the row's total_DE as a double.  A wave builds the slab of its
+// unit in LDS (rows of classes with LDS integer atomics for the detection counters, whose lanes are list rows; plain
+// stores by the class's own lane for the DCASE counters), copies it to slab `unit` of the workspace, and
+// breakdown_reduce_kernel adds the slabs of a recording in block order: no global atomics, nothing to zero beforehand,
+// the same bits every run.
+constexpr int BY_COUNTERS = 16;
+constexpr int BY_ROW = BY_COUNTERS + 1;
+
+inline size_t breakdown_workspace_bytes(long long recordings, long long blocks, int classes) {
+    return (size_t)recordings * (size_t)blocks * (size_t)(classes + 2) * BY_ROW * sizeof(long long);
+}
+
+// one more count in counter k of class row `row` of the LDS slab (v may be negative)
+__device__ __forceinline__ void slab_add(long long* slab, int row, int k, int v) {
+    atomicAdd(reinterpret_cast<unsigned long long*>(slab + row * BY_ROW + k), (unsigned long long)(long long)v);
+}
+
+// what class `row` of one block adds to the DCASE counters, by the row's own lane; S, D, I from the class's own
+// loc_FP / loc_FN (the class-wise definition behind DCASE's macro average)
+__device__ __forceinline__ void slab_put_dcase(long long* slab, int row, const DcaseAdd& a, double de) {
+    long long* s = slab + row * BY_ROW;
+    s[3] = a.tp; s[4] = a.fp; s[5] = a.fn;
+    s[6] = min(a.fp, a.fn); s[7] = max(0, a.fn - a.fp); s[8] = max(0, a.fp - a.fn);
+    s[9] = a.nref; s[10] = a.de_tp; s[11] = a.de_fp; s[12] = a.de_fn;
+    reinterpret_cast<double*>(s)[BY_COUNTERS] = de;
+}
+
+// row "all" of the slab: the wave's sums of what the unit added to the lanes' counters, which is what the plain call adds
+template <int N>
+__device__ __forceinline__ void slab_put_all(long long* slab, int row, int lane, const long long (&cnt)[N], double total_de) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        const long long s = wave_sum_i64(cnt[i]);
+        if (lane == 0) slab[row * BY_ROW + i] = s;
+    }
+    const double de = wave_sum_d(total_de);
+    if (lane == 0) reinterpret_cast<double*>(slab)[row * BY_ROW + BY_COUNTERS] = de;
+}
+
+struct BreakdownP {
+    const long long* work;          // (recordings, blocks, rows, BY_ROW) slabs
+    const long long* flags;         // flags[1] != 0: a refused call, the table is zeros (NULL: never refused)
+    long long recordings, blocks;
+    int rows;                       // classes + 2
+    long long* counters;            // (recordings, rows, 16)
+    double* total_de;               // (recordings, rows)
+};
+
+// One thread per word of the table; the blocks of its recording in ascending order.  Neighbouring threads read
+// neighbouring words of a slab.
+template <int ROW>
+__global__ __launch_bounds__(256) void breakdown_reduce_kernel(const BreakdownP p) {
+    const long long words = p.recordings * p.rows * ROW;
+    const bool refused = p.flags && p.flags[1] != 0;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < words; i += (long long)gridDim.x * blockDim.x) {
+        const long long rec = i / ((long long)p.rows * ROW);
+        const int w = (int)(i - rec * p.rows * ROW), row = w / ROW, k = w - row * ROW;
+        const long long* src = p.work + rec * p.blocks * p.rows * ROW + w;
+        if (k < ROW - 1) {
+            long long s = 0;
+            if (!refused)
+                for (long long b = 0; b < p.blocks; ++b) s += src[b * p.rows * ROW];
+            p.counters[(rec * p.rows + row) * (ROW - 1) + k] = s;
+        } else {
+            double s = 0.0;
+            if (!refused)
+                for (long long b = 0; b < p.blocks; ++b) s += reinterpret_cast<const double*>(src)[b * p.rows * ROW];
+            p.total_de[rec * p.rows + row] = s;
+        }
+    }
+}
+
+inline int launch_breakdown_reduce(const BreakdownP& p, hipStream_t stream) {
+    const long long words = p.recordings * p.rows * BY_ROW;
+    if (words == 0) return SELD_OK;
+    long long wgs = (words + 255) / 256;
+    if (wgs > 4096) wgs = 4096;
+    hipLaunchKernelGGL(breakdown_reduce_kernel<BY_ROW>, dim3((unsigned)wgs), dim3(256), 0, stream, p);
+    return check_launch();
+}
 
 }  // namespace seld

@@ -5,11 +5,11 @@ import numpy as np
 import torch
 
 from .. import _lib as L
-from ._core import timed
-from .train_ops import METRIC_COUNTERS
+from ._core import scratch, timed
+from .train_ops import METRIC_COUNTERS, breakdown_out
 
 __all__ = ["EVENT_METRIC_COUNTERS", "EVENT_METRICS_MAX_TRACKS", "EVENT_METRICS_MAX_TRACKS_EX", "assign_doas",
-           "event_metrics_new", "score_events", "sort_events"]
+           "event_metrics_new", "score_events", "score_events_by", "sort_events"]
 
 EVENT_METRIC_COUNTERS = METRIC_COUNTERS + ("sed_TP", "sed_FP", "sed_FN")
 EVENT_METRICS_MAX_TRACKS = 3        # SELD_EVENT_METRICS_MAX_TRACKS: events of one class in one frame the association takes
@@ -52,6 +52,41 @@ def sort_events(rows, offsets):
     return rows[by_frame[torch.sort(rec, stable=True).indices]].contiguous()
 
 
+def _check_lists(pred_rows, pred_offsets, true_rows, true_offsets, coords, max_tracks):
+    """The checks score_events and score_events_by share; returns the four tensors as the library takes them."""
+    if coords not in (2, 3):
+        raise L.SeldHipError(f"score_events: coords must be 3 (x, y, z) or 2 (azimuth, elevation in degrees), got {coords!r}")
+    if isinstance(max_tracks, bool) or not isinstance(max_tracks, (int, np.integer)) \
+            or not 1 <= max_tracks <= EVENT_METRICS_MAX_TRACKS_EX:
+        raise L.SeldHipError(f"score_events: max_tracks must be an integer in 1 .. {EVENT_METRICS_MAX_TRACKS_EX}, "
+                             f"got {max_tracks!r}")
+    pred_rows, pred_offsets = _check_side(pred_rows, pred_offsets, "pred", coords)
+    true_rows, true_offsets = _check_side(true_rows, true_offsets, "true", coords)
+    if pred_offsets.shape[0] != true_offsets.shape[0]:
+        raise L.SeldHipError(f"score_events: {pred_offsets.shape[0] - 1} predicted recordings against "
+                             f"{true_offsets.shape[0] - 1} reference recordings")
+    return pred_rows, pred_offsets, true_rows, true_offsets
+
+
+def _check_flags(flags, dev):
+    """(flags, read_back): a new pair of flags that the call reads back itself, or the caller's, checked."""
+    if flags is None:
+        return torch.empty(2, device=dev, dtype=torch.int64), True
+    if (not torch.is_tensor(flags) or flags.device != dev or flags.dtype != torch.int64 or flags.numel() != 2
+            or not flags.is_contiguous()):
+        raise L.SeldHipError("score_events: flags must be a contiguous int64 device tensor of two entries")
+    return flags, False
+
+
+def _raise_if_refused(flags, max_tracks):
+    cells = int(flags[1].item())                        # the one read-back
+    if cells:
+        raise L.SeldHipError(f"score_events: {cells} (recording, frame, class) cells hold more than "
+                             f"{max_tracks} events; the track association takes "
+                             f"{max_tracks} x {max_tracks} at most (max_tracks = {max_tracks}, up to "
+                             f"{EVENT_METRICS_MAX_TRACKS_EX} can be asked for)")
+
+
 def score_events(acc, pred_rows, pred_offsets, true_rows, true_offsets, n_frames, nb_classes=14, spatial_threshold=2.,
                  doa_threshold=20, frames_per_block=10, coords=3, max_tracks=EVENT_METRICS_MAX_TRACKS, flags=None):
     """Score predicted against reference event rows of a batch of recordings and add the counters to `acc`
@@ -71,29 +106,15 @@ def score_events(acc, pred_rows, pred_offsets, true_rows, true_offsets, n_frames
     frame is no integer in [0, n_frames) are left out of the detection counters and are not an error here (the drop-in
     metrics module turns them into the reference's KeyError).  With `flags` given (a device int64 tensor of two entries)
     nothing is read back and nothing is raised: the caller reads [rows with a frame out of range, overflowing cells]."""
-    if coords not in (2, 3):
-        raise L.SeldHipError(f"score_events: coords must be 3 (x, y, z) or 2 (azimuth, elevation in degrees), got {coords!r}")
-    if isinstance(max_tracks, bool) or not isinstance(max_tracks, (int, np.integer)) \
-            or not 1 <= max_tracks <= EVENT_METRICS_MAX_TRACKS_EX:
-        raise L.SeldHipError(f"score_events: max_tracks must be an integer in 1 .. {EVENT_METRICS_MAX_TRACKS_EX}, "
-                             f"got {max_tracks!r}")
-    pred_rows, pred_offsets = _check_side(pred_rows, pred_offsets, "pred", coords)
-    true_rows, true_offsets = _check_side(true_rows, true_offsets, "true", coords)
-    if pred_offsets.shape[0] != true_offsets.shape[0]:
-        raise L.SeldHipError(f"score_events: {pred_offsets.shape[0] - 1} predicted recordings against "
-                             f"{true_offsets.shape[0] - 1} reference recordings")
+    pred_rows, pred_offsets, true_rows, true_offsets = _check_lists(pred_rows, pred_offsets, true_rows, true_offsets, coords,
+                                                                    max_tracks)
     counters, total_de = acc
     dev = counters.device
     if any(t.device != dev for t in (total_de, pred_rows, pred_offsets, true_rows, true_offsets)):
         raise L.SeldHipError("score_events: the accumulators and the event lists are on different devices")
     if counters.dtype != torch.int64 or counters.numel() != len(EVENT_METRIC_COUNTERS) or total_de.dtype != torch.float64:
         raise L.SeldHipError(f"score_events: acc must come from event_metrics_new ({len(EVENT_METRIC_COUNTERS)} int64, 1 double)")
-    read_back = flags is None
-    if read_back:
-        flags = torch.empty(2, device=dev, dtype=torch.int64)
-    elif (not torch.is_tensor(flags) or flags.device != dev or flags.dtype != torch.int64 or flags.numel() != 2
-          or not flags.is_contiguous()):
-        raise L.SeldHipError("score_events: flags must be a contiguous int64 device tensor of two entries")
+    flags, read_back = _check_flags(flags, dev)
     R = pred_offsets.shape[0] - 1
     Ep, Et = pred_rows.shape[0], true_rows.shape[0]
     with torch.cuda.device(dev):
@@ -103,13 +124,43 @@ def score_events(acc, pred_rows, pred_offsets, true_rows, true_offsets, n_frames
                 int(nb_classes), int(frames_per_block), coords, int(max_tracks), float(spatial_threshold), float(doa_threshold),
                 L.ptr(counters), L.ptr(total_de), L.ptr(flags), L.current_stream()), "seld_event_metrics_accumulate_ex")
         if read_back:
-            cells = int(flags[1].item())                # the one read-back
-            if cells:
-                raise L.SeldHipError(f"score_events: {cells} (recording, frame, class) cells hold more than "
-                                     f"{max_tracks} events; the track association takes "
-                                     f"{max_tracks} x {max_tracks} at most (max_tracks = {max_tracks}, up to "
-                                     f"{EVENT_METRICS_MAX_TRACKS_EX} can be asked for)")
+            _raise_if_refused(flags, max_tracks)
     return acc
+
+
+def score_events_by(pred_rows, pred_offsets, true_rows, true_offsets, n_frames, nb_classes=14, spatial_threshold=2.,
+                    doa_threshold=20, frames_per_block=10, coords=3, max_tracks=EVENT_METRICS_MAX_TRACKS, flags=None, out=None):
+    """`score_events` broken down by recording and class (seld_event_metrics_breakdown, include/seld_hip.h): the lists, the
+    checks, the flags and the refusal rule are score_events'.
+
+    Returns (counters (R, C + 2, 16) int64 in EVENT_METRIC_COUNTERS order, total_de (R, C + 2) float64), C = nb_classes,
+    WRITTEN (not added to) into `out` when given, so successive batches can go to successive slices of one table.  Rows
+    0 .. C - 1: what each class contributes (S, D, I class-wise, the detection counters row by row); row C ("other"): the
+    rows whose class is no integer in [0, C), which only the detection counters see; row C + 1 ("all"): what
+    `score_events` adds to `acc` for that recording.  A call refused for an overflowing cell has written zeros.
+    `class_metrics` turns the tables into per-class scores, macro averages and leave-one-recording-out estimates."""
+    pred_rows, pred_offsets, true_rows, true_offsets = _check_lists(pred_rows, pred_offsets, true_rows, true_offsets, coords,
+                                                                    max_tracks)
+    dev = pred_rows.device
+    if any(t.device != dev for t in (pred_offsets, true_rows, true_offsets)):
+        raise L.SeldHipError("score_events_by: the event lists are on different devices")
+    R = pred_offsets.shape[0] - 1
+    counters, total_de = breakdown_out(out, R, int(nb_classes), dev, "score_events_by")
+    flags, read_back = _check_flags(flags, dev)
+    Ep, Et = pred_rows.shape[0], true_rows.shape[0]
+    nbytes = L.lib().seld_metrics_breakdown_workspace(R, int(n_frames), int(nb_classes), int(frames_per_block))
+    with torch.cuda.device(dev):
+        work = scratch("metrics_breakdown", max(nbytes, 8), dev)
+        with timed("event_breakdown_kernel",
+                   lambda: (0.0, float((Ep + Et) * (8 * (2 + coords) + 16) + 2 * (R + 1) * 8 + 2 * nbytes))):
+            L.check(L.lib().seld_event_metrics_breakdown(
+                L.ptr(pred_rows), L.ptr(pred_offsets), Ep, L.ptr(true_rows), L.ptr(true_offsets), Et, R, int(n_frames),
+                int(nb_classes), int(frames_per_block), coords, int(max_tracks), float(spatial_threshold), float(doa_threshold),
+                L.ptr(counters), L.ptr(total_de), L.ptr(work), work.numel(), L.ptr(flags), L.current_stream()),
+                "seld_event_metrics_breakdown")
+        if read_back:
+            _raise_if_refused(flags, max_tracks)
+    return counters, total_de
 
 
 def assign_doas(gt, pred, gt_counts, pred_counts, spherical=False):

@@ -3,7 +3,7 @@
 import torch
 
 from .. import _lib as L
-from ._core import _req
+from ._core import _req, scratch, timed
 
 
 # ======================================================================================
@@ -228,6 +228,51 @@ def metrics_accumulate(acc, sed, doa, target, num_frames, num_classes=14, max_ov
                                             L.current_stream()),
             "seld_metrics_accumulate")
     return acc
+
+
+def breakdown_out(out, recordings, num_classes, device, what):
+    """The (counters (R, C + 2, 16) int64, total_de (R, C + 2) float64) tables of a breakdown call: `out` checked, or new
+    ones (uninitialised: the calls write every entry)."""
+    if num_classes < 0:
+        raise L.SeldHipError(f"{what}: {num_classes} classes")
+    shape = (recordings, num_classes + 2)
+    if out is None:
+        return (torch.empty(shape + (16,), device=device, dtype=torch.int64), torch.empty(shape, device=device, dtype=torch.float64))
+    counters, total_de = out
+    for t, dtype, want in ((counters, torch.int64, shape + (16,)), (total_de, torch.float64, shape)):
+        if not torch.is_tensor(t) or t.device != device or t.dtype != dtype or tuple(t.shape) != want or not t.is_contiguous():
+            raise L.SeldHipError(f"{what}: out must be contiguous (int64 {shape + (16,)}, float64 {shape}) tensors on {device}")
+    return counters, total_de
+
+
+def metrics_accumulate_by(sed, doa, target, num_frames, num_classes=14, max_overlaps=3, max_loc_value=2.0,
+                          spatial_threshold=2.0, doa_threshold=20, frames_per_block=10, out=None):
+    """`metrics_accumulate` broken down by recording and class (seld_metrics_breakdown, include/seld_hip.h).
+
+    Returns (counters (R, C + 2, 16) int64 in EVENT_METRIC_COUNTERS order, total_de (R, C + 2) float64), WRITTEN into `out`
+    when given (a slice of a larger table, say): rows 0 .. C - 1 the classes, row C ("other") zero on this path as are
+    counters 13..15, row C + 1 ("all") what `metrics_accumulate` adds for that recording.  `class_metrics` turns the tables
+    into per-class and macro scores.  Nothing is read back."""
+    sed, doa, target = _req(sed, "sed"), _req(doa, "doa"), _req(target, "target")
+    n = num_classes * max_overlaps
+    if sed.dim() == 2:
+        sed, doa, target = sed[None], doa[None], target[None]
+    clips, frames = sed.shape[0], sed.shape[1]
+    if tuple(sed.shape) != (clips, frames, n) or tuple(doa.shape) != (clips, frames, 3 * n) or \
+            tuple(target.shape) != (clips, frames, 4 * n):
+        raise L.SeldHipError(f"metrics_accumulate_by: shapes {tuple(sed.shape)} / {tuple(doa.shape)} / {tuple(target.shape)} do "
+                             f"not match (clips, frames, {n}) / (.., {3 * n}) / (.., {4 * n})")
+    counters, total_de = breakdown_out(out, clips, int(num_classes), sed.device, "metrics_accumulate_by")
+    nbytes = L.lib().seld_metrics_breakdown_workspace(clips, frames, int(num_classes), int(frames_per_block))
+    with torch.cuda.device(sed.device):
+        work = scratch("metrics_breakdown", max(nbytes, 8), sed.device)
+        with timed("metrics_breakdown_kernel", lambda: (0.0, float(sed.numel() * 32 + 2 * nbytes))):
+            L.check(L.lib().seld_metrics_breakdown(L.ptr(sed), L.ptr(doa), L.ptr(target), clips, frames, int(num_frames),
+                                                   int(num_classes), int(max_overlaps), max_loc_value, spatial_threshold,
+                                                   doa_threshold, int(frames_per_block), L.ptr(counters), L.ptr(total_de),
+                                                   L.ptr(work), work.numel(), L.current_stream()),
+                    "seld_metrics_breakdown")
+    return counters, total_de
 
 
 def decode_events(sed, doa, max_loc_value=2., num_classes=14, max_overlaps=3):

@@ -13,6 +13,7 @@ this file restates its behaviour rather than its text.
 import argparse
 import ast
 import functools
+import json
 import os
 import pickle
 import shutil
@@ -23,6 +24,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
+from . import class_metrics as CM
 from . import hip_ops as H
 from .model import SE_MODES, SELD_Model
 
@@ -428,7 +430,7 @@ _FLAGS = [
 ]
 _EVAL = ('use_cuda', 'early_stopping', 'fixed_seed', 'pool_size', 'cnn_filters', 'verbose', 'D', 'V', 'use_lr_scheduler',
          'phase', 'use_tcn', 'use_bias_conv', 'use_bias_linear', 'fc_layers', 'parallel_magphase',
-         'resident_loader', 'graph_step', 'pit_loss')
+         'resident_loader', 'graph_step', 'pit_loss', 'class_report')
 # extensions of this implementation (not in the reference): synthetic data so the step can run without L3DAS21;
 # resident_loader: minibatches gathered on the device (ResidentLoader) instead of a DataLoader over the resident arrays;
 # graph_step (needs resident_loader): full batches run as replays of one recorded step (GraphedTrainStep);
@@ -457,14 +459,20 @@ _EVAL = ('use_cuda', 'early_stopping', 'fixed_seed', 'pool_size', 'cnn_filters',
 # on the device before it is scored (hip_ops.smooth_tracks) -- post_median: odd window of a median filter on the activity;
 # post_on / post_off: hysteresis, a stretch above post_off is an event iff it holds a frame above post_on;
 # post_max_gap: gaps of at most so many frames between two events are filled; post_min_frames: shorter events are
-# dropped; post_doa: frame, mean or weighted -- one DOA per event
+# dropped; post_doa: frame, mean or weighted -- one DOA per event;
+# class_report (off by default): the test leg scores with hip_ops.metrics_accumulate_by, returns and prints the same 16
+# results (from row "all" of the table), then prints per class Nref, precision / recall / F1 and ER, F, LE, LR, the class-wise
+# macro averages with their leave-one-recording-out standard errors (class_metrics), and writes class_report.json under
+# results_path; metrics_average: micro or macro -- which ER, F, LE, LR feed the early stopping metric the report states
+# (macro builds the table too; the 16 results stay the micro ones either way)
 _EXTRA = [('synthetic', int, 0), ('max_steps', int, 0), ('epochs', int, 0), ('resident_loader', str, 'False'),
           ('graph_step', str, 'False'), ('augment_swap', float, 0.), ('augment_freq_masks', int, 0),
           ('augment_freq_width', int, 0), ('augment_time_masks', int, 0), ('augment_time_width', int, 0),
           ('augment_seed', int, 0), ('feature_layout', str, 'magphase'), ('augment_rotate', float, 0.),
           ('pit_loss', str, 'False'), ('test_hop', int, 0), ('test_tta', int, 0),
           ('post_median', int, 1), ('post_on', float, 0.5), ('post_off', float, 0.5), ('post_min_frames', int, 1),
-          ('post_max_gap', int, 0), ('post_doa', str, 'frame'), ('se_reduction', int, 0), ('se_mode', str, 'both')]
+          ('post_max_gap', int, 0), ('post_doa', str, 'frame'), ('se_reduction', int, 0), ('se_mode', str, 'both'),
+          ('class_report', str, 'False'), ('metrics_average', str, 'micro')]
 
 
 def build_parser():
@@ -956,26 +964,96 @@ def _print_test_results(results):
         print(label, v)
 
 
+def class_report_from_args(args):
+    """(report, average) of the --class_report / --metrics_average flags; an args object without them counts as (False,
+    'micro').  Every refusal comes before the device is touched."""
+    report, average = getattr(args, "class_report", False), getattr(args, "metrics_average", "micro")
+    if not isinstance(report, (bool, int)):
+        raise ValueError(f"--class_report is True or False, got {report!r}")
+    if average not in ("micro", "macro"):
+        raise ValueError(f"--metrics_average is micro or macro, got {average!r}")
+    return bool(report), average
+
+
+def _results_from_table(counters, total_de, epoch):
+    """The 16 results from row "all" of a breakdown table (numpy, all recordings)."""
+    all_c, all_de = CM.totals(counters, total_de)
+    counts = dict(zip(H.METRIC_COUNTERS, all_c[-1].tolist()))
+    return test_results_from_counters(counts, float(all_de[-1]), epoch)
+
+
+def class_report(counters, total_de, results, epoch=0, average="micro", report=True, results_path=None):
+    """The per-class report of a test leg from its breakdown table (numpy (R, C + 2, 16) and (R, C + 2)): printed, returned
+    as a dict and, with `results_path`, written to <results_path>/class_report.json.  report=False (metrics_average=macro
+    alone): the macro line only, nothing written."""
+    scores = CM.class_scores(counters, total_de)
+    macro = CM.macro_scores(counters, total_de)
+    jack = CM.jackknife(counters, total_de) if counters.shape[0] >= 2 else None
+    names = ("ER", "F", "LE", "LR", "early_stopping_metric")
+    stderr = dict(zip(names, jack["stderr"].tolist())) if jack is not None else None
+    micro = dict(ER=results[12], F=results[13], LE=results[14], LR=results[15], early_stopping_metric=results[11])
+    chosen = macro if average == "macro" else micro
+    out = dict(epoch=int(epoch), recordings=int(counters.shape[0]), metrics_average=average,
+               early_stopping_metric=float(chosen["early_stopping_metric"]),
+               micro={k: float(v) for k, v in micro.items()}, macro={k: float(macro[k]) for k in names},
+               macro_classes=macro["classes"], macro_jackknife_stderr=stderr,
+               classes=[{k: (int(v[c]) if k == "Nref" else float(v[c])) for k, v in scores.items()}
+                        for c in range(len(scores["Nref"]))])
+    if report:
+        print("class  Nref  precision  recall      F1       ER        F       LE       LR")
+        for c, row in enumerate(out["classes"]):
+            print(f"{c:5d} {row['Nref']:5d} {row['precision']:10.4f} {row['recall']:7.4f} {row['f1']:7.4f} {row['ER']:8.4f} "
+                  f"{row['F']:8.4f} {row['LE']:8.3f} {row['LR']:8.4f}")
+    print("macro (%d classes): " % macro["classes"]
+          + "  ".join(f"{k} {macro[k]:.4f}" + (f" +- {stderr[k]:.4f}" if stderr else "") for k in names))
+    print(f"early stopping metric ({average}): {out['early_stopping_metric']}")
+    if report and results_path:
+        os.makedirs(results_path, exist_ok=True)
+        with open(os.path.join(results_path, "class_report.json"), "w") as f:
+            json.dump(out, f, indent=1)
+    return out
+
+
 def evaluate_test(model, device, dataloader, epoch=0, max_loc_value=2., num_frames=600, spatial_threshold=2., args=None):
     """train.py:84-166: same arguments, same 16-entry result list.  The network outputs never leave the device: each
-    batch's decode + counting is one kernel (hip_ops.metrics_accumulate) and the counters are read back once."""
+    batch's decode + counting is one kernel (hip_ops.metrics_accumulate) and the counters are read back once.
+    --class_report / --metrics_average=macro: the counting is hip_ops.metrics_accumulate_by, the results come from row
+    "all" of its table (the same numbers) and class_report prints and writes the rest."""
     output_classes = args.output_classes if args is not None else 14
     class_overlaps = args.class_overlaps if args is not None else 3
     doa_threshold = args.Dcase21_metrics_DOA_threshold if args is not None else 20
     post = postprocess_from_args(args) if args is not None else None
+    report, average = class_report_from_args(args)
+    by = report or average == "macro"
     model.eval()
-    acc = H.metrics_new(device)
+    acc, tables = H.metrics_new(device), []
     with torch.no_grad():
         for x, target in dataloader:
             sed, doa = model(x.to(device))
             if post is not None:
                 sed, doa = H.smooth_tracks(sed, doa, **post.kwargs())
             # gen_submission_list_task2 is called with its default num_classes = 14 (train.py:110-116)
-            H.metrics_accumulate(acc, sed, doa, target.to(device), num_frames, 14, class_overlaps, max_loc_value,
-                                 spatial_threshold, doa_threshold)
+            if by:
+                tables.append(H.metrics_accumulate_by(sed, doa, target.to(device), num_frames, 14, class_overlaps, max_loc_value,
+                                                      spatial_threshold, doa_threshold))
+            else:
+                H.metrics_accumulate(acc, sed, doa, target.to(device), num_frames, 14, class_overlaps, max_loc_value,
+                                     spatial_threshold, doa_threshold)
+    if by:
+        return _report_results(tables, epoch, args, report, average)
     counts = dict(zip(H.METRIC_COUNTERS, acc[0].cpu().tolist()))
     results = test_results_from_counters(counts, float(acc[1].item()), epoch)
     _print_test_results(results)
+    return results
+
+
+def _report_results(tables, epoch, args, report, average):
+    """The close of a test leg that scored with metrics_accumulate_by: one read-back of the tables, the 16 results, the report."""
+    counters = torch.cat([t[0] for t in tables]).cpu().numpy()
+    total_de = torch.cat([t[1] for t in tables]).cpu().numpy()
+    results = _results_from_table(counters, total_de, epoch)
+    _print_test_results(results)
+    class_report(counters, total_de, results, epoch, average, report, getattr(args, "results_path", None))
     return results
 
 
@@ -1142,6 +1220,11 @@ def evaluate_recordings(model, device, x_all, y_all, args, *, hop, table, epoch=
                                   batch=batch, frames=y_all.shape[1])
     if post is not None:
         sed, doa = H.smooth_tracks(sed, doa, **post.kwargs())
+    report, average = class_report_from_args(args)
+    if report or average == "macro":                    # one launch for all recordings: the table keeps them apart
+        table = H.metrics_accumulate_by(sed, doa, y_all.to(device), num_frames, 14, args.class_overlaps, max_loc_value,
+                                        spatial_threshold, args.Dcase21_metrics_DOA_threshold)
+        return _report_results([table], epoch, args, report, average)
     acc = H.metrics_new(device)
     for r in range(sed.shape[0]):                       # one recording per launch, as evaluate_test's loader gives them
         H.metrics_accumulate(acc, sed[r:r + 1], doa[r:r + 1], y_all[r:r + 1].to(device), num_frames, 14, args.class_overlaps,
@@ -1180,6 +1263,7 @@ def main(args, history=None):
         raise ValueError("--augment_* flags need --resident_loader (the augmentation is part of the device gather)")
     ensemble = ensemble_from_args(args)
     post = postprocess_from_args(args)
+    class_report_from_args(args)
     pit = pit_overlaps_from_args(args)
     se_from_args(args)
     if pit > 3:
