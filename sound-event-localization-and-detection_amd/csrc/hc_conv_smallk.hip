@@ -389,7 +389,9 @@ static int launch_smallk(const ConvP& p, hipStream_t st) {
     int NG, NGP;
     smallk_groups(p, &NG, &NGP);
     const long long ntiles = (p.Ptot + TP - 1) / TP;
-    const size_t smem_generic = ((size_t)NG * CT * 16 * 4 + (size_t)NG * TP * 4) * sizeof(float);
+    // the im2col image doubles as the statistics fold's [NW][BC][2] buffer: below CT / 2 k-groups the fold is the larger
+    const size_t x_floats = (size_t)NG * TP * 4, red_floats = (size_t)NW * CT * 16 * 2;
+    const size_t smem_generic = ((size_t)NG * CT * 16 * 4 + (x_floats > red_floats ? x_floats : red_floats)) * sizeof(float);
 #define SELD_SK(KH_, KW_, NG_, NGP_)                                                                               \
     do {                                                                                                           \
         auto kern = hc_conv_smallk_kernel<CT, KH_, KW_, NW, NG_, NGP_>;                                            \

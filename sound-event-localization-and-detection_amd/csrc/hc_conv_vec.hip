@@ -448,7 +448,7 @@ __global__ __launch_bounds__(256) void hc_conv_vec_kernel(const ConvP p) {
         if (epi & SELD_EPI_STATS) {
             static_assert(sizeof(Xs) >= 4 * BC * 2 * sizeof(float), "statistics scratch fits the X staging buffers");
             __syncthreads();
-            const float* redbuf = &Xs[0][0][0];
+            const float* redbuf = FWD_PAIR ? pair_red_s : &Xs[0][0][0];      // where the partial sums were put above
             float* rep = statsz + (size_t)(blockIdx.x % SELD_STATS_REPLICAS) * 2 * p.Cdst;
             for (int t = tid; t < BC; t += 256) {
                 const int ch = chan_of(t);
