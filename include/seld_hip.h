@@ -751,6 +751,40 @@ int seld_adam_flat_state(float* param, const float* grad, float* exp_avg, float*
                          uint64_t* state, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The optimiser's extras: clipping by global norm, decoupled (AdamW) decay, an exponential moving average of the weights.
+ *
+ * seld_grad_norm: one launch, nothing read back, no float atomics.  With x[i] = grad[i] * grad_scale rounded to fp32 (the
+ * product seld_adam_flat forms), squares and sums in fp64 and ONE rounding to fp32 after the square root, it writes
+ *     clip[0] = ||x||_2
+ *     clip[1] = min(1, max_norm / (clip[0] + 1e-6f))      torch.nn.utils.clip_grad_norm_'s coefficient: an infinite norm
+ *                                                         gives 0, a NaN norm NaN; no step is skipped
+ *     clip[2] = max(clip[2], clip[0])                     the largest norm since the host zeroed it (a NaN norm is not kept)
+ *     clip[3] += (clip[1] < 1)                            the steps that were clipped since the host zeroed it
+ * clip: 4 floats on the device.  The grid depends on n alone and the workgroup sums are added in a fixed order by the last
+ * workgroup to finish, so two runs give the same bits; the scratch is a per-device static of the library (not the loss
+ * kernels'), so launches on ONE device must not overlap on different streams.  n == 0: norm 0, coefficient 1.
+ * SELD_EINVAL: NULL grad with n > 0, NULL clip, n < 0, max_norm not greater than 0.
+ *
+ * seld_adam_flat_ex / seld_adam_flat_state_ex: seld_adam_flat / seld_adam_flat_state with, per element,
+ *     g' = (grad * grad_scale) * clip[1]                  clip (nullable) read on the device; NULL: no multiply
+ *     decoupled == 0:  g' = fma(weight_decay, p, g')      as seld_adam_flat
+ *     decoupled != 0:  p <- p * (1 - lr * weight_decay)   torch.optim.AdamW; g' gets no decay term
+ *     m, v and the update as seld_adam_flat
+ *     ema = d * ema + (1 - d) * p_new,  d = min(ema_decay, (1 + step) / (10 + step))      ema nullable; step 1-based
+ *         (evaluated as ema + (1 - d) * (p_new - ema): an average equal to the weight stays on it bit for bit)
+ * With clip NULL, ema NULL and decoupled 0 they give the bits of seld_adam_flat / seld_adam_flat_state.  The state entry
+ * ends the step as seld_adam_flat_state does (state[0] += state[3]), for n == 0 too.
+ * SELD_EINVAL: as seld_adam_flat / seld_adam_flat_state, or ema given with an ema_decay outside [0, 1).
+ * ------------------------------------------------------------------------------------------ */
+int seld_grad_norm(const float* grad, int64_t n, float grad_scale, float max_norm, float* clip, void* stream);
+int seld_adam_flat_ex(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float* ema, int64_t n,
+                      float lr, float beta1, float beta2, float eps, float weight_decay, int32_t decoupled,
+                      int32_t step, float grad_scale, const float* clip, float ema_decay, void* stream);
+int seld_adam_flat_state_ex(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float* ema, int64_t n,
+                            float beta1, float beta2, float eps, float weight_decay, int32_t decoupled,
+                            float grad_scale, const float* clip, float ema_decay, uint64_t* state, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * STFT magnitude / phase (utility_functions.py:129-155 = scipy.signal.stft(window='hamming',
  * boundary='zeros', padded=True) -> abs/angle -> drop DC bin -> drop last frame).
  * x (C, L) fp32; out (C or 2C, nperseg/2, frames-1) fp32, phase channels after magnitude channels.

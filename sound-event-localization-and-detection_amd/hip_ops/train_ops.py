@@ -144,6 +144,63 @@ def adam_flat_step_state(param, grad, exp_avg, exp_avg_sq, state, beta1=0.9, bet
                                          L.current_stream()), "seld_adam_flat_state")
 
 
+def _flat(t, name, what, n=None):
+    """A flat fp32 device buffer of the optimiser (of n elements when given), or a SeldHipError naming it."""
+    if not torch.is_tensor(t) or not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous():
+        raise L.SeldHipError(f"{what}: {name} must be a contiguous float32 HIP device tensor (this package has no CPU path)")
+    if n is not None and t.numel() != n:
+        raise L.SeldHipError(f"{what}: {name} holds {t.numel()} elements, expected {n}")
+    return t
+
+
+def grad_norm(grad, grad_scale, max_norm, clip):
+    """One launch, nothing read back (seld_grad_norm): clip (4 floats on the device) receives ||grad * grad_scale||_2,
+    torch.nn.utils.clip_grad_norm_'s coefficient min(1, max_norm / (norm + 1e-6)), the running largest norm and the
+    running count of clipped steps.  Returns clip."""
+    _flat(grad, "grad", "grad_norm")
+    _flat(clip, "clip", "grad_norm", 4)
+    if not float(max_norm) > 0.0:
+        raise L.SeldHipError(f"grad_norm: max_norm must be greater than 0, got {max_norm!r}")
+    L.check(L.lib().seld_grad_norm(L.ptr(grad), grad.numel(), grad_scale, max_norm, L.ptr(clip), L.current_stream()),
+            "seld_grad_norm")
+    return clip
+
+
+def _adam_ex_buffers(what, param, grad, exp_avg, exp_avg_sq, ema, clip, ema_decay):
+    n = _flat(param, "param", what).numel()
+    for t, name in ((grad, "grad"), (exp_avg, "exp_avg"), (exp_avg_sq, "exp_avg_sq")):
+        _flat(t, name, what, n)
+    if ema is not None:
+        _flat(ema, "ema", what, n)
+        if not 0.0 <= float(ema_decay) < 1.0:
+            raise L.SeldHipError(f"{what}: ema_decay must lie in [0, 1), got {ema_decay!r}")
+    if clip is not None:
+        _flat(clip, "clip", what, 4)
+    return n
+
+
+def adam_flat_step_ex(param, grad, exp_avg, exp_avg_sq, step, lr=1e-4, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0,
+                      grad_scale=1.0, decoupled=False, clip=None, ema=None, ema_decay=0.0):
+    """adam_flat_step with the extras (seld_adam_flat_ex): the gradient times clip[1] (clip: what grad_norm wrote; None:
+    as it is), weight decay decoupled as torch.optim.AdamW has it, and ema <- d ema + (1 - d) param after the update
+    with d = min(ema_decay, (1 + step) / (10 + step)).  All three off: the bits of adam_flat_step."""
+    n = _adam_ex_buffers("adam_flat_step_ex", param, grad, exp_avg, exp_avg_sq, ema, clip, ema_decay)
+    L.check(L.lib().seld_adam_flat_ex(L.ptr(param), L.ptr(grad), L.ptr(exp_avg), L.ptr(exp_avg_sq), L.ptr(ema), n, lr,
+                                      beta1, beta2, eps, weight_decay, int(bool(decoupled)), int(step), grad_scale,
+                                      L.ptr(clip), ema_decay, L.current_stream()), "seld_adam_flat_ex")
+
+
+def adam_flat_step_state_ex(param, grad, exp_avg, exp_avg_sq, state, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0,
+                            grad_scale=1.0, decoupled=False, clip=None, ema=None, ema_decay=0.0):
+    """adam_flat_step_ex with the step number and learning rate taken from the device-resident step state; the end of
+    the step, as adam_flat_step_state."""
+    n = _adam_ex_buffers("adam_flat_step_state_ex", param, grad, exp_avg, exp_avg_sq, ema, clip, ema_decay)
+    L.check(L.lib().seld_adam_flat_state_ex(L.ptr(param), L.ptr(grad), L.ptr(exp_avg), L.ptr(exp_avg_sq), L.ptr(ema), n,
+                                            beta1, beta2, eps, weight_decay, int(bool(decoupled)), grad_scale,
+                                            L.ptr(clip), ema_decay, L.ptr(state), L.current_stream()),
+            "seld_adam_flat_state_ex")
+
+
 def stft_magphase(x, nperseg=512, noverlap=128, output_phase=True):
     """x: (C, L) float32 device tensor -> (C or 2C, nperseg/2, frames) (utility_functions.py:129-155)."""
     x = _req(x, "x")

@@ -12,6 +12,7 @@ this file restates its behaviour rather than its text.
 """
 import argparse
 import ast
+import contextlib
 import functools
 import json
 import os
@@ -76,12 +77,26 @@ class FlatAdam:
     batch_gate1.*, the last block's conv2_residual) keep a zero gradient, which leaves them unchanged, as
     torch.optim.Adam does by skipping them."""
 
-    def __init__(self, params, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, late=None):
+    def __init__(self, params, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, late=None, decoupled=False,
+                 max_grad_norm=0.0, ema_decay=0.0):
         """`late`: parameters whose gradients are the LAST ones a backward pass completes (the front-end convolutions,
         see dp.late_parameters).  They are stored at the front of the flat buffers, so [0, late_numel) and
         [late_numel, total) are the two contiguous buckets of the data-parallel exchange (dp.BucketedGradSync: the big
         bucket is all-reduced while the front end's backward pass is still running).  `self.params`, the state dict
-        and the relative order inside each bucket keep `model.parameters()` order."""
+        and the relative order inside each bucket keep `model.parameters()` order.
+
+        The extras, all off by default (then nothing below is allocated and `step()` is the launch it always was):
+        `max_grad_norm` > 0: `step()` first launches hip_ops.grad_norm over `flat_grad` -- after the data-parallel
+        exchange, so every rank computes the same norm from the same averaged gradient and no collective is added -- and
+        the update multiplies the gradient by the coefficient that launch left in device memory (`clip`, 4 floats: norm,
+        coefficient, largest norm and clipped steps since `clip_stats()`); nothing is read back, so a recorded step clips
+        like an eager one.  `decoupled`: `weight_decay` shrinks the weights as torch.optim.AdamW does instead of joining
+        the gradient.  `ema_decay` > 0: the flat buffer `ema` follows the weights inside the update's launch,
+        ema <- d ema + (1 - d) p with d = min(ema_decay, (1 + step) / (10 + step)); `ema_weights()` lends it to the model."""
+        if not max_grad_norm >= 0.0:
+            raise ValueError(f"FlatAdam: max_grad_norm must not be negative (0: no clipping), got {max_grad_norm!r}")
+        if not 0.0 <= ema_decay < 1.0:
+            raise ValueError(f"FlatAdam: ema_decay must lie in [0, 1) (0: no moving average), got {ema_decay!r}")
         self.params = [p for p in params if p.requires_grad]
         if not self.params:
             raise ValueError("FlatAdam: no parameters")
@@ -110,6 +125,12 @@ class FlatAdam:
         self.param_groups = [dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, params=self.params)]
         self.step_count = 0
         self.grad_generation = 0
+        self.lr_scale = 1.0         # the learning-rate warm-up's factor (main, --warmup_steps): host side, on top of "lr"
+        self.decoupled, self.max_grad_norm, self.ema_decay = bool(decoupled), float(max_grad_norm), float(ema_decay)
+        self.clip = torch.zeros(4, device=dev, dtype=torch.float32) if self.max_grad_norm > 0 else None
+        self.ema = self.flat_param.clone() if self.ema_decay > 0 else None
+        self._extras = self.decoupled or self.clip is not None or self.ema is not None
+        self._ema_lent = False
 
     def zero_grad(self, set_to_none=False, state=None):
         """`state`: the device-resident step state (hip_ops.philox.state): also advance it (graph-recorded steps)."""
@@ -131,13 +152,87 @@ class FlatAdam:
         H.join_side_stream()            # weight gradients issued on the side stream (hip_ops._on_side_stream)
         H.hcq_weights.weights_changed() # the packed weight forms of the fast-product convolutions are stale now
         g = self.param_groups[0]
+        if self._extras:
+            return self._step_ex(g, grad_scale, state)
         if state is not None:
             H.adam_flat_step_state(self.flat_param, self.flat_grad, self.exp_avg, self.exp_avg_sq, state, g["betas"][0],
                                    g["betas"][1], g["eps"], g["weight_decay"], grad_scale)
             return
         self.step_count += 1
-        H.adam_flat_step(self.flat_param, self.flat_grad, self.exp_avg, self.exp_avg_sq, self.step_count, g["lr"],
-                         g["betas"][0], g["betas"][1], g["eps"], g["weight_decay"], grad_scale)
+        H.adam_flat_step(self.flat_param, self.flat_grad, self.exp_avg, self.exp_avg_sq, self.step_count,
+                         g["lr"] * self.lr_scale, g["betas"][0], g["betas"][1], g["eps"], g["weight_decay"], grad_scale)
+
+    def _step_ex(self, g, grad_scale, state):
+        """The step with any of the extras on: the norm launch (clipping only), then the extended update."""
+        if self._ema_lent:
+            raise RuntimeError("FlatAdam.step() inside ema_weights(): the parameters hold the moving average")
+        if self.clip is not None:
+            H.grad_norm(self.flat_grad, grad_scale, self.max_grad_norm, self.clip)
+        extras = dict(decoupled=self.decoupled, clip=self.clip, ema=self.ema, ema_decay=self.ema_decay)
+        if state is not None:
+            H.adam_flat_step_state_ex(self.flat_param, self.flat_grad, self.exp_avg, self.exp_avg_sq, state, g["betas"][0],
+                                      g["betas"][1], g["eps"], g["weight_decay"], grad_scale, **extras)
+            return
+        self.step_count += 1
+        H.adam_flat_step_ex(self.flat_param, self.flat_grad, self.exp_avg, self.exp_avg_sq, self.step_count,
+                            g["lr"] * self.lr_scale, g["betas"][0], g["betas"][1], g["eps"], g["weight_decay"], grad_scale,
+                            **extras)
+
+    def ema_reset(self):
+        """The moving average starts (again) from the weights as they are now: after a broadcast of the parameters, after
+        loading a checkpoint that carries no average."""
+        if self.ema is not None:
+            self.ema.copy_(self.flat_param)
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Inside the context the model computes with the moving average: the contents of `flat_param` and `ema` are
+        exchanged (the parameters are views of `flat_param`) and exchanged back on the way out, also when the body raised.
+        The packed weight forms of the fast-product convolutions are marked stale both times.  BatchNorm buffers are
+        not parameters: both sets of weights see the same running statistics.  No average (ema_decay == 0): nothing moves."""
+        if self.ema is None:
+            yield self
+            return
+        if self._ema_lent:
+            raise RuntimeError("FlatAdam.ema_weights() does not nest")
+        self._swap_ema()
+        self._ema_lent = True
+        try:
+            yield self
+        finally:
+            self._swap_ema()
+            self._ema_lent = False
+
+    def _swap_ema(self):
+        with torch.no_grad():
+            held = self.flat_param.clone()
+            self.flat_param.copy_(self.ema)
+            self.ema.copy_(held)
+        H.hcq_weights.weights_changed()
+
+    def clip_stats(self):
+        """(largest gradient norm, clipped steps) since the last call, read from the device and zeroed there: one small
+        read, for the epoch line.  (0.0, 0) without clipping."""
+        if self.clip is None:
+            return 0.0, 0
+        largest, clipped = self.clip[2:].tolist()
+        self.clip[2:].zero_()
+        return float(largest), int(clipped)
+
+    def ema_state_dict(self, named_parameters):
+        """{name: the moving average of that parameter} for the checkpoint, keyed like the model's parameters."""
+        return {name: self.ema[self._offset[id(p)]:self._offset[id(p)] + p.numel()].view(p.shape).clone()
+                for name, p in named_parameters if id(p) in self._offset}
+
+    def load_ema_state_dict(self, named_parameters, sd):
+        """Restore `ema_state_dict`'s tensors; a parameter the file does not name starts from its weights."""
+        self.ema_reset()
+        for name, p in named_parameters:
+            if id(p) in self._offset and name in sd:
+                if tuple(sd[name].shape) != tuple(p.shape):
+                    raise ValueError(f"moving average of {name}: shape {tuple(sd[name].shape)} != {tuple(p.shape)}")
+                off = self._offset[id(p)]
+                self.ema[off:off + p.numel()].copy_(sd[name].reshape(-1))
 
     def state_dict(self):
         """torch.optim.Adam's layout (the reference saves `optimizer.state_dict()`, train.py:36): per-parameter
@@ -200,7 +295,8 @@ class GraphedTrainStep:
     same C-ABI calls the eager step makes.
 
     What a replay must not freeze is kept in device memory and read by the kernels: the Philox base of the dropout
-    masks, the optimiser's step number and the learning rate (the 4-word step state of seld_step_begin).
+    masks, the optimiser's step number and the learning rate (the 4-word step state of seld_step_begin), and, with
+    gradient clipping, the clip coefficient (FlatAdam.clip, written by the norm launch and read by Adam's).
 
     Single process: one graph.  Data parallel (`sync` = dp.BucketedGradSync): three graphs with the two collectives
     issued eagerly between them, so that no collective is ever captured:
@@ -270,7 +366,7 @@ class GraphedTrainStep:
         self._hcq_pinned = H.hcq_weights.pin_for_graph()
 
     def _push_lr(self):
-        lr = float(self.opt.param_groups[0]["lr"])
+        lr = float(self.opt.param_groups[0]["lr"]) * float(getattr(self.opt, "lr_scale", 1.0))      # StepLR's, times the warm-up's
         if lr != self._lr:
             self._lr = lr
             self.state[2] = int(np.float32(lr).view(np.uint32))
@@ -430,7 +526,7 @@ _FLAGS = [
 ]
 _EVAL = ('use_cuda', 'early_stopping', 'fixed_seed', 'pool_size', 'cnn_filters', 'verbose', 'D', 'V', 'use_lr_scheduler',
          'phase', 'use_tcn', 'use_bias_conv', 'use_bias_linear', 'fc_layers', 'parallel_magphase',
-         'resident_loader', 'graph_step', 'pit_loss', 'class_report')
+         'resident_loader', 'graph_step', 'pit_loss', 'class_report', 'decoupled_weight_decay')
 # extensions of this implementation (not in the reference): synthetic data so the step can run without L3DAS21;
 # resident_loader: minibatches gathered on the device (ResidentLoader) instead of a DataLoader over the resident arrays;
 # graph_step (needs resident_loader): full batches run as replays of one recorded step (GraphedTrainStep);
@@ -464,7 +560,15 @@ _EVAL = ('use_cuda', 'early_stopping', 'fixed_seed', 'pool_size', 'cnn_filters',
 # results (from row "all" of the table), then prints per class Nref, precision / recall / F1 and ER, F, LE, LR, the class-wise
 # macro averages with their leave-one-recording-out standard errors (class_metrics), and writes class_report.json under
 # results_path; metrics_average: micro or macro -- which ER, F, LE, LR feed the early stopping metric the report states
-# (macro builds the table too; the 16 results stay the micro ones either way)
+# (macro builds the table too; the 16 results stay the micro ones either way);
+# grad_clip / weight_decay / decoupled_weight_decay / ema_decay / warmup_steps (all off by default: then the optimiser
+# allocates and launches what it always did) -- grad_clip=G: the global gradient norm is clipped to G inside the step
+# (hip_ops.grad_norm, one launch, the coefficient stays on the device; eager, data-parallel and recorded steps alike) and
+# the epoch line prints the largest norm and the share of clipped steps; weight_decay=W: L2 decay added to the gradient,
+# or with decoupled_weight_decay=True torch.optim.AdamW's shrinking of the weights; ema_decay=D: an exponential moving
+# average of the weights, updated inside Adam's launch, under which validation and the test leg run and which the
+# checkpoints carry as `ema_state_dict` beside the training weights; warmup_steps=N: the learning rate is
+# lr * min(1, step / N) on top of StepLR (host side: the factor FlatAdam.lr_scale)
 _EXTRA = [('synthetic', int, 0), ('max_steps', int, 0), ('epochs', int, 0), ('resident_loader', str, 'False'),
           ('graph_step', str, 'False'), ('augment_swap', float, 0.), ('augment_freq_masks', int, 0),
           ('augment_freq_width', int, 0), ('augment_time_masks', int, 0), ('augment_time_width', int, 0),
@@ -472,7 +576,9 @@ _EXTRA = [('synthetic', int, 0), ('max_steps', int, 0), ('epochs', int, 0), ('re
           ('pit_loss', str, 'False'), ('test_hop', int, 0), ('test_tta', int, 0),
           ('post_median', int, 1), ('post_on', float, 0.5), ('post_off', float, 0.5), ('post_min_frames', int, 1),
           ('post_max_gap', int, 0), ('post_doa', str, 'frame'), ('se_reduction', int, 0), ('se_mode', str, 'both'),
-          ('class_report', str, 'False'), ('metrics_average', str, 'micro')]
+          ('class_report', str, 'False'), ('metrics_average', str, 'micro'),
+          ('grad_clip', float, 0.), ('weight_decay', float, 0.), ('decoupled_weight_decay', str, 'False'),
+          ('ema_decay', float, 0.), ('warmup_steps', int, 0)]
 
 
 def build_parser():
@@ -509,6 +615,32 @@ def se_from_args(args):
     return dict(se_reduction=reduction, se_mode=mode)
 
 
+def optimizer_from_args(args):
+    """FlatAdam's keyword arguments of the --grad_clip / --weight_decay / --decoupled_weight_decay / --ema_decay flags, after
+    checking them and --warmup_steps (an args object without the flags: everything off).  Every refusal comes before the
+    device is touched."""
+    clip, decay = getattr(args, "grad_clip", 0.), getattr(args, "weight_decay", 0.)
+    ema, warmup = getattr(args, "ema_decay", 0.), getattr(args, "warmup_steps", 0)
+    decoupled = getattr(args, "decoupled_weight_decay", False)
+    if not clip >= 0.:
+        raise ValueError(f"--grad_clip must not be negative (0: no clipping), got {clip!r}")
+    if not decay >= 0.:
+        raise ValueError(f"--weight_decay must not be negative, got {decay!r}")
+    if not isinstance(decoupled, (bool, int)):
+        raise ValueError(f"--decoupled_weight_decay is True or False, got {decoupled!r}")
+    if not 0. <= ema < 1.:
+        raise ValueError(f"--ema_decay must lie in [0, 1) (0: no moving average), got {ema!r}")
+    if isinstance(warmup, bool) or not isinstance(warmup, int) or warmup < 0:
+        raise ValueError(f"--warmup_steps must be a non-negative integer (0: no warm-up), got {warmup!r}")
+    return dict(weight_decay=float(decay), decoupled=bool(decoupled) and decay > 0, max_grad_norm=float(clip),
+                ema_decay=float(ema))
+
+
+def warmup_scale(step, warmup_steps):
+    """The learning-rate warm-up's factor for the 1-based `step`: min(1, step / warmup_steps); 1 without warm-up."""
+    return min(1.0, step / warmup_steps) if warmup_steps > 0 else 1.0
+
+
 def model_from_args(args):
     """train.py:448-465, plus the squeeze-and-excitation flags."""
     return SELD_Model(time_dim=args.time_dim, freq_dim=args.freq_dim, input_channels=args.input_channels,
@@ -537,6 +669,11 @@ def save_model(model, optimizer, state, path, scheduler=None):
           'state': state}
     if scheduler is not None:
         ck['scheduler_state_dict'] = scheduler.state_dict()
+    if getattr(optimizer, "ema", None) is not None:
+        # --ema_decay: the moving average beside the training weights (model_state_dict stays those: a run resumes
+        # exactly), keyed like the model's parameters.  Without the flag the file's keys are what they were
+        target = model.module if hasattr(model, "module") else model
+        ck['ema_state_dict'] = optimizer.ema_state_dict(target.named_parameters())
     # the reference's three RNG states (train.py:40-43, read back by index at :77-80) + a fourth entry it never looks at:
     # the position of the dropout kernels' counter-based RNG stream, so that a resumed run does not replay masks
     ck['random_states'] = (np.random.get_state(), torch.get_rng_state(),
@@ -547,7 +684,8 @@ def save_model(model, optimizer, state, path, scheduler=None):
 
 def load_model(model, optimizer, path, cuda, device, scheduler=None):
     """train.py:47-81: `module.` prefixes stripped, optimizer / scheduler restored when given, checkpoints that only
-    hold `step` accepted, the numpy / torch / device RNG states restored."""
+    hold `step` accepted, the numpy / torch / device RNG states restored.  An optimiser that keeps a moving average of
+    the weights gets the file's `ema_state_dict` back, or, from a file without one, an average that starts at the loaded weights."""
     ck = torch.load(path, map_location=device if cuda else 'cpu', weights_only=False)
     sd = {(k[7:] if k.startswith('module.') else k): v for k, v in ck['model_state_dict'].items()}
     target = model.module if hasattr(model, "module") else model
@@ -555,6 +693,9 @@ def load_model(model, optimizer, path, cuda, device, scheduler=None):
     H.hcq_weights.weights_changed()          # the packed weight forms of the fast-product convolutions are stale now
     if optimizer is not None:
         optimizer.load_state_dict(ck['optimizer_state_dict'])
+        if getattr(optimizer, "ema", None) is not None:
+            # the file's moving average; a file without one (written without --ema_decay): the average starts from its weights
+            optimizer.load_ema_state_dict(target.named_parameters(), ck.get('ema_state_dict') or {})
     if scheduler is not None:
         scheduler.load_state_dict(ck['scheduler_state_dict'])
     state = ck['state'] if 'state' in ck else {'step': ck['step']}
@@ -793,9 +934,14 @@ class ResidentLoader:
 
 def training_snapshot(model, optimizer):
     """Everything a training step changes: weights, Adam moments and step count, every module buffer (BatchNorm running
-    statistics, num_batches_tracked) and the position of the dropout RNG stream."""
-    return dict(param=optimizer.flat_param.clone(), exp_avg=optimizer.exp_avg.clone(), exp_avg_sq=optimizer.exp_avg_sq.clone(),
+    statistics, num_batches_tracked), the position of the dropout RNG stream and, where the optimiser keeps them, the
+    moving average of the weights and the clip statistics."""
+    snap = dict(param=optimizer.flat_param.clone(), exp_avg=optimizer.exp_avg.clone(), exp_avg_sq=optimizer.exp_avg_sq.clone(),
                 step=optimizer.step_count, buffers=[b.clone() for b in model.buffers()], philox=H.philox.get_offset())
+    for key in ("ema", "clip"):         # the moving average and the clip statistics, where the optimiser keeps them
+        if getattr(optimizer, key, None) is not None:
+            snap[key] = getattr(optimizer, key).clone()
+    return snap
 
 
 def training_restore(model, optimizer, snap):
@@ -807,6 +953,9 @@ def training_restore(model, optimizer, snap):
         optimizer.exp_avg_sq.copy_(snap["exp_avg_sq"])
         for b, saved in zip(model.buffers(), snap["buffers"]):
             b.copy_(saved)
+        for key in ("ema", "clip"):
+            if key in snap:
+                getattr(optimizer, key).copy_(snap[key])
     optimizer.step_count = snap["step"]         # GraphedTrainStep.sync_from_host pushes it into the step state
     H.philox.set_offset(snap["philox"])
     H.hcq_weights.weights_changed()
@@ -1057,6 +1206,14 @@ def _report_results(tables, epoch, args, report, average):
     return results
 
 
+def ema_scope(optimizer):
+    """`optimizer.ema_weights()` for a FlatAdam that keeps a moving average of the weights (--ema_decay); a context that
+    does nothing for None or any other optimiser.  `with ema_scope(optimizer): predict_test(model, ...)` -- or
+    predict_test_post, predict_recordings, evaluate_test, evaluate_recordings -- predicts with the average, as main's
+    validation and test leg do; the signatures of those functions stay what they were."""
+    return optimizer.ema_weights() if getattr(optimizer, "ema", None) is not None else contextlib.nullcontext()
+
+
 def predict_test(model, device, dataloader, max_loc_value=2., num_frames=600):
     """The prediction half of evaluate_test (train.py:100-111): the model under no_grad exactly as there, every batch
     decoded on the device (hip_ops.decode_events, with gen_submission_list_task2's default of 14 classes as the
@@ -1154,7 +1311,8 @@ def predict_recordings(model, x, *, seg_len, hop, table=None, window="triangular
     hip_ops.ensemble_combine per chunk of recordings then maps the DOAs back, aligns the slots of every (frame, class)
     (`align`, for models trained with --pit_loss a must) and averages with the weights `window`.  The pooling factor
     P = seg_len / T_out is read from the first forward: hop must be a multiple of it, frames defaults to L // P.
-    n = classes * overlaps is split as 14 classes x n / 14 overlaps, the way predict_test reads it."""
+    n = classes * overlaps is split as 14 classes x n / 14 overlaps, the way predict_test reads it.  Under
+    `ema_scope(optimizer)` the recordings are predicted with the moving average of the weights."""
     seg_len, hop, batch = int(seg_len), int(hop), int(batch)
     if x.dim() != 4 or not x.is_cuda:
         raise H.L.SeldHipError(f"predict_recordings: x must be a device tensor (R, C, F, L), got {tuple(x.shape)} on {x.device}")
@@ -1266,6 +1424,8 @@ def main(args, history=None):
     class_report_from_args(args)
     pit = pit_overlaps_from_args(args)
     se_from_args(args)
+    extras = optimizer_from_args(args)
+    warmup_steps = getattr(args, "warmup_steps", 0)
     if pit > 3:
         raise ValueError(f"--pit_loss searches the pairings of at most 3 slots per class, got --class_overlaps {pit}")
     if not args.use_cuda or not torch.cuda.is_available():
@@ -1295,11 +1455,12 @@ def main(args, history=None):
     sync = None
     if world > 1:
         DP.seed_rank_streams(rank)
-        optimizer = FlatAdam(model.parameters(), lr=args.lr, late=DP.late_parameters(model))
+        optimizer = FlatAdam(model.parameters(), lr=args.lr, late=DP.late_parameters(model), **extras)
         DP.broadcast_parameters(optimizer.flat_param)
+        optimizer.ema_reset()               # the moving average starts from the weights every rank now holds
         sync = DP.BucketedGradSync(optimizer, model)
     else:
-        optimizer = FlatAdam(model.parameters(), lr=args.lr)
+        optimizer = FlatAdam(model.parameters(), lr=args.lr, **extras)
     scheduler = StepLR(optimizer, args.lr_scheduler_step_size, args.lr_scheduler_gamma) if args.use_lr_scheduler else None
     n_out = int(args.output_classes * args.class_overlaps)
     # bound once: the data-parallel step and the recorded step take the loss the eager step and `evaluate` reach through
@@ -1385,9 +1546,11 @@ def main(args, history=None):
         model.train()
         train_loss = 0.0
         t0 = time.time()
+        steps_before = state["step"]
         if resident:
             tr_data.begin_epoch()
             for _, count, graphable in tr_data.plan:
+                optimizer.lr_scale = warmup_scale(state["step"] + 1, warmup_steps)     # a replay takes it through _push_lr
                 if runner is not None and graphable:
                     runner()                    # gather, step and running mean: one replay (three when data parallel)
                 else:
@@ -1402,6 +1565,7 @@ def main(args, history=None):
             train_loss = tr_data.mean.item()    # the epoch's one read-back
         else:
             for i, (x, target) in enumerate(tr_data):
+                optimizer.lr_scale = warmup_scale(state["step"] + 1, warmup_steps)
                 optimizer.zero_grad()
                 loss = seld_loss(x.to(device), target.to(device), model, criterion_sed, criterion_doa, args)
                 loss.backward()
@@ -1412,7 +1576,10 @@ def main(args, history=None):
                     break
         if world > 1:
             DP.average_bn_running_stats(model)      # rank 0's validation and checkpoint speak for all ranks
-        val_loss = evaluate(model, device, criterion_sed, criterion_doa, val_data, args) if rank == 0 else None
+        # one small read per epoch, next to the loss mean; every rank's statistics are the same (same averaged gradient)
+        largest_norm, clipped = optimizer.clip_stats()
+        with optimizer.ema_weights():       # --ema_decay: validation sees the moving average (nothing moves without it)
+            val_loss = evaluate(model, device, criterion_sed, criterion_doa, val_data, args) if rank == 0 else None
         if scheduler is not None and optimizer.param_groups[0]['lr'] > args.min_lr:
             scheduler.step()
         if rank != 0:
@@ -1426,7 +1593,9 @@ def main(args, history=None):
         if history is not None:
             history.append((epoch, float(train_loss), val_loss))
         print(f"epoch {epoch}: train {float(train_loss):.5f} val {val_loss:.5f} lr {optimizer.param_groups[0]['lr']:.2e} "
-              f"({time.time() - t0:.1f}s)")
+              f"({time.time() - t0:.1f}s)"
+              + (f" grad norm max {largest_norm:.3e} clipped {clipped / max(1, state['step'] - steps_before):.0%}"
+                 if optimizer.clip is not None else ""))
         if rotation.end_of_epoch(model, optimizer, scheduler, state, epoch, val_loss, periodic_copy=False):
             print("MODEL IMPROVED ON VALIDATION SET!")
         if test_data is not None and args.test_step > 0 and epoch % args.test_step == 0:      # train.py:623-670
@@ -1435,15 +1604,17 @@ def main(args, history=None):
                 live = os.path.join(model_dir, "checkpoint")
                 state = load_model(model, optimizer, path, args.use_cuda, device, scheduler)
                 at_epoch = state['best_epoch'] if at_epoch is None else at_epoch
-            if ensemble is None:
-                results = evaluate_test(model, device, test_data, epoch=epoch if path is None else at_epoch,
-                                        max_loc_value=args.max_loc_value, num_frames=args.num_frames,
-                                        spatial_threshold=args.spatial_threshold, args=args)
-            else:
-                results = evaluate_recordings(model, device, *test_arrays, args, epoch=epoch if path is None else at_epoch,
-                                              align=args.class_overlaps <= 3, max_loc_value=args.max_loc_value,
-                                              num_frames=args.num_frames, spatial_threshold=args.spatial_threshold,
-                                              **ensemble, **({} if post is None else dict(post=post)))
+            # --ema_decay: the loaded checkpoint (or the live model) is scored under its moving average
+            with optimizer.ema_weights():
+                if ensemble is None:
+                    results = evaluate_test(model, device, test_data, epoch=epoch if path is None else at_epoch,
+                                            max_loc_value=args.max_loc_value, num_frames=args.num_frames,
+                                            spatial_threshold=args.spatial_threshold, args=args)
+                else:
+                    results = evaluate_recordings(model, device, *test_arrays, args, epoch=epoch if path is None else at_epoch,
+                                                  align=args.class_overlaps <= 3, max_loc_value=args.max_loc_value,
+                                                  num_frames=args.num_frames, spatial_threshold=args.spatial_threshold,
+                                                  **ensemble, **({} if post is None else dict(post=post)))
             rotation.after_test(model, optimizer, scheduler, state, epoch, results, args.test_mode)
             if path is not None:
                 # the reference reloads args.load_model here (train.py:667), which only exists when resuming; the live
