@@ -1418,6 +1418,54 @@ int seld_se_bwd_apply(const float* dy, int32_t N, int32_t C, int32_t S, int32_t 
                       float* dx, void* stream);
 int seld_se_kernel_label(int32_t op, int32_t S, int32_t same_phase, char* buf, int32_t buflen);
 
+/* ------------------------------------------------------------------------------------------
+ * Temporal attention (csrc/temporal_attention.hip): the single-head attention core of the TCN's "AT" blocks, flash style,
+ * on ONE projected tensor qkv (N, 2K + V, T) = [q (K) | k (K) | v (V)] along the channels, fp32 contiguous, T contiguous.
+ * The key width K and the value width V are independent, 1 <= K, V <= SELD_AT_MAX_WIDTH.
+ *
+ *   score[n,t,s]   = (sum_d q[n,d,t] k[n,d,s]) / sqrt(K)
+ *   allowed(n,t,s) = kind(t, s) && s < len[n]
+ *                    SELD_AT_NONE: true      SELD_AT_CAUSAL: s <= t      SELD_AT_BAND: |t - s| <= band
+ *   p[n,t,:]       = softmax of score[n,t,:] over the allowed s; an excluded key has weight EXACTLY 0 (this is not the
+ *                    -1e9 convention of seld_mha_*_ex, where a fully masked row attends uniformly)
+ *   read[n,:,t]    = sum_s p[n,t,s] v[n,:,s]            (N, V, T)
+ *   lse[n,t]       = log sum_{allowed s} exp(score[n,t,s])       (N, T)
+ *
+ * lengths: an optional int32 device array of N valid lengths, each clamped by the kernels into [1, T]; NULL: T.  band is
+ * read for SELD_AT_BAND only (but must never be negative).  A row with no allowed key can arise only from SELD_AT_BAND
+ * together with lengths (t - band >= len[n]): it gives read = 0 and lse = +inf and contributes nothing to any gradient.
+ *
+ *   delta[n,t] = sum_d dread[n,d,t] read[n,d,t]         dp[n,t,s] = sum_d dread[n,d,t] v[n,d,s]
+ *   ds = p (dp - delta) / sqrt(K)      dq[n,:,t] = sum_s ds k[n,:,s]      dk[n,:,s] = sum_t ds q[n,:,t]
+ *   dv[n,:,s] = sum_t p dread[n,:,t]                    dqkv = [dq | dk | dv], every element written
+ *
+ * seld_at_fwd is one launch; seld_at_bwd three (delta into the workspace of seld_at_bwd_workspace(N, T) bytes, a dq kernel
+ * that owns query tiles, a dk/dv kernel that owns key tiles).  No atomics: a repeated call gives the same bytes.  All on
+ * `stream`, no host read, no allocation: the calls record into a HIP graph.  Every kernel loops only over the tiles of the
+ * opposite index that the mask allows for its own tile; tiles the mask excludes are never loaded.
+ * Forms (seld_at_kernel_label: "at_<fwd|bwd_dq|bwd_dkv>_mfma_kernel<K,V>" or "..._valu_kernel<W>", W = max(K, V) rounded up to
+ * 8 / 16 / 32 / 48 / 64): fp32-MFMA kernels when K and V are each one of 16, 32, 48, 64 and T % 16 == 0 (and
+ * SELD_MHA_NO_MFMA is not set); VALU kernels otherwise, and for tensors off a 16-byte boundary.  Element offsets are 64-bit.
+ *   SELD_EINVAL: a NULL tensor, a size <= 0, band < 0, an unknown mask kind (for the label: an unknown op, a short buffer).
+ *   SELD_EUNSUPPORTED: K or V > SELD_AT_MAX_WIDTH; N * ceil(T / 32) workgroups of 2^31 or more.
+ *   SELD_EWORKSPACE: workspace NULL or smaller than seld_at_bwd_workspace(N, T).
+ * All are returned before anything is launched or written.  Outputs may not alias inputs.
+ * ------------------------------------------------------------------------------------------ */
+#define SELD_AT_MAX_WIDTH 64
+#define SELD_AT_NONE 0                 /* mask_kind */
+#define SELD_AT_CAUSAL 1
+#define SELD_AT_BAND 2
+#define SELD_AT_FWD 0                  /* seld_at_kernel_label(op, ...) */
+#define SELD_AT_BWD_DQ 1
+#define SELD_AT_BWD_DKV 2
+int seld_at_fwd(const float* qkv, int32_t N, int32_t T, int32_t K, int32_t V, int32_t mask_kind, int32_t band,
+                const int32_t* lengths /* may be NULL */, float* read, float* lse, void* stream);
+size_t seld_at_bwd_workspace(int32_t N, int32_t T);
+int seld_at_bwd(const float* qkv, const float* read, const float* dread, const float* lse, int32_t N, int32_t T, int32_t K,
+                int32_t V, int32_t mask_kind, int32_t band, const int32_t* lengths /* may be NULL */, float* dqkv,
+                void* workspace, size_t workspace_bytes, void* stream);
+int seld_at_kernel_label(int32_t op, int32_t T, int32_t K, int32_t V, char* buf, int32_t buflen);
+
 #ifdef __cplusplus
 }
 #endif

@@ -128,3 +128,39 @@ class SqueezeExcite(nn.Module):
 
     def forward(self, x):
         return H.squeeze_excite(x, self.fc1.weight, self.fc1.bias, self.fc2.weight, self.fc2.bias, self.components)
+
+
+class TemporalAttention(nn.Module):
+    """Temporal attention (AT) block on a (N, channels, T) tensor: y = x + out(read(qkv(x))), a single-head attention over
+    the time axis with key width `key_size`, value width `value_size` and an index mask (none | causal | band of +-`band`
+    frames; hip_ops.at_core).  qkv is a 1x1 convolution to 2 key_size + value_size channels with torch's default
+    initialisation; out, a 1x1 convolution back to `channels`, starts at zero, so a fresh block is the identity and grows
+    in from there.  Both run on the real 1x1 convolution path; out and the residual sum are one launch."""
+
+    def __init__(self, channels, key_size, value_size, mask='causal', band=0):
+        super().__init__()
+        for name, w in (("channels", channels), ("key_size", key_size), ("value_size", value_size)):
+            if isinstance(w, bool) or not isinstance(w, int) or w < 1:
+                raise ValueError(f"{name} must be a positive integer, got {w!r}")
+        if key_size > H.AT_MAX_WIDTH or value_size > H.AT_MAX_WIDTH:
+            raise ValueError(f"key_size {key_size} / value_size {value_size}: the kernels hold at most {H.AT_MAX_WIDTH}")
+        if mask not in H.AT_MASKS:
+            raise ValueError(f"mask must be one of {', '.join(H.AT_MASKS)}, got {mask!r}")
+        if isinstance(band, bool) or not isinstance(band, int) or band < 0 or (mask == 'band' and band < 1):
+            raise ValueError(f"band must be a non-negative integer, and at least 1 with mask='band', got {band!r}")
+        self.channels, self.key_size, self.value_size = channels, key_size, value_size
+        self.mask, self.band = mask, band
+        self.qkv = Conv1d(channels, 2 * key_size + value_size, 1)
+        self.out = Conv1d(value_size, channels, 1)
+        nn.init.zeros_(self.out.weight)
+        nn.init.zeros_(self.out.bias)
+
+    def extra_repr(self):
+        return f"mask={self.mask}, band={self.band}"
+
+    def forward(self, x, lengths=None):
+        if x.dim() != 3 or x.shape[1] != self.channels:
+            raise L.SeldHipError(f"TemporalAttention: expected (N, {self.channels}, T), got {tuple(x.shape)}")
+        read = H.at_core(self.qkv(x), self.key_size, self.value_size, self.mask, self.band, lengths)
+        return H.hyper_conv_add(read, (self.out.weight,), self.out.bias, x, self.out.stride, self.out.padding,
+                                self.out.dilation)

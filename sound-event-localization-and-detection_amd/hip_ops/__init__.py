@@ -21,6 +21,7 @@ from .event_metrics import *    # noqa: F401,F403
 from .ensemble import *         # noqa: F401,F403
 from .smooth import *           # noqa: F401,F403
 from .squeeze_excite import *   # noqa: F401,F403
+from .temporal_attention import *  # noqa: F401,F403
 from .features import *         # noqa: F401,F403
 # `import *` skips underscore names: the ones train.py, the tests and tools/ reach, and the rest of the module surface
 from ._core import _drop_kernel_choice_caches, _pair, _req, _scratch_pools  # noqa: F401

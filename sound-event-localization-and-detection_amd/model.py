@@ -34,6 +34,8 @@ _CNN_BN = {'BN', 'BN_on_CNN', 'BNonCNN'}
 _TWO_STREAM = {'2Parallel', '2BParallel', '2ParallelBranches', '2PB'}
 SE_MODES = ('cnn', 'tcn', 'both')
 _SE_COMPONENTS = {'Q': 4, 'DQ': 8}
+AT_MASKS = ('none', 'causal', 'band')
+AT_MAX_WIDTH = 64           # hip_ops.AT_MAX_WIDTH
 
 
 def _se_check(se_reduction, se_mode):
@@ -41,6 +43,25 @@ def _se_check(se_reduction, se_mode):
         raise ValueError(f"se_reduction must be a non-negative integer (0: no squeeze-and-excitation), got {se_reduction!r}")
     if se_mode not in SE_MODES:
         raise ValueError(f"se_mode must be one of {', '.join(SE_MODES)}, got {se_mode!r}")
+
+
+def _at_check(at_key_size, at_value_size, at_mask, at_band):
+    """Refuses bad temporal-attention arguments (nothing here touches the device); returns (key, value) widths, (0, 0)
+    for a model without the blocks.  at_value_size=0 takes the key size."""
+    for name, w in (("at_key_size", at_key_size), ("at_value_size", at_value_size)):
+        if isinstance(w, bool) or not isinstance(w, int) or w < 0:
+            raise ValueError(f"{name} must be a non-negative integer, got {w!r}")
+        if w > AT_MAX_WIDTH:
+            raise ValueError(f"{name} {w}: the attention kernels hold at most {AT_MAX_WIDTH}")
+    if at_mask not in AT_MASKS:
+        raise ValueError(f"at_mask must be one of {', '.join(AT_MASKS)}, got {at_mask!r}")
+    if isinstance(at_band, bool) or not isinstance(at_band, int) or at_band < 0:
+        raise ValueError(f"at_band must be a non-negative integer, got {at_band!r}")
+    if at_mask == 'band' and at_band < 1:
+        raise ValueError(f"at_mask='band' needs at_band >= 1, got {at_band!r}")
+    if not at_key_size:
+        return 0, 0
+    return at_key_size, at_value_size or at_key_size
 
 
 def _make_se(domain, channels, se_reduction):
@@ -222,9 +243,11 @@ class TC_Block(nn.Module):
     def __init__(self, in_channels, domain='DQ', G=128, U=128, V=[128, 128], V_kernel_size=3,
                  pool_size=[[8, 2], [8, 2], [2, 2]], D=[10], spatial_dropout_rate=0.5, use_bias_conv=True,
                  dilation_mode='fibonacci', pool_time='TCN', batch_norm='BN', kernel_size_dilated_conv=3,
-                 verbose=False, attention_type=None, key_size=None, value_size=None, se_reduction=0, se_mode='both'):
+                 verbose=False, attention_type=None, key_size=None, value_size=None, se_reduction=0, se_mode='both',
+                 at_key_size=0, at_value_size=0, at_mask='causal', at_band=0):
         super().__init__()
         _se_check(se_reduction, se_mode)
+        at_k, at_v = _at_check(at_key_size, at_value_size, at_mask, at_band)
         self.verbose, self.D, self.pool_time, self.domain = verbose, D, pool_time, domain
         self._gate_channels = G
         self.ResBlocks = nn.ModuleList()
@@ -246,6 +269,28 @@ class TC_Block(nn.Module):
         self.tanh = hnn.Tanh()
         if self.pool_time == 'TCN':
             self.maxpool3 = hnn.MaxPool1d(pool_size[2][1])
+        # temporal attention: one block per dilation stack (entry of D), on the residual stream in front of the stack's
+        # first ResBlock.  Registered last, and the global RNG is put back to where the blocks found it: every other
+        # parameter of the model (the modules built after this one included) keeps its draw.  attention_type / key_size
+        # / value_size stay inert, as in the reference.
+        self._at_before = {}
+        if at_k:
+            self._at_before = {first: j for j, first in enumerate(self.stack_starts(D))}
+            rng = torch.get_rng_state()
+            self.at = nn.ModuleList(hnn.TemporalAttention(in_channels, at_k, at_v, at_mask, at_band)
+                                    for _ in self._at_before)
+            torch.set_rng_state(rng)
+
+    @staticmethod
+    def stack_starts(D):
+        """Index of the first ResBlock of every dilation stack: an entry of D is a stack (an explicit list counts as one)."""
+        out, first = [], 0
+        for stack in D:
+            n = len(stack) if type(stack) == list else int(stack)
+            if n > 0:
+                out.append(first)
+            first += n
+        return out
 
     @staticmethod
     def dilation_schedule(D, dilation_mode):
@@ -288,6 +333,9 @@ class TC_Block(nn.Module):
         stats = None                     # batch statistics of `residual`, gathered by the convolution that wrote it
         masks = self._dropout_masks(residual)
         for i, blk in enumerate(self.ResBlocks):
+            if i in self._at_before:
+                # the epilogue statistics of the previous convolution describe the tensor in front of the AT block
+                residual, stats = self.at[self._at_before[i]](residual), None
             residual, skip, stats = blk.fused(residual, skip, need_residual=i < last, x_stats=stats,
                                               want_res_stats=i < last, mask=None if masks is None else masks[i])
         out = self.relu1(skip)
@@ -344,9 +392,11 @@ class ConvTC_Block(nn.Module):
                  kernel_size_cnn_blocks=3, pool_size=[[8, 2], [8, 2], [2, 2]], pool_time='TCN', D=[10],
                  dilation_mode='fibonacci', G=128, U=128, kernel_size_dilated_conv=3, spatial_dropout_rate=0.5,
                  V=[128, 128], V_kernel_size=3, dropout_perc=0.3, use_bias_conv=True, batch_norm='noBN',
-                 attention_type=None, key_size=None, value_size=None, verbose=False, se_reduction=0, se_mode='both'):
+                 attention_type=None, key_size=None, value_size=None, verbose=False, se_reduction=0, se_mode='both',
+                 at_key_size=0, at_value_size=0, at_mask='causal', at_band=0):
         super().__init__()
         _se_check(se_reduction, se_mode)
+        _at_check(at_key_size, at_value_size, at_mask, at_band)
         self.time_dim, self.freq_dim, self.domain, self.verbose = time_dim, freq_dim, domain, verbose
         self.D, self.kernel_size_dilated_conv, self.dilation_mode = D, kernel_size_dilated_conv, dilation_mode
         self.attenyion_type = attention_type          # (sic) attribute name of the reference, model.py:250
@@ -376,7 +426,8 @@ class ConvTC_Block(nn.Module):
                             use_bias_conv=use_bias_conv, dilation_mode=dilation_mode, pool_time=pool_time,
                             batch_norm=batch_norm, kernel_size_dilated_conv=kernel_size_dilated_conv, verbose=verbose,
                             attention_type=attention_type, key_size=key_size, value_size=value_size,
-                            se_reduction=se_reduction, se_mode=se_mode)
+                            se_reduction=se_reduction, se_mode=se_mode, at_key_size=at_key_size,
+                            at_value_size=at_value_size, at_mask=at_mask, at_band=at_band)
 
     def forward(self, x):
         x = self.cnn(x)
@@ -401,9 +452,10 @@ class SELD_Model(nn.Module):
                  fc_activations='Linear', fc_dropout='all', dropout_perc=0.3, class_overlaps=3., use_bias_conv=False,
                  use_bias_linear=True, batch_norm='BN', parallel_ConvTC_block='False', parallel_magphase=False,
                  extra_name='', attention_type=None, key_size=None, value_size=None, verbose=False, se_reduction=0,
-                 se_mode='both'):
+                 se_mode='both', at_key_size=0, at_value_size=0, at_mask='causal', at_band=0):
         super().__init__()
         _se_check(se_reduction, se_mode)
+        _at_check(at_key_size, at_value_size, at_mask, at_band)
         self.input_channels, self.time_dim, self.freq_dim = input_channels, time_dim, freq_dim
         self.domain, self.verbose, self.D = domain, verbose, D
         self.kernel_size_dilated_conv, self.dilation_mode = kernel_size_dilated_conv, dilation_mode
@@ -420,7 +472,8 @@ class SELD_Model(nn.Module):
                         dilation_mode=dilation_mode, G=G, U=U, kernel_size_dilated_conv=kernel_size_dilated_conv,
                         spatial_dropout_rate=spatial_dropout_rate, V=V, V_kernel_size=V_kernel_size,
                         dropout_perc=dropout_perc, use_bias_conv=use_bias_conv, batch_norm=batch_norm, verbose=False,
-                        se_reduction=se_reduction, se_mode=se_mode)
+                        se_reduction=se_reduction, se_mode=se_mode, at_key_size=at_key_size,
+                        at_value_size=at_value_size, at_mask=at_mask, at_band=at_band)
         if parallel_ConvTC_block in _TWO_STREAM:
             self.branch_A = ConvTC_Block(input_channels=input_channels // 2, **block_kw)
             self.branch_B = ConvTC_Block(input_channels=input_channels // 2, **block_kw)

@@ -27,7 +27,7 @@ import torch.nn as nn
 
 from . import class_metrics as CM
 from . import hip_ops as H
-from .model import SE_MODES, SELD_Model
+from .model import SE_MODES, SELD_Model, _at_check
 
 
 # ------------------------------------------------------------------------------------------
@@ -568,7 +568,10 @@ _EVAL = ('use_cuda', 'early_stopping', 'fixed_seed', 'pool_size', 'cnn_filters',
 # or with decoupled_weight_decay=True torch.optim.AdamW's shrinking of the weights; ema_decay=D: an exponential moving
 # average of the weights, updated inside Adam's launch, under which validation and the test leg run and which the
 # checkpoints carry as `ema_state_dict` beside the training weights; warmup_steps=N: the learning rate is
-# lr * min(1, step / N) on top of StepLR (host side: the factor FlatAdam.lr_scale)
+# lr * min(1, step / N) on top of StepLR (host side: the factor FlatAdam.lr_scale);
+# at_key_size / at_value_size / at_mask / at_band (off by default): at_key_size=K puts a temporal-attention block
+# (hip_nn.TemporalAttention, key width K, value width at_value_size or K) in front of every dilation stack of the TCN;
+# at_mask: none | causal | band, the band +-at_band frames wide
 _EXTRA = [('synthetic', int, 0), ('max_steps', int, 0), ('epochs', int, 0), ('resident_loader', str, 'False'),
           ('graph_step', str, 'False'), ('augment_swap', float, 0.), ('augment_freq_masks', int, 0),
           ('augment_freq_width', int, 0), ('augment_time_masks', int, 0), ('augment_time_width', int, 0),
@@ -578,7 +581,8 @@ _EXTRA = [('synthetic', int, 0), ('max_steps', int, 0), ('epochs', int, 0), ('re
           ('post_max_gap', int, 0), ('post_doa', str, 'frame'), ('se_reduction', int, 0), ('se_mode', str, 'both'),
           ('class_report', str, 'False'), ('metrics_average', str, 'micro'),
           ('grad_clip', float, 0.), ('weight_decay', float, 0.), ('decoupled_weight_decay', str, 'False'),
-          ('ema_decay', float, 0.), ('warmup_steps', int, 0)]
+          ('ema_decay', float, 0.), ('warmup_steps', int, 0),
+          ('at_key_size', int, 0), ('at_value_size', int, 0), ('at_mask', str, 'causal'), ('at_band', int, 0)]
 
 
 def build_parser():
@@ -615,6 +619,19 @@ def se_from_args(args):
     return dict(se_reduction=reduction, se_mode=mode)
 
 
+def at_from_args(args):
+    """dict(at_key_size=, at_value_size=, at_mask=, at_band=) of the --at_* flags for SELD_Model (temporal-attention
+    blocks; key size 0, also for an args object without the flags: none).  Every refusal comes before the device is
+    touched."""
+    kw = dict(at_key_size=getattr(args, "at_key_size", 0), at_value_size=getattr(args, "at_value_size", 0),
+              at_mask=getattr(args, "at_mask", "causal"), at_band=getattr(args, "at_band", 0))
+    try:
+        _at_check(**kw)
+    except ValueError as e:
+        raise ValueError("--" + str(e)) from None
+    return kw
+
+
 def optimizer_from_args(args):
     """FlatAdam's keyword arguments of the --grad_clip / --weight_decay / --decoupled_weight_decay / --ema_decay flags, after
     checking them and --warmup_steps (an args object without the flags: everything off).  Every refusal comes before the
@@ -642,7 +659,7 @@ def warmup_scale(step, warmup_steps):
 
 
 def model_from_args(args):
-    """train.py:448-465, plus the squeeze-and-excitation flags."""
+    """train.py:448-465, plus the squeeze-and-excitation and temporal-attention flags."""
     return SELD_Model(time_dim=args.time_dim, freq_dim=args.freq_dim, input_channels=args.input_channels,
                       output_classes=args.output_classes, domain=args.domain, domain_classifier=args.domain_classifier,
                       cnn_filters=args.cnn_filters, kernel_size_cnn_blocks=args.kernel_size_cnn_blocks,
@@ -653,7 +670,8 @@ def model_from_args(args):
                       dropout_perc=args.dropout_perc, class_overlaps=args.class_overlaps, use_bias_conv=args.use_bias_conv,
                       use_bias_linear=args.use_bias_linear, batch_norm=args.batch_norm,
                       parallel_ConvTC_block=args.parallel_ConvTC_block, parallel_magphase=args.parallel_magphase,
-                      extra_name=args.model_extra_name, verbose=args.verbose, **se_from_args(args))
+                      extra_name=args.model_extra_name, verbose=args.verbose, **se_from_args(args),
+                      **at_from_args(args))
 
 
 # ------------------------------------------------------------------------------------------
@@ -1424,6 +1442,7 @@ def main(args, history=None):
     class_report_from_args(args)
     pit = pit_overlaps_from_args(args)
     se_from_args(args)
+    at_from_args(args)
     extras = optimizer_from_args(args)
     warmup_steps = getattr(args, "warmup_steps", 0)
     if pit > 3:
