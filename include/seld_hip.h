@@ -1211,6 +1211,49 @@ int seld_segment(const void* src, int32_t dtype, int32_t layout, int64_t rows, i
  *   SELD_EINVAL: whatever seld_gather_rows_rot refuses of the arguments they share; n_groups outside [1, 2];
  *   6 * n_groups > C; an entry of groups outside [0, C) or given twice, a set bit above the last entry.
  *   SELD_EUNSUPPORTED: a row of 2^31 floats or more.  Nothing is launched on refusal.
+ * seld_target_occupancy, once per resident target array (outside any capture): target rows are (T_out, y_cols) with
+ * y_cols = 4 * n_sed, n_sed = classes * overlaps, the slot of (class c, place o) being c * overlaps + o (what
+ * seld_encode_events writes).  A slot is ACTIVE iff its activity > 0.5f (a NaN is inactive).
+ *     occ[r, c] = max over the frames of row r of the number of active slots of class c        occ: (n_rows, classes) uint8
+ *   One launch, one writer per byte, no atomics.  SELD_EINVAL: a NULL pointer, a non-positive size, y_cols no positive
+ *   multiple of 4 * overlaps, row_y no multiple of y_cols.  SELD_EUNSUPPORTED: classes > 64, overlaps > 8, row_y >= 2^31.
+ *   Nothing is launched on refusal.
+ * seld_gather_rows_mix is seld_gather_rows with a SECOND clip mixed into a sample on the way, for predictors stored as
+ * [magnitude channels | phase channels]: the STFT is linear, so the mixture a + g b of two recordings has the spectrum
+ * z_A + g z_B bin by bin; on these predictors mixing in the loader equals mixing the waveforms.  Addressing, cursor / start
+ * / count / stride, zero-fill of invalid positions, untouched rows [count, B), geometry (C, F, T, y_cols), epoch, seed, the
+ * counter, groups 1 and 2 (the masks, after the mix, over every channel), the 16-byte / scalar path rule and `stats` (NULL:
+ * both affine steps are skipped) are those of seld_gather_rows_polar; one launch, recordable.
+ *   Layout: C is even; channel c < C / 2 is a magnitude and channel c + C / 2 its phase.  Every pair is mixed, W like
+ *   any other: a mixed sample has no channel that is copied.
+ *   The draw.  Groups 0..3 of a sample's counter are taken, so the mix has a key of its own:
+ *       w = philox4x32_10(counter with g = 0, seed ^ 0x9E3779B97F4A7C15)
+ *       drawn iff p_mix > 0, n_index > 1 and u01(w[1]) < p_mix
+ *       p2 = (p + 1 + int(w[0], n_index - 1)) mod n_index      the partner POSITION: never p; any position of `index`
+ *       g  = fma(u01(w[2]), gain_hi - gain_lo, gain_lo)
+ *   partners, gains (nullable, both or neither): `count` int64 and `count` fp32 on the device.  Sample b then takes
+ *   p2 = partners[b] and g = gains[b] and nothing is drawn; p2 outside [0, n_index) means no mix.  Their content is the
+ *   caller's business, as that of `matrices` is.
+ *   A drawn sample IS mixed iff its partner row r2 = index[p2] lies in [0, n_rows) and, with `occupancy` (nullable: the
+ *   table of seld_target_occupancy over y_all with the same overlaps),  occ[r, c] + occ[r2, c] <= overlaps  for every
+ *   class c: no frame can then hold more events of a class than it has slots, so no label is ever dropped (the test is
+ *   per clip, not per frame: conservative).  A sample that is not mixed moves as bits, masks aside.
+ *   A mixed sample, per pair (m, p) and (f, t), in fp32 without contraction (S = A, the sample, and B, its partner):
+ *       m_S = fma(x_S[m], sd_m, mean_m)       phi_S = fma(x_S[p], sd_p, mean_p)
+ *       (s_S, c_S) = sincosf(phi_S);   re_S = m_S * c_S;   im_S = m_S * s_S
+ *       re = fma(g, re_B, re_A)               im = fma(g, im_B, im_A)
+ *       m' = sqrtf(fma(im, im, re * re))      phi' = atan2f(im, re)
+ *       x'[m] = __fdiv_rn(m' - mean_m, sd_m)  x'[p] = __fdiv_rn(phi' - mean_p, sd_p)
+ *     (with stats NULL x'[m] = m' and x'[p] = phi').  A lane that owns a 16-byte piece of a pair loads it from both
+ *     channels of both rows, four loads ahead of two stores; a frequency row under a mask is read from neither row.
+ *   Targets of a mixed sample, per (frame, class): the LIST is A's active slots in slot order, then B's.  Output slot k of
+ *   the class takes the activity and the three location values of entry k as bits; slots behind the list get +0.0f in
+ *   all four; entries from `overlaps` on are dropped (without `occupancy` that truncation is the defined result).
+ *   Locations are not scaled by g.  One writer per element, no LDS, no atomics: results are run-to-run identical.
+ *   SELD_EINVAL: whatever seld_gather_rows_polar refuses of the arguments they share; C odd; overlaps < 1; y_cols no
+ *   multiple of 4 * overlaps (with the y pair or with occupancy, which both read y_cols as 4 * classes * overlaps); p_mix
+ *   outside [0, 1]; gains that are not finite or not 0 < gain_lo <= gain_hi; one of partners / gains without the other.
+ *   SELD_EUNSUPPORTED: classes > 64, overlaps > 8, a row of 2^31 floats or more.  Nothing is launched on refusal.
  * seld_epoch_step_end, one thread, as the last launch of a step:
  *     mean[0] += (loss[0] - mean[0]) / (float)(cursor[0] + 1);   cursor[0] += 1          (fp32: the epoch loop's
  *   running mean of the loss, train.py:559, in the form train.main takes it)
@@ -1237,6 +1280,14 @@ int seld_gather_rows_polar(const float* x_all, int64_t row_x, float* out_x, cons
                            int32_t y_cols, const int32_t* epoch, uint64_t seed, uint64_t groups, int32_t n_groups,
                            const float* stats, float p_rot, int32_t rot_mirror, int32_t rot_zflip, const float* matrices,
                            int32_t n_fmask, int32_t f_max, int32_t n_tmask, int32_t t_max, float fill, void* stream);
+int seld_target_occupancy(const float* y_all, int64_t n_rows, int64_t row_y, int32_t y_cols, int32_t overlaps, uint8_t* occ,
+                          void* stream);
+int seld_gather_rows_mix(const float* x_all, int64_t row_x, float* out_x, const float* y_all, int64_t row_y, float* out_y,
+                         const int64_t* index, int64_t n_index, int64_t n_rows, const int32_t* cursor, int64_t cursor_stride,
+                         int64_t start, int32_t B, int32_t count, int32_t C, int32_t F, int32_t T, int32_t y_cols,
+                         const int32_t* epoch, uint64_t seed, int32_t overlaps, const float* stats, float p_mix, float gain_lo,
+                         float gain_hi, const int64_t* partners, const float* gains, const uint8_t* occupancy, int32_t n_fmask,
+                         int32_t f_max, int32_t n_tmask, int32_t t_max, float fill, void* stream);
 int seld_epoch_step_end(const float* loss, float* mean, int32_t* cursor, void* stream);
 
 /* ------------------------------------------------------------------------------------------

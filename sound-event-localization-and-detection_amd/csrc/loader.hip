@@ -9,6 +9,9 @@
 //                         channels of every intensity vector and the DOA labels, then the masks
 //   seld_gather_rows_polar  the rotating gather for magnitude / phase predictors: R mixes the complex value m e^(i phi) of
 //                         the three directional channels of every group (polar to Cartesian, mix, back), then the masks
+//   seld_gather_rows_mix  the gather that mixes a second clip into a sample, for magnitude / phase predictors: the complex
+//                         sum z_A + g z_B per bin, the track slots of both targets packed per (frame, class), then the masks
+//   seld_target_occupancy per resident target row and class the most slots active in one frame (what the mix consults)
 //   seld_epoch_step_end   running mean of the loss, cursor += 1 (the last launch of a step)
 //
 // The gather is an HBM-bound copy (config 3: 2 MB per predictor row, 67 MB per batch): a row is spread over many
@@ -24,6 +27,8 @@
 // The two rotating kernels are ONE body, `rot_gather`, instantiated with the kind of tile that mixes: channel triples
 // (gather_rows_rot_kernel) or magnitude / phase groups with their statistics (gather_rows_polar_kernel); the draw of R,
 // the label rows, the masks, the pass tiles and the walk over "mixing tiles, then pass tiles" are the body's.
+// gather_rows_mix_kernel has the preamble, the masks, the items and the pass tiles of the rotating kernels, a draw of its
+// own (a partner and a gain under another Philox key) and a second source row on both sides.
 //
 // Two things that look alike stay apart on purpose: the signed permutation of gather_rows_aug_kernel (labels sign * v,
 // channels moved and flipped) and the 3x3 matrix of the rotating kernels (fmaf(r2, z, fmaf(r1, y, r0 * x))).  A
@@ -75,7 +80,7 @@ __device__ __forceinline__ void gather_tile(const float* __restrict__ s, float* 
 struct GatherRow {
     bool is_y, valid;           // valid: the position and its index exist; anything else is zero-filled, nothing is read
     int first, step;
-    long long p, row;           // position in `index`; floats in a row of this side
+    long long p, r, row;        // position in `index`, the resident row it names (when valid); floats in a row of this side
     const float* src;           // the resident row (dst when !valid)
     float* dst;
 };
@@ -95,6 +100,7 @@ __device__ __forceinline__ GatherRow resolve_row(const GatherSide& x, const Gath
     long long r = -1;
     if (w.p >= 0 && w.p < n_index) r = index[w.p];
     w.valid = r >= 0 && r < n_rows;
+    w.r = r;
     w.row = sd.row;
     w.dst = sd.out + (long long)b * sd.row;
     w.src = w.valid ? sd.all + r * sd.row : w.dst;
@@ -612,6 +618,209 @@ __global__ __launch_bounds__(TILE_THREADS, 4) void gather_rows_polar_kernel(Gath
     rot_gather<Groups>(resolve_row(x, y, gx, index, n_index, n_rows, cursor, stride, start), epoch, matrices, stats, a, q);
 }
 
+// ---- gather that mixes two clips ---------------------------------------------------------------------------------------------
+// Magnitude and phase of a bin are one complex number and the STFT is linear: the mixture a + g b of two recordings has
+// the spectrum z_A + g z_B bin by bin.  The channels are PAIRS (magnitude c, phase c + C / 2), every one of them mixed (W
+// is a pair like any other), so a mixed sample has pair items only and an unmixed one pass items only: it moves as bits.
+// A pair item is the same piece of both channels of a pair from BOTH rows: four loads in flight ahead of two stores.
+constexpr int MIX_VEC = 1, MIX_MAX_CLASSES = 64, MIX_MAX_OVERLAPS = 8;
+constexpr uint32_t MIX_TILE = TILE_THREADS * MIX_VEC;
+constexpr uint64_t MIX_KEY = 0x9E3779B97F4A7C15ull;         // the four groups of a sample's counter are taken: another key
+
+struct MixParams {
+    int overlaps, classes;      // classes: 0 where nothing needs it (no targets and no occupancy table)
+    float p_mix, gain_lo, gain_hi;
+};
+
+// one (f, t) of one pair, in place: m, ph of row A as stored -> as stored of the mixture with g times (mb, pb) of row B
+template <bool STATS> __device__ __forceinline__ void mix_bin(const PolarStats& st, float g, float& m, float& ph, float mb, float pb) {
+#pragma clang fp contract(off)
+    const float mag_a = STATS ? fmaf(m, st.sd_m, st.mean_m) : m, phi_a = STATS ? fmaf(ph, st.sd_p, st.mean_p) : ph;
+    const float mag_b = STATS ? fmaf(mb, st.sd_m, st.mean_m) : mb, phi_b = STATS ? fmaf(pb, st.sd_p, st.mean_p) : pb;
+    float sa, ca, sb, cb;
+    sincosf(phi_a, &sa, &ca);
+    sincosf(phi_b, &sb, &cb);
+    const float re = fmaf(g, mag_b * cb, mag_a * ca), im = fmaf(g, mag_b * sb, mag_a * sa);
+    const float mag = sqrtf(fmaf(im, im, re * re)), phi = atan2f(im, re);
+    m = STATS ? __fdiv_rn(mag - st.mean_m, st.sd_m) : mag;
+    ph = STATS ? __fdiv_rn(phi - st.mean_p, st.sd_p) : phi;
+}
+
+// items [first, first + MIX_TILE) of the n pair items: item i is piece i % P of pair i / P; `half`: floats between the
+// magnitude and the phase channel of a pair
+template <bool VEC, bool STATS>
+__device__ __forceinline__ void mix_tile(const float* __restrict__ sa, const float* __restrict__ sb, float* __restrict__ d, uint32_t first,
+                                         uint32_t n, uint32_t half, float g, const RotX& a, const PolarStats& st) {
+    float4 v[MIX_VEC][4];
+    uint32_t om[MIX_VEC];
+    RotItem it[MIX_VEC];
+#pragma unroll
+    for (int k = 0; k < MIX_VEC; ++k) {
+        it[k] = rot_item<VEC>(first, k, n, a);
+        om[k] = it[k].u * a.FT + it[k].e;
+        const bool load = it[k].live && !it[k].whole;           // a masked frequency row is read from neither clip
+        const float4 none = make_float4(0.f, 0.f, 0.f, 0.f);
+        v[k][0] = load ? rot_load<VEC>(sa + om[k]) : none;
+        v[k][1] = load ? rot_load<VEC>(sa + om[k] + half) : none;
+        v[k][2] = load ? rot_load<VEC>(sb + om[k]) : none;
+        v[k][3] = load ? rot_load<VEC>(sb + om[k] + half) : none;
+    }
+#pragma unroll
+    for (int k = 0; k < MIX_VEC; ++k) {
+        if (!it[k].live) continue;
+        float* lane[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) lane[j] = reinterpret_cast<float*>(&v[k][j]);
+#pragma unroll
+        for (int q = 0; q < (VEC ? 4 : 1); ++q) mix_bin<STATS>(st, g, lane[0][q], lane[1][q], lane[2][q], lane[3][q]);
+        rot_store<VEC>(d + om[k], rot_masked(v[k][0], it[k].whole, it[k].t0, a));
+        rot_store<VEC>(d + om[k] + half, rot_masked(v[k][1], it[k].whole, it[k].t0, a));
+    }
+}
+
+// the predictor row of one sample: n_a pair items (a mixed sample) in tiles of MIX_TILE, then n_b pass items (an unmixed one)
+template <bool VEC, bool STATS>
+__device__ __forceinline__ void mix_x_row(const float* __restrict__ sa, const float* __restrict__ sb, float* __restrict__ d, uint32_t first,
+                                          uint32_t step, uint32_t n_a, uint32_t n_b, uint32_t half, float g, const RotX& a,
+                                          const PolarStats& st) {
+    const uint32_t tiles_a = (n_a + MIX_TILE - 1u) / MIX_TILE, tiles_b = (n_b + ROT_TILE_B - 1u) / ROT_TILE_B;
+    for (uint32_t tile = first; tile < tiles_a + tiles_b; tile += step) {
+        if (tile < tiles_a) mix_tile<VEC, STATS>(sa, sb, d, tile * MIX_TILE, n_a, half, g, a, st);
+        else rot_tile_pass<VEC>(sa, d, (tile - tiles_a) * ROT_TILE_B, n_b, 0xFEDCBA9876543210ull, a);
+    }
+}
+
+// The target row of a mixed sample.  Per (frame, class) the list of A's active slots in slot order, then B's; output slot k
+// of the class takes activity and location of entry k as bits, +0 behind the list; entries past `overlaps` are dropped
+// (the occupancy test keeps a sample whose clips could overflow from being mixed at all).  Active: activity > 0.5f, so a
+// NaN is not.  One writer per element.
+__device__ __forceinline__ void mix_y_row(const float* __restrict__ sa, const float* __restrict__ sb, float* __restrict__ dst, uint32_t row,
+                                          uint32_t first, uint32_t step, uint32_t n_sed, uint32_t overlaps) {
+    const uint32_t cols = 4u * n_sed;
+    const uint64_t tile_step = (uint64_t)step * (uint64_t)TILE_FLOATS;
+    for (uint64_t off = (uint64_t)first * (uint64_t)TILE_FLOATS; off < row; off += tile_step) {
+        const uint32_t left = row - (uint32_t)off, len = left < TILE_FLOATS ? left : TILE_FLOATS;
+        for (uint32_t i = threadIdx.x; i < len; i += TILE_THREADS) {
+            const uint32_t o = (uint32_t)off + i, j = o % cols, base = o - j;
+            const bool act = j < n_sed;
+            const uint32_t s = act ? j : (j - n_sed) / 3u, axis = act ? 0u : (j - n_sed) - 3u * s;
+            const uint32_t c0 = s - s % overlaps, k = s - c0;       // the first slot of the class, the place in it
+            uint32_t seen = 0u, pick = 2u * overlaps;
+            for (uint32_t e = 0u; e < 2u * overlaps; ++e) {
+                const float v = e < overlaps ? sa[base + c0 + e] : sb[base + c0 + e - overlaps];
+                if (v > 0.5f) {
+                    if (seen == k) pick = e;
+                    ++seen;
+                }
+            }
+            float out = 0.f;
+            if (pick < 2u * overlaps) {
+                const float* __restrict__ src = pick < overlaps ? sa : sb;
+                const uint32_t from = c0 + (pick < overlaps ? pick : pick - overlaps);
+                out = src[base + (act ? from : n_sed + 3u * from + axis)];
+            }
+            dst[o] = out;
+        }
+    }
+}
+
+// grid (gx + gy, count).  Everything up to the tile loops is uniform over the workgroup: the draw or the explicit partner
+// and gain, the partner's resident row, the 2 * classes bytes of the occupancy test, the four statistics, the mask bounds.
+// `epoch`, `partners`, `gains`, `stats` and `occupancy` are __restrict__ arguments and are read before the first store.
+// Two sincosf and one atan2f per position: 74 VGPRs on gfx950, 6 waves per SIMD (gather_rows_polar_kernel, with three of
+// each, has 108 and 4); under the 8 of the plain gathers it would spill.
+__global__ __launch_bounds__(TILE_THREADS, 6) void gather_rows_mix_kernel(GatherSide x, GatherSide y, int gx,
+                                                                       const int64_t* __restrict__ index, long long n_index,
+                                                                       long long n_rows, const int32_t* __restrict__ cursor,
+                                                                       long long stride, long long start,
+                                                                       const int32_t* __restrict__ epoch,
+                                                                       const int64_t* __restrict__ partners,
+                                                                       const float* __restrict__ gains, const float* __restrict__ stats,
+                                                                       const uint8_t* __restrict__ occupancy, AugParams a, MixParams q) {
+    const GatherRow w = resolve_row(x, y, gx, index, n_index, n_rows, cursor, stride, start);
+
+    // the partner of this sample and its gain: explicit, or drawn with the key of the mix
+    uint64_t counter = 0;
+    long long r2 = -1;
+    float g = 0.f;
+    if (w.valid) {
+        counter = sample_counter(epoch, w.p);
+        long long p2 = -1;
+        if (partners) {
+            p2 = partners[blockIdx.y];
+            g = gains[blockIdx.y];
+        } else if (q.p_mix > 0.f && n_index > 1) {
+            const uint4 d = philox4x32_10(counter, a.seed ^ MIX_KEY);
+            if (u01(d.y) < q.p_mix) {           // (p + 1 + int(w[0], n_index - 1)) mod n_index: the sum is below 2 * n_index
+                p2 = w.p + 1 + (long long)int_below(d.x, (uint32_t)(n_index - 1));
+                if (p2 >= n_index) p2 -= n_index;
+            }
+            g = fmaf(u01(d.z), q.gain_hi - q.gain_lo, q.gain_lo);
+        }
+        if (p2 >= 0 && p2 < n_index) r2 = index[p2];
+        if (r2 >= n_rows) r2 = -1;
+    }
+    bool mix = r2 >= 0;
+    if (mix && occupancy) {                     // no class may hold more events in the two clips than it has slots
+        const uint8_t* __restrict__ oa = occupancy + w.r * q.classes;
+        const uint8_t* __restrict__ ob = occupancy + r2 * q.classes;
+        for (int c = 0; c < q.classes; ++c) mix &= (int)oa[c] + (int)ob[c] <= q.overlaps;
+    }
+    PolarStats st{0.f, 1.f, 0.f, 1.f};
+    if (stats && mix && !w.is_y) st = PolarStats{stats[0], stats[1], stats[2], stats[3]};
+
+    if (!w.valid || (w.is_y && !mix)) {         // zero-fill, or targets of a sample that is not mixed
+        plain_row(w);
+        return;
+    }
+
+    const GatherSide sd = w.is_y ? y : x;
+    const float* __restrict__ src = w.src;
+    const float* __restrict__ src2 = mix ? sd.all + r2 * sd.row : w.src;
+    float* __restrict__ dst = w.dst;
+    const uint32_t first = (uint32_t)w.first, step = (uint32_t)w.step;
+    if (w.is_y) {
+        mix_y_row(src, src2, dst, (uint32_t)w.row, first, step, (uint32_t)a.n_sed, (uint32_t)q.overlaps);     // rows are below 2^31 floats
+        return;
+    }
+
+    RotX ax;
+    ax.fm = draw_masks(counter | 1u, a.seed, a.n_fmask, a.f_max, a.F);
+    ax.tm = draw_masks(counter | 2u, a.seed, a.n_tmask, a.t_max, a.T);
+    ax.T = (uint32_t)a.T;
+    ax.FT = (uint32_t)a.F * ax.T;
+    ax.P = a.vec ? ax.FT >> 2 : ax.FT;
+    ax.fill = a.fill;
+    const uint32_t pairs = (uint32_t)a.C >> 1, n_a = mix ? pairs * ax.P : 0u, n_b = mix ? 0u : (uint32_t)a.C * ax.P;
+    const uint32_t half = pairs * ax.FT;
+    if (stats) {
+        if (a.vec) mix_x_row<true, true>(src, src2, dst, first, step, n_a, n_b, half, g, ax, st);
+        else mix_x_row<false, true>(src, src2, dst, first, step, n_a, n_b, half, g, ax, st);
+    } else {
+        if (a.vec) mix_x_row<true, false>(src, src2, dst, first, step, n_a, n_b, half, g, ax, st);
+        else mix_x_row<false, false>(src, src2, dst, first, step, n_a, n_b, half, g, ax, st);
+    }
+}
+
+// occ[r, c]: the largest number of active slots of class c in one frame of target row r.  A workgroup per row (and
+// onwards in steps of the grid), a lane per class: neighbouring lanes read neighbouring slots.  One writer per byte.
+__global__ __launch_bounds__(MIX_MAX_CLASSES) void target_occupancy_kernel(const float* __restrict__ y_all, long long n_rows,
+                                                                          uint32_t row_y, uint32_t cols, uint32_t overlaps,
+                                                                          uint32_t classes, uint8_t* __restrict__ occ) {
+    const uint32_t c = threadIdx.x;
+    if (c >= classes) return;
+    for (long long r = blockIdx.x; r < n_rows; r += gridDim.x) {
+        const float* __restrict__ src = y_all + r * (long long)row_y;
+        uint32_t most = 0u;
+        for (uint32_t base = 0u; base < row_y; base += cols) {
+            uint32_t n = 0u;
+            for (uint32_t e = 0u; e < overlaps; ++e) n += src[base + c * overlaps + e] > 0.5f ? 1u : 0u;
+            most = n > most ? n : most;
+        }
+        occ[r * classes + c] = (uint8_t)most;
+    }
+}
+
 // one thread: the epoch loop's running mean (train.main), `mean += (loss - mean) / (i + 1)` in fp32 with i the cursor,
 // then the cursor
 __global__ void epoch_step_end_kernel(const float* __restrict__ loss, float* __restrict__ mean, int32_t* __restrict__ cursor) {
@@ -771,6 +980,43 @@ extern "C" int seld_gather_rows_polar(const float* x_all, int64_t row_x, float* 
     const AugParams a = aug_params(g, C, F, T, y_cols, seed, n_fmask, f_max, n_tmask, t_max, fill);
     return launch_rotating(gather_rows_polar_kernel, g, a, y_cols, epoch, groups, n_groups, POLAR_MAX_GROUPS, 6, POLAR_TILE, p_rot,
                            rot_mirror, rot_zflip, matrices, stream, stats);
+}
+
+extern "C" int seld_target_occupancy(const float* y_all, int64_t n_rows, int64_t row_y, int32_t y_cols, int32_t overlaps, uint8_t* occ,
+                                     void* stream) {
+    if (!y_all || !occ || n_rows <= 0 || row_y <= 0 || y_cols <= 0 || overlaps <= 0) return SELD_EINVAL;
+    if (y_cols % (4ll * overlaps) || row_y % y_cols) return SELD_EINVAL;
+    const int classes = y_cols / (4 * overlaps);
+    if (classes > MIX_MAX_CLASSES || overlaps > MIX_MAX_OVERLAPS || row_y >= (1ll << 31)) return SELD_EUNSUPPORTED;
+    const long long cap = 1ll << 16;
+    hipLaunchKernelGGL(target_occupancy_kernel, dim3((unsigned)(n_rows < cap ? n_rows : cap)), dim3(MIX_MAX_CLASSES), 0, (hipStream_t)stream,
+                       y_all, (long long)n_rows, (uint32_t)row_y, (uint32_t)y_cols, (uint32_t)overlaps, (uint32_t)classes, occ);
+    return check_launch();
+}
+
+// The grid covers the larger of a mixed and an unmixed sample's tiling, as that of the rotating gathers.
+extern "C" int seld_gather_rows_mix(const float* x_all, int64_t row_x, float* out_x, const float* y_all, int64_t row_y,
+                                    float* out_y, const int64_t* index, int64_t n_index, int64_t n_rows, const int32_t* cursor,
+                                    int64_t cursor_stride, int64_t start, int32_t B, int32_t count, int32_t C, int32_t F,
+                                    int32_t T, int32_t y_cols, const int32_t* epoch, uint64_t seed, int32_t overlaps,
+                                    const float* stats, float p_mix, float gain_lo, float gain_hi, const int64_t* partners,
+                                    const float* gains, const uint8_t* occupancy, int32_t n_fmask, int32_t f_max, int32_t n_tmask,
+                                    int32_t t_max, float fill, void* stream) {
+    const GatherArgs g{x_all, row_x, out_x, y_all, row_y, out_y, index, n_index, n_rows, cursor, cursor_stride, start, B, count};
+    const AugParams a = aug_params(g, C, F, T, y_cols, seed, n_fmask, f_max, n_tmask, t_max, fill);
+    if (aug_gather_refused(g, a, y_cols, epoch)) return SELD_EINVAL;
+    if (C % 2 || overlaps < 1) return SELD_EINVAL;
+    const bool slots = g.has_y() || occupancy;                                      // what reads y_cols as classes * overlaps
+    if (slots && (y_cols < 4 || y_cols % (4ll * overlaps))) return SELD_EINVAL;
+    if (!(p_mix >= 0.f && p_mix <= 1.f)) return SELD_EINVAL;                        // a NaN fails both
+    if (!(gain_lo > 0.f && gain_lo <= gain_hi && gain_hi < INFINITY)) return SELD_EINVAL;
+    if ((partners != nullptr) != (gains != nullptr)) return SELD_EINVAL;
+    const int classes = slots ? y_cols / (4 * overlaps) : 0;
+    if (classes > MIX_MAX_CLASSES || overlaps > MIX_MAX_OVERLAPS || long_rows(g)) return SELD_EUNSUPPORTED;
+    const MixParams q{overlaps, classes, p_mix, gain_lo, gain_hi};
+    const long long P = a.vec ? (long long)a.F * a.T / 4 : (long long)a.F * a.T;
+    const long long t_mix = tiles_of(a.C / 2 * P, MIX_TILE), t_plain = tiles_of(a.C * P, ROT_TILE_B);
+    return launch_gather(gather_rows_mix_kernel, g, t_mix > t_plain ? t_mix : t_plain, stream, epoch, partners, gains, stats, occupancy, a, q);
 }
 
 extern "C" int seld_epoch_step_end(const float* loss, float* mean, int32_t* cursor, void* stream) {

@@ -13,9 +13,10 @@ import torch
 from .. import _lib as L
 from ._core import _req, timed
 
-__all__ = ["gather_rows", "gather_rows_aug", "gather_rows_rot", "gather_rows_polar", "Augment", "foa_transforms", "foa_triples",
-           "foa_polar", "epoch_step_end", "epoch_permutation"]
+__all__ = ["gather_rows", "gather_rows_aug", "gather_rows_rot", "gather_rows_polar", "gather_rows_mix", "target_occupancy", "Augment",
+           "foa_transforms", "foa_triples", "foa_polar", "epoch_step_end", "epoch_permutation"]
 AUG_MAX_CHANNELS, AUG_MAX_TRANSFORMS, ROT_MAX_TRIPLES, POLAR_MAX_GROUPS = 16, 64, 5, 2
+MIX_MAX_CLASSES, MIX_MAX_OVERLAPS = 64, 8
 
 
 def _rows(t, what, name):
@@ -254,7 +255,11 @@ class Augment:
 
     What seld_gather_rows_polar applies (hip_ops.gather_rows_polar): the same p_rot, rot_mirror and rot_zflip on
     magnitude-phase predictors; rot_polar, 1..2 channel groups (mx, my, mz, px, py, pz), e.g. `foa_polar(...)`, held as a
-    tuple of tuples.  p_rot > 0 needs exactly one of rot_triples and rot_polar."""
+    tuple of tuples.  p_rot > 0 needs exactly one of rot_triples and rot_polar.
+
+    What seld_gather_rows_mix applies (hip_ops.gather_rows_mix): p_mix, the probability that a second clip of the epoch is
+    mixed into a sample of magnitude-phase predictors, with a gain drawn uniformly from mix_gain = (lo, hi),
+    0 < lo <= hi.  p_mix > 0 excludes p_rot > 0 and p_swap > 0 (one transforming gather per sample); masks go with it."""
     table: object = None
     p_swap: float = 0.0
     freq_masks: int = 0
@@ -268,6 +273,8 @@ class Augment:
     rot_mirror: bool = True
     rot_zflip: bool = True
     rot_polar: object = None
+    p_mix: float = 0.0
+    mix_gain: tuple = (0.5, 1.0)
 
     def __post_init__(self):
         host = None if self.table is None else _check_table(self.table, None)
@@ -290,12 +297,25 @@ class Augment:
             raise L.SeldHipError("Augment: p_rot > 0 with both rot_triples and rot_polar (one kind of predictors per loader)")
         if float(self.p_rot) > 0.0 and float(self.p_swap) > 0.0:
             raise L.SeldHipError("Augment: p_rot > 0 together with p_swap > 0 (one channel transform per sample)")
+        if not 0.0 <= float(self.p_mix) <= 1.0:
+            raise L.SeldHipError(f"Augment: p_mix {self.p_mix} is no probability")
+        try:
+            lo, hi = (float(v) for v in self.mix_gain)
+        except (TypeError, ValueError):
+            raise L.SeldHipError(f"Augment: mix_gain must be a pair (lo, hi), got {self.mix_gain!r}") from None
+        if not (0.0 < lo <= hi < float("inf")):
+            raise L.SeldHipError(f"Augment: mix_gain needs finite 0 < lo <= hi, got {(lo, hi)}")
+        object.__setattr__(self, "mix_gain", (lo, hi))
+        if float(self.p_mix) > 0.0 and (float(self.p_rot) > 0.0 or float(self.p_swap) > 0.0):
+            raise L.SeldHipError("Augment: p_mix > 0 together with p_rot > 0 or p_swap > 0 (one transforming gather per sample)")
         object.__setattr__(self, "table", None if host is None else torch.from_numpy(host).to(self.device))
 
     @property
     def kind(self):
-        """Which gather a loader fetches with: 'polar' (gather_rows_polar) or 'rot' (gather_rows_rot) when p_rot > 0, by the
-        channel sets given; otherwise 'swap' (gather_rows_aug: table and masks)."""
+        """Which gather a loader fetches with: 'mix' (gather_rows_mix) when p_mix > 0; 'polar' (gather_rows_polar) or 'rot'
+        (gather_rows_rot) when p_rot > 0, by the channel sets given; otherwise 'swap' (gather_rows_aug: table and masks)."""
+        if float(self.p_mix) > 0.0:
+            return "mix"
         if float(self.p_rot) > 0.0:
             return "polar" if self.rot_polar is not None else "rot"
         return "swap"
@@ -329,18 +349,22 @@ class Augment:
         return 0 if self.table is None else self.table.shape[0]
 
 
-def _launch_aug(what, gather, epoch, seed, augment, field, own, matrices=None, stats=None):
-    """What the three augmenting gathers do alike.  The checks of `_gather_args` (`gather`: its arguments behind `what`), of
+def _launch_aug(what, gather, epoch, seed, augment, field, own, matrices=None, stats=None, y_cols=None):
+    """What the four augmenting gathers do alike.  The checks of `_gather_args` (`gather`: its arguments behind `what`), of
     `augment`, `epoch` and the geometry: predictors (n, C, F, T), targets (n, ..., 4 * n_sed).  `field` names the channel
-    sets of a rotating gather, which must be there and fit into C (None: the table, which must be for C channels);
-    without predictors C is what the sets or the table need.  `matrices` and `stats` as the rotating entry points read
-    them.  Then the launch with `own()`, the arguments of this entry point alone, between (C, F, T, y_cols, epoch, seed)
-    and the masks."""
+    sets of a rotating gather, which must be there and fit into C (None: the table, which must be for C channels; 'mix':
+    neither, every channel takes part and C is 2 without predictors); without predictors C is what the sets or the table
+    need.  `matrices` and `stats` as the rotating entry points read them; `y_cols`: the target columns where there are no
+    targets to tell (the mix with an occupancy table).  Then the launch with `own()`, the arguments of this entry point
+    alone, between (C, F, T, y_cols, epoch, seed) and the masks."""
     if not isinstance(augment, Augment):
         raise L.SeldHipError(f"{what}: augment must be an Augment, got {type(augment).__name__}")
+    mix = field == "mix"
+    if mix:
+        field = None
     if field is not None and getattr(augment, field) is None:
         raise L.SeldHipError(f"{what}: the Augment has no {field}")
-    channels = augment.channels if field is None else _least_channels(getattr(augment, field))
+    channels = 2 if mix else augment.channels if field is None else _least_channels(getattr(augment, field))
     g = _gather_args(what, *gather)
     x_all, y_all, _, _, dev, count, _, _ = g
     if _scalar(epoch, what, "epoch", torch.int32).device != dev:
@@ -352,13 +376,13 @@ def _launch_aug(what, gather, epoch, seed, augment, field, own, matrices=None, s
         C, F, T = x_all.shape[1:]
         if field is not None and channels > C:
             raise L.SeldHipError(f"{what}: {field} name channel {channels - 1}, the predictors have {C}")
-    y_cols = 4
+    y_cols = 4 if y_cols is None else int(y_cols)
     if y_all is not None:
         if y_all.dim() < 2:
             raise L.SeldHipError(f"{what}: targets must be (n, ..., 4 * n_sed), got {tuple(y_all.shape)}")
         y_cols = y_all.shape[-1]
     table = augment.table
-    if field is None and table is not None and (table.device != dev or channels != C):
+    if field is None and not mix and table is not None and (table.device != dev or channels != C):
         raise L.SeldHipError(f"{what}: the transform table is for {channels} channels on {table.device}, "
                              f"the predictors have {C} on {dev}")
     if matrices is not None:
@@ -438,6 +462,84 @@ def gather_rows_polar(x_all, y_all, index, out_x, out_y, *, epoch, seed, augment
                        "rot_polar",
                        lambda: (augment.polar_packed, len(augment.rot_polar), L.ptr(stats)) + _rotation_args(augment, matrices),
                        matrices, stats)
+
+
+def target_occupancy(y_all, overlaps):
+    """uint8 (n, classes): per target row and class the largest number of slots that are active (activity > 0.5) in one
+    frame (seld_target_occupancy).  y_all (n, ..., 4 * classes * overlaps): contiguous fp32 on the device, the slot of
+    (class c, place o) at column c * overlaps + o.  What `gather_rows_mix(occupancy=...)` consults; made once per array,
+    outside any capture (it allocates)."""
+    y_all, row_y = _rows(y_all, "target_occupancy", "y_all")
+    overlaps = int(overlaps)
+    if y_all is None or y_all.dim() < 2 or y_all.shape[0] < 1 or row_y < 1:
+        raise L.SeldHipError(f"target_occupancy: targets must be (n, ..., 4 * n_sed), got {None if y_all is None else tuple(y_all.shape)}")
+    y_cols = y_all.shape[-1]
+    if overlaps < 1 or y_cols % (4 * overlaps):
+        raise L.SeldHipError(f"target_occupancy: {y_cols} target columns are not 4 * classes * {overlaps} overlaps")
+    occ = torch.empty((y_all.shape[0], y_cols // (4 * overlaps)), device=y_all.device, dtype=torch.uint8)
+    with torch.cuda.device(y_all.device):
+        L.check(L.lib().seld_target_occupancy(L.ptr(y_all), y_all.shape[0], row_y, y_cols, overlaps, L.ptr(occ), L.current_stream()),
+                "seld_target_occupancy")
+    return occ
+
+
+def _per_sample(t, what, name, dtype, dev, count):
+    if not torch.is_tensor(t) or t.device != dev or t.dtype != dtype or not t.is_contiguous() or t.dim() != 1 or t.shape[0] < count:
+        raise L.SeldHipError(f"{what}: {name} must be a contiguous {dtype} tensor of {count} entries on {dev}, "
+                             f"got {getattr(t, 'shape', type(t).__name__)}")
+    return t
+
+
+def gather_rows_mix(x_all, y_all, index, out_x, out_y, *, epoch, seed, augment, overlaps, stats=None, partners=None, gains=None,
+                    occupancy=None, cursor=None, start=0, count=None, stride=None):
+    """`gather_rows` with a second clip mixed into every sample that draws one, then the masks of `augment`, in ONE launch
+    (seld_gather_rows_mix; include/seld_hip.h has the draw and the formula).  Predictors are magnitude-phase, channel
+    c < C / 2 a magnitude and c + C / 2 its phase: a mixed sample gets, per pair and (f, t), the complex sum
+    z_A + g z_B written back as magnitude and phase, which is what the STFT of the mixed waveforms holds.  Its targets
+    (..., 4 * classes * overlaps) are merged per (frame, class): A's active slots, then B's, packed into the `overlaps`
+    slots; entries beyond them are dropped.  With `occupancy` (`target_occupancy(y_all, overlaps)`) a pair of clips that
+    could overflow a class is not mixed at all, so no label is lost.  The partner is drawn with probability
+    augment.p_mix among the OTHER positions of `index` and the gain from augment.mix_gain, from (seed, epoch, position);
+    or, with `partners` (int64, count) and `gains` (fp32, count) on the device, sample b takes the position partners[b]
+    (negative: no mix) and gains[b] as they are.  stats as in `gather_rows_polar`.  Geometry, epoch, cursor, start, count,
+    stride and the zero rows of invalid positions as in `gather_rows_aug`; augment.table, p_swap and the rotation fields
+    are not used."""
+    what = "gather_rows_mix"
+    overlaps = int(overlaps)
+    if not isinstance(augment, Augment):
+        raise L.SeldHipError(f"{what}: augment must be an Augment, got {type(augment).__name__}")
+    if not 1 <= overlaps <= MIX_MAX_OVERLAPS:
+        raise L.SeldHipError(f"{what}: 1..{MIX_MAX_OVERLAPS} overlaps, got {overlaps}")
+    if (partners is None) != (gains is None):
+        raise L.SeldHipError(f"{what}: partners and gains are given together or not at all")
+    if torch.is_tensor(x_all) and x_all.dim() == 4 and x_all.shape[1] % 2:
+        raise L.SeldHipError(f"{what}: magnitude-phase predictors have an even number of channels, got {x_all.shape[1]}")
+    y_cols = None
+    if torch.is_tensor(y_all) and y_all.dim() >= 2:
+        y_cols = y_all.shape[-1]
+    if occupancy is not None:
+        if not torch.is_tensor(occupancy) or occupancy.dtype != torch.uint8 or not occupancy.is_contiguous() or occupancy.dim() != 2:
+            raise L.SeldHipError(f"{what}: occupancy must be the contiguous uint8 table (n, classes) of target_occupancy")
+        y_cols = 4 * overlaps * occupancy.shape[1] if y_cols is None else y_cols
+        if y_cols != 4 * overlaps * occupancy.shape[1]:
+            raise L.SeldHipError(f"{what}: an occupancy table of {occupancy.shape[1]} classes with {y_cols} target columns "
+                                 f"and {overlaps} overlaps")
+    if y_cols is not None and (y_cols % (4 * overlaps) or y_cols // (4 * overlaps) > MIX_MAX_CLASSES):
+        raise L.SeldHipError(f"{what}: {y_cols} target columns are not 4 * (1..{MIX_MAX_CLASSES} classes) * {overlaps} overlaps")
+
+    def own():
+        n = (x_all if x_all is not None else y_all).shape[0]
+        dev = (x_all if x_all is not None else y_all).device
+        rows = (out_x if out_x is not None else out_y).shape[0] if count is None else int(count)
+        if partners is not None:
+            _per_sample(partners, what, "partners", torch.int64, dev, rows)
+            _per_sample(gains, what, "gains", torch.float32, dev, rows)
+        if occupancy is not None and (occupancy.device != dev or occupancy.shape[0] != n):
+            raise L.SeldHipError(f"{what}: the occupancy table has {occupancy.shape[0]} rows on {occupancy.device}, the arrays {n} on {dev}")
+        return (overlaps, L.ptr(stats), float(augment.p_mix), augment.mix_gain[0], augment.mix_gain[1], L.ptr(partners), L.ptr(gains),
+                L.ptr(occupancy))
+    return _launch_aug(what, (x_all, y_all, index, out_x, out_y, cursor, start, count, stride), epoch, seed, augment, "mix", own,
+                       None, stats, y_cols)
 
 
 def epoch_step_end(loss, mean, cursor):

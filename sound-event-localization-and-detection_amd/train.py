@@ -571,7 +571,15 @@ _EVAL = ('use_cuda', 'early_stopping', 'fixed_seed', 'pool_size', 'cnn_filters',
 # lr * min(1, step / N) on top of StepLR (host side: the factor FlatAdam.lr_scale);
 # at_key_size / at_value_size / at_mask / at_band (off by default): at_key_size=K puts a temporal-attention block
 # (hip_nn.TemporalAttention, key width K, value width at_value_size or K) in front of every dilation stack of the TCN;
-# at_mask: none | causal | band, the band +-at_band frames wide
+# at_mask: none | causal | band, the band +-at_band frames wide;
+# augment_mix=P (off by default; needs resident_loader, feature_layout=magphase and phase=True; not with augment_rotate or
+# augment_swap; masks go with it): with probability P another clip of the epoch is mixed into a sample with a gain drawn
+# from [augment_mix_gain_lo, augment_mix_gain_hi] (hip_ops.gather_rows_mix, the same single launch): per bin the complex
+# sum z_A + g z_B, which is the STFT of the mixed waveforms, and per (frame, class) the active track slots of both targets
+# packed into the class_overlaps slots.  A pair of clips that could overflow a class (hip_ops.target_occupancy, computed
+# once for the training array) is not mixed, so no label is dropped; a standardising dataset_normalization is undone and
+# redone around the sum with the training array's statistics.  Magnitudes alone and intensity vectors are not linear in the
+# waveform and stay refused
 _EXTRA = [('synthetic', int, 0), ('max_steps', int, 0), ('epochs', int, 0), ('resident_loader', str, 'False'),
           ('graph_step', str, 'False'), ('augment_swap', float, 0.), ('augment_freq_masks', int, 0),
           ('augment_freq_width', int, 0), ('augment_time_masks', int, 0), ('augment_time_width', int, 0),
@@ -582,7 +590,8 @@ _EXTRA = [('synthetic', int, 0), ('max_steps', int, 0), ('epochs', int, 0), ('re
           ('class_report', str, 'False'), ('metrics_average', str, 'micro'),
           ('grad_clip', float, 0.), ('weight_decay', float, 0.), ('decoupled_weight_decay', str, 'False'),
           ('ema_decay', float, 0.), ('warmup_steps', int, 0),
-          ('at_key_size', int, 0), ('at_value_size', int, 0), ('at_mask', str, 'causal'), ('at_band', int, 0)]
+          ('at_key_size', int, 0), ('at_value_size', int, 0), ('at_mask', str, 'causal'), ('at_band', int, 0),
+          ('augment_mix', float, 0.), ('augment_mix_gain_lo', float, 0.5), ('augment_mix_gain_hi', float, 1.0)]
 
 
 def build_parser():
@@ -889,9 +898,11 @@ class ResidentLoader:
     ranks need no agreement, and a recorded fetch draws anew in every epoch.  `epoch` is -1 until the first
     `begin_epoch`, which adds 1 to it.  An `augment` with rot_polar and p_rot > 0 (magnitude-phase predictors) fetches
     with hip_ops.gather_rows_polar; `polar_stats` is then the fp32 device tensor (mean_m, sd_m, mean_p, sd_p) with which
-    `x_all` was standardised (`polar_stats_from`), None for raw magnitude and phase."""
+    `x_all` was standardised (`polar_stats_from`), None for raw magnitude and phase.  An `augment` with p_mix > 0 fetches
+    with hip_ops.gather_rows_mix: `overlaps` is the number of track slots per class of the targets, `polar_stats` means
+    what it means above, and the occupancy table of the targets (hip_ops.target_occupancy) is computed here, once."""
 
-    def __init__(self, x_all, y_all, batch_size, shuffle, rank=0, world=1, augment=None, seed=0, polar_stats=None):
+    def __init__(self, x_all, y_all, batch_size, shuffle, rank=0, world=1, augment=None, seed=0, polar_stats=None, overlaps=None):
         self.plan = epoch_plan(x_all.shape[0], batch_size, world)
         if y_all.shape[0] != x_all.shape[0]:
             raise ValueError(f"ResidentLoader: {x_all.shape[0]} predictors but {y_all.shape[0]} targets")
@@ -906,6 +917,12 @@ class ResidentLoader:
         self.mean = torch.zeros(1, device=dev, dtype=torch.float32)
         self.epoch = torch.full((1,), -1, device=dev, dtype=torch.int32)
         self.augment, self.seed, self.polar_stats = augment, int(seed), polar_stats
+        self.overlaps = self.occupancy = None
+        if augment is not None and augment.kind == "mix":
+            if overlaps is None:
+                raise ValueError("ResidentLoader: an augment that mixes clips needs `overlaps`, the track slots per class of the targets")
+            self.overlaps = int(overlaps)
+            self.occupancy = H.target_occupancy(self.y_all, self.overlaps)
 
     def __len__(self):
         return len(self.plan)
@@ -933,8 +950,10 @@ class ResidentLoader:
             H.gather_rows(self.x_all, self.y_all, self.index, self.x, self.target, **where)
         else:
             kind = self.augment.kind
-            gather = {"swap": H.gather_rows_aug, "rot": H.gather_rows_rot, "polar": H.gather_rows_polar}[kind]
+            gather = {"swap": H.gather_rows_aug, "rot": H.gather_rows_rot, "polar": H.gather_rows_polar, "mix": H.gather_rows_mix}[kind]
             own = dict(stats=self.polar_stats) if kind == "polar" else {}
+            if kind == "mix":
+                own = dict(stats=self.polar_stats, overlaps=self.overlaps, occupancy=self.occupancy)
             gather(self.x_all, self.y_all, self.index, self.x, self.target, epoch=self.epoch, seed=self.seed, augment=self.augment,
                    **own, **where)
         return self.x[:count], self.target[:count]
@@ -1053,7 +1072,7 @@ def feature_layout(args, flag):
 
 def augment_requested(args):
     return (args.augment_swap > 0 or args.augment_freq_masks > 0 or args.augment_time_masks > 0
-            or getattr(args, 'augment_rotate', 0.) > 0)
+            or getattr(args, 'augment_rotate', 0.) > 0 or getattr(args, 'augment_mix', 0.) != 0)
 
 
 def augment_from_args(args, device):
@@ -1066,6 +1085,27 @@ def augment_from_args(args, device):
     swap, rotate = args.augment_swap > 0, getattr(args, 'augment_rotate', 0.)
     if not 0. <= rotate <= 1.:
         raise ValueError(f"--augment_rotate is a probability, got {rotate}")
+    mix = getattr(args, 'augment_mix', 0.)
+    if not 0. <= mix <= 1.:
+        raise ValueError(f"--augment_mix is a probability, got {mix}")
+    if mix > 0:
+        if rotate > 0 or swap:
+            raise ValueError("--augment_mix with --augment_rotate or --augment_swap: one transforming gather per sample "
+                             "(composing them in one launch is not built)")
+        layout = feature_layout(args, "--augment_mix")
+        if layout != 'magphase' or not args.phase:
+            raise ValueError(f"--augment_mix needs --feature_layout=magphase with --phase=True, got {layout}"
+                             + ("" if args.phase else " without phase")
+                             + ": magnitude and phase together are linear in the waveform (the mixture's spectrum is the sum "
+                               "of the spectra); magnitudes alone and intensity vectors are not linear and cannot be mixed")
+        lo, hi = args.augment_mix_gain_lo, args.augment_mix_gain_hi
+        if not (0. < lo <= hi < float('inf')):
+            raise ValueError(f"--augment_mix_gain_lo / --augment_mix_gain_hi need finite 0 < lo <= hi, got {lo}, {hi}")
+        if not 1 <= args.class_overlaps <= H.loader.MIX_MAX_OVERLAPS:
+            raise ValueError(f"--augment_mix packs at most {H.loader.MIX_MAX_OVERLAPS} track slots per class, got --class_overlaps "
+                             f"{args.class_overlaps}")
+        return H.Augment(freq_masks=args.augment_freq_masks, freq_width=args.augment_freq_width, time_masks=args.augment_time_masks,
+                         time_width=args.augment_time_width, device=device, p_mix=mix, mix_gain=(lo, hi))
     if rotate > 0 and swap:
         raise ValueError("--augment_rotate with --augment_swap: the rotations with their mirrors contain the signed "
                          "permutations, one channel transform per sample")
@@ -1437,6 +1477,8 @@ def main(args, history=None):
         raise ValueError("--graph_step needs --resident_loader")
     if augment_requested(args) and not resident:
         raise ValueError("--augment_* flags need --resident_loader (the augmentation is part of the device gather)")
+    if getattr(args, 'augment_mix', 0.) != 0:
+        augment_from_args(args, "cpu")                  # its refusals, before the device is touched
     ensemble = ensemble_from_args(args)
     post = postprocess_from_args(args)
     class_report_from_args(args)
@@ -1497,7 +1539,7 @@ def main(args, history=None):
         def loader(x, y, batch_size, shuffle, rank=0, world=1, augment=None, polar_stats=None):
             if resident:
                 return ResidentLoader(x, y, batch_size, shuffle, rank, world, augment=augment, seed=args.augment_seed,
-                                      polar_stats=polar_stats)
+                                      polar_stats=polar_stats, overlaps=args.class_overlaps if augment is not None else None)
             return torch.utils.data.DataLoader(torch.utils.data.TensorDataset(x, y), batch_size, shuffle=shuffle,
                                                pin_memory=False)
         augment = augment_from_args(args, device)      # the training loader's alone: validation and test see the data as it is
@@ -1513,7 +1555,7 @@ def main(args, history=None):
             normalize_dataset(args, xs, stats=norm_stats)
         # the rotating gather of magnitude-phase predictors undoes and redoes the standardisation: it takes the training
         # array's own statistics, which every rank computed from the same array
-        polar = augment is not None and augment.kind == "polar"
+        polar = augment is not None and augment.kind in ("polar", "mix")        # the mix does the same around its sum
         tr_data = loader(xs, ys, args.batch_size, True, rank, world, augment,
                          polar_stats_from(norm_stats[0], device) if polar else None)
         if rank == 0:
