@@ -14,6 +14,8 @@ import os
 import torch
 import torch.distributed as dist
 
+from .step import train_step
+
 
 def init_from_env(backend=None):
     """Initialise the default process group from RANK / WORLD_SIZE / LOCAL_RANK / MASTER_* (torchrun)."""
@@ -111,15 +113,15 @@ def cut_backward_here(module, x):
         # a backward pass ran to the cut and nobody ran the rest: the front end would silently get no gradient
         raise RuntimeError("BackwardCut: the previous step's backward pass stopped at the front-end cut and finish() was "
                            "never called (use dp.dp_train_step / GraphedTrainStep, or remove() the cut before a plain "
-                           "loss.backward())")
+                           "backward pass)")
     leaf = x.detach().requires_grad_(True)
     cuts.append((x, leaf))
     return leaf
 
 
 class BackwardCut:
-    """Splits the backward pass at the input of every TCN (the output of the front-end convolutions): `loss.backward()`
-    then stops there -- every gradient of the TCN, the attention and the heads is complete and can be exchanged -- and
+    """Splits the backward pass at the input of every TCN (the output of the front-end convolutions): the loss's backward
+    pass then stops there -- every gradient of the TCN, the attention and the heads is complete and can be exchanged -- and
     `finish()` runs the rest (the front end), which overlaps that exchange.  The model cooperates through
     `cut_backward_here` (model.ConvTC_Block.forward calls it on its TCN input)."""
 
@@ -236,39 +238,10 @@ def average_bn_running_stats(module):
         off += b.numel()
 
 
-def _join_side_stream():
-    """The accumulating weight-gradient kernels run on hip_ops' side stream: a collective may only read the gradient
-    buffer after the compute stream has joined it."""
-    from . import hip_ops as H
-    H.join_side_stream()
-
-
 def dp_train_step(model, optimizer, sync, x, target, n_sed, loss_fn, sed_weight=1.0, doa_weight=5.0):
-    """One data-parallel step on this rank's shard (eager; train.GraphedTrainStep is the recorded form):
-    zero_grad -> fwd -> loss -> bwd [-> exchange of the main bucket || bwd of the front end -> exchange of the late
-    bucket] -> Adam(mean gradient)."""
-    optimizer.zero_grad()
-    cut = getattr(sync, "cut", None)
-    if cut is not None:
-        cut.reset()
-    sed, doa = model(x)
-    loss = loss_fn(sed, doa, target, n_sed, sed_weight, doa_weight)
-    from .hip_ops import backward_from_loss
-    backward_from_loss(loss)
-    if x.is_cuda:
-        _join_side_stream()
-    if isinstance(sync, BucketedGradSync):
-        sync.reduce_main()
-        if cut is not None:
-            cut.finish()
-            if x.is_cuda:
-                _join_side_stream()
-        sync.reduce_late()
-        sync.wait()
-    else:
-        sync.all_reduce()
-    optimizer.step(grad_scale=sync.average_scale())
-    return loss
+    """One eager data-parallel step on this rank's shard: step.train_step, which spells the order out, under the name and
+    signature its callers know (step.GraphedTrainStep is the recorded form).  `sync`: a BucketedGradSync or a FlatGradSync."""
+    return train_step(model, optimizer, sync, x, target, loss_fn, n_sed, sed_weight, doa_weight)
 
 
 def seed_rank_streams(rank):

@@ -23,7 +23,7 @@ from .smooth import *           # noqa: F401,F403
 from .squeeze_excite import *   # noqa: F401,F403
 from .temporal_attention import *  # noqa: F401,F403
 from .features import *         # noqa: F401,F403
-# `import *` skips underscore names: the ones train.py, the tests and tools/ reach, and the rest of the module surface
+# `import *` skips underscore names: the ones the training harness, the tests and tools/ reach, and the rest of the module surface
 from ._core import _drop_kernel_choice_caches, _pair, _req, _scratch_pools  # noqa: F401
 from .train_ops import _req_inplace, _unit_gradients  # noqa: F401
 from .norm_act import (_claim_grad_slots, _direct_targets, _identity_cache, _nbt, _ncs, _one_pass_ok, _Philox,  # noqa: F401

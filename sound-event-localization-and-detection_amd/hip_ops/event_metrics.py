@@ -18,7 +18,7 @@ EVENT_METRICS_MAX_TRACKS_EX = 8     # SELD_EVENT_METRICS_MAX_TRACKS_EX: the most
 
 def event_metrics_new(device):
     """Zeroed accumulators for `score_events`: (16 int64 counters in EVENT_METRIC_COUNTERS order, 1 double).  The first 13
-    are METRIC_COUNTERS, so `train.test_results_from_counters` reads them unchanged."""
+    are METRIC_COUNTERS, so `evaluate.test_results_from_counters` reads them unchanged."""
     return (torch.zeros(len(EVENT_METRIC_COUNTERS), device=device, dtype=torch.int64),
             torch.zeros(1, device=device, dtype=torch.float64))
 

@@ -132,7 +132,7 @@ def foa_triples(order="WYZX", mics=1, layout="quaternion"):
 def foa_polar(order="WYZX", mics=1):
     """The channel groups (mx, my, mz, px, py, pz) of `Augment(rot_polar=...)` for magnitude-phase predictors in the layout
     [magnitude mic A | magnitude mic B | phase mic A | phase mic B] (C = 8 * mics: what `foa_transforms(phase=True)` and
-    train.normalize_dataset assume): magnitude and phase channel of the x, y and z axis, one group per microphone.
+    data.normalize_dataset assume): magnitude and phase channel of the x, y and z axis, one group per microphone.
     `order` names the channels of a 4-channel block; W may sit anywhere in it and is in no group (it is copied)."""
     pos = _axis_positions("foa_polar", order, mics)
     return [tuple(4 * g + p for p in pos) + tuple(4 * (mics + g) + p for p in pos) for g in range(mics)]
@@ -148,7 +148,7 @@ def foa_transforms(order="WYZX", mics=1, phase=False, elevation=True, layout="ma
     x, y, z = 0, 1, 2) and does the same to the directional channels of every microphone's 4-channel block: the channel
     of axis a becomes sign[a] times the channel of axis[a]; W stays.  `order` names the channels of a block.
 
-    Channel layout, as train.normalize_dataset assumes: [magnitude mic A | magnitude mic B | phase mic A | phase mic B]
+    Channel layout, as data.normalize_dataset assumes: [magnitude mic A | magnitude mic B | phase mic A | phase mic B]
     (the second microphone with mics == 2, the phase half with phase=True), C = 4 * mics * (2 if phase else 1).
     Magnitude channels get flip 0 (a magnitude has no sign).  Phase channels get flip 2 where the sign is -1: the
     phase turned by pi.  Flip 2 is valid on RAW phase only, values in (-pi, pi]; on standardised phase it is wrong,
@@ -454,7 +454,7 @@ def gather_rows_polar(x_all, y_all, index, out_x, out_y, *, epoch, seed, augment
     group and (f, t), the complex 3-vector m e^(i phi) of its directional channels multiplied by R and written back as
     magnitude and phase; location'(s, a) = sum_j R[a][j] location(s, j); every other channel (W among them) and the
     activity are copied; then the masks of `augment`.  stats: fp32 device tensor (mean_m, sd_m, mean_p, sd_p) when the
-    predictors are standardised per half as train.normalize_dataset leaves them (the kernel undoes and redoes it around
+    predictors are standardised per half as data.normalize_dataset leaves them (the kernel undoes and redoes it around
     the rotation), None for raw magnitude and phase; its content is checked at the first call with that tensor.  R,
     `matrices`, geometry, epoch, cursor, start, count, stride and the zero rows of invalid positions as in
     `gather_rows_rot`.  augment.table, p_swap and rot_triples are not used."""

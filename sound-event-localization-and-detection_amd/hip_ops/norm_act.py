@@ -385,7 +385,7 @@ class _Philox:
     the counter of a draw is  host offset (advances by the number of 128-bit draws) + device base.
 
     The device base is word 0 of the per-device STEP STATE (4 x uint64, see seld_step_begin in include/seld_hip.h):
-    it is zero in eager mode; a step recorded as a HIP graph (train.GraphedTrainStep) is captured with host offsets that
+    it is zero in eager mode; a step recorded as a HIP graph (step.GraphedTrainStep) is captured with host offsets that
     start at zero and replays with the base advanced by the draws of one step, so every replay sees fresh masks."""
 
     def __init__(self):
@@ -413,7 +413,7 @@ class _Philox:
         return self.seed(), off, self.state(device)
 
     def get_offset(self):
-        """Absolute position in the stream (checkpointed by train.save_model): host offset + device base."""
+        """Absolute position in the stream (checkpointed by checkpoint.save_model): host offset + device base."""
         base = sum(int(t[0].item()) for t in self._state.values())
         return self.offset + base
 

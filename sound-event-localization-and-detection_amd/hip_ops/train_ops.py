@@ -51,7 +51,7 @@ def unit_gradient(device):
 
 
 def backward_from_loss(loss):
-    """loss.backward() seeded with the cached unit gradient."""
+    """The backward pass from `loss`, seeded with the cached unit gradient."""
     loss.backward(unit_gradient(loss.device))
 
 

@@ -95,7 +95,7 @@ class _HcqWeights:
 
     def refresh_table(self):
         """Bring the device-side table up to date with the registered entries WITHOUT packing (host work + two small
-        host-to-device copies).  train.GraphedTrainStep calls it right before recording: entries registered during the
+        host-to-device copies).  step.GraphedTrainStep calls it right before recording: entries registered during the
         warm-up step left the table dirty, and the copies are not allowed inside a stream capture."""
         return self._collect()[0]
 

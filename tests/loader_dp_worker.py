@@ -22,7 +22,7 @@ def main():
     rank = int(os.environ["RANK"])
     saves = []
     save_model = T.save_model
-    T.save_model = lambda *a, **k: (saves.append(rank), save_model(*a, **k))[1]
+    importlib.import_module(PKG).checkpoint.save_model = lambda *a, **k: (saves.append(rank), save_model(*a, **k))[1]
     made = {}
     adam = T.FlatAdam
     T.FlatAdam = lambda *a, **k: made.setdefault("opt", adam(*a, **k))

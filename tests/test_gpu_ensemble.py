@@ -326,11 +326,11 @@ def test_predict_recordings_without_overlap_or_transforms_is_the_models_output()
         want_sed, want_doa = model(xb[:4])
     assert torch.equal(sed, want_sed.reshape(2, 16, 42)) and torch.equal(doa, want_doa.reshape(2, 16, 126))
     # chunks of one recording and a partial last batch give the same bytes
-    old, T.MEMBER_BUFFER_BYTES = T.MEMBER_BUFFER_BYTES, 1
+    old, pkg().evaluate.MEMBER_BUFFER_BYTES = T.MEMBER_BUFFER_BYTES, 1
     try:
         again = T.predict_recordings(model, xd, seg_len=64, hop=64, window="uniform", batch=8)
     finally:
-        T.MEMBER_BUFFER_BYTES = old
+        pkg().evaluate.MEMBER_BUFFER_BYTES = old
     assert torch.allclose(again[0], sed, atol=1e-5) and torch.allclose(again[1], doa, atol=1e-5)
     with pytest.raises(pkg()._lib.SeldHipError, match="multiple"):
         T.predict_recordings(model, xd, seg_len=64, hop=20)

@@ -87,3 +87,22 @@ def test_new_flags_default_to_off_and_parse_like_the_other_switches():
     assert off.resident_loader is False and off.graph_step is False
     on = T.parse_args(["--TextArgs=none", "--resident_loader=True", "--graph_step=True"])
     assert on.resident_loader is True and on.graph_step is True
+
+
+def test_recorded_step_refuses_an_exchange_it_could_not_replay(monkeypatch):
+    """A sync over two ranks without the front-end cut (built without `model=`, or over a FlatAdam built without `late=`)
+    would be recorded as one graph and replayed with no collective: refused first, before the device is touched.  The
+    same for a sync that states its ranks only through average_scale() (dp.FlatGradSync has no `world`); a sync that states
+    neither is an error, never taken for one rank."""
+    import types
+    T = pkg().train
+    model = torch.nn.Linear(4, 3)
+    opt = T.FlatAdam(model.parameters(), lr=1e-3)
+    monkeypatch.setattr(torch.cuda, "_lazy_init", lambda *a, **k: pytest.fail("the device was touched"))
+    call = lambda sync: T.GraphedTrainStep(model, opt, torch.zeros(2, 4), torch.zeros(2, 3), 3, sync=sync)     # noqa: E731
+    with pytest.raises(ValueError, match="late"):
+        call(types.SimpleNamespace(world=2, cut=None))
+    with pytest.raises(ValueError, match="late"):
+        call(types.SimpleNamespace(cut=None, average_scale=lambda: 0.5, all_reduce=lambda: None))
+    with pytest.raises(AttributeError):
+        call(types.SimpleNamespace(cut=None))
