@@ -57,7 +57,7 @@ struct WgradP {
     int inS, outS;
     long long Ptot;    // N*outS  (reduction length)
     int nsplit;
-    long long split_len;   // positions per split (multiple of 16)
+    long long split_len;   // positions per split (multiple of 32: wgrad_splits; hc_wgrad_row_kernel relies on it)
     const float* x;
     const float* dy;
     WPtrsMut gw;       // component gradients (accumulated into)
@@ -132,6 +132,110 @@ __device__ __forceinline__ int hc_comp(int algebra, int pp, int qq, bool* zero, 
     return c;
 }
 
+// ---- what the three block-matrix weight-gradient kernels (hc_wgrad.hip, hc_wgrad_row.hip) share: origin, column decode,
+// LDS -> MFMA step, Hamilton fold.  Their staging is their own.
+
+// Tile origin and position range of a workgroup.  CHUNK positions per staged step; WHOLE: the range is a whole number of
+// steps (the row kernel: split_len and Ptot are multiples of 32), so the step count needs no round-up.
+struct WgradOrigin {
+    int m0, n0;                // first row (co) and column (kk) of the tile
+    long long pbeg, pend;      // positions [pbeg, pend) of this split
+    int nchunks;
+    bool zero;                 // the tile lies wholly in the dual-quaternion zero block: rows primal (co < Cout/2), columns
+                               // dual (ci >= Cin/2) -- the caller returns
+};
+template <int BM, int BN, int CHUNK, bool WHOLE>
+__device__ __forceinline__ WgradOrigin wgrad_origin(const WgradP& p) {
+    static_assert(CHUNK == 16 || CHUNK == 32, "staged step");
+    WgradOrigin o;
+    int tile_m, tile_n;
+    wgrad_tile(p, &tile_m, &tile_n);
+    o.m0 = tile_m * BM;
+    o.n0 = tile_n * BN;
+    o.zero = p.algebra == 8 && o.m0 + BM <= (p.Cout >> 1) && o.n0 >= (p.Ktot >> 1);
+    o.pbeg = (long long)blockIdx.x * p.split_len;
+    o.pend = o.pbeg + p.split_len;
+    if (o.pend > p.Ptot) o.pend = p.Ptot;
+    o.nchunks = o.pbeg < o.pend ? (int)((o.pend - o.pbeg + (WHOLE ? 0 : CHUNK - 1)) >> (CHUNK == 32 ? 5 : 4)) : 0;
+    return o;
+}
+
+// Column kk = ci*KH*KW + kh*KW + kw of the im2col matrix; taps fixed at compile time, 0 = run-time.
+template <int KH_T, int KW_T>
+__device__ __forceinline__ void wgrad_col(const WgradP& p, int kk, int* ci, int* kh, int* kw) {
+    const int KW = KW_T ? KW_T : p.KW;
+    const int KK = (KH_T ? KH_T : p.KH) * KW;
+    *ci = kk / KK;
+    const int kidx = kk - *ci * KK;
+    *kh = kidx / KW;
+    *kw = kidx - *kh * KW;
+}
+
+// One staged step: 4 * HALVES k-groups of LDS images [k-group][row][4 positions].  Lane (fr, fk) of wave (wr, wc) reads one
+// 16-byte fragment per tile and k-group, which feeds four MFMAs.  LATE_BARRIER: nothing may move across the start of the last
+// k-step, so the LDS stores that follow mix with that k-step only (hc_wgrad_row_kernel).
+template <int RT, int CTL, int HALVES, bool LATE_BARRIER, int AROWS, int BROWS>
+__device__ __forceinline__ void wgrad_mfma_step(const float (&As)[2][4 * HALVES][AROWS][4], const float (&Bs)[2][4 * HALVES][BROWS][4],
+                                                int buf, int wr, int wc, int fr, int fk, floatx4 (&acc)[RT][CTL]) {
+#pragma unroll
+    for (int half = 0; half < HALVES; ++half) {
+        floatx4 av[RT], bv[CTL];
+#pragma unroll
+        for (int i = 0; i < RT; ++i) av[i] = *reinterpret_cast<const floatx4*>(&As[buf][half * 4 + fk][wr * (RT * 16) + i * 16 + fr][0]);
+#pragma unroll
+        for (int j = 0; j < CTL; ++j) bv[j] = *reinterpret_cast<const floatx4*>(&Bs[buf][half * 4 + fk][wc * (CTL * 16) + j * 16 + fr][0]);
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            if (LATE_BARRIER && half == HALVES - 1 && s == 3) __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int i = 0; i < RT; ++i)
+#pragma unroll
+                for (int j = 0; j < CTL; ++j)
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[i][s], bv[j][s], acc[i][j], 0, 0, 0);
+        }
+    }
+}
+
+// D layout: col = fr (B index = column kk), row = fk*4 + r (A index = co).  Fold the tile into the component gradients gw
+// with float atomics: block (pp, qq) -> sign * dw[comp][o][c*KK + kidx].  CK = IA * KH * KW.
+template <int RT, int CTL>
+__device__ __forceinline__ void wgrad_fold(const WgradP& p, const WPtrsMut& gw, const floatx4 (&acc)[RT][CTL], int m0, int n0,
+                                           int CK, int wr, int wc, int fr, int fk) {
+    // read once: the atomics below keep the compiler from carrying a load through `p` across them
+    const int algebra = p.algebra, Cout = p.Cout, Ktot = p.Ktot, OA = p.OA;
+#pragma unroll
+    for (int j = 0; j < CTL; ++j) {
+        const int kk = n0 + wc * (CTL * 16) + j * 16 + fr;
+        if (kk >= Ktot) continue;
+        const int qq = kk / CK;
+        const int ckl = kk - qq * CK;
+#pragma unroll
+        for (int i = 0; i < RT; ++i) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int co = m0 + wr * (RT * 16) + i * 16 + fk * 4 + r;
+                if (co >= Cout) continue;
+                const int pp = co / OA;
+                const int o = co - pp * OA;
+                bool zero, neg;
+                const int comp = hc_comp(algebra, pp, qq, &zero, &neg);
+                if (zero) continue;
+                const float v = acc[i][j][r];
+                atomicAdd(gw.p[comp] + (size_t)o * CK + ckl, neg ? -v : v);
+            }
+        }
+    }
+}
+
+// Taps the weight-gradient kernels are specialised for: (1,1), (1,3), (3,3); anything else runs with run-time taps (0,0).
+// The launches, the label and the row kernel's eligibility all read this.
+inline bool wgrad_taps(const WgradP& p, int* kh, int* kw) {
+    const bool fixed = (p.KH == 1 && (p.KW == 1 || p.KW == 3)) || (p.KH == 3 && p.KW == 3);
+    *kh = fixed ? p.KH : 0;
+    *kw = fixed ? p.KW : 0;
+    return fixed;
+}
+
 inline int hc_validate(const seld_conv_desc* d) {
     if (!d) return SELD_EINVAL;
     if (d->algebra != 1 && d->algebra != 4 && d->algebra != 8) return SELD_EINVAL;
@@ -171,5 +275,18 @@ inline bool hcq_same_geometry(const seld_conv_desc* d) {
     const long long S = (long long)d->N * d->in[0] * d->in[1] * 4;
     return S * d->Cin < 0xFFFFFFF0ll && S * d->Cout < 0xFFFFFFF0ll;
 }
+
+// ---- entry points one hc_*.hip file offers another --------------------------------------------------------------------------
+// hc_wgrad_row.hip: does the row-chunk kernel take this call, and its launch for tile configuration cfg (index into WGRAD_TILES)
+bool hc_wgrad_row_ok(const WgradP& p);
+void hc_wgrad_row_launch(const WgradP& p, int cfg, hipStream_t st);
+// hc_wgrad.hip: the kernel a weight gradient launches, whether a pair launch would run, and the weight gradient reduced over
+// the output extent o
+int hc_wgrad_label(const seld_conv_desc* d, char* buf, int buflen);
+int hc_wgrad_pair_ok(const seld_conv_desc* d);
+int hc_wgrad_out(const seld_conv_desc* d, const int o[2], const float* x, const float* dy, float* const dw[8], void* det_ws,
+                 size_t det_bytes, hipStream_t st);
+// hc_conv_fwd.hip: the forward convolution evaluated on the output extent o
+int hc_conv_fwd_out(const seld_conv_desc* d, const int o[2], const float* x, const float* const w[8], float* y, hipStream_t st);
 
 }  // namespace seld

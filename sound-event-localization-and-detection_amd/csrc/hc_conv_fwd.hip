@@ -724,9 +724,6 @@ int hc_conv_fwd_out(const seld_conv_desc* d, const int o[2], const float* x, con
     p.src = x; p.bias = nullptr; p.dst = y;
     return run_conv(p, st, false);                 // the reduced extent runs on the tiled kernels only
 }
-
-int hc_wgrad_label(const seld_conv_desc* d, char* buf, int buflen);
-int hc_wgrad_pair_ok(const seld_conv_desc* d);
 }
 
 // ---- two convolutions of one geometry in one launch (filter | gate, skip | residual of a residual block) ---------

@@ -402,11 +402,6 @@ static seld_conv_desc tconv_mirror(const seld_conv_desc* d, const int out[2]) {
     return m;
 }
 
-int hc_conv_fwd_out(const seld_conv_desc* d, const int o[2], const float* x, const float* const w[8], float* y,
-                    hipStream_t st);
-int hc_wgrad_out(const seld_conv_desc* d, const int o[2], const float* x, const float* dy, float* const dw[8],
-                 void* det_ws, size_t det_bytes, hipStream_t st);
-
 }  // namespace seld
 
 using namespace seld;

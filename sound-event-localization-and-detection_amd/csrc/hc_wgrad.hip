@@ -8,7 +8,9 @@
 // the tiles of the dual quaternion's structurally-zero quadrant are never computed.
 // The atomic payload is nsplit * 0.75 * Cout * Cin * K floats per call (a few MB: far below the
 // ~1.3 TB/s chip-wide float-atomic rate, guide Guideline 12).
-// Staging follows hc_conv_fwd.hip: wave w stages k-group w (4 consecutive positions) of every row, the
+// Tile origin, column decode, LDS -> MFMA step and fold are hc_common.h's (wgrad_origin, wgrad_col, wgrad_mfma_step,
+// wgrad_fold), shared with hc_wgrad_row.hip; the kernels here differ in their staging.
+// Staging of hc_wgrad_kernel follows hc_conv_fwd.hip: wave w stages k-group w (4 consecutive positions) of every row, the
 // (image, row, column) of that group is tracked incrementally in SGPRs, per-row decodes are hoisted.
 #include "hc_common.h"
 
@@ -27,23 +29,11 @@ __global__ __launch_bounds__(256) void hc_wgrad_kernel(const WgradP p) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wr_ = wave / WCW, wc_ = wave % WCW;
-    int tile_m, tile_n;
-    wgrad_tile(p, &tile_m, &tile_n);
-    const int m0 = tile_m * BM;
-    const int n0 = tile_n * BN;
-    const int split = blockIdx.x;
-    const int KH = KH_T ? KH_T : p.KH;
-    const int KW = KW_T ? KW_T : p.KW;
-    const int KK = KH * KW;
-    const int CK = p.IA * KK;
-
-    // structural zero block of the dual-quaternion matrix: rows primal (co < Cout/2), cols dual (ci >= Cin/2)
-    if (p.algebra == 8 && m0 + BM <= (p.Cout >> 1) && n0 >= (p.Ktot >> 1)) return;
-
-    const long long pbeg = (long long)split * p.split_len;
-    long long pend = pbeg + p.split_len;
-    if (pend > p.Ptot) pend = p.Ptot;
-    const int nchunks = pbeg < pend ? (int)((pend - pbeg + 15) >> 4) : 0;
+    const WgradOrigin og = wgrad_origin<BM, BN, 16, false>(p);
+    if (og.zero) return;
+    const int m0 = og.m0, n0 = og.n0, nchunks = og.nchunks;
+    const long long pbeg = og.pbeg, pend = og.pend;
+    const int CK = p.IA * (KH_T ? KH_T : p.KH) * (KW_T ? KW_T : p.KW);
 
     // hoisted per-lane decodes
     bool a_ok[AR];
@@ -61,10 +51,8 @@ __global__ __launch_bounds__(256) void hc_wgrad_kernel(const WgradP p) {
         const int c = lane + 64 * j;
         const int kk = n0 + c;
         b_ok[j] = c < BN && kk < p.Ktot;
-        const int kkc = b_ok[j] ? kk : 0;
-        const int ci = kkc / KK;
-        const int kidx = kkc - ci * KK;
-        const int kh = kidx / KW, kw = kidx - kh * KW;
+        int ci, kh, kw;
+        wgrad_col<KH_T, KW_T>(p, b_ok[j] ? kk : 0, &ci, &kh, &kw);
         b_coff[j] = ci * p.inS;
         b_dh[j] = kh * p.dh - p.ph;
         b_dw[j] = kw * p.dw - p.pw;
@@ -162,51 +150,11 @@ __global__ __launch_bounds__(256) void hc_wgrad_kernel(const WgradP p) {
     for (int chunk = 0; chunk < nchunks; ++chunk) {
         const int buf = chunk & 1;
         if (chunk + 1 < nchunks) load_chunk(chunk + 1);
-        float av[RT][4], bv[CTL][4];
-#pragma unroll
-        for (int i = 0; i < RT; ++i) {
-            const float4 t = *reinterpret_cast<const float4*>(&As[buf][fk][wr_ * (RT * 16) + i * 16 + fr][0]);
-            av[i][0] = t.x; av[i][1] = t.y; av[i][2] = t.z; av[i][3] = t.w;
-        }
-#pragma unroll
-        for (int j = 0; j < CTL; ++j) {
-            const float4 t = *reinterpret_cast<const float4*>(&Bs[buf][fk][wc_ * (CTL * 16) + j * 16 + fr][0]);
-            bv[j][0] = t.x; bv[j][1] = t.y; bv[j][2] = t.z; bv[j][3] = t.w;
-        }
-#pragma unroll
-        for (int s = 0; s < 4; ++s)
-#pragma unroll
-            for (int i = 0; i < RT; ++i)
-#pragma unroll
-                for (int j = 0; j < CTL; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[i][s], bv[j][s], acc[i][j], 0, 0, 0);
+        wgrad_mfma_step<RT, CTL, 1, false>(As, Bs, buf, wr_, wc_, fr, fk, acc);
         if (chunk + 1 < nchunks) store_chunk(buf ^ 1);
         __syncthreads();
     }
-    // D layout: col = lane&15 (B index = column kk), row = (lane>>4)*4 + r (A index = co).
-    // Fold into the component gradients: block (p, q) -> sign * dw[comp][o][c*KK + kidx].
-#pragma unroll
-    for (int j = 0; j < CTL; ++j) {
-        const int kk = n0 + wc_ * (CTL * 16) + j * 16 + fr;
-        if (kk >= p.Ktot) continue;
-        const int qq = kk / CK;
-        const int ckl = kk - qq * CK;
-#pragma unroll
-        for (int i = 0; i < RT; ++i) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int co = m0 + wr_ * (RT * 16) + i * 16 + fk * 4 + r;
-                if (co >= p.Cout) continue;
-                const int pp = co / p.OA;
-                const int o = co - pp * p.OA;
-                bool zero, neg;
-                const int comp = hc_comp(p.algebra, pp, qq, &zero, &neg);
-                if (zero) continue;
-                const float v = acc[i][j][r];
-                atomicAdd(p.gw.p[comp] + (size_t)o * CK + ckl, neg ? -v : v);
-            }
-        }
-    }
+    wgrad_fold<RT, CTL>(p, p.gw, acc, m0, n0, CK, wr_, wc_, fr, fk);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -230,24 +178,13 @@ __global__ __launch_bounds__(256) void hc_wgrad32_kernel(const WgradP p) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wr_ = wave / WCW, wc_ = wave % WCW;
-    int tile_m, tile_n;
-    wgrad_tile(p, &tile_m, &tile_n);
-    const int m0 = tile_m * BM;
-    const int n0 = tile_n * BN;
-    const int split = blockIdx.x;
-    const int KH = KH_T ? KH_T : p.KH;
-    const int KW = KW_T ? KW_T : p.KW;
-    const int KK = KH * KW;
-    const int CK = p.IA * KK;
+    const WgradOrigin og = wgrad_origin<BM, BN, 32, false>(p);
+    if (og.zero) return;
+    const int m0 = og.m0, n0 = og.n0, nchunks = og.nchunks;
+    const long long pbeg = og.pbeg, pend = og.pend;
+    const int CK = p.IA * (KH_T ? KH_T : p.KH) * (KW_T ? KW_T : p.KW);
 
-    if (p.algebra == 8 && m0 + BM <= (p.Cout >> 1) && n0 >= (p.Ktot >> 1)) return;   // zero quadrant
-
-    const long long pbeg = (long long)split * p.split_len;
-    long long pend = pbeg + p.split_len;
-    if (pend > p.Ptot) pend = p.Ptot;
-    const int nchunks = pbeg < pend ? (int)((pend - pbeg + 31) >> 5) : 0;
-
-    const int g = tid & 7;                   // 4-position group inside the 32-position step
+    const int g = tid & 7;                  // 4-position group inside the 32-position step
     const int rsub = tid >> 3;               // 0..31
 
     bool a_ok[AR];
@@ -265,10 +202,8 @@ __global__ __launch_bounds__(256) void hc_wgrad32_kernel(const WgradP p) {
         const int c = rsub + 32 * j;
         const int kk = n0 + c;
         b_ok[j] = c < BN && kk < p.Ktot;
-        const int kkc = b_ok[j] ? kk : 0;
-        const int ci = kkc / KK;
-        const int kidx = kkc - ci * KK;
-        const int kh = kidx / KW, kw = kidx - kh * KW;
+        int ci, kh, kw;
+        wgrad_col<KH_T, KW_T>(p, b_ok[j] ? kk : 0, &ci, &kh, &kw);
         b_coff[j] = ci * p.inS;
         b_dh[j] = kh * p.dh - p.ph;
         b_dw[j] = kw * p.dw - p.pw;
@@ -355,52 +290,11 @@ __global__ __launch_bounds__(256) void hc_wgrad32_kernel(const WgradP p) {
     for (int chunk = 0; chunk < nchunks; ++chunk) {
         const int buf = chunk & 1;
         if (chunk + 1 < nchunks) load_chunk(chunk + 1);
-#pragma unroll
-        for (int half = 0; half < 2; ++half) {
-            float av[RT][4], bv[CTL][4];
-#pragma unroll
-            for (int i = 0; i < RT; ++i) {
-                const float4 t = *reinterpret_cast<const float4*>(&As[buf][half * 4 + fk][wr_ * (RT * 16) + i * 16 + fr][0]);
-                av[i][0] = t.x; av[i][1] = t.y; av[i][2] = t.z; av[i][3] = t.w;
-            }
-#pragma unroll
-            for (int j = 0; j < CTL; ++j) {
-                const float4 t = *reinterpret_cast<const float4*>(&Bs[buf][half * 4 + fk][wc_ * (CTL * 16) + j * 16 + fr][0]);
-                bv[j][0] = t.x; bv[j][1] = t.y; bv[j][2] = t.z; bv[j][3] = t.w;
-            }
-#pragma unroll
-            for (int s = 0; s < 4; ++s)
-#pragma unroll
-                for (int i = 0; i < RT; ++i)
-#pragma unroll
-                    for (int j = 0; j < CTL; ++j)
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[i][s], bv[j][s], acc[i][j], 0, 0, 0);
-        }
+        wgrad_mfma_step<RT, CTL, 2, false>(As, Bs, buf, wr_, wc_, fr, fk, acc);
         if (chunk + 1 < nchunks) store_chunk(buf ^ 1);
         __syncthreads();
     }
-#pragma unroll
-    for (int j = 0; j < CTL; ++j) {
-        const int kk = n0 + wc_ * (CTL * 16) + j * 16 + fr;
-        if (kk >= p.Ktot) continue;
-        const int qq = kk / CK;
-        const int ckl = kk - qq * CK;
-#pragma unroll
-        for (int i = 0; i < RT; ++i) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int co = m0 + wr_ * (RT * 16) + i * 16 + fk * 4 + r;
-                if (co >= p.Cout) continue;
-                const int pp = co / p.OA;
-                const int o = co - pp * p.OA;
-                bool zero, neg;
-                const int comp = hc_comp(p.algebra, pp, qq, &zero, &neg);
-                if (zero) continue;
-                const float v = acc[i][j][r];
-                atomicAdd(p.gw.p[comp] + (size_t)o * CK + ckl, neg ? -v : v);
-            }
-        }
-    }
+    wgrad_fold<RT, CTL>(p, p.gw, acc, m0, n0, CK, wr_, wc_, fr, fk);
 }
 
 // per-channel sum over (N, S): dbias  (accumulates)
@@ -488,9 +382,6 @@ static int wgrad_cfg(const seld_conv_desc* d) {
     return 0;
 }
 
-bool hc_wgrad_row_ok(const WgradP& p);
-void hc_wgrad_row_launch(const WgradP& p, int cfg, hipStream_t st);
-
 // hc_wgrad32_kernel (32 positions of one output row per step) instead of hc_wgrad_kernel
 static bool wgrad_fast_ok(const WgradP& p) { return (p.outW % 4 == 0) && p.outW >= 32 && p.sw == 1; }
 
@@ -521,18 +412,20 @@ static void launch_wgrad(const WgradP& p, hipStream_t st) {
         if (fast) hipLaunchKernelGGL((hc_wgrad32_kernel<WRW, RT, CTL, KH_, KW_>), grid, dim3(256), 0, st, p);      \
         else hipLaunchKernelGGL((hc_wgrad_kernel<WRW, RT, CTL, KH_, KW_>), grid, dim3(256), 0, st, p);            \
     } while (0)
-    if (p.KH == 1 && p.KW == 1) SELD_WG(1, 1);
-    else if (p.KH == 1 && p.KW == 3) SELD_WG(1, 3);
-    else if (p.KH == 3 && p.KW == 3) SELD_WG(3, 3);
+    int kh, kw;
+    wgrad_taps(p, &kh, &kw);
+    if (kh == 1 && kw == 1) SELD_WG(1, 1);
+    else if (kh == 1 && kw == 3) SELD_WG(1, 3);
+    else if (kh == 3 && kw == 3) SELD_WG(3, 3);
     else SELD_WG(0, 0);
 #undef SELD_WG
 }
 
 // One weight gradient, or (dy2 != nullptr) the two of a pair that shares x and the geometry.  o_over: reduce over the
 // first o_over[0] x o_over[1] output positions only (dy has that extent; the transposed convolution's weight gradient).
-static int wgrad_run2(const seld_conv_desc* d, const float* x, const float* dy, float* const dw[8], float* dbias,
-                      const float* dy2, float* const dw2[8], float* dbias2, int accumulate, hipStream_t st,
-                      const int* o_over = nullptr) {
+static int wgrad_run(const seld_conv_desc* d, const float* x, const float* dy, float* const dw[8], float* dbias,
+                     const float* dy2, float* const dw2[8], float* dbias2, int accumulate, hipStream_t st,
+                     const int* o_over = nullptr) {
     int rc = hc_validate(d);
     if (rc) return rc;
     int o[2];
@@ -582,11 +475,6 @@ static int wgrad_run2(const seld_conv_desc* d, const float* x, const float* dy, 
     return rc;
 }
 
-static int wgrad_run(const seld_conv_desc* d, const float* x, const float* dy, float* const dw[8], float* dbias,
-                     int accumulate, hipStream_t st) {
-    return wgrad_run2(d, x, dy, dw, dbias, nullptr, nullptr, nullptr, accumulate, st);
-}
-
 // Would a pair launch run (row kernel eligibility)?
 int hc_wgrad_pair_ok(const seld_conv_desc* d) {
     int o[2];
@@ -601,9 +489,9 @@ int hc_wgrad_label(const seld_conv_desc* d, char* buf, int buflen) {
     hc_out_shape(d, o);
     WgradP p{};
     const WgradTile t = WGRAD_TILES[fill_wgrad(p, d, o, 1)];
-    const bool taps = (p.KH == 1 && p.KW == 1) || (p.KH == 1 && p.KW == 3) || (p.KH == 3 && p.KW == 3);
-    const int kh = taps ? p.KH : 0, kw = taps ? p.KW : 0;
-    if (hc_wgrad_row_ok(p))     // last argument: fused BN/pool backward
+    int kh, kw;
+    wgrad_taps(p, &kh, &kw);
+    if (hc_wgrad_row_ok(p))    // last argument: fused BN/pool backward
         snprintf(buf, buflen, "hc_wgrad_row_kernel<%d, %d, %d, %d, %d, 0>", t.wrw, t.rt, t.ctl, kh, kw);
     else
         snprintf(buf, buflen, "%s<%d, %d, %d, %d, %d>", wgrad_fast_ok(p) ? "hc_wgrad32_kernel" : "hc_wgrad_kernel", t.wrw,
@@ -617,18 +505,7 @@ using namespace seld;
 // dw[c] += weight gradient of a convolution that is followed by BatchNorm2d -> ReLU -> MaxPool2d(ph, 1) and whose
 // input needs no gradient: the gradient w.r.t. the conv output is formed from y, the pooled-size tensors and `coef`
 // (seld_bn_relu_pool_bwd_coef) while the operand is staged.  SELD_EUNSUPPORTED when the shape does not qualify.
-extern "C" int seld_hc_conv_bwd_weight_bnpool_drop_acc(const seld_conv_desc* d, const float* x, const float* y,
-                                                       const float* pooled, const float* dpooled, const uint8_t* idx,
-                                                       int32_t ph, const float* coef, float* const dw[8], float drop_p,
-                                                       uint64_t seed, uint64_t offset, const uint64_t* state, void* stream);
-
-extern "C" int seld_hc_conv_bwd_weight_bnpool_acc(const seld_conv_desc* d, const float* x, const float* y,
-                                                  const float* pooled, const float* dpooled, const uint8_t* idx,
-                                                  int32_t ph, const float* coef, float* const dw[8], void* stream) {
-    return seld_hc_conv_bwd_weight_bnpool_drop_acc(d, x, y, pooled, dpooled, idx, ph, coef, dw, 0.f, 0, 0, nullptr, stream);
-}
-
-// ... with dpooled = the gradient BEHIND the stage's Dropout(drop_p): its mask is replayed while dpooled is loaded
+// dpooled is the gradient BEHIND the stage's Dropout(drop_p): its mask is replayed while dpooled is loaded.
 extern "C" int seld_hc_conv_bwd_weight_bnpool_drop_acc(const seld_conv_desc* d, const float* x, const float* y,
                                                        const float* pooled, const float* dpooled, const uint8_t* idx,
                                                        int32_t ph, const float* coef, float* const dw[8], float drop_p,
@@ -652,13 +529,20 @@ extern "C" int seld_hc_conv_bwd_weight_bnpool_drop_acc(const seld_conv_desc* d, 
     return check_launch();
 }
 
+// ... without a Dropout behind the stage
+extern "C" int seld_hc_conv_bwd_weight_bnpool_acc(const seld_conv_desc* d, const float* x, const float* y,
+                                                  const float* pooled, const float* dpooled, const uint8_t* idx,
+                                                  int32_t ph, const float* coef, float* const dw[8], void* stream) {
+    return seld_hc_conv_bwd_weight_bnpool_drop_acc(d, x, y, pooled, dpooled, idx, ph, coef, dw, 0.f, 0, 0, nullptr, stream);
+}
+
 // dwA[c] += wgrad(x, dyA), dwB[c] += wgrad(x, dyB) (+ bias gradients): one launch for two convolutions that read
 // the same input with the same geometry.  SELD_EUNSUPPORTED when the shape does not qualify: call the single form twice.
 extern "C" int seld_hc_conv_pair_bwd_weight_acc(const seld_conv_desc* d, const float* x, const float* dyA,
                                                 const float* dyB, float* const dwA[8], float* const dwB[8],
                                                 float* dbiasA, float* dbiasB, void* stream) {
     if (!dyB || !dwB) return SELD_EINVAL;
-    return wgrad_run2(d, x, dyA, dwA, dbiasA, dyB, dwB, dbiasB, 1, (hipStream_t)stream);
+    return wgrad_run(d, x, dyA, dwA, dbiasA, dyB, dwB, dbiasB, 1, (hipStream_t)stream);
 }
 
 extern "C" size_t seld_hc_conv_bwd_weight_workspace(const seld_conv_desc* d) {
@@ -670,7 +554,7 @@ extern "C" int seld_hc_conv_bwd_weight(const seld_conv_desc* d, const float* x, 
                                        float* const dw[8], float* dbias, void* workspace,
                                        size_t workspace_bytes, void* stream) {
     (void)workspace; (void)workspace_bytes;
-    return wgrad_run(d, x, dy, dw, dbias, 0, (hipStream_t)stream);
+    return wgrad_run(d, x, dy, dw, dbias, nullptr, nullptr, nullptr, 0, (hipStream_t)stream);
 }
 
 // Hamilton fold of a real (Cout, Cin, K) gradient into the component gradients: element (comp, o, i, k) += the signed sum of
@@ -709,14 +593,6 @@ extern "C" size_t seld_hc_conv_bwd_weight_det_workspace(const seld_conv_desc* d)
     return (size_t)d->Cout * d->Cin * d->k[0] * d->k[1] * sizeof(float);
 }
 static int wgrad_det(const seld_conv_desc* d, const float* x, const float* dy, float* const dw[8], float* dbias,
-                     void* workspace, size_t workspace_bytes, hipStream_t st, const int* o_over);
-
-extern "C" int seld_hc_conv_bwd_weight_det(const seld_conv_desc* d, const float* x, const float* dy, float* const dw[8],
-                                           float* dbias, void* workspace, size_t workspace_bytes, void* stream) {
-    return wgrad_det(d, x, dy, dw, dbias, workspace, workspace_bytes, (hipStream_t)stream, nullptr);
-}
-
-static int wgrad_det(const seld_conv_desc* d, const float* x, const float* dy, float* const dw[8], float* dbias,
                      void* workspace, size_t workspace_bytes, hipStream_t st, const int* o_over) {
     int rc = hc_validate(d);
     if (rc) return rc;
@@ -726,7 +602,7 @@ static int wgrad_det(const seld_conv_desc* d, const float* x, const float* dy, f
     seld_conv_desc real = *d;
     real.algebra = 1;
     float* full[8] = {(float*)workspace, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    rc = wgrad_run2(&real, x, dy, full, nullptr, nullptr, nullptr, nullptr, 0, st, o_over);           // zero-fills `full`, then one contribution per element
+    rc = wgrad_run(&real, x, dy, full, nullptr, nullptr, nullptr, nullptr, 0, st, o_over);           // zero-fills `full`, then one contribution per element
     if (rc) return rc;
     DetFoldP f{};
     f.full = (const float*)workspace; f.A = d->algebra; f.OA = d->Cout / d->algebra; f.IA = d->Cin / d->algebra;
@@ -749,10 +625,15 @@ static int wgrad_det(const seld_conv_desc* d, const float* x, const float* dy, f
     return rc;
 }
 
-// dw[c] += ..., dbias += ...  (gradient accumulation straight into the optimiser's flat gradient buffer)
+extern "C" int seld_hc_conv_bwd_weight_det(const seld_conv_desc* d, const float* x, const float* dy, float* const dw[8],
+                                           float* dbias, void* workspace, size_t workspace_bytes, void* stream) {
+    return wgrad_det(d, x, dy, dw, dbias, workspace, workspace_bytes, (hipStream_t)stream, nullptr);
+}
+
+// dw[c] += ..., dbias += ... (gradient accumulation straight into the optimiser's flat gradient buffer)
 extern "C" int seld_hc_conv_bwd_weight_acc(const seld_conv_desc* d, const float* x, const float* dy,
                                            float* const dw[8], float* dbias, void* stream) {
-    return wgrad_run(d, x, dy, dw, dbias, 1, (hipStream_t)stream);
+    return wgrad_run(d, x, dy, dw, dbias, nullptr, nullptr, nullptr, 1, (hipStream_t)stream);
 }
 
 namespace seld {
@@ -762,6 +643,6 @@ namespace seld {
 int hc_wgrad_out(const seld_conv_desc* d, const int o[2], const float* x, const float* dy, float* const dw[8],
                  void* det_ws, size_t det_bytes, hipStream_t st) {
     if (env().deterministic) return wgrad_det(d, x, dy, dw, nullptr, det_ws, det_bytes, st, o);
-    return wgrad_run2(d, x, dy, dw, nullptr, nullptr, nullptr, nullptr, 1, st, o);
+    return wgrad_run(d, x, dy, dw, nullptr, nullptr, nullptr, nullptr, 1, st, o);
 }
 }  // namespace seld

@@ -17,8 +17,9 @@
 //     element with the halo test;
 //   * rows / columns outside the tensor carry an out-of-range offset that the descriptor zero-fills.
 //
-// Tiling, LDS images ([k-group][row][4 positions], one ds_read_b128 feeds four MFMAs), the dual-quaternion
-// zero-quadrant exit and the atomic fold are those of hc_wgrad32_kernel.
+// Tile origin with the dual-quaternion zero-quadrant test, column decode, the LDS -> MFMA step ([k-group][row][4 positions]
+// images, one ds_read_b128 feeds four MFMAs) and the atomic fold are shared with hc_wgrad.hip (hc_common.h: wgrad_origin,
+// wgrad_col, wgrad_mfma_step, wgrad_fold); this file is the staging.
 #include <type_traits>
 #include "hc_common.h"
 
@@ -44,20 +45,13 @@ __global__ __launch_bounds__(256) void hc_wgrad_row_kernel(const WgradP p) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wr_ = wave / WCW, wc_ = wave % WCW;
-    int tile_m, tile_n;
-    wgrad_tile(p, &tile_m, &tile_n);
-    const int m0 = tile_m * BM;
-    const int n0 = tile_n * BN;
+    const WgradOrigin og = wgrad_origin<BM, BN, 32, true>(p);      // split_len and Ptot are multiples of 32
+    if (og.zero) return;
+    const int m0 = og.m0, n0 = og.n0, nchunks = og.nchunks;
+    const long long pbeg = og.pbeg;
     const int CK = p.IA * KK;
     const float* const dyz = blockIdx.y ? p.dy2 : p.dy;            // pair launch: which of the two gradients
     const WPtrsMut& gwz = blockIdx.y ? p.gw2 : p.gw;
-
-    if (p.algebra == 8 && m0 + BM <= (p.Cout >> 1) && n0 >= (p.Ktot >> 1)) return;   // zero quadrant
-
-    const long long pbeg = (long long)blockIdx.x * p.split_len;          // multiple of 32
-    long long pend = pbeg + p.split_len;
-    if (pend > p.Ptot) pend = p.Ptot;                                    // Ptot is a multiple of 32 too
-    const int nchunks = pbeg < pend ? (int)((pend - pbeg) >> 5) : 0;
 
     const int g = tid & 7;                   // 4-position group inside the 32-position step
     const int rsub = tid >> 3;               // 0..31
@@ -91,10 +85,8 @@ __global__ __launch_bounds__(256) void hc_wgrad_row_kernel(const WgradP p) {
         const int c = rsub + 32 * j;
         const int kk = n0 + c;
         const bool ok = c < BN && kk < p.Ktot;
-        const int kkc = ok ? kk : 0;
-        const int ci = kkc / KK;
-        const int tap = kkc - ci * KK;
-        const int kh = tap / KW_T, kw = tap - kh * KW_T;
+        int ci, kh, kw;
+        wgrad_col<KH_T, KW_T>(p, ok ? kk : 0, &ci, &kh, &kw);
         b_voff[j] = ok ? (unsigned)((ci * p.inS + kh * p.dh * p.inW + kw * p.dw + 4 * g) * 4) : OOB;
         b_row[j] = kh * p.dh - p.ph;
         b_col[j] = kw * p.dw - p.pw + 4 * g;
@@ -254,25 +246,6 @@ __global__ __launch_bounds__(256) void hc_wgrad_row_kernel(const WgradP p) {
     const int fr = lane & 15, fk = lane >> 4;
     using S0 = std::integral_constant<int, 0>;
     using S1 = std::integral_constant<int, NSET - 1>;
-    auto mfma_step = [&](int buf) __attribute__((always_inline)) {
-#pragma unroll
-        for (int half = 0; half < 2; ++half) {
-            floatx4 av[RT], bv[CTL];
-#pragma unroll
-            for (int i = 0; i < RT; ++i) av[i] = *reinterpret_cast<const floatx4*>(&As[buf][half * 4 + fk][wr_ * (RT * 16) + i * 16 + fr][0]);
-#pragma unroll
-            for (int j = 0; j < CTL; ++j) bv[j] = *reinterpret_cast<const floatx4*>(&Bs[buf][half * 4 + fk][wc_ * (CTL * 16) + j * 16 + fr][0]);
-#pragma unroll
-            for (int s = 0; s < 4; ++s) {
-                if (half == 1 && s == 3) __builtin_amdgcn_sched_barrier(0);    // stores may mix with the last k-step only
-#pragma unroll
-                for (int i = 0; i < RT; ++i)
-#pragma unroll
-                    for (int j = 0; j < CTL; ++j)
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[i][s], bv[j][s], acc[i][j], 0, 0, 0);
-            }
-        }
-    };
     if constexpr (DEEP) {
         // step c multiplies LDS[c & 1]; register set (c & 1) holds step c + 1 (stored to LDS after the MFMAs); the loads
         // issued in step c are those of step c + 2, into the other set
@@ -283,7 +256,7 @@ __global__ __launch_bounds__(256) void hc_wgrad_row_kernel(const WgradP p) {
             const int buf = chunk & 1;
             if (chunk + 2 < nchunks) load_chunk(chunk + 3 < nchunks, oth);
             __builtin_amdgcn_sched_barrier(0);
-            mfma_step(buf);
+            wgrad_mfma_step<RT, CTL, 2, true>(As, Bs, buf, wr_, wc_, fr, fk, acc);    // stores may mix with the last k-step only
             if (chunk + 1 < nchunks) store_chunk(buf ^ 1, cur);
             __syncthreads();
         };
@@ -300,41 +273,19 @@ __global__ __launch_bounds__(256) void hc_wgrad_row_kernel(const WgradP p) {
             // The loads must stay at the top and the LDS stores at the bottom of the step: left alone, the scheduler
             // hoists the stores (and their vmcnt wait) to the middle, which leaves the loads 48 MFMAs to land.
             __builtin_amdgcn_sched_barrier(0);
-            mfma_step(buf);
+            wgrad_mfma_step<RT, CTL, 2, true>(As, Bs, buf, wr_, wc_, fr, fk, acc);    // stores may mix with the last k-step only
             __builtin_amdgcn_sched_barrier(0);       // stores after the MFMAs: mixed in, the 128 x 128 fused form needs > 256 registers
             store_chunk(buf ^ 1, S0{});
             __syncthreads();
         }
     }
 
-    // ---- fold the tile into the component gradients ------------------------------------------------------------
-#pragma unroll
-    for (int j = 0; j < CTL; ++j) {
-        const int kk = n0 + wc_ * (CTL * 16) + j * 16 + fr;
-        if (kk >= p.Ktot) continue;
-        const int qq = kk / CK;
-        const int ckl = kk - qq * CK;
-#pragma unroll
-        for (int i = 0; i < RT; ++i) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int co = m0 + wr_ * (RT * 16) + i * 16 + fk * 4 + r;
-                if (co >= p.Cout) continue;
-                const int pp = co / p.OA;
-                const int o = co - pp * p.OA;
-                bool zero, neg;
-                const int comp = hc_comp(p.algebra, pp, qq, &zero, &neg);
-                if (zero) continue;
-                const float v = acc[i][j][r];
-                atomicAdd(gwz.p[comp] + (size_t)o * CK + ckl, neg ? -v : v);
-            }
-        }
-    }
+    wgrad_fold<RT, CTL>(p, gwz, acc, m0, n0, CK, wr_, wc_, fr, fk);
 }
 
 bool hc_wgrad_row_ok(const WgradP& p) {
-    const bool taps = (p.KH == 1 && p.KW == 1) || (p.KH == 1 && p.KW == 3) || (p.KH == 3 && p.KW == 3);
-    return taps && p.sw == 1 && (p.outW % 32 == 0) && (p.split_len % 32 == 0) &&
+    int kh, kw;
+    return wgrad_taps(p, &kh, &kw) && p.sw == 1 && (p.outW % 32 == 0) && (p.split_len % 32 == 0) &&
            (long long)p.Cout * p.outS < (1LL << 29) && (long long)p.Cin * p.inS < (1LL << 29);
 }
 
@@ -342,9 +293,11 @@ template <int WRW, int RT, int CTL>
 static void launch_row(const WgradP& p, hipStream_t st) {
     constexpr int BM = WRW * RT * 16, BN = (4 / WRW) * CTL * 16;
     dim3 grid(p.nsplit, p.nslots > 1 ? 2 : 1, p.mz * p.nact + ((p.Cout + BM - 1) / BM - p.mz) * p.nt);
+    int kh, kw;
+    wgrad_taps(p, &kh, &kw);                 // fixed taps: hc_wgrad_row_ok
     if (p.coef) hipLaunchKernelGGL((hc_wgrad_row_kernel<WRW, RT, CTL, 3, 3, 1>), grid, dim3(256), 0, st, p);   // fused BN/pool backward
-    else if (p.KH == 3) hipLaunchKernelGGL((hc_wgrad_row_kernel<WRW, RT, CTL, 3, 3, 0>), grid, dim3(256), 0, st, p);
-    else if (p.KW == 3) hipLaunchKernelGGL((hc_wgrad_row_kernel<WRW, RT, CTL, 1, 3, 0>), grid, dim3(256), 0, st, p);
+    else if (kh == 3 && kw == 3) hipLaunchKernelGGL((hc_wgrad_row_kernel<WRW, RT, CTL, 3, 3, 0>), grid, dim3(256), 0, st, p);
+    else if (kh == 1 && kw == 3) hipLaunchKernelGGL((hc_wgrad_row_kernel<WRW, RT, CTL, 1, 3, 0>), grid, dim3(256), 0, st, p);
     else hipLaunchKernelGGL((hc_wgrad_row_kernel<WRW, RT, CTL, 1, 1, 0>), grid, dim3(256), 0, st, p);
 }
 

@@ -15,7 +15,9 @@ asserts the labels the library reports, so a case that drifted to another kernel
   C  the pair launches against the oracle and against two single launches
   D  hyper_conv and hyper_conv_transpose under autograd
   E  the case list once more with randn inputs at test_gpu_conv.py's 1e-4 of max|ref| (integers are exact in any
-     reduced-precision format too: exactness alone would not notice a loss of precision); prints the worst ratio"""
+     reduced-precision format too: exactness alone would not notice a loss of precision); prints the worst ratio
+  F  the fused BatchNorm/ReLU/MaxPool form of the row kernel (seld_hc_conv_bwd_weight_bnpool_drop_acc) against the plain
+     launch fed the gradient it forms, and both against the oracle"""
 import ctypes
 
 import pytest
@@ -375,3 +377,56 @@ def test_plain_launches_rounding(case, seld_env):
     if 1 in case["pair"]:
         _check(f"{name} data gradient of a pair",
                H.conv_pair_bwd_data(d, t["dy"], t["dyB"], t["wA"], t["wB"], tuple(case["x"])), r["dx_pair"])
+
+
+# ---- F ---------------------------------------------------------------------------------------------------------------------
+FUSED_CASE = C._c("fused_q_3x3_c4_o8_4x32", "conv", 4, (1, 4, 4, 32), 8, (3, 3), (1, 1),
+                  labels={2: "hc_wgrad_row_kernel<2, 2, 2, 3, 3, 0>"},
+                  why="hc_wgrad_row_kernel<2, 2, 2, 3, 3, 1>: the gradient formed while the operand is staged")
+FUSED_POOL = 2
+
+
+def test_fused_bnpool_weight_gradient_exact(seld_env):
+    """hc_wgrad_row_kernel<..., FUSED = 1> forms dy = y*c1 + (pooled > 0 and idx == row ? dpooled*a : 0) + c0 while it
+    stages.  With y, dpooled, c1 | a | c0 and x integers in [-2, 2], |dy| <= 2*2 + 2*2 + 2 = 10 and a Hamilton block's sum
+    over the 128 positions stays below 10 * 2 * 128 < 2^12, a component's over its 4 blocks plus the slot's fill below 2^24
+    in quarters: every operation is exact in any order.  So the fused entry, the plain entry fed the host's float64 dy, and
+    the oracle's dw hold the same bits."""
+    case, ph = FUSED_CASE, FUSED_POOL
+    P, H, L = _enter(case, seld_env)
+    name, lib, st = case["name"], L.lib(), L.current_stream()
+    d = X.desc(H, case)
+    N, Co, Ho, Wo = X.y_shape(case)
+    gen = torch.Generator().manual_seed(X.W._seed(case, None))
+    draw = lambda s: torch.randint(-2, 3, s, generator=gen).float()
+    x, y, dpooled, coef = draw(tuple(case["x"])), draw((N, Co, Ho, Wo)), draw((N, Co, Ho // ph, Wo)), draw((3, Co))
+    win = y.view(N, Co, Ho // ph, ph, Wo)
+    pooled, idx = win.max(dim=3)                                       # window max and its row
+    c1, a, c0 = (coef[i].double().view(1, Co, 1, 1, 1) for i in range(3))
+    row = torch.arange(ph).view(1, 1, 1, ph, 1)
+    hit = (pooled.unsqueeze(3) > 0) & (idx.unsqueeze(3) == row)
+    dy64 = (win.double() * c1 + torch.where(hit, dpooled.double().unsqueeze(3) * a, torch.zeros((), dtype=torch.float64))
+            + c0).reshape(N, Co, Ho, Wo)
+    assert bool(hit.any()) and not bool(hit.any(dim=3).all()), "both branches of the arg-max term"
+    # the bound, as assert_exactness_bound states it
+    assert float(dy64.abs().max()) <= 10 and float(x.abs().max()) <= 2
+    block = 10 * 2 * X.positions(case)
+    assert block < 2 ** 12 and 4 * (X.blocks_per_component(case["algebra"]) * block + 1) < X.EXACT_LIMIT
+    r = X.oracle(case, {"x": x, "dy": dy64, "wA": [torch.zeros(X.weight_shape(case)) for _ in range(case["algebra"])]})
+    assert all(bool((w == w.round()).all()) for w in r["dwA"])
+
+    out, band = Outputs(case), X.guard_band(case)
+    g = {n: X.guarded(v.to(DEV), band)[0] for n, v in (("x", x), ("y", y), ("pooled", pooled), ("dpooled", dpooled),
+                                                        ("dy", dy64.float()))}
+    idx8, coef_d = idx.to(torch.uint8).to(DEV), coef.to(DEV).contiguous()
+    fused, plain = out.slots(case, X.FILL_STEP), out.slots(case, X.FILL_STEP)
+    L.check(lib.seld_hc_conv_bwd_weight_bnpool_drop_acc(ctypes.byref(d), L.ptr(g["x"]), L.ptr(g["y"]), L.ptr(g["pooled"]),
+                                                        L.ptr(g["dpooled"]), L.ptr(idx8), ph, L.ptr(coef_d),
+                                                        L.ptr_array8(fused), 0.0, 0, 0, None, st),
+            "seld_hc_conv_bwd_weight_bnpool_drop_acc")
+    _wgrad_acc(L, d, g["x"], g["dy"], plain, None)
+    torch.cuda.synchronize()
+    X.assert_slots_exact(f"{name} fused weight gradient", fused, r["dwA"], X.FILL_STEP)
+    X.assert_slots_exact(f"{name} plain weight gradient of the host's dy ({case['labels'][2]})", plain, r["dwA"], X.FILL_STEP)
+    assert all(torch.equal(f, p) for f, p in zip(fused, plain)), f"{name}: fused against plain, identical bits"
+    out.check(name)
