@@ -473,7 +473,7 @@ int seld_gate_bwd_apply(const float* dy, const float* yf, const float* yg, int32
                         const float* mean_g, const float* invstd_g, const float* gamma_g, const float* beta_g,
                         const float* mask, const float* red, int32_t train, float* dyf, float* dyg, void* stream);
 
-/* First stage with the pooling decision inside the convolution (csrc/hcq_conv.hip hcq_first_pool_kernel): for
+/* First stage with the pooling decision inside the convolution (csrc/hcq_first.hip hcq_first_pool_kernel): for
  * conv -> BatchNorm2d -> ReLU -> MaxPool2d(8, 1) on the network input (model.py:273-281) the sign of gamma says whether a
  * window's maximum after BatchNorm + ReLU sits at the largest or the smallest conv output, so the convolution writes y,
  * the batch statistics and, per window, that raw value and its row; seld_bn_pool_finish applies relu(a v + b) on the

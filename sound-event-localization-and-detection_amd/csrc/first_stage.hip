@@ -13,7 +13,7 @@
 //     15 tiles of 16 x 16 per 4 positions), fs_gram_fold_kernel adds the workgroups' partials in double precision in a fixed
 //     order, fs_bn_from_gram_kernel evaluates the two forms above in double and finishes mean / invstd / running
 //     statistics exactly as seld_bn_finalize_ex does.
-//   * The pooling convolution (csrc/hcq_conv.hip, hcq_first_pool_kernel<.., FIN>) then runs with y and its statistics
+//   * The pooling convolution (csrc/hcq_first.hip, hcq_first_pool_kernel<.., FIN>) then runs with y and its statistics
 //     switched off and finishes the stage in its epilogue: relu(a v + b) and the Dropout on the window value -- the stage's
 //     output and the window row are all it writes (pooled size; the raw value only for channels with gamma == 0).
 //   * Backward, the gradient w.r.t. y is dy = c1 y + a dz + c0 per channel (BatchNorm backward; dz = the pooled gradient at

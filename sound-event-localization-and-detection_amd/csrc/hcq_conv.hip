@@ -1,6 +1,12 @@
 // Quaternion / dual-quaternion convolution with the 8-multiplication Hamilton product (gfx950), forward and data
 // gradient of the 1-D layers (1x3 dilated, 1x1) and the 3x3 layers.
 //
+// In this file: hcq_conv_kernel; the kernels that pack the weight forms (hcq_pack_kernel for one layer, hcq_pack_flat_kernel
+// for every registered layer in one launch); hcq_plan, which decides kernel, tile program, ring, grid and LDS for a
+// (descriptor, mode, pair count); the seld_hcq_* entry points.  The row-walking kernels of the first layers and the two
+// pooling entry points are in hcq_first.hip; launch arguments, instantiation table, dispatch macros and the device
+// pieces that more than one kernel uses in hcq_conv.h.
+//
 // A Hamilton product w (x) x costs 16 real sub-products when it is evaluated as the 4 x 4 block matrix the reference
 // assembles (quaternion_ops.py:131-135).  It is a bilinear map of rank 8: eight products P_m = F_m(a) G_m(b) of sums of
 // two components, recombined into the four components of c (the forms, the recombination and the proof that they are
@@ -37,10 +43,7 @@
 //   TCN 1x3 halo 16, forward            global loads (GF): 49 152 B of input leave no room for a ring at 3 per CU
 //   TCN 1x1 pair   <1,1,16,1,2,2,8>     168 (198)                         65 536 + 12 288     2   (half-pair slots)
 // No instantiation spills.
-#include <string.h>
-#include <type_traits>
-#include "hc_common.h"
-#include "hcq_forms.h"
+#include "hcq_conv.h"
 
 // Phase ablation for timing experiments only (tools/hcq_ablate.sh builds variants into tools/_bin; results are WRONG with
 // any bit set): 1 = weight fragments requested once (every unit reads slot 0), 2 = LDS operand reads + sums once,
@@ -66,50 +69,6 @@
 #endif
 
 namespace seld {
-
-// The channel-tile layout of a launch, shared by the convolution kernels and the kernel that packs their weights.
-struct HcqTiles {
-    int NT1, NT2, NR;            // tiles active in range 0 only / in both ranges; K ranges (1 quaternion, 2 dual quaternion)
-    int nreg, mix;               // regular channel tiles per weight set; 1: a mixed 8 + 8 tile follows them
-    int ob_step;                 // block channels a channel tile advances by (16 / 32, or 0 for the single-tile layout)
-    int half_src[2];             // source half (0 primal, 1 dual) read by range 0 / range 1
-    int tile_half[3][2];         // tile t, 8-channel group g: destination half ...
-    int tile_ob[3][2];           // ... and first block channel (-1: padding, nothing stored); tile 2 = the mixed tile
-    long long range_stride[2];   // floats of one (chunk, range) block of the packed weights
-    long long ytile_stride;      // floats of one regular channel tile (all chunks of all sources)
-    long long set_stride;        // floats of one weight set (regular tiles + the mixed tile's block)
-};
-
-struct HcqP {
-    const float* src;
-    const float* src2;           // data gradient of a pair: dst = dgrad(src, W_0) + dgrad(src2, W_1), the K loop runs over both
-    int nsrc;                    // 1 or 2
-    int mix_ytile;               // index of the channel tile that holds ONLY the mixed 8 + 8 tile (dual quaternion with
-                                 // 24 block channels), or -1
-    const float* wpack;
-    float* dst[2];               // per weight set (a pair launch computes two convolutions of the same input)
-    const float* bias[2];
-    const float* addend[2];
-    float* stats[2];
-    int epilogue[2];
-    int A;                       // 4 or 8
-    int N, Csrc, Cdst;           // channels of src / of ONE dst
-    int IB, OB;                  // Csrc / A, Cdst / A
-    int W;                       // row length (T of a 1-D layer, image width of a 2-D layer)
-    int Himg;                    // image height (1 for 1-D)
-    int dil, dpad;               // dilation along W, padded up to a multiple of 4 (the halo each side of a tile)
-    int wext;                    // 64 + 2 * dpad
-    int nch;                     // K chunks per range (IB / IBC)
-    int ytiles;                  // channel tiles per weight set (t.nreg + t.mix)
-    HcqTiles t;
-    int ring_off;                // hcq_conv_kernel: byte offset of the fragment ring in LDS (behind the input buffers)
-    int half_slots;              // ring slot = 8 forms of a pair of k-groups (0) or 4 forms (1: half the ring, one more barrier)
-};
-
-typedef unsigned int uintx4h __attribute__((ext_vector_type(4)));
-
-// n / d for 0 <= n < 2^20 with a precomputed 1.0f / d (exact: see hc_conv_vec.hip)
-__device__ __forceinline__ int small_div_h(int n, float inv_d) { return (int)(((float)n + 0.5f) * inv_d); }
 
 // KH x KW taps (1x1, 1x3, 3x3), IBC block channels per K chunk, NT1 tiles active in range 0 only + NT2 tiles active
 // in both ranges (NR = 1: quaternion, one range), XI staging items per thread.
@@ -140,9 +99,7 @@ __global__ __launch_bounds__(256, 2) void hcq_conv_kernel(const HcqP p) {
 
     // ---- tile position (32-bit arithmetic throughout: the host checked that both tensors are below 4 GB) ------------
     const unsigned tiles_per_row = (unsigned)p.W >> 6;    // 64 consecutive positions inside ONE row (W % 64 == 0)
-    // workgroups go round-robin to the 8 XCDs: give each XCD (its own L2) a contiguous range of position tiles, so that
-    // the tiles sharing halo rows / output lines meet in one L2
-    const unsigned bx = (gridDim.x & 7u) ? blockIdx.x : (blockIdx.x & 7u) * (gridDim.x >> 3) + (blockIdx.x >> 3);
+    const unsigned bx = hcq_xcd_block();
     const unsigned row_g = bx / tiles_per_row;            // n * Himg + h
     const int w0 = (int)(bx - row_g * tiles_per_row) * 64;
     const int n_img = (int)(row_g / (unsigned)p.Himg);
@@ -503,7 +460,6 @@ __global__ __launch_bounds__(256, 2) void hcq_conv_kernel(const HcqP p) {
     float* const dst = p.dst[set];
     const float* const bias = p.bias[set];
     const float* const addend = p.addend[set];
-    float* const stats = p.stats[set];
     const int epi = p.epilogue[set];
     const int grp = fr >> 3;
     const unsigned pos_off = (unsigned)h0 * (unsigned)p.W + (unsigned)(w0 + wave * 16 + fk * 4);
@@ -515,6 +471,8 @@ __global__ __launch_bounds__(256, 2) void hcq_conv_kernel(const HcqP p) {
 #pragma unroll
         for (int t = 0; t < NT; ++t) {
             // a mixed-tile workgroup: accumulator slot NT1 is descriptor slot 2, the other slots are padding
+            // (hcq_lane_channel's decode in a spelling of its own: through the helper 11 instantiations allocate 1 to 6
+            //  registers fewer and five of them run at another occupancy -- DESIGN.md)
             const int ds = mix_wg ? 2 : t;
             const int ob0 = (mix_wg && t != NT1) ? -1 : p.t.tile_ob[ds][grp];
             const int half = p.t.tile_half[ds][grp];
@@ -562,565 +520,11 @@ __global__ __launch_bounds__(256, 2) void hcq_conv_kernel(const HcqP p) {
     };
     if (epi == 0 && !bias) epilogue(std::true_type{});
     else epilogue(std::false_type{});
-    if (epi & SELD_EPI_STATS) {
-        __syncthreads();
-        float* rep = stats + (size_t)(blockIdx.x % SELD_STATS_REPLICAS) * 2 * p.Cdst;
-        for (int e = tid; e < NT * 4 * 16; e += 256) {
-            const int fr_ = e & 15, q = (e >> 4) & 3, t = e >> 6;
-            const int g_ = fr_ >> 3;
-            const int ds = mix_wg ? 2 : t;
-            const int ob0 = (mix_wg && t != NT1) ? -1 : p.t.tile_ob[ds][g_];
-            if (ob0 < 0) continue;
-            const int chn = (p.t.tile_half[ds][g_] * 4 + q) * p.OB + ob0 + (mix_wg ? 0 : ytile * p.t.ob_step) + (fr_ & 7);
-            float a1 = 0.f, a2 = 0.f;
-#pragma unroll
-            for (int wv = 0; wv < 4; ++wv) {
-                const int slot = ((wv * NT + t) * 4 + q) * 16 + fr_;
-                a1 += redbuf[slot * 2 + 0];
-                a2 += redbuf[slot * 2 + 1];
-            }
-            atomicAdd(rep + chn, a1);
-            atomicAdd(rep + p.Cdst + chn, a2);
-        }
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------------------------
-// First layers (3x3, one or two input block channels): the K loop is ONE short chunk (9 or 18 k of 12 / 20 slots), so
-// hcq_conv_kernel above is all prologue and epilogue there (120 MFMAs per workgroup: 688 us for the 8-channel layer at
-// batch 32, the block-matrix short-K kernel takes 609).  Here a workgroup keeps its 64 columns and walks R consecutive
-// image rows: the R + 2 input rows are staged once (23 / 46 KB), there is ONE barrier, the weight fragments of row r+1
-// are requested under the MFMAs of row r, a row's stores drain under the next row's MFMAs and the BatchNorm statistics
-// stay in registers until the last row.
-// ---------------------------------------------------------------------------------------------------------------------
-template <int IBC, int NT1, int NT2, int NR, int R>
-__global__ __launch_bounds__(256, 2) void hcq_first_kernel(const HcqP p) {
-    constexpr int KH = 3, KW = 3, TAPS = 9;
-    constexpr int NT = NT1 + NT2;
-    constexpr int KQ = IBC * TAPS;
-    constexpr int NG = (KQ + 3) / 4;
-    constexpr int NPAIR = (NG + 1) / 2;
-    constexpr int NPC = NR * NPAIR;
-    constexpr int XR = R + KH - 1;                    // staged input rows
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int fr = lane & 15, fk = lane >> 4;
-    const int A = p.A;
-    constexpr int wext = 72, qw = wext >> 2, DPAD = 4;    // dilation 1: halo of 4 each side (the host checks p.wext)
-
-    const unsigned tiles_per_row = (unsigned)p.W >> 6;
-    const unsigned hblocks = (unsigned)p.Himg / R;
-    // Workgroups are dealt round-robin to the 8 XCDs (each with its own L2): give an XCD consecutive tiles, so that the
-    // 64-column pieces of one 2 KB image row are written back by ONE L2 (spread over eight, every piece was a separate
-    // 256-byte DRAM write)
-    unsigned b = blockIdx.x;
-    if ((gridDim.x & 7u) == 0) b = (blockIdx.x & 7u) * (gridDim.x >> 3) + (blockIdx.x >> 3);
-    const int w0 = (int)(b % tiles_per_row) * 64;
-    b /= tiles_per_row;
-    const int h0 = (int)(b % hblocks) * R;
-    const int n_img = (int)(b / hblocks);
-
-    // ---- stage the R + 2 rows of every (component, block channel) once -------------------------------------------
-    const unsigned S = (unsigned)(p.Himg * p.W);
-    {
-        const unsigned src_bytes = (unsigned)p.N * (unsigned)p.Csrc * S * 4u;
-        const unsigned OOB = 0xFFFFFFF0u;
-        const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p.src, 0, src_bytes, 0x00020000);
-        const int items = A * IBC * XR * qw;
-        const unsigned img_base = (unsigned)n_img * (unsigned)p.Csrc * S;
-        constexpr float inv_qw = 1.0f / (float)qw;
-        // four requests in flight per thread, then their four LDS stores (one load -> wait -> store per iteration exposed a
-        // first-touch memory latency six to twelve times at the head of every workgroup)
-        for (int f0 = tid; f0 < items; f0 += 4 * 256) {
-            uintx4h v[4];
-            int dst_[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int f = f0 + 256 * u;
-                const int row = small_div_h(f, inv_qw);               // (comp * IBC + ibl) * XR + xr
-                const int quad = f - row * qw;
-                const int ci = row / XR;
-                const int xr = row - ci * XR;
-                const int comp = ci / IBC;
-                const int ibl = ci - comp * IBC;
-                const int hh = h0 - (KH - 1) / 2 + xr;
-                const int ww = w0 - DPAD + 4 * quad;
-                const bool ok = f < items && (unsigned)hh < (unsigned)p.Himg && (unsigned)ww < (unsigned)p.W;
-                const unsigned e = img_base + ((unsigned)(comp * p.IB + ibl) * (unsigned)p.Himg + (unsigned)hh) * (unsigned)p.W + (unsigned)ww;
-                v[u] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, ok ? e * 4u : OOB, 0, 0);
-                dst_[u] = f < items ? (row * qw + quad) * 4 : -1;
-            }
-#pragma unroll
-            for (int u = 0; u < 4; ++u)
-                if (dst_[u] >= 0)
-                    *reinterpret_cast<float4*>(lds + dst_[u]) =
-                        make_float4(__uint_as_float(v[u][0]), __uint_as_float(v[u][1]), __uint_as_float(v[u][2]), __uint_as_float(v[u][3]));
-        }
-    }
-
-    int aoff[NG];
-#pragma unroll
-    for (int g = 0; g < NG; ++g) {
-        const int kq = (4 * g + fk) < KQ ? 4 * g + fk : 0;
-        const int ibl = kq / TAPS;
-        const int tap = kq - ibl * TAPS;
-        const int kh = tap / KW;
-        const int kw = tap - kh * KW;
-        aoff[g] = (ibl * XR + kh) * wext + DPAD + wave * 16 + fr + (kw - (KW - 1) / 2);
-    }
-    constexpr int comp_stride = IBC * XR * wext;
-    const float* const wbase = p.wpack;                 // one channel tile, one weight set, one chunk
-
-    float2 bfr[8][NT];
-    float gm[2][8];
-    float raw[4];
-    auto load_b1 = [&](const float* blk, int j, int m, auto ntrc) __attribute__((always_inline)) {
-        constexpr int NTR = decltype(ntrc)::value;
-        const float* q = blk + ((long long)(j * 8 + m) * 64 + lane) * (2 * NTR);
-#pragma unroll
-        for (int t = 0; t < NTR; ++t) bfr[m][t] = *reinterpret_cast<const float2*>(q + 2 * t);
-    };
-    auto read_raw = [&](const float* xs, int g) __attribute__((always_inline)) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) raw[q] = xs[aoff[g] + q * comp_stride];
-    };
-    using INT = std::integral_constant<int, NT>;
-    using INT2 = std::integral_constant<int, NT2>;
-
-    float* const dst = p.dst[0];
-    const float* const bias = p.bias[0];
-    const int epi = p.epilogue[0];
-    const int grp = fr >> 3;
-    const unsigned img_off = (unsigned)n_img * (unsigned)p.Cdst * S;
-    // BatchNorm statistics: one slot per (wave, tile, component, LANE) behind the staged rows, read-modify-written row by
-    // row by its owner (24 more registers per lane would spill; LDS float atomics doubled the kernel's time)
-    float* const sbuf = lds + A * IBC * XR * wext;
-    const bool want_stats = (epi & SELD_EPI_STATS) != 0;
-    if (want_stats)
-        for (int e = tid; e < 4 * NT * 4 * 64 * 2; e += 256) sbuf[e] = 0.f;
-    int chbase[NT];                                     // first-component channel of this lane in tile t, -1: padding
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-        const int ob0 = p.t.tile_ob[t][grp];
-        chbase[t] = ob0 >= 0 ? p.t.tile_half[t][grp] * 4 * p.OB + ob0 + (fr & 7) : -1;
-    }
-
-#pragma unroll
-    for (int m = 0; m < 8; ++m) load_b1(wbase, 0, m, INT{});
-    __syncthreads();
-
-#pragma unroll 1
-    for (int r = 0; r < R; ++r) {
-        floatx4 acc[NT][8];
-#pragma unroll
-        for (int t = 0; t < NT; ++t)
-#pragma unroll
-            for (int m = 0; m < 8; ++m) acc[t][m] = (floatx4){0.f, 0.f, 0.f, 0.f};
-        const bool more = r + 1 < R;
-        // the fragments are the same for every row: without this the compiler hoists all 160 registers of them out of
-        // the row loop (414 VGPRs wanted)
-        const float* wrow = wbase;
-        asm volatile("" : "+s"(wrow));
-        const float* xs0 = lds + r * wext + p.t.half_src[0] * 4 * comp_stride;
-        const float* xs1 = lds + r * wext + p.t.half_src[1] * 4 * comp_stride;
-        read_raw(xs0, 0);
-        hcq_xforms(raw, gm[0]);
-#pragma unroll
-        for (int s = 0; s < NR * NG; ++s) {
-            const int rr = s / NG, g = s - rr * NG;
-            const int pc = rr * NPAIR + g / 2;
-            const int gst = s & 1;
-            const bool last = s + 1 == NR * NG;
-            const bool pair_ends = (g & 1) == 1 || g + 1 == NG;
-            if (!last) {
-                const int rn = (s + 1) / NG, gn = (s + 1) - rn * NG;
-                read_raw(rn == 0 ? xs0 : xs1, gn);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int m = 0; m < 8; ++m) {
-                if (rr == 0) {
-#pragma unroll
-                    for (int t = 0; t < NT; ++t)
-                        acc[t][m] = __builtin_amdgcn_mfma_f32_16x16x4f32(gm[gst][m], (g & 1) ? bfr[m][t].y : bfr[m][t].x,
-                                                                          acc[t][m], 0, 0, 0);
-                } else {
-#pragma unroll
-                    for (int t = 0; t < NT2; ++t)
-                        acc[NT1 + t][m] = __builtin_amdgcn_mfma_f32_16x16x4f32(gm[gst][m], (g & 1) ? bfr[m][t].y : bfr[m][t].x,
-                                                                                acc[NT1 + t][m], 0, 0, 0);
-                }
-                if (pair_ends) {
-                    const int pn = pc + 1;
-                    if (pn < NPC) {
-                        const int rn = pn / NPAIR, jn = pn - rn * NPAIR;
-                        if (rn == 0) load_b1(wrow, jn, m, INT{});
-                        else load_b1(wrow + p.t.range_stride[0], jn, m, INT2{});
-                    } else if (more) {
-                        load_b1(wrow, 0, m, INT{});               // the next row starts with the same fragments
-                    }
-                }
-            }
-            if (!last) hcq_xforms(raw, gm[gst ^ 1]);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        // ---- this row's results ------------------------------------------------------------------------------------
-        const unsigned pos_off = (unsigned)(h0 + r) * (unsigned)p.W + (unsigned)(w0 + wave * 16 + fk * 4);
-#pragma unroll
-        for (int t = 0; t < NT; ++t) {
-            floatx4 c[4];
-            hcq_recombine4(acc[t], c);
-            if (chbase[t] >= 0) {
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const int chn = chbase[t] + q * p.OB;
-                    const float bq = bias ? bias[chn] : 0.f;
-                    const float4 o = make_float4(c[q][0] + bq, c[q][1] + bq, c[q][2] + bq, c[q][3] + bq);
-                    *reinterpret_cast<float4*>(dst + img_off + (unsigned)chn * S + pos_off) = o;
-                    if (want_stats) {
-                        const int slot = ((wave * NT + t) * 4 + q) * 64 + lane;
-                        sbuf[slot] += (o.x + o.y) + (o.z + o.w);                       // the slot is this lane's own
-                        sbuf[4 * NT * 4 * 64 + slot] += (o.x * o.x + o.y * o.y) + (o.z * o.z + o.w * o.w);
-                    }
-                }
-            }
-            __builtin_amdgcn_sched_barrier(0);           // one tile's recombination at a time (registers)
-        }
-    }
-
-    if (want_stats) {
-        __syncthreads();
-        float* rep = p.stats[0] + (size_t)(blockIdx.x % SELD_STATS_REPLICAS) * 2 * p.Cdst;
-        for (int e = tid; e < NT * 4 * 16; e += 256) {
-            const int fr_ = e & 15, q = (e >> 4) & 3, t = e >> 6;
-            const int g_ = fr_ >> 3;
-            const int ob0 = p.t.tile_ob[t][g_];
-            if (ob0 < 0) continue;
-            const int chn = (p.t.tile_half[t][g_] * 4 + q) * p.OB + ob0 + (fr_ & 7);
-            float a1 = 0.f, a2 = 0.f;
-#pragma unroll
-            for (int wv = 0; wv < 4; ++wv)
-#pragma unroll
-                for (int k4 = 0; k4 < 4; ++k4) {
-                    const int slot = ((wv * NT + t) * 4 + q) * 64 + k4 * 16 + fr_;
-                    a1 += sbuf[slot];
-                    a2 += sbuf[4 * NT * 4 * 64 + slot];
-                }
-            atomicAdd(rep + chn, a1);
-            atomicAdd(rep + p.Cdst + chn, a2);
-        }
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------------------------
-// First stage with the pooling decision fused in: conv -> [BatchNorm2d -> ReLU ->] MaxPool2d(8, 1).  BatchNorm + ReLU is
-// z = relu(a y + b) with a = gamma * invstd, and invstd > 0: the SIGN of a is the sign of gamma, known before the batch
-// statistics are.  So the maximum of z over a pooling window sits where y is largest (gamma > 0) or smallest (gamma < 0),
-// and the convolution kernel -- whose workgroup walks exactly the 8 rows of a window -- can pick that element itself:
-// it writes y (the backward pass needs it), the BatchNorm statistics, and per window the chosen raw value + its row.
-// A pooled-size kernel (seld_bn_pool_finish) then applies relu(a v + b) once the statistics are final; the 1.6 GB
-// read-back of y by bn_relu_pool_fwd disappears.  (Ties: where the window's maximum of z is 0 every position ties and
-// torch takes the first; the element chosen here may differ, but ReLU's derivative is 0 there, so no gradient does.
-// gamma == 0 keeps row 0, as torch's first-maximum rule does.)
-//
-// Unlike hcq_first_kernel a wave finishes one channel tile for all 8 rows before the next (the running window maximum of
-// three tiles at once does not fit the register file): 8 accumulators instead of 24, the sums G_m recomputed per tile.
-// ---------------------------------------------------------------------------------------------------------------------
-struct HcqPoolP {
-    const float* gamma;          // (Cdst)
-    float* pool_raw;             // (N, Cdst, Himg / 8, W): the conv output at the window's arg-max / arg-min row
-    unsigned char* idx;          // same shape: that row (0..7)
-    // FIN: BatchNorm with KNOWN statistics (first_stage.hip: from the input's second moments), ReLU and the stage's Dropout
-    // applied to the window value before it is stored: out = relu(a raw + b) * mask; pool_raw is then written only for
-    // channels with gamma == 0 (the one case in which the backward pass cannot recover xhat from out)
-    const float* beta;
-    const float* mean;
-    const float* invstd;
-    float* out;
-    DropP drop;
-};
-
-// WY = false: y is not written and no statistics are gathered (csrc/first_stage.hip: the statistics come from the input's
-// second moments, the backward pass never reads y) -- the kernel's only output is the pooled-size window value + row.
-template <int IBC, int NT1, int NT2, int NR, int R, bool WY, bool FIN = false>
-__global__ __launch_bounds__(256, 3) void hcq_first_pool_kernel(const HcqP p, const HcqPoolP pp) {
-    static_assert(!(WY && FIN), "the finishing variant knows the statistics beforehand: it never writes y");
-    constexpr int KH = 3, KW = 3, TAPS = 9;
-    constexpr int NT = NT1 + NT2;
-    constexpr int KQ = IBC * TAPS;
-    constexpr int NG = (KQ + 3) / 4;
-    constexpr int NPAIR = (NG + 1) / 2;
-    constexpr int XR = R + KH - 1;
-    static_assert(R == 8, "one workgroup = one MaxPool2d(8, 1) window");
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int fr = lane & 15, fk = lane >> 4;
-    const int A = p.A;
-    constexpr int wext = 72, qw = wext >> 2, DPAD = 4;
-
-    const unsigned tiles_per_row = (unsigned)p.W >> 6;
-    const unsigned hblocks = (unsigned)p.Himg / R;
-    unsigned b = blockIdx.x;
-    if ((gridDim.x & 7u) == 0) b = (blockIdx.x & 7u) * (gridDim.x >> 3) + (blockIdx.x >> 3);     // XCD-contiguous ranges
-    const int w0 = (int)(b % tiles_per_row) * 64;
-    b /= tiles_per_row;
-    const int hq = (int)(b % hblocks);
-    const int h0 = hq * R;
-    const int n_img = (int)(b / hblocks);
-
-    const unsigned S = (unsigned)(p.Himg * p.W);
-    {
-        const unsigned src_bytes = (unsigned)p.N * (unsigned)p.Csrc * S * 4u;
-        const unsigned OOB = 0xFFFFFFF0u;
-        const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p.src, 0, src_bytes, 0x00020000);
-        const int items = A * IBC * XR * qw;
-        const unsigned img_base = (unsigned)n_img * (unsigned)p.Csrc * S;
-        constexpr float inv_qw = 1.0f / (float)qw;
-        // four requests in flight per thread, then their four LDS stores (one load -> wait -> store per iteration exposed a
-        // first-touch memory latency six to twelve times at the head of every workgroup)
-        for (int f0 = tid; f0 < items; f0 += 4 * 256) {
-            uintx4h v[4];
-            int dst_[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int f = f0 + 256 * u;
-                const int row = small_div_h(f, inv_qw);               // (comp * IBC + ibl) * XR + xr
-                const int quad = f - row * qw;
-                const int ci = row / XR;
-                const int xr = row - ci * XR;
-                const int comp = ci / IBC;
-                const int ibl = ci - comp * IBC;
-                const int hh = h0 - (KH - 1) / 2 + xr;
-                const int ww = w0 - DPAD + 4 * quad;
-                const bool ok = f < items && (unsigned)hh < (unsigned)p.Himg && (unsigned)ww < (unsigned)p.W;
-                const unsigned e = img_base + ((unsigned)(comp * p.IB + ibl) * (unsigned)p.Himg + (unsigned)hh) * (unsigned)p.W + (unsigned)ww;
-                v[u] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, ok ? e * 4u : OOB, 0, 0);
-                dst_[u] = f < items ? (row * qw + quad) * 4 : -1;
-            }
-#pragma unroll
-            for (int u = 0; u < 4; ++u)
-                if (dst_[u] >= 0)
-                    *reinterpret_cast<float4*>(lds + dst_[u]) =
-                        make_float4(__uint_as_float(v[u][0]), __uint_as_float(v[u][1]), __uint_as_float(v[u][2]), __uint_as_float(v[u][3]));
-        }
-    }
-    int aoff[NG];
-#pragma unroll
-    for (int g = 0; g < NG; ++g) {
-        const int kq = (4 * g + fk) < KQ ? 4 * g + fk : 0;
-        const int ibl = kq / TAPS;
-        const int tap = kq - ibl * TAPS;
-        const int kh = tap / KW;
-        const int kw = tap - kh * KW;
-        aoff[g] = (ibl * XR + kh) * wext + DPAD + wave * 16 + fr + (kw - (KW - 1) / 2);
-    }
-    constexpr int comp_stride = IBC * XR * wext;
-    float* const sred = lds + A * IBC * XR * wext;      // statistics: [tile][wave][component][16 channels][2]
-    // The current tile's weight fragments live in LDS ([pair][form][lane] float2): with them in global memory every row
-    // ended on `s_waitcnt vmcnt` for its fragment loads -- and loads and stores retire in order on one counter, so each
-    // row also waited for the previous row's 12 stores to reach memory: store time ADDED to compute time (686 us).  With no
-    // global load inside the row loop the stores drain under the next rows' MFMAs.
-    float2* const wl = reinterpret_cast<float2*>(sred + NT * 4 * 4 * 16 * 2);
-    const float* const wbase = p.wpack;
-    float* const dst = p.dst[0];
-    const float* const bias = p.bias[0];
-    const bool want_stats = WY && (p.epilogue[0] & SELD_EPI_STATS) != 0;
-    const int grp = fr >> 3;
-    const unsigned img_off = (unsigned)n_img * (unsigned)p.Cdst * S;
-    const unsigned PS = (unsigned)hblocks * (unsigned)p.W;                   // pooled plane
-    const unsigned pool_off = (unsigned)n_img * (unsigned)p.Cdst * PS + (unsigned)hq * (unsigned)p.W +
-                              (unsigned)(w0 + wave * 16 + fk * 4);
-    __syncthreads();
-
-    float2 bfr[8];
-    float gm[2][8];
-    float raw[4];
-    auto read_raw = [&](const float* xs, int g) __attribute__((always_inline)) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) raw[q] = xs[aoff[g] + q * comp_stride];
-    };
-
-    auto tile_body = [&](auto tc) __attribute__((always_inline)) {
-        constexpr int T = decltype(tc)::value;
-        constexpr bool BOTH = NR == 2 && T >= NT1;            // this tile's channels take the second K range too
-        constexpr int NRT = BOTH ? 2 : 1;
-        constexpr int NPCT = NRT * NPAIR;
-        const int ob0 = p.t.tile_ob[T][grp];
-        const int chb = ob0 >= 0 ? p.t.tile_half[T][grp] * 4 * p.OB + ob0 + (fr & 7) : -1;
-        // fragments of tile T only (range 0 blocks hold NT tiles per (pair, form, lane), range 1 blocks NT2): into LDS
-        __syncthreads();                                  // everybody is done with the previous tile's fragments
-        {
-            // all of a thread's loads first, then its stores: as one load -> wait -> store per iteration the fill exposed
-            // 4 / 8 / 8 cache latencies per tile, a fifth of the workgroup's time
-            constexpr int NIT = NPCT * 8 * 64 / 256;
-            float2 tmp[NIT];
-#pragma unroll
-            for (int it = 0; it < NIT; ++it) {
-                const int e = tid + 256 * it;
-                const int ln = e & 63, jm = e >> 6;       // jm = pair * 8 + form over both ranges
-                const int rr = jm / (NPAIR * 8), jm0 = jm - rr * (NPAIR * 8);
-                const float* blk = rr == 0 ? wbase : wbase + p.t.range_stride[0];
-                const int ntr = rr == 0 ? NT : NT2, tt = rr == 0 ? T : T - NT1;
-                tmp[it] = *reinterpret_cast<const float2*>(blk + ((long long)jm0 * 64 + ln) * (2 * ntr) + 2 * tt);
-            }
-#pragma unroll
-            for (int it = 0; it < NIT; ++it) wl[tid + 256 * it] = tmp[it];
-        }
-        __syncthreads();
-        auto load_b1 = [&](int pc, int m) __attribute__((always_inline)) { bfr[m] = wl[(pc * 8 + m) * 64 + lane]; };
-        float sg[4], yb[4][4], sb[4][4], s1[4], s2[4], bq[4];     // sb = sg * yb, the key the window maximum is taken over
-        unsigned bi[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const float gq = chb >= 0 ? pp.gamma[chb + q * p.OB] : 1.f;
-            bq[q] = (bias && chb >= 0) ? bias[chb + q * p.OB] : 0.f;
-            sg[q] = gq > 0.f ? 1.f : (gq < 0.f ? -1.f : 0.f);
-            s1[q] = 0.f; s2[q] = 0.f; bi[q] = 0u;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) { yb[q][e] = 0.f; sb[q][e] = -INFINITY; }
-        }
-#pragma unroll
-        for (int m = 0; m < 8; ++m) load_b1(0, m);
-#pragma unroll 1
-        for (int r = 0; r < R; ++r) {
-            floatx4 acc[8];
-#pragma unroll
-            for (int m = 0; m < 8; ++m) acc[m] = (floatx4){0.f, 0.f, 0.f, 0.f};
-            const bool more = r + 1 < R;
-            const float* xs0 = lds + r * wext + p.t.half_src[0] * 4 * comp_stride;
-            const float* xs1 = lds + r * wext + p.t.half_src[1] * 4 * comp_stride;
-            read_raw(xs0, 0);
-            hcq_xforms(raw, gm[0]);
-#pragma unroll
-            for (int s = 0; s < NRT * NG; ++s) {
-                const int rr = s / NG, g = s - rr * NG;
-                const int pc = rr * NPAIR + g / 2;
-                const int gst = s & 1;
-                const bool last = s + 1 == NRT * NG;
-                const bool pair_ends = (g & 1) == 1 || g + 1 == NG;
-                if (!last) {
-                    const int rn = (s + 1) / NG, gn = (s + 1) - rn * NG;
-                    read_raw(rn == 0 ? xs0 : xs1, gn);
-                }
-                __builtin_amdgcn_sched_barrier(0);      // (without the two barriers of a group: 710 us against 670-690)
-#pragma unroll
-                for (int m = 0; m < 8; ++m) {
-                    acc[m] = __builtin_amdgcn_mfma_f32_16x16x4f32(gm[gst][m], (g & 1) ? bfr[m].y : bfr[m].x, acc[m], 0, 0, 0);
-                    if (pair_ends) {
-                        const int pn = pc + 1;
-                        if (pn < NPCT) load_b1(pn, m);
-                        else if (more) load_b1(0, m);
-                    }
-                }
-                if (!last) hcq_xforms(raw, gm[gst ^ 1]);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            // ---- this row of this tile: components, store, statistics, window maximum ------------------------------
-            floatx4 c[4];
-            hcq_recombine4(acc, c);
-            if (chb >= 0) {
-                const unsigned pos_off = (unsigned)(h0 + r) * (unsigned)p.W + (unsigned)(w0 + wave * 16 + fk * 4);
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const int chn = chb + q * p.OB;
-                    float o[4] = {c[q][0], c[q][1], c[q][2], c[q][3]};
-                    if (bias) { o[0] += bq[q]; o[1] += bq[q]; o[2] += bq[q]; o[3] += bq[q]; }
-                    if constexpr (WY) {
-                        *reinterpret_cast<float4*>(dst + img_off + (unsigned)chn * S + pos_off) = make_float4(o[0], o[1], o[2], o[3]);
-                        s1[q] += (o[0] + o[1]) + (o[2] + o[3]);
-                        s2[q] += (o[0] * o[0] + o[1] * o[1]) + (o[2] * o[2] + o[3] * o[3]);
-                    }
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        // first maximum wins, NaN propagates: "not (key <= best)" is true for a larger key and for NaN, and
-                        // for row 0 (best = -inf); gamma == 0 makes every key 0, so row 0 stays
-                        const float so = sg[q] * o[e];
-                        const bool take = !(so <= sb[q][e]);
-                        yb[q][e] = take ? o[e] : yb[q][e];
-                        sb[q][e] = take ? so : sb[q][e];
-                        bi[q] = take ? ((bi[q] & ~(0xFFu << (8 * e))) | ((unsigned)r << (8 * e))) : bi[q];
-                    }
-                }
-            }
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        if (chb >= 0) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const unsigned po = pool_off + (unsigned)(chb + q * p.OB) * PS;
-                *reinterpret_cast<unsigned*>(pp.idx + po) = bi[q];
-                if constexpr (FIN) {
-                    const int chn = chb + q * p.OB;
-                    const float gq = pp.gamma[chn];
-                    const float a = gq * pp.invstd[chn], bb = pp.beta[chn] - pp.mean[chn] * a;
-                    float z[4];
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        const float v = yb[q][e];
-                        z[e] = fmaxf(v * a + bb, 0.f);
-                        if (v != v) z[e] = v;                                   // NaN propagates (torch's relu / max_pool)
-                    }
-                    if (pp.drop.p > 0.f) {       // the mask seld_dropout_fwd draws for element group po / 4 of `out`
-                        const uint64_t off = pp.drop.offset + (pp.drop.state ? pp.drop.state[0] : 0ull);
-                        const float4 mk = dropout_mask4(off + (uint64_t)(po >> 2), pp.drop.seed, pp.drop.p, pp.drop.scale);
-                        z[0] = mk.x != 0.f ? z[0] * mk.x : 0.f;
-                        z[1] = mk.y != 0.f ? z[1] * mk.y : 0.f;
-                        z[2] = mk.z != 0.f ? z[2] * mk.z : 0.f;
-                        z[3] = mk.w != 0.f ? z[3] * mk.w : 0.f;
-                    }
-                    *reinterpret_cast<float4*>(pp.out + po) = make_float4(z[0], z[1], z[2], z[3]);
-                    if (gq == 0.f) *reinterpret_cast<float4*>(pp.pool_raw + po) = make_float4(yb[q][0], yb[q][1], yb[q][2], yb[q][3]);
-                } else {
-                    *reinterpret_cast<float4*>(pp.pool_raw + po) = make_float4(yb[q][0], yb[q][1], yb[q][2], yb[q][3]);
-                }
-            }
-        }
-        if (want_stats) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                float a1 = s1[q], a2 = s2[q];
-                a1 += __shfl_xor(a1, 16, 64);
-                a1 += __shfl_xor(a1, 32, 64);
-                a2 += __shfl_xor(a2, 16, 64);
-                a2 += __shfl_xor(a2, 32, 64);
-                if (fk == 0) {
-                    const int slot = ((T * 4 + wave) * 4 + q) * 16 + fr;
-                    sred[slot * 2 + 0] = a1;
-                    sred[slot * 2 + 1] = a2;
-                }
-            }
-        }
-    };
-    tile_body(std::integral_constant<int, 0>{});
-    if constexpr (NT > 1) tile_body(std::integral_constant<int, 1>{});
-    if constexpr (NT > 2) tile_body(std::integral_constant<int, 2>{});
-
-    if (want_stats) {
-        __syncthreads();
-        float* rep = p.stats[0] + (size_t)(blockIdx.x % SELD_STATS_REPLICAS) * 2 * p.Cdst;
-        for (int e = tid; e < NT * 4 * 16; e += 256) {
-            const int fr_ = e & 15, q = (e >> 4) & 3, t = e >> 6;
-            const int g_ = fr_ >> 3;
-            const int ob0 = p.t.tile_ob[t][g_];
-            if (ob0 < 0) continue;
-            const int chn = (p.t.tile_half[t][g_] * 4 + q) * p.OB + ob0 + (fr_ & 7);
-            float a1 = 0.f, a2 = 0.f;
-#pragma unroll
-            for (int wv = 0; wv < 4; ++wv) {
-                const int slot = ((t * 4 + wv) * 4 + q) * 16 + fr_;
-                a1 += sred[slot * 2 + 0];
-                a2 += sred[slot * 2 + 1];
-            }
-            atomicAdd(rep + chn, a1);
-            atomicAdd(rep + p.Cdst + chn, a2);
-        }
-    }
+    if (epi & SELD_EPI_STATS)
+        hcq_stats_flush<NT, 1>(p, set, tid, mix_wg ? NT1 : -1, mix_wg ? 0 : ytile * p.t.ob_step, redbuf, 1,
+                               [](int wv, int, int t, int q, int fr_) __attribute__((always_inline)) {
+                                   return (((wv * NT + t) * 4 + q) * 16 + fr_) * 2;
+                               });
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -1130,18 +534,6 @@ __global__ __launch_bounds__(256, 3) void hcq_first_pool_kernel(const HcqP p, co
 // Layout: [weight set (forward pairs)] x { regular channel tiles [ytile][source (gradient pairs)][chunk][range][pair]
 // [m][lane][tile][2 groups], the mixed channel tile (if any) last, same layout }.
 // ---------------------------------------------------------------------------------------------------------------------
-struct HcqPackP {
-    WPtrs w[2];                  // component tensors (OA, IA, taps) of the 1 or 2 weight sets
-    float* out;
-    int A, mode;
-    int OA, IA, taps;            // of the CONVOLUTION (not swapped for the data gradient)
-    int IBC, nch, NG, NPAIR;
-    int nsets;                   // forward pairs: separate outputs
-    int nsrc;                    // gradient pairs: two (source, weight set) along K
-    HcqTiles t;
-    long long total;
-};
-
 __device__ __forceinline__ float hcq_pack_value(const HcqPackP& p, long long idx) {
     // 32-bit index arithmetic (the host keeps every buffer below 2^31 floats): the 64-bit divisions this decode started
     // with were most of the kernel's 60 us
@@ -1228,61 +620,8 @@ __global__ __launch_bounds__(256) void hcq_pack_flat_kernel(const HcqPackP* __re
 // ---------------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------------
-// The instantiations, once: taps, K chunk, staging items per thread of the dual-quaternion and of the quaternion kernels
-// (0: none).  XI is fixed by (taps, IBC, algebra) except for the dilated 1x3 layers (halo width): a plan takes the first
-// row whose XI is enough.
-struct HcqInst { int KH, KW, IBC, XI8, XI4; };
-constexpr HcqInst HCQ_INST[] = {{1, 3, 8, 5, 3},  {1, 3, 8, 7, 5},   {1, 3, 8, 9, 0}, {1, 3, 4, 6, 3}, {1, 1, 16, 8, 4},
-                                  {1, 1, 24, 12, 6}, {1, 1, 8, 4, 2},   {3, 3, 4, 7, 4}, {3, 3, 2, 4, 2}, {3, 3, 1, 2, 1}};
-// ... and the channel-tile programs every row exists in (MX: launches with mixed-tile workgroups)
-struct HcqTileV { int NT1, NT2, NR; bool MX; };
-constexpr HcqTileV HCQ_TILEV[] = {{1, 2, 2, false}, {1, 1, 2, true}, {1, 1, 2, false}, {2, 0, 1, false}, {1, 0, 1, false}};
-constexpr int HCQ_FIRST_R = 8;   // image rows per workgroup of hcq_first_kernel / hcq_first_pool_kernel (a pooling window)
-
-constexpr int HCQ_NINST = sizeof(HCQ_INST) / sizeof(HCQ_INST[0]), HCQ_NTILEV = sizeof(HCQ_TILEV) / sizeof(HCQ_TILEV[0]);
-
-// FN<row, variant>::run(args...) for the (row, variant) a plan resolved
-static_assert(HCQ_NINST == 10 && HCQ_NTILEV == 5, "SELD_HCQ_DISPATCH lists the rows 0..9 and the tile programs 0..4");
-#define SELD_HCQ_V(I, FN, ...)                                                          \
-    case I:                                                                             \
-        switch (pl.variant) {                                                           \
-            case 0: return FN<I, 0>::run(__VA_ARGS__);                                  \
-            case 1: return FN<I, 1>::run(__VA_ARGS__);                                  \
-            case 2: return FN<I, 2>::run(__VA_ARGS__);                                  \
-            case 3: return FN<I, 3>::run(__VA_ARGS__);                                  \
-            case 4: return FN<I, 4>::run(__VA_ARGS__);                                  \
-        }                                                                               \
-        break;
-#define SELD_HCQ_DISPATCH(FN, ...)                                                                                     \
-    switch (pl.row) {                                                                                                  \
-        SELD_HCQ_V(0, FN, __VA_ARGS__) SELD_HCQ_V(1, FN, __VA_ARGS__) SELD_HCQ_V(2, FN, __VA_ARGS__)                   \
-        SELD_HCQ_V(3, FN, __VA_ARGS__) SELD_HCQ_V(4, FN, __VA_ARGS__) SELD_HCQ_V(5, FN, __VA_ARGS__)                   \
-        SELD_HCQ_V(6, FN, __VA_ARGS__) SELD_HCQ_V(7, FN, __VA_ARGS__) SELD_HCQ_V(8, FN, __VA_ARGS__)                   \
-        SELD_HCQ_V(9, FN, __VA_ARGS__)                                                                                 \
-    }
-
-// Everything the entry points need to know about (desc, mode, npair): which kernel, its grid and LDS, its arguments and
-// the arguments of the kernel that packs its weights.
-struct HcqPlan {
-    int ok;
-    int row, variant;            // HCQ_INST / HCQ_TILEV
-    int XI;                      // of the instantiation
-    bool gf;                     // hcq_conv_kernel with per-wave global fragment loads (no ring)
-    int first_rows;              // > 0: hcq_first_kernel (pool: hcq_first_pool_kernel) walks this many image rows per workgroup
-    bool pool;
-    HcqP kp;
-    HcqPackP pp;
-    size_t pack_floats;
-    dim3 grid;
-    size_t smem;
-};
-
-// mode 0 forward (npair: 1 or 2 convolutions of the same input -> separate outputs),
-// mode 1 data gradient (npair: 1, or 2 = sum of the gradients of two convolutions w.r.t. their common input).
-// mode 2 = mode 0 for the pooling first-stage kernel (hcq_first_pool_kernel): same packed forms, and the 8-channel
-// dual-quaternion layer is NOT left to the short-K kernel.
-// first_ok = false: never the row-walking first-layer kernel (it takes no addend / accumulate epilogue).
-static HcqPlan hcq_plan(const seld_conv_desc* d, int mode, int npair, bool first_ok = true) {
+// The plan of (desc, mode, npair); modes and first_ok: hcq_conv.h.
+HcqPlan hcq_plan(const seld_conv_desc* d, int mode, int npair, bool first_ok) {
     HcqPlan pl{};
     const bool pool = mode == 2;
     if (pool) mode = 0;
@@ -1428,15 +767,6 @@ static HcqPlan hcq_plan(const seld_conv_desc* d, int mode, int npair, bool first
     return pl;
 }
 
-template <typename Kern, typename... Args>
-static int hcq_launch_kernel(Kern kern, const HcqPlan& pl, hipStream_t st, const Args&... args) {
-    if (pl.smem > 64 * 1024 &&
-        hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.smem) != hipSuccess)
-        return SELD_ELAUNCH;
-    hipLaunchKernelGGL(kern, pl.grid, dim3(256), pl.smem, st, args...);
-    return check_launch();
-}
-
 // XI of (row, variant), 0: not instantiated
 template <int I, int V> constexpr int hcq_xi() { return HCQ_TILEV[V].NR == 2 ? HCQ_INST[I].XI8 : HCQ_INST[I].XI4; }
 
@@ -1456,40 +786,9 @@ struct HcqLaunchConv {
     }
 };
 
-// the first layers' kernels: 3x3 with one or two block channels, no mixed-tile workgroups
-template <int I, int V> constexpr bool hcq_is_first() { return HCQ_INST[I].KH == 3 && HCQ_INST[I].IBC <= 2 && !HCQ_TILEV[V].MX; }
-
-template <int I, int V>
-struct HcqLaunchFirst {
-    static int run(const HcqPlan& pl, hipStream_t st) {
-        constexpr HcqTileV T = HCQ_TILEV[V];
-        if constexpr (hcq_is_first<I, V>())
-            return hcq_launch_kernel(hcq_first_kernel<HCQ_INST[I].IBC, T.NT1, T.NT2, T.NR, HCQ_FIRST_R>, pl, st, pl.kp);
-        return SELD_EUNSUPPORTED;
-    }
-};
-
-// fin: BatchNorm + ReLU + Dropout applied to the window value; else y is written (with statistics) or not at all
-template <int I, int V>
-struct HcqLaunchPool {
-    static int run(const HcqPlan& pl, const HcqPoolP& pp, bool fin, hipStream_t st) {
-        constexpr HcqTileV T = HCQ_TILEV[V];
-        if constexpr (hcq_is_first<I, V>()) {
-            constexpr int IBC = HCQ_INST[I].IBC;
-            if (fin) return hcq_launch_kernel(hcq_first_pool_kernel<IBC, T.NT1, T.NT2, T.NR, HCQ_FIRST_R, false, true>, pl, st, pl.kp, pp);
-            if (pl.kp.dst[0]) return hcq_launch_kernel(hcq_first_pool_kernel<IBC, T.NT1, T.NT2, T.NR, HCQ_FIRST_R, true>, pl, st, pl.kp, pp);
-            return hcq_launch_kernel(hcq_first_pool_kernel<IBC, T.NT1, T.NT2, T.NR, HCQ_FIRST_R, false>, pl, st, pl.kp, pp);
-        }
-        return SELD_EUNSUPPORTED;
-    }
-};
-
 static int hcq_launch(const HcqPlan& pl, hipStream_t st) {
-    if (pl.first_rows) {
-        SELD_HCQ_DISPATCH(HcqLaunchFirst, pl, st)
-    } else {
-        SELD_HCQ_DISPATCH(HcqLaunchConv, pl, st)
-    }
+    if (pl.first_rows) return hcq_launch_first(pl, st);
+    SELD_HCQ_DISPATCH(HcqLaunchConv, pl, st)
     return SELD_EUNSUPPORTED;
 }
 
@@ -1596,39 +895,4 @@ extern "C" int seld_hcq_conv(const seld_conv_desc* d, int32_t mode, int32_t npai
     pl.kp.src2 = x2;
     pl.kp.wpack = wpack;
     return hcq_launch(pl, (hipStream_t)stream);
-}
-
-
-/* conv -> [BatchNorm2d -> ReLU ->] MaxPool2d(8, 1) for the network's first layer (model.py:273-281), pooling decision
- * inside the convolution (hcq_first_pool_kernel): writes y (nullable: not written, and then no statistics either -- the
- * seld_first_stage_* path), the BatchNorm statistics (want_stats), and per pooling window
- * the raw value at the row that will be the maximum after BatchNorm + ReLU (by the sign of gamma) and that row.
- * wpack: seld_hcq_pack(desc, mode 2).  Follow with seld_bn_finalize_ex and seld_bn_pool_finish. */
-static int hcq_first_pool_impl(const seld_conv_desc* d, const float* x, const float* wpack, const float* bias,
-                               int32_t want_stats, float* y, float* stats, const HcqPoolP& pp, bool fin, void* stream) {
-    HcqPlan pl = hcq_plan(d, 2, 1);
-    if (!pl.ok) return SELD_EUNSUPPORTED;
-    pl.kp.src = x; pl.kp.src2 = nullptr; pl.kp.wpack = wpack;
-    pl.kp.dst[0] = y; pl.kp.bias[0] = bias; pl.kp.epilogue[0] = want_stats ? SELD_EPI_STATS : 0; pl.kp.stats[0] = stats;
-    SELD_HCQ_DISPATCH(HcqLaunchPool, pl, pp, fin, (hipStream_t)stream)
-    return SELD_EUNSUPPORTED;
-}
-
-extern "C" int seld_hcq_first_pool(const seld_conv_desc* d, const float* x, const float* wpack, const float* bias,
-                                   const float* gamma, int32_t want_stats, float* y, float* stats, float* pool_raw,
-                                   uint8_t* idx, void* stream) {
-    if (hc_validate(d) != SELD_OK || !x || !wpack || !gamma || !pool_raw || !idx || (want_stats && (!stats || !y))) return SELD_EINVAL;
-    const HcqPoolP pp{gamma, pool_raw, idx, nullptr, nullptr, nullptr, nullptr, DropP{0.f, 1.f, 0, 0, nullptr}};
-    return hcq_first_pool_impl(d, x, wpack, bias, want_stats, y, stats, pp, false, stream);
-}
-
-extern "C" int seld_hcq_first_pool_bn(const seld_conv_desc* d, const float* x, const float* wpack, const float* bias,
-                                      const float* gamma, const float* beta, const float* mean, const float* invstd,
-                                      float drop_p, uint64_t seed, uint64_t offset, const uint64_t* state, float* pool_raw,
-                                      uint8_t* idx, float* out, void* stream) {
-    if (hc_validate(d) != SELD_OK || !x || !wpack || !gamma || !beta || !mean || !invstd || !pool_raw || !idx || !out ||
-        drop_p < 0.f || drop_p >= 1.f)
-        return SELD_EINVAL;
-    const HcqPoolP pp{gamma, pool_raw, idx, beta, mean, invstd, out, DropP{drop_p, 1.0f / (1.0f - drop_p), seed, offset, state}};
-    return hcq_first_pool_impl(d, x, wpack, bias, 0, nullptr, nullptr, pp, true, stream);
 }

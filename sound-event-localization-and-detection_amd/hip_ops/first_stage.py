@@ -1,4 +1,4 @@
-"""The first CNN stage fused (csrc/first_stage.hip, csrc/hcq_conv.hip, csrc/norm.hip, csrc/elementwise.hip)."""
+"""The first CNN stage fused (csrc/first_stage.hip, csrc/hcq_first.hip, csrc/norm.hip, csrc/elementwise.hip)."""
 import ctypes
 import os
 
@@ -173,7 +173,7 @@ class ConvBnReluPoolFn(torch.autograd.Function):
             return result
         if wp is not None:
             # the convolution picks every pooling window's element itself (by the sign of gamma): y is written for the
-            # backward pass but never read back in the forward pass (csrc/hcq_conv.hip hcq_first_pool_kernel)
+            # backward pass but never read back in the forward pass (csrc/hcq_first.hip hcq_first_pool_kernel)
             o = conv_out_shape(desc)
             y = torch.empty(_y_shape(desc, o), device=x.device, dtype=torch.float32)
             N, C, Hh, Ww = y.shape

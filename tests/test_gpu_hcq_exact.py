@@ -1,5 +1,5 @@
-"""The fast-product forward and data-gradient kernels (csrc/hcq_conv.hip: hcq_conv_kernel, hcq_first_kernel) on the MI355X
-against the float64 oracle, EXACTLY: with integer inputs in [-2, 2] and weights in {-1, 0, 1} every float32 operation of
+"""The fast-product forward and data-gradient kernels (csrc/hcq_conv.hip: hcq_conv_kernel, csrc/hcq_first.hip:
+hcq_first_kernel) on the MI355X against the float64 oracle, EXACTLY: with integer inputs in [-2, 2] and weights in {-1, 0, 1} every float32 operation of
 the kernels is exact in any order (tests/hcq_exact.py), so every output must hold the oracle's integers bit for bit.
 Cases: tests/golden/hcq_exact_cases.py -- one per launch (mode, npair, kernel label, ring slot kind) that the dispatch
 fixture records, plus edge shapes.
