@@ -7,303 +7,31 @@
 // per axis (D, H, W); M is the Hamilton block matrix of the component tensors, read directly with the signs applied
 // while staging into LDS (hc_comp), never materialised.  Three kernels serve both operations:
 //
-//   hc_conv3d_fwd_kernel    implicit GEMM, positions (n, od, oh, ow) x reduction (ci, td, th, tw): conv forward (+ bias),
-//                           transposed-conv input gradient
-//   hc_conv3d_phase_kernel  stride-phase GEMM (hc_tconv_kernel of hc_conv_transpose.hip on three axes): the output
-//                           splits into sd*sh*sw residue classes; inside a class the taps that reach it form a fixed
-//                           progression and the input index is an exact quotient, so each class is a dense stride-1
-//                           GEMM with no per-element divisibility test and no MFMA on zeros.  Transposed-conv forward
-//                           (+ bias; positions no tap reaches get the bias alone), conv input gradient
+//   hc_conv3d_fwd_kernel    the implicit GEMM of hc_phase_gemm.h on three axes with its forward map: positions
+//                           (n, od, oh, ow) x reduction (ci, td, th, tw).  Conv forward (+ bias), transposed-conv input
+//                           gradient
+//   hc_conv3d_phase_kernel  the same body with its stride-phase map and the weights read transposed: sd*sh*sw residue
+//                           classes, a dense stride-1 GEMM per class.  Transposed-conv forward (+ bias; positions no tap
+//                           reaches get the bias alone), conv input gradient
 //   hc_conv3d_wgrad_kernel  G = sum dy (x) im2col(x), split over positions into a workspace of partials;
 //                           hc_conv3d_fold_kernel then sums the splits in a fixed order, folds the block matrix onto the
 //                           components and ADDS into dw[c] (and the bias partials into dbias)
 //
-// Both GEMM kernels are one body over a per-axis affine index map: output class r, phase index q (o = r + os*q), tap t
-// of the class is kernel index k0[r] + t*kstep and reads input index q*im + c0[r] - t*ia.  The forward kernel is the
-// single-class case (os = 1, im = stride, ia = -dil); the phase kernel has im = 1 and reads the weights transposed (the
-// reduction runs over the component tensors' FIRST index, as MODE_DGRAD does).  Tiling as hc_tconv_kernel: 4 waves,
-// 16*CT channels x 64*PT positions, LDS images [k/4][row][4], one ds_read_b128 feeds four v_mfma_f32_16x16x4_f32.
-// For the dual quaternion a channel tile that lies in one half skips the reduction half of the zero quadrant.
+// The GEMM body, its index maps, the dual quaternion's zero-quadrant skip, the tile choice and the launch are described
+// and live in hc_phase_gemm.h; this file keeps the 3-D descriptor checks, the weight gradient and the entry points.
 //
 // No float atomics anywhere: every result is run-to-run bit-identical, with or without SELD_DETERMINISTIC.
-#include "hc_common.h"
+#include "hc_phase_gemm.h"
 
 namespace seld {
 
-constexpr int C3_MAXS = 16;        // largest stride per axis (phase tables)
-
-// one axis of the GEMM kernels' index map (see the file comment)
-struct C3Axis {
-    int in, out, K;
-    int os, im, kstep, ia;
-    int k0[C3_MAXS], n[C3_MAXS], c0[C3_MAXS], q[C3_MAXS];
-};
-
-struct C3P {
-    int A, N, Cr, Co;              // reduction (streamed operand) channels, output channels
-    int RA, OA;                    // Cr/A, Co/A
-    int KK;                        // kd*kh*kw
-    int nph;                       // residue classes: os_d*os_h*os_w
-    C3Axis ax[3];
-    long long x_elems;
-    WPtrs w;
-    const float* x;
-    const float* bias;
-    float* y;
-};
-
-template <int CT, int PT, bool WT>
-__device__ __forceinline__ void c3_gemm(const C3P& p) {
-    constexpr int BC = CT * 16;
-    constexpr int BP = PT * 64;
-    constexpr int XG = PT;
-    constexpr int XSTEP = 256 / BP;
-    constexpr int WR = (BC + 63) / 64;
-    static_assert(PT == 1 || PT == 2 || PT == 4, "BP must divide 256");
-
-    __shared__ __attribute__((aligned(16))) float Xs[2][4][BP][4];
-    __shared__ __attribute__((aligned(16))) float Ws[2][4][BC][4];
-    __shared__ const float* wptr_s[8];
-
-    // ---- residue class and position tile (class fastest in the grid) ----------------------------------------
-    const int ph = blockIdx.x % p.nph;
-    const int tile = blockIdx.x / p.nph;
-    const int rw = ph % p.ax[2].os;
-    const int rdh = ph / p.ax[2].os;
-    const int rh = rdh % p.ax[1].os, rd = rdh / p.ax[1].os;
-    const int Qd = p.ax[0].q[rd], Qh = p.ax[1].q[rh], Qw = p.ax[2].q[rw];
-    const int Qhw = Qh * Qw;
-    const int PS = Qd * Qhw;                      // class positions per image
-    const long long Ptot = (long long)p.N * PS;
-    const long long p0 = (long long)tile * BP;
-    if (p0 >= Ptot) return;                       // whole workgroup: this class has fewer tiles
-
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int xpos = tid & (BP - 1);
-    const int xg0 = __builtin_amdgcn_readfirstlane(tid / BP);
-    const int c0 = blockIdx.y * BC;
-    const int KHW = p.ax[1].K * p.ax[2].K;
-    const int Hi = p.ax[1].in, Wi = p.ax[2].in;
-    const int Si = p.ax[0].in * Hi * Wi;
-
-    if (tid < 8) wptr_s[tid] = p.w.p[tid];
-
-    // reduction channel blocks; the dual quaternion's zero quadrant is M[low][high] of the component tensors' (first,
-    // second) index: a low output tile of the forward reads the low reduction half only, a high output tile of the
-    // phase kernel (weights transposed) the high half only
-    int cb_lo = 0, cb_hi = (p.Cr + 15) >> 4;
-    if (p.A == 8) {
-        const int half = p.Co >> 1, rhalf = p.Cr >> 1;
-        if (!WT && c0 + BC <= half) cb_hi = (rhalf + 15) >> 4;
-        if (WT && c0 >= half) cb_lo = rhalf >> 4;
-    }
-
-    // taps of this class
-    const int ntd = p.ax[0].n[rd], nth = p.ax[1].n[rh], ntw = p.ax[2].n[rw];
-    const int nchunks = ntd * nth * ntw * (cb_hi - cb_lo);
-    const int kd0 = p.ax[0].k0[rd], kh0 = p.ax[1].k0[rh], kw0 = p.ax[2].k0[rw];
-
-    // ---- streamed operand: buffer descriptor based at the first image of the tile ----------------------------
-    const long long img0 = p0 / PS;
-    const long long img_elems = (long long)p.Cr * Si;
-    const float* sbase = p.x + img0 * img_elems;
-    const long long remain = (p.x_elems - img0 * img_elems) * 4;
-    const unsigned nrec = remain > 0xFFFFFFFFLL ? 0xFFFFFFFFu : (unsigned)remain;
-    const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)sbase, 0, nrec, 0x00020000);
-
-    // ---- this thread's staged position ------------------------------------------------------------------
-    const long long pg = p0 + xpos;
-    const bool pvalid = pg < Ptot;
-    int bd = 0, bh = 0, bw = 0, img_b = 0;
-    if (pvalid) {
-        const long long n = pg / PS;
-        int rem = (int)(pg - n * PS);
-        const int qd = rem / Qhw;
-        rem -= qd * Qhw;
-        const int qh = rem / Qw;
-        const int qw = rem - qh * Qw;
-        bd = qd * p.ax[0].im + p.ax[0].c0[rd];
-        bh = qh * p.ax[1].im + p.ax[1].c0[rh];
-        bw = qw * p.ax[2].im + p.ax[2].c0[rw];
-        img_b = (int)((n - img0) * img_elems * 4);
-    }
-    const int sib = Si * 4;
-
-    // ---- weight rows this lane stages: output channel co -> (component, offset in component) -----------------
-    int w_a[WR], w_off[WR];
-    bool w_ok[WR];
-#pragma unroll
-    for (int j = 0; j < WR; ++j) {
-        const int ch = lane + 64 * j;
-        const int co = c0 + ch;
-        w_ok[j] = (ch < BC) && (co < p.Co);
-        const int cc = w_ok[j] ? co : 0;
-        w_a[j] = cc / p.OA;
-        w_off[j] = (cc - w_a[j] * p.OA) * (WT ? p.KK : p.RA * p.KK);
-    }
-
-    // ---- wave-uniform K trackers of the NEXT chunk to load: 16-channel block cb, tap (td, th, tw) ------------
-    int cb = cb_lo, td = 0, th = 0, tw = 0;
-
-    float xr[XG][4];
-    float wr[WR][4], wm[WR][4];
-
-    auto load_chunk = [&]() __attribute__((always_inline)) {
-        const int ci0 = cb * 16;
-        // X operand: one range check per tap, one select per element
-        const int id = bd - td * p.ax[0].ia;
-        const int ih = bh - th * p.ax[1].ia;
-        const int iw = bw - tw * p.ax[2].ia;
-        const bool ok = pvalid && ((unsigned)id < (unsigned)p.ax[0].in) && ((unsigned)ih < (unsigned)Hi) &&
-                        ((unsigned)iw < (unsigned)Wi);
-        const int tapb = img_b + ((id * Hi + ih) * Wi + iw) * 4;
-#pragma unroll
-        for (int j = 0; j < XG; ++j) {
-            const int g = xg0 + j * XSTEP;
-#pragma unroll
-            for (int s = 0; s < 4; ++s) {
-                const int ci = ci0 + g * 4 + s;
-                const unsigned off = (ok && ci < p.Cr) ? (unsigned)(tapb + ci * sib) : 0xFFFFFFFFu;
-                xr[j][s] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rsrc, off, 0, 0));
-            }
-        }
-        // W operand: k-group = wave.  Loads are unconditional (an unused element reads the component's first word);
-        // the sign / zero is a multiplier applied at the LDS store.
-        typedef const __attribute__((address_space(1))) float* gptr;
-        const int kidx = (kd0 + td * p.ax[0].kstep) * KHW + (kh0 + th * p.ax[1].kstep) * p.ax[2].K + kw0 +
-                         tw * p.ax[2].kstep;
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            const int ci = ci0 + wave * 4 + s;
-            const bool kin = ci < p.Cr;
-            const int cic = kin ? ci : 0;
-            const int qa = cic / p.RA;
-            const int cl = cic - qa * p.RA;
-            const int soff = (WT ? cl * p.OA * p.KK : cl * p.KK) + kidx;
-#pragma unroll
-            for (int j = 0; j < WR; ++j) {
-                bool zero, neg;
-                const int comp = WT ? hc_comp(p.A, qa, w_a[j], &zero, &neg) : hc_comp(p.A, w_a[j], qa, &zero, &neg);
-                const bool use = kin && w_ok[j] && !zero;
-                gptr base = (gptr)wptr_s[comp];
-                wr[j][s] = base[use ? soff + w_off[j] : 0];
-                wm[j][s] = use ? (neg ? -1.f : 1.f) : 0.f;
-            }
-        }
-        // advance: taps fastest (w, h, d), then the channel block
-        if (++tw >= ntw) {
-            tw = 0;
-            if (++th >= nth) {
-                th = 0;
-                if (++td >= ntd) { td = 0; ++cb; }
-            }
-        }
-    };
-    auto store_chunk = [&](int buf) __attribute__((always_inline)) {
-#pragma unroll
-        for (int j = 0; j < XG; ++j)
-            *reinterpret_cast<float4*>(&Xs[buf][xg0 + j * XSTEP][xpos][0]) = make_float4(xr[j][0], xr[j][1], xr[j][2], xr[j][3]);
-#pragma unroll
-        for (int j = 0; j < WR; ++j) {
-            const int ch = lane + 64 * j;
-            if (ch < BC)
-                *reinterpret_cast<float4*>(&Ws[buf][wave][ch][0]) =
-                    make_float4(wr[j][0] * wm[j][0], wr[j][1] * wm[j][1], wr[j][2] * wm[j][2], wr[j][3] * wm[j][3]);
-        }
-    };
-
-    floatx4 acc[PT][CT];
-#pragma unroll
-    for (int i = 0; i < PT; ++i)
-#pragma unroll
-        for (int j = 0; j < CT; ++j) acc[i][j] = (floatx4){0.f, 0.f, 0.f, 0.f};
-
-    const int fr = lane & 15;
-    const int fk = lane >> 4;
-
-    __syncthreads();               // wptr_s visible
-    if (nchunks > 0) {
-        load_chunk();
-        store_chunk(0);
-    }
-    __syncthreads();
-    for (int chunk = 0; chunk < nchunks; ++chunk) {
-        const int buf = chunk & 1;
-        if (chunk + 1 < nchunks) load_chunk();
-        float av[PT][4], bv[CT][4];
-#pragma unroll
-        for (int i = 0; i < PT; ++i) {
-            const float4 t = *reinterpret_cast<const float4*>(&Xs[buf][fk][wave * (PT * 16) + i * 16 + fr][0]);
-            av[i][0] = t.x; av[i][1] = t.y; av[i][2] = t.z; av[i][3] = t.w;
-        }
-#pragma unroll
-        for (int j = 0; j < CT; ++j) {
-            const float4 t = *reinterpret_cast<const float4*>(&Ws[buf][fk][j * 16 + fr][0]);
-            bv[j][0] = t.x; bv[j][1] = t.y; bv[j][2] = t.z; bv[j][3] = t.w;
-        }
-#pragma unroll
-        for (int s = 0; s < 4; ++s)
-#pragma unroll
-            for (int j = 0; j < CT; ++j)
-#pragma unroll
-                for (int i = 0; i < PT; ++i)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[i][s], bv[j][s], acc[i][j], 0, 0, 0);
-        if (chunk + 1 < nchunks) store_chunk(buf ^ 1);
-        __syncthreads();
-    }
-
-    // ---- epilogue: lane holds class positions (4 fk + r), r = 0..3, of channel fr of each 16x16 tile -------------
-    const int Ho = p.ax[1].out, Wo = p.ax[2].out;
-    const long long So = (long long)p.ax[0].out * Ho * Wo;
-    const int osd = p.ax[0].os, osh = p.ax[1].os, osw = p.ax[2].os;
-    const bool row4 = (Qw & 3) == 0;              // a lane's 4 positions lie in one class row
-    const bool vec = row4 && osw == 1 && (Wo & 3) == 0;
-#pragma unroll
-    for (int i = 0; i < PT; ++i) {
-        const long long pos = p0 + wave * (PT * 16) + i * 16 + fk * 4;
-        long long off[4];
-        bool ok[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const long long q = pos + r;
-            ok[r] = q < Ptot;
-            if (r == 0 || !row4) {
-                const long long n = ok[r] ? q / PS : 0;
-                int rem = (int)(q - n * PS);
-                const int qd = rem / Qhw;
-                rem -= qd * Qhw;
-                const int qh = rem / Qw;
-                const int qw = rem - qh * Qw;
-                off[r] = n * p.Co * So + ((long long)(rd + osd * qd) * Ho + rh + osh * qh) * Wo + rw + osw * qw;
-            } else {
-                off[r] = off[0] + r * osw;
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < CT; ++j) {
-            const int co = c0 + j * 16 + fr;
-            if (co >= p.Co) continue;
-            const float b = p.bias ? p.bias[co] : 0.f;
-            const floatx4 v = acc[i][j];
-            float* yc = p.y + co * So;
-            if (vec && ok[0]) {
-                *reinterpret_cast<float4*>(yc + off[0]) = make_float4(v[0] + b, v[1] + b, v[2] + b, v[3] + b);
-            } else {
-#pragma unroll
-                for (int r = 0; r < 4; ++r)
-                    if (ok[r]) yc[off[r]] = v[r] + b;
-            }
-        }
-    }
-}
+typedef PgP<3> C3P;
 
 template <int CT, int PT>
-__global__ __launch_bounds__(256) void hc_conv3d_fwd_kernel(const C3P p) { c3_gemm<CT, PT, false>(p); }
+__global__ __launch_bounds__(256) void hc_conv3d_fwd_kernel(const C3P p) { pg_gemm<CT, PT, false, 3>(p); }
 
 template <int CT, int PT>
-__global__ __launch_bounds__(256) void hc_conv3d_phase_kernel(const C3P p) { c3_gemm<CT, PT, true>(p); }
+__global__ __launch_bounds__(256) void hc_conv3d_phase_kernel(const C3P p) { pg_gemm<CT, PT, true, 3>(p); }
 
 // ------------------------------------------------------------------------------------------
 // weight gradient: G[co][c] = sum_pos dy[n][co][pos] * x[n][ci][pos*s - p + tap*d], c = ci*KK + tap
@@ -508,8 +236,6 @@ __global__ __launch_bounds__(256) void hc_conv3d_fold_kernel(const float* __rest
 // ------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------
-static int c3_gcd(int a, int b) { while (b) { const int t = a % b; a = b; b = t; } return a; }
-
 static long long vol3(const int v[3]) { return (long long)v[0] * v[1] * v[2]; }
 
 // descriptor checks shared by the convolution and the transposed convolution
@@ -522,7 +248,7 @@ static int c3_validate(const seld_conv3d_desc* d) {
     for (int i = 0; i < 3; ++i)
         if (d->in[i] <= 0 || d->k[i] <= 0 || d->stride[i] <= 0 || d->dil[i] <= 0 || d->pad[i] < 0) return SELD_EINVAL;
     for (int i = 0; i < 3; ++i)
-        if (d->stride[i] > C3_MAXS) return SELD_EUNSUPPORTED;          // phase tables
+        if (d->stride[i] > PG_MAXS) return SELD_EUNSUPPORTED;          // phase tables
     const long long KK = vol3(d->k);
     if (KK > 4096) return SELD_EUNSUPPORTED;
     // component tensors and one image of either operand are addressed with 32-bit offsets
@@ -560,10 +286,7 @@ static int c3_tconv_out(const seld_conv3d_desc* d, const int32_t op[3], int out[
 }
 
 // geometry of one GEMM / weight-gradient launch in convolution terms: x (Ci, in) -> y (Co, out)
-struct G3 {
-    int A, N, Ci, Co;
-    int in[3], out[3], k[3], s[3], p[3], d[3];
-};
+typedef PgGeom<3> G3;
 
 static G3 g3_of(const seld_conv3d_desc* d, const int out[3], bool mirror) {
     G3 g;
@@ -578,126 +301,30 @@ static G3 g3_of(const seld_conv3d_desc* d, const int out[3], bool mirror) {
     return g;
 }
 
-// forward map: one class, input index q*s - p + t*d
-static void c3_axis_fwd(C3Axis& a, int s, int pad, int dil, int K, int in, int out) {
-    a.in = in; a.out = out; a.K = K;
-    a.os = 1; a.im = s; a.kstep = 1; a.ia = -dil;
-    a.k0[0] = 0; a.n[0] = K; a.c0[0] = -pad; a.q[0] = out;
-}
-
-// stride-phase map of the transposed direction o = i*s - p + k*d (hc_conv_transpose.hip, tconv_axis)
-static void c3_axis_phase(C3Axis& a, int s, int pad, int dil, int K, int in, int out) {
-    const int g = c3_gcd(s, dil);
-    a.in = in; a.out = out; a.K = K;
-    a.os = s; a.im = 1; a.kstep = s / g; a.ia = dil / g;
-    for (int r = 0; r < s; ++r) {
-        int first = -1;
-        for (int k = 0; k < K && k < a.kstep; ++k) {
-            const int v = r + pad - k * dil;
-            if (((v % s) + s) % s == 0) { first = k; break; }
-        }
-        if (first < 0) {
-            a.k0[r] = 0; a.n[r] = 0; a.c0[r] = 0;
-        } else {
-            a.k0[r] = first;
-            a.n[r] = (K - 1 - first) / a.kstep + 1;
-            a.c0[r] = (r + pad - first * dil) / s;            // exact
-        }
-        a.q[r] = r < out ? (out - r + s - 1) / s : 0;
-    }
-}
-
-// phase == false: y (Co, out) = conv(x (Ci, in)), weights (Co/A, Ci/A, k).
-// phase == true : y (Co, out) = conv_transpose(x (Ci, in)), weights (Ci/A, Co/A, k).
-static void c3_fill(C3P& p, const G3& g, bool phase, const float* const w[8]) {
-    p.A = g.A; p.N = g.N; p.Cr = g.Ci; p.Co = g.Co;
-    p.RA = g.Ci / g.A; p.OA = g.Co / g.A;
-    p.KK = g.k[0] * g.k[1] * g.k[2];
-    for (int i = 0; i < 3; ++i) {
-        if (phase) c3_axis_phase(p.ax[i], g.s[i], g.p[i], g.d[i], g.k[i], g.in[i], g.out[i]);
-        else c3_axis_fwd(p.ax[i], g.s[i], g.p[i], g.d[i], g.k[i], g.in[i], g.out[i]);
-    }
-    p.nph = p.ax[0].os * p.ax[1].os * p.ax[2].os;
-    p.x_elems = (long long)g.N * g.Ci * vol3(g.in);
-    for (int i = 0; i < 8; ++i) p.w.p[i] = (w && i < g.A) ? w[i] : nullptr;
-}
-
-static long long c3_class_ps(const C3P& p, int ph) {
-    const int rw = ph % p.ax[2].os, rdh = ph / p.ax[2].os;
-    return (long long)p.ax[0].q[rdh / p.ax[1].os] * p.ax[1].q[rdh % p.ax[1].os] * p.ax[2].q[rw];
-}
-
-// the input images a 256-position tile can touch are addressed with 32-bit byte offsets from its first image
-static int c3_addressable(const C3P& p) {
-    long long min_ps = 1LL << 62;
-    for (int ph = 0; ph < p.nph; ++ph) {
-        const long long ps = c3_class_ps(p, ph);
-        if (ps > 0 && ps < min_ps) min_ps = ps;
-    }
-    const long long imgs = 256 / min_ps + 2;
-    const long long n = imgs < p.N ? imgs : p.N;
-    if (n * p.Cr * p.ax[0].in * p.ax[1].in * p.ax[2].in * 4 >= (1LL << 31)) return SELD_EUNSUPPORTED;
-    return SELD_OK;
-}
-
-struct C3Cfg { int ct, pt; };
-
-// tile choice as tconv_cfg (hc_conv_transpose.hip): fill >= 2 workgroups per CU, avoid padded channels, prefer wide tiles.
-// {4, 1} serves few positions x 64 channels (a strided layer's forward): {12, 1} would pad two thirds of its channels.
-static C3Cfg c3_cfg(const C3P& p) {
-    static const C3Cfg cand[] = {{12, 1}, {4, 4}, {4, 1}, {2, 4}, {1, 4}};
-    static const double pref[] = {1.00, 0.90, 0.60, 0.45, 0.30};
-    long long P = 0;
-    for (int ph = 0; ph < p.nph; ++ph) P += (long long)p.N * c3_class_ps(p, ph);
-    double best = -1.0;
-    C3Cfg pick = cand[1];
-    for (int i = 0; i < 5; ++i) {
-        const int bc = cand[i].ct * 16, bp = cand[i].pt * 64;
-        const long long cb = (p.Co + bc - 1) / bc;
-        const long long wgs = ((P + bp - 1) / bp) * cb;
-        const double fill = wgs >= 512 ? 1.0 : (double)wgs / 512.0;
-        const double use = (double)p.Co / (double)(cb * bc);
-        const double score = fill * use * pref[i];
-        if (score > best) { best = score; pick = cand[i]; }
-    }
-    return pick;
-}
-
-template <int CT, int PT>
-static int c3_launch(const C3P& p, bool phase, hipStream_t st) {
-    constexpr int BC = CT * 16, BP = PT * 64;
-    long long maxp = 0;
-    for (int ph = 0; ph < p.nph; ++ph) {
-        const long long pp = (long long)p.N * c3_class_ps(p, ph);
-        if (pp > maxp) maxp = pp;
-    }
-    const long long tiles = (maxp + BP - 1) / BP;
-    if (tiles * p.nph >= (1LL << 31)) return SELD_EUNSUPPORTED;
-    dim3 grid((unsigned)(tiles * p.nph), (unsigned)((p.Co + BC - 1) / BC), 1);
-    if (phase) hipLaunchKernelGGL((hc_conv3d_phase_kernel<CT, PT>), grid, dim3(256), 0, st, p);
-    else hipLaunchKernelGGL((hc_conv3d_fwd_kernel<CT, PT>), grid, dim3(256), 0, st, p);
-    return check_launch();
+// the kernel of tile c: the five tiles of the 3-D tile choice, forward or phase map
+static auto c3_kernel(PgCfg c, bool phase) -> void (*)(const C3P) {
+    if (c.ct == 12) return phase ? hc_conv3d_phase_kernel<12, 1> : hc_conv3d_fwd_kernel<12, 1>;
+    if (c.ct == 4 && c.pt == 1) return phase ? hc_conv3d_phase_kernel<4, 1> : hc_conv3d_fwd_kernel<4, 1>;
+    if (c.ct == 2) return phase ? hc_conv3d_phase_kernel<2, 4> : hc_conv3d_fwd_kernel<2, 4>;
+    if (c.ct == 1) return phase ? hc_conv3d_phase_kernel<1, 4> : hc_conv3d_fwd_kernel<1, 4>;
+    return phase ? hc_conv3d_phase_kernel<4, 4> : hc_conv3d_fwd_kernel<4, 4>;
 }
 
 // one GEMM launch: every check before the launch, nothing written on refusal
 static int c3_gemm_run(const G3& g, bool phase, const float* x, const float* const w[8], const float* bias, float* y,
                        hipStream_t st, char* label, int buflen) {
     C3P p{};
-    c3_fill(p, g, phase, w);
-    int rc = c3_addressable(p);
+    pg_fill(p, g, phase, w);
+    int rc = pg_addressable(p);
     if (rc) return rc;
-    const C3Cfg c = c3_cfg(p);
+    const PgCfg c = pg_cfg(p, true);
     if (label) {
         snprintf(label, buflen, "%s<%d, %d>", phase ? "hc_conv3d_phase_kernel" : "hc_conv3d_fwd_kernel", c.ct, c.pt);
         return SELD_OK;
     }
     if (!x || !w || !y) return SELD_EINVAL;
     p.x = x; p.bias = bias; p.y = y;
-    if (c.ct == 12) return c3_launch<12, 1>(p, phase, st);
-    if (c.ct == 4 && c.pt == 1) return c3_launch<4, 1>(p, phase, st);
-    if (c.ct == 2) return c3_launch<2, 4>(p, phase, st);
-    if (c.ct == 1) return c3_launch<1, 4>(p, phase, st);
-    return c3_launch<4, 4>(p, phase, st);
+    return pg_launch(c3_kernel(c, phase), c, p, st);
 }
 
 // weight-gradient plan: position splits so that the grid fills the GPU, bias blocks likewise; workspace floats
