@@ -33,8 +33,9 @@ struct ConvP {
     const float* addend;
     float* stats;
     // A second convolution of the SAME geometry in the same launch (hc_conv_vec_kernel only; nslots = 2).
-    //   forward : same src, blockIdx.z selects {w, bias, dst, addend, stats, epilogue} or the *2 set
-    //             (filter | gate and skip | residual of a residual block read the same tensor, model.py:121-132)
+    //   forward : same src, two K passes in one workgroup: the first writes {w, bias, dst, addend, stats, epilogue}, the
+    //             second the *2 set (filter | gate and skip | residual of a residual block read the same tensor,
+    //             model.py:121-132)
     //   dgrad   : dst = dgrad(src, w) + dgrad(src2, w2): the K loop runs over both sources in turn
     int nslots;
     int epilogue2;

@@ -25,8 +25,7 @@
 //     compare, 3-input address add, select of an out-of-range offset that the hardware zero-fills);
 //   * per-row decodes are hoisted out of the K loop.
 // (CT, PT) is picked per problem so that small layers (B*T = 16k positions) still fill 256 CUs.
-#include <type_traits>
-#include "hc_common.h"
+#include "hc_conv_tile.h"
 
 namespace seld {
 
@@ -52,8 +51,9 @@ __global__ __launch_bounds__(256) void hc_conv_kernel(const ConvP p) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int xpos = tid & (BP - 1);
     const int xg0 = __builtin_amdgcn_readfirstlane(tid / BP);
-    const int c0 = blockIdx.y * BC;
-    const long long p0 = (long long)blockIdx.x * BP;
+    const ConvOrigin<BP> og = conv_origin<BC, BP>(p);
+    const int c0 = og.c0;
+    const long long p0 = og.p0, img0 = og.img0;
 
     const int KH = KH_T ? KH_T : p.KH;
     const int KW = KW_T ? KW_T : p.KW;
@@ -67,29 +67,11 @@ __global__ __launch_bounds__(256) void hc_conv_kernel(const ConvP p) {
     if (tid < 8) wptr_s[tid] = p.w.p[tid];
 
     // ---- buffer descriptor of the streamed operand, based at the first image this tile touches -----
-    const long long img0 = p0 / p.dstS;
     const long long img_elems = (long long)p.Csrc * p.srcS;
     const float* sbase = p.src + img0 * img_elems;
     const long long remain = (p.src_elems - img0 * img_elems) * 4;
     const unsigned nrec = remain > 0xFFFFFFFFLL ? 0xFFFFFFFFu : (unsigned)remain;
     const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)sbase, 0, nrec, 0x00020000);
-
-    // Position -> (image relative to img0, offset in image) without per-lane 64-bit division: the tile
-    // starts at (img0, rem0) (scalar), a lane adds its local index and wraps (32-bit divide only when an
-    // image is shorter than the tile).
-    const int rem0 = (int)(p0 - img0 * p.dstS);
-    auto decode = [&](int local, int* dimg, int* rem) __attribute__((always_inline)) {
-        int r = rem0 + local;
-        int di = 0;
-        if (p.dstS >= BP) {
-            if (r >= p.dstS) { r -= p.dstS; di = 1; }
-        } else {
-            di = r / p.dstS;
-            r -= di * p.dstS;
-        }
-        *dimg = di;
-        *rem = r;
-    };
 
     // ---- per-thread position decode for the X stage (one position per thread) ----------------------
     const long long pg = p0 + xpos;
@@ -98,7 +80,7 @@ __global__ __launch_bounds__(256) void hc_conv_kernel(const ConvP p) {
     int img_b = 0;                                 // byte offset of this position's image from sbase
     if (pvalid) {
         int dimg, rem;
-        decode(xpos, &dimg, &rem);
+        og.decode(xpos, &dimg, &rem);
         const int oh = rem / p.dstW;
         const int ow = rem - oh * p.dstW;
         base_h = oh * p.SMh + p.OFFh;
@@ -112,21 +94,13 @@ __global__ __launch_bounds__(256) void hc_conv_kernel(const ConvP p) {
     const bool hok0 = pvalid && ((unsigned)base_h < (unsigned)p.srcH);
     const int rowb0 = img_b + base_h * srcWb;
 
-    // ---- channel tile of this workgroup -----------------------------------------------------------
-    // Dual quaternion: the first half of the channels (primal part) sees a structurally-zero K half.  Tiles are
-    // contiguous channel ranges.
-    const int half_c = p.Cdst >> 1;
-    const int half_k = p.Ktot >> 1;
-    const bool halves_aligned = (p.skip_mode != 0) && (half_k % 16 == 0) && (half_c % 16 == 0);
-    auto chan_of = [&](int t) __attribute__((always_inline)) { return c0 + t; };
-
     // ---- per-lane decode of the weight rows this lane stages ---------------------------------------
     int w_a[WR], w_off[WR];        // fwd: a = output component p, off = o*CK ; dgrad: a = input component q, off = c*KK
     bool w_ok[WR];
 #pragma unroll
     for (int j = 0; j < WR; ++j) {
         const int ch = lane + 64 * j;
-        const int chg = chan_of(ch);
+        const int chg = c0 + ch;
         w_ok[j] = (ch < BC) && (chg < p.Cdst);
         const int cc = w_ok[j] ? chg : 0;
         if (MODE == MODE_FWD) {
@@ -139,15 +113,9 @@ __global__ __launch_bounds__(256) void hc_conv_kernel(const ConvP p) {
     }
 
     // ---- K range of this workgroup (dual-quaternion zero quadrant) ----------------------------------
-    int kbeg = 0, kend = p.Ktot;
-    if (halves_aligned) {
-        if (p.skip_mode == 1 && c0 + BC <= half_c) kend = half_k;      // all channels primal
-        if (p.skip_mode == 2 && c0 >= half_c) kbeg = half_k;           // all channels dual
-    }
+    const ConvKRange kr = conv_k_range<BC, CT, 16>(p, c0);
+    const int kbeg = kr.kbeg, kend = kr.kend;
     const int nchunks = (kend - kbeg + 15) >> 4;
-    // workgroup whose lower tiles are primal and upper tiles dual: half of its tiles skip the zero quadrant's
-    // chunks (any other straddle just multiplies by the staged zeros)
-    const bool mixed_wg = halves_aligned && (CT % 2 == 0) && (c0 + BC / 2 == half_c);
 
     // ---- scalar trackers of this wave's weight k-group start kw = kbeg + 16*chunk + 4*wave ----------
     // fwd  : kw = kq*CK + kl           (input component, local index)
@@ -291,10 +259,7 @@ __global__ __launch_bounds__(256) void hc_conv_kernel(const ConvP p) {
     };
 
     floatx4 acc[PT][CT];
-#pragma unroll
-    for (int i = 0; i < PT; ++i)
-#pragma unroll
-        for (int j = 0; j < CT; ++j) acc[i][j] = (floatx4){0.f, 0.f, 0.f, 0.f};
+    conv_zero_acc(acc);
 
     const int fr = lane & 15;      // row / col inside a 16x16 tile
     const int fk = lane >> 4;      // k group of this lane
@@ -306,11 +271,9 @@ __global__ __launch_bounds__(256) void hc_conv_kernel(const ConvP p) {
     }
     __syncthreads();
 
-    // The K loop is run as up to two consecutive loops, each with a compile-time set of channel tiles
-    // [J0, J1): a workgroup that straddles the primal/dual boundary computes all of its tiles over one K half
-    // and only half of them over the other (the zero quadrant).  Each loop body is straight-line code (no
-    // per-tile branches, accumulators stay in place).  s is outermost so that consecutive MFMAs hit different
-    // accumulators (16x16x4 f32: 40-cycle dependent latency against a 32-cycle issue interval).
+    // One loop over chunks [cbeg, cend) with the compile-time channel tiles [J0, J1) (conv_run_k_range).  s is outermost so
+    // that consecutive MFMAs hit different accumulators (16x16x4 f32: 40-cycle dependent latency against a 32-cycle issue
+    // interval).
     auto run_chunks = [&](int cbeg, int cend, auto j0c, auto j1c) __attribute__((always_inline)) {
         constexpr int J0 = decltype(j0c)::value, J1 = decltype(j1c)::value;
         for (int chunk = cbeg; chunk < cend; ++chunk) {
@@ -338,113 +301,11 @@ __global__ __launch_bounds__(256) void hc_conv_kernel(const ConvP p) {
             __syncthreads();
         }
     };
-    using IC0 = std::integral_constant<int, 0>;
-    using ICH = std::integral_constant<int, CT / 2>;
-    using ICT = std::integral_constant<int, CT>;
-    if (mixed_wg) {
-        const int csplit = (half_k - kbeg) >> 4;          // first chunk of the upper K half
-        if (p.skip_mode == 1) {                           // forward: primal tiles (lower half) see zeros there
-            run_chunks(0, csplit, IC0{}, ICT{});
-            run_chunks(csplit, nchunks, ICH{}, ICT{});
-        } else {                                          // dgrad: dual tiles (upper half) see zeros in the lower K half
-            run_chunks(0, csplit, IC0{}, ICH{});
-            run_chunks(csplit, nchunks, IC0{}, ICT{});
-        }
-    } else {
-        run_chunks(0, nchunks, IC0{}, ICT{});
-    }
+    conv_run_k_range<CT, MODE>(kr, p.skip_mode, nchunks, run_chunks);
 
-
-    // ---- epilogue: lane holds positions prow..prow+3 (regs) of channel ch -----------------------------
-    const bool vec_ok = (p.dstS % 4 == 0);
-    // element offset of (first image of the tile, channel 0, position 0) and, per position tile i, of this
-    // lane's 4 positions relative to it
-    float* const dst0 = p.dst + (size_t)img0 * p.Cdst * p.dstS;
-    const float* const add0 = p.addend ? p.addend + (size_t)img0 * p.Cdst * p.dstS : nullptr;
-    int poff[PT];
-#pragma unroll
-    for (int i = 0; i < PT; ++i) {
-        int dimg, rem;
-        decode(wave * (PT * 16) + i * 16 + fk * 4, &dimg, &rem);
-        poff[i] = dimg * p.Cdst * p.dstS + rem;
-    }
-#pragma unroll
-    for (int j = 0; j < CT; ++j) {
-        const int ch = chan_of(j * 16 + fr);
-        const bool chok = ch < p.Cdst;
-        const float bvv = (chok && p.bias) ? p.bias[ch] : 0.0f;
-        float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-        for (int i = 0; i < PT; ++i) {
-            const long long pos = p0 + wave * (PT * 16) + i * 16 + fk * 4;
-            floatx4 v = acc[i][j];
-            if (chok && pos < p.Ptot) {
-                if (vec_ok) {
-                    const size_t off = (size_t)(poff[i] + ch * p.dstS);
-                    float4 o = make_float4(v[0] + bvv, v[1] + bvv, v[2] + bvv, v[3] + bvv);
-                    if (p.epilogue & SELD_EPI_ADD) {
-                        float4 ad = *reinterpret_cast<const float4*>(add0 + off);
-                        o.x += ad.x; o.y += ad.y; o.z += ad.z; o.w += ad.w;
-                    }
-                    if (p.epilogue & SELD_EPI_ACCUMULATE) {
-                        float4 old = *reinterpret_cast<const float4*>(dst0 + off);
-                        o.x += old.x; o.y += old.y; o.z += old.z; o.w += old.w;
-                    }
-                    *reinterpret_cast<float4*>(dst0 + off) = o;
-                    s1 += o.x + o.y + o.z + o.w;
-                    s2 += o.x * o.x + o.y * o.y + o.z * o.z + o.w * o.w;
-                } else {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        long long pr = pos + r;
-                        if (pr < p.Ptot) {
-                            long long img = pr / p.dstS;
-                            int rem = (int)(pr - img * p.dstS);
-                            size_t off = ((size_t)img * p.Cdst + ch) * p.dstS + rem;
-                            float o = v[r] + bvv;
-                            if (p.epilogue & SELD_EPI_ADD) o += p.addend[off];
-                            if (p.epilogue & SELD_EPI_ACCUMULATE) o += p.dst[off];
-                            p.dst[off] = o;
-                            s1 += o;
-                            s2 += o * o;
-                        }
-                    }
-                }
-            }
-        }
-        if (p.epilogue & SELD_EPI_STATS) {
-            // lanes fr, fr+16, fr+32, fr+48 hold the same channel; the 4 waves hold different positions
-            s1 += __shfl_xor(s1, 16, 64);
-            s1 += __shfl_xor(s1, 32, 64);
-            s2 += __shfl_xor(s2, 16, 64);
-            s2 += __shfl_xor(s2, 32, 64);
-            if (fk == 0) {
-                float* redbuf = &Xs[0][0][0][0];       // the K loop is over: the staging buffers are free
-                redbuf[(wave * BC + j * 16 + fr) * 2 + 0] = s1;
-                redbuf[(wave * BC + j * 16 + fr) * 2 + 1] = s2;
-            }
-        }
-    }
-    if (p.epilogue & SELD_EPI_STATS) {
-        // one atomic pair per channel per workgroup, spread over SELD_STATS_REPLICAS rows so that the
-        // thousands of workgroups of a layer do not serialise on 2*C addresses
-        __syncthreads();
-        const float* redbuf = &Xs[0][0][0][0];
-        float* rep = p.stats + (size_t)(blockIdx.x % SELD_STATS_REPLICAS) * 2 * p.Cdst;
-        for (int t = tid; t < BC; t += 256) {
-            const int ch = chan_of(t);
-            if (ch < p.Cdst) {
-                float a1 = 0.f, a2 = 0.f;
-#pragma unroll
-                for (int wv = 0; wv < 4; ++wv) {
-                    a1 += redbuf[(wv * BC + t) * 2 + 0];
-                    a2 += redbuf[(wv * BC + t) * 2 + 1];
-                }
-                atomicAdd(rep + ch, a1);
-                atomicAdd(rep + p.Cdst + ch, a2);
-            }
-        }
-    }
+    // the K loop is over: the staging buffers are free for the statistics
+    static_assert(sizeof(Xs) >= 4 * BC * 2 * sizeof(float), "statistics scratch fits the X staging buffers");
+    conv_epilogue<CT, PT, true>(p, og, conv_out(p, 0), acc, &Xs[0][0][0][0], tid);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -567,11 +428,33 @@ static int run_conv(const ConvP& p, hipStream_t st, bool allow_smallk = true) {
     return check_launch();
 }
 
+// The component pointers of a weight set (none: w == nullptr) / of a transposed-weight workspace
+static WPtrs weight_ptrs(const seld_conv_desc* d, const float* const w[8]) {
+    WPtrs r{};
+    for (int i = 0; i < d->algebra; ++i) r.p[i] = w ? w[i] : nullptr;
+    return r;
+}
+static WPtrs workspace_ptrs(const seld_conv_desc* d, const void* workspace) {
+    const size_t per = (size_t)(d->Cout / d->algebra) * (d->Cin / d->algebra) * d->k[0] * d->k[1];
+    WPtrs r{};
+    for (int i = 0; i < d->algebra; ++i) r.p[i] = (const float*)workspace + i * per;
+    return r;
+}
+
+// out <- Wt[comp][c][o][k] of the weight set w (seld_hc_conv_bwd_data_workspace(d) bytes)
+static int transpose_weights(const seld_conv_desc* d, const WPtrs& w, void* out, hipStream_t st) {
+    const int OA = d->Cout / d->algebra, IA = d->Cin / d->algebra, KK = d->k[0] * d->k[1];
+    const int per = OA * IA * KK;
+    hipLaunchKernelGGL(hc_transpose_w_kernel, dim3((per * d->algebra + 255) / 256), dim3(256), 0, st, w, d->algebra, OA, IA, KK,
+                       (float*)out);
+    return check_launch();
+}
+
 static void fill_common(ConvP& p, const seld_conv_desc* d, const float* const w[8]) {
     p.algebra = d->algebra;
     p.KH = d->k[0]; p.KW = d->k[1];
     p.OA = d->Cout / d->algebra; p.IA = d->Cin / d->algebra;
-    for (int i = 0; i < 8; ++i) p.w.p[i] = (w && i < d->algebra) ? w[i] : nullptr;
+    p.w = weight_ptrs(d, w);
 }
 
 static void fill_fwd(ConvP& p, const seld_conv_desc* d, const float* const w[8], const int o[2]) {
@@ -602,6 +485,20 @@ static void fill_dgrad(ConvP& p, const seld_conv_desc* d, const float* const w[8
     p.src_elems = (long long)d->N * p.Csrc * p.srcS;
     p.skip_mode = (d->algebra == 8) ? 2 : 0;
     p.epilogue = 0;
+}
+
+// What every data-gradient entry point does first: validate, the output shape, the caller's pointers (args_ok), the 32-bit
+// addressing limit of one dy image, and p <- dx = dgrad(dy, .) with no weights yet.
+static int dgrad_begin(ConvP& p, const seld_conv_desc* d, bool args_ok, const float* dy, float* dx) {
+    int rc = hc_validate(d);
+    if (rc) return rc;
+    int o[2];
+    hc_out_shape(d, o);
+    if (o[0] <= 0 || o[1] <= 0 || !args_ok) return SELD_EINVAL;
+    if ((long long)d->Cout * o[0] * o[1] >= (1LL << 28)) return SELD_EUNSUPPORTED;
+    fill_dgrad(p, d, nullptr, o);
+    p.src = dy; p.bias = nullptr; p.dst = dx;
+    return SELD_OK;
 }
 
 }  // namespace seld
@@ -649,25 +546,15 @@ extern "C" int seld_hc_conv_bwd_data(const seld_conv_desc* d, const float* dy, c
 
 extern "C" int seld_hc_conv_bwd_data_ex(const seld_conv_desc* d, const float* dy, const float* const w[8],
                                         float* dx, void* workspace, size_t workspace_bytes, void* stream) {
-    int rc = hc_validate(d);
-    if (rc) return rc;
-    int o[2];
-    hc_out_shape(d, o);
-    if (o[0] <= 0 || o[1] <= 0 || !dy || !w || !dx) return SELD_EINVAL;
-    if ((long long)d->Cout * o[0] * o[1] >= (1LL << 28)) return SELD_EUNSUPPORTED;
     ConvP p{};
-    fill_dgrad(p, d, w, o);
-    p.src = dy; p.bias = nullptr; p.dst = dx;
-    const size_t need = seld_hc_conv_bwd_data_workspace(d);
-    if (workspace && workspace_bytes >= need) {
+    int rc = dgrad_begin(p, d, dy && w && dx, dy, dx);
+    if (rc) return rc;
+    p.w = weight_ptrs(d, w);
+    if (workspace && workspace_bytes >= seld_hc_conv_bwd_data_workspace(d)) {
         // fast path: transposed component tensors in the workspace, staged with 16-byte loads like the forward
-        const int per = p.OA * p.IA * p.KH * p.KW;
-        float* wt = (float*)workspace;
-        hipLaunchKernelGGL(hc_transpose_w_kernel, dim3((per * d->algebra + 255) / 256), dim3(256), 0, (hipStream_t)stream,
-                           p.w, d->algebra, p.OA, p.IA, p.KH * p.KW, wt);
-        rc = check_launch();
+        rc = transpose_weights(d, p.w, workspace, (hipStream_t)stream);
         if (rc) return rc;
-        for (int i = 0; i < d->algebra; ++i) p.w.p[i] = wt + (size_t)i * per;
+        p.w = workspace_ptrs(d, workspace);
         p.wt = 1;
     }
     return run_conv(p, (hipStream_t)stream);
@@ -681,28 +568,15 @@ extern "C" int seld_hc_conv_transpose_weights(const seld_conv_desc* d, const flo
     int rc = hc_validate(d);
     if (rc) return rc;
     if (!w || !workspace || workspace_bytes < seld_hc_conv_bwd_data_workspace(d)) return SELD_EINVAL;
-    WPtrs src{};
-    for (int i = 0; i < 8; ++i) src.p[i] = (i < d->algebra) ? w[i] : nullptr;
-    const int OA = d->Cout / d->algebra, IA = d->Cin / d->algebra, KK = d->k[0] * d->k[1];
-    const int per = OA * IA * KK;
-    hipLaunchKernelGGL(hc_transpose_w_kernel, dim3((per * d->algebra + 255) / 256), dim3(256), 0, (hipStream_t)stream,
-                       src, d->algebra, OA, IA, KK, (float*)workspace);
-    return check_launch();
+    return transpose_weights(d, weight_ptrs(d, w), workspace, (hipStream_t)stream);
 }
 
 extern "C" int seld_hc_conv_bwd_data_wt(const seld_conv_desc* d, const float* dy, const void* wt_workspace, float* dx,
                                         void* stream) {
-    int rc = hc_validate(d);
-    if (rc) return rc;
-    int o[2];
-    hc_out_shape(d, o);
-    if (o[0] <= 0 || o[1] <= 0 || !dy || !wt_workspace || !dx) return SELD_EINVAL;
-    if ((long long)d->Cout * o[0] * o[1] >= (1LL << 28)) return SELD_EUNSUPPORTED;
     ConvP p{};
-    fill_dgrad(p, d, nullptr, o);
-    p.src = dy; p.bias = nullptr; p.dst = dx;
-    const int per = p.OA * p.IA * p.KH * p.KW;
-    for (int i = 0; i < d->algebra; ++i) p.w.p[i] = (const float*)wt_workspace + (size_t)i * per;
+    int rc = dgrad_begin(p, d, dy && wt_workspace && dx, dy, dx);
+    if (rc) return rc;
+    p.w = workspace_ptrs(d, wt_workspace);
     p.wt = 1;
     return run_conv(p, (hipStream_t)stream);
 }
@@ -760,7 +634,7 @@ extern "C" int seld_hc_conv_pair_fwd(const seld_conv_desc* d, const float* x, co
     fill_fwd(p, d, wA, o);
     p.epilogue = epilogueA; p.src = x; p.bias = biasA; p.dst = yA; p.addend = addendA; p.stats = statsA;
     p.nslots = 2;
-    for (int i = 0; i < 8; ++i) p.w2.p[i] = (i < d->algebra) ? wB[i] : nullptr;
+    p.w2 = weight_ptrs(d, wB);
     p.epilogue2 = epilogueB; p.src2 = x; p.bias2 = biasB; p.dst2 = yB; p.addend2 = addendB; p.stats2 = statsB;
     rc = run_conv(p, (hipStream_t)stream, false);
     if (rc != SELD_EUNSUPPORTED) return rc;
@@ -773,19 +647,12 @@ extern "C" int seld_hc_conv_pair_fwd(const seld_conv_desc* d, const float* x, co
 extern "C" int seld_hc_conv_pair_bwd_data_wt(const seld_conv_desc* d, const float* dyA, const float* dyB,
                                              const void* wtA, const void* wtB, float* dx, void* stream) {
     if (!seld_hc_conv_pair_supported(d, 1)) return SELD_EUNSUPPORTED;
-    if (!dyA || !dyB || !wtA || !wtB || !dx) return SELD_EINVAL;
-    int o[2];
-    hc_out_shape(d, o);
-    if ((long long)d->Cout * o[0] * o[1] >= (1LL << 28)) return SELD_EUNSUPPORTED;
     ConvP p{};
-    fill_dgrad(p, d, nullptr, o);
-    p.src = dyA; p.bias = nullptr; p.dst = dx;
+    int rc = dgrad_begin(p, d, dyA && dyB && wtA && wtB && dx, dyA, dx);
+    if (rc) return rc;
     p.nslots = 2; p.src2 = dyB;
-    const int per = p.OA * p.IA * p.KH * p.KW;
-    for (int i = 0; i < d->algebra; ++i) {
-        p.w.p[i] = (const float*)wtA + (size_t)i * per;
-        p.w2.p[i] = (const float*)wtB + (size_t)i * per;
-    }
+    p.w = workspace_ptrs(d, wtA);
+    p.w2 = workspace_ptrs(d, wtB);
     p.wt = 1;
     return run_conv(p, (hipStream_t)stream);
 }
@@ -795,28 +662,16 @@ extern "C" int seld_hc_conv_pair_bwd_data(const seld_conv_desc* d, const float* 
                                           const float* const wA[8], const float* const wB[8], float* dx,
                                           void* workspace, size_t workspace_bytes, void* stream) {
     if (!seld_hc_conv_pair_supported(d, 1)) return SELD_EUNSUPPORTED;
-    if (!dyA || !dyB || !wA || !wB || !dx) return SELD_EINVAL;
     const size_t need = seld_hc_conv_bwd_data_workspace(d);
-    if (!workspace || workspace_bytes < 2 * need) return SELD_EINVAL;
-    int o[2];
-    hc_out_shape(d, o);
-    if ((long long)d->Cout * o[0] * o[1] >= (1LL << 28)) return SELD_EUNSUPPORTED;
     ConvP p{};
-    fill_dgrad(p, d, wA, o);
-    p.src = dyA; p.bias = nullptr; p.dst = dx;
+    int rc = dgrad_begin(p, d, dyA && dyB && wA && wB && dx && workspace && workspace_bytes >= 2 * need, dyA, dx);
+    if (rc) return rc;
     p.nslots = 2; p.src2 = dyB;
-    const int per = p.OA * p.IA * p.KH * p.KW;
-    float* wt = (float*)workspace;
-    for (int sl = 0; sl < 2; ++sl) {
-        WPtrs src{};
-        for (int i = 0; i < 8; ++i) src.p[i] = (i < d->algebra) ? (sl ? wB[i] : wA[i]) : nullptr;
-        float* out = wt + (size_t)sl * d->algebra * per;
-        hipLaunchKernelGGL(hc_transpose_w_kernel, dim3((per * d->algebra + 255) / 256), dim3(256), 0, (hipStream_t)stream,
-                           src, d->algebra, p.OA, p.IA, p.KH * p.KW, out);
-        int rc = check_launch();
-        if (rc) return rc;
-        for (int i = 0; i < d->algebra; ++i) (sl ? p.w2 : p.w).p[i] = out + (size_t)i * per;
-    }
+    void* const wtB = (char*)workspace + need;
+    if ((rc = transpose_weights(d, weight_ptrs(d, wA), workspace, (hipStream_t)stream)) != SELD_OK) return rc;
+    if ((rc = transpose_weights(d, weight_ptrs(d, wB), wtB, (hipStream_t)stream)) != SELD_OK) return rc;
+    p.w = workspace_ptrs(d, workspace);
+    p.w2 = workspace_ptrs(d, wtB);
     p.wt = 1;
     return run_conv(p, (hipStream_t)stream);
 }

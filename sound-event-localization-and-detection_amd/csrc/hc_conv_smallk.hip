@@ -3,24 +3,25 @@
 // For `cnn.0` (8 -> 192 channels, 3x3, 52 MB and 1.36 GFLOP per sample, model.py:273-274) the reduction is
 // only 72 deep, so the general kernel's K loop is all prologue: it ran latency-bound at ~1.1 TB/s while the
 // layer's roof is the 1.6 GB output write.  This variant is persistent and weight-stationary:
-//   * one 8-wave workgroup per CU keeps the WHOLE expanded, signed weight tile [K/4][Cout][4] in LDS (55 KB)
-//     for its lifetime -- the Hamilton assembly happens once per workgroup, not once per tile;
-//   * it walks 128-position tiles; the im2col image of tile t+1 (18 KB) is gathered with buffer loads
-//     (hardware zero-fill for the halo) into registers while tile t is multiplied, then dropped into the
-//     other half of a double-buffered LDS image: one barrier per tile;
+//   * two 4-wave workgroups per CU each keep the WHOLE expanded, signed weight tile [K/4][Cout][4] in LDS (55 KB)
+//     for their lifetime -- the Hamilton assembly happens once per workgroup, not once per tile;
+//   * a workgroup walks 64-position tiles; the im2col image of tile t+1 (18 KB) is gathered with buffer loads
+//     (hardware zero-fill for the halo) into registers while tile t is multiplied, then dropped into the one
+//     LDS image between two barriers;
 //   * MFMA granularity is one k-group (4 taps) per v_mfma_f32_16x16x4_f32 with ds_read_b32 operands, so the
 //     72-deep reduction costs exactly 18 MFMAs and the primal output channels stop after the 9 groups that
 //     are not structurally zero (162 instead of 240 MFMAs per 16 x 192 output tile);
 //   * each lane stores 4 consecutive positions of a channel (16-byte stores); BatchNorm statistics are kept in
 //     registers across tiles and leave the workgroup as ONE set of atomics.
-#include "hc_common.h"
-#include <type_traits>
+#include "hc_conv_tile.h"
 
 namespace seld {
 
-// Waves per workgroup: SK_NW = 4 is the one instantiation.  4-wave workgroups, two per CU (each with its own copy of
+// Four waves per workgroup, 16 positions of a tile each.  4-wave workgroups, two per CU (each with its own copy of
 // the weights in LDS), run out of phase with each other, so one workgroup's stores / gathers hide under the other's MFMAs;
 // an 8-wave workgroup per CU kept its two waves per SIMD in lock-step and measured slower.
+constexpr int SK_TP = 64, SK_NT = 256;         // positions per tile, threads per workgroup
+
 // Workgroup barrier that orders LDS traffic only.  __syncthreads() is a workgroup-scope fence over ALL address spaces: on
 // gfx9 it waits vmcnt(0), i.e. for the write acknowledgement of every global store the wave has in flight -- in a loop
 // that stores 12 KB per wave per tile that wait was a third of the kernel.  The image in LDS is the only data the waves
@@ -29,34 +30,29 @@ __device__ __forceinline__ void lds_barrier() {
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
 }
 
-template <int NW> struct SkGeom { static constexpr int TP = NW * 16, NT = NW * 64; };
-
 // NG_T / NGP_T: k-group counts known at compile time (0 = take the run-time arguments).  With constants the two MFMA loops
 // unroll completely and the compiler hoists the LDS operand reads of later groups above the MFMAs of earlier ones; as
 // run-time loops every group started with an exposed LDS round trip (the MFMA pipe sat idle for a third of the loop).
-template <int CT, int KH_T, int KW_T, int SK_NW, int NG_T, int NGP_T>
-__global__ __launch_bounds__(SK_NW * 64, (SK_NW == 8 && NG_T) ? 4 : 1) void hc_conv_smallk_kernel(const ConvP p, int NG_arg, int NGP_arg, long long ntiles) {
+template <int CT, int KH_T, int KW_T, int NG_T, int NGP_T>
+__global__ __launch_bounds__(SK_NT, 1) void hc_conv_smallk_kernel(const ConvP p, int NG_arg, int NGP_arg, long long ntiles) {
     const int NG = NG_T ? NG_T : NG_arg;
     const int NGP = NG_T ? NGP_T : NGP_arg;
     constexpr int BC = CT * 16;
-    constexpr int SK_TP = SkGeom<SK_NW>::TP, SK_NT = SkGeom<SK_NW>::NT;
-    // SPLIT (dual quaternion first layer, 4 waves): a wave owns 32 positions x (CT/4 primal + CT/4 dual) channel tiles instead
+    // SPLIT (dual quaternion first layer): a wave owns 32 positions x (CT/4 primal + CT/4 dual) channel tiles instead
     // of 16 positions x all CT tiles.  Same 12 accumulators and MFMA count, but (a) the two 16-position halves of a
     // channel are stored back to back by ONE wave, completing 128-byte lines (with 16 positions per wave every store
     // instruction left sixteen 64-byte half lines for another wave to finish: the write stream ran at 2.3 TB/s), and
     // (b) 8 instead of 13 LDS operand reads per k-group.  Primal and dual tiles are dealt evenly, so the waves stay
     // balanced although primal channels stop after half the groups.
-    constexpr bool SPLIT = NG_T && (NGP_T * 2 == NG_T) && (SK_NW == 4 || SK_NW == 8) && (CT % 4 == 0);
-    constexpr bool DB = (SK_NW == 8) && !SPLIT;          // double-buffered X image (else single buffer, two barriers)
+    constexpr bool SPLIT = NG_T && (NGP_T * 2 == NG_T) && (CT % 4 == 0);
     // SPLIT keeps the structurally-zero quadrant out of the weight image (groups >= NGP hold the dual channels only): 41
-    // instead of 55 KB.  With 8 waves sharing it and a 128-position image that is 78 KB per workgroup: two per CU, four waves
-    // per SIMD.
-    constexpr int PQ = SK_NW / 2;                        // 32-position quarters (halves) of a tile, one per wave pair
+    // instead of 55 KB.
+    constexpr int PQ = 2;                                // 32-position halves of a tile, one per wave pair
     constexpr int QT = CT / 4;                           // primal (and dual) channel tiles per wave in SPLIT mode
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int ws_groups = SPLIT ? NGP * BC + (NG - NGP) * (BC / 2) : NG * BC;     // 4-float weight groups in LDS
     float* Ws = smem;                                    // [NG][BC][4]  (SPLIT: [NGP][BC][4] then [NG-NGP][BC/2][4])
-    float* Xs = smem + (size_t)ws_groups * 4;            // [2][NG][SK_TP][4]
+    float* Xs = smem + (size_t)ws_groups * 4;            // [NG][SK_TP][4]
     __shared__ const float* wptr_s[8];
 
     const int tid = threadIdx.x;
@@ -104,7 +100,7 @@ __global__ __launch_bounds__(SK_NW * 64, (SK_NW == 8 && NG_T) ? 4 : 1) void hc_c
     const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
         (void*)p.src, 0, (unsigned)(p.src_elems * 4 > 0xFFFFFFFFLL ? 0xFFFFFFFFu : p.src_elems * 4), 0x00020000);
 
-    // im2col items of one tile: (g, pos), pos = tid & 127 for every item of this thread, g = (tid >> 7) + 4*i
+    // im2col items of one tile: (g, pos), pos = tid & 63 for every item of this thread, g = (tid >> 6) + 4*i
     const int xpos = tid & (SK_TP - 1);
     const int xg0 = __builtin_amdgcn_readfirstlane(tid / SK_TP);
     constexpr int XI_MAX = NG_T ? (NG_T + 3) / 4 : 10;   // NG <= 40
@@ -161,14 +157,12 @@ __global__ __launch_bounds__(SK_NW * 64, (SK_NW == 8 && NG_T) ? 4 : 1) void hc_c
         for (int i = 0; i < XI_MAX; ++i) {
 #pragma unroll
             for (int s = 0; s < 4; ++s) {
-                constexpr int dummy = 0;
                 const int g = W + 4 * i, kk = g * 4 + s;           // constants after unrolling
                 const int chan = kk / 9, kh = (kk % 9) / 3, kw = kk % 3;
                 const bool live = g < NG_T && kk < NG_T * 4 && kk < 9 * 8;
                 const bool ok = live && (kh == 0 ? r0 : kh == 1 ? r1 : r2) && (kw == 0 ? c0 : kw == 1 ? c1 : c2);
                 const unsigned off = ok ? vbase + (unsigned)((chan * p.srcS + kh * p.srcW + kw) * 4) : 0xFFFFFFFFu;
                 xr[i][s] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rsrc, off, 0, 0));
-                (void)dummy;
             }
         }
     };
@@ -178,12 +172,11 @@ __global__ __launch_bounds__(SK_NW * 64, (SK_NW == 8 && NG_T) ? 4 : 1) void hc_c
         else if (xg0 == 2) gather_fast(tile, std::integral_constant<int, 2>{});
         else gather_fast(tile, std::integral_constant<int, 3>{});
     };
-    auto scatter = [&](int buf) __attribute__((always_inline)) {
-        float* dst = Xs + (size_t)buf * NG * SK_TP * 4;
+    auto scatter = [&]() __attribute__((always_inline)) {
 #pragma unroll
         for (int i = 0; i < XI_MAX; ++i)
             if (i < xi_n)
-                *reinterpret_cast<float4*>(&dst[((size_t)(xg0 + 4 * i) * SK_TP + xpos) * 4]) =
+                *reinterpret_cast<float4*>(&Xs[((size_t)(xg0 + 4 * i) * SK_TP + xpos) * 4]) =
                     make_float4(xr[i][0], xr[i][1], xr[i][2], xr[i][3]);
     };
 
@@ -205,11 +198,10 @@ __global__ __launch_bounds__(SK_NW * 64, (SK_NW == 8 && NG_T) ? 4 : 1) void hc_c
     long long seq = blockIdx.x;
     if (seq < ntiles) {
         if constexpr (SPLIT) gather_split(tile_of(seq)); else gather(tile_of(seq));
-        scatter(0);
+        scatter();
     }
     __syncthreads();
 
-    int buf = 0;
     for (; seq < ntiles; seq += gridDim.x) {
         const long long tile = tile_of(seq);
         const bool has_next = seq + gridDim.x < ntiles;
@@ -226,7 +218,7 @@ __global__ __launch_bounds__(SK_NW * 64, (SK_NW == 8 && NG_T) ? 4 : 1) void hc_c
         }
         if constexpr (SPLIT) {
             const int half = wave % PQ, cgp = wave / PQ;
-            const float* xb = Xs + (size_t)buf * NG * SK_TP * 4 + (size_t)(half * 32 + fr) * 4 + fk;
+            const float* xb = Xs + (size_t)(half * 32 + fr) * 4 + fk;
             const float* wp = Ws + (size_t)(cgp * QT * 16 + fr) * 4 + fk;                      // primal tiles of this wave
             const float* wd = Ws + (size_t)((CT / 2 + cgp * QT) * 16 + fr) * 4 + fk;             // dual tiles
             const float* wd2 = Ws + (size_t)(NGP_T * BC + cgp * QT * 16 + fr) * 4 + fk;         // dual tiles, groups >= NGP
@@ -250,7 +242,7 @@ __global__ __launch_bounds__(SK_NW * 64, (SK_NW == 8 && NG_T) ? 4 : 1) void hc_c
                 }
             }
         } else {
-        const float* xb = Xs + (size_t)buf * NG * SK_TP * 4 + (size_t)(wave * 16 + fr) * 4 + fk;
+        const float* xb = Xs + (size_t)(wave * 16 + fr) * 4 + fk;
         const float* wb = Ws + (size_t)fr * 4 + fk;
         // groups every channel tile needs
 #pragma unroll
@@ -322,56 +314,27 @@ __global__ __launch_bounds__(SK_NW * 64, (SK_NW == 8 && NG_T) ? 4 : 1) void hc_c
         // tile's store addresses / data, and the compiler guards that reuse with s_waitcnt vmcnt(..) -- the next tile's MFMAs
         // start only when this tile's stores are acknowledged.  Stores straight from a second, alternating accumulator set
         // with SGPR-base addressing would remove the reuse; not done yet.
-        if (DB) {
-            if (has_next) scatter(buf ^ 1);
-            lds_barrier();
-            buf ^= 1;
-        } else {
-            lds_barrier();                               // everyone is done reading the image
-            if (has_next) scatter(0);
-            lds_barrier();
-        }
+        lds_barrier();                                   // everyone is done reading the image
+        if (has_next) scatter();
+        lds_barrier();
     }
 
     if (p.epilogue & SELD_EPI_STATS) {
-        // lanes fr, fr+16, fr+32, fr+48 hold the same channel; 8 waves hold different positions
-        float* red = Xs;                                   // free now: [SK_NW][BC][2]
+        float* red = Xs;                                   // free now: [4][BC][2]
         if constexpr (SPLIT) {
-            for (int t = tid; t < SK_NW * BC * 2; t += SK_NT) red[t] = 0.f;       // a wave fills its own tiles only
+            for (int t = tid; t < 4 * BC * 2; t += SK_NT) red[t] = 0.f;           // a wave fills its own tiles only
             __syncthreads();
             const int cgp = wave / PQ;
 #pragma unroll
             for (int t = 0; t < 2 * QT; ++t) {
                 const int ch = (t < QT ? cgp * QT + t : CT / 2 + cgp * QT + (t - QT)) * 16 + fr;
-                float a = s1[t], b = s2[t];
-                a += __shfl_xor(a, 16, 64); a += __shfl_xor(a, 32, 64);
-                b += __shfl_xor(b, 16, 64); b += __shfl_xor(b, 32, 64);
-                if (fk == 0) {
-                    red[(wave * BC + ch) * 2 + 0] = a;
-                    red[(wave * BC + ch) * 2 + 1] = b;
-                }
+                conv_stats_put<BC>(red, wave, ch, fk, s1[t], s2[t]);
             }
         } else {
 #pragma unroll
-        for (int j = 0; j < CT; ++j) {
-            float a = s1[j], b = s2[j];
-            a += __shfl_xor(a, 16, 64); a += __shfl_xor(a, 32, 64);
-            b += __shfl_xor(b, 16, 64); b += __shfl_xor(b, 32, 64);
-            if (fk == 0) {
-                red[(wave * BC + j * 16 + fr) * 2 + 0] = a;
-                red[(wave * BC + j * 16 + fr) * 2 + 1] = b;
-            }
+            for (int j = 0; j < CT; ++j) conv_stats_put<BC>(red, wave, j * 16 + fr, fk, s1[j], s2[j]);
         }
-        }
-        __syncthreads();
-        float* rep = p.stats + (size_t)(blockIdx.x % SELD_STATS_REPLICAS) * 2 * p.Cdst;
-        for (int t = tid; t < BC; t += SK_NT) {
-            float a = 0.f, b = 0.f;
-#pragma unroll
-            for (int wv = 0; wv < SK_NW; ++wv) { a += red[(wv * BC + t) * 2]; b += red[(wv * BC + t) * 2 + 1]; }
-            atomicAdd(rep + t, a);
-            atomicAdd(rep + p.Cdst + t, b);
-        }
+        conv_stats_flush<BC>(red, p.stats, p.Cdst, 0, tid);        // Cdst == BC (hc_conv_smallk_ct)
     }
 }
 
@@ -383,18 +346,18 @@ static void smallk_groups(const ConvP& p, int* NG, int* NGP) {
     if (p.algebra == 8 && (p.Ktot / 2) % 4 == 0 && (p.Cdst / 2) % 16 == 0) *NGP = p.Ktot / 8;
 }
 
-template <int CT, int NW>
+template <int CT>
 static int launch_smallk(const ConvP& p, hipStream_t st) {
-    constexpr int TP = SkGeom<NW>::TP, NT = SkGeom<NW>::NT;
+    constexpr int TP = SK_TP, NT = SK_NT;
     int NG, NGP;
     smallk_groups(p, &NG, &NGP);
     const long long ntiles = (p.Ptot + TP - 1) / TP;
-    // the im2col image doubles as the statistics fold's [NW][BC][2] buffer: below CT / 2 k-groups the fold is the larger
-    const size_t x_floats = (size_t)NG * TP * 4, red_floats = (size_t)NW * CT * 16 * 2;
+    // the im2col image doubles as the statistics fold's [4][BC][2] buffer: below CT / 2 k-groups the fold is the larger
+    const size_t x_floats = (size_t)NG * TP * 4, red_floats = (size_t)4 * CT * 16 * 2;
     const size_t smem_generic = ((size_t)NG * CT * 16 * 4 + (x_floats > red_floats ? x_floats : red_floats)) * sizeof(float);
 #define SELD_SK(KH_, KW_, NG_, NGP_)                                                                               \
     do {                                                                                                           \
-        auto kern = hc_conv_smallk_kernel<CT, KH_, KW_, NW, NG_, NGP_>;                                            \
+        auto kern = hc_conv_smallk_kernel<CT, KH_, KW_, NG_, NGP_>;                                                \
         constexpr bool split = NG_ && (NGP_ * 2 == NG_) && (CT % 4 == 0);                                          \
         const size_t smem = split ? ((size_t)(NGP_ * CT * 16 + (NG_ - NGP_) * CT * 8) * 4 + (size_t)NG_ * TP * 4) * sizeof(float) \
                                   : smem_generic;                                                                   \
@@ -426,14 +389,14 @@ int hc_conv_smallk_ct(const ConvP& p) {
     int NG, NGP;
     smallk_groups(p, &NG, &NGP);
     // weight image + one 64-position im2col image, two workgroups per CU
-    const size_t smem = ((size_t)NG * ct * 16 * 4 + (size_t)NG * SkGeom<4>::TP * 4) * sizeof(float);
+    const size_t smem = ((size_t)NG * ct * 16 * 4 + (size_t)NG * SK_TP * 4) * sizeof(float);
     return 2 * smem > 156 * 1024 ? 0 : ct;
 }
 
 int hc_conv_smallk_launch(const ConvP& p, int ct, hipStream_t st) {
-    if (ct == 12) return launch_smallk<12, 4>(p, st);
-    if (ct == 8) return launch_smallk<8, 4>(p, st);
-    return launch_smallk<4, 4>(p, st);
+    if (ct == 12) return launch_smallk<12>(p, st);
+    if (ct == 8) return launch_smallk<8>(p, st);
+    return launch_smallk<4>(p, st);
 }
 
 }  // namespace seld

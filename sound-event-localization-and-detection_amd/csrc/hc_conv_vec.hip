@@ -25,8 +25,7 @@
 // descriptor; workgroups that can reach those rows ("edge" workgroups, wave-uniform) gather per element instead.
 //
 // Eligibility is hc_conv_vec_chunk(), which hc_conv_plan (hc_conv_fwd.hip) asks; everything else runs on hc_conv_kernel.
-#include <type_traits>
-#include "hc_common.h"
+#include "hc_conv_tile.h"
 
 namespace seld {
 
@@ -61,15 +60,16 @@ __global__ __launch_bounds__(256) void hc_conv_vec_kernel(const ConvP p) {
 
     __shared__ __attribute__((aligned(16))) float Xs[2][KC][XROW];
     __shared__ __attribute__((aligned(16))) float Ws[2][BC][RS][4];
-    __shared__ unsigned wdelta_s[16];
+    __shared__ unsigned wdelta_s[16];              // [slot][component] byte offsets from p.wmin
     // statistics scratch of a forward pair: the staging buffers hold slot 1's first chunk while slot 0 is written out
-    __shared__ float pair_red_s[(PAIRS && MODE == MODE_FWD) ? 4 * CT * 16 * 2 : 1];              // [slot][component] byte offsets from p.wmin
+    __shared__ float pair_red_s[(PAIRS && MODE == MODE_FWD) ? 4 * CT * 16 * 2 : 1];
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int c0 = blockIdx.y * BC;
-    const long long p0 = (long long)blockIdx.x * BP;
+    const ConvOrigin<BP> og = conv_origin<BC, BP>(p);
+    const int c0 = og.c0;
+    const long long p0 = og.p0, img0 = og.img0;
     const int A = p.algebra;
     const int CK = (MODE == MODE_FWD ? p.IA : p.OA) * KK;   // K extent of one component block (multiple of KC)
 
@@ -85,13 +85,10 @@ __global__ __launch_bounds__(256) void hc_conv_vec_kernel(const ConvP p) {
     // A separate instantiation: the extra state costs the single-convolution kernels 10 %.
     static_assert(!PAIRS || MODE == MODE_DGRAD || (KH_T == 1 && KW_T == 1), "forward pairs: 1x1 layers only");
     constexpr bool FWD_PAIR = PAIRS && MODE == MODE_FWD;
-    const int zslot = 0;
-    const int kslots = PAIRS ? 2 : 1;
-    int wslot = zslot;                             // weight set the next chunk to load belongs to
+    int wslot = 0;                                 // weight set the next chunk to load belongs to
 
     // ---- buffer descriptor of the streamed operand: based one image before the tile's first image so that the
     // halo of the tile's first row reads (and masks) the end of the previous image instead of wrapping -----------
-    const long long img0 = p0 / p.dstS;
     const long long imgb = img0 > 0 ? img0 - 1 : 0;
     const long long img_elems = (long long)p.Csrc * p.srcS;
     const float* sbase = p.src + imgb * img_elems;
@@ -100,45 +97,22 @@ __global__ __launch_bounds__(256) void hc_conv_vec_kernel(const ConvP p) {
     const unsigned nrec = remain > (long long)OOB ? OOB : (unsigned)remain;
     __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)sbase, 0, nrec, 0x00020000);
 
-    const int rem0 = (int)(p0 - img0 * p.dstS);
-    auto decode = [&](int local, int* dimg, int* rem) __attribute__((always_inline)) {
-        int r = rem0 + local;
-        int di = 0;
-        if (p.dstS >= BP) {
-            if (r >= p.dstS) { r -= p.dstS; di = 1; }
-        } else {
-            di = r / p.dstS;
-            r -= di * p.dstS;
-        }
-        *dimg = di;
-        *rem = r;
-    };
-
     // Workgroups that can touch the first row of the tensor with a left halo, or the last row with a right halo.
     const int hs = max(abs(p.OFFh), (KH_T - 1) * abs(p.KDh)) + 1;
     const long long edge_span = (long long)hs * p.dstW;
     const bool edge_wg = (p0 < edge_span) || (p0 + BP + edge_span > p.Ptot);
 
     // ---- K range of this workgroup (dual-quaternion zero quadrant), in whole chunks -------------------------
-    const int half_c = p.Cdst >> 1;
-    const int half_k = p.Ktot >> 1;
-    const bool halves_aligned = (p.skip_mode != 0) && (half_k % KC == 0) && (half_c % 16 == 0);
     // (Pairing primal and dual tiles in one workgroup for balance was measured 0-7 % SLOWER on the TCN layers: the
-    // half-K chunks then carry half the MFMAs for the same staging and barrier.  Tiles stay contiguous.)
-    // (Balanced tiles -- every workgroup half primal, half dual channels, so that all run 12 full + 12 half chunks
-    // instead of 12 or 24 full ones -- were measured in round 2: 1x3 forward 67.4 vs 66.7 us, pair data gradient 77.6 vs
-    // 69.4: a chunk costs the same with 36 MFMAs as with 72, the loop is bound by the staging round trip, not by the
-    // matrix pipe.  Tiles stay contiguous.)
-    auto chan_of = [&](int t) __attribute__((always_inline)) { return c0 + t; };
-    int kbeg = 0, kend = p.Ktot;
-    if (halves_aligned) {
-        if (p.skip_mode == 1 && c0 + BC <= half_c) kend = half_k;      // all channels primal
-        if (p.skip_mode == 2 && c0 >= half_c) kbeg = half_k;           // all channels dual
-    }
+    // half-K chunks then carry half the MFMAs for the same staging and barrier.  Balanced tiles -- every workgroup half
+    // primal, half dual channels, so that all run 12 full + 12 half chunks instead of 12 or 24 full ones -- were measured
+    // too: 1x3 forward 67.4 vs 66.7 us, pair data gradient 77.6 vs 69.4: a chunk costs the same with 36 MFMAs as with 72,
+    // the loop is bound by the staging round trip, not by the matrix pipe.  Tiles stay contiguous.)
+    const ConvKRange kr = conv_k_range<BC, CT, KC>(p, c0);
+    const int kbeg = kr.kbeg;
     // (Where the time goes on the 1x3 TCN layer, 74 us: launch + setup 2.6 us, first load round trip 2.7, first iteration
     // 4.7 (cold), output write-back 4.5, 23 more iterations 2.4 each.)
-    const int nchunks = (kend - kbeg) / KC;
-    const bool mixed_wg = halves_aligned && (CT % 2 == 0) && (c0 + BC / 2 == half_c);
+    const int nchunks = (kr.kend - kbeg) / KC;
 
     // ---- X items: everything but the channel advance is loop-invariant ----------------------------------------
     const int quad = tid % QP;
@@ -151,7 +125,7 @@ __global__ __launch_bounds__(256) void hc_conv_vec_kernel(const ConvP p) {
         const long long pg = p0 + 4 * quad;
         const bool pvalid = pg < p.Ptot;               // Ptot is a multiple of 4: the quad is all-in or all-out
         int dimg = 0, rem = 0;
-        if (pvalid) decode(4 * quad, &dimg, &rem);
+        if (pvalid) og.decode(4 * quad, &dimg, &rem);
         const int oh = (p.dstS < (1 << 20)) ? small_div(rem, 1.0f / (float)p.dstW) : rem / p.dstW;
         const int ow = rem - oh * p.dstW;              // multiple of 4, the quad stays inside the row
         const int base_h = oh * p.SMh + p.OFFh;
@@ -198,7 +172,7 @@ __global__ __launch_bounds__(256) void hc_conv_vec_kernel(const ConvP p) {
         const int row = f / NG;
         const int g = f - row * NG;
         wlds[i] = (row * RS + g) * 4;
-        const int chg = chan_of(row);
+        const int chg = c0 + row;
         const bool ok = chg < p.Cdst;
         const int cc = ok ? chg : 0;
         const int per = (MODE == MODE_FWD) ? p.OA : p.IA;
@@ -287,10 +261,7 @@ __global__ __launch_bounds__(256) void hc_conv_vec_kernel(const ConvP p) {
     };
 
     floatx4 acc[PT][CT];
-#pragma unroll
-    for (int i = 0; i < PT; ++i)
-#pragma unroll
-        for (int j = 0; j < CT; ++j) acc[i][j] = (floatx4){0.f, 0.f, 0.f, 0.f};
+    conv_zero_acc(acc);
 
     const int fr = lane & 15;      // row / col inside a 16x16 tile
     const int fk = lane >> 4;      // k group of this lane
@@ -388,126 +359,21 @@ __global__ __launch_bounds__(256) void hc_conv_vec_kernel(const ConvP p) {
             __syncthreads();
         }
     };
-    using IC0 = std::integral_constant<int, 0>;
-    using ICH = std::integral_constant<int, CT / 2>;
-    using ICT = std::integral_constant<int, CT>;
-    // ---- epilogue: lane holds 4 consecutive positions (regs) of channel c0 + j*16 + fr ----------------------
-    auto epilogue = [&](int zs) __attribute__((always_inline)) {
-        float* const dstz = zs ? p.dst2 : p.dst;
-        const float* const addz = zs ? p.addend2 : p.addend;
-        const float* const biasz = zs ? p.bias2 : p.bias;
-        float* const statsz = zs ? p.stats2 : p.stats;
-        const int epi = zs ? p.epilogue2 : p.epilogue;
-        float* const dst0 = dstz + (size_t)img0 * p.Cdst * p.dstS;
-        const float* const add0 = addz ? addz + (size_t)img0 * p.Cdst * p.dstS : nullptr;
-        int poff[PT];
-    #pragma unroll
-        for (int i = 0; i < PT; ++i) {
-            int dimg, rem;
-            decode(wave * (PT * 16) + i * 16 + fk * 4, &dimg, &rem);
-            poff[i] = dimg * p.Cdst * p.dstS + rem;
-        }
-    #pragma unroll
-        for (int j = 0; j < CT; ++j) {
-            const int ch = chan_of(j * 16 + fr);
-            const bool chok = ch < p.Cdst;
-            const float bvv = (chok && biasz) ? biasz[ch] : 0.0f;
-            float s1 = 0.f, s2 = 0.f;
-    #pragma unroll
-            for (int i = 0; i < PT; ++i) {
-                const long long pos = p0 + wave * (PT * 16) + i * 16 + fk * 4;
-                const floatx4 v = acc[i][j];
-                if (chok && pos < p.Ptot) {
-                    const size_t off = (size_t)(poff[i] + ch * p.dstS);
-                    float4 o = make_float4(v[0] + bvv, v[1] + bvv, v[2] + bvv, v[3] + bvv);
-                    if (epi & SELD_EPI_ADD) {
-                        const float4 ad = *reinterpret_cast<const float4*>(add0 + off);
-                        o.x += ad.x; o.y += ad.y; o.z += ad.z; o.w += ad.w;
-                    }
-                    if (epi & SELD_EPI_ACCUMULATE) {
-                        const float4 old = *reinterpret_cast<const float4*>(dst0 + off);
-                        o.x += old.x; o.y += old.y; o.z += old.z; o.w += old.w;
-                    }
-                    *reinterpret_cast<float4*>(dst0 + off) = o;
-                    s1 += o.x + o.y + o.z + o.w;
-                    s2 += o.x * o.x + o.y * o.y + o.z * o.z + o.w * o.w;
-                }
-            }
-            if (epi & SELD_EPI_STATS) {
-                s1 += __shfl_xor(s1, 16, 64);
-                s1 += __shfl_xor(s1, 32, 64);
-                s2 += __shfl_xor(s2, 16, 64);
-                s2 += __shfl_xor(s2, 32, 64);
-                if (fk == 0) {
-                    float* redbuf = FWD_PAIR ? pair_red_s : &Xs[0][0][0];   // the K loop is over: the staging buffers are free
-                    redbuf[(wave * BC + j * 16 + fr) * 2 + 0] = s1;
-                    redbuf[(wave * BC + j * 16 + fr) * 2 + 1] = s2;
-                }
-            }
-        }
-        if (epi & SELD_EPI_STATS) {
-            static_assert(sizeof(Xs) >= 4 * BC * 2 * sizeof(float), "statistics scratch fits the X staging buffers");
-            __syncthreads();
-            const float* redbuf = FWD_PAIR ? pair_red_s : &Xs[0][0][0];      // where the partial sums were put above
-            float* rep = statsz + (size_t)(blockIdx.x % SELD_STATS_REPLICAS) * 2 * p.Cdst;
-            for (int t = tid; t < BC; t += 256) {
-                const int ch = chan_of(t);
-                if (ch < p.Cdst) {
-                    float a1 = 0.f, a2 = 0.f;
-    #pragma unroll
-                    for (int wv = 0; wv < 4; ++wv) {
-                        a1 += redbuf[(wv * BC + t) * 2 + 0];
-                        a2 += redbuf[(wv * BC + t) * 2 + 1];
-                    }
-                    atomicAdd(rep + ch, a1);
-                    atomicAdd(rep + p.Cdst + ch, a2);
-                }
-            }
-        }
-    };
-
-    // (data gradient of a pair: the chunk ranges are simply run again for the second source; load_chunk's state
-    // machine switches descriptor and weights by itself.  Written as straight-line repeats, not as a loop over the
-    // slots: the nested loop cost the 12-tile kernels 100+ VGPRs.)
-    auto zero_acc = [&]() __attribute__((always_inline)) {
-#pragma unroll
-        for (int i = 0; i < PT; ++i)
-#pragma unroll
-            for (int j = 0; j < CT; ++j) acc[i][j] = (floatx4){0.f, 0.f, 0.f, 0.f};
+    // The K range once per slot; load_chunk's state machine switches descriptor and weights by itself.  A forward pair
+    // writes slot 0 out between the two walks, a data-gradient pair runs on into the same accumulators.
+    static_assert(sizeof(Xs) >= 4 * BC * 2 * sizeof(float), "statistics scratch fits the X staging buffers");
+    float* const red = FWD_PAIR ? pair_red_s : &Xs[0][0][0];    // single convolution: the K loop is over, the staging buffers are free
+    auto slot0_out = [&]() __attribute__((always_inline)) {
+        conv_epilogue<CT, PT, false>(p, og, conv_out(p, 0), acc, red, tid);
+        conv_zero_acc(acc);
     };
     auto run_all = [&](auto edgec) __attribute__((always_inline)) {
-        if (mixed_wg) {
-            const int csplit = (half_k - kbeg) / KC;          // first chunk of the upper K half
-            if (p.skip_mode == 1) {                           // forward: primal tiles (lower half) see zeros there
-                run_chunks(0, csplit, IC0{}, ICT{}, edgec);
-                run_chunks(csplit, nchunks, ICH{}, ICT{}, edgec);
-                if (FWD_PAIR) {
-                    epilogue(0);
-                    zero_acc();
-                    run_chunks(0, csplit, IC0{}, ICT{}, edgec);
-                    run_chunks(csplit, nchunks, ICH{}, ICT{}, edgec);
-                }
-            } else {                                          // dgrad: dual tiles (upper half) see zeros in the lower K half
-                run_chunks(0, csplit, IC0{}, ICH{}, edgec);
-                run_chunks(csplit, nchunks, IC0{}, ICT{}, edgec);
-                if (PAIRS) {
-                    run_chunks(0, csplit, IC0{}, ICH{}, edgec);
-                    run_chunks(csplit, nchunks, IC0{}, ICT{}, edgec);
-                }
-            }
-        } else if (FWD_PAIR) {
-            run_chunks(0, nchunks, IC0{}, ICT{}, edgec);
-            epilogue(0);
-            zero_acc();
-            run_chunks(0, nchunks, IC0{}, ICT{}, edgec);
-        } else {
-            run_chunks(0, kslots * nchunks, IC0{}, ICT{}, edgec);
-        }
+        auto run = [&](int cbeg, int cend, auto j0c, auto j1c) __attribute__((always_inline)) { run_chunks(cbeg, cend, j0c, j1c, edgec); };
+        conv_run_k_range<CT, MODE, PAIRS ? 2 : 1>(kr, p.skip_mode, nchunks, run, slot0_out);
     };
     if (edge_wg) run_all(ETrue{});
     else run_all(EFalse{});
-    epilogue(FWD_PAIR ? 1 : 0);
-
+    conv_epilogue<CT, PT, false>(p, og, conv_out(p, FWD_PAIR ? 1 : 0), acc, red, tid);
 }
 
 // Can this problem run on the vector-staging kernel with tile (ct, pt)?  Returns the K chunk (36 / 24) or 0.
