@@ -23,6 +23,7 @@ import torch
 
 from tests import hcq_exact as X
 from tests import philox_ref as R
+from tests import pool_window_ref as PW
 from tests.helpers import pkg
 
 pytestmark = pytest.mark.gpu
@@ -62,14 +63,7 @@ assert len(set(IDS)) == len(IDS) and len({c["pool_label"] for c in CASES[:8]}) =
 def _bn_inputs(case):
     """gamma in {-2 .. 2} with a positive, a negative and a zero channel in every group of 8 (their places move with the
     group); mean, beta integers in [-2, 2]; invstd in {0.5, 1, 2}."""
-    C = case["cout"]
-    gen = torch.Generator().manual_seed(X.W._seed(case, None) ^ 0x9001)
-    gamma = torch.randint(-2, 3, (C,), generator=gen).float().view(C // 8, 8)
-    for g in range(C // 8):
-        gamma[g, g % 8], gamma[g, (g + 3) % 8], gamma[g, (g + 5) % 8] = 1 + g % 2, -1 - (g // 2) % 2, 0
-    mean, beta = (torch.randint(-2, 3, (C,), generator=gen).float() for _ in range(2))
-    invstd = torch.tensor([0.5, 1.0, 2.0])[torch.randint(0, 3, (C,), generator=gen)]
-    return {"gamma": gamma.view(C), "mean": mean, "beta": beta, "invstd": invstd}
+    return PW.bn_inputs(case["cout"], torch.Generator().manual_seed(X.W._seed(case, None) ^ 0x9001))
 
 
 _refs = {}
@@ -84,16 +78,9 @@ def _ref(case):
         o = X.epilogue_reference(y, t["biasA"])                              # float64 (N, C, H, W)
         assert bool((o == o.round()).all())
         b = _bn_inputs(case)
-        N, C, H, Wd = o.shape
-        win = o.view(N, C, H // POOL, POOL, Wd)
-        key = torch.sign(b["gamma"]).double().view(1, C, 1, 1, 1) * win
-        best = key.max(dim=3, keepdim=True).values
-        idx = ((key == best).cumsum(3) == 0).sum(3)                          # rows before the first maximum
-        raw = win.gather(3, idx.unsqueeze(3)).squeeze(3)
-        a = (b["gamma"] * b["invstd"]).double()
-        bb = b["beta"].double() - b["mean"].double() * a
-        z = torch.relu(a.view(1, C, 1, 1) * raw + bb.view(1, C, 1, 1))
-        _refs[case["name"]] = dict(b, o=o, raw=raw, idx=idx.to(torch.uint8), z=z, ties=int(((key == best).sum(3) > 1).sum()))
+        raw, idx, ties = PW.window_rows(o, b["gamma"], POOL)
+        z = PW.bn_relu(raw, b["gamma"], b["beta"], b["mean"], b["invstd"])
+        _refs[case["name"]] = dict(b, o=o, raw=raw, idx=idx.to(torch.uint8), z=z, ties=ties)
     return _refs[case["name"]]
 
 

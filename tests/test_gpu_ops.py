@@ -501,9 +501,17 @@ def test_spectrum_fast_full_clip():
                                                              (4, 8, 64, (16, 64), 8, True),      # quaternion, pooling convolution
                                                              (4, 8, 128, (8, 128), 8, False)])   # ... two tiles, eval statistics
 def test_first_stage_fused_backward(algebra, cin, cout, hw, ph, training, monkeypatch):
-    """conv -> BatchNorm2d -> ReLU -> MaxPool(ph, 1) on an input that needs no gradient: the fused backward
-    (seld_bn_relu_pool_bwd_coef + seld_hc_conv_bwd_weight_bnpool_acc, dy never written) against the unfused path
-    (seld_bn_relu_pool_bwd + seld_hc_conv_bwd_weight_acc), and that one against torch autograd on the CPU in fp64."""
+    """conv -> BatchNorm2d -> ReLU -> MaxPool(ph, 1) on an input that needs no gradient: H.conv_bn_relu_pool (dy never
+    written) against the unfused path (SELD_NO_FUSED_STAGE0: seld_bn_relu_pool_bwd + seld_hc_conv_bwd_weight_acc), and
+    both against torch autograd on the CPU in fp64.  Which route the fused call takes, by parametrisation:
+      (8, 8, 192, (16, 64), 8, train) and (4, 8, 64, (16, 64), 8, train): the stage without its convolution output
+          (csrc/first_stage.hip: seld_first_stage_gram / _bn, seld_hcq_first_pool_bn, seld_first_stage_bwd) -- 8 input
+          channels, training mode, ph = 8, H % 8 == 0, W % 64 == 0, a channel count the backward pass instantiates.  N = 3
+          gives 6 blocks, one per workgroup; tests/test_gpu_first_stage_exact.py holds that path to fp64 exactly, at
+          ragged and multi-block shapes too;
+      (4, 8, 64, (8, 32), 2, train) (ph = 2, W = 32), (8, 8, 64, (16, 96), 8, eval) and (4, 8, 128, (8, 128), 8, eval)
+          (eval statistics; W = 96), (8, 16, 192, (16, 64), 8, train) (16 input channels): y is written, the backward
+          is seld_bn_relu_pool_bwd_coef[_drop] + seld_hc_conv_bwd_weight_bnpool[_drop]_acc."""
     P = pkg()
     H, T = P.hip_ops, P.train
     gen = torch.Generator().manual_seed(21)
