@@ -1517,6 +1517,56 @@ int seld_at_bwd(const float* qkv, const float* read, const float* dread, const f
                 void* workspace, size_t workspace_bytes, void* stream);
 int seld_at_kernel_label(int32_t op, int32_t T, int32_t K, int32_t V, char* buf, int32_t buflen);
 
+/* ------------------------------------------------------------------------------------------
+ * GRU (csrc/gru.hip): the recurrence of one torch.nn.GRU layer, gate order r | z | n, for 1 or 2 directions (direction 1
+ * walks time backwards).  fp32, contiguous.  With gx = x @ W_ih^T + b_ih (seld_hc_linear_fwd; not part of the recurrence):
+ *
+ *   r  = sigmoid(gx_r + W_hr h + b_hr)
+ *   z  = sigmoid(gx_z + W_hz h + b_hz)
+ *   n  = tanh(gx_n + r * (W_hn h + b_hn))
+ *   h' = (1 - z) * n + z * h
+ *
+ * seld_gru_pack writes, for every direction, W_hh (3H, H) as the forward kernel's and W_hh^T as the backward kernel's MFMA
+ * fragments and b_hh (NULL: zeros), all zero-padded to Hp = H rounded up to 16, into wpack (seld_gru_pack_floats floats):
+ * the recurrence calls read the weights from there only, so the two directions' parameters need not be adjacent.
+ *
+ * seld_gru_fwd, one launch for every direction:
+ *   gx (dirs, B, T, 3H), h0 (dirs, B, H) or NULL (zeros)  ->  y (B, T, dirs*H): each direction writes its half, there is
+ *   no concatenation; h_n (dirs, B, H); saved, if not NULL, (5, dirs, B, T, H) = r, z, n, W_hn h + b_hn, h_prev, what
+ *   seld_gru_bwd reads (seld_gru_saved_floats floats; h_prev is contiguous per direction: it is the x of dW_hh).
+ * seld_gru_bwd, one launch for the reverse recurrence of every direction:
+ *   dy (B, T, dirs*H), dh_n (dirs, B, H) or NULL, saved  ->  dgx (dirs, B, T, 3H); dgh (dirs, B, T, 3H) = dgx with the n
+ *   part multiplied by r; dh0 (dirs, B, H) or NULL.  dh is carried through W_hh^T.
+ *   dW_hh = dgh^T @ h_prev and db_hh = column sums of dgh are ONE product over all steps: seld_hc_linear_bwd(SELD_LIN_REAL,
+ *   B*T, H, 3H, h_prev, dgh, ...) per direction; dx, dW_ih, db_ih come from the same call on (x, dgx).
+ *
+ * Form (seld_gru_kernel_label: "gru_<fwd|bwd>_kernel<Hp/16>"): one workgroup per (direction, 16 batch columns) holds
+ * W_hh (backward: W_hh^T) in registers for the whole launch as fp32-MFMA fragments, wave w owning hidden units
+ * 16w .. 16w+15; h (backward: dgh) is double-buffered in LDS, one barrier per step.  Columns past B are masked.  No
+ * grid-wide barrier, no cooperative launch, no atomics: a repeated call gives the same bytes, and a sample gives the same
+ * bytes alone as inside a batch.  All on `stream`, no host read, no allocation: the calls record into a HIP graph.
+ * 1 <= H <= SELD_GRU_MAX_HIDDEN: the resident form ends where W_hh outgrows one workgroup's registers; larger hidden
+ * sizes need the weights streamed or the units split across workgroups, which is not built.
+ *   SELD_EINVAL: a NULL required tensor, a size <= 0, dirs outside {1, 2} (for the label: an unknown op, a short buffer).
+ *   SELD_EUNSUPPORTED: H > SELD_GRU_MAX_HIDDEN; 5 * dirs * B * T * H (the saved tensors) of 2^31 or more.
+ *   SELD_EWORKSPACE: saved smaller than seld_gru_saved_floats(dirs, B, T, H).
+ * All are returned before anything is launched or written.  Outputs may not alias inputs.
+ * ------------------------------------------------------------------------------------------ */
+#define SELD_GRU_MAX_HIDDEN 128
+#define SELD_GRU_FWD 0                 /* seld_gru_kernel_label(op, ...) */
+#define SELD_GRU_BWD 1
+size_t seld_gru_pack_floats(int32_t dirs, int32_t H);      /* 0 for sizes the calls refuse */
+int seld_gru_pack(int32_t dirs, int32_t H, const float* w_hh0, const float* w_hh1 /* dirs == 2 */,
+                  const float* b_hh0 /* nullable */, const float* b_hh1 /* nullable, as b_hh0 */, float* wpack, void* stream);
+size_t seld_gru_saved_floats(int32_t dirs, int32_t B, int32_t T, int32_t H);       /* 0 for sizes the calls refuse */
+int seld_gru_fwd(int32_t dirs, int32_t B, int32_t T, int32_t H, const float* gx, const float* wpack,
+                 const float* h0 /* nullable */, float* y, float* h_n, float* saved /* nullable */, size_t saved_floats,
+                 void* stream);
+int seld_gru_bwd(int32_t dirs, int32_t B, int32_t T, int32_t H, const float* dy, const float* dh_n /* nullable */,
+                 const float* wpack, const float* saved, size_t saved_floats, float* dgx, float* dgh,
+                 float* dh0 /* nullable */, void* stream);
+int seld_gru_kernel_label(int32_t op, int32_t H, char* buf, int32_t buflen);
+
 #ifdef __cplusplus
 }
 #endif

@@ -5,7 +5,7 @@ import os
 import sys
 
 from . import hip_ops as H
-from .model import SE_MODES, SELD_Model, _at_check
+from .model import SE_MODES, SELD_Model, _at_check, _rnn_check
 
 
 # ------------------------------------------------------------------------------------------
@@ -108,7 +108,9 @@ _EVAL = ('use_cuda', 'early_stopping', 'fixed_seed', 'pool_size', 'cnn_filters',
 # packed into the class_overlaps slots.  A pair of clips that could overflow a class (hip_ops.target_occupancy, computed
 # once for the training array) is not mixed, so no label is dropped; a standardising dataset_normalization is undone and
 # redone around the sum with the training array's statistics.  Magnitudes alone and intensity vectors are not linear in the
-# waveform and stay refused
+# waveform and stay refused;
+# rnn_size / rnn_layers (read only with the reference's --use_tcn=False, which needs --pool_time=CNN): the TCN is replaced by
+# rnn_layers bidirectional GRU layers of rnn_size units (hip_nn.GRU, at most 128), the back end of SELDnet / QSELDnet
 _EXTRA = [('synthetic', int, 0), ('max_steps', int, 0), ('epochs', int, 0), ('resident_loader', str, 'False'),
           ('graph_step', str, 'False'), ('augment_swap', float, 0.), ('augment_freq_masks', int, 0),
           ('augment_freq_width', int, 0), ('augment_time_masks', int, 0), ('augment_time_width', int, 0),
@@ -120,7 +122,8 @@ _EXTRA = [('synthetic', int, 0), ('max_steps', int, 0), ('epochs', int, 0), ('re
           ('grad_clip', float, 0.), ('weight_decay', float, 0.), ('decoupled_weight_decay', str, 'False'),
           ('ema_decay', float, 0.), ('warmup_steps', int, 0),
           ('at_key_size', int, 0), ('at_value_size', int, 0), ('at_mask', str, 'causal'), ('at_band', int, 0),
-          ('augment_mix', float, 0.), ('augment_mix_gain_lo', float, 0.5), ('augment_mix_gain_hi', float, 1.0)]
+          ('augment_mix', float, 0.), ('augment_mix_gain_lo', float, 0.5), ('augment_mix_gain_hi', float, 1.0),
+          ('rnn_size', int, 128), ('rnn_layers', int, 2)]
 
 
 def build_parser():
@@ -175,6 +178,20 @@ def at_from_args(args):
     return kw
 
 
+def rnn_from_args(args):
+    """dict(use_tcn=, rnn_size=, rnn_layers=) of the --use_tcn / --rnn_size / --rnn_layers flags for SELD_Model
+    (use_tcn=False: bidirectional GRUs in place of the TCN; an args object without the flags: the TCN), checked against
+    --pool_time, --se_mode and --at_key_size.  Every refusal comes before the device is touched."""
+    kw = dict(use_tcn=getattr(args, "use_tcn", True), rnn_size=getattr(args, "rnn_size", 128),
+              rnn_layers=getattr(args, "rnn_layers", 2))
+    try:
+        _rnn_check(pool_time=getattr(args, "pool_time", "CNN"), se_mode=getattr(args, "se_mode", "both"),
+                   at_key_size=getattr(args, "at_key_size", 0), **kw)
+    except ValueError as e:
+        raise ValueError("--" + str(e)) from None
+    return kw
+
+
 def optimizer_from_args(args):
     """FlatAdam's keyword arguments of the --grad_clip / --weight_decay / --decoupled_weight_decay / --ema_decay flags, after
     checking them and --warmup_steps (an args object without the flags: everything off).  Every refusal comes before the
@@ -197,7 +214,7 @@ def optimizer_from_args(args):
 
 
 def model_from_args(args):
-    """train.py:448-465, plus the squeeze-and-excitation and temporal-attention flags."""
+    """train.py:448-465, plus the squeeze-and-excitation, temporal-attention and recurrent-back-end flags."""
     return SELD_Model(time_dim=args.time_dim, freq_dim=args.freq_dim, input_channels=args.input_channels,
                       output_classes=args.output_classes, domain=args.domain, domain_classifier=args.domain_classifier,
                       cnn_filters=args.cnn_filters, kernel_size_cnn_blocks=args.kernel_size_cnn_blocks,
@@ -209,7 +226,7 @@ def model_from_args(args):
                       use_bias_linear=args.use_bias_linear, batch_norm=args.batch_norm,
                       parallel_ConvTC_block=args.parallel_ConvTC_block, parallel_magphase=args.parallel_magphase,
                       extra_name=args.model_extra_name, verbose=args.verbose, **se_from_args(args),
-                      **at_from_args(args))
+                      **at_from_args(args), **rnn_from_args(args))
 
 
 _NORM_OFF = {'False', 'false', 'None', 'none'}

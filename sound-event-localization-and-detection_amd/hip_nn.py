@@ -164,3 +164,40 @@ class TemporalAttention(nn.Module):
         read = H.at_core(self.qkv(x), self.key_size, self.value_size, self.mask, self.band, lengths)
         return H.hyper_conv_add(read, (self.out.weight,), self.out.bias, x, self.out.stride, self.out.padding,
                                 self.out.dilation)
+
+
+def _swap01(x):
+    """(A, B, C) -> (B, A, C), contiguous, as two transposes of the last two axes."""
+    A, B, C = x.shape
+    return H.transpose12(H.transpose12(x.reshape(1, A, B * C)).view(B, C, A))
+
+
+class GRU(nn.GRU):
+    """torch.nn.GRU on the HIP kernels (hip_ops.gru): same constructor, parameter names and initial draws, so state dicts
+    go either way.  `forward(x, h0=None)` takes a batched 3-D x in the layout `batch_first` names and returns (y, h_n).
+    The recurrent weights stay resident in one workgroup's registers, which bounds hidden_size by 128; packed
+    variable-length sequences are not supported.  Dropout between the layers draws from the project's Philox stream: the
+    distribution is torch's, the mask is not."""
+
+    def __init__(self, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        if self.hidden_size > H.GRU_MAX_HIDDEN:
+            raise ValueError(f"GRU: hidden_size {self.hidden_size} > {H.GRU_MAX_HIDDEN}: the recurrent weights no longer "
+                             "fit one workgroup's registers")
+
+    def flatten_parameters(self):
+        """Nothing to do: the kernels read every parameter where it lies (torch's version re-homes them for MIOpen)."""
+
+    def forward(self, x, h0=None):
+        if isinstance(x, nn.utils.rnn.PackedSequence):
+            raise ValueError("GRU: PackedSequence input is not supported")
+        if x.dim() != 3:
+            raise L.SeldHipError(f"GRU: expected a batched 3-D input, got {tuple(x.shape)}")
+        dirs = 2 if self.bidirectional else 1
+        names = ("weight_ih", "weight_hh", "bias_ih", "bias_hh")
+        params = [[tuple(getattr(self, f"{n}_l{layer}{sfx}") if self.bias or n.startswith("weight") else None for n in names)
+                   for sfx in ("", "_reverse")[:dirs]] for layer in range(self.num_layers)]
+        if not self.batch_first:
+            x = _swap01(x)
+        y, h_n = H.gru(x, params, self.hidden_size, self.num_layers, dirs, h0, self.dropout, self.training)
+        return (y if self.batch_first else _swap01(y)), h_n

@@ -23,13 +23,14 @@ from .smooth import *           # noqa: F401,F403
 from .squeeze_excite import *   # noqa: F401,F403
 from .temporal_attention import *  # noqa: F401,F403
 from .features import *         # noqa: F401,F403
+from .gru import *              # noqa: F401,F403
 # `import *` skips underscore names: the ones the training harness, the tests and tools/ reach, and the rest of the module surface
 from ._core import _drop_kernel_choice_caches, _pair, _req, _scratch_pools  # noqa: F401
 from .train_ops import _req_inplace, _unit_gradients  # noqa: F401
 from .norm_act import (_claim_grad_slots, _direct_targets, _identity_cache, _nbt, _ncs, _one_pass_ok, _Philox,  # noqa: F401
                        _rowscale, _stats_pool)
 from .conv3d import _conv3d_backward, _conv3d_weights, _triple  # noqa: F401
-from .weight_forms import _hcq_ok, _HcqWeights  # noqa: F401
+from .weight_forms import _GruWeights, _hcq_ok, _HcqWeights  # noqa: F401
 from .streams import _on_side_stream, _side_enabled  # noqa: F401
 from .conv import (_conv_backward, _DeferredWgrads, _hcq_wgrad_label, _hcq_wgrad_ok, _label,  # noqa: F401
                    _pair_ok, _ptr2, _transpose_ahead, _y_shape)

@@ -185,3 +185,49 @@ class _HcqWeights:
 
 hcq_weights = _HcqWeights()
 L._reload_hooks.append(hcq_weights.reset)       # the forms are packed for the kernels the switches selected
+
+
+class _GruWeights:
+    """Packed recurrent weights of the GRU layers (seld_gru_pack: W_hh and W_hh^T of every direction as MFMA fragments, b_hh,
+    zero-padded to a multiple of 16 hidden units), one buffer per layer.  Rebuilt by the rules of the fast-product forms
+    above, whose epoch counter it shares: `hcq_weights.weights_changed()` re-packs at the layer's next request (in a
+    recorded step that request, and so the pack launch, is part of the graph), an in-place edit torch knows about shows in
+    the version counters, a move in the pointers.  Entries hold weak references; dead ones go when a layer registers."""
+
+    class _Entry:
+        __slots__ = ("refs", "buf", "ptrs", "vers", "epoch")
+
+    def __init__(self):
+        self.entries = {}
+
+    def reset(self):
+        self.entries.clear()
+
+    def get(self, hidden, w_hh, b_hh):
+        """The packed buffer for `w_hh` (one (3H, H) tensor per direction) and `b_hh` (one (3H,) tensor per direction, or
+        all None), fresh with respect to the weights as they are when the returned launch order is reached."""
+        dirs = len(w_hh)
+        ts = list(w_hh) + [b for b in b_hh if b is not None]
+        if len(ts) not in (dirs, 2 * dirs) or any(_req(t, "gru weight") is not t for t in ts):
+            raise L.SeldHipError("gru: the recurrent weights must be contiguous, and the biases given for every direction or none")
+        key = tuple(id(t) for t in ts)
+        e = self.entries.get(key)
+        if e is None or any(r() is not t for r, t in zip(e.refs, ts)):
+            for k in [k for k, old in self.entries.items() if any(r() is None for r in old.refs)]:
+                del self.entries[k]
+            e = self._Entry()
+            e.refs = [weakref.ref(t) for t in ts]
+            e.buf = torch.empty(int(L.lib().seld_gru_pack_floats(dirs, hidden)), device=ts[0].device, dtype=torch.float32)
+            e.ptrs = e.vers = None
+            e.epoch = -1
+            self.entries[key] = e
+        ptrs, vers = tuple(t.data_ptr() for t in ts), tuple(t._version for t in ts)
+        if e.ptrs != ptrs or e.vers != vers or e.epoch != hcq_weights.epoch:
+            L.check(L.lib().seld_gru_pack(dirs, hidden, L.ptr(w_hh[0]), L.ptr(w_hh[-1] if dirs == 2 else None),
+                                          L.ptr(b_hh[0]), L.ptr(b_hh[-1] if dirs == 2 else None), L.ptr(e.buf),
+                                          L.current_stream()), "seld_gru_pack")
+            e.ptrs, e.vers, e.epoch = ptrs, vers, hcq_weights.epoch
+        return e.buf
+
+
+gru_weights = _GruWeights()

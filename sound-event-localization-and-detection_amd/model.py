@@ -1,4 +1,4 @@
-"""(Dual-)quaternion SELD-TCN on the gfx950 kernels.
+"""(Dual-)quaternion SELD-TCN, and its recurrent baselines (use_tcn=False), on the gfx950 kernels.
 
 Drop-in for the reference's model.py: same class names, constructor signatures, sub-module names
 (so state dicts / checkpoints are interchangeable), same `forward(x) -> (sed, doa)`.
@@ -36,6 +36,7 @@ SE_MODES = ('cnn', 'tcn', 'both')
 _SE_COMPONENTS = {'Q': 4, 'DQ': 8}
 AT_MASKS = ('none', 'causal', 'band')
 AT_MAX_WIDTH = 64           # hip_ops.AT_MAX_WIDTH
+RNN_MAX_SIZE = 128          # hip_ops.GRU_MAX_HIDDEN
 
 
 def _se_check(se_reduction, se_mode):
@@ -62,6 +63,27 @@ def _at_check(at_key_size, at_value_size, at_mask, at_band):
     if not at_key_size:
         return 0, 0
     return at_key_size, at_value_size or at_key_size
+
+
+def _rnn_check(use_tcn, rnn_size, rnn_layers, pool_time='CNN', se_mode='both', at_key_size=0):
+    """Refuses a recurrent back end (use_tcn=False: bidirectional GRUs in place of the TCN, hip_nn.GRU) that cannot be
+    built; nothing here touches the device.  With use_tcn=True the rnn arguments are not read."""
+    if not isinstance(use_tcn, (bool, int)):
+        raise ValueError(f"use_tcn is True or False, got {use_tcn!r}")
+    if use_tcn:
+        return
+    if isinstance(rnn_size, bool) or not isinstance(rnn_size, int) or not 1 <= rnn_size <= RNN_MAX_SIZE:
+        raise ValueError(f"rnn_size must be an integer in 1..{RNN_MAX_SIZE} (the recurrent weights stay resident in one "
+                         f"workgroup's registers), got {rnn_size!r}")
+    if isinstance(rnn_layers, bool) or not isinstance(rnn_layers, int) or rnn_layers < 1:
+        raise ValueError(f"rnn_layers must be a positive integer, got {rnn_layers!r}")
+    if pool_time != 'CNN':
+        raise ValueError(f"use_tcn=False needs pool_time='CNN' (the time pooling of pool_time={pool_time!r} lives in the "
+                         "TCN's tail), got it with use_tcn=False")
+    if se_mode == 'tcn':
+        raise ValueError("se_mode='tcn' gates the TCN's residual blocks: not with use_tcn=False")
+    if at_key_size:
+        raise ValueError(f"at_key_size {at_key_size!r}: the temporal-attention blocks sit in the TCN: not with use_tcn=False")
 
 
 def _make_se(domain, channels, se_reduction):
@@ -393,10 +415,12 @@ class ConvTC_Block(nn.Module):
                  dilation_mode='fibonacci', G=128, U=128, kernel_size_dilated_conv=3, spatial_dropout_rate=0.5,
                  V=[128, 128], V_kernel_size=3, dropout_perc=0.3, use_bias_conv=True, batch_norm='noBN',
                  attention_type=None, key_size=None, value_size=None, verbose=False, se_reduction=0, se_mode='both',
-                 at_key_size=0, at_value_size=0, at_mask='causal', at_band=0):
+                 at_key_size=0, at_value_size=0, at_mask='causal', at_band=0, use_tcn=True, rnn_size=128, rnn_layers=2):
         super().__init__()
         _se_check(se_reduction, se_mode)
         _at_check(at_key_size, at_value_size, at_mask, at_band)
+        _rnn_check(use_tcn, rnn_size, rnn_layers, pool_time, se_mode, at_key_size)
+        self.use_tcn = bool(use_tcn)
         self.time_dim, self.freq_dim, self.domain, self.verbose = time_dim, freq_dim, domain, verbose
         self.D, self.kernel_size_dilated_conv, self.dilation_mode = D, kernel_size_dilated_conv, dilation_mode
         self.attenyion_type = attention_type          # (sic) attribute name of the reference, model.py:250
@@ -421,6 +445,10 @@ class ConvTC_Block(nn.Module):
             in_chans = c
         self.cnn = nn.Sequential(*stages)
         Lc = int(freq_dim / np.prod(np.array(pool_size), axis=0)[0] * cnn_filters[-1])
+        if not self.use_tcn:
+            # the recurrent back end of SELDnet / QSELDnet: bidirectional GRUs over the pooled frames
+            self.rnn = hnn.GRU(Lc, rnn_size, rnn_layers, batch_first=True, bidirectional=True)
+            return
         self.tcn = TC_Block(in_channels=Lc, domain=domain, G=G, U=U, V=V, V_kernel_size=V_kernel_size,
                             pool_size=pool_size, D=D, spatial_dropout_rate=spatial_dropout_rate,
                             use_bias_conv=use_bias_conv, dilation_mode=dilation_mode, pool_time=pool_time,
@@ -438,6 +466,8 @@ class ConvTC_Block(nn.Module):
         # data-parallel training (dp.BackwardCut): the backward pass can stop here so that the gradients of everything
         # behind this point are exchanged while the front end's backward pass still runs; a no-op otherwise
         x = cut_backward_here(self, x)
+        if not self.use_tcn:
+            return self.rnn(H.transpose12(x))[0]            # (B, T', 2 rnn_size)
         x = self.tcn(x)
         return H.transpose12(x)                             # (B, T', V), model.py:318
 
@@ -452,10 +482,13 @@ class SELD_Model(nn.Module):
                  fc_activations='Linear', fc_dropout='all', dropout_perc=0.3, class_overlaps=3., use_bias_conv=False,
                  use_bias_linear=True, batch_norm='BN', parallel_ConvTC_block='False', parallel_magphase=False,
                  extra_name='', attention_type=None, key_size=None, value_size=None, verbose=False, se_reduction=0,
-                 se_mode='both', at_key_size=0, at_value_size=0, at_mask='causal', at_band=0):
+                 se_mode='both', at_key_size=0, at_value_size=0, at_mask='causal', at_band=0, use_tcn=True, rnn_size=128,
+                 rnn_layers=2):
         super().__init__()
         _se_check(se_reduction, se_mode)
         _at_check(at_key_size, at_value_size, at_mask, at_band)
+        _rnn_check(use_tcn, rnn_size, rnn_layers, pool_time, se_mode, at_key_size)
+        self.use_tcn, self.rnn_size, self.rnn_layers = bool(use_tcn), rnn_size, rnn_layers
         self.input_channels, self.time_dim, self.freq_dim = input_channels, time_dim, freq_dim
         self.domain, self.verbose, self.D = domain, verbose, D
         self.kernel_size_dilated_conv, self.dilation_mode = kernel_size_dilated_conv, dilation_mode
@@ -473,15 +506,17 @@ class SELD_Model(nn.Module):
                         spatial_dropout_rate=spatial_dropout_rate, V=V, V_kernel_size=V_kernel_size,
                         dropout_perc=dropout_perc, use_bias_conv=use_bias_conv, batch_norm=batch_norm, verbose=False,
                         se_reduction=se_reduction, se_mode=se_mode, at_key_size=at_key_size,
-                        at_value_size=at_value_size, at_mask=at_mask, at_band=at_band)
+                        at_value_size=at_value_size, at_mask=at_mask, at_band=at_band, use_tcn=use_tcn, rnn_size=rnn_size,
+                        rnn_layers=rnn_layers)
+        back_end_size = V[-1] if self.use_tcn else 2 * rnn_size
         if parallel_ConvTC_block in _TWO_STREAM:
             self.branch_A = ConvTC_Block(input_channels=input_channels // 2, **block_kw)
             self.branch_B = ConvTC_Block(input_channels=input_channels // 2, **block_kw)
-            fc_input_size = V[-1] * 2
+            fc_input_size = back_end_size * 2
         else:
             self.seld_block = ConvTC_Block(input_channels=input_channels, attention_type=attention_type,
                                            key_size=key_size, value_size=value_size, **block_kw)
-            fc_input_size = V[-1]
+            fc_input_size = back_end_size
 
         sed_layers, doa_layers = [], []
         for width in fc_layers:
@@ -515,19 +550,23 @@ class SELD_Model(nn.Module):
             name = 'DualQ'
         else:
             name = ''
-        name += 'SELD-TCN'
-        if dilation_mode == 'fibonacci':
-            name += '-PHI'
-        name += '-'
-        if len(D) > 1 and D[0] < D[1]:
-            name += 'I'
-        name += 'S' + str(len(D))
+        if not self.use_tcn:
+            name += 'SELDnet-GRU{}x{}'.format(self.rnn_layers, self.rnn_size)
+        else:
+            name += 'SELD-TCN'
+            if dilation_mode == 'fibonacci':
+                name += '-PHI'
+            name += '-'
+            if len(D) > 1 and D[0] < D[1]:
+                name += 'I'
+            name += 'S' + str(len(D))
         if parallel not in {'False', 'false', 'None', 'none'}:
             name += '_' + parallel
         name += '_' + batch_norm
         if pool_time == 'CNN':
             name += '_pooltCNN'
-        name += '_RF{}_{}RB'.format(self.receptive_field, self.total_n_resblocks)
+        if self.use_tcn:
+            name += '_RF{}_{}RB'.format(self.receptive_field, self.total_n_resblocks)
         return name + extra_name
 
     def forward(self, x):

@@ -28,7 +28,7 @@ from .checkpoint import CheckpointRotation, load_model, save_model  # noqa: F401
 from .cli import (_EVAL, _EXTRA, _FLAGS, _NORM_OFF, _NORM_UNIT, FEATURE_LAYOUTS, at_from_args, augment_from_args,  # noqa: F401
                   augment_requested, build_parser, class_report_from_args, ensemble_from_args, ensemble_requested,
                   feature_layout, model_from_args, optimizer_from_args, parse_args, pit_overlaps_from_args,
-                  postprocess_from_args, postprocess_requested, readFile, se_from_args)
+                  postprocess_from_args, postprocess_requested, readFile, rnn_from_args, se_from_args)
 from .data import (_DOMAIN_DQ, ResidentLoader, _normalize_dataset, epoch_left_out, epoch_plan, load_pickled,  # noqa: F401
                    normalize_dataset, polar_stats_from, rank_rows, synthetic_batch)
 from .evaluate import (MEMBER_BUFFER_BYTES, _active_post, _predict_test, _print_test_results, _results_from_table,  # noqa: F401
@@ -94,6 +94,7 @@ def main(args, history=None):
     pit = pit_overlaps_from_args(args)
     se_from_args(args)
     at_from_args(args)
+    rnn_from_args(args)
     extras = optimizer_from_args(args)
     warmup_steps = getattr(args, "warmup_steps", 0)
     if pit > 3:
